@@ -84,7 +84,13 @@ def parse(argv=None):
                          'training iteration); stdout carries only the compact headline line (< 4 KB)')
     ap.add_argument('--plan', action='store_true',
                     help='print the child commands / environment `--gpus N` would start (JSON) and exit; touches no GPU')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the LAST timed step computed (rank 0) as DIR/<name>.npy, '
+                         'float32 / float64, at most 64 MB in all (see dump_outputs)')
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def _shard(n_rows, rank, world):
@@ -398,6 +404,62 @@ def measure_train(enc, dec, store, batch, S, iters, warmup, group=None, world=1,
                                                        'ONE global batch of %d rows split over %d ranks (dp.shard_rows; %d here)'
                                                        % (rows, world, B), S),
                 loss=float(st.loss.detach()))
+
+
+# ------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT = 64 * 10 ** 6   # bytes one --dump-outputs directory receives at most (.npy headers included)
+DUMP_SAMPLE = 1 << 16       # elements kept of an array that does not fit: a fixed, seeded sample
+
+
+def step_outputs(st, shards=None, trained=None):
+    """{name: numpy array} a caller of the timed path receives from one step: the rollout's actions [S,B], logits
+    [S,B,A], step scores [S,B], final hidden / cell state [B,H] and loss; with `trained` = (encoder, decoder,
+    gradient buffer) -- --workload train -- also the gradients and every parameter after the Adam steps.
+    The rollout masks candidate a >= a_num[t, b] with -inf; those slots are written as 0 and `logits_valid` (1 = a real
+    candidate) says which they are, so every file holds finite numbers when the rollout computed finite ones."""
+    import torch
+    parts = shards or [st]
+    logits = torch.cat([s.logits for s in parts], 1)
+    a_num = torch.cat([s.batch.a_num for s in parts], 1)
+    valid = torch.arange(logits.shape[2], device=logits.device) < a_num[..., None]
+    out = dict(actions=torch.cat([s.actions for s in parts], 1), logits=torch.where(valid, logits, 0.0),
+               logits_valid=valid, step_scores=torch.cat([s.step_scores for s in parts], 1),
+               h=torch.cat([s.h for s in parts], 0), c=torch.cat([s.c for s in parts], 0), loss=st.loss_buf)
+    if trained is not None:
+        enc, dec, flat = trained
+        out['grad_flat'] = flat.flat
+        for prefix, m in (('encoder', enc), ('decoder', dec)):
+            for name, p in m.named_parameters():
+                out['%s.%s' % (prefix, name)] = p
+    return {k: v.detach().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT, sample=DUMP_SAMPLE):
+    """Writes {name: array} as out_dir/<name>.npy: integer and boolean arrays as float64 (exact), float64 as it is,
+    every other float as float32.  When the whole set is larger than `limit` bytes, each array of more than `sample`
+    elements is replaced by `sample` of its elements (flattened, ascending index), chosen by a generator seeded with the
+    array's name -- the same elements in every run of the same shapes.  Returns {name: (shape written, sampled)}."""
+    import zlib
+    import numpy as np
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = a.astype(np.float64 if a.dtype.kind in 'biu' or a.dtype == np.float64 else np.float32)
+    sampling = sum(a.nbytes + 256 for a in conv.values()) > limit
+    picked = {}
+    for name, a in conv.items():
+        sampled = sampling and a.size > sample
+        if sampled:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, sample, replace=False))]
+        picked[name] = (a, sampled)
+    total = sum(a.nbytes + 256 for a, _ in picked.values())          # (an .npy header is 128 bytes for these shapes)
+    if total > limit:
+        raise ValueError('--dump-outputs: %d bytes after sampling, more than %d' % (total, limit))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (a, _) in picked.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {name: (a.shape, sampled) for name, (a, sampled) in picked.items()}
 
 
 # --------------------------------------------------------------------------- per-kernel roofline table
@@ -813,6 +875,8 @@ def main(argv=None):
     value = agent_steps / elapsed
     if shard_states is not None:                # outside the timed region: stitch shard results
         graph_state.actions = torch.cat([x.actions for x in shard_states], dim=1)
+    if args.dump_outputs and rank == 0:         # (before any extra runs: what the last timed step left)
+        dump_outputs(args.dump_outputs, step_outputs(st, shard_states, (enc, dec, flat) if train else None))
     extras = not args.no_extras
 
     # ---- extra (not `value`), N > 1: the data-parallel TRAINING iteration (BASELINE configs[3]) on the

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -60,8 +61,18 @@ def _check_headline(d, steps, warmup):
 
 
 def test_bench_prints_one_compact_json_line_with_the_contract_keys(tmp_path):
-    d, full = _run(['--steps', '2', '--warmup', '1', '--n-viewpoints', '96', '--cpu-reps', '1'], tmp_path)
+    dump = tmp_path / 'outputs'
+    d, full = _run(['--steps', '2', '--warmup', '1', '--n-viewpoints', '96', '--cpu-reps', '1',
+                    '--dump-outputs', str(dump)], tmp_path)
     _check_headline(d, 2, 1)
+    # --dump-outputs: what the last timed replay left, float32 / float64 only
+    out = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert sorted(out) == ['actions', 'c', 'h', 'logits', 'logits_valid', 'loss', 'step_scores']
+    assert all(a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)) for a in out.values())
+    assert out['logits_valid'].shape == out['logits'].shape and set(np.unique(out['logits_valid'])) == {0.0, 1.0}
+    assert out['actions'].shape == (20, 100) and out['logits'].shape[:2] == (20, 100) and out['h'].shape == (100, 512)
+    assert np.array_equal(out['actions'], np.round(out['actions']))
+    assert float(out['loss'][0]) == np.float32(full['loss'])
     assert d['extras_file']
     # the full object (side file) carries the per-kernel table and the other configs
     for k in CONTRACT:
