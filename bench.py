@@ -10,8 +10,14 @@ BPTT, the (data-parallel) gradient all-reduce and two Adam updates (train.py:263
     python bench.py --gpus 1 --steps 20 --warmup 5
     python bench.py --gpus 8 ...          # spawns 8 ranks itself (one process per GPU, RCCL)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   # or be launched
+    python bench.py --full ...            # + everything that is not the headline (see --full)
 
 Prints ONE JSON line on rank 0.  value = B * decode_steps * world * K / max-over-ranks time.
+
+A plain run does what the headline needs and nothing more: set-up, warm-up, the timed steps, --dump-outputs, the
+line.  --full measures and checks the rest after the timed steps: the per-kernel roofline, the CPU baseline and the
+parity check against it, the other BASELINE configs, the training iteration, rollouts in flight and, at N > 1, the
+data-parallel training iteration; the full object goes to --extras-out.
 
 Process model: when WORLD_SIZE is not in the environment and --gpus N > 1, this process is only a
 launcher -- it starts N children (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rendezvous on
@@ -55,17 +61,20 @@ def parse(argv=None):
     ap.add_argument('--batch', type=int, default=100)
     ap.add_argument('--decode-steps', type=int, default=20)
     ap.add_argument('--n-viewpoints', type=int, default=10567)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, measure and check everything else too (module docstring); off: the '
+                         'headline alone')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip every measurement that is not `value`, `roofline` or `cpu_baseline`')
-    ap.add_argument('--no-train-extra', action='store_true', help='skip the extra training-iteration measurement')
+                    help='--full: skip every measurement that is not `value`, `roofline` or `cpu_baseline`')
+    ap.add_argument('--no-train-extra', action='store_true', help='--full: skip the extra training-iteration measurement')
     ap.add_argument('--no-graph', action='store_true', help='issue the rollout eagerly instead of replaying a hipGraph')
     ap.add_argument('--row-shards', type=int, default=1,
                     help='rollout only: run the batch as this many concurrent row shards (measured: no gain, '
                          'a half-batch chain is as long as a full one)')
     ap.add_argument('--in-flight', type=int, default=2,
-                    help='extra measurement: this many independent batch-100 rollouts in flight on separate streams')
-    ap.add_argument('--cpu-reps', type=int, default=5, help='timed CPU-port rollouts behind one warm-up (median reported)')
+                    help='--full: extra measurement, this many independent batch-100 rollouts in flight on separate streams')
+    ap.add_argument('--cpu-reps', type=int, default=5, help='--full: timed CPU-port rollouts behind one warm-up (median reported)')
     ap.add_argument('--two-stream-forward', action='store_true', help='(experiment) visual half on a side stream, device-flag ordering')
     # test-only switches: exercise the N > 1 code path (launcher, rendezvous, collectives, JSON) on a
     # box with ONE GPU.  Ranks share cuda:0 and reduce through gloo; the line is marked oversubscribed.
@@ -73,14 +82,14 @@ def parse(argv=None):
     ap.add_argument('--share-gpu', action='store_true', help='(test) every rank uses cuda:0')
     ap.add_argument('--force-collectives', action='store_true',
                     help='(test) --gpus 1 only: initialise the process group (world size 1) and issue every collective of '
-                         'the data-parallel path anyway -- RCCL executes on this GPU; adds `train_dp` to the line')
+                         'the data-parallel path anyway -- RCCL executes on this GPU; with --full adds `train_dp` to the line')
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak',
                     help='weak (default): every rank takes its own batch of --batch rows; strong: ONE global batch of --batch '
                          'rows (the reference\'s batch is 100 globally, train.py:28) split over the ranks with dp.shard_rows')
     ap.add_argument('--extras-budget', type=int, default=240,
-                    help='N > 1: seconds the data-parallel training extra may take before the headline line is printed without it')
+                    help='--full, N > 1: seconds the data-parallel training extra may take before the headline line is printed without it')
     ap.add_argument('--extras-out', default=os.path.join(ROOT, 'bench_extras.json'),
-                    help='file that receives the FULL result object (per-kernel tables, the other BASELINE configs, the '
+                    help='--full: file that receives the FULL result object (per-kernel tables, the other BASELINE configs, the '
                          'training iteration); stdout carries only the compact headline line (< 4 KB)')
     ap.add_argument('--plan', action='store_true',
                     help='print the child commands / environment `--gpus N` would start (JSON) and exit; touches no GPU')
@@ -671,16 +680,16 @@ def headline_of(full, extras_file):
 
 
 def print_result(full, result_out, extras_path):
-    """Write the full object to `extras_path` (best effort) and print the compact headline as ONE line on the
-    original stdout.  NaN / Infinity would make the line invalid JSON: refuse them (allow_nan=False), falling back to a
-    line that says which part was not finite."""
+    """Write the full object to `extras_path` (best effort; None: no side file) and print the compact headline as ONE
+    line on the original stdout.  NaN / Infinity would make the line invalid JSON: refuse them (allow_nan=False),
+    falling back to a line that says which part was not finite."""
     written = None
-    for path in (extras_path, os.path.join(ROOT, 'gpurun_out', 'bench_extras.json')):
+    if extras_path:
         try:
-            if path and os.path.isdir(os.path.dirname(path)):
-                with open(path, 'w') as f:
+            if os.path.isdir(os.path.dirname(os.path.abspath(extras_path))):
+                with open(extras_path, 'w') as f:
                     json.dump(full, f, indent=1, default=str)
-                written = written or os.path.relpath(path, ROOT)
+                written = os.path.relpath(extras_path, ROOT)
         except OSError:
             pass
     def shorten(o):                     # six significant digits are more than any of these measurements carries
@@ -877,6 +886,37 @@ def main(argv=None):
         graph_state.actions = torch.cat([x.actions for x in shard_states], dim=1)
     if args.dump_outputs and rank == 0:         # (before any extra runs: what the last timed step left)
         dump_outputs(args.dump_outputs, step_outputs(st, shard_states, (enc, dec, flat) if train else None))
+    out = dict(metric='agent-steps/sec (follower rollout, batch %d)' % B, value=value,
+               unit='agent-steps/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
+               ms_per_step=1e3 * elapsed / args.steps, higher_is_better=True, scaling=args.scaling,
+               vs_baseline=None, dtype='f32', data='synthetic',
+               config=dict(workload='follower %s: batch %d %s, 36 views x 2048-d features from a '
+                                    '%d-viewpoint HBM table, <=80-token instructions, %d decode steps, '
+                                    'argmax (student-forcing) feedback, every step executed for every row (no early exit), encoder included%s'
+                                    % (args.workload, B, 'GLOBALLY, split over the ranks' if strong else 'per GPU',
+                                       args.n_viewpoints, S,
+                                       ', batch run as %d concurrent row shards' % args.row_shards
+                                       if shard_states else ''),
+                           global_batch=B if strong else B * world, parallelism='dp%d' % world),
+               launch=('hipGraph replay, %d concurrent row shards' % args.row_shards if shard_states
+                       else 'hipGraph replay') if replay else 'eager')
+    if args.share_gpu:
+        out['oversubscribed'] = 'TEST RUN: %d ranks share one GPU, %s collectives' % (world, args.backend)
+    if not args.full:
+        # the headline alone, with the fault words of the launches it timed: a starved persistent launch would have
+        # poisoned a rollout with NaN (0 = healthy) and the measurement would not stand
+        from speaker_follower_amd import runtime as _rt
+        faults = _rt.take_fault(device)
+        if rank == 0:
+            out['persistent_launch_faults'] = faults
+            print_result(out, result_out, None)
+        if coll:
+            torch.distributed.destroy_process_group()
+        if faults:
+            sys.stderr.write('bench.py: persistent-launch faults were raised on rank %d (see persistent_launch_faults)\n'
+                             % rank)
+            sys.exit(3)
+        return
     extras = not args.no_extras
 
     # ---- extra (not `value`), N > 1: the data-parallel TRAINING iteration (BASELINE configs[3]) on the
@@ -885,11 +925,7 @@ def main(argv=None):
     # The headline is measured; what follows at N > 1 issues collectives from every rank.  If that part raises on one
     # rank or hangs (a rank lost, a collective that never completes), the line with the headline is still printed: a
     # watchdog on every rank gives the extras a budget, then rank 0 prints the line it has and every rank leaves.
-    headline = dict(metric='agent-steps/sec (follower rollout, batch %d)' % B, value=value, unit='agent-steps/s',
-                    n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=1e3 * elapsed / args.steps,
-                    higher_is_better=True, scaling=args.scaling, vs_baseline=None, dtype='f32', data='synthetic',
-                    config=dict(workload='follower rollout: batch %d per GPU, %d decode steps, encoder included'
-                                         % (B, S)))
+    headline = dict(out)
     watchdog = None
     if world > 1:
         import threading
@@ -1027,23 +1063,7 @@ def main(argv=None):
                'traffic_offline_pmc: HBM bytes per launch from committed rocprofv3 --pmc passes '
                '(profiles/pmc_traffic.json), NOT measured in this run' % n_prof)
 
-    out = dict(metric='agent-steps/sec (follower rollout, batch %d)' % B, value=value,
-               unit='agent-steps/s', n_gpus=world, steps=args.steps, warmup=args.warmup,
-               ms_per_step=1e3 * elapsed / args.steps, higher_is_better=True, scaling=args.scaling,
-               vs_baseline=None, dtype='f32', data='synthetic',
-               config=dict(workload='follower %s: batch %d %s, 36 views x 2048-d features from a '
-                                    '%d-viewpoint HBM table, <=80-token instructions, %d decode steps, '
-                                    'argmax (student-forcing) feedback, every step executed for every row (no early exit), encoder included%s'
-                                    % (args.workload, B, 'GLOBALLY, split over the ranks' if strong else 'per GPU',
-                                       args.n_viewpoints, S,
-                                       ', batch run as %d concurrent row shards' % args.row_shards
-                                       if shard_states else ''),
-                           global_batch=B if strong else B * world, parallelism='dp%d' % world),
-               roofline=roofline, concurrent=concurrent, loss=float(st.loss_buf),
-               launch=('hipGraph replay, %d concurrent row shards' % args.row_shards if shard_states
-                       else 'hipGraph replay') if replay else 'eager')
-    if args.share_gpu:
-        out['oversubscribed'] = 'TEST RUN: %d ranks share one GPU, %s collectives' % (world, args.backend)
+    out.update(roofline=roofline, concurrent=concurrent, loss=float(st.loss_buf))
     if train_dp is not None:
         out['train_dp'] = train_dp
 

@@ -70,3 +70,20 @@ def test_a_hostile_object_still_prints_a_valid_line(tmp_path):
     assert d['roofline']['kernel'] == 'some_kernel<1, 2>'
     assert d['roofline']['traffic'] is None or isinstance(d['roofline']['traffic'], (int, float))
     assert len(d['config']['workload']) <= 260
+
+
+def test_a_plain_run_prints_the_headline_and_writes_no_side_file(tmp_path, monkeypatch):
+    bench = _bench()
+    assert bench.parse([]).full is False and bench.parse(['--full']).full is True
+    full = json.load(open(os.path.join(ROOT, 'profiles', 'r06_zzz_bench_default_extras.json')))
+    plain = {k: full[k] for k in CONTRACT[:13] + ('launch', 'persistent_launch_faults')}
+    monkeypatch.chdir(tmp_path)
+    buf = io.StringIO()
+    bench.print_result(plain, buf, None)
+    assert os.listdir(tmp_path) == []
+    text = buf.getvalue()
+    assert text.endswith('\n') and text.count('\n') == 1
+    d = json.loads(text)
+    assert sorted(d) == sorted(list(plain) + ['extras_file']) and d['extras_file'] is None
+    for k in ('value', 'ms_per_step'):
+        assert abs(d[k] - full[k]) <= 1e-5 * full[k], k

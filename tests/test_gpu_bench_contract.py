@@ -1,5 +1,6 @@
 """GPU: the driver contract of bench.py -- ONE compact JSON line (< 4 KB, strict JSON) with the required keys,
-the full object in the extras file beside it -- on a reduced table, and once as the DEFAULT command the driver runs."""
+the full object in the extras file beside it -- with --full on a reduced table and at the default sizes, and the plain
+default command, which prints the headline alone."""
 import json
 import os
 import subprocess
@@ -26,7 +27,7 @@ def _run(argv, tmp_path):
     def no_constants(name):
         raise AssertionError('non-finite constant %s in the line' % name)
     d = json.loads(lines[0], parse_constant=no_constants)
-    return d, json.load(open(extras))
+    return d, json.load(open(extras)) if os.path.exists(extras) else None
 
 
 def _check_headline(d, steps, warmup):
@@ -62,7 +63,7 @@ def _check_headline(d, steps, warmup):
 
 def test_bench_prints_one_compact_json_line_with_the_contract_keys(tmp_path):
     dump = tmp_path / 'outputs'
-    d, full = _run(['--steps', '2', '--warmup', '1', '--n-viewpoints', '96', '--cpu-reps', '1',
+    d, full = _run(['--full', '--steps', '2', '--warmup', '1', '--n-viewpoints', '96', '--cpu-reps', '1',
                     '--dump-outputs', str(dump)], tmp_path)
     _check_headline(d, 2, 1)
     # --dump-outputs: what the last timed replay left, float32 / float64 only
@@ -92,8 +93,31 @@ def test_bench_prints_one_compact_json_line_with_the_contract_keys(tmp_path):
 
 
 def test_the_default_command_fits_one_driver_line(tmp_path):
-    """`python bench.py` exactly as the driver runs it (full 10 567-viewpoint table, every extra)."""
-    d, full = _run([], tmp_path)
+    """`python bench.py --full` at the default sizes (full 10 567-viewpoint table, every extra)."""
+    d, full = _run(['--full'], tmp_path)
     _check_headline(d, 20, 5)
     assert 'train_iteration' in d['extras'] and 'speaker_sweep' in d['extras']
     assert 'real_env_full' in full and 'pragmatic_inference' in full
+
+
+def test_the_plain_default_command_prints_the_headline_alone(tmp_path):
+    """`python bench.py` without --full: the headline of the default workload, the last timed step's outputs, and
+    nothing that is measured or checked after the timed steps -- no roofline, CPU baseline, extras or side file."""
+    dump = tmp_path / 'outputs'
+    d, full = _run(['--dump-outputs', str(dump)], tmp_path)
+    for k in CONTRACT[:13]:
+        assert k in d, k
+    assert d['n_gpus'] == 1 and d['steps'] == 20 and d['warmup'] == 5 and d['higher_is_better'] is True
+    assert d['scaling'] == 'weak' and d['vs_baseline'] is None and d['dtype'] == 'f32'
+    assert d['unit'] == 'agent-steps/s' and d['value'] > 0
+    assert abs(d['value'] - 100 * 20 / (d['ms_per_step'] * 1e-3)) < 1e-3 * d['value']
+    assert d['metric'] == 'agent-steps/sec (follower rollout, batch 100)' and d['launch'] == 'hipGraph replay'
+    assert '10567-viewpoint' in d['config']['workload'] and d['config']['global_batch'] == 100
+    assert d['persistent_launch_faults'] == 0
+    for k in ('roofline', 'cpu_baseline', 'parity_vs_cpu_port', 'extras', 'train_dp'):
+        assert k not in d, k
+    assert full is None and d['extras_file'] is None
+    out = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert sorted(out) == ['actions', 'c', 'h', 'logits', 'logits_valid', 'loss', 'step_scores']
+    assert all(a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)) for a in out.values())
+    assert out['actions'].shape == (20, 100) and out['logits'].shape[:2] == (20, 100) and out['h'].shape == (100, 512)

@@ -203,7 +203,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(tmp_path):
     """The N > 1 code path of bench.py end to end -- self-launch, rendezvous, weak-scaling rollout,
     data-parallel training iteration with the flat gradient all-reduce, one JSON line from rank 0 --
     with both ranks sharing this box's single GPU and gloo standing in for RCCL."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--share-gpu',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--share-gpu', '--full',
                           '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--n-viewpoints', '96',
                           '--batch', '16', '--decode-steps', '5', '--extras-out', str(tmp_path / 'x.json')],
                          capture_output=True, text=True, timeout=900, cwd=ROOT,
@@ -234,7 +234,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(tmp_path):
 
 def test_bench_strong_scaling_two_ranks_on_one_gpu_over_gloo(tmp_path):
     """`--scaling strong`: the headline loop itself over ONE global batch split with dp.shard_rows."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--share-gpu',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--share-gpu', '--full',
                           '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--n-viewpoints', '96',
                           '--batch', '18', '--decode-steps', '5', '--scaling', 'strong', '--no-cpu-baseline',
                           '--extras-out', str(tmp_path / 'x.json')],

@@ -42,7 +42,7 @@ def test_rccl_one_rank_training_iteration_is_bit_identical_to_no_collectives():
 
 
 def test_bench_force_collectives_reports_train_dp(tmp_path):
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--backend', 'nccl', '--force-collectives',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--backend', 'nccl', '--force-collectives', '--full',
            '--steps', '3', '--warmup', '2', '--n-viewpoints', '512', '--no-extras', '--no-cpu-baseline',
            '--extras-out', str(tmp_path / 'x.json')]
     res = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=900)

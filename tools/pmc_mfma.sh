@@ -1,5 +1,5 @@
 #!/bin/bash
-# On the GPU box: matrix-core counters of every kernel of the headline rollout (bench.py --no-extras) and of the
+# On an MI355X: matrix-core counters of every kernel of the headline rollout (bench.py --full --no-extras) and of the
 # training iteration (--workload train), per dispatch.  One SQ pass + GRBM (MI355X_MICROARCH.md: 8 SQ slots, GRBM
 # independent); --kernel-trace only beside --pmc, the program directly after `--`.
 cd /tmp && export TMPDIR=/tmp
@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_mfma
 rm -rf $O && mkdir -p $O
 pass() { # name workload counters...
   n=$1; w=$2; shift; shift
-  timeout 900 rocprofv3 --kernel-trace --pmc "$@" -d $O/$n -- python3 $R/bench.py --no-extras --no-cpu-baseline --workload $w --steps 5 --warmup 2 > $O/$n.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --pmc "$@" -d $O/$n -- python3 $R/bench.py --full --no-extras --no-cpu-baseline --workload $w --steps 5 --warmup 2 > $O/$n.log 2>&1
   f=$(find $O/$n -name "*.db" | head -1)
   if [ -n "$f" ]; then python3 $R/tools/rocpd_pmc.py $f sf:: > $O/$n.txt 2>&1; fi
   rm -rf $O/$n
