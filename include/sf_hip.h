@@ -548,6 +548,34 @@ int sf_encoder_lstm_bwd(const sf_encoder_w* w, const sf_encoder_g* g, int B, int
                         const sf_dropout* drop, uint32_t drop_stream, void* ws, size_t ws_bytes,
                         sf_stream stream);
 
+/* ---- bidirectional EncoderLSTM (model.py:47-66, 81-104 with bidirectional=True; train.py:197-199) -----------------
+ * H = hidden units PER DIRECTION (hidden_size // 2).  fwd / rev: the two directions' weights (weight_ih_l0 ... and
+ * weight_ih_l0_reverse ...; their w_e2d fields are ignored), each with its own xw_table; w_e2d / b_e2d [2H,2H],[2H]
+ * (w_e2d_t optional) = encoder2decoder.  seq [B,Lpad] in the given token order for both directions: the reverse one reads
+ * position lengths[b] - 1 - t at its step t.  Writes
+ *   ctx [B,T,2H] = dropout([forward output | reverse output]) (site drop_stream; the mask is keyed on row b and column
+ *     t * 2H + j, i.e. it is the mask of sf_dropout_copy over the assembled [B, T * 2H] rows), zero beyond each length;
+ *   decoder_init [B,2H] = tanh(encoder2decoder([h_reverse ; h_forward])), c_t [B,2H] = [c_reverse ; c_forward].
+ * tape_f / tape_r: each direction's sf_encoder_tape (as for sf_encoder_lstm_fwd, in that direction's step order).
+ * With both xw_tables, H == 256, B <= 128, T <= 128, >= 256 CUs and no SF_ENC_PER_STEP in fwd->flags, both recurrences
+ * run as ONE persistent launch (16 workgroups per row group and direction); otherwise the entry composes the per-step
+ * kernels of sf_encoder_lstm_fwd itself.  path (optional, host): set to 1 when the persistent launch ran, 0 otherwise. */
+int sf_encoder_bilstm_fwd(const sf_encoder_w* fwd, const sf_encoder_w* rev, const float* w_e2d, const float* b_e2d,
+                          const float* w_e2d_t, int B, int Lpad, int T, int E, int H, const int64_t* seq,
+                          const int32_t* lengths, float* ctx, float* decoder_init, float* c_t,
+                          const sf_encoder_tape* tape_f, const sf_encoder_tape* tape_r, const sf_dropout* drop,
+                          uint32_t drop_stream, int32_t* path, void* ws, size_t ws_bytes, sf_stream stream);
+/* dctx [B,T,2H] (gradient wrt the dropped ctx), d_init, d_ct [B,2H] in (NULL = zero); accumulates into g_fwd / g_rev (their
+ * w_e2d / b_e2d fields are ignored; embedding gradients: give seq in the FORWARD token order in both -- the entry reverses
+ * it for the reverse direction) and g_w_e2d / g_b_e2d (NULL = not needed).  Same persistent condition as the forward
+ * (the launch of enc_bwd_persist_kernel for both directions), no embedding gradient; path as there. */
+int sf_encoder_bilstm_bwd(const sf_encoder_w* fwd, const sf_encoder_w* rev, const float* w_e2d, const float* w_e2d_t,
+                          const sf_encoder_g* g_fwd, const sf_encoder_g* g_rev, float* g_w_e2d, float* g_b_e2d, int B,
+                          int T, int E, int H, const int32_t* lengths, const float* decoder_init, const float* dctx,
+                          const float* d_init, const float* d_ct, const sf_encoder_tape* tape_f,
+                          const sf_encoder_tape* tape_r, const sf_dropout* drop, uint32_t drop_stream, int32_t* path,
+                          void* ws, size_t ws_bytes, sf_stream stream);
+
 /* ---- batched feature gathers (env.py:380-383, 771-774, 60-75; follower.py:291-320) ------------
  * Materialise the dense tensors the reference builds on the host, from the HBM table. */
 int sf_gather_panorama(const sf_pano* X, int B, float* out /* [B,V,F] */, sf_stream stream);

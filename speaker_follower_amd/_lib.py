@@ -233,6 +233,12 @@ _SIGNATURES = {
                                       c_f, P(EncoderTape), P(Dropout), u32] + WS),
     'sf_encoder_lstm_bwd': (C.c_int, [P(EncoderW), P(EncoderG), i32, i32, i32, i32, c_p, c_f, c_f,
                                       c_f, c_f, P(EncoderTape), P(Dropout), u32] + WS),
+    'sf_encoder_bilstm_fwd': (C.c_int, [P(EncoderW), P(EncoderW), c_f, c_f, c_f, i32, i32, i32, i32, i32, i64p, c_p,
+                                        c_f, c_f, c_f, P(EncoderTape), P(EncoderTape), P(Dropout), u32,
+                                        P(C.c_int32)] + WS),
+    'sf_encoder_bilstm_bwd': (C.c_int, [P(EncoderW), P(EncoderW), c_f, c_f, P(EncoderG), P(EncoderG), c_f, c_f, i32,
+                                        i32, i32, i32, c_p, c_f, c_f, c_f, c_f, P(EncoderTape), P(EncoderTape),
+                                        P(Dropout), u32, P(C.c_int32)] + WS),
     'sf_gather_panorama': (C.c_int, [P(Pano), i32, c_f, c_p]),
     'sf_gather_candidates': (C.c_int, [P(Cands), i32, c_f, c_f, c_p]),
     'sf_gather_actions': (C.c_int, [P(Cands), i32, c_p, c_f, c_p]),

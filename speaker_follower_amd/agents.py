@@ -534,7 +534,9 @@ class Seq2SeqAgent(BaseAgent):
         # (a process group: iterations replay as SEGMENTS cut at the collective points, FollowerEngine._capture_training_dp;
         # that needs the gradient buckets the all-reduces work on)
         dp_ok = (eng.group is None and eng.grad_sync is None) or (eng.group is not None and eng.grad_sync is not None)
-        return (dp_ok and getattr(self.encoder, 'num_directions', 1) == 1
+        # (a bidirectional encoder: single process only -- its data-parallel iteration keeps the eager loop)
+        one_dir = getattr(self.encoder, 'num_directions', 1) == 1
+        return (dp_ok and (one_dir or (eng.group is None and eng.grad_sync is None))
                 and getattr(self.encoder, 'persistent', True))
 
     def _train_on_graph(self, encoder_optimizer, decoder_optimizer, n_iters):

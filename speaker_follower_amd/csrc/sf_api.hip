@@ -1808,6 +1808,173 @@ int sf_encoder_lstm_bwd(const sf_encoder_w* w, const sf_encoder_g* g, int B, int
     return SF_OK;
 }
 
+// ---- a5 bidirectional EncoderLSTM (model.py:47-66, 81-104 with bidirectional=True) -------------------------------
+namespace {
+EncDir enc_dir(const sf_encoder_w* w, const sf_encoder_tape* tp) {
+    return EncDir{w->lstm.w_hh, w->lstm.b_ih, w->lstm.b_hh, w->xw_table, tp->gates, tp->hs, tp->cs, tp->xg};
+}
+bool bi_persistent(const sf_encoder_w* f, const sf_encoder_w* r, int B, int H, int T) {
+    return f->xw_table && r->xw_table && !(f->flags & SF_ENC_PER_STEP) && encoder_bi_persistent_supported(B, H, T);
+}
+// a nested entry-point call on what is left of the arena (the ticket region stays where it is)
+inline size_t nested_bytes(const Arena& a) { return (a.rest_n() + SYNC_WORDS) * 4; }
+}  // namespace
+
+int sf_encoder_bilstm_fwd(const sf_encoder_w* fwd, const sf_encoder_w* rev, const float* w_e2d, const float* b_e2d,
+                          const float* w_e2d_t, int B, int Lpad, int T, int E, int H, const int64_t* seq,
+                          const int32_t* lengths, float* ctx, float* decoder_init, float* c_t,
+                          const sf_encoder_tape* tf, const sf_encoder_tape* tr, const sf_dropout* drop,
+                          uint32_t drop_stream, int32_t* path, void* ws, size_t ws_bytes, sf_stream stream) {
+    SF_ENTER();
+    (void)w_e2d_t;
+    SF_CHECK_ARG(fwd && rev && w_e2d && seq && lengths && ctx && decoder_init && c_t && tf && tr && B > 0 && T > 0 &&
+                 T <= Lpad && E % 4 == 0 && H % 16 == 0 && tf->hs && tf->cs && tr->hs && tr->cs);
+    SF_CHECK_ARG((tf->emb || fwd->xw_table) && (tr->emb || rev->xw_table));
+    if (path) *path = 0;
+    Arena ar = arena(ws, ws_bytes);
+    hipStream_t st = S(stream);
+    const size_t BH = (size_t)B * H;
+    float* h_out = ar.take(2 * BH);                       // [h_reverse ; h_forward]
+    NEED(h_out);
+    if (bi_persistent(fwd, rev, B, H, T) && ar.tickets()) {
+        Arena pa = ar;
+        float* xchg = pa.take(encoder_bi_persistent_xchg_floats(H));
+        int64_t* seq_rev = tr->emb ? reinterpret_cast<int64_t*>(pa.take((size_t)2 * B * Lpad)) : nullptr;
+        if (xchg && (seq_rev || !tr->emb)) {
+            // the embedded tokens of both directions, each in its step order (kept for dW_ih)
+            if (tf->emb) TRY(embedding_tm(fwd->embedding, E, seq, B, Lpad, T, tf->emb, st));
+            if (tr->emb) {
+                TRY(reverse_tokens(seq, Lpad, lengths, B, seq_rev, st));
+                TRY(embedding_tm(rev->embedding, E, seq_rev, B, Lpad, T, tr->emb, st));
+            }
+            TRY(encoder_bi_persistent(enc_dir(fwd, tf), enc_dir(rev, tr), seq, Lpad, lengths, B, H, T, ctx,
+                                      make_dropout(drop, drop_stream), h_out, c_t, xchg, ar.tickets() + PERSIST_TICKET,
+                                      st));
+            if (path) *path = 1;
+            return linear_plain(h_out, 2 * H, w_e2d, 2 * H, b_e2d, B, 2 * H, 2 * H, EPI_TANH, decoder_init, 2 * H,
+                                pa, st);
+        }
+    }
+    // the per-step kernels: each direction through sf_encoder_lstm_fwd (raw state, undropped ctx), then the assembly
+    int64_t* seq_rev = reinterpret_cast<int64_t*>(ar.take((size_t)2 * B * Lpad));
+    float* ctx_f = ar.take((size_t)B * T * H);
+    float* ctx_r = ar.take((size_t)B * T * H);
+    float* st4 = ar.take(4 * BH);                         // raw h_T and c_T of both directions
+    NEED(seq_rev && ctx_f && ctx_r && st4);
+    TRY(reverse_tokens(seq, Lpad, lengths, B, seq_rev, st));
+    sf_encoder_w wf = *fwd, wr = *rev;
+    wf.flags |= SF_ENC_RAW_STATE;
+    wr.flags |= SF_ENC_RAW_STATE | SF_ENC_REVERSED;
+    TRY(sf_encoder_lstm_fwd(&wf, B, Lpad, T, E, H, seq, lengths, ctx_f, st4, st4 + BH, tf, drop, drop_stream,
+                            ar.rest(), nested_bytes(ar), stream));
+    TRY(sf_encoder_lstm_fwd(&wr, B, Lpad, T, E, H, seq_rev, lengths, ctx_r, st4 + 2 * BH, st4 + 3 * BH, tr, drop,
+                            drop_stream, ar.rest(), nested_bytes(ar), stream));
+    TRY(bi_assemble(ctx_f, ctx_r, lengths, B, T, H, make_dropout(drop, drop_stream), ctx, st));
+    TRY(add2(st4 + 2 * BH, H, nullptr, 0, B, H, h_out, 2 * H, st));         // model.py:93-94: [-1] (reverse) first
+    TRY(add2(st4, H, nullptr, 0, B, H, h_out + H, 2 * H, st));
+    TRY(add2(st4 + 3 * BH, H, nullptr, 0, B, H, c_t, 2 * H, st));
+    TRY(add2(st4 + BH, H, nullptr, 0, B, H, c_t + H, 2 * H, st));
+    return linear_plain(h_out, 2 * H, w_e2d, 2 * H, b_e2d, B, 2 * H, 2 * H, EPI_TANH, decoder_init, 2 * H, ar, st);
+}
+
+int sf_encoder_bilstm_bwd(const sf_encoder_w* fwd, const sf_encoder_w* rev, const float* w_e2d, const float* w_e2d_t,
+                          const sf_encoder_g* g_fwd, const sf_encoder_g* g_rev, float* g_w_e2d, float* g_b_e2d, int B,
+                          int T, int E, int H, const int32_t* lengths, const float* decoder_init, const float* dctx,
+                          const float* d_init, const float* d_ct, const sf_encoder_tape* tf,
+                          const sf_encoder_tape* tr, const sf_dropout* drop, uint32_t drop_stream, int32_t* path,
+                          void* ws, size_t ws_bytes, sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(fwd && rev && w_e2d && lengths && decoder_init && tf && tr && B > 0 && T > 0 && E % 4 == 0 &&
+                 H % 16 == 0 && tf->gates && tf->cs && tf->hs && tf->xg && tr->gates && tr->cs && tr->hs && tr->xg);
+    if (path) *path = 0;
+    Arena ar = arena(ws, ws_bytes);
+    hipStream_t st = S(stream);
+    const size_t BH = (size_t)B * H;
+    // through decoder_init = tanh(encoder2decoder([h_r ; h_f])): dh [B,2H] = gradient wrt the raw [h_r ; h_f]
+    float* dh = ar.take(2 * BH);
+    float* dpre = ar.take(2 * BH);
+    NEED(dh && dpre);
+    if (d_init) {
+        TRY(tanh_bwd(decoder_init, 2 * H, d_init, 2 * H, B, 2 * H, dpre, 2 * H, st));
+        TRY(data_grad(dpre, 2 * H, w_e2d, w_e2d_t, B, 2 * H, 2 * H, dh, 2 * H, 0, ar, st));
+        if (g_w_e2d) {
+            TRY(gemm_tn(dpre, 2 * H, tr->hs + T * BH, H, B, 2 * H, H, g_w_e2d, 2 * H, 1, st, ar.rest(), ar.rest_n()));
+            TRY(gemm_tn(dpre, 2 * H, tf->hs + T * BH, H, B, 2 * H, H, g_w_e2d + H, 2 * H, 1, st, ar.rest(), ar.rest_n()));
+        }
+        if (g_b_e2d) TRY(colsum(dpre, 2 * H, B, 2 * H, g_b_e2d, 1, st, nullptr, ar.rest(), ar.rest_n()));
+    }
+    const bool emb_grad = (g_fwd && g_fwd->embedding) || (g_rev && g_rev->embedding);
+    if (bi_persistent(fwd, rev, B, H, T) && !emb_grad && ar.tickets()) {
+        Arena pa = ar;
+        float* xchg = pa.take(encoder_bi_bwd_persistent_xchg_floats());
+        if (xchg) {
+            TRY(encoder_bi_bwd_persistent(enc_dir(fwd, tf), enc_dir(rev, tr), lengths, B, H, T, dctx,
+                                          make_dropout(drop, drop_stream), d_init ? dh : nullptr, d_ct, xchg,
+                                          ar.tickets() + PERSIST_TICKET, st));
+            if (path) *path = 1;
+            // the weight gradients of both directions (dgates in tape->xg): one grouped sequence of many-row products
+            TnJob jobs[4];
+            int nj = 0;
+            const sf_encoder_g* gs[2] = {g_fwd, g_rev};
+            const sf_encoder_tape* ts[2] = {tf, tr};
+            for (int d = 0; d < 2; ++d) {
+                if (!gs[d]) continue;
+                if (gs[d]->lstm.w_hh) jobs[nj++] = TnJob{ts[d]->xg, 4 * H, ts[d]->hs, H, T * B, 4 * H, H, gs[d]->lstm.w_hh, H, 1};
+                if (gs[d]->lstm.w_ih) {
+                    SF_CHECK_ARG(ts[d]->emb);
+                    jobs[nj++] = TnJob{ts[d]->xg, 4 * H, ts[d]->emb, E, T * B, 4 * H, E, gs[d]->lstm.w_ih, E, 1};
+                }
+            }
+            if (nj) TRY(gemm_tn_group(jobs, nj, st, pa.rest(), pa.rest_n()));
+            for (int d = 0; d < 2; ++d)
+                if (gs[d]) TRY(colsum_pair(ts[d]->xg, 4 * H, T * B, 4 * H, gs[d]->lstm.b_ih, gs[d]->lstm.b_hh, pa, st));
+            return SF_OK;
+        }
+    }
+    // the per-step kernels: the assembled gradients taken apart, each direction through sf_encoder_lstm_bwd (raw state)
+    float* dctx_f = ar.take((size_t)B * T * H);
+    float* dctx_r = ar.take((size_t)B * T * H);
+    float* halves = ar.take(4 * BH);                      // dh_f, dh_r, dc_f, dc_r
+    int64_t* seq_rev = reinterpret_cast<int64_t*>(ar.take((size_t)2 * B * T));
+    NEED(dctx_f && dctx_r && halves && seq_rev);
+    if (dctx) TRY(bi_split(dctx, lengths, B, T, H, make_dropout(drop, drop_stream), dctx_f, dctx_r, st));
+    else {
+        TRY(fill(dctx_f, (size_t)B * T * H, 0.f, st));
+        TRY(fill(dctx_r, (size_t)B * T * H, 0.f, st));
+    }
+    if (d_init) {
+        TRY(add2(dh + H, 2 * H, nullptr, 0, B, H, halves, H, st));
+        TRY(add2(dh, 2 * H, nullptr, 0, B, H, halves + BH, H, st));
+    }
+    if (d_ct) {
+        TRY(add2(d_ct + H, 2 * H, nullptr, 0, B, H, halves + 2 * BH, H, st));
+        TRY(add2(d_ct, 2 * H, nullptr, 0, B, H, halves + 3 * BH, H, st));
+    }
+    sf_encoder_w wf = *fwd, wr = *rev;
+    wf.flags |= SF_ENC_RAW_STATE;
+    wr.flags |= SF_ENC_RAW_STATE | SF_ENC_REVERSED;
+    sf_encoder_g gf{}, gr{};
+    if (g_fwd) gf = *g_fwd;
+    if (g_rev) gr = *g_rev;
+    gf.w_e2d = gf.b_e2d = gr.w_e2d = gr.b_e2d = nullptr;
+    if (gr.embedding) {                                   // the reverse direction's tokens in its step order
+        SF_CHECK_ARG(gr.seq && gr.Lpad >= T);
+        Arena sa = ar;
+        int64_t* sr = reinterpret_cast<int64_t*>(sa.take((size_t)2 * B * gr.Lpad));
+        NEED(sr);
+        TRY(reverse_tokens(gr.seq, gr.Lpad, lengths, B, sr, st));
+        gr.seq = sr;
+        ar = sa;
+    }
+    TRY(sf_encoder_lstm_bwd(&wf, g_fwd ? &gf : nullptr, B, T, E, H, lengths, decoder_init, dctx_f,
+                            d_init ? halves : nullptr, d_ct ? halves + 2 * BH : nullptr, tf, drop, drop_stream,
+                            ar.rest(), nested_bytes(ar), stream));
+    TRY(sf_encoder_lstm_bwd(&wr, g_rev ? &gr : nullptr, B, T, E, H, lengths, decoder_init, dctx_r,
+                            d_init ? halves + BH : nullptr, d_ct ? halves + 3 * BH : nullptr, tr, drop, drop_stream,
+                            ar.rest(), nested_bytes(ar), stream));
+    return SF_OK;
+}
+
 // ---- a11 gathers ---------------------------------------------------------------------------------------
 int sf_gather_panorama(const sf_pano* X, int B, float* out, sf_stream stream) {
     SF_ENTER();

@@ -95,6 +95,25 @@ int encoder_bwd_persistent(const float* w_hh, const int* lengths, int B, int H, 
                            // dc0_out [B,H] = gradient wrt a given initial cell state; lengths may be null
                            long dctx_sb = 0, long dctx_st = 0, float* dc0_out = nullptr);
 
+// Both directions of a bidirectional encoder (H = 256 per direction) as one launch (enc_persist_kernel<2>): per
+// direction its weights, [vocab,4H] table and tapes (hs / cs slot 0 zeroed here); ctx [B,T,2H] assembled and dropped
+// (mask keyed on column t * 2H + j, as a dropout over the assembled rows), h_out / c_out [B,2H] = [reverse ; forward].
+// xchg: scratch of encoder_bi_persistent_xchg_floats floats.  The backward (enc_bwd_persist_kernel<2>) reads the
+// assembled dctx [B,T,2H], dh_in / dc_in [B,2H] and writes each direction's dgates [T,B,4H].
+struct EncDir {
+    const float *w_hh, *b_ih, *b_hh, *xw_table;
+    float *gates, *hs, *cs, *dgates;
+};
+size_t encoder_bi_persistent_xchg_floats(int H);
+size_t encoder_bi_bwd_persistent_xchg_floats();
+bool encoder_bi_persistent_supported(int B, int H, int T);
+int encoder_bi_persistent(const EncDir& f, const EncDir& r, const int64_t* seq, int Lpad, const int* lengths, int B,
+                          int H, int T, float* ctx, const Dropout& ctx_drop, float* h_out, float* c_out, float* xchg,
+                          unsigned* done, hipStream_t st);
+int encoder_bi_bwd_persistent(const EncDir& f, const EncDir& r, const int* lengths, int B, int H, int T,
+                              const float* dctx, const Dropout& ctx_drop, const float* dh_in, const float* dc_in,
+                              float* xchg, unsigned* done, hipStream_t st);
+
 int lstm_pointwise_bwd(const LstmPwBwd& a, hipStream_t st);
 
 int dropout_copy(const float* src, int lds, int B, int N, float* dst, int ldd, const Dropout& d,
@@ -160,6 +179,13 @@ int gather_actions(const CandSrc& s, int B, const int* a, float* out, hipStream_
 int gather_path_actions(const float* table, int V, int IMG, int LOC, const int* vp, const int* act_view,
                         const float* sincos, const int* act, int N, float* out, int ldo, hipStream_t st);
 
+// bidirectional encoder on the per-step kernels: tokens in per-row reversed order, [forward | reverse] assembly of ctx
+// (+ dropout) and its transpose (sf_pointwise.hip)
+int reverse_tokens(const int64_t* seq, int Lpad, const int* lengths, int B, int64_t* out, hipStream_t st);
+int bi_assemble(const float* ctx_f, const float* ctx_r, const int* lengths, int B, int T, int H, const Dropout& d,
+                float* out, hipStream_t st);
+int bi_split(const float* dctx, const int* lengths, int B, int T, int H, const Dropout& d, float* dctx_f,
+             float* dctx_r, hipStream_t st);
 int gather_rows(const float* src, int lds, const int* idx, int n, int w, float* dst, int ldd,
                 hipStream_t st);
 int scatter_rows(const float* src, int lds, const int* idx, int n, int w, float* dst, int ldd,

@@ -61,15 +61,16 @@ __device__ __forceinline__ void raise_fault(unsigned* fault, unsigned code) {
 // Per-launch placement record of one row group: [0] arrivals, [1] min XCC id, [2] max XCC id
 // (initialised by the prologue kernel).  EP_PLACE_WORDS dwords per group.
 constexpr int EP_PLACE_WORDS = 4;
-__device__ __forceinline__ void place_init(unsigned* place, size_t i, int force_sc1) {
-    if (i < (size_t)EP_GROUPS * EP_PLACE_WORDS)
+__device__ __forceinline__ void place_init(unsigned* place, size_t i, int force_sc1, int n_rec = EP_GROUPS) {
+    if (i < (size_t)n_rec * EP_PLACE_WORDS)
         place[i] = (i % EP_PLACE_WORDS) == 1 ? 0xFFFFFFFFu : ((i % EP_PLACE_WORDS) == 3 && force_sc1 ? 1u : 0u);
 }
-// True iff all EP_SLOTS workgroups of `grp` run on ONE XCD (read from the hardware id register, agreed
+// True iff all `nslots` workgroups of exchange partition `grp` (a row group, or a (row group, direction) pair of the
+// two-direction encoder) run on ONE XCD (read from the hardware id register, agreed
 // on through agent-scope atomics once per launch).  Then their exchange can stay inside that XCD's
 // L2: plain stores (L1 is write-through, the line stays in L2) + L1-bypassing loads -- no write-through
 // to the fabric.  Any doubt (timeout, mixed ids) => false => the placement-independent sc1 protocol.
-__device__ __forceinline__ bool group_on_one_xcd(unsigned* place, int grp) {
+__device__ __forceinline__ bool group_on_one_xcd(unsigned* place, int grp, int nslots = EP_SLOTS) {
     __shared__ int s_fast;
     if (threadIdx.x == 0) {
         unsigned* p = place + grp * EP_PLACE_WORDS;
@@ -80,7 +81,7 @@ __device__ __forceinline__ bool group_on_one_xcd(unsigned* place, int grp) {
         atomicAdd(p, 1u);
         const long long t0 = wall_clock64();
         bool all = false;
-        while (!(all = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)EP_SLOTS)) {
+        while (!(all = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)nslots)) {
             __builtin_amdgcn_s_sleep(2);
             if (wall_clock64() - t0 > 2000) break;                         // 20 us: decide without the others
         }
@@ -104,15 +105,21 @@ __device__ __forceinline__ void take_persist_lock(unsigned* fault, long long tim
     }
 }
 
+// (h0b / c0b: the reverse direction's slot 0 of the two-direction launch, or null; n_rec placement records)
 __global__ __launch_bounds__(256) void enc_persist_prologue_kernel(unsigned* xchg, size_t n_xchg, float* h0,
                                                                    float* c0, size_t n_state, unsigned* place,
-                                                                   int force_sc1, unsigned* fault, long long timeout) {
+                                                                   int force_sc1, unsigned* fault, long long timeout,
+                                                                   float* h0b, float* c0b, int n_rec) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    place_init(place, (size_t)blockIdx.x * blockDim.x + threadIdx.x, force_sc1);
+    place_init(place, (size_t)blockIdx.x * blockDim.x + threadIdx.x, force_sc1, n_rec);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_xchg; i += stride) xchg[i] = EP_SENTINEL;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_state; i += stride) {
         h0[i] = 0.f;                       // model.py:67-79 init_state
         c0[i] = 0.f;
+        if (h0b) {
+            h0b[i] = 0.f;
+            c0b[i] = 0.f;
+        }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) take_persist_lock(fault, timeout < 0 ? EP_TIMEOUT_TICKS : timeout);
 }
@@ -142,35 +149,66 @@ struct EncPersistArgs {
     unsigned* place;                                           // placement record (group_on_one_xcd)
     unsigned* fault; long long timeout;                        // fault word, wait bound (ticks)
     unsigned long long* trace;                                 // sf_debug_trace: [blocks][8] tick sums, or null
+    // the REVERSE direction of the two-direction launch (enc_persist_kernel<2>): its weights, table and tapes; h_out
+    // [B,2H] = [h_reverse ; h_forward] (c_out likewise)
+    const float* w_hh_r; const float* b_ih_r; const float* b_hh_r; const float* xw_table_r;
+    float* gates_r; float* hs_r; float* cs_r;
+    float* h_out;
 };
 
+// NDIR = 1: the unidirectional encoder (H = 512, 32 workgroups per row group).  NDIR = 2: both directions of a
+// bidirectional one (H = 256 per direction) on the same 256-workgroup grid -- workgroup (group, q) runs direction
+// q / 16 with hidden units [16 (q % 16), +16); every (group, direction) pair is an exchange partition of its own
+// (16 workgroups, a K = 256 slice of W_hh each).  The reverse direction's step t of row b is position len_b - 1 - t:
+// it reads that token and writes ctx[b, len_b - 1 - t, H:2H], so no reversed copy of the tokens or of ctx is formed.
+template <int NDIR>
 __global__ __launch_bounds__(256, 1) void enc_persist_kernel(EncPersistArgs p) {
-    __shared__ float s_red[2][8][4][256];               // paired K-slice partials R_k of the 4 gates, double
+    constexpr int SLOTS = EP_SLOTS / NDIR;              // workgroups per exchange partition
+    constexpr int NJ = 4 / NDIR;                        // K-slices of 32 per wave
+    constexpr int NH2 = NJ / 2;
+    constexpr int NPART = 4 * NH2;                      // paired K-slice partials per gate
+    __shared__ float s_red[2][NPART][4][256];           // paired K-slice partials R_k of the 4 gates, double
                                                         // buffered by step parity: ONE barrier per step
     __shared__ int s_tok[EP_ROWS][EP_TMAX];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int li = lane & 15, kk = lane >> 4;
-    const int grp = blockIdx.x & (EP_GROUPS - 1), slot = blockIdx.x >> 3;
+    const int grp = blockIdx.x & (EP_GROUPS - 1);
+    const int dir = NDIR == 1 ? 0 : (int)(blockIdx.x >> 3) / SLOTS;
+    const int slot = NDIR == 1 ? (int)(blockIdx.x >> 3) : (int)(blockIdx.x >> 3) % SLOTS;
     const int H = p.H, T = p.T, B = p.B;
     const int row0 = grp * p.rpg;
     const int nrows = max(0, min(p.rpg, B - row0));
+    const float* w_hh = dir ? p.w_hh_r : p.w_hh;
+    const float* b_ih = dir ? p.b_ih_r : p.b_ih;
+    const float* b_hh = dir ? p.b_hh_r : p.b_hh;
+    const float* xw_table = dir ? p.xw_table_r : p.xw_table;
+    float* gates = dir ? p.gates_r : p.gates;
+    float* hs = dir ? p.hs_r : p.hs;
+    float* cs = dir ? p.cs_r : p.cs;
 
     // ---- resident operands --------------------------------------------------------------------
-    // wave w: K-slices sj = {w, w+8 | w+4, w+12} (32 k each = chunks 2s, 2s+1), all four gates
-    const int sj[4] = {w, w + 8, w + 4, w + 12};
+    // wave w: K-slices sj = {w, w+8 | w+4, w+12} (32 k each = chunks 2s, 2s+1), all four gates; K = 256: {w, w+4}
+    int sj[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) sj[j] = w + (j & 1) * (8 / NDIR) + (j >> 1) * 4;
     // (lane (li, kk) holds, of K-slice sj, k = 32 sj + 4 kk + {0..3} and 32 sj + 16 + 4 kk + {0..3}: the K order inside
     // an MFMA is free as long as A and B agree, and this one is what the 16-byte exchange loads deliver)
-    Split8 wq[4][4];
+    Split8 wq[4][NJ];
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float* wp = p.w_hh + (size_t)(g * H + 16 * slot + li) * H + 32 * sj[j] + 4 * kk;
+        for (int j = 0; j < NJ; ++j) {
+            const float* wp = w_hh + (size_t)(g * H + 16 * slot + li) * H + 32 * sj[j] + 4 * kk;
             wq[g][j] = split3_f8(ld4(wp), ld4(wp + 16));
         }
     for (int i = tid; i < EP_ROWS * T; i += 256) {
         const int r = i / T, t = i - r * T;
-        s_tok[r][t] = r < nrows ? (int)p.seq[(size_t)(row0 + r) * p.seq_sb + (size_t)t * p.seq_st] : 0;
+        int pos = t;                                     // reverse direction: position len - 1 - t of a live step
+        if (NDIR == 2 && dir && r < nrows) {
+            const int len = p.lengths ? min(p.lengths[row0 + r], T) : T;
+            if (t < len) pos = len - 1 - t;
+        }
+        s_tok[r][t] = r < nrows ? (int)p.seq[(size_t)(row0 + r) * p.seq_sb + (size_t)pos * p.seq_st] : 0;
     }
     // the (row, unit) this thread updates; rows beyond the group's share compute on row B-1's
     // operands (clamped, as the per-step kernel does) and store nothing
@@ -180,27 +218,28 @@ __global__ __launch_bounds__(256, 1) void enc_persist_kernel(EncPersistArgs p) {
     const int ej = 16 * slot + eu;
     float bias[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) bias[g] = p.b_ih[g * H + ej] + p.b_hh[g * H + ej];
-    const int len_b = p.lengths ? p.lengths[eb] : T;
+    for (int g = 0; g < 4; ++g) bias[g] = b_ih[g * H + ej] + b_hh[g * H + ej];
+    int len_b = p.lengths ? p.lengths[eb] : T;
+    if (NDIR == 2) len_b = min(len_b, T);                // (the reverse direction indexes by it: never past T)
     const uint32_t rk = drop_key(p.ctx_drop, (uint32_t)(p.ctx_drop.row0 + eb));
     float c_state = p.c_init ? p.c_init[(size_t)eb * H + ej] : 0.f;
     float h_state = p.h_init ? p.h_init[(size_t)eb * H + ej] : 0.f;
     const size_t BH = (size_t)B * H;
 
-    unsigned* xg = p.xchg + (size_t)grp * 3 * EP_ROWS * H;
+    unsigned* xg = p.xchg + (size_t)(grp * NDIR + dir) * 3 * EP_ROWS * H;
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(xg, 0, 3 * EP_ROWS * H * 4, 0x00020000);
     // packed 16-byte access of this workgroup's own [16 x 16] patch: thread with (tid & 3) == 0
     // covers units eu .. eu+3 of row er
     const unsigned patch_off = (unsigned)((er * H + ej) * 4);
     bool dead = false;
-    const bool local = group_on_one_xcd(p.place, grp);
+    const bool local = group_on_one_xcd(p.place, grp * NDIR + dir, SLOTS);
 
     __syncthreads();
     float xv[4];
     {
         const int tok = s_tok[er][0];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) xv[g] = p.xw_table[(size_t)tok * 4 * H + g * H + ej];
+        for (int g = 0; g < 4; ++g) xv[g] = xw_table[(size_t)tok * 4 * H + g * H + ej];
     }
 
     long long tk[5] = {0, 0, 0, 0, 0}, tprev = wall_clock64();    // development aid (p.trace)
@@ -214,13 +253,13 @@ __global__ __launch_bounds__(256, 1) void enc_persist_kernel(EncPersistArgs p) {
         EP_STAMP(4)                                      // tapes + loop back
         float xn[4] = {0.f, 0.f, 0.f, 0.f};
         if (t > 0 || p.h_init) {                         // h_0 = 0 (no initial state given): the first step has no product
-            v4u a[4][2];
+            v4u a[NJ][2];
             const unsigned base = (unsigned)((((t % 3) * EP_ROWS + li) * H) * 4);
             const long long t0 = wall_clock64();
             if (t == 0) {                                // the given initial state: an input, read where it lies
                 const float* hrow = p.h_init + (size_t)min(row0 + li, B - 1) * H;
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
+                for (int j = 0; j < NJ; ++j)
 #pragma unroll
                     for (int cc = 0; cc < 2; ++cc) {
                         const float4 x = ld4(hrow + 16 * (2 * sj[j] + cc) + 4 * kk);
@@ -231,13 +270,13 @@ __global__ __launch_bounds__(256, 1) void enc_persist_kernel(EncPersistArgs p) {
                 asm volatile("" ::: "memory");           // the loads below are re-issued every pass
                 bool ok = true;
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
+                for (int j = 0; j < NJ; ++j)
 #pragma unroll
                     for (int cc = 0; cc < 2; ++cc)
                         a[j][cc] = __builtin_amdgcn_raw_buffer_load_b128(
                             rs, base + (unsigned)((16 * (2 * sj[j] + cc) + 4 * kk) * 4), 0, AUX_SC1);
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
+                for (int j = 0; j < NJ; ++j)
 #pragma unroll
                     for (int cc = 0; cc < 2; ++cc)
                         ok = ok && a[j][cc].x != EP_SENTINEL && a[j][cc].y != EP_SENTINEL &&
@@ -254,10 +293,10 @@ __global__ __launch_bounds__(256, 1) void enc_persist_kernel(EncPersistArgs p) {
             if (t + 1 < T) {
                 const int tok = s_tok[er][t + 1];
 #pragma unroll
-                for (int g = 0; g < 4; ++g) xn[g] = p.xw_table[(size_t)tok * 4 * H + g * H + ej];
+                for (int g = 0; g < 4; ++g) xn[g] = xw_table[(size_t)tok * 4 * H + g * H + ej];
             }
 #pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
+            for (int h2 = 0; h2 < NH2; ++h2) {
                 f32x4 hi[2][4], lo[2][4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) hi[0][g] = hi[1][g] = lo[0][g] = lo[1][g] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -286,10 +325,10 @@ __global__ __launch_bounds__(256, 1) void enc_persist_kernel(EncPersistArgs p) {
             if (T > 1) {
                 const int tok = s_tok[er][1];
 #pragma unroll
-                for (int g = 0; g < 4; ++g) xn[g] = p.xw_table[(size_t)tok * 4 * H + g * H + ej];
+                for (int g = 0; g < 4; ++g) xn[g] = xw_table[(size_t)tok * 4 * H + g * H + ej];
             }
 #pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2)
+            for (int h2 = 0; h2 < NH2; ++h2)
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -309,7 +348,7 @@ __global__ __launch_bounds__(256, 1) void enc_persist_kernel(EncPersistArgs p) {
         for (int g = 0; g < 4; ++g) {
             float v = bias[g] + xv[g];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) v += s_red[t & 1][k][g][tid];
+            for (int k = 0; k < NPART; ++k) v += s_red[t & 1][k][g][tid];
             g4[g] = v;
         }
         const float ig = sigmoidf_(g4[0]), fg = sigmoidf_(g4[1]), gg = tanhf(g4[2]), og = sigmoidf_(g4[3]);
@@ -329,19 +368,26 @@ __global__ __launch_bounds__(256, 1) void enc_persist_kernel(EncPersistArgs p) {
         }
         EP_STAMP(2)                                      // reduce + cell + publish
         if (evalid) {
-            if (p.gates) {
-                float* gp = p.gates + ((size_t)t * B + eb) * 4 * H + ej;
+            if (gates) {
+                float* gp = gates + ((size_t)t * B + eb) * 4 * H + ej;
                 gp[0] = ig; gp[H] = fg; gp[2 * H] = gg; gp[3 * H] = og;
             }
+            // ctx position of this output (reverse: len_b - 1 - t; steps beyond the length zero position t) and its
+            // column in the [B, T * NDIR * H] view the dropout mask is keyed on (model.py:101-102)
+            const int pos = (NDIR == 2 && dir && live) ? len_b - 1 - t : t;
+            const int ccol = pos * (NDIR * H) + dir * H + ej;
             float cv = live ? h1 : 0.f;
             if (live && p.ctx_drop.on())
-                cv = dropout_keep(rk, (uint32_t)(t * H + ej), p.ctx_drop.thresh) ? cv * p.ctx_drop.scale : 0.f;
-            if (p.ctx) p.ctx[(size_t)eb * p.ld_ctx + (size_t)t * H + ej] = cv;
-            if (p.gates || t == T - 1) {                 // inference (no gates tape): only the final state
-                p.cs[(size_t)(t + 1) * BH + (size_t)eb * H + ej] = c1;
-                p.hs[(size_t)(t + 1) * BH + (size_t)eb * H + ej] = h1;
+                cv = dropout_keep(rk, (uint32_t)ccol, p.ctx_drop.thresh) ? cv * p.ctx_drop.scale : 0.f;
+            if (p.ctx) p.ctx[(size_t)eb * p.ld_ctx + (size_t)ccol] = cv;
+            if (gates || t == T - 1) {                   // inference (no gates tape): only the final state
+                cs[(size_t)(t + 1) * BH + (size_t)eb * H + ej] = c1;
+                hs[(size_t)(t + 1) * BH + (size_t)eb * H + ej] = h1;
             }
-            if (t == T - 1 && p.c_out) p.c_out[(size_t)eb * H + ej] = c1;
+            // final states [reverse ; forward] (model.py:92-94)
+            const size_t so = (size_t)eb * (NDIR * H) + (size_t)((NDIR - 1 - dir) * H) + ej;
+            if (t == T - 1 && p.c_out) p.c_out[so] = c1;
+            if (NDIR == 2 && t == T - 1 && p.h_out) p.h_out[so] = h1;
         }
         c_state = c1;
         h_state = h1;
@@ -393,29 +439,41 @@ struct EncBwdPersistArgs {
     unsigned* place;
     unsigned* fault; long long timeout;
     unsigned long long* trace;
+    // the REVERSE direction of the two-direction launch (enc_bwd_persist_kernel<2>); dh_in / dc_in are then [B,2H] =
+    // [reverse ; forward] and dctx the assembled [B,T,2H] (its reverse half read at position len_b - 1 - t)
+    const float* w_hh_r; const float* gates_r; const float* cs_r; float* dgates_r;
 };
 constexpr int EB_LDA = 68;                        // LDS row stride of the [16 x 64] dgates tile
 
+template <int NDIR>
 __global__ __launch_bounds__(256, 1) void enc_bwd_persist_kernel(EncBwdPersistArgs p) {
+    constexpr int SLOTS = EP_SLOTS / NDIR;        // workgroups per exchange partition
+    constexpr int NT = 8 / NDIR;                  // n-tiles of 16 units per wave
     __shared__ float sA[2][EP_ROWS][EB_LDA];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int li = lane & 15, kk = lane >> 4;
-    const int grp = blockIdx.x & (EP_GROUPS - 1), slot = blockIdx.x >> 3;
+    const int grp = blockIdx.x & (EP_GROUPS - 1);
+    const int dir = NDIR == 1 ? 0 : (int)(blockIdx.x >> 3) / SLOTS;
+    const int slot = NDIR == 1 ? (int)(blockIdx.x >> 3) : (int)(blockIdx.x >> 3) % SLOTS;
     const int H = p.H, T = p.T, B = p.B;
     const int row0 = grp * p.rpg;
     const int nrows = max(0, min(p.rpg, B - row0));
-    // resident: wave w covers units [128 w, +128) = 8 n-tiles; k = 16 kk + c  <->  gate kk, unit c.  Round 4: held as
-    // three bf16 planes (sf_split.h: the product runs on the bf16 matrix cores at fp32 accuracy); lane (li, kk) holds
-    // units c = 8 s .. 8 s + 7 of gate kk in the operand of MFMA s (K = 64 = 2 x 32)
-    Split8 wq[8][2];
+    const float* w_hh = dir ? p.w_hh_r : p.w_hh;
+    const float* gates = dir ? p.gates_r : p.gates;
+    const float* cs = dir ? p.cs_r : p.cs;
+    float* dgates = dir ? p.dgates_r : p.dgates;
+    // resident: wave w covers units [128 w, +128) = 8 n-tiles (H = 256: [64 w, +64), 4 n-tiles); k = 16 kk + c  <->
+    // gate kk, unit c.  Round 4: held as three bf16 planes (sf_split.h: the product runs on the bf16 matrix cores at
+    // fp32 accuracy); lane (li, kk) holds units c = 8 s .. 8 s + 7 of gate kk in the operand of MFMA s (K = 64 = 2 x 32)
+    Split8 wq[NT][2];
 #pragma unroll
-    for (int nt = 0; nt < 8; ++nt)
+    for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             float v[8];
 #pragma unroll
             for (int c = 0; c < 8; ++c)
-                v[c] = p.w_hh[(size_t)(kk * H + 16 * slot + 8 * s2 + c) * H + 16 * (8 * w + nt) + li];
+                v[c] = w_hh[(size_t)(kk * H + 16 * slot + 8 * s2 + c) * H + 16 * (NT * w + nt) + li];
             wq[nt][s2] = split3_f8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]));
         }
     // this thread's element in the MFMA output layout: index e = (kk*16 + col)*4 + r
@@ -423,26 +481,33 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_persist_kernel(EncBwdPersistAr
     const bool evalid = er < nrows;
     const int eb = evalid ? row0 + er : B - 1;
     const int ej = 16 * slot + eu;
-    const int len_b = p.lengths ? p.lengths[eb] : T;
+    int len_b = p.lengths ? p.lengths[eb] : T;
+    if (NDIR == 2) len_b = min(len_b, T);                // (the reverse direction indexes by it: never past T)
     const uint32_t rk = drop_key(p.ctx_drop, (uint32_t)(p.ctx_drop.row0 + eb));
     const size_t BH = (size_t)B * H;
-    float dc = p.dc_in ? p.dc_in[(size_t)eb * H + ej] : 0.f;
-    float dh_pass = p.dh_in ? p.dh_in[(size_t)eb * H + ej] : 0.f;
+    const size_t so = (size_t)eb * (NDIR * H) + (size_t)((NDIR - 1 - dir) * H) + ej;   // [reverse ; forward] halves
+    float dc = p.dc_in ? p.dc_in[so] : 0.f;
+    float dh_pass = p.dh_in ? p.dh_in[so] : 0.f;
 
-    unsigned* xg = p.xchg + (size_t)grp * 2 * EP_SLOTS * EP_SLOTS * 256;
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(xg, 0, 2 * EP_SLOTS * EP_SLOTS * 256 * 4, 0x00020000);
+    unsigned* xg = p.xchg + (size_t)(grp * NDIR + dir) * 2 * SLOTS * SLOTS * 256;
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc(xg, 0, 2 * SLOTS * SLOTS * 256 * 4, 0x00020000);
     bool dead_wg = false;
-    const bool local = group_on_one_xcd(p.place, grp);
+    const bool local = group_on_one_xcd(p.place, grp * NDIR + dir, SLOTS);
     long long tk[5] = {0, 0, 0, 0, 0}, tprev = wall_clock64();
 
     // operands of step t (activated gates, cell states, dctx), fetched one step ahead
     float g_i, g_f, g_g, g_o, c0v, c1v, dcx;
     auto fetch = [&](int t) {
-        const float* gp = p.gates + ((size_t)t * B + eb) * 4 * H + ej;
+        const float* gp = gates + ((size_t)t * B + eb) * 4 * H + ej;
         g_i = gp[0]; g_f = gp[H]; g_g = gp[2 * H]; g_o = gp[3 * H];
-        c0v = p.cs[(size_t)t * BH + (size_t)eb * H + ej];
-        c1v = p.cs[(size_t)(t + 1) * BH + (size_t)eb * H + ej];
-        dcx = p.dctx ? p.dctx[(size_t)eb * p.dctx_sb + (size_t)t * p.dctx_st + ej] : 0.f;
+        c0v = cs[(size_t)t * BH + (size_t)eb * H + ej];
+        c1v = cs[(size_t)(t + 1) * BH + (size_t)eb * H + ej];
+        if (NDIR == 1)
+            dcx = p.dctx ? p.dctx[(size_t)eb * p.dctx_sb + (size_t)t * p.dctx_st + ej] : 0.f;
+        else if (dir)                             // reverse: position len_b - 1 - t; a step beyond the length has none
+            dcx = (p.dctx && t < len_b) ? p.dctx[(size_t)eb * p.dctx_sb + (size_t)(len_b - 1 - t) * p.dctx_st + H + ej] : 0.f;
+        else
+            dcx = p.dctx ? p.dctx[(size_t)eb * p.dctx_sb + (size_t)t * p.dctx_st + ej] : 0.f;
     };
     fetch(T - 1);
 
@@ -451,17 +516,17 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_persist_kernel(EncBwdPersistAr
         float dh = dh_pass;
         if (t < T - 1) {
             // ---- 1. gather the 32 partials of dgates_{t+1} W_hh for this patch
-            unsigned v[EP_SLOTS];
-            const unsigned base = (unsigned)(((((t + 1) & 1) * EP_SLOTS + slot) * EP_SLOTS) * 256 + tid) * 4u;
+            unsigned v[SLOTS];
+            const unsigned base = (unsigned)(((((t + 1) & 1) * SLOTS + slot) * SLOTS) * 256 + tid) * 4u;
             const long long t0 = wall_clock64();
             for (;;) {
                 asm volatile("" ::: "memory");
                 bool ok = true;
 #pragma unroll
-                for (int c = 0; c < EP_SLOTS; ++c)
+                for (int c = 0; c < SLOTS; ++c)
                     v[c] = __builtin_amdgcn_raw_buffer_load_b32(rs, base + (unsigned)(c * 256 * 4), 0, AUX_SC1);
 #pragma unroll
-                for (int c = 0; c < EP_SLOTS; ++c) ok = ok && v[c] != EP_SENTINEL;
+                for (int c = 0; c < SLOTS; ++c) ok = ok && v[c] != EP_SENTINEL;
                 if (__all(ok) || dead_wg) break;
                 if (wall_clock64() - t0 >= p.timeout) {
                     dead_wg = true;
@@ -471,13 +536,15 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_persist_kernel(EncBwdPersistAr
             }
             EP_STAMP(0)                                  // waiting for the partials
 #pragma unroll
-            for (int c = 0; c < EP_SLOTS; ++c) dh += __uint_as_float(v[c]);
+            for (int c = 0; c < SLOTS; ++c) dh += __uint_as_float(v[c]);
         }
         // ---- 2. cell backward of step t (lstm_bwd_step_fused_kernel's arithmetic)
         {
             float vctx = dcx;
+            // (the forward's mask: column pos * NDIR * H + dir * H + j of the [B, T * NDIR * H] context)
+            const int pos = (NDIR == 2 && dir && t < len_b) ? len_b - 1 - t : t;
             if (p.dctx && p.ctx_drop.on())
-                vctx = dropout_keep(rk, (uint32_t)(t * H + ej), p.ctx_drop.thresh) ? vctx * p.ctx_drop.scale : 0.f;
+                vctx = dropout_keep(rk, (uint32_t)(pos * (NDIR * H) + dir * H + ej), p.ctx_drop.thresh) ? vctx * p.ctx_drop.scale : 0.f;
             dh += vctx;
         }
         if (dead_wg) dh = __uint_as_float(0x7FC00000u);
@@ -495,20 +562,20 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_persist_kernel(EncBwdPersistAr
         const float z = evalid ? 1.f : 0.f;              // rows beyond the group's share contribute nothing
         sa[eu] = dgi * z; sa[16 + eu] = dgf * z; sa[32 + eu] = dgg * z; sa[48 + eu] = dgo * z;
         if (evalid) {
-            float* dg = p.dgates + ((size_t)t * B + eb) * 4 * H + ej;
+            float* dg = dgates + ((size_t)t * B + eb) * 4 * H + ej;
             dg[0] = dgi; dg[H] = dgf; dg[2 * H] = dgg; dg[3 * H] = dgo;
         }
         __syncthreads();                                 // tile complete; every wave has finished its gather
         if (t < T - 1) {                                 // the region just read becomes the region of step t-1
-            const unsigned rb = (unsigned)(((((t + 1) & 1) * EP_SLOTS + slot) * EP_SLOTS) * 256) * 4u;
+            const unsigned rb = (unsigned)(((((t + 1) & 1) * SLOTS + slot) * SLOTS) * 256) * 4u;
 #pragma unroll
-            for (int i = 0; i < 8; ++i)
+            for (int i = 0; i < SLOTS / 4; ++i)
                 xstore(local, v4u{EP_SENTINEL, EP_SENTINEL, EP_SENTINEL, EP_SENTINEL}, rs,
                        rb + (unsigned)((tid + 256 * i) * 16));
         }
         EP_STAMP(1)                                      // cell backward + tile + barrier + reset issue
         if (t == 0) {                                    // nothing to publish (the caller forms d h_init = dgates_0 W_hh)
-            if (p.dc0_out && evalid) p.dc0_out[(size_t)eb * H + ej] = dc;
+            if (NDIR == 1 && p.dc0_out && evalid) p.dc0_out[(size_t)eb * H + ej] = dc;
             break;
         }
         fetch(t - 1);
@@ -522,27 +589,27 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_persist_kernel(EncBwdPersistAr
                 a[4 * q] = x.x; a[4 * q + 1] = x.y; a[4 * q + 2] = x.z; a[4 * q + 3] = x.w;
             }
         }
-        f32x4 acc[8];
+        f32x4 acc[NT];
         {
             const Split8 a0 = split3_f8(make_float4(a[0], a[1], a[2], a[3]), make_float4(a[4], a[5], a[6], a[7]));
             const Split8 a1 = split3_f8(make_float4(a[8], a[9], a[10], a[11]), make_float4(a[12], a[13], a[14], a[15]));
-            f32x4 hi[8], lo[8];
+            f32x4 hi[NT], lo[NT];
 #pragma unroll
-            for (int nt = 0; nt < 8; ++nt) hi[nt] = lo[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            mfma_split6_across<8>(a0, [&](int nt) -> const Split8& { return wq[nt][0]; }, hi, lo);
-            mfma_split6_across<8>(a1, [&](int nt) -> const Split8& { return wq[nt][1]; }, hi, lo);
+            for (int nt = 0; nt < NT; ++nt) hi[nt] = lo[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            mfma_split6_across<NT>(a0, [&](int nt) -> const Split8& { return wq[nt][0]; }, hi, lo);
+            mfma_split6_across<NT>(a1, [&](int nt) -> const Split8& { return wq[nt][1]; }, hi, lo);
 #pragma unroll
-            for (int nt = 0; nt < 8; ++nt) acc[nt] = hi[nt] + lo[nt];
+            for (int nt = 0; nt < NT; ++nt) acc[nt] = hi[nt] + lo[nt];
         }
         // ---- 4. publish: block (dest = 8 w + nt, src = slot), lane's four rows contiguous
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the resets above are behind us
-        const unsigned pb = (unsigned)((t & 1) * EP_SLOTS * EP_SLOTS * 256) * 4u;
+        const unsigned pb = (unsigned)((t & 1) * SLOTS * SLOTS * 256) * 4u;
         EP_STAMP(2)                                      // MFMAs + drain
 #pragma unroll
-        for (int nt = 0; nt < 8; ++nt)
+        for (int nt = 0; nt < NT; ++nt)
             xstore(local, v4u{__float_as_uint(acc[nt][0]), __float_as_uint(acc[nt][1]), __float_as_uint(acc[nt][2]),
                               __float_as_uint(acc[nt][3])},
-                   rs, pb + (unsigned)((((8 * w + nt) * EP_SLOTS + slot) * 256 + (kk * 16 + li) * 4) * 4));
+                   rs, pb + (unsigned)((((NT * w + nt) * SLOTS + slot) * 256 + (kk * 16 + li) * 4) * 4));
         EP_STAMP(3)                                      // publish issue
     }
     if (p.trace && lane == 0 && w == 0) {
@@ -562,9 +629,10 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_persist_kernel(EncBwdPersistAr
 
 // sentinel fill + device-wide lock of the backward launch (no state to zero)
 __global__ __launch_bounds__(256) void enc_bwd_persist_prologue_kernel(unsigned* xchg, size_t n_xchg, unsigned* place,
-                                                                       int force_sc1, unsigned* fault, long long timeout) {
+                                                                       int force_sc1, unsigned* fault, long long timeout,
+                                                                       int n_rec) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    place_init(place, (size_t)blockIdx.x * blockDim.x + threadIdx.x, force_sc1);
+    place_init(place, (size_t)blockIdx.x * blockDim.x + threadIdx.x, force_sc1, n_rec);
     v4u* x4 = reinterpret_cast<v4u*>(xchg);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_xchg / 4; i += stride)
         x4[i] = v4u{EP_SENTINEL, EP_SENTINEL, EP_SENTINEL, EP_SENTINEL};
@@ -1116,8 +1184,63 @@ int encoder_persistent(const float* w_hh, const float* b_ih, const float* b_hh, 
     a.fault = done + EP_FAULT_WORD; a.timeout = g_persist_timeout < 0 ? EP_TIMEOUT_TICKS : g_persist_timeout;
     // (slot 0 of the tapes: zeroed here, or -- given an initial state -- the caller's)
     SF_LAUNCH(enc_persist_prologue_kernel, dim3(96), dim3(256), 0, st, a.xchg, encoder_persistent_xchg_floats(H),
-              hs, cs, h_init ? (size_t)0 : (size_t)B * H, a.place, g_force_sc1, a.fault, g_persist_timeout);
-    SF_LAUNCH(enc_persist_kernel, dim3(EP_GROUPS * EP_SLOTS), dim3(256), 0, st, a);
+              hs, cs, h_init ? (size_t)0 : (size_t)B * H, a.place, g_force_sc1, a.fault, g_persist_timeout,
+              (float*)nullptr, (float*)nullptr, EP_GROUPS);
+    SF_LAUNCH_AS("enc_persist_kernel", enc_persist_kernel<1>, dim3(EP_GROUPS * EP_SLOTS), dim3(256), 0, st, a);
+    return launch_status();
+}
+
+// ---- both directions of a bidirectional encoder (H = 256 per direction) as one launch each way ----------------------
+// The placement records of the 16 (group, direction) partitions do not fit beside the ticket word: they follow the
+// exchange buffers in the caller's scratch.
+constexpr int EP_BI_REC = 2 * EP_GROUPS;
+size_t encoder_bi_persistent_xchg_floats(int H) { return (size_t)EP_GROUPS * 2 * 3 * EP_ROWS * H + EP_BI_REC * EP_PLACE_WORDS; }
+size_t encoder_bi_bwd_persistent_xchg_floats() {
+    return (size_t)EP_GROUPS * 2 * 2 * (EP_SLOTS / 2) * (EP_SLOTS / 2) * 256 + EP_BI_REC * EP_PLACE_WORDS;
+}
+
+bool encoder_bi_persistent_supported(int B, int H, int T) {
+    return H == 16 * (EP_SLOTS / 2) && B >= 1 && B <= EP_GROUPS * EP_ROWS && T >= 1 && T <= EP_TMAX &&
+           device_cus() >= EP_GROUPS * EP_SLOTS;
+}
+
+int encoder_bi_persistent(const EncDir& f, const EncDir& r, const int64_t* seq, int Lpad, const int* lengths, int B,
+                          int H, int T, float* ctx, const Dropout& ctx_drop, float* h_out, float* c_out, float* xchg,
+                          unsigned* done, hipStream_t st) {
+    if (!encoder_bi_persistent_supported(B, H, T) || !f.xw_table || !r.xw_table || !lengths || !xchg || !done)
+        return SF_ERR_UNSUPPORTED;
+    EncPersistArgs a{};
+    a.w_hh = f.w_hh; a.b_ih = f.b_ih; a.b_hh = f.b_hh; a.xw_table = f.xw_table;
+    a.w_hh_r = r.w_hh; a.b_ih_r = r.b_ih; a.b_hh_r = r.b_hh; a.xw_table_r = r.xw_table;
+    a.seq = seq; a.seq_sb = Lpad; a.seq_st = 1; a.lengths = lengths; a.B = B; a.H = H; a.T = T;
+    a.rpg = ceil_div(B, EP_GROUPS);
+    a.gates = f.gates; a.hs = f.hs; a.cs = f.cs; a.gates_r = r.gates; a.hs_r = r.hs; a.cs_r = r.cs;
+    a.ctx = ctx; a.ld_ctx = T * 2 * H; a.ctx_drop = ctx_drop; a.c_out = c_out; a.h_out = h_out;
+    const size_t n_xchg = (size_t)EP_GROUPS * 2 * 3 * EP_ROWS * H;
+    a.xchg = reinterpret_cast<unsigned*>(xchg); a.done = done; a.place = a.xchg + n_xchg; a.trace = g_trace;
+    a.fault = done + EP_FAULT_WORD; a.timeout = g_persist_timeout < 0 ? EP_TIMEOUT_TICKS : g_persist_timeout;
+    SF_LAUNCH(enc_persist_prologue_kernel, dim3(96), dim3(256), 0, st, a.xchg, n_xchg, f.hs, f.cs, (size_t)B * H,
+              a.place, g_force_sc1, a.fault, g_persist_timeout, r.hs, r.cs, EP_BI_REC);
+    SF_LAUNCH_AS("enc_persist_kernel<bidir>", enc_persist_kernel<2>, dim3(EP_GROUPS * EP_SLOTS), dim3(256), 0, st, a);
+    return launch_status();
+}
+
+int encoder_bi_bwd_persistent(const EncDir& f, const EncDir& r, const int* lengths, int B, int H, int T,
+                              const float* dctx, const Dropout& ctx_drop, const float* dh_in, const float* dc_in,
+                              float* xchg, unsigned* done, hipStream_t st) {
+    if (!encoder_bi_persistent_supported(B, H, T) || !lengths || !xchg || !done) return SF_ERR_UNSUPPORTED;
+    EncBwdPersistArgs a{};
+    a.w_hh = f.w_hh; a.gates = f.gates; a.cs = f.cs; a.dgates = f.dgates;
+    a.w_hh_r = r.w_hh; a.gates_r = r.gates; a.cs_r = r.cs; a.dgates_r = r.dgates;
+    a.lengths = lengths; a.B = B; a.H = H; a.T = T; a.rpg = ceil_div(B, EP_GROUPS);
+    a.dctx = dctx; a.ctx_drop = ctx_drop; a.dctx_sb = (long)T * 2 * H; a.dctx_st = 2 * H;
+    a.dh_in = dh_in; a.dc_in = dc_in; a.dc0_out = nullptr;
+    const size_t n_xchg = (size_t)EP_GROUPS * 2 * 2 * (EP_SLOTS / 2) * (EP_SLOTS / 2) * 256;
+    a.xchg = reinterpret_cast<unsigned*>(xchg); a.done = done; a.place = a.xchg + n_xchg; a.trace = g_trace;
+    a.fault = done + EP_FAULT_WORD; a.timeout = g_persist_timeout < 0 ? EP_TIMEOUT_TICKS : g_persist_timeout;
+    SF_LAUNCH(enc_bwd_persist_prologue_kernel, dim3(512), dim3(256), 0, st, a.xchg, n_xchg, a.place, g_force_sc1,
+              a.fault, g_persist_timeout, EP_BI_REC);
+    SF_LAUNCH_AS("enc_bwd_persist_kernel<bidir>", enc_bwd_persist_kernel<2>, dim3(EP_GROUPS * EP_SLOTS), dim3(256), 0, st, a);
     return launch_status();
 }
 
@@ -1148,7 +1271,7 @@ int speaker_persistent(const float* w_hh, const float* b_ih, const float* b_hh, 
     a.sample_site = sample && sample->stream_dev ? sample->stream_dev : site_zero();
     if (sample) { a.sample_seed = sample->seed; a.sample_stream = sample->stream; a.sample_row0 = sample->row0; }
     SF_LAUNCH(enc_bwd_persist_prologue_kernel, dim3(256), dim3(256), 0, st, a.xchg, speaker_persistent_xchg_floats(),
-              a.place, g_force_sc1, a.fault, g_persist_timeout);
+              a.place, g_force_sc1, a.fault, g_persist_timeout, EP_GROUPS);
     if (feedback == 2)
         SF_LAUNCH_AS("spk_persist_kernel<sample>", spk_persist_kernel<true>, dim3(EP_GROUPS * EP_SLOTS), dim3(256), 0, st, a);
     else
@@ -1170,8 +1293,8 @@ int encoder_bwd_persistent(const float* w_hh, const int* lengths, int B, int H, 
     a.dgates = dgates; a.xchg = reinterpret_cast<unsigned*>(xchg); a.done = done; a.place = done + 4; a.trace = g_trace;
     a.fault = done + EP_FAULT_WORD; a.timeout = g_persist_timeout < 0 ? EP_TIMEOUT_TICKS : g_persist_timeout;
     SF_LAUNCH(enc_bwd_persist_prologue_kernel, dim3(512), dim3(256), 0, st, a.xchg, encoder_bwd_persistent_xchg_floats(),
-              a.place, g_force_sc1, a.fault, g_persist_timeout);
-    SF_LAUNCH(enc_bwd_persist_kernel, dim3(EP_GROUPS * EP_SLOTS), dim3(256), 0, st, a);
+              a.place, g_force_sc1, a.fault, g_persist_timeout, EP_GROUPS);
+    SF_LAUNCH_AS("enc_bwd_persist_kernel", enc_bwd_persist_kernel<1>, dim3(EP_GROUPS * EP_SLOTS), dim3(256), 0, st, a);
     return launch_status();
 }
 

@@ -1090,6 +1090,70 @@ int gather_path_actions(const float* table, int V, int IMG, int LOC, const int* 
               LOC, vp, act_view, sincos, act, N, out, ldo);
     return launch_status();
 }
+// ---- bidirectional encoder on the per-step kernels (sf_encoder_bilstm_fwd / _bwd when the two-direction launch does
+// not apply): the reverse direction runs over every row's tokens in reversed order, and its outputs are put back ----
+// out[b, t] = seq[b, len_b - 1 - t] for t < len_b, seq[b, t] beyond (model.py:88: what pack_padded_sequence feeds the
+// reverse direction)
+__global__ __launch_bounds__(TPB) void reverse_tokens_kernel(const int64_t* seq, int Lpad, const int* lengths, int B,
+                                                             int64_t* out) {
+    const size_t n = (size_t)B * Lpad;
+    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (size_t)gridDim.x * TPB) {
+        const int b = (int)(i / Lpad), t = (int)(i % Lpad), len = lengths[b];
+        out[i] = seq[(size_t)b * Lpad + (t < len ? len - 1 - t : t)];
+    }
+}
+// ctx[b, t] = dropout([ctx_f[b, t] | ctx_r[b, len_b - 1 - t]]), zeros beyond the length (model.py:92-102); the mask is
+// keyed on (row b, column t * 2H + j) like a dropout over the assembled [B, T * 2H] rows
+__global__ __launch_bounds__(TPB) void bi_assemble_kernel(const float* ctx_f, const float* ctx_r, const int* lengths,
+                                                          int B, int T, int H, Dropout d, float* out) {
+    const size_t n = (size_t)B * T * 2 * H;
+    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (size_t)gridDim.x * TPB) {
+        const int c = (int)(i % (2 * H)), t = (int)((i / (2 * H)) % T), b = (int)(i / ((size_t)2 * H * T));
+        const int len = lengths[b];
+        float v = c < H ? ctx_f[((size_t)b * T + t) * H + c]
+                        : (t < len ? ctx_r[((size_t)b * T + (len - 1 - t)) * H + (c - H)] : 0.f);
+        if (d.on()) v = dropout_keep(drop_key(d, (uint32_t)(d.row0 + b)), (uint32_t)(t * 2 * H + c), d.thresh) ? v * d.scale : 0.f;
+        out[i] = v;
+    }
+}
+// the transposed movement: dctx [B,T,2H] (gradient wrt the dropped ctx) -> the two directions' [B,T,H] gradients, the
+// reverse one in its step order, both through the mask
+__global__ __launch_bounds__(TPB) void bi_split_kernel(const float* dctx, const int* lengths, int B, int T, int H,
+                                                       Dropout d, float* dctx_f, float* dctx_r) {
+    const size_t n = (size_t)B * T * 2 * H;
+    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (size_t)gridDim.x * TPB) {
+        const int c = (int)(i % (2 * H)), s = (int)((i / (2 * H)) % T), b = (int)(i / ((size_t)2 * H * T));
+        const int len = lengths[b];
+        int t = s;                                        // source position
+        if (c >= H) {
+            if (s >= len) {
+                dctx_r[((size_t)b * T + s) * H + (c - H)] = 0.f;
+                continue;
+            }
+            t = len - 1 - s;
+        }
+        float v = dctx[((size_t)b * T + t) * 2 * H + c];
+        if (d.on()) v = dropout_keep(drop_key(d, (uint32_t)(d.row0 + b)), (uint32_t)(t * 2 * H + c), d.thresh) ? v * d.scale : 0.f;
+        if (c < H) dctx_f[((size_t)b * T + s) * H + c] = v;
+        else dctx_r[((size_t)b * T + s) * H + (c - H)] = v;
+    }
+}
+int reverse_tokens(const int64_t* seq, int Lpad, const int* lengths, int B, int64_t* out, hipStream_t st) {
+    SF_LAUNCH(reverse_tokens_kernel, dim3(grid1d((size_t)B * Lpad)), dim3(TPB), 0, st, seq, Lpad, lengths, B, out);
+    return launch_status();
+}
+int bi_assemble(const float* ctx_f, const float* ctx_r, const int* lengths, int B, int T, int H, const Dropout& d,
+                float* out, hipStream_t st) {
+    SF_LAUNCH(bi_assemble_kernel, dim3(grid1d((size_t)B * T * 2 * H)), dim3(TPB), 0, st, ctx_f, ctx_r, lengths, B, T, H,
+              d, out);
+    return launch_status();
+}
+int bi_split(const float* dctx, const int* lengths, int B, int T, int H, const Dropout& d, float* dctx_f,
+             float* dctx_r, hipStream_t st) {
+    SF_LAUNCH(bi_split_kernel, dim3(grid1d((size_t)B * T * 2 * H)), dim3(TPB), 0, st, dctx, lengths, B, T, H, d,
+              dctx_f, dctx_r);
+    return launch_status();
+}
 int gather_rows(const float* src, int lds, const int* idx, int n, int w, float* dst, int ldd,
                 hipStream_t st) {
     if ((w & 3) || (lds & 3) || (ldd & 3)) return SF_ERR_UNSUPPORTED;

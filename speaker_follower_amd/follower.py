@@ -21,8 +21,8 @@ from . import _lib
 from ._lib import call
 from .features import cand_sincos
 from .model import (decoder_params, decoder_w_struct, decoder_fold, _encoder_structs, _TAPE_KEYS,
-                    grad_ptr, trainable_embedding)
-from .runtime import ptr, stream, ws_args, wgrad_ws_args, ensure_workspace, dropout_arg, fill_regions, take_fault, PersistentLaunchFault, concurrent_stream, graph_capture, WeightsMoved
+                    grad_ptr, trainable_embedding, bi_encoder_tapes, bi_encoder_fwd, bi_encoder_bwd)
+from .runtime import ptr, stream, ws_args, wgrad_ws_args, ensure_workspace, dropout_arg, fill_regions, take_fault, PersistentLaunchFault, concurrent_stream, graph_capture, WeightsMoved, transposed
 from .dp import collectives_on
 
 byref = C.byref
@@ -230,7 +230,7 @@ class FollowerEngine:
         # (an inference rollout keeps no embedded tokens / gate tape: nothing will run backward)
         keep = training or (torch.is_grad_enabled() and any(
             p.requires_grad for p in list(enc.parameters()) + list(dec.parameters())))
-        st.enc_tape = {} if bidir else \
+        st.enc_tape = bi_encoder_tapes(B, T, E, H // 2, dev, keep) if bidir else \
             dict(emb=new(T, B, E) if keep else None, xg=new(T, B, 4 * H) if keep else None,
                  gates=new(T, B, 4 * H) if keep else None, hs=new(T + 1, B, H), cs=new(T + 1, B, H))
         etp = None if bidir else _lib.EncoderTape(*(st.enc_tape[k].data_ptr() if st.enc_tape[k] is not None else None
@@ -238,19 +238,14 @@ class FollowerEngine:
         # a trainable (non-GloVe) embedding with a backward to follow: the input product is formed from the embedded
         # (train mode: dropped, model.py:86-87) tokens, not read from the cached table
         st.enc_table = not (keep and trainable_embedding(enc))
-        st.enc_graph = None
         if bidir:
-            # the module's composition of the two directions (model.EncoderLSTM._forward_bidirectional); its autograd
-            # graph is the encoder's tape, and _backward() enters it with the decoder's (dctx, dh, dc)
+            # the module's entry (model.EncoderLSTM._forward_bidirectional: sf_encoder_bilstm_fwd) on the engine's fixed
+            # tapes; _backward() calls sf_encoder_bilstm_bwd.  The ctx mask is keyed on (seed + row0 mix, row b) -- the
+            # numbering of the module's dropout over the assembled rows -- and the site is a device word under capture.
             p_e, seed_e, row0 = st.drop_enc[:3]
-            cfg = (p_e, (seed_e + 0x9E3779B1 * row0) & 0xFFFFFFFF, st.site0)
-            with torch.set_grad_enabled(keep and torch.is_grad_enabled()):
-                ctx_e, h_e, c_e = enc._forward_bidirectional(batch.seq, batch.lengths_dev, T, cfg, st.enc_table)
-            st.ctx = ctx_e.detach()
-            st.h_init.copy_(h_e.detach())
-            st.c_init.copy_(c_e.detach())
-            if ctx_e.requires_grad:
-                st.enc_graph = (ctx_e, h_e, c_e)
+            st.drop_enc_bi = (p_e, (seed_e + 0x9E3779B1 * row0) & 0xFFFFFFFF, 0, st.site_dev, 1)
+            bi_encoder_fwd(enc, batch.seq, batch.lengths_dev, T, dropout_arg(*st.drop_enc_bi), st.site_rel,
+                           st.enc_table, st.enc_tape, st.ctx, st.h_init, st.c_init)
         else:
             ew = _encoder_structs(enc, table=st.enc_table)
             call('sf_encoder_lstm_fwd', byref(ew), B, Lpad, T, E, H, ptr(batch.seq),
@@ -330,7 +325,7 @@ class FollowerEngine:
             # and two dependent launches leave every decode step.  Nothing is taped for a backward, hence never for a
             # differentiable or train-mode rollout; one stream only.
             st.text_folded = (self.fold_text and not st.differentiable and not training and fold is None
-                              and ep.side_stream is None and S > 1 and T <= 80 and not bidir)
+                              and ep.side_stream is None and S > 1 and T <= 80)
             if st.text_folded and self.fold_build_overlap:
                 # the two fold products (they need the encoder's context only) on a second stream beside step 0's attention
                 if self._side_stream is None:
@@ -482,7 +477,7 @@ class FollowerEngine:
         if enc.num_directions == 2:
             e2d = enc.encoder2decoder
             ew = b''.join(bytes(_encoder_structs(enc, direction=d)) for d in (0, 1)) + \
-                repr((e2d.weight.data_ptr(), e2d.bias.data_ptr())).encode()
+                repr((e2d.weight.data_ptr(), e2d.bias.data_ptr(), transposed(e2d.weight).data_ptr())).encode()
         else:
             ew = bytes(_encoder_structs(enc))
         dw = decoder_w_struct(decoder_params(self.decoder))
@@ -557,13 +552,15 @@ class FollowerEngine:
 
         Every replay draws fresh dropout masks / samples and takes the next Adam step: sites and step counters are
         device words the graph reads (sf_dropout.site_dev, sf_adam_step_dev), numbered exactly like the eager loop's.
-        Single process only (a gradient all-reduce cannot live in the graph); unidirectional encoder; pre-drawn
-        observations or a device-resident environment (nav.DeviceNavBatch)."""
+        Single process only (a gradient all-reduce cannot live in the graph); pre-drawn observations or a device-resident
+        environment (nav.DeviceNavBatch).  A bidirectional encoder is captured in the single-process form only; the
+        segmented data-parallel capture takes a unidirectional one."""
         from .runtime import TrainingGraph
-        if self.encoder.num_directions == 2:
-            raise NotImplementedError('capture_training: unidirectional encoder only')
         opts = list(optimizers)
         if self.group is not None or self.grad_sync is not None:
+            if self.encoder.num_directions == 2:
+                raise NotImplementedError('capture_training: a data-parallel iteration with a bidirectional encoder '
+                                          'runs eagerly')
             return self._capture_training_dp(batch, steps, feedback, opts, zero)
 
         def body():
@@ -770,8 +767,8 @@ class FollowerEngine:
         elif not overlap:
             self._decoder_wgrad(dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, wgrad_ws_args(dev), sync)
         if enc.num_directions == 2:
-            if st.enc_graph is not None:         # the two directions' tapes: entered with the decoder's gradients
-                torch.autograd.backward(list(st.enc_graph), [dctx, dh1, dc1])
+            bi_encoder_bwd(enc, batch.seq, batch.lengths_dev, T, dropout_arg(*st.drop_enc_bi), st.site_rel,
+                           st.enc_table, st.enc_tape, st.h_init, dctx, dh1, dc1)
         else:
             etp = _lib.EncoderTape(*(st.enc_tape[k].data_ptr() for k in ('emb', 'xg', 'gates', 'hs', 'cs')))
             ew = _encoder_structs(enc, table=st.enc_table)

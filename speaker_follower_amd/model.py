@@ -431,46 +431,88 @@ class _EncoderFn(torch.autograd.Function):
         return (None,) * (7 + ctx.n_params)
 
 
-class _BiAssembleFn(torch.autograd.Function):
-    """model.py:92-102 for nn.LSTM(bidirectional=True): ctx[b, t] = [forward output at t | reverse output at t] (the
-    reverse direction ran over the row's tokens in reversed order, so its output for position t is its step
-    len_b - 1 - t), zeros beyond the row's length; h_t = [h_reverse ; h_forward], c_t likewise.  Pure data movement
-    through the C ABI (row-strided copies and an index gather); the backward is the transposed movement."""
+_ENC_TAPE_KEYS = ('emb', 'xg', 'gates', 'hs', 'cs')
+
+
+def bi_encoder_tapes(B, T, E, H, device, keep=True):
+    """The two directions' sf_encoder_tape buffers (H per direction); `keep` = a backward may follow (embedded tokens and
+    gate tape kept; an inference call needs only the state slots)."""
+    new = lambda *s: torch.empty(*s, device=device, dtype=torch.float32)  # noqa: E731
+    return [dict(emb=new(T, B, E) if keep else None, xg=new(T, B, 4 * H) if keep else None,
+                 gates=new(T, B, 4 * H) if keep else None, hs=new(T + 1, B, H), cs=new(T + 1, B, H))
+            for _ in range(2)]
+
+
+def _tape_struct(tape):
+    return _lib.EncoderTape(*(tape[k].data_ptr() if tape[k] is not None else None for k in _ENC_TAPE_KEYS))
+
+
+def _e2d_ptrs(mod):
+    e2d = mod.encoder2decoder
+    return e2d.weight.data_ptr(), e2d.bias.data_ptr(), transposed(e2d.weight).data_ptr()
+
+
+def bi_encoder_fwd(mod, seq, lengths_dev, T, drop, site, use_table, tapes, ctx_out, dinit, c_t):
+    """sf_encoder_bilstm_fwd: both directions, the [forward | reverse] assembly, the ctx dropout and decoder_init in one
+    call (one persistent launch for both recurrences where it applies).  `drop`: the sf_dropout* argument, `site` its
+    stream id.  Records on the module which path ran (`mod.last_path`: 'persistent' or 'per_step')."""
+    B, Lpad = seq.shape
+    E, H = mod.embedding_size, mod.hidden_size
+    wf = _encoder_structs(mod, table=use_table, direction=0)
+    wr = _encoder_structs(mod, table=use_table, direction=1)
+    w_e2d, b_e2d, w_e2d_t = _e2d_ptrs(mod)
+    path = C.c_int32(-1)
+    call('sf_encoder_bilstm_fwd', C.byref(wf), C.byref(wr), w_e2d, b_e2d, w_e2d_t, B, Lpad, T, E, H, ptr(seq),
+         ptr(lengths_dev), ptr(ctx_out), ptr(dinit), ptr(c_t), C.byref(_tape_struct(tapes[0])),
+         C.byref(_tape_struct(tapes[1])), drop, site, C.byref(path), *ws_args(seq.device))
+    mod.last_path = 'persistent' if path.value == 1 else 'per_step'
+
+
+def bi_encoder_bwd(mod, seq, lengths_dev, T, drop, site, use_table, tapes, dinit, dctx, d_init, d_ct):
+    """sf_encoder_bilstm_bwd: accumulates into both directions' LSTM gradients, encoder2decoder's and (trainable
+    embedding) the embedding's.  Records `mod.last_backward_path`."""
+    B = lengths_dev.shape[0]
+    E, H = mod.embedding_size, mod.hidden_size
+    wf = _encoder_structs(mod, table=use_table, direction=0)
+    wr = _encoder_structs(mod, table=use_table, direction=1)
+    gf = _encoder_structs(mod, grad=True, seq=None if use_table else seq, direction=0)
+    gr = _encoder_structs(mod, grad=True, seq=None if use_table else seq, direction=1)
+    w_e2d, _, w_e2d_t = _e2d_ptrs(mod)
+    g_w, g_b = _grads((mod.encoder2decoder.weight, mod.encoder2decoder.bias))
+    path = C.c_int32(-1)
+    call('sf_encoder_bilstm_bwd', C.byref(wf), C.byref(wr), w_e2d, w_e2d_t, C.byref(gf), C.byref(gr), g_w, g_b, B, T,
+         E, H, ptr(lengths_dev), ptr(dinit), ptr(dctx), ptr(d_init), ptr(d_ct), C.byref(_tape_struct(tapes[0])),
+         C.byref(_tape_struct(tapes[1])), drop, site, C.byref(path), *ws_args(dinit.device))
+    mod.last_backward_path = 'persistent' if path.value == 1 else 'per_step'
+
+
+class _BiEncoderFn(torch.autograd.Function):
+    """model.py:61-66, 88-102 with bidirectional=True: ctx = dropout([forward | reverse]), decoder_init =
+    tanh(encoder2decoder([h_reverse ; h_forward])), c_t = [c_reverse ; c_forward] -- one C call each way."""
 
     @staticmethod
-    def forward(ctx, idx_rev, ctx_f, ctx_r, h_f, h_r, c_f, c_r):
-        B, T, Hd = ctx_f.shape
-        dev = ctx_f.device
-        s = stream()
-        out = torch.empty(B, T, 2 * Hd, device=dev)
-        call('sf_dropout_copy', ptr(ctx_f), Hd, B * T, Hd, ptr(out), 2 * Hd, None, 0, 0, s)
-        call('sf_gather_rows', ptr(ctx_r), Hd, ptr(idx_rev), B * T, Hd, C.c_void_p(out.data_ptr() + 4 * Hd), 2 * Hd, s)
-        h_t, c_t = torch.empty(B, 2 * Hd, device=dev), torch.empty(B, 2 * Hd, device=dev)
-        for dst, first, second in ((h_t, h_r, h_f), (c_t, c_r, c_f)):              # model.py:93-94: [-1] (reverse) first
-            call('sf_dropout_copy', ptr(first), Hd, B, Hd, ptr(dst), 2 * Hd, None, 0, 0, s)
-            call('sf_dropout_copy', ptr(second), Hd, B, Hd, C.c_void_p(dst.data_ptr() + 4 * Hd), 2 * Hd, None, 0, 0, s)
-        ctx.save_for_backward(idx_rev)
-        ctx.dims = (B, T, Hd)
-        return out, h_t, c_t
+    def forward(ctx, mod, seq, lengths_dev, T, drop_cfg, use_table, *params):
+        B, Lpad = seq.shape
+        E, H = mod.embedding_size, mod.hidden_size
+        dev = seq.device
+        ctx_out = torch.empty(B, T, 2 * H, device=dev)
+        dinit, c_t = torch.empty(B, 2 * H, device=dev), torch.empty(B, 2 * H, device=dev)
+        tapes = bi_encoder_tapes(B, T, E, H, dev)
+        p, seed, site = drop_cfg
+        bi_encoder_fwd(mod, seq, lengths_dev, T, dropout_arg(p, seed), site, use_table, tapes, ctx_out, dinit, c_t)
+        ctx.mod, ctx.tapes, ctx.cfg = mod, tapes, (T, drop_cfg, use_table)
+        ctx.n_params = len(params)
+        ctx.save_for_backward(lengths_dev, dinit, seq)
+        return ctx_out, dinit, c_t
 
     @staticmethod
-    def backward(ctx, dout, dh_t, dc_t):
-        (idx_rev,) = ctx.saved_tensors
-        B, T, Hd = ctx.dims
-        dev = idx_rev.device
-        s = stream()
-        dout, dh_t, dc_t = dout.contiguous(), dh_t.contiguous(), dc_t.contiguous()
-        dctx_f, dctx_r = torch.empty(B, T, Hd, device=dev), torch.empty(B, T, Hd, device=dev)
-        call('sf_dropout_copy', ptr(dout), 2 * Hd, B * T, Hd, ptr(dctx_f), Hd, None, 0, 0, s)
-        # (the reversal is an involution on the live positions; idx < 0 -- beyond the row's length -- gives zeros)
-        call('sf_gather_rows', C.c_void_p(dout.data_ptr() + 4 * Hd), 2 * Hd, ptr(idx_rev), B * T, Hd, ptr(dctx_r), Hd, s)
-        outs = []
-        for d in (dh_t, dc_t):
-            first, second = torch.empty(B, Hd, device=dev), torch.empty(B, Hd, device=dev)
-            call('sf_dropout_copy', ptr(d), 2 * Hd, B, Hd, ptr(first), Hd, None, 0, 0, s)
-            call('sf_dropout_copy', C.c_void_p(d.data_ptr() + 4 * Hd), 2 * Hd, B, Hd, ptr(second), Hd, None, 0, 0, s)
-            outs += [second, first]                                   # (forward half, reverse half)
-        return None, dctx_f, dctx_r, outs[0], outs[1], outs[2], outs[3]
+    def backward(ctx, dctx, dinit_g, dct_g):
+        lengths_dev, dinit, seq = ctx.saved_tensors
+        T, (p, seed, site), use_table = ctx.cfg
+        cont = lambda t: t.contiguous() if t is not None else None  # noqa: E731
+        bi_encoder_bwd(ctx.mod, seq, lengths_dev, T, dropout_arg(p, seed), site, use_table, ctx.tapes, dinit,
+                       cont(dctx), cont(dinit_g), cont(dct_g))
+        return (None,) * (6 + ctx.n_params)
 
 
 class EncoderLSTM(nn.Module):
@@ -514,30 +556,16 @@ class EncoderLSTM(nn.Module):
         return _EncoderFn.apply(self, inputs.contiguous(), lengths_dev, T, cfg, table, None, *params)
 
     def _forward_bidirectional(self, seq, lengths_dev, T, cfg, table):
-        """model.py:61-66, 88-102 with bidirectional=True (train.py:197-199: hidden_size // 2 per direction): two
+        """model.py:61-66, 88-102 with bidirectional=True (train.py:197-199: hidden_size // 2 per direction): both
         recurrences over the packed sequences -- the reverse one over every row's tokens in reversed order --, ctx =
         dropout([forward | reverse]), decoder_init = tanh(encoder2decoder([h_reverse ; h_forward])), c_t = [c_reverse ;
-        c_forward].  Each direction is the unidirectional C entry (SF_ENC_RAW_STATE); per-step kernels (the persistent
-        launch is built for hidden 512)."""
-        B, Lpad = seq.shape
-        dev = seq.device
-        ln = lengths_dev.view(B, 1).long()
-        t_ = torch.arange(Lpad, device=dev).view(1, Lpad)
-        src = torch.where(t_ < ln, ln - 1 - t_, t_)                    # position read by step t of the reverse direction
-        seq_rev = torch.gather(seq, 1, src).contiguous()
-        tt = torch.arange(T, device=dev).view(1, T)
-        base = torch.arange(B, device=dev).view(B, 1) * T
-        idx_rev = torch.where(tt < ln, base + ln - 1 - tt, torch.full_like(tt, -1)).to(torch.int32).reshape(-1).contiguous()
-        outs = []
-        for direction, s_ in ((0, seq), (1, seq_rev)):                 # (cfg: only the embedded tokens' dropout here)
-            params = list(_lstm_dir_params(self, direction)) + [self.embedding.weight]
-            outs.append(_EncoderFn.apply(self, s_, lengths_dev, T, cfg, table, direction, *params))
-        (ctx_f, h_f, c_f), (ctx_r, h_r, c_r) = outs
-        ctx_raw, h_t, c_t = _BiAssembleFn.apply(idx_rev, ctx_f, ctx_r, h_f, h_r, c_f, c_r)
-        decoder_init = linear(self.encoder2decoder, h_t, act=1)        # model.py:99
-        p, seed, site = cfg
-        ctx_out = _DropoutFn.apply(ctx_raw, p, seed, site) if p > 0 else ctx_raw     # model.py:101-102
-        return ctx_out, decoder_init, c_t
+        c_forward]: sf_encoder_bilstm_fwd / _bwd (one persistent launch for both directions where it applies; the
+        per-step kernels with `persistent = False`)."""
+        params = [self.lstm.weight_ih_l0, self.lstm.weight_hh_l0, self.lstm.bias_ih_l0, self.lstm.bias_hh_l0,
+                  self.lstm.weight_ih_l0_reverse, self.lstm.weight_hh_l0_reverse, self.lstm.bias_ih_l0_reverse,
+                  self.lstm.bias_hh_l0_reverse, self.encoder2decoder.weight, self.encoder2decoder.bias,
+                  self.embedding.weight]
+        return _BiEncoderFn.apply(self, seq, lengths_dev, T, cfg, table, *params)
 
 
 # ------------------------------------------------------------------------------------------------
