@@ -786,6 +786,44 @@ int sf_logprob_topk(float* logit, int ld, int N, int n, const int32_t* n_valid, 
 int sf_scatter_rows(const float* src, int ld_src, const int32_t* idx, int n, int width, float* dst,
                     int ld_dst, sf_stream stream);
 
+/* The speaker's beam selection for one word step (speaker.py:262-296), all instances at once, no host round trip:
+ * what search.DeviceSpeakerBeam issues after sf_speaker_decoder_fwd + sf_logprob_topk in its device word loop.
+ * R = B * beam_size hypothesis slots; instance b owns slots b*beam_size .. b*beam_size + beam_size - 1, its live slots
+ * at the front of that block.  Per instance with inst[b] = (live, n_done, t), live > 0 and t < T (else nothing
+ * changes -- steps issued after the search has ended are no-ops):
+ *   candidates  score[i] + top_lp[i, j] (float32 add) for the live slots i and their k words j, ordered by score
+ *               descending, then flat index i*k + j ascending; the best beam_size are selected (top_w / top_lp are
+ *               [R,k] rows of sf_logprob_topk: descending, ties lower column first);
+ *   history     selection q goes to position base + p of step t: hist_word / hist_parent (the slot i it extends,
+ *               global) / hist_score at [t * ld_hist + base + p]; continuing selections (word != eos, t < T-1) take
+ *               p = 0, 1, .. in selection order, finals follow them in selection order; hist_attn (optional, with
+ *               alpha [R,Tp]) receives alpha[i] at [t * ld_hist + i * Tp] for the live slots i;
+ *   finals      appended to the instance's completion list done_rec / done_score [B, 2*beam_size] in selection order
+ *               at n_done, n_done + 1, .. as t * R + base + p (so history row t, position base + p);
+ *   next slots  slot base + p (p < live') = continuing selection p: words (int64: the next prev_word), parent (gather
+ *               index of its h / c: the slot i of step t) and score; live' = their number, 0 once n_done >= beam_size
+ *               (speaker.py:281-290); the other slots get words = eos, parent = -1, score = 0;
+ *               inst[b] = (live', n_done + finals, t + 1); live_total[t] += live' (the caller zeroes live_total [T]).
+ * A slot's history position at step t is the slot it occupies at step t + 1: the backchain of (t, p) is
+ * p -> hist_parent[t, p] = position at t - 1 -> ..., down to the root slot base at t = 0.
+ * SF_ERR_ARG on NULL pointers, k < 1, k > beam_size, ld_hist < R (< R * Tp with hist_attn); SF_ERR_UNSUPPORTED for
+ * beam_size > 64 (one wavefront per instance, one lane per slot). */
+typedef struct sf_spk_beam {
+    int32_t B, beam_size, k, T, Tp, eos;
+    float* score;         /* [R] running score of every slot */
+    int64_t* words;       /* [R] */
+    int32_t* parent;      /* [R] */
+    int32_t* inst;        /* [B,3] live, n_done, t */
+    int32_t* live_total;  /* [T] */
+    int32_t *hist_word, *hist_parent;
+    float *hist_score, *hist_attn;
+    int64_t ld_hist;      /* elements between word steps of every history array */
+    int32_t* done_rec;    /* [B, 2*beam_size] */
+    float* done_score;    /* [B, 2*beam_size] */
+} sf_spk_beam;
+int sf_speaker_beam_select(const sf_spk_beam* s, const int32_t* top_w, const float* top_lp, const float* alpha,
+                           sf_stream stream);
+
 /* Up to SF_ROW_MOVES_MAX row gathers (scatter = 0: dst[i, :width] = src[idx[i], :width], idx < 0 => zeros) and row
  * scatters (scatter = 1: dst[idx[i], :width] = src[i, :width], idx < 0 => row skipped; the idx >= 0 distinct) over the
  * same n rows in ONE launch: `h_t[flat_indices]` and `c_t[flat_indices]` of a search step (follower.py:588-589, 826-827)

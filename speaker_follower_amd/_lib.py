@@ -145,6 +145,14 @@ class NavIO(C.Structure):
 SpkDecoderTape = _ptr_struct('SpkDecoderTape', ['emb', 'gates', 'c1', 'h1', 'cat2', 't_text',
                                                 'alpha', 'h_tilde', 'logit'])
 
+
+class SpkBeam(C.Structure):
+    """sf_spk_beam: state and history of the speaker's device beam search (sf_speaker_beam_select)."""
+    _fields_ = ([(n, C.c_int32) for n in ('B', 'beam_size', 'k', 'T', 'Tp', 'eos')] +
+                [(n, c_p) for n in ('score', 'words', 'parent', 'inst', 'live_total', 'hist_word', 'hist_parent',
+                                    'hist_score', 'hist_attn')] +
+                [('ld_hist', C.c_int64), ('done_rec', c_p), ('done_score', c_p)])
+
 i32, u32, i64p = C.c_int, C.c_uint32, C.c_void_p
 P = C.POINTER
 WS = [c_p, C.c_size_t, c_p]          # ws, ws_bytes, stream
@@ -247,6 +255,7 @@ _SIGNATURES = {
     'sf_gather_rows': (C.c_int, [c_f, i32, c_p, i32, i32, c_f, i32, c_p]),
     'sf_scatter_rows': (C.c_int, [c_f, i32, c_p, i32, i32, c_f, i32, c_p]),
     'sf_logprob_topk': (C.c_int, [c_f, i32, i32, i32, c_p, i32, c_p, c_f, c_p]),
+    'sf_speaker_beam_select': (C.c_int, [P(SpkBeam), c_p, c_f, c_f, c_p]),
     'sf_speaker_decoder_fwd': (C.c_int, [P(SpkDecoderW), i32, i32, i32, i32, i32, i64p, c_f, c_f,
                                          c_f, c_p, c_p, P(SpkDecoderTape), P(Dropout), u32] + WS),
     'sf_speaker_decoder_bwd': (C.c_int, [P(SpkDecoderW), P(SpkDecoderG), i32, i32, i32, i32, i32, i64p,

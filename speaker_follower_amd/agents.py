@@ -1220,9 +1220,22 @@ class Seq2SeqSpeaker(object):
         self.losses.append(float(loss.detach()) if torch.is_tensor(loss) else float(loss))
         return outputs
 
+    # beam_search with its word loop on the device (search.DeviceSpeakerBeam: no host round trip per word, chunks of
+    # `beam_chunk` word steps as replayed hipGraphs, or issued eagerly with beam_graphs = False).  Off by default.  Same
+    # outputs as the host loop; inference only; beam_size <= 64 -- wider beams run the host loop and count a fallback.
+    beam_on_device = False
+    beam_chunk = 8
+    beam_graphs = True
+    beam_fallbacks = 0
+    device_beam = None
+
     def beam_search(self, beam_size, path_obs, path_actions):
         """speaker.py:211-318 (search.py)."""
         from . import search
+        if self.beam_on_device:
+            if search.DeviceSpeakerBeam.supports(beam_size):
+                return search.speaker_beam_search_device(self, beam_size, path_obs, path_actions)
+            self.beam_fallbacks += 1
         return search.speaker_beam_search(self, beam_size, path_obs, path_actions)
 
     sweep_test_after = 30            # test(): minibatches (cumulative over calls) before the split is decoded as a sweep

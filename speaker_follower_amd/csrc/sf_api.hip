@@ -2026,6 +2026,17 @@ int sf_scatter_rows(const float* src, int ld_src, const int32_t* idx, int n, int
     SF_CHECK_ARG(src && idx && dst && n > 0 && width > 0);
     return scatter_rows(src, ld_src, idx, n, width, dst, ld_dst, S(stream));
 }
+int sf_speaker_beam_select(const sf_spk_beam* s, const int32_t* top_w, const float* top_lp, const float* alpha,
+                           sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(s && top_w && top_lp && s->B > 0 && s->beam_size > 0 && s->k >= 1 && s->k <= s->beam_size &&
+                 s->T > 0 && s->Tp > 0 && s->eos >= 0);
+    SF_CHECK_ARG(s->score && s->words && s->parent && s->inst && s->live_total && s->hist_word && s->hist_parent &&
+                 s->hist_score && s->done_rec && s->done_score && !s->hist_attn == !alpha);
+    const int64_t R = (int64_t)s->B * s->beam_size;
+    SF_CHECK_ARG(s->ld_hist >= R && (!s->hist_attn || s->ld_hist >= R * s->Tp));
+    return speaker_beam_select(*s, top_w, top_lp, alpha, S(stream));
+}
 
 // ---- a9 SpeakerDecoderLSTM.forward (model.py:497-519) -----------------------------------------------------
 int sf_speaker_decoder_fwd(const sf_spk_decoder_w* w, int B, int E, int H, int Tp, int vocab,

@@ -749,15 +749,17 @@ def physical_walks(t, visits, depth):
 
 # ------------------------------------------------------------------------------------ speaker beam search
 @_gc_paused
-def speaker_beam_search(speaker, beam_size, path_obs, path_actions):
+def speaker_beam_search(speaker, beam_size, path_obs, path_actions, pad_rows=None):
     """Seq2SeqSpeaker.beam_search (speaker.py:211-318): one flat SpeakerDecoderLSTM step per word over all live
-    hypotheses of all paths; hypotheses are rows (parent, path, word, float32 score, pool row)."""
+    hypotheses of all paths; hypotheses are rows (parent, path, word, float32 score, pool row).  pad_rows: every
+    decoder step runs over that many rows (search.FlatSpeakerDecoder), the live ones first -- the products then see
+    the row count of the device word loop (search.speaker_beam_search_device) and the two agree bit for bit."""
     from . import search
     start_obs, feats, acts, path_mask, _, _, perm = speaker._batch_observations_and_actions(path_obs, path_actions, None)
     B = len(start_obs)
     with torch.no_grad():
         ctx, h_t, c_t = speaker.encoder(acts, feats)
-    sd = search.FlatSpeakerDecoder(speaker.decoder, ctx.detach(), path_mask)
+    sd = search.FlatSpeakerDecoder(speaker.decoder, ctx.detach(), path_mask, pad_rows=pad_rows)
     sd.seed(h_t.detach(), c_t.detach())
     parent, inst, word, pool = [np.full(B, -1)], [np.arange(B)], [np.full(B, search.BOS)], [np.arange(B)]
     score = [np.zeros(B, F32)]
@@ -786,8 +788,16 @@ def speaker_beam_search(speaker, beam_size, path_obs, path_actions):
         frontier = ids[~final & (n_done[I[ids]] < beam_size)]
         if len(frontier) == 0:
             break
-    tok = getattr(speaker.env, 'tokenizer', None)
-    outputs = [[] for _ in range(B)]
+    return speaker_beam_outputs(start_obs, perm, done, P, W, S, R, beam_size, sd.attention_rows,
+                                getattr(speaker.env, 'tokenizer', None))
+
+
+def speaker_beam_outputs(start_obs, perm, done, P, W, S, R, beam_size, attention_rows, tok):
+    """The result lists of the speaker's beam search (speaker.py:298-318), shared by the host word loop and the device
+    one (search.speaker_beam_search_device).  Hypotheses are nodes: P parent (-1 at the BOS roots), W word, S float32
+    score, R the row of its attention (`attention_rows(rows)` -> list of [Tp] arrays); done[b] the completed nodes of
+    instance b in the order they completed.  Per instance the beam_size best (stable by score), backchained."""
+    outputs = [[] for _ in range(len(start_obs))]
     for b, src in enumerate(perm):
         assert not outputs[src]
         lst = done[b]
@@ -804,5 +814,5 @@ def speaker_beam_search(speaker, beam_size, path_obs, path_actions):
                 'instr_id': start_obs[b]['instr_id'], 'word_indices': words, 'score': sc[-1],
                 'scores': [y - x for x, y in zip(sc, sc[1:])],
                 'words': tok.decode_sentence(words, break_on_eos=True, join=False) if tok is not None else list(words),
-                'attentions': sd.attention_rows([int(R[n]) for n in lin[1:]])})
+                'attentions': attention_rows([int(R[n]) for n in lin[1:]])})
     return outputs

@@ -25,6 +25,7 @@ step over all live states on the device:
 The agent needs a `features.FeatureStore` (`agent.store`) and an env.R2RIndexEnv.
 """
 import ctypes as C
+import time
 from collections import namedtuple, Counter
 
 import numpy as np
@@ -35,7 +36,7 @@ from ._lib import call
 from .features import cand_sincos
 from .follower import batch_instructions_from_encoded, EOS, BOS
 from .model import decoder_params, decoder_w_struct, decoder_tape, tape_struct
-from .runtime import ptr, stream, ws_args, gc_paused, graph_capture
+from .runtime import ptr, stream, ws_args, gc_paused, graph_capture, ensure_workspace
 
 byref = C.byref
 
@@ -453,9 +454,11 @@ def _encode_items(agent, items):
 
 
 class FlatSpeakerDecoder:
-    """One SpeakerDecoderLSTM step (model.py:487-519) over a flat list of word hypotheses."""
+    """One SpeakerDecoderLSTM step (model.py:487-519) over a flat list of word hypotheses.  pad_rows (default off):
+    every step runs over at least that many rows, the hypotheses first, then padding rows (zero state, path 0) whose
+    results are dropped -- the row count of the device word loop (DeviceSpeakerBeam), for bit-exact comparisons."""
 
-    def __init__(self, decoder, ctx, path_mask):
+    def __init__(self, decoder, ctx, path_mask, pad_rows=None):
         from .model import _SPK_TAPE
         self.dec, self.keys = decoder, _SPK_TAPE
         self.ctx = ctx.contiguous()
@@ -467,6 +470,7 @@ class FlatSpeakerDecoder:
         self.Tp = ctx.shape[1]
         self.hpool, self.cpool, self.apool = _Pool(self.H, self.dev), _Pool(self.H, self.dev), _Pool(self.Tp, self.dev)
         self.w = decoder._w_struct()
+        self.pad_rows = pad_rows
         self._keep = None
 
     def seed(self, h, c):
@@ -481,8 +485,14 @@ class FlatSpeakerDecoder:
         """words / rows / inst [N]: previous word, pool row of (h, c), path of every hypothesis.  Returns (pool
         row base of the N new states, top-k words [N,k], their log-probabilities [N,k])."""
         dev, H = self.dev, self.H
-        N = len(words)
+        n_hyp = len(words)
         k = min(k, self.vocab)
+        if self.pad_rows is not None and self.pad_rows > n_hyp:
+            pad = self.pad_rows - n_hyp
+            words = np.concatenate((np.asarray(words, np.int64), np.full(pad, EOS, np.int64)))
+            rows = np.concatenate((np.asarray(rows), np.full(pad, -1)))
+            inst = np.concatenate((np.asarray(inst), np.zeros(pad, np.int64)))
+        N = len(words)
         ints = torch.from_numpy(np.stack((rows, inst)).astype(np.int32)).to(dev)
         wd = torch.from_numpy(np.asarray(words, np.int64)).to(dev)
         new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
@@ -502,13 +512,250 @@ class FlatSpeakerDecoder:
         logp = new(N, k)
         call('sf_logprob_topk', ptr(tape['logit']), self.ldv, N, self.vocab, None, k, ptr(idx), ptr(logp), s_)
         self._keep = (ints, wd, h0, c0, tape)
-        both = torch.cat((idx.to(torch.float32), logp), dim=1).cpu().numpy()
+        both = torch.cat((idx.to(torch.float32), logp), dim=1)[:n_hyp].cpu().numpy()
         return base, both[:, :k].astype(np.int64), both[:, k:]
 
     def attention_rows(self, rows):
         if not rows:
             return []
         return list(self.apool.buf[torch.tensor(rows, dtype=torch.int64, device=self.dev)].cpu().numpy())
+
+
+class DeviceSpeakerBeam:
+    """The speaker's beam search (speaker.py:211-318) with its word loop on the device: R = B * beam_size fixed
+    hypothesis slots (instance b owns slots b*beam_size ..), per word step
+
+        h / c of every slot from its parent slot (sf_move_rows), SpeakerDecoderLSTM over all R rows (ctx_row = the
+        slot's path; dead rows are decoded and ignored), sf_logprob_topk (k = min(beam_size, vocab)), and
+        sf_speaker_beam_select: the next words, parent slots and scores, the completed hypotheses, the history;
+
+    all issued without a host synchronisation.  A chunk of `chunk` word steps is ONE replayed hipGraph (captured once per
+    path length Tp on one stream, no forked branches); the host reads the batch's live count once per chunk (4 bytes) and
+    the histories once at the end: at most ceil(T / chunk) + 1 reads per minibatch instead of T blocking round trips.
+    Steps issued after the search has ended change nothing, so every chunk size gives the same results.  The outputs
+    are assembled by the host loop's own code (frontier.speaker_beam_outputs) from the same float32 scores.
+
+    Inference only; beam_size <= MAX_BEAM (one wavefront per instance in the selection kernel)."""
+    MAX_BEAM = 64
+
+    def __init__(self, decoder, B, beam_size, T, chunk=8, graphs=True):
+        if not self.supports(beam_size):
+            raise ValueError('DeviceSpeakerBeam: beam_size %d > %d' % (beam_size, self.MAX_BEAM))
+        self.dec, self.dev = decoder, next(decoder.parameters()).device
+        self.B, self.beam, self.T = B, beam_size, T
+        self.chunk, self.graphs = max(1, int(chunk)), bool(graphs)
+        self.H, self.E = decoder.hidden_size, decoder.embedding.weight.shape[1]
+        self.vocab = decoder.decoder2action.weight.shape[0]
+        self.ldv = (self.vocab + 3) & ~3
+        self.k = min(beam_size, self.vocab)
+        R = self.R = B * beam_size
+        dev = self.dev
+        f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)          # noqa: E731
+        self.h0, self.c0 = f32(R, self.H), f32(R, self.H)
+        from .model import _SPK_TAPE
+        self.keys = _SPK_TAPE
+        self.tape = dict(emb=f32(R, self.E), gates=f32(R, 4 * self.H), c1=f32(R, self.H), h1=f32(R, self.H),
+                         cat2=f32(R, 2 * self.H), t_text=f32(R, self.H), h_tilde=f32(R, self.H), logit=f32(R, self.ldv))
+        self.idx = torch.zeros(R, self.k, device=dev, dtype=torch.int32)
+        self.logp = f32(R, self.k)
+        self.score = f32(R)
+        self.words = torch.full((R,), EOS, device=dev, dtype=torch.int64)
+        self.parent = torch.full((R,), -1, device=dev, dtype=torch.int32)
+        self.ctx_row = torch.arange(R, device=dev, dtype=torch.int32) // beam_size
+        # the record: [inst B x 3 | live_total T | done_rec B x 2 beam | done_score B x 2 beam] then per word step
+        # [hist_word R | hist_parent R | hist_score R | hist_attn R x Tp] -- one download at the end
+        self.o_live = 3 * B
+        self.o_done = self.o_live + T
+        self.o_dscore = self.o_done + 2 * beam_size * B
+        self.hdr = (self.o_dscore + 2 * beam_size * B + 3) & ~3
+        self.head0 = torch.zeros(self.hdr, dtype=torch.int32)
+        self.head0[0:3 * B:3] = 1                                      # one live slot per path, nothing done, t = 0
+        self.head0 = self.head0.to(dev)
+        self.words0 = self.words.clone()
+        self.words0[::beam_size] = BOS
+        self.parent0 = self.parent.clone()
+        self.parent0[::beam_size] = torch.arange(0, R, beam_size, device=dev, dtype=torch.int32)
+        self.Tp_cap = 0
+        self.graph_by_tp = {}
+        self.baked = self._side = None
+        self.host_reads = self.last_host_reads = 0
+        self.minibatches, self.last_run_s = 0, 0.0          # (last_run_s: the word loop and its download, seconds)
+
+    @classmethod
+    def supports(cls, beam_size):
+        return 1 <= beam_size <= cls.MAX_BEAM
+
+    # ---- buffers that depend on the path length (grown, never shrunk: the graphs hold their addresses)
+    def _reserve(self, Tp):
+        if Tp <= self.Tp_cap:
+            return
+        dev, B, R = self.dev, self.B, self.R
+        self.Tp_cap = Tp
+        self.ctx_buf = torch.zeros(B * Tp * self.H, device=dev, dtype=torch.float32)
+        self.mask_buf = torch.ones(B * Tp, device=dev, dtype=torch.uint8)
+        self.alpha_buf = torch.zeros(R * Tp, device=dev, dtype=torch.float32)
+        self.rec = torch.zeros(self.hdr + self.T * R * (3 + Tp), device=dev, dtype=torch.int32)
+        self.graph_by_tp = {}
+
+    def _views(self, Tp):
+        B, R, H = self.B, self.R, self.H
+        ctx = self.ctx_buf[:B * Tp * H].view(B, Tp, H)
+        mask = self.mask_buf[:B * Tp].view(B, Tp)
+        alpha = self.alpha_buf[:R * Tp].view(R, Tp)
+        return ctx, mask, alpha
+
+    def _structs(self, Tp):
+        R, S = self.R, self.R * (3 + Tp)
+        rec, base = self.rec, self.rec.data_ptr()
+        steps = base + 4 * self.hdr
+        sb = _lib.SpkBeam(self.B, self.beam, self.k, self.T, Tp, EOS,
+                          self.score.data_ptr(), self.words.data_ptr(), self.parent.data_ptr(), base,
+                          base + 4 * self.o_live, steps, steps + 4 * R, steps + 8 * R, steps + 12 * R, S,
+                          base + 4 * self.o_done, base + 4 * self.o_dscore)
+        _, _, alpha = self._views(Tp)
+        tape = dict(self.tape, alpha=alpha)
+        tp = _lib.SpkDecoderTape(*(tape[key].data_ptr() for key in self.keys))
+        H = self.H
+        gat = (_lib.RowMove * 2)(_lib.RowMove(tape['h1'].data_ptr(), self.h0.data_ptr(), self.parent.data_ptr(), H, H, H, 0),
+                                 _lib.RowMove(tape['c1'].data_ptr(), self.c0.data_ptr(), self.parent.data_ptr(), H, H, H, 0))
+        assert rec.numel() >= self.hdr + self.T * S
+        return sb, tp, gat
+
+    def _issue(self, Tp, n_steps):
+        s = stream()
+        ctx, mask, alpha = self._views(Tp)
+        sb, tp, gat = self._structs(Tp)
+        w = self.w
+        for _ in range(n_steps):
+            call('sf_move_rows', gat, 2, self.R, s)
+            call('sf_speaker_decoder_fwd', byref(w), self.R, self.E, self.H, Tp, self.vocab, ptr(self.words),
+                 ptr(self.h0), ptr(self.c0), ptr(ctx), ptr(mask), ptr(self.ctx_row), byref(tp), None, 0,
+                 *ws_args(self.dev))
+            call('sf_logprob_topk', ptr(self.tape['logit']), self.ldv, self.R, self.vocab, None, self.k, ptr(self.idx),
+                 ptr(self.logp), s)
+            call('sf_speaker_beam_select', byref(sb), ptr(self.idx), ptr(self.logp), ptr(alpha), s)
+        self._keep = (sb, tp, gat, w)
+
+    def _capture(self, Tp):
+        # dead slots for the warm-up step (every instance ended: the selection changes nothing)
+        self.rec[:self.hdr].zero_()
+        self.words.fill_(EOS)
+        self.parent.fill_(-1)
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.dev)              # (one capture stream: its workspace is baked)
+            ensure_workspace(self._side, self.dev)
+        side = self._side
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.no_grad(), torch.cuda.stream(side):
+            self._issue(Tp, 1)                                           # warm-up: cached layouts, lazy tables
+            side.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with graph_capture(graph, side):
+                self._issue(Tp, self.chunk)
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph_by_tp[Tp] = graph
+        return graph
+
+    # ---- per minibatch
+    def run(self, ctx, path_mask, h, c):
+        """One search over the encoder outputs (ctx [B,Tp,H], path_mask [B,Tp], h / c [B,H]).  Returns the host
+        arrays (inst [B,3], done_rec / done_score [B, 2 beam], hist_word / hist_parent / hist_score [t_end, R],
+        hist_attn [t_end, R, Tp])."""
+        t0 = time.perf_counter()
+        B, R, Tp = self.B, self.R, ctx.shape[1]
+        if ctx.shape[0] != B:
+            raise ValueError('DeviceSpeakerBeam built for %d paths, got %d' % (B, ctx.shape[0]))
+        self._reserve(Tp)
+        self.w = self.dec._w_struct()
+        wb = bytes(self.w)
+        if wb != self.baked:                                             # a weight (or its cached table) moved
+            self.graph_by_tp, self.baked = {}, wb
+        graph = None
+        if self.graphs:
+            graph = self.graph_by_tp.get(Tp) or self._capture(Tp)
+        cv, mv, _ = self._views(Tp)
+        cv.copy_(ctx)
+        mv.copy_(path_mask.to(torch.uint8))
+        self.tape['h1'].view(B, self.beam, self.H)[:, 0].copy_(h)
+        self.tape['c1'].view(B, self.beam, self.H)[:, 0].copy_(c)
+        self.rec[:self.hdr].copy_(self.head0)
+        self.words.copy_(self.words0)
+        self.parent.copy_(self.parent0)
+        self.score.zero_()
+        reads, issued = 0, 0
+        while issued < self.T:
+            if graph is not None:
+                graph.replay()
+            else:
+                self._issue(Tp, self.chunk)
+            issued += self.chunk
+            if issued >= self.T:
+                break
+            reads += 1
+            if int(self.rec[self.o_live + issued - 1].item()) == 0:     # nothing live after the chunk's last step
+                break
+        S = R * (3 + Tp)
+        flat = self.rec[:self.hdr + min(issued, self.T) * S].cpu().numpy()       # the one download of the results
+        reads += 1
+        self.last_host_reads = reads
+        self.host_reads += reads
+        self.minibatches += 1
+        self.last_run_s = time.perf_counter() - t0
+        inst = flat[:3 * B].reshape(B, 3)
+        t_end = int(inst[:, 2].max())                                    # (the step after the last one any path ran)
+        fl = flat.view(np.float32)
+        done_rec = flat[self.o_done:self.o_dscore].reshape(B, 2 * self.beam)
+        done_score = fl[self.o_dscore:self.o_dscore + 2 * self.beam * B].reshape(B, 2 * self.beam)
+        st = flat[self.hdr:self.hdr + t_end * S].reshape(t_end, S)
+        stf = fl[self.hdr:self.hdr + t_end * S].reshape(t_end, S)
+        return dict(inst=inst, done_rec=done_rec, done_score=done_score, hist_word=st[:, :R], hist_parent=st[:, R:2 * R],
+                    hist_score=stf[:, 2 * R:3 * R], hist_attn=stf[:, 3 * R:].reshape(t_end, R, Tp))
+
+
+def speaker_beam_nodes(hist, B, beam_size):
+    """The device word loop's histories as the host loop's hypothesis nodes (frontier.speaker_beam_outputs): roots
+    0..B-1 (BOS, score 0), then node B + t*R + p for history position p of word step t.  Returns (done, P, W, S, rows)
+    with rows[node] the row of its attention in hist_attn.reshape(-1, Tp)."""
+    hw, hp, hs = hist['hist_word'], hist['hist_parent'], hist['hist_score']
+    t_end, R = hw.shape
+    t = np.arange(t_end, dtype=np.int64)[:, None]
+    hp64 = hp.astype(np.int64)
+    parent = np.where(t == 0, hp64 // beam_size, B + (t - 1) * R + hp64)
+    P = np.concatenate((np.full(B, -1, np.int64), parent.reshape(-1)))
+    W = np.concatenate((np.full(B, BOS, np.int64), hw.reshape(-1).astype(np.int64)))
+    S = np.concatenate((np.zeros(B, np.float32), hs.reshape(-1).astype(np.float32)))
+    rows = np.concatenate((np.full(B, -1, np.int64), (t * R + hp64).reshape(-1)))
+    n_done = hist['inst'][:, 1]
+    done = [[B + int(x) for x in hist['done_rec'][b, :n_done[b]]] for b in range(B)]
+    return done, P, W, S, rows
+
+
+@gc_paused
+def speaker_beam_search_device(speaker, beam_size, path_obs, path_actions, chunk=None, graphs=None):
+    """Seq2SeqSpeaker.beam_search (speaker.py:211-318) through DeviceSpeakerBeam: the same hypotheses in the same order
+    with the same scores, words and attentions as frontier.speaker_beam_search.  The DeviceSpeakerBeam (buffers and
+    captured graphs) is kept on the speaker per (decoder, batch, beam, words, chunk, graphs); `speaker.device_beam` is the
+    one used last (its host_reads / last_host_reads count the host synchronisations)."""
+    from . import frontier
+    chunk = speaker.beam_chunk if chunk is None else chunk
+    graphs = speaker.beam_graphs if graphs is None else graphs
+    start_obs, feats, acts, path_mask, _, _, perm = speaker._batch_observations_and_actions(path_obs, path_actions, None)
+    B = len(start_obs)
+    with torch.no_grad():
+        ctx, h_t, c_t = speaker.encoder(acts, feats)
+        key = (id(speaker.decoder), B, beam_size, speaker.instruction_len, int(chunk), bool(graphs))
+        cache = speaker.__dict__.setdefault('_device_beams', {})
+        db = cache.get(key)
+        if db is None or db.dec is not speaker.decoder:
+            if len(cache) >= 4:
+                cache.clear()
+            db = cache[key] = DeviceSpeakerBeam(speaker.decoder, B, beam_size, speaker.instruction_len, chunk, graphs)
+        speaker.device_beam = db
+        hist = db.run(ctx.detach().contiguous(), path_mask, h_t.detach(), c_t.detach())
+    done, P, W, S, rows = speaker_beam_nodes(hist, B, beam_size)
+    att = hist['hist_attn'].reshape(-1, hist['hist_attn'].shape[-1])
+    return frontier.speaker_beam_outputs(start_obs, perm, done, P, W, S, rows, beam_size,
+                                         lambda r: list(att[r]) if r else [], getattr(speaker.env, 'tokenizer', None))
 
 
 def beam_search(agent, beam_size, load_next_minibatch=True, mask_undo=False):
