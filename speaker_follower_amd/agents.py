@@ -419,10 +419,21 @@ class Seq2SeqAgent(BaseAgent):
         self.losses.append(float(self.loss.detach()) if torch.is_tensor(self.loss) else float(self.loss))
         return traj
 
+    SCORE_CHUNK = 256          # rows of one teacher-forced pass of an index-form scoring call (inference)
+    score_on_device = False    # True: observations with dense features are scored through the device pass as well
+
     def _score_obs_actions_and_instructions(self, path_obs, path_actions, encoded_instructions):
-        """follower.py:342-428: teacher-forced scoring of given paths."""
+        """follower.py:342-428: teacher-forced scoring of given paths.  Observations in index form (no 'feature' /
+        'action_embedding': an env that carries its feature store), or any with `score_on_device`, go through
+        _score_routes_on_device; dense ones through the per-step host loop below."""
         B = len(path_obs)
         assert len(path_actions) == B and len(encoded_instructions) == B
+        if self.score_on_device or 'feature' not in path_obs[0][0]:
+            store = self.store if self.store is not None else self._env_store()
+            if store is None:
+                raise RuntimeError('index-form observations need a features.FeatureStore (agent.store or '
+                                   'env.image_features_list[0].store)')
+            return self._score_routes_on_device(path_obs, path_actions, encoded_instructions, store)
         dev = self._device()
         seq, seq_mask, seq_lengths, perm = batch_instructions_from_encoded(
             encoded_instructions, self.max_instruction_length, reverse=self.reverse_instruction,
@@ -467,6 +478,77 @@ class Seq2SeqAgent(BaseAgent):
             if ended.all():
                 break
         return traj, loss
+
+    def _scoring_engine(self, store):
+        from .follower import FollowerEngine
+        eng = self.__dict__.get('_score_engine')
+        if eng is None or eng.store is not store or eng.encoder is not self.encoder or eng.decoder is not self.decoder:
+            eng = self._score_engine = FollowerEngine(self.encoder, self.decoder, store)
+            eng.dropout_seed = self._sample_seed ^ 0x1B873593
+        return eng
+
+    @gc_paused
+    def _score_routes_on_device(self, path_obs, path_actions, encoded_instructions, store):
+        """The same scoring as teacher-forced FollowerEngine passes over the routes in index form
+        (follower.route_index_batch).  Inference walks the rows in chunks of SCORE_CHUNK, in the caller's order, each
+        chunk over its own steps; every chunk is uploaded before the first is issued, so nothing waits for the device
+        until the ONE download of the actions, step scores, live flags, loss and fault words at the end.  The loss
+        (per step, the mean over the live rows of ALL chunks) is re-assembled from the chunks' (sum, count) tables.  With
+        autograd on, or in train mode, one unchunked pass whose loss backpropagates through the engine's backward.  A
+        starved persistent encoder launch re-issues the whole call on the per-step kernels (FollowerEngine.run).
+        `last_host_reads` counts the host synchronisations of the call."""
+        from .follower import DeviceFollowerBatch, route_index_batch, scored_route_outputs
+        from .runtime import fault_views, take_fault
+        B = len(path_obs)
+        eng, dev = self._scoring_engine(store), store.device
+        training = self.decoder.training
+        step = B if (training or torch.is_grad_enabled()) else self.SCORE_CHUNK
+        chunks = []
+        for lo in range(0, B, step):
+            hi = min(lo + step, B)
+            fb, S_k = route_index_batch(path_obs[lo:hi], path_actions[lo:hi], encoded_instructions[lo:hi], self.episode_len)
+            chunks.append((lo, hi, S_k, DeviceFollowerBatch.from_synth(fb, device=dev, max_length=self.max_instruction_length,
+                                                                       reverse=self.reverse_instruction, row0=lo)))
+        S = max(c[2] for c in chunks)
+
+        def issue():
+            out = torch.zeros(3, S, B, device=dev)                 # actions, step scores, live
+            total, last = None, None
+            for lo, hi, S_k, batch in chunks:
+                st = eng.rollout(batch, S_k, 'teacher', train=training, finalize=False)
+                out[0, :S_k, lo:hi] = st.actions
+                out[1, :S_k, lo:hi] = st.step_scores
+                out[2, :S_k, lo:hi] = st.live
+                if len(chunks) > 1:
+                    if total is None:
+                        total = torch.zeros(S, 2, device=dev)
+                    total[:S_k] += st.sum_cnt
+                if S_k == S and last is None:
+                    last = st
+            eng.finish(last, total)
+            faults = fault_views(dev)
+            flat = torch.cat([out.reshape(-1), last.loss_buf] + [f.to(torch.float32) for f in faults])
+            return last, flat.cpu()                                 # (the one host sync)
+
+        site, it = eng.site_next, eng.iteration
+        st, flat = issue()
+        reads = 1
+        if flat[3 * S * B + 1:].any():
+            take_fault(dev)                                         # (read and cleared)
+            eng.fallbacks += 1
+            keep = getattr(self.encoder, 'persistent', True)
+            self.encoder.persistent, eng.site_next, eng.iteration = False, site, it
+            try:
+                st, flat = issue()
+            finally:
+                self.encoder.persistent = keep
+            reads += 2
+            if flat[3 * S * B + 1:].any():
+                raise PersistentLaunchFault('the per-step re-issue of a route scoring pass raised a fault again')
+        self.last_host_reads = reads
+        res = flat[:3 * S * B].numpy().reshape(3, S, B)
+        traj = scored_route_outputs(path_obs, path_actions, res[0], res[1], res[2])
+        return traj, st.loss
 
     def test(self, use_dropout=False, feedback='argmax', allow_cheat=False, beam_size=1):
         """follower.py:987-999."""
@@ -859,6 +941,8 @@ class Seq2SeqSpeaker(object):
 
     def _batch_observations_and_actions(self, path_obs, path_actions, encoded_instructions):
         """speaker.py:68-121."""
+        if 'feature' not in path_obs[0][0]:
+            return self._batch_index_observations_and_actions(path_obs, path_actions, encoded_instructions)
         seq_lengths = np.array([len(a) for a in path_actions])
         Tp = int(seq_lengths.max())
         B = len(path_obs)
@@ -878,6 +962,44 @@ class Seq2SeqSpeaker(object):
         to = lambda x: torch.from_numpy(x).to(dev)  # noqa: E731
         return ([obs[0] for obs in path_obs], [to(f) for f in feats], [to(a) for a in acts],
                 to(mask), list(seq_lengths), encoded_instructions, list(range(B)))
+
+    def _batch_index_observations_and_actions(self, path_obs, path_actions, encoded_instructions):
+        """The same tensors from INDEX-FORM observations (what the beam search's encoder pass needs on an env that
+        carries its feature store): per path step the panorama and the chosen action's embedding gathered from the
+        store on the device (sf_gather_panorama, sf_gather_actions); padded steps are zero, as on the dense path."""
+        store = self._env_store()
+        if store is None:
+            raise RuntimeError('index-form observations need a features.FeatureStore (env.image_features_list[0].store '
+                               'or speaker.store)')
+        seq_lengths = np.array([len(a) for a in path_actions])
+        Tp, B = int(seq_lengths.max()), len(path_obs)
+        mask = np.ones((B, Tp), np.uint8)
+        vp, view, act_view = (np.zeros((Tp, B), np.int32) for _ in range(3))
+        act = np.zeros((Tp, B), np.int32)         # 1: candidate 1 of the [stop, chosen action] list gather_actions reads
+        heading, elevation = np.zeros((Tp, B), np.float64), np.zeros((Tp, B), np.float64)
+        for i, (obs, actions) in enumerate(zip(path_obs, path_actions)):
+            assert len(obs) == len(actions) + 1
+            mask[i, :len(actions)] = 0
+            for t, (ob, a) in enumerate(zip(obs[:-1], actions)):
+                assert a >= 0
+                vp[t, i], view[t, i] = ob['vp_row'], ob['viewIndex']
+                if a > 0:
+                    act[t, i] = 1
+                    d = ob['adj_loc_list'][a]
+                    act_view[t, i], heading[t, i], elevation[t, i] = d['absViewIndex'], d['rel_heading'], d['rel_elevation']
+        from .features import cand_sincos
+        dev = store.device
+        to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+        vp_d, view_d, av_d, act_d = to(vp), to(view), to(act_view), to(act)
+        sc_d = to(cand_sincos(heading, elevation))
+        pad = to(mask.T.astype(bool))
+        feats, acts = [], []
+        for t in range(Tp):
+            f = store.gather_panorama(vp_d[t], view_d[t])
+            feats.append(f.masked_fill_(pad[t][:, None, None], 0.0))
+            acts.append(store.gather_actions(vp_d[t], av_d[t], sc_d[t], act_d[t]))     # (action 0 / padding: zeros)
+        return ([obs[0] for obs in path_obs], feats, acts, to(mask), list(seq_lengths), encoded_instructions,
+                list(range(B)))
 
     def _env_store(self):
         feats = getattr(self.env, 'image_features_list', None) or [None]

@@ -114,6 +114,90 @@ class DeviceFollowerBatch:
                    target=dev(fb.target[:, sl], torch.int64), a_max=fb.a_max, row0=row0)
 
 
+def route_index_batch(path_obs, path_actions, encoded_instructions, episode_len, a_max=None):
+    """Given routes (follower.py:342-428's input) -> (synth.FollowerBatch with [S,B] grids, S) for a teacher-forced
+    FollowerEngine pass, in the host loop's layout: step t < len(actions) of row b stands at obs[t] with target
+    actions[t], later steps repeat the last of those observations with target -1.  S is the step at which the host loop
+    stops: every row has taken action 0 (its own stop, or the clamped -1 behind a route that ends without one), at most
+    `episode_len`.  Every distinct observation dictionary is read once (the candidate instructions of one route share
+    its observations, rational_speaker.py:54-69).  Raises ValueError on what the device pass cannot reproduce: an empty
+    route, an action outside the candidates, an action 0 before the last action (the engine latches `ended`,
+    csrc/sf_glue.h; the host loop goes on scoring the targets behind it)."""
+    from .synth import FollowerBatch
+    B = len(path_obs)
+    if len(path_actions) != B or len(encoded_instructions) != B:
+        raise ValueError('%d routes, %d action lists, %d instructions' % (B, len(path_actions), len(encoded_instructions)))
+    stop = np.empty(B, np.int64)                  # the step at which row b takes action 0
+    for b, (obs, acts) in enumerate(zip(path_obs, path_actions)):
+        m = len(acts)
+        if m == 0 or len(obs) < m:
+            raise ValueError('route %d: %d actions over %d observations' % (b, m, len(obs)))
+        z = next((t for t, a in enumerate(acts) if a == 0), m)
+        if z < m - 1 and z < episode_len - 1:
+            raise ValueError('route %d stops at step %d of %d: the device pass scores no target behind a stop' % (b, z, m))
+        stop[b] = z
+    S = int(min(episode_len, stop.max() + 1))
+    slot, distinct = {}, []
+    at = np.empty((S, B), np.int64)               # [S,B] -> index into `distinct`
+    target = np.full((S, B), -1, np.int64)
+    for b, (obs, acts) in enumerate(zip(path_obs, path_actions)):
+        m = len(acts)
+        for t in range(S):
+            ob = obs[min(t, m - 1)]
+            k = slot.get(id(ob))
+            if k is None:
+                k = slot[id(ob)] = len(distinct)
+                distinct.append(ob)
+            at[t, b] = k
+            if t < m:
+                target[t, b] = acts[t]
+    adj = [ob['adj_loc_list'] for ob in distinct]
+    n_adj = np.array([len(x) for x in adj], np.int32)
+    A = int(a_max or n_adj.max())
+    D = len(distinct)
+    d_vp, d_view = np.empty(D, np.int32), np.empty(D, np.int32)
+    d_cv = np.zeros((D, A), np.int32)
+    d_h, d_e = np.zeros((D, A), np.float64), np.zeros((D, A), np.float64)      # (sin / cos taken in float64, env.py:69-74)
+    for k, (ob, cands) in enumerate(zip(distinct, adj)):
+        d_vp[k], d_view[k] = ob['vp_row'], ob['viewIndex']
+        for a, d in enumerate(cands[1:], 1):
+            d_cv[k, a], d_h[k, a], d_e[k, a] = d['absViewIndex'], d['rel_heading'], d['rel_elevation']
+    a_num = n_adj[at]
+    bad = (target != -1) & ((target < 0) | (target >= a_num))
+    if bad.any():
+        t, b = np.argwhere(bad)[0]
+        raise ValueError('route %d, step %d: action %d of %d candidates' % (b, t, target[t, b], a_num[t, b]))
+    fb = FollowerBatch(instr=list(encoded_instructions), vp=d_vp[at], view=d_view[at], a_num=a_num,
+                       cand_view=d_cv[at], cand_heading=d_h[at], cand_elevation=d_e[at], target=target, a_max=A)
+    return fb, S
+
+
+def scored_route_outputs(path_obs, path_actions, actions, step_scores, live):
+    """follower.py:342-428's result dictionaries from a teacher-forced pass over route_index_batch's grids: actions,
+    step_scores, live [S,B] as the engine leaves them.  The host loop's bookkeeping: a row records steps up to and
+    including the first at which it takes action 0; 'trajectory' is the first observation, then the observation of
+    every recorded step (so the first one twice, and the repeated last one behind a route that ends without a stop);
+    'scores' are the step scores of live targets (0 for the clamped -1), 'score' their float32 running sum in step
+    order; 'observations' holds the first observation only."""
+    acts = np.asarray(actions).astype(np.int64)
+    sc = np.asarray(step_scores, np.float32) * np.asarray(live, np.float32)       # (score * live, :405)
+    S = acts.shape[0]
+    ss = np.add.accumulate(sc, axis=0, dtype=np.float32)                          # (sequential float32 sums)
+    is0 = acts == 0
+    last = np.where(is0.any(0), is0.argmax(0), S - 1).tolist()
+    acts_l, sc_l, ss_l = acts.T.tolist(), sc.T.tolist(), ss.T.tolist()
+    out = []
+    for b, (obs, pa) in enumerate(zip(path_obs, path_actions)):
+        k, m = last[b] + 1, len(pa)
+        o0 = obs[0]
+        steps = [o0] + [obs[t] for t in range(min(k, m))] + [obs[m - 1]] * max(0, k - m)
+        out.append({'instr_id': o0['instr_id'],
+                    'trajectory': [(ob['viewpoint'], ob['heading'], ob['elevation']) for ob in steps],
+                    'actions': acts_l[b][:k], 'scores': sc_l[b][:k], 'observations': [o0],
+                    'instr_encoding': o0['instr_encoding'], 'score': ss_l[b][k - 1]})
+    return out
+
+
 class RolloutState:
     """Everything one rollout keeps in HBM: per-step tapes and the glue outputs."""
     pass
