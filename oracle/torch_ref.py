@@ -1,18 +1,22 @@
-"""Oracle (test infrastructure): the hot path as differentiable torch-CPU fp32
-functions, so that autograd supplies the reference gradients for backward parity.
-See oracle/__init__.py for the rules.  Own code built from stock torch ops; each
+"""Oracle (test infrastructure): the hot path as differentiable torch-CPU functions,
+so that autograd supplies the reference gradients for backward parity.  See
+oracle/__init__.py for the rules.  Own code built from stock torch ops; each
 function cites the reference lines it restates (paths under /root/reference).
 
-Weights are dicts of torch tensors keyed like the reference state_dicts.
+Weights are dicts of torch tensors keyed like the reference state_dicts.  Every
+function computes in the dtype of the weights it is given: fp32 by default
+(`to_torch`), float64 with `to_torch(..., dtype=torch.float64)` -- the exact-arithmetic
+anchor the training-gradient tests measure both the HIP path and the fp32 reference
+against.  Inputs (features, masks) are cast to that dtype where they enter.
 """
 import torch
 import torch.nn.functional as F
 
 
-def to_torch(state, requires_grad=False, frozen=()):
+def to_torch(state, requires_grad=False, frozen=(), dtype=torch.float32):
     out = {}
     for k, v in state.items():
-        t = torch.tensor(v, dtype=torch.float32)
+        t = torch.tensor(v, dtype=dtype)
         if requires_grad and k not in frozen:
             t.requires_grad_(True)
         out[k] = t
@@ -57,31 +61,68 @@ def eltwise_prod_scoring(h, all_u, w_h, b_h, w_a, b_a, w_out, b_out):
     return F.linear(target * context, w_out, b_out).squeeze(2)
 
 
-def encoder_lstm(enc, seq, lengths, drop_ctx=None):
-    """model.py:81-104 with packed-sequence semantics written out (rows stop
-    advancing at their own length; ctx zero beyond).  drop_ctx: optional
-    multiplicative mask for the ctx dropout at :102 (GloVe path: no input dropout)."""
-    emb = enc['embedding.weight'][seq]
-    B = seq.shape[0]
-    H = enc['lstm.weight_hh_l0'].shape[1]
-    T = int(max(lengths))
-    lens = torch.as_tensor(lengths)
-    h = torch.zeros(B, H)
-    c = torch.zeros(B, H)
-    outs = []
-    for t in range(T):
-        h1, c1 = lstm_cell(emb[:, t], h, c, enc['lstm.weight_ih_l0'], enc['lstm.weight_hh_l0'],
-                           enc['lstm.bias_ih_l0'], enc['lstm.bias_hh_l0'])
+def _lstm_over(enc, emb, lens, sfx, reverse=False):
+    """One direction of the packed nn.LSTM (model.py:61-62, 89-90): rows advance over
+    their own length only -- forward from position 0, reverse from position len-1
+    down to 0 -- from a zero state (:68-79).  Returns (ctx [B,T,H] zero beyond a row's
+    length, final h, final c)."""
+    B, T = emb.shape[0], int(lens.max())
+    H = enc['lstm.weight_hh_l0' + sfx].shape[1]
+    h = torch.zeros(B, H, dtype=emb.dtype)
+    c = torch.zeros(B, H, dtype=emb.dtype)
+    outs = [None] * T
+    for t in (range(T - 1, -1, -1) if reverse else range(T)):
+        h1, c1 = lstm_cell(emb[:, t], h, c, enc['lstm.weight_ih_l0' + sfx], enc['lstm.weight_hh_l0' + sfx],
+                           enc['lstm.bias_ih_l0' + sfx], enc['lstm.bias_hh_l0' + sfx])
         live = (t < lens).unsqueeze(1)
         h = torch.where(live, h1, h)
         c = torch.where(live, c1, c)
-        outs.append(torch.where(live, h1, torch.zeros_like(h1)))
-    ctx = torch.stack(outs, dim=1)
+        outs[t] = torch.where(live, h1, torch.zeros_like(h1))
+    return torch.stack(outs, dim=1), h, c
+
+
+def _embed(enc, seq, drop_emb):
+    """model.py:84-87: the embedded tokens, and -- trainable embedding (glove=None) in
+    train mode -- their dropout; drop_emb: multiplicative mask [B, seq_len, E]."""
+    emb = enc['embedding.weight'][seq]
+    if drop_emb is not None:
+        emb = emb * drop_emb.to(emb.dtype)
+    return emb
+
+
+def encoder_lstm(enc, seq, lengths, drop_ctx=None, drop_emb=None):
+    """model.py:81-104 with packed-sequence semantics written out (rows stop
+    advancing at their own length; ctx zero beyond).  drop_ctx: optional
+    multiplicative mask for the ctx dropout at :102; drop_emb: the mask of the
+    embedded tokens (:86-87, trainable embedding only; GloVe: no input dropout)."""
+    emb = _embed(enc, seq, drop_emb)
+    ctx, h, c = _lstm_over(enc, emb, torch.as_tensor(lengths), '')
     decoder_init = torch.tanh(F.linear(h, enc['encoder2decoder.weight'],
                                        enc['encoder2decoder.bias']))
     if drop_ctx is not None:
-        ctx = ctx * drop_ctx
+        ctx = ctx * drop_ctx.to(ctx.dtype)
     return ctx, decoder_init, c
+
+
+def encoder_bilstm(enc, seq, lengths, drop_ctx=None, drop_emb=None):
+    """EncoderLSTM(bidirectional=True), model.py:47-66, 81-104: both directions over
+    the packed sequence; ctx = [forward | reverse] per position (pad_packed_sequence,
+    :101: zero beyond a row's length), h_t = cat(enc_h_t[-1], enc_h_t[-2]) -- the
+    REVERSE direction's final state first (:93-94), c_t likewise, decoder_init =
+    tanh(encoder2decoder(h_t)) (:99), then the ctx dropout (:102).  Masks as in
+    `encoder_lstm` (drop_ctx over the assembled [B,T,2H])."""
+    emb = _embed(enc, seq, drop_emb)
+    lens = torch.as_tensor(lengths)
+    ctx_f, h_f, c_f = _lstm_over(enc, emb, lens, '')
+    ctx_r, h_r, c_r = _lstm_over(enc, emb, lens, '_reverse', reverse=True)
+    ctx = torch.cat((ctx_f, ctx_r), 2)
+    h_t = torch.cat((h_r, h_f), 1)
+    c_t = torch.cat((c_r, c_f), 1)
+    decoder_init = torch.tanh(F.linear(h_t, enc['encoder2decoder.weight'],
+                                       enc['encoder2decoder.bias']))
+    if drop_ctx is not None:
+        ctx = ctx * drop_ctx.to(ctx.dtype)
+    return ctx, decoder_init, c_t
 
 
 def attn_decoder_step(dec, u_prev, all_u, visual_context, h0, c0, ctx, ctx_mask,
@@ -109,19 +150,24 @@ def attn_decoder_step(dec, u_prev, all_u, visual_context, h0, c0, ctx, ctx_mask,
 
 
 def follower_rollout(enc, dec, seq, lengths, ctx_mask, steps, step_inputs, targets,
-                     feedback, dims_feat, drop_masks=None):
+                     feedback, dims_feat, drop_masks=None, drop_emb=None):
     """follower.py:430-539 without the simulator (see oracle.np_model.follower_rollout).
-    drop_masks(t) -> (drop_in[B,2F], drop_h[B,H]) or None; drop_masks('ctx') -> [B,T,H]."""
+    drop_masks(t) -> (drop_in[B,2F], drop_h[B,H]) or None; drop_masks('ctx') -> [B,T,H].
+    drop_emb: the embedded tokens' mask [B,seq_len,E] (trainable embedding, model.py:86-87).
+    A bidirectional encoder (its state holds the `_reverse` weights) runs `encoder_bilstm`."""
     drop_ctx = drop_masks('ctx') if drop_masks else None
-    ctx, h, c = encoder_lstm(enc, seq, lengths, drop_ctx)
+    encode = encoder_bilstm if 'lstm.weight_ih_l0_reverse' in enc else encoder_lstm
+    ctx, h, c = encode(enc, seq, lengths, drop_ctx, drop_emb)
+    dt = ctx.dtype
     B = seq.shape[0]
-    u_prev = torch.zeros(B, dims_feat)
-    loss = torch.zeros(())
-    seq_scores = torch.zeros(B)
+    u_prev = torch.zeros(B, dims_feat, dtype=dt)
+    loss = torch.zeros((), dtype=dt)
+    seq_scores = torch.zeros(B, dtype=dt)
     ended = torch.zeros(B, dtype=torch.bool)
     logits, actions = [], []
     for t in range(steps):
         X, all_u, is_valid = (torch.as_tensor(a) for a in step_inputs(t))
+        X, all_u = X.to(dt), all_u.to(dt)
         d_in, d_h = drop_masks(t) if drop_masks else (None, None)
         h, c, alpha, logit, alpha_v = attn_decoder_step(dec, u_prev, all_u, X, h, c, ctx,
                                                         ctx_mask, d_in, d_h)
@@ -149,19 +195,21 @@ def follower_rollout(enc, dec, seq, lengths, ctx_mask, steps, step_inputs, targe
 def speaker_encoder(enc, action_embs, world_feats, drop_masks=None):
     """model.py:437-457.  drop_masks(t) -> mask for the concat input (:433);
     drop_masks('ctx') -> mask for :456."""
+    dt = enc['lstm.weight_hh'].dtype
     B = world_feats[0].shape[0]
     H = enc['lstm.weight_hh'].shape[1]
-    h = torch.zeros(B, H)
-    c = torch.zeros(B, H)
+    h = torch.zeros(B, H, dtype=dt)
+    c = torch.zeros(B, H, dtype=dt)
     hs = []
     p = 'visual_attention_layer.'
     for t, (a_emb, X) in enumerate(zip(action_embs, world_feats)):
+        a_emb, X = torch.as_tensor(a_emb).to(dt), torch.as_tensor(X).to(dt)
         feature, _ = visual_soft_dot_attention(
             h, X, enc[p + 'linear_in_h.weight'], enc[p + 'linear_in_h.bias'],
             enc[p + 'linear_in_v.weight'], enc[p + 'linear_in_v.bias'])
         concat = torch.cat((a_emb, feature), 1)
         if drop_masks:
-            concat = concat * drop_masks(t)
+            concat = concat * drop_masks(t).to(dt)
         h, c = lstm_cell(concat, h, c, enc['lstm.weight_ih'], enc['lstm.weight_hh'],
                          enc['lstm.bias_ih'], enc['lstm.bias_hh'])
         hs.append(h)
@@ -169,13 +217,16 @@ def speaker_encoder(enc, action_embs, world_feats, drop_masks=None):
                                        enc['encoder2decoder.bias']))
     ctx = torch.stack(hs, dim=1)
     if drop_masks:
-        ctx = ctx * drop_masks('ctx')
+        ctx = ctx * drop_masks('ctx').to(dt)
     return ctx, decoder_init, c
 
 
-def speaker_decoder_step(dec, prev_word, h0, c0, ctx, ctx_mask, drop_h=None):
-    """model.py:497-519, GloVe (no embedding dropout), non-att-feed branch."""
+def speaker_decoder_step(dec, prev_word, h0, c0, ctx, ctx_mask, drop_h=None, drop_emb=None):
+    """model.py:497-519, the non-att-feed branch.  drop_emb: the mask of the embedded
+    word (:499-500, trainable embedding only; GloVe: none); drop_h: dropout(h_1) (:516)."""
     emb = dec['embedding.weight'][prev_word]
+    if drop_emb is not None:
+        emb = emb * drop_emb.to(emb.dtype)
     h1, c1 = lstm_cell(emb, h0, c0, dec['lstm.weight_ih'], dec['lstm.weight_hh'],
                        dec['lstm.bias_ih'], dec['lstm.bias_hh'])
     h1_drop = h1 if drop_h is None else h1 * drop_h
@@ -186,18 +237,57 @@ def speaker_decoder_step(dec, prev_word, h0, c0, ctx, ctx_mask, drop_h=None):
     return h1, c1, alpha, logit
 
 
+def context_only_soft_dot_attention(h, context, mask, w_in):
+    """ContextOnlySoftDotAttention.forward, model.py:161-177."""
+    target = F.linear(h, w_in)
+    attn = torch.bmm(context, target.unsqueeze(2)).squeeze(2)
+    if mask is not None:
+        attn = attn.masked_fill(mask, float('-inf'))
+    attn = torch.softmax(attn, dim=1)
+    weighted = torch.bmm(attn.unsqueeze(1), context).squeeze(1)
+    return weighted, attn
+
+
+def speaker_decoder_step_att_feed(dec, prev_word, h0, c0, ctx, ctx_mask, drops=None):
+    """SpeakerDecoderLSTM.forward, the use_input_att_feed branch, model.py:497-513.
+    drops: None (eval mode) or the four masks (embedded word [B,E] or None for GloVe,
+    h_0 [B,H], h_tilde [B,H], cat(h_1, h_tilde) [B,2H]) of :500, :503, :504, :507."""
+    d_emb, d_h0, d_ht, d_x = drops if drops is not None else (None, None, None, None)
+    mul = lambda x, m: x if m is None else x * m.to(x.dtype)                # noqa: E731
+    emb = mul(dec['embedding.weight'][prev_word], d_emb)                    # :497-500
+    h_tilde, alpha = context_only_soft_dot_attention(mul(h0, d_h0), ctx, ctx_mask,
+                                                     dec['attention_layer.linear_in.weight'])  # :502-503
+    concat = torch.cat((emb, mul(h_tilde, d_ht)), 1)                        # :504
+    h1, c1 = lstm_cell(concat, h0, c0, dec['lstm.weight_ih'], dec['lstm.weight_hh'],
+                       dec['lstm.bias_ih'], dec['lstm.bias_hh'])            # :505
+    x = mul(torch.cat((h1, h_tilde), 1), d_x)                               # :506-507
+    x = torch.tanh(F.linear(x, dec['output_l1.weight'], dec['output_l1.bias']))   # :508-509
+    logit = F.linear(x, dec['decoder2action.weight'], dec['decoder2action.bias'])  # :510
+    return h1, c1, alpha, logit
+
+
 def speaker_score(enc, dec, action_embs, world_feats, path_mask, instr_seq, steps,
-                  feedback, pad_idx=0, bos_idx=3, eos_idx=2):
-    """speaker.py:135-197."""
-    ctx, h, c = speaker_encoder(enc, action_embs, world_feats)
+                  feedback, pad_idx=0, bos_idx=3, eos_idx=2, enc_drop=None, dec_drop=None):
+    """speaker.py:135-197.  Train mode: enc_drop as `speaker_encoder`'s drop_masks;
+    dec_drop(t) -> the masks of word step t: (drop_emb or None, drop_h) for the plain
+    decoder, the four of `speaker_decoder_step_att_feed` for an att-feed decoder (its
+    state holds `output_l1.weight`, model.py:475-481)."""
+    ctx, h, c = speaker_encoder(enc, action_embs, world_feats, enc_drop)
+    dt = ctx.dtype
+    att_feed = 'output_l1.weight' in dec
     B = ctx.shape[0]
     w_t = torch.full((B,), bos_idx, dtype=torch.long)
     ended = torch.zeros(B, dtype=torch.bool)
-    loss = torch.zeros(())
-    seq_scores = torch.zeros(B)
+    loss = torch.zeros((), dtype=dt)
+    seq_scores = torch.zeros(B, dtype=dt)
     words, logits = [], []
     for t in range(steps):
-        h, c, alpha, logit = speaker_decoder_step(dec, w_t, h, c, ctx, path_mask)
+        if att_feed:
+            h, c, alpha, logit = speaker_decoder_step_att_feed(
+                dec, w_t, h, c, ctx, path_mask, dec_drop(t) if dec_drop else None)
+        else:
+            d_emb, d_h = dec_drop(t) if dec_drop else (None, None)
+            h, c, alpha, logit = speaker_decoder_step(dec, w_t, h, c, ctx, path_mask, d_h, d_emb)
         target = instr_seq[:, t]
         if feedback == 'teacher':
             w_t = target

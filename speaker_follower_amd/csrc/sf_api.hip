@@ -814,7 +814,8 @@ static int decoder_tail_i(const sf_decoder_w* w, const sf_cands* U, int B, int H
         unsigned* tcount = af.tickets() ? af.tickets() + TEXT_TICKET : nullptr;
         float* part = (paired && B <= 1024) ? af.take(visual_attn_split_floats(B, F)) : nullptr;
         SmallPlan py, pq, pm;
-        bool ok = tpart && ybuf && zbuf && rext && (part || !paired) && tcount && B <= 256 && fm->m_v && fm->c_v && fm->m_a &&
+        bool ok = tpart && ybuf && zbuf && rext && (part || !paired) && tcount && B <= VIS_SPLIT_MAX_B && fm->m_v &&
+                  fm->c_v && fm->m_a &&
                   fm->c_a &&
                   plan_linear(tp->cat2 + H, 2 * H, tw->w_out + H, 2 * H, nullptr, B, H, H, EPI_NONE, ybuf, ldp, &py) == SF_OK;
         if (ok && !last_step) {
@@ -873,7 +874,7 @@ static int decoder_tail_i(const sf_decoder_w* w, const sf_cands* U, int B, int H
         unsigned* tcount = af.tickets() ? af.tickets() + TEXT_TICKET : nullptr;
         float* part = (paired && B <= 1024) ? af.take(visual_attn_split_floats(B, F)) : nullptr;
         SmallPlan py, pv, pta, pq, pr;
-        bool ok = tpart && ybuf && zbuf && (part || !paired) && tcount && B <= 256 &&
+        bool ok = tpart && ybuf && zbuf && (part || !paired) && tcount && B <= VIS_SPLIT_MAX_B &&
             plan_linear(tp->cat2 + H, 2 * H, tw->w_out + H, 2 * H, nullptr, B, H, H, EPI_NONE, ybuf, ldp, &py) == SF_OK &&
             plan_linear(tp->wt, D, w->action.w_a_t, D, nullptr, B, F, D, EPI_NONE, tp->r, F, &pr) == SF_OK;
         if (ok && !last_step) {
@@ -1468,7 +1469,11 @@ int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episo
     // stream, each behind the event of its own head.  The heads write only per-step tape slots and
     // their own arena region, so nothing is shared but the events.
     hipStream_t main_st = S(stream), side_st = S(e->side_stream);
-    const bool two = side_st && side_st != main_st && gtape->dh1d && gtape->dcat2 && gtape->ds;
+    // (up to VIS_SPLIT_MAX_B rows only: above it the tails take the un-split, un-paired visual-attention backward and
+    // the tails' share of the workspace -- the heads' region is split off below -- did not hold it: the call failed with
+    // SF_ERR_WORKSPACE at B = 300, while B = 256 fits.  The one-stream walk gets the whole workspace.)
+    const bool two = side_st && side_st != main_st && gtape->dh1d && gtape->dcat2 && gtape->ds &&
+                     e->B <= VIS_SPLIT_MAX_B;
     if (two) {
         SF_CHECK_ARG(e->ctx && dctx);
         std::vector<hipEvent_t>& ev = event_pool(e->S + 1);

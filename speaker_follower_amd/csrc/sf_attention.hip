@@ -1090,7 +1090,7 @@ bool visual_attn_f64_supported(const PanoSrc& src, int B) {
     const int F = src.IMG + src.LOC;
     return !(src.V > VIS_RPW * VIS_NW || src.V > 64 || F > VIS_CPL * 256 || (F & 3) ||
              (!src.dense && ((src.IMG & 3) || (src.LOC & 3)))) &&
-           src.V > (VSP_G - 1) * VSP_RPG && src.V <= VSP_G * VSP_RPG && B <= 256;
+           src.V > (VSP_G - 1) * VSP_RPG && src.V <= VSP_G * VSP_RPG && B <= VIS_SPLIT_MAX_B;
 }
 
 int visual_attn(int mode, const PanoSrc& src, int B, const float* vec, int ldvec, float* alpha,
@@ -1110,7 +1110,7 @@ int visual_attn(int mode, const PanoSrc& src, int B, const float* vec, int ldvec
     }
     // small batches: two workgroups per sample (see visual_attn_split_kernel)
     if (mode == 0 && split_part && split_counter && src.V > (VSP_G - 1) * VSP_RPG &&
-        src.V <= VSP_G * VSP_RPG && B <= 256) {
+        src.V <= VSP_G * VSP_RPG && B <= VIS_SPLIT_MAX_B) {
         SF_LAUNCH(visual_attn_split_kernel, dim3(VSP_G, B), dim3(VSP_NW * 64), 0, st, a,
                            VisSplit{split_part, split_counter, nullptr});
         return launch_status();
@@ -1199,7 +1199,7 @@ int pair_score_merge(const CandSrc& src, int B, int D, const float* r, const flo
     if (ldr <= 0) ldr = F;
     if (src.A > SC_NW || src.A < 1 || F > SC_CPL * 256 || (F & 3) || (!src.dense && ((src.IMG & 3) || (src.LOC & 15))))
         return SF_ERR_UNSUPPORTED;
-    if (!split_part || psrc.V <= (VSP_G - 1) * VSP_RPG || psrc.V > VSP_G * VSP_RPG || B > 256 || (ldo & 3))
+    if (!split_part || psrc.V <= (VSP_G - 1) * VSP_RPG || psrc.V > VSP_G * VSP_RPG || B > VIS_SPLIT_MAX_B || (ldo & 3))
         return SF_ERR_UNSUPPORTED;
     ScoreArgs a{src, ldr, cst, r, wt, b_a, b_out, D, g.logit, nullptr, nullptr, CeSrc{}};
     VisArgs va{psrc, nullptr, 0, alpha, out, ldo, drop, drop_col0};
@@ -1295,7 +1295,7 @@ int pair_vis_text(const PanoSrc& src, int B, const float* vec, int ldvec, float*
                   int L, int H, const float* t, int ldt, float* talpha, float* wc, int ldwc,
                   const int32_t* ctx_row, hipStream_t st) {
     const int F = src.IMG + src.LOC;
-    if (!split_part || src.V <= (VSP_G - 1) * VSP_RPG || src.V > VSP_G * VSP_RPG || B > 256 || F > VIS_CPL * 256 ||
+    if (!split_part || src.V <= (VSP_G - 1) * VSP_RPG || src.V > VSP_G * VSP_RPG || B > VIS_SPLIT_MAX_B || F > VIS_CPL * 256 ||
         (F & 3) || (!src.dense && ((src.IMG & 3) || (src.LOC & 3))) || (ldvec & 3) || (ldo & 3))
         return SF_ERR_UNSUPPORTED;
     if (H > TXT_CPL * 256 || (H & 3) || (ldt & 3) || (ldwc & 3) || L < 1 || L > SMALL_WAVES * 10)
@@ -1359,7 +1359,7 @@ int pair_vis_apro(const PanoSrc* src, int B, const float* vec, int ldvec, float*
     VisArgs va{};
     if (src) {
         const int F = src->IMG + src->LOC;
-        if (!split_part || src->V <= (VSP_G - 1) * VSP_RPG || src->V > VSP_G * VSP_RPG || B > 256 || F > VIS_CPL * 256 ||
+        if (!split_part || src->V <= (VSP_G - 1) * VSP_RPG || src->V > VSP_G * VSP_RPG || B > VIS_SPLIT_MAX_B || F > VIS_CPL * 256 ||
             (F & 3) || (!src->dense && ((src->IMG & 3) || (src->LOC & 3))) || (ldvec & 3))
             return SF_ERR_UNSUPPORTED;
         va = VisArgs{*src, vec, ldvec, nullptr, nullptr, 0, Dropout{}, 0};
@@ -1388,7 +1388,7 @@ int pair_vis_small(const PanoSrc& src, int B, const float* vec, int ldvec, float
     const bool wide = b.cpw == 2 && (b.mt == 1 || b.mt == 2 || b.mt == 4) && phase != 2;
     if (!wide && !(b.mt == 1 && (b.cpw == 8 || (phase == 2 && b.cpw == 4)))) return SF_ERR_UNSUPPORTED;
     if (!split_part || (phase == 0 && !split_counter) || src.V <= (VSP_G - 1) * VSP_RPG || src.V > VSP_G * VSP_RPG ||
-        B > 256 ||
+        B > VIS_SPLIT_MAX_B ||
         F > VIS_CPL * 256 || (F & 3) || (!src.dense && ((src.IMG & 3) || (src.LOC & 3))) ||
         (ldvec & 3) || (ldo & 3))
         return SF_ERR_UNSUPPORTED;

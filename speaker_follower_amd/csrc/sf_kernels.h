@@ -8,6 +8,12 @@
 
 namespace sf {
 
+// Largest batch of the split visual attention (two workgroups per sample, per-sample ticket counters) and of the
+// schedules built around it: the paired / folded decode steps and the two-stream backward through time
+// (sf_follower_episode_bwd_range).  Above it the un-split kernels run and those schedules fall back to one launch at a
+// time on one stream.
+constexpr int VIS_SPLIT_MAX_B = 256;
+
 // ---- sf_attention.hip ---------------------------------------------------------------------------
 // split_part / split_counter (optional): scratch ([visual_attn_split_floats] floats) and the
 // per-sample ticket counters that let the forward pass use two workgroups per sample.
