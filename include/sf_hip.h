@@ -1010,6 +1010,55 @@ int sf_nav_step(const sf_nav_table* nav, int B, const int32_t* row, const int32_
                 int32_t* a_num_next, int32_t* cand_view_next, float* sincos_next,
                 int64_t* target_next, sf_stream stream);
 
+/* The follower's beam selection for one decode step (follower.py:606-690), all instances at once, no host round trip:
+ * what search.DeviceFollowerBeam issues after sf_attn_decoder_fwd + sf_logprob_topk (n_valid = a_num) in its device
+ * step loop.  R = B * beam_size hypothesis slots; instance b owns slots b*beam_size .. b*beam_size + beam_size - 1, its
+ * live slots at the front of that block.  A slot's state is (row, view) of the navigation table `nav`,
+ * sid = row * V + view.  Per instance with inst[b] = (live, n_done, t), live > 0 and t < episode_len (else nothing
+ * changes -- steps issued after the search has ended are no-ops):
+ *   candidates  for the live slots i and ranks j < k: action top_a[i, j] with score[i] + top_lp[i, j] (float32 add);
+ *               top_a / top_lp are [R,k] rows of sf_logprob_topk (descending, ties lower column first).  The first
+ *               rank whose action is < 0 or >= a_num[sid] ends slot i's list (is_valid, follower.py:626);
+ *   selection   the beam_size best by score descending, then flat index i*k + j ascending; q = 0, 1, .. is the
+ *               selection order (the host loop's stable per-instance sort);
+ *   successor   of parent state psid under action a: nxt = next_row[psid, a]; the state stays psid when a == 0 or
+ *               nxt == psid / V, else it becomes nxt * V + cand_view[psid, a];
+ *   history     selection q goes to position base + p of step t: hist_parent (the slot i it extends, global),
+ *               hist_action, hist_rank (q), hist_sid (the new state), hist_psid (the parent's state), hist_score at
+ *               [t * ld_hist + base + p]; continuing selections (a != 0, t < episode_len - 1) take p = 0, 1, .. in
+ *               selection order, finals follow them in selection order; hist_attn (optional, with alpha [R,T])
+ *               receives alpha[i] at [t * ld_hist + i * T] for the live slots i.  Positions that hold no selection are
+ *               not written (the caller presets hist_action to -1 to tell them apart);
+ *   finals      appended to the instance's completion list done_rec / done_score [B, 2*beam_size] in selection order
+ *               at n_done, n_done + 1, .. as t * R + base + p;
+ *   next slots  slot base + p (p < live') = continuing selection p: row / view [2R] (entries [0, R): the slot's new
+ *               state; entries [R, 2R): its parent's state -- both halves are sf_nav_step's input, the second with
+ *               act [R] forms the previous action's embedding through sf_gather_actions_ld), parent (gather index of
+ *               its h / c: the slot i of step t) and score; live' = their number, 0 once n_done + finals >= beam_size
+ *               (follower.py:674); the other slots get act = 0, parent = -1, score = 0 and keep their (valid) state;
+ *               inst[b] = (live', n_done + finals, t + 1); live_total[t] += live' (the caller zeroes live_total).
+ * A slot's history position at step t is the slot it occupies at step t + 1.  No result of an instance depends on
+ * another instance's slots.
+ * SF_ERR_ARG on NULL pointers, k < 1, k > beam_size, k > nav.A, ld_hist < R (< R * T with hist_attn);
+ * SF_ERR_UNSUPPORTED for beam_size > 64 (one wavefront per instance, one lane per slot). */
+typedef struct sf_fol_beam {
+    int32_t B, beam_size, k, episode_len, T, reserved;
+    sf_nav_table nav;     /* a_num, next_row, cand_view, A, V are read */
+    float* score;         /* [R] running score of every slot */
+    int32_t *row, *view;  /* [2R] */
+    int32_t* act;         /* [R] the action that led to the slot's state (0: none, zero embedding) */
+    int32_t* parent;      /* [R] */
+    int32_t* inst;        /* [B,3] live, n_done, t */
+    int32_t* live_total;  /* [episode_len] */
+    int32_t *hist_parent, *hist_action, *hist_rank, *hist_sid, *hist_psid;
+    float *hist_score, *hist_attn;
+    int64_t ld_hist;      /* elements between steps of every history array */
+    int32_t* done_rec;    /* [B, 2*beam_size] */
+    float* done_score;    /* [B, 2*beam_size] */
+} sf_fol_beam;
+int sf_follower_beam_select(const sf_fol_beam* s, const int32_t* top_a, const float* top_lp, const float* alpha,
+                            sf_stream stream);
+
 /* In-process kernel timing (no reference counterpart; what bench.py's `roofline.kernels` table is
  * measured with).  Between sf_profile_begin() and sf_profile_end() every kernel ANY host thread of the
  * process launches through this library (torch runs backward() on its own thread) carries a start and a stop event on its own dispatch, so a

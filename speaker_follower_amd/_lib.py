@@ -153,6 +153,15 @@ class SpkBeam(C.Structure):
                                     'hist_score', 'hist_attn')] +
                 [('ld_hist', C.c_int64), ('done_rec', c_p), ('done_score', c_p)])
 
+
+class FolBeam(C.Structure):
+    """sf_fol_beam: state and history of the follower's device beam search (sf_follower_beam_select)."""
+    _fields_ = ([(n, C.c_int32) for n in ('B', 'beam_size', 'k', 'episode_len', 'T', 'reserved')] +
+                [('nav', NavTableS)] +
+                [(n, c_p) for n in ('score', 'row', 'view', 'act', 'parent', 'inst', 'live_total', 'hist_parent',
+                                    'hist_action', 'hist_rank', 'hist_sid', 'hist_psid', 'hist_score', 'hist_attn')] +
+                [('ld_hist', C.c_int64), ('done_rec', c_p), ('done_score', c_p)])
+
 i32, u32, i64p = C.c_int, C.c_uint32, C.c_void_p
 P = C.POINTER
 WS = [c_p, C.c_size_t, c_p]          # ws, ws_bytes, stream
@@ -256,6 +265,7 @@ _SIGNATURES = {
     'sf_scatter_rows': (C.c_int, [c_f, i32, c_p, i32, i32, c_f, i32, c_p]),
     'sf_logprob_topk': (C.c_int, [c_f, i32, i32, i32, c_p, i32, c_p, c_f, c_p]),
     'sf_speaker_beam_select': (C.c_int, [P(SpkBeam), c_p, c_f, c_f, c_p]),
+    'sf_follower_beam_select': (C.c_int, [P(FolBeam), c_p, c_f, c_f, c_p]),
     'sf_speaker_decoder_fwd': (C.c_int, [P(SpkDecoderW), i32, i32, i32, i32, i32, i64p, c_f, c_f,
                                          c_f, c_p, c_p, P(SpkDecoderTape), P(Dropout), u32] + WS),
     'sf_speaker_decoder_bwd': (C.c_int, [P(SpkDecoderW), P(SpkDecoderG), i32, i32, i32, i32, i32, i64p,

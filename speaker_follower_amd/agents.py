@@ -343,6 +343,16 @@ class Seq2SeqAgent(BaseAgent):
         beams, _, _ = self.beam_search(self.beam_size)
         return [beam[0] for beam in beams]
 
+    # beam_search with its step loop on the device (search.DeviceFollowerBeam: no host round trip per decode step, chunks
+    # of `beam_chunk` steps as replayed hipGraphs, or issued eagerly with beam_graphs = False).  Off by default.  Same
+    # results as the host loop up to the roundoff of a decoder step over other row counts; inference only;
+    # beam_size <= 64 -- wider beams run the host loop and count a fallback.
+    beam_on_device = False
+    beam_chunk = 2
+    beam_graphs = True
+    beam_fallbacks = 0
+    device_beam = None
+
     def beam_search(self, beam_size, load_next_minibatch=True, mask_undo=False):
         """follower.py:541-718 (search.py; needs `self.store` and index-form observations)."""
         from . import search

@@ -2042,6 +2042,20 @@ int sf_speaker_beam_select(const sf_spk_beam* s, const int32_t* top_w, const flo
     SF_CHECK_ARG(s->ld_hist >= R && (!s->hist_attn || s->ld_hist >= R * s->Tp));
     return speaker_beam_select(*s, top_w, top_lp, alpha, S(stream));
 }
+int sf_follower_beam_select(const sf_fol_beam* s, const int32_t* top_a, const float* top_lp, const float* alpha,
+                            sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(s && top_a && top_lp && s->B > 0 && s->beam_size > 0 && s->k >= 1 && s->k <= s->beam_size &&
+                 s->episode_len > 0 && s->T > 0);
+    SF_CHECK_ARG(s->nav.a_num && s->nav.next_row && s->nav.cand_view && s->nav.A > 0 && s->nav.V > 0 &&
+                 s->k <= s->nav.A);
+    SF_CHECK_ARG(s->score && s->row && s->view && s->act && s->parent && s->inst && s->live_total && s->hist_parent &&
+                 s->hist_action && s->hist_rank && s->hist_sid && s->hist_psid && s->hist_score && s->done_rec &&
+                 s->done_score && !s->hist_attn == !alpha);
+    const int64_t R = (int64_t)s->B * s->beam_size;
+    SF_CHECK_ARG(s->ld_hist >= R && (!s->hist_attn || s->ld_hist >= R * s->T));
+    return follower_beam_select(*s, top_a, top_lp, alpha, S(stream));
+}
 
 // ---- a9 SpeakerDecoderLSTM.forward (model.py:497-519) -----------------------------------------------------
 int sf_speaker_decoder_fwd(const sf_spk_decoder_w* w, int B, int E, int H, int Tp, int vocab,

@@ -198,9 +198,12 @@ int scatter_rows(const float* src, int lds, const int* idx, int n, int w, float*
                  hipStream_t st);
 int logprob_topk(float* logit, int ld, int N, int n, const int* n_valid, int k, int* idx,
                  float* logp, hipStream_t st);
-// ---- sf_beam.hip: the speaker's beam selection (sf_speaker_beam_select)
+// ---- sf_beam.hip: the beam selections; the speaker's (sf_speaker_beam_select)
 int speaker_beam_select(const sf_spk_beam& s, const int32_t* top_w, const float* top_lp, const float* alpha,
                         hipStream_t st);
+// the follower's (sf_follower_beam_select)
+int follower_beam_select(const sf_fol_beam& s, const int32_t* top_a, const float* top_lp, const float* alpha,
+                         hipStream_t st);
 
 // paired launches (see sf_attention.hip); SF_ERR_UNSUPPORTED = not pairable, launch separately
 struct SmallPlan;

@@ -421,9 +421,15 @@ def _setup(agent, load_next_minibatch, key_fields=4):
 def beam_search(agent, beam_size, load_next_minibatch=True, mask_undo=False):
     """Seq2SeqAgent.beam_search (follower.py:541-718): per instance the `beam_size` best partial paths are
     extended by their `beam_size` best actions each step; a path is complete when it stops or reaches the
-    episode length.  Returns (trajs, completed hypotheses per instance, None)."""
+    episode length.  Returns (trajs, completed hypotheses per instance, None).  mask_undo is accepted and ignored
+    (it has no effect in the reference either: follower.py:595-598).
+
+    `agent.tie_log` (a list; nothing is recorded unless the attribute is set): per step ('select', step, instances,
+    gaps) -- for every instance that dropped a successor, the float32 gap between its last kept and its first dropped
+    one -- and, from the final ranking, ('rank', instance, gaps between neighbouring completions)."""
     env, space, fd, t, frontier = _setup(agent, load_next_minibatch)
     assert env.beam_size >= beam_size
+    tie_log = getattr(agent, 'tie_log', None)
     B = len(space.items)
     done = [[] for _ in range(B)]                       # completed hypotheses in completion order
     n_done = np.zeros(B, np.int64)
@@ -440,7 +446,12 @@ def beam_search(agent, beam_size, load_next_minibatch=True, mask_undo=False):
         score = (t.score[par] + lp.astype(F32)).astype(F32)
         # per instance: best `beam_size` successors, ties in generation order (a stable descending sort)
         order = np.lexsort((np.arange(len(score)), -score, inst))
-        order = order[_first_k_per_group(inst[order], beam_size)]
+        kept = _first_k_per_group(inst[order], beam_size)
+        if tie_log is not None and len(order) > 1:
+            io, so = inst[order], score[order]
+            first_out = np.flatnonzero(~kept[1:] & kept[:-1] & (io[1:] == io[:-1])) + 1
+            tie_log.append(('select', step, io[first_out], so[first_out - 1] - so[first_out]))
+        order = order[kept]
         owner, act, par, inst, score = owner[order], act[order], par[order], inst[order], score[order]
         nsid, stay = space.successors(sid[owner], act)
         ids = t.append(score, t.start_pose[par] & stay, parent=par, inst=inst, sid=nsid,
@@ -454,11 +465,66 @@ def beam_search(agent, beam_size, load_next_minibatch=True, mask_undo=False):
         frontier = ids[keep]
         if len(frontier) == 0:
             break
+    return beam_outputs(fd, t, space, done, beam_size, agent.episode_len, tie_log)
+
+
+def beam_outputs(fd, t, space, done, beam_size, depth, tie_log=None):
+    """The results of the follower's beam search (follower.py:684-718), shared by the host step loop above and the
+    device one (search.beam_search_device): per instance the `beam_size` best of its completions `done[b]` (nodes of
+    `t` in completion order; a stable sort by score, so equal scores keep that order), their result dictionaries, and
+    the completions as hypothesis views.  fd: what answers `attention_rows(rows)` for the `pool` rows of `t`."""
     best = []
-    for lst in done:
+    for b, lst in enumerate(done):
         sc = t.score[lst]
-        best.append([lst[i] for i in np.lexsort((np.arange(len(lst)), -sc))[:beam_size]])
-    return _trajectories(fd, t, space, best, agent.episode_len), [HypList(t, space, lst) for lst in done], None
+        order = np.lexsort((np.arange(len(lst)), -sc))
+        if tie_log is not None and len(lst) > 1:
+            ranked = sc[order]
+            tie_log.append(('rank', b, ranked[:-1] - ranked[1:]))
+        best.append([lst[i] for i in order[:beam_size]])
+    return _trajectories(fd, t, space, best, depth), [HypList(t, space, lst) for lst in done], None
+
+
+class HistoryAttention:
+    """`attention_rows` over the downloaded attention history of the device step loop ([steps * R, T] on the host)."""
+
+    def __init__(self, att):
+        self.att = att
+
+    def attention_rows(self, rows):
+        return list(self.att[np.asarray(rows, np.int64)]) if len(rows) else []
+
+
+def hypotheses_from_history(space, hist, beam_size):
+    """The device step loop's history (include/sf_hip.h: sf_follower_beam_select; search.DeviceFollowerBeam.run) as the
+    host loop's hypothesis table, node for node: roots 0..B-1, then step after step the selections instance-major in
+    selection order.  hist: inst [B,3], done_rec [B, 2 beam], parent / action / rank / sid / psid / score [t_end, R]
+    (action -1 = the position holds no selection).  A node's `pool` is the row of its attention in the history
+    flattened to [t_end * R, T]: step * R + the parent's slot.  Returns (Hypotheses, done lists)."""
+    B = len(space.items)
+    t_end, R = hist['action'].shape
+    t = Hypotheses(cap=B + int((hist['action'] >= 0).sum()))
+    roots = t.append(np.zeros(B, F32), np.ones(B, bool), parent=-1, inst=np.arange(B), sid=space.root_sid,
+                     key=space.root_key, action=-1, count=0, pool=-1)
+    slot_node = np.full(R, -1, np.int64)                 # node in every slot of the coming step
+    slot_node[np.arange(B) * beam_size] = roots
+    node_at = np.full((t_end, R), -1, np.int64)          # node at every history position
+    for step in range(t_end):
+        pos = np.flatnonzero(hist['action'][step] >= 0)
+        pos = pos[np.argsort((pos // beam_size) * beam_size + hist['rank'][step, pos], kind='stable')]
+        par = slot_node[hist['parent'][step, pos]]
+        assert (par >= 0).all()
+        inst = pos // beam_size
+        nsid = hist['sid'][step, pos].astype(np.int64)
+        stay = nsid == hist['psid'][step, pos]           # (a move changes the nav row: StateSpace.successors)
+        ids = t.append(hist['score'][step, pos].astype(F32), t.start_pose[par] & stay, parent=par, inst=inst, sid=nsid,
+                       key=np.where(stay, t.key[par], space.key_of(nsid, inst)),
+                       action=hist['action'][step, pos].astype(np.int64), count=t.count[par] + 1,
+                       pool=step * R + hist['parent'][step, pos].astype(np.int64))
+        node_at[step, pos] = ids
+        slot_node = node_at[step]                        # a position at step t is the slot at step t + 1
+    flat = node_at.reshape(-1)
+    done = [flat[hist['done_rec'][b, :hist['inst'][b, 1]]].tolist() for b in range(B)]
+    return t, done
 
 
 # --------------------------------------------------------------------------------- state-factored search

@@ -758,9 +758,257 @@ def speaker_beam_search_device(speaker, beam_size, path_obs, path_actions, chunk
                                          lambda r: list(att[r]) if r else [], getattr(speaker.env, 'tokenizer', None))
 
 
+class DeviceFollowerBeam:
+    """The follower's beam search (follower.py:541-718) with its step loop on the device: R = B * beam_size fixed
+    hypothesis slots (instance b owns slots b*beam_size ..), per decode step
+
+        sf_nav_step over the slots' and their parents' states (candidate lists straight from the device navigation
+        table), the previous action's embedding from the parent's candidates (sf_gather_actions_ld), h / c of every slot
+        from its parent slot (sf_move_rows), AttnDecoderLSTM over all R rows (crow = the slot's instance; dead rows are
+        decoded and ignored), sf_logprob_topk (k = min(beam_size, A), n_valid = a_num), and sf_follower_beam_select:
+        the next states, parent slots and scores, the completed hypotheses, the history;
+
+    all issued on one stream without a host synchronisation.  A chunk of `chunk` steps is ONE replayed hipGraph; the host
+    reads the batch's live count once per chunk (4 bytes) and the history once at the end: at most
+    ceil(episode_len / chunk) + 1 reads per minibatch.  Steps issued after the search has ended change nothing, so every
+    chunk size gives the same history.  Instructions live in a [B, t_max] buffer (padding masked out), so the graph
+    outlives the minibatch; it is re-captured when a weight (or one of its cached layouts) moved.
+
+    Inference only; beam_size <= MAX_BEAM (one wavefront per instance in the selection kernel)."""
+    MAX_BEAM = 64
+    N_INT = 6                                     # history arrays besides the attention: parent action rank sid psid score
+
+    def __init__(self, decoder, store, nav, B, beam_size, episode_len, t_max, chunk=2, graphs=True):
+        if not self.supports(beam_size, decoder):
+            raise ValueError('DeviceFollowerBeam: beam_size %d > %d, or a decoder without visual attention'
+                             % (beam_size, self.MAX_BEAM))
+        dev = store.device
+        self.dec, self.store, self.nav, self.dev = decoder, store, nav, dev
+        self.B, self.beam, self.E, self.T, self.A = B, beam_size, episode_len, t_max, nav.A
+        self.chunk, self.graphs = max(1, int(chunk)), bool(graphs)
+        self.H = decoder.hidden_size
+        self.D = decoder.visual_attention_layer.linear_in_h.weight.shape[0]
+        self.k = min(beam_size, self.A)
+        R = self.R = B * beam_size
+        A, H, T = self.A, self.H, t_max
+        f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)           # noqa: E731
+        i32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.int32)             # noqa: E731
+        # slot state: (row, view) of the slots [0, R) and of their parents [R, 2R), previous action, parent slot, score
+        self.rv = i32(2, 2 * R)
+        self.act, self.parent, self.score = i32(R), i32(R), f32(R)
+        self.obs2 = dict(row=i32(2 * R), vp=i32(2 * R), view=i32(2 * R), a_num=i32(2 * R),
+                         cand_view=i32(2 * R, A), sincos=f32(2 * R, A, 4))
+        self.obs = [{k: v[j * R:(j + 1) * R] for k, v in self.obs2.items()} for j in range(2)]
+        self.h0, self.c0 = f32(R, H), f32(R, H)
+        self.tape = decoder_tape(R, H, store.F, self.D, store.V, T, A, dev)
+        for v in self.tape.values():
+            v.zero_()
+        self.idx = i32(R, self.k)
+        self.logp = f32(R, self.k)
+        self.crow = (torch.arange(R, device=dev, dtype=torch.int32) // beam_size).contiguous()
+        self.ctx = f32(B, T, H)
+        self.mask = torch.ones(B, T, dtype=torch.uint8, device=dev)
+        # the record: [inst B x 3 | live_total E | done_rec B x 2 beam | done_score B x 2 beam] then per step
+        # [parent R | action R | rank R | sid R | psid R | score R | attention R x T] -- one download at the end
+        self.o_live = 3 * B
+        self.o_done = self.o_live + episode_len
+        self.o_dscore = self.o_done + 2 * beam_size * B
+        self.hdr = (self.o_dscore + 2 * beam_size * B + 3) & ~3
+        self.S = R * (self.N_INT + T)
+        self.rec = i32(self.hdr + episode_len * self.S)
+        self.pin = torch.zeros(self.rec.numel(), dtype=torch.int32).pin_memory()
+        head0 = torch.zeros(self.hdr, dtype=torch.int32)
+        head0[0:3 * B:3] = 1                                           # one live slot per instance, nothing done, t = 0
+        self.head0 = head0.to(dev)
+        self.parent0 = torch.full((R,), -1, device=dev, dtype=torch.int32)
+        self.parent0[::beam_size] = torch.arange(0, R, beam_size, device=dev, dtype=torch.int32)
+        self.graph = self.baked = self._side = None
+        self.captures = 0
+        self.host_reads = self.last_host_reads = 0
+        self.minibatches, self.last_run_s = 0, 0.0          # (last_run_s: the step loop and its download, seconds)
+        self.last = None                                    # what the last run returned
+
+    @classmethod
+    def supports(cls, beam_size, decoder=None):
+        return 1 <= beam_size <= cls.MAX_BEAM and (decoder is None or hasattr(decoder, 'visual_attention_layer'))
+
+    def _struct(self):
+        R, base = self.R, self.rec.data_ptr()
+        steps = base + 4 * self.hdr
+        return _lib.FolBeam(self.B, self.beam, self.k, self.E, self.T, 0, self.nav.struct(),
+                            self.score.data_ptr(), self.rv[0].data_ptr(), self.rv[1].data_ptr(), self.act.data_ptr(),
+                            self.parent.data_ptr(), base, base + 4 * self.o_live,
+                            *(steps + 4 * j * R for j in range(self.N_INT + 1)), self.S,
+                            base + 4 * self.o_done, base + 4 * self.o_dscore)
+
+    def _issue(self, n_steps):
+        st, R, A, H = self.store, self.R, self.A, self.H
+        s = stream()
+        ns = self.nav.struct()
+        o = self.obs2
+        cur, par = self.obs
+        fb = self._struct()
+        ucand = st.cands(par['vp'], par['cand_view'], par['sincos'], par['a_num'], A)
+        pano = st.pano(cur['vp'], cur['view'])
+        cnd = st.cands(cur['vp'], cur['cand_view'], cur['sincos'], cur['a_num'], A)
+        w = decoder_w_struct(decoder_params(self.dec))
+        tp = tape_struct(self.tape)
+        gat = (_lib.RowMove * 2)(
+            _lib.RowMove(self.tape['h1'].data_ptr(), self.h0.data_ptr(), self.parent.data_ptr(), H, H, H, 0),
+            _lib.RowMove(self.tape['c1'].data_ptr(), self.c0.data_ptr(), self.parent.data_ptr(), H, H, H, 0))
+        for _ in range(n_steps):
+            call('sf_nav_step', byref(ns), 2 * R, ptr(self.rv[0]), ptr(self.rv[1]), None, None, None, 0, None,
+                 ptr(o['row']), ptr(o['vp']), ptr(o['view']), ptr(o['a_num']), ptr(o['cand_view']), ptr(o['sincos']),
+                 None, s)
+            # (the previous action's embedding straight into the first half of the LSTM input rows)
+            call('sf_gather_actions_ld', byref(ucand), R, ptr(self.act), ptr(self.tape['xin']), 2 * st.F, s)
+            call('sf_move_rows', gat, 2, R, s)
+            call('sf_attn_decoder_fwd', byref(w), byref(pano), byref(cnd), R, H, self.D, self.T,
+                 None, ptr(self.h0), ptr(self.c0), ptr(self.ctx), ptr(self.mask), ptr(self.crow), byref(tp), None,
+                 None, 0, *ws_args(self.dev))
+            call('sf_logprob_topk', ptr(self.tape['logit']), A, R, A, ptr(cur['a_num']), self.k, ptr(self.idx),
+                 ptr(self.logp), s)
+            call('sf_follower_beam_select', byref(fb), ptr(self.idx), ptr(self.logp), ptr(self.tape['alpha']), s)
+        self._keep = (ns, fb, ucand, pano, cnd, w, tp, gat)
+
+    def _capture(self):
+        # dead slots for the warm-up step (every instance ended: the selection changes nothing)
+        self.rec[:self.hdr].zero_()
+        self.rv.zero_()
+        self.act.zero_()
+        self.parent.fill_(-1)
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.dev)              # (one capture stream: its workspace is baked)
+            ensure_workspace(self._side, self.dev)
+        side = self._side
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.no_grad(), torch.cuda.stream(side):
+            self._issue(1)                                               # warm-up: cached layouts, lazy tables
+            side.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with graph_capture(graph, side):
+                self._issue(self.chunk)
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = graph
+        self.captures += 1
+
+    # ---- per minibatch
+    def run(self, ctx, mask, h, c, root_sid):
+        """One search over the encoder outputs (ctx [B,T',H], mask [B,T'], h / c [B,H]) from the start states root_sid
+        [B].  Returns host arrays: inst [B,3], done_rec / done_score [B, 2 beam], parent / action / rank / sid / psid
+        / score [t_end, R], attn [t_end, R, T] (views of one pinned buffer: valid until the next run)."""
+        t0 = time.perf_counter()
+        B, R, W = self.B, self.R, self.beam
+        Tm = ctx.shape[1]
+        if ctx.shape[0] != B or Tm > self.T:
+            raise ValueError('DeviceFollowerBeam built for %d instructions of <= %d tokens' % (B, self.T))
+        wb = bytes(decoder_w_struct(decoder_params(self.dec)))          # (also refreshes stale cached layouts in place)
+        if wb != self.baked:                                             # a weight (or its cached layout) moved
+            self.graph, self.baked = None, wb
+        if self.graphs and self.graph is None:
+            self._capture()
+        self.mask.fill_(1)
+        self.mask[:, :Tm].copy_(mask.to(torch.uint8))
+        self.ctx[:, :Tm].copy_(ctx)
+        self.tape['h1'].view(B, W, self.H)[:, 0].copy_(h)
+        self.tape['c1'].view(B, W, self.H)[:, 0].copy_(c)
+        sid = np.repeat(np.asarray(root_sid, np.int64), W)               # every slot starts on a valid state
+        rv0 = np.stack((np.tile(sid // 36, 2), np.tile(sid % 36, 2))).astype(np.int32)
+        self.rv.copy_(torch.from_numpy(rv0))
+        self.rec[:self.hdr].copy_(self.head0)
+        self.rec[self.hdr:].zero_()                                      # (nothing of an earlier search in the download)
+        self.rec[self.hdr:].view(self.E, self.S)[:, R:2 * R].fill_(-1)  # hist_action: -1 = no selection there
+        self.act.zero_()
+        self.parent.copy_(self.parent0)
+        self.score.zero_()
+        reads, issued = 0, 0
+        while issued < self.E:
+            if self.graphs:
+                self.graph.replay()
+            else:
+                self._issue(self.chunk)
+            issued += self.chunk
+            if issued >= self.E:
+                break
+            reads += 1
+            if int(self.rec[self.o_live + issued - 1].item()) == 0:     # nothing live after the chunk's last step
+                break
+        n = self.hdr + min(issued, self.E) * self.S
+        self.pin[:n].copy_(self.rec[:n], non_blocking=True)              # the one download of the results
+        torch.cuda.current_stream().synchronize()
+        reads += 1
+        self.last_host_reads = reads
+        self.host_reads += reads
+        self.minibatches += 1
+        self.last_run_s = time.perf_counter() - t0
+        flat = self.pin.numpy()
+        inst = flat[:3 * B].reshape(B, 3)
+        t_end = int(inst[:, 2].max())                                    # (the step after the last one any instance ran)
+        fl = flat.view(np.float32)
+        S, NI = self.S, self.N_INT
+        st = flat[self.hdr:self.hdr + t_end * S].reshape(t_end, S)
+        stf = fl[self.hdr:self.hdr + t_end * S].reshape(t_end, S)
+        out = dict(inst=inst, done_rec=flat[self.o_done:self.o_dscore].reshape(B, 2 * W),
+                   done_score=fl[self.o_dscore:self.o_dscore + 2 * W * B].reshape(B, 2 * W))
+        for j, name in enumerate(('parent', 'action', 'rank', 'sid', 'psid')):
+            out[name] = st[:, j * R:(j + 1) * R]
+        out['score'] = stf[:, (NI - 1) * R:NI * R]
+        out['attn'] = stf[:, NI * R:].reshape(t_end, R, self.T)
+        self.last = out
+        return out
+
+
+def follower_beam_for(agent, nav, B, beam_size, chunk, graphs):
+    """The agent's DeviceFollowerBeam for these sizes (buffers and captured graph; built on first use, kept on the
+    agent the way graph_step_for keeps its step)."""
+    t_max = agent.max_instruction_length
+    # (a captured step keeps the gate-product kernel it was captured with: runtime.strict_gate_product)
+    key = (id(agent.decoder), id(agent.store), id(nav), B, beam_size, agent.episode_len, t_max, int(chunk), bool(graphs),
+           int(_lib.lib.sf_gate_product_is_strict()))
+    cache = agent.__dict__.setdefault('_device_beams', {})
+    db = cache.get(key)
+    if db is None or db.dec is not agent.decoder or db.store is not agent.store or db.nav is not nav:
+        if len(cache) >= 4:
+            cache.clear()
+        db = cache[key] = DeviceFollowerBeam(agent.decoder, agent.store, nav, B, beam_size, agent.episode_len, t_max,
+                                             chunk, graphs)
+    return db
+
+
+@gc_paused
+def beam_search_device(agent, beam_size, load_next_minibatch=True, mask_undo=False, chunk=None, graphs=None):
+    """Seq2SeqAgent.beam_search (follower.py:541-718) through DeviceFollowerBeam: what frontier.beam_search returns,
+    assembled by the same code (frontier.beam_outputs) from the hypothesis table rebuilt out of the device history.
+    `agent.device_beam` is the DeviceFollowerBeam used last (its host_reads / last_host_reads count the host
+    synchronisations).  mask_undo is accepted and ignored, as in the host loop."""
+    from . import frontier, nav
+    chunk = agent.beam_chunk if chunk is None else chunk
+    graphs = agent.beam_graphs if graphs is None else graphs
+    env = agent.env
+    _require_store(agent)
+    env.reset(sort=True, beamed=True, load_next_minibatch=load_next_minibatch)
+    assert env.beam_size >= beam_size
+    items = list(env.batch)
+    table = nav.table_for(env, agent.store)
+    space = frontier.StateSpace(env, table, items)
+    ctx, seq_mask, h_t, c_t = _encode_items(agent, items)
+    with torch.no_grad():
+        db = follower_beam_for(agent, table, len(items), beam_size, chunk, graphs)
+        agent.device_beam = db
+        hist = db.run(ctx, seq_mask, h_t, c_t, space.root_sid)
+    t, done = frontier.hypotheses_from_history(space, hist, beam_size)
+    att = hist['attn'].reshape(-1, hist['attn'].shape[-1])
+    return frontier.beam_outputs(frontier.HistoryAttention(att), t, space, done, beam_size, agent.episode_len)
+
+
 def beam_search(agent, beam_size, load_next_minibatch=True, mask_undo=False):
-    """follower.py:541-718.  Returns (trajs, completed, traversed_lists=None)."""
+    """follower.py:541-718.  Returns (trajs, completed, traversed_lists=None).  With `agent.beam_on_device` the step loop
+    runs on the device (beam_search_device); a beam or decoder it cannot take runs the host loop and is counted."""
     from . import frontier
+    if getattr(agent, 'beam_on_device', False):
+        if DeviceFollowerBeam.supports(beam_size, agent.decoder):
+            return beam_search_device(agent, beam_size, load_next_minibatch, mask_undo)
+        agent.beam_fallbacks += 1
     return frontier.beam_search(agent, beam_size, load_next_minibatch, mask_undo)
 
 
