@@ -777,7 +777,15 @@ int sf_gather_rows(const float* src, int ld_src, const int32_t* idx, int n, int 
  * (ties: lower column first): idx [N,k] int32, logp [N,k] = log_softmax(logit)[row, idx].  k == n
  * returns the whole row sorted (follower.py:802).  idx == NULL (k == n required): no selection -- logp [N,n] =
  * log_softmax(logit) in COLUMN order, -inf beyond n_valid: what state_factored_search consumes (it walks every
- * successor of a state, follower.py:802-836). */
+ * successor of a state, follower.py:802-836).
+ * The order is the stable descending sort of the MASKED row.  Ranks past the finite columns therefore hold the
+ * remaining columns in ascending column order with logp = -inf -- the masked columns [n_valid, n) and valid columns
+ * whose logit is -inf alike; idx is always a column of [0, n), never -1.  A consumer ends a row's list at the first
+ * -inf (or, like sf_follower_beam_select, at the first column that is no candidate of the state).
+ * Columns [n, ld) are neither read nor written.  1 <= n_valid[row] is required and every row needs one finite valid
+ * column (n_valid is device data and is not checked; a row without one has no log_softmax -- the reference's is NaN
+ * there -- and its outputs are undefined).  SF_ERR_ARG for NULL logit / logp, N < 1, n < 1, ld < n, idx == NULL with
+ * k != n; SF_ERR_UNSUPPORTED for n > 1024, k < 1, k > n. */
 int sf_logprob_topk(float* logit, int ld, int N, int n, const int32_t* n_valid, int k, int32_t* idx,
                     float* logp, sf_stream stream);
 /* dst[idx[i], :width] = src[i, :width] (idx < 0: row i skipped): the h / c / attention rows of newly expanded
@@ -797,7 +805,10 @@ int sf_scatter_rows(const float* src, int ld_src, const int32_t* idx, int n, int
  *   history     selection q goes to position base + p of step t: hist_word / hist_parent (the slot i it extends,
  *               global) / hist_score at [t * ld_hist + base + p]; continuing selections (word != eos, t < T-1) take
  *               p = 0, 1, .. in selection order, finals follow them in selection order; hist_attn (optional, with
- *               alpha [R,Tp]) receives alpha[i] at [t * ld_hist + i * Tp] for the live slots i;
+ *               alpha [R,Tp]) receives row alpha[i] at [t * ld_hist + i * Tp] for every live slot of the step, i
+ *               being the GLOBAL slot b * beam_size + (the slot's place inside its instance) -- the row index of
+ *               alpha itself, not the place inside the instance -- so step t's attention rows form an [R,Tp] array
+ *               at t * ld_hist whose rows of dead slots are left untouched;
  *   finals      appended to the instance's completion list done_rec / done_score [B, 2*beam_size] in selection order
  *               at n_done, n_done + 1, .. as t * R + base + p (so history row t, position base + p);
  *   next slots  slot base + p (p < live') = continuing selection p: words (int64: the next prev_word), parent (gather

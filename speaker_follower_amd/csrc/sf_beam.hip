@@ -125,8 +125,9 @@ __global__ __launch_bounds__(BEAM_WAVE) void speaker_beam_select_kernel(sf_spk_b
 }
 
 // The follower's step.  A slot's state is (row, view) of the navigation table, sid = row * V + view; a successor list
-// ends at the first rank that is no candidate of the state (-1 from sf_logprob_topk, or an action >= a_num: the
-// is_valid filter of follower.py:626), so every list stays sorted and the merge above applies unchanged.
+// ends at the first rank that is no candidate of the state (an action >= a_num -- sf_logprob_topk returns the masked
+// columns as (column, -inf) behind the valid ones -- or a negative action: the is_valid filter of follower.py:626), so
+// every list stays sorted and the merge above applies unchanged.
 __global__ __launch_bounds__(BEAM_WAVE) void follower_beam_select_kernel(sf_fol_beam s, const int32_t* top_a,
                                                                          const float* top_lp, const float* alpha) {
     __shared__ int s_row[BEAM_WAVE], s_act[BEAM_WAVE], s_sid[BEAM_WAVE];

@@ -131,11 +131,11 @@ def history_alpha(hist, T):
 
 
 def topk_valid(lp, n_valid, k):
-    """sf_logprob_topk with n_valid: descending, ties lower column first, -1 / -inf past the valid columns."""
-    o = np.lexsort((np.arange(n_valid), -lp[:n_valid]))[:k]
-    idx, val = np.full(k, -1, np.int32), np.full(k, -np.inf, F32)
-    idx[:len(o)], val[:len(o)] = o, lp[o]
-    return idx, val
+    """sf_logprob_topk with n_valid (include/sf_hip.h): the stable descending sort of the masked row -- descending,
+    ties lower column first, and past the valid columns the masked ones in column order as (column, -inf)."""
+    masked = np.where(np.arange(len(lp)) < n_valid, lp, F32(-np.inf)).astype(F32)
+    o = np.lexsort((np.arange(len(lp)), -masked))[:k]
+    return o.astype(np.int32), masked[o]
 
 
 TT = 5                            # attention row width of the stand-in

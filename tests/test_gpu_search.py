@@ -312,6 +312,93 @@ def test_logprob_rows_in_column_order():
     assert rc == _lib.SF_ERR_ARG
 
 
+def _topk_edge_rows(rng, N, n, case):
+    """Rows of logits for the edges of sf_logprob_topk, moved by a constant BEFORE they are rounded to float32."""
+    shift = {'plus80': 80.0, 'minus80': -80.0, 'plus1e4': 1e4}.get(case, 0.0)
+    x = (rng.standard_normal((N, n)) * 3 + shift).astype(np.float32)
+    x[:, 1 % n] = x[:, 0]                                          # ties: lower column first
+    x[:, n - 1] = x[:, n // 2]
+    if n > 256:
+        x[:, 256 + 7] = x[:, 7]                                    # the same thread's next column
+        x[:, 64 + 9] = x[:, 9] = x.max(1) + np.float32(0.5)        # the row's best twice, in two wavefronts
+    if case == 'equal':
+        x[:] = np.float32(-2.5)                                    # a whole row equal: the order is 0, 1, 2, ...
+    if case == 'neg_inf':
+        gone = rng.random((N, n)) < 0.3
+        gone[:, 0] = False                                         # (n_valid >= 1: one finite valid column per row)
+        x[gone] = -np.inf
+    return x
+
+
+@pytest.mark.parametrize('case', ['plain', 'equal', 'neg_inf', 'plus80', 'minus80', 'plus1e4'])
+@pytest.mark.parametrize('n', [991, 1024])
+def test_logprob_topk_edges_against_a_stable_sort(n, case):
+    """sf_logprob_topk at n_valid in {1, 2, 63, 64, 65, n-1, n} (and without n_valid) for n = 991 / 1024, in the sorted
+    form at k = 40 and k = n and in the column-order form: the order is the stable descending sort of the MASKED row,
+    so once the finite columns run out the -inf columns -- masked ones and valid ones that hold -inf alike -- follow in
+    column order as (column, -inf); an index of -1 is never returned.  Columns [n_valid, n) are masked in place,
+    columns [n, ld) are left alone.  Values by the rule of tests/choice_models.py (float64 model, K x the float32
+    model's own error, floor 1e-5)."""
+    from tests import choice_models as CM
+    from speaker_follower_amd._lib import call
+    from speaker_follower_amd.runtime import ptr, stream
+    rng = np.random.default_rng([n, len(case)])
+    nvs = [1, 2, 63, 64, 65, n - 1, n]
+    N, ld = len(nvs), n + 8
+    x = _topk_edge_rows(rng, N, n, case)
+    full = np.full((N, ld), 7.25, np.float32)                     # columns [n, ld): not the kernel's to touch
+    full[:, :n] = x
+    for n_valid in (np.array(nvs, np.int32), None):
+        nv = torch.tensor(n_valid).cuda() if n_valid is not None else None
+        for k in (40, n):
+            masked, order, r, _ = CM.logprob_topk(x, n_valid, k, np.float64)
+            f = CM.logprob_topk(x, n_valid, k, np.float32)[2]
+            xin = torch.tensor(full).cuda()
+            idx = torch.full((N, k), -7, dtype=torch.int32, device='cuda')
+            logp = torch.full((N, k), 7.0, device='cuda')
+            call('sf_logprob_topk', ptr(xin), ld, N, n, ptr(nv) if nv is not None else None, k, ptr(idx), ptr(logp),
+                 stream())
+            torch.cuda.synchronize()
+            assert np.array_equal(idx.cpu().numpy(), order), (n, case, k)
+            out = xin.cpu().numpy()
+            assert np.array_equal(out[:, :n].view(np.int32), masked.view(np.int32))          # masked in place
+            assert np.array_equal(out[:, n:], full[:, n:])
+            CM.check_values('logprob_topk n %d %s k %d%s' % (n, case, k, '' if nv is None else ' n_valid'),
+                            logp.cpu().numpy(), r, f)
+            if case == 'equal' and n_valid is None:
+                assert np.array_equal(order, np.tile(np.arange(k, dtype=np.int32), (N, 1)))
+        # the column-order form (idx = NULL, k = n)
+        masked, _, _, r = CM.logprob_topk(x, n_valid, n, np.float64)
+        f = CM.logprob_topk(x, n_valid, n, np.float32)[3]
+        xin = torch.tensor(full).cuda()
+        out = torch.full((N, n), 7.0, device='cuda')
+        call('sf_logprob_topk', ptr(xin), ld, N, n, ptr(nv) if nv is not None else None, n, None, ptr(out), stream())
+        torch.cuda.synchronize()
+        CM.check_values('logprob_topk n %d %s column order%s' % (n, case, '' if nv is None else ' n_valid'),
+                        out.cpu().numpy(), r, f)
+        assert np.array_equal(xin.cpu().numpy()[:, :n].view(np.int32), masked.view(np.int32))
+        assert np.array_equal(xin.cpu().numpy()[:, n:], full[:, n:])
+
+
+def test_logprob_topk_rejects_what_it_does_not_define():
+    """The argument checks of the entry (n_valid itself is device data: 1 <= n_valid[row] is the caller's to keep,
+    include/sf_hip.h)."""
+    from speaker_follower_amd import _lib
+    from speaker_follower_amd.runtime import ptr, stream
+    x = torch.zeros(2, 1028, device='cuda')
+    idx = torch.zeros(2, 1028, dtype=torch.int32, device='cuda')
+    out = torch.zeros(2, 1028, device='cuda')
+    topk = _lib.lib.sf_logprob_topk
+    assert topk(ptr(x), 8, 2, 9, None, 3, ptr(idx), ptr(out), stream()) == _lib.SF_ERR_ARG             # ld < n
+    assert topk(ptr(x), 8, 0, 8, None, 3, ptr(idx), ptr(out), stream()) == _lib.SF_ERR_ARG             # no rows
+    assert topk(ptr(x), 8, 2, 0, None, 0, ptr(idx), ptr(out), stream()) == _lib.SF_ERR_ARG             # no columns
+    assert topk(None, 8, 2, 8, None, 3, ptr(idx), ptr(out), stream()) == _lib.SF_ERR_ARG
+    assert topk(ptr(x), 8, 2, 8, None, 3, ptr(idx), None, stream()) == _lib.SF_ERR_ARG
+    assert topk(ptr(x), 8, 2, 8, None, 9, ptr(idx), ptr(out), stream()) == _lib.SF_ERR_UNSUPPORTED     # k > n
+    assert topk(ptr(x), 8, 2, 8, None, 0, ptr(idx), ptr(out), stream()) == _lib.SF_ERR_UNSUPPORTED     # k < 1
+    assert topk(ptr(x), 1028, 2, 1025, None, 3, ptr(idx), ptr(out), stream()) == _lib.SF_ERR_UNSUPPORTED   # n > 1024
+
+
 def test_scatter_rows_kernel():
     from speaker_follower_amd._lib import call
     from speaker_follower_amd.runtime import ptr, stream

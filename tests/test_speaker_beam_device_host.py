@@ -2,9 +2,12 @@
 
 * frontier.speaker_beam_outputs -- the result assembly the host and device word loops share -- gives what the host
   loop's own tail gave before it was factored out, on synthetic hypotheses with exact score ties;
-* the device loop's history layout (include/sf_hip.h: sf_speaker_beam_select), produced by a step-by-step model of the
-  kernel and read back through search.speaker_beam_nodes, gives the host loop's results (frontier.speaker_beam_search
-  over a stand-in decoder whose log-probabilities are a function of the word history, with many ties);
+* the device loop's history layout (include/sf_hip.h: sf_speaker_beam_select), produced by a launch-by-launch numpy
+  model of the kernel (`model_step`, which tests/test_gpu_choice_kernels.py holds the kernel to bit for bit) and read
+  back through search.speaker_beam_nodes, gives the host loop's results (frontier.speaker_beam_search over a stand-in
+  decoder whose log-probabilities are a function of the word history, with many ties);
+* `model_step` gives what the one-function model it was taken out of gave, and the constructed inputs of the
+  kernel-alone test reach every case that test is there for (ties, EOS at once, a full completion list, short lists);
 * the new C entry rejects bad arguments before touching the device."""
 import ctypes as C
 import zlib
@@ -152,9 +155,126 @@ class FakeSpeaker:
                 list(range(self.B)))
 
 
+# ------------------------------------------------------------------------------------------ the kernel's model
+POISON = 0x7fc0dead              # an int32 pattern (a NaN as float32) for places the contract does not name
+
+
+def new_state(B, beam, T, Tp, eos=EOS, bos=BOS, with_attn=True, ld=None):
+    """The buffers of sf_spk_beam as DeviceSpeakerBeam presets them; every history array is [T, ld_hist] (ld_hist
+    defaults to the smallest the entry accepts) and filled with POISON, as are the completion lists."""
+    R = B * beam
+    ld = (R * Tp if with_attn else R) if ld is None else ld
+    poison = lambda *shape: np.full(shape, POISON, np.int32)                    # noqa: E731
+    s = dict(B=B, beam=beam, T=T, Tp=Tp, eos=eos, ld=ld,
+             score=np.zeros(R, F32), words=np.full(R, eos, np.int64), parent=np.full(R, -1, np.int32),
+             inst=np.zeros((B, 3), np.int32), live_total=np.zeros(T, np.int32),
+             hist_word=poison(T, ld), hist_parent=poison(T, ld), hist_score=poison(T, ld).view(F32),
+             hist_attn=poison(T, ld).view(F32) if with_attn else None,
+             done_rec=poison(B, 2 * beam), done_score=poison(B, 2 * beam).view(F32))
+    s['words'][::beam] = bos
+    s['parent'][::beam] = np.arange(0, R, beam)
+    s['inst'][:, 0] = 1
+    return s
+
+
+def model_step(s, top_w, top_lp, alpha, trace=None):
+    """One launch of sf_speaker_beam_select (include/sf_hip.h) on the buffers `s`, in place.  top_w int32 / top_lp
+    float32 [R, k] as sf_logprob_topk gives them; alpha [R, Tp], or None when the state keeps no attention history.
+    Returns [(b, successors)] of the instances that moved: the selections (score, flat index, slot i inside the
+    instance, word) that became the next step's slots base, base + 1, ..  trace (optional dict of counters): which
+    cases of the contract this launch went through."""
+    B, W, T, Tp, eos = s['B'], s['beam'], s['T'], s['Tp'], s['eos']
+    R, k = B * W, top_w.shape[1]
+    tr = trace if trace is not None else {}
+    bump = lambda name, n=1: tr.__setitem__(name, tr.get(name, 0) + n)          # noqa: E731
+    moved = []
+    for b in range(B):
+        live, n_done, t = (int(x) for x in s['inst'][b])
+        if live <= 0 or t >= T:
+            bump('noop')                                     # an ended instance: the launch changes nothing
+            continue
+        base = b * W
+        sc = (s['score'][base:base + live, None] + top_lp[base:base + live]).astype(F32).ravel()    # one float32 add
+        order = np.lexsort((np.arange(live * k), -sc.astype(np.float64)))      # score descending, then flat index i*k + j
+        cands = [(sc[n], int(n), int(n) // k, int(top_w[base + n // k, n % k])) for n in order[:W + 1]]
+        sel = cands[:W]
+        fin = [c[3] == eos or t == T - 1 for c in sel]
+        cont = [c for c, f in zip(sel, fin) if not f]
+        finals = [c for c, f in zip(sel, fin) if f]
+        for p, c in enumerate(cont + finals):
+            s['hist_word'][t, base + p], s['hist_parent'][t, base + p], s['hist_score'][t, base + p] = c[3], base + c[2], c[0]
+        for q, c in enumerate(finals):
+            s['done_rec'][b, n_done + q] = t * R + base + len(cont) + q
+            s['done_score'][b, n_done + q] = c[0]
+        if s['hist_attn'] is not None:                       # alpha[i] of the GLOBAL slot i = base + its place
+            s['hist_attn'][t, base * Tp:(base + live) * Tp] = np.asarray(alpha, F32)[base:base + live].ravel()
+        done_after = n_done + len(finals)
+        live_next = 0 if done_after >= W else len(cont)
+        moved.append((b, cont[:live_next]))
+        for p, c in enumerate(cont[:live_next]):
+            s['words'][base + p], s['parent'][base + p], s['score'][base + p] = c[3], base + c[2], c[0]
+        s['words'][base + live_next:base + W] = eos
+        s['parent'][base + live_next:base + W] = -1
+        s['score'][base + live_next:base + W] = 0
+        s['inst'][b] = live_next, done_after, t + 1
+        s['live_total'][t] += live_next
+        # ---- which cases this was
+        for x, y in zip(cands, cands[1:len(sel) + 1]):       # neighbours in the order, the first one selected
+            if x[0] == y[0]:
+                bump('tie_within_slot' if x[2] == y[2] else 'tie_across_slots')
+        if t == 0 and any(c[3] == eos for c in sel):
+            bump('eos_at_t0')
+        if t == T - 1 and any(c[3] != eos for c in sel):
+            bump('final_by_last_step')
+        if done_after >= W and cont:
+            bump('stopped_with_continuing_dropped')
+        if live * k < W and k < W:
+            bump('fewer_candidates_than_beam')
+        if np.isneginf(top_lp[base:base + live]).any():
+            bump('neg_inf_entry')
+        if any(np.isneginf(c[0]) for c in sel):
+            bump('neg_inf_selected')
+        if live_next == 0:
+            tr.setdefault('end_steps', set()).add(t)
+    return moved
+
+
+def history_of(s):
+    """The model's buffers as DeviceSpeakerBeam.run returns them (ld_hist at its minimum)."""
+    B, W, T, Tp = s['B'], s['beam'], s['T'], s['Tp']
+    R = B * W
+    t_end = int(s['inst'][:, 2].max())
+    return dict(inst=s['inst'].astype(np.int64), done_rec=s['done_rec'], done_score=s['done_score'],
+                hist_word=s['hist_word'][:t_end, :R], hist_parent=s['hist_parent'][:t_end, :R],
+                hist_score=s['hist_score'][:t_end, :R], hist_attn=s['hist_attn'][:t_end, :R * Tp].reshape(t_end, R, Tp))
+
+
 def device_model(B, beam, T):
-    """sf_speaker_beam_select step by step (include/sf_hip.h layout), the decoder replaced by lineage_logp; returns
-    what DeviceSpeakerBeam.run returns."""
+    """The device word loop: sf_speaker_beam_select launch by launch (`model_step`), the decoder replaced by
+    lineage_logp; returns what DeviceSpeakerBeam.run returns."""
+    R, k = B * beam, min(beam, VOCAB)
+    s = new_state(B, beam, T, TP)
+    lineage = {b * beam: (b,) for b in range(B)}                     # the word history of every live slot
+    for _ in range(T + 2):                                           # (launches past the end change nothing)
+        top_w, top_lp = np.full((R, k), EOS, np.int32), np.full((R, k), np.nan, F32)
+        alpha = np.full((R, TP), np.nan, F32)
+        cur = {}
+        for b in range(B):
+            for i in range(int(s['inst'][b, 0])):
+                r = b * beam + i
+                cur[r] = lineage[r] + (int(s['words'][r]),)
+                alpha[r] = lineage_alpha(cur[r])
+                top_w[r], top_lp[r] = topk(lineage_logp(cur[r]), k)
+        lineage = {}
+        for b, successors in model_step(s, top_w, top_lp, alpha):
+            for p, c in enumerate(successors):
+                lineage[b * beam + p] = cur[b * beam + c[2]]
+    return history_of(s)
+
+
+def device_model_whole(B, beam, T):
+    """The device word loop as ONE function, as it stood before `model_step` was taken out of it (verbatim): what
+    `device_model` has to reproduce."""
     R, k = B * beam, min(beam, VOCAB)
     inst = np.zeros((B, 3), np.int64)
     inst[:, 0] = 1
@@ -216,6 +336,28 @@ def test_device_history_layout_gives_the_host_loop_results(monkeypatch, B, beam,
     assert sum(len(x) for x in want) == B * beam
 
 
+@pytest.mark.parametrize('B,beam,T', [(3, 4, 6), (4, 5, 12), (2, 1, 5), (3, 12, 4)])
+def test_model_step_reproduces_the_whole_loop_model(B, beam, T):
+    """`model_step` driven launch by launch gives what the one-function model gave before it was split: every place the
+    contract names, bit for bit (the places it does not name hold the filler of either model and are left out)."""
+    got, want = device_model(B, beam, T), device_model_whole(B, beam, T)
+    assert np.array_equal(got['inst'], want['inst'])
+    assert got['hist_word'].shape == want['hist_word'].shape
+    named = want['hist_word'] != -7
+    assert np.array_equal(got['hist_word'] != POISON, named)
+    for key in ('hist_word', 'hist_parent'):
+        assert np.array_equal(got[key][named], want[key][named]), key
+    assert np.array_equal(got['hist_score'][named].view(np.int32), want['hist_score'][named].view(np.int32))
+    att = ~np.isnan(want['hist_attn'])
+    assert np.array_equal(got['hist_attn'].view(np.int32) != POISON, att)
+    assert np.array_equal(got['hist_attn'][att].view(np.int32), want['hist_attn'][att].view(np.int32))
+    for b in range(B):
+        n = int(want['inst'][b, 1])
+        assert np.array_equal(got['done_rec'][b, :n], want['done_rec'][b, :n])
+        assert np.array_equal(got['done_score'][b, :n].view(np.int32), want['done_score'][b, :n].view(np.int32))
+        assert (got['done_rec'][b, n:] == POISON).all()
+
+
 # ---- the C entry
 def _beam_struct(lib_mod, B=4, beam=8, k=8, T=10, Tp=5, eos=2, ld=None, nulls=()):
     R = B * beam
@@ -259,3 +401,78 @@ def test_beam_select_rejects_bad_arguments_without_gpu():
     assert sel(C.byref(s), dev, dev, dev, None) == 2
     s = _beam_struct(_lib, beam=65, k=66)
     assert sel(C.byref(s), dev, dev, dev, None) == 1
+
+
+# ---- constructed inputs of the kernel-alone test (tests/test_gpu_choice_kernels.py), checked here for what they reach
+VOC = 70                          # >= 64: k = beam_size at every beam the kernel takes
+SCENARIOS = ('to_the_last_step', 'eos_early', 'short_lists')
+
+
+def scenario_shape(name, B, beam, Tp=4):
+    """(k, T, with_attn, ld_hist) of a scenario: the attention history present and absent, ld_hist at and above its
+    minimum, k = beam_size and k < beam_size."""
+    R = B * beam
+    if name == 'to_the_last_step':
+        return min(beam, VOC), 5, True, R * Tp + 8
+    if name == 'eos_early':
+        return min(beam, VOC), 7, False, R
+    return max(1, min(beam - 1, 2)), 7, True, R * Tp
+
+
+def scenario_inputs(rng, s, k, name, step):
+    """top_w / top_lp / alpha of one launch on state `s`.  Live slots get what sf_logprob_topk gives for a row of coarse
+    log-probabilities (multiples of 0.5: the float32 sums tie exactly), some rows perturbed; dead slots get junk that
+    would win the selection if it were read."""
+    B, W, Tp, eos = s['B'], s['beam'], s['Tp'], s['eos']
+    R = B * W
+    top_w = rng.integers(0, VOC, (R, k)).astype(np.int32)
+    top_lp = (rng.standard_normal((R, k)) * 3 + 50).astype(F32)
+    alpha = rng.random((R, Tp)).astype(F32)
+    for b in range(B):
+        for i in range(int(s['inst'][b, 0]) if s['inst'][b, 2] < s['T'] else 0):
+            lp = (-0.5 * rng.integers(0, 4, VOC)).astype(F32)
+            if rng.random() < 0.3:
+                lp = (lp + rng.standard_normal(VOC).astype(F32) * F32(0.37)).astype(F32)
+            if name == 'to_the_last_step':
+                lp[eos] = F32(-60.0)                          # never among the best: the last step makes the finals
+            elif step <= 1:                                   # EOS the best word of every live slot of the even instances
+                lp[eos] = F32(0.5) if b % 2 == 0 else F32(-9.0)
+            else:
+                lp[eos] = F32(0.5 * rng.integers(0, 3)) if step >= 2 + b % 3 else F32(-9.0)
+            if name == 'short_lists' and (step + b + i) % 2 == 0:     # fewer finite words than k: -inf inside the list
+                gone = rng.permutation(VOC)[1 + (step + b) % k:]
+                lp[gone] = -np.inf
+            top_w[b * W + i], top_lp[b * W + i] = topk(lp, k)
+    return top_w, top_lp, alpha
+
+
+def scenario_expectations(trace, B, beam):
+    """What the scenarios of one (B, beam) must have reached, on the model's own trace."""
+    need = ['eos_at_t0', 'final_by_last_step', 'noop', 'neg_inf_entry'] if beam > 1 else ['eos_at_t0', 'final_by_last_step', 'noop']
+    if beam >= 3:
+        need += ['tie_across_slots', 'tie_within_slot', 'stopped_with_continuing_dropped', 'fewer_candidates_than_beam']
+    missing = [n for n in need if not trace.get(n)]
+    assert not missing, (B, beam, missing, trace)
+    if B > 1:
+        assert len(trace['end_steps']) > 1, 'every instance ended at the same step'
+
+
+@pytest.mark.parametrize('B,beam', [(1, 1), (1, 3), (64, 3), (1, 40), (5, 40), (1, 64), (3, 64)])
+def test_scenarios_reach_every_case_of_the_contract(B, beam):
+    """The model alone over the constructed inputs (the GPU test runs the same at B = 64 as well): every case the
+    kernel-alone test is there for is reached, and launches after the end leave every buffer as it was."""
+    trace = {}
+    for name in SCENARIOS:
+        rng = np.random.default_rng([B, beam, SCENARIOS.index(name)])
+        k, T, with_attn, ld = scenario_shape(name, B, beam)
+        s = new_state(B, beam, T, 4, with_attn=with_attn, ld=ld)
+        for step in range(T + 2):
+            before = {n: v.copy() for n, v in s.items() if isinstance(v, np.ndarray)}
+            ended = (s['inst'][:, 0] == 0).all()
+            top_w, top_lp, alpha = scenario_inputs(rng, s, k, name, step)
+            model_step(s, top_w, top_lp, alpha if with_attn else None, trace)
+            if ended:
+                assert all(np.array_equal(before[n].view(np.int32), s[n].view(np.int32)) for n in before)
+        assert (s['inst'][:, 0] == 0).all() and (s['inst'][:, 2] <= T).all()
+        assert ((s['inst'][:, 1] >= 1) & (s['inst'][:, 1] < 2 * beam)).all()
+    scenario_expectations(trace, B, beam)
