@@ -927,6 +927,42 @@ int sf_debug_cotenant(int blocks, int threads, int lds_bytes, long long ticks, f
  * this switch).  sf_gate_product_is_strict() reads it back. */
 void sf_gate_product_strict(int on);
 int sf_gate_product_is_strict(void);
+/* BF16 WEIGHT STORAGE for the LSTM gate product (supported runtime switch, opt-in, additive to ABI 9).
+ *
+ * Contract: with the switch on, for a REGISTERED weight pair and a SUPPORTED shape, the gate pre-activations that
+ * sf_lstm_cell_fwd, the decode step, the search step and sf_linear_slabs_fwd form are the fp32-accurate product of the
+ * UNROUNDED activations with bf16_rne(W_ih) and bf16_rne(W_hh) (round to nearest even, bit for bit what
+ * torch.Tensor.to(torch.bfloat16) gives): csrc/sf_gemm.hip: gemm_nt_bf16w_kernel reads each weight once per step as ONE
+ * bf16 plane (half the bytes of the fp32 rows), keeps the error-free three-way split of the activations, three
+ * v_mfma_f32_16x16x32_bf16 per product instead of six.  Biases, the cell and every other product are unchanged.  In every
+ * other case -- switch off (the default), pair not registered, shape not supported, strict switch on (it wins) -- the
+ * calls run exactly the kernels they run without this feature, bit for bit.  It is an INFERENCE mode: the backward
+ * entry points know nothing of it, so a pass whose gradients are wanted must run with the switch off.
+ *
+ *   sf_pack_bf16_bytes(rows, K)   size of the packed image of a [rows, K] matrix; 0 when K % 64 != 0 or a size is < 1.
+ *   sf_pack_bf16(w, ld, rows, K, out, stream)
+ *                                 rounds and packs w (fp32, leading dimension ld >= K, ld % 4 == 0, w and out 16-byte
+ *                                 aligned) into `out` on `stream`.  The layout is the library's own (opaque).  Call it again
+ *                                 (same buffer, in place) whenever the weights change.
+ *   sf_lstm_weights_bf16(w_ih, w_hh, packed_ih, packed_hh)
+ *                                 associates the fp32 weight ADDRESSES a call will be given (w_hh may be NULL for a product of
+ *                                 one segment) with their packed images; both packed pointers NULL forgets the pair.  A few
+ *                                 pairs (16) are remembered, under a mutex; SF_ERR_UNSUPPORTED when the table is full.
+ *                                 LIFETIME: the caller keeps both packed buffers alive, and their contents current, for as
+ *                                 long as the pair is registered and for as long as any captured hipGraph that ran with them
+ *                                 may replay -- the library stores the pointers only.
+ *   sf_gate_product_bf16_weights(on) / _is_on()
+ *                                 the process-wide switch.  A captured hipGraph keeps the kernels (and the packed pointers)
+ *                                 it was captured with, whatever the switch says at replay.
+ *   sf_gate_product_bf16_supported(M, K1, K2, N)
+ *                                 1 when the product x [M,K1] w [N,K1]^T + h [M,K2] u [N,K2]^T takes the bf16 kernel:
+ *                                 1 <= M <= 128, K1 > 0 and K1 % 64 == 0, K2 == 0 (no second segment) or K2 % 64 == 0, N >= 1. */
+size_t sf_pack_bf16_bytes(int rows, int K);
+int sf_pack_bf16(const float* w, int ld, int rows, int K, void* out, sf_stream stream);
+int sf_lstm_weights_bf16(const float* w_ih, const float* w_hh, const void* packed_ih, const void* packed_hh);
+void sf_gate_product_bf16_weights(int on);
+int sf_gate_product_bf16_weights_is_on(void);
+int sf_gate_product_bf16_supported(int M, int K1, int K2, int N);
 /* Older name of the same switch (tools/, A/B timing): on != 0 runs the large LSTM gate products (K >= 2048, M <= 128: sf_lstm_cell_fwd, the decode
  * step) on the fp32 MFMA (v_mfma_f32_16x16x4_f32, rounds 1-3) instead of the bf16 matrix cores with three-way
  * error-free operand splitting (csrc/sf_gemm.hip: gemm_nt_split_kernel; same fp32 accuracy class, measured closer

@@ -191,6 +191,12 @@ _SIGNATURES = {
     'sf_debug_cotenant': (C.c_int, [i32, i32, i32, C.c_longlong, c_f, c_p]),
     'sf_gate_product_strict': (None, [C.c_int]),
     'sf_gate_product_is_strict': (C.c_int, []),
+    'sf_pack_bf16_bytes': (C.c_size_t, [i32, i32]),
+    'sf_pack_bf16': (C.c_int, [c_f, i32, i32, i32, c_p, c_p]),
+    'sf_lstm_weights_bf16': (C.c_int, [c_f, c_f, c_p, c_p]),
+    'sf_gate_product_bf16_weights': (None, [C.c_int]),
+    'sf_gate_product_bf16_weights_is_on': (C.c_int, []),
+    'sf_gate_product_bf16_supported': (C.c_int, [i32, i32, i32, i32]),
     'sf_debug_tn_split_min_rows': (None, [C.c_int]),
     'sf_workspace_fault_offset': (C.c_size_t, [C.c_size_t]),
     'sf_debug_trace': (None, [C.c_void_p]),

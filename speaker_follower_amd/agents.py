@@ -136,6 +136,26 @@ class Seq2SeqAgent(BaseAgent):
         self.nav_table = nav_table
         self._engine = FollowerEngine(self.encoder, self.decoder, self.store)
         self._engine.dropout_seed = self._sample_seed ^ 0x1B873593
+        self._engine.gate_weights = self.gate_weights
+
+    # Weight storage of the decoder LSTM's gate product in INFERENCE passes: 'fp32' (default) or 'bf16' (FollowerEngine.
+    # gate_weights; include/sf_hip.h: sf_gate_product_bf16_weights).  Handed to every engine and search step the agent
+    # builds -- test on the device environment, beam_search, state_factored_search, route scoring; training passes ignore
+    # it.  The per-step host loop over the decoder MODULE (no store / device environment) is not covered.
+    _gate_weights = 'fp32'
+
+    @property
+    def gate_weights(self):
+        return self._gate_weights
+
+    @gate_weights.setter
+    def gate_weights(self, mode):
+        from .runtime import check_gate_weights
+        self._gate_weights = check_gate_weights(mode)
+        for name in ('_engine', '_score_engine'):
+            eng = self.__dict__.get(name)
+            if eng is not None:
+                eng.gate_weights = mode
 
     def _env_store(self):
         """The feature store the current env was built over (compat.env.MeanPooledImageFeatures.store), if any."""
@@ -158,6 +178,7 @@ class Seq2SeqAgent(BaseAgent):
         if self._engine is None:
             self._engine = FollowerEngine(self.encoder, self.decoder, self.store)
             self._engine.dropout_seed = self._sample_seed ^ 0x1B873593
+            self._engine.gate_weights = self.gate_weights
         return table_for(self.env, self.store)
 
     def _rollout_on_device(self, table=None, reissue=False):
@@ -209,6 +230,12 @@ class Seq2SeqAgent(BaseAgent):
 
     test_graph = True            # argmax inference rollouts on the device environment: one hipGraph replay per minibatch
 
+    def _test_graph_key(self, nav, eng, n_items):
+        """What tells the captured inference rollouts of `_rollout_on_graph` apart (a capture keeps its gate-product mode)."""
+        from .runtime import gate_mode_key
+        return (id(nav), id(eng), self.episode_len, n_items, self.max_instruction_length,
+                self.reverse_instruction) + gate_mode_key(eng.gate_weights)
+
     def _rollout_on_graph(self, nav, items, host=None):
         """An inference rollout (agent.test, follower.py:987-999) as ONE graph replay over a fixed-shape minibatch: the
         items are written into the captured batch's tensors (one pinned copy), the next minibatch is peeked and encoded
@@ -223,7 +250,7 @@ class Seq2SeqAgent(BaseAgent):
         from .nav import DeviceNavBatch
         from .runtime import take_fault, fault_views
         eng, dev = self._engine, self._device()
-        key = (id(nav), id(eng), self.episode_len, len(items), self.max_instruction_length, self.reverse_instruction)
+        key = self._test_graph_key(nav, eng, len(items))
         graphs = self.__dict__.setdefault('_test_graphs', {})  # (train.py alternates between its validation environments)
         S = self.episode_len
         # (key, items, weight versions): the replay the previous call issued ahead -- good for exactly these items under
@@ -495,6 +522,7 @@ class Seq2SeqAgent(BaseAgent):
         if eng is None or eng.store is not store or eng.encoder is not self.encoder or eng.decoder is not self.decoder:
             eng = self._score_engine = FollowerEngine(self.encoder, self.decoder, store)
             eng.dropout_seed = self._sample_seed ^ 0x1B873593
+            eng.gate_weights = self.gate_weights
         return eng
 
     @gc_paused

@@ -156,6 +156,27 @@ int data_grad(const float* dy, int lddy, const float* w, const float* w_t, int M
     return gemm_nn_ws(dy, lddy, w, K, M, K, N, dx, lddx, accumulate, ar.rest(), ar.rest_n(), st);
 }
 
+// ---- bf16 weight storage of the gate product (include/sf_hip.h: sf_gate_product_bf16_weights) ---------------------------
+std::atomic<int> g_bf16w_on{0};
+struct Bf16Pair { const float* w_ih; const float* w_hh; const void* p_ih; const void* p_hh; };
+constexpr int BF16_PAIRS = 16;
+Bf16Pair g_bf16_pairs[BF16_PAIRS];
+int g_bf16_npairs = 0;
+std::mutex g_bf16_mutex;
+
+// the packed images of (w_ih, w_hh) when the switch is on and the pair is registered; false: today's kernels
+bool bf16_packed(const float* w_ih, const float* w_hh, const void* (&packed)[2]) {
+    if (!g_bf16w_on.load(std::memory_order_relaxed) || sf::g_nt_force_f32) return false;
+    std::lock_guard<std::mutex> lock(g_bf16_mutex);
+    for (int i = 0; i < g_bf16_npairs; ++i)
+        if (g_bf16_pairs[i].w_ih == w_ih && g_bf16_pairs[i].w_hh == w_hh) {
+            packed[0] = g_bf16_pairs[i].p_ih;
+            packed[1] = g_bf16_pairs[i].p_hh;
+            return true;
+        }
+    return false;
+}
+
 // ---- a2 LSTMCell --------------------------------------------------------------------------------
 int lstm_fwd_i(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx, const float* h0,
                const float* c0, float* h1, float* c1, float* gates, float* h1_drop, int ld_h1_drop,
@@ -175,7 +196,9 @@ int lstm_fwd_i(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx,
     LinearOut o{};
     float* slabs = nullptr;
     int ks = 1;
-    TRY(linear_nt(segs, 2, B, 4 * H, o, ar.rest(), ar.rest_n(), st, &slabs, &ks));
+    const void* packed[2];
+    const bool bf16w = bf16_packed(w->w_ih, w->w_hh, packed);
+    TRY(linear_nt(segs, 2, B, 4 * H, o, ar.rest(), ar.rest_n(), st, &slabs, &ks, bf16w ? packed : nullptr));
     p.slabs = slabs; p.ks = ks;
     return lstm_pointwise_fwd(p, st);
 }
@@ -512,6 +535,35 @@ int sf_debug_cotenant(int blocks, int threads, int lds_bytes, long long ticks, f
 }
 void sf_gate_product_strict(int on) { sf::g_nt_force_f32 = on ? 1 : 0; }
 int sf_gate_product_is_strict(void) { return sf::g_nt_force_f32 != 0; }
+size_t sf_pack_bf16_bytes(int rows, int K) { return sf::pack_bf16_bytes(rows, K); }
+int sf_pack_bf16(const float* w, int ld, int rows, int K, void* out, sf_stream stream) {
+    SF_ENTER();
+    return sf::pack_bf16(w, ld, rows, K, out, S(stream));
+}
+int sf_lstm_weights_bf16(const float* w_ih, const float* w_hh, const void* packed_ih, const void* packed_hh) {
+    SF_CHECK_ARG(w_ih && (packed_ih || !packed_hh) && (!packed_ih || !w_hh == !packed_hh));
+    std::lock_guard<std::mutex> lock(g_bf16_mutex);
+    int at = -1;
+    for (int i = 0; i < g_bf16_npairs; ++i)
+        if (g_bf16_pairs[i].w_ih == w_ih && g_bf16_pairs[i].w_hh == w_hh) at = i;
+    if (!packed_ih) {                                           // forget the pair (unknown: nothing to do)
+        if (at >= 0) g_bf16_pairs[at] = g_bf16_pairs[--g_bf16_npairs];
+        return SF_OK;
+    }
+    if (at < 0) {
+        if (g_bf16_npairs == BF16_PAIRS) return SF_ERR_UNSUPPORTED;
+        at = g_bf16_npairs++;
+    }
+    g_bf16_pairs[at] = Bf16Pair{w_ih, w_hh, packed_ih, packed_hh};
+    return SF_OK;
+}
+void sf_gate_product_bf16_weights(int on) { g_bf16w_on.store(on ? 1 : 0, std::memory_order_relaxed); }
+int sf_gate_product_bf16_weights_is_on(void) { return g_bf16w_on.load(std::memory_order_relaxed); }
+int sf_gate_product_bf16_supported(int M, int K1, int K2, int N) {
+    if (K2 < 0) return 0;
+    const int K[2] = {K1, K2};
+    return sf::bf16w_supported(M, N, K, K2 ? 2 : 1) ? 1 : 0;
+}
 void sf_debug_fold_merge_with_glue(int on) { g_fold_merge_with_glue = on; }
 void sf_debug_fold_chain3(int on) { g_fold_chain3 = on; }
 void sf_debug_fold_build_overlap(int on) { g_fold_build_overlap = on; }
@@ -551,7 +603,9 @@ int sf_linear_slabs_fwd(const float* x, int ldx, const float* w, int K1, const f
     Seg segs[2] = {{x, ldx, w, K1, K1}, {h, ldh, u, K2, K2}};
     LinearOut o{};
     float* slabs = nullptr;
-    return linear_nt(segs, h ? 2 : 1, M, N, o, ar.rest(), ar.rest_n(), S(stream), &slabs, ksplit);
+    const void* packed[2];
+    const bool bf16w = bf16_packed(w, h ? u : nullptr, packed);
+    return linear_nt(segs, h ? 2 : 1, M, N, o, ar.rest(), ar.rest_n(), S(stream), &slabs, ksplit, bf16w ? packed : nullptr);
 }
 
 int sf_linear_bwd(const float* x, int ldx, const float* w, const float* y, int ldy, const float* dy,

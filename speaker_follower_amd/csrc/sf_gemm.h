@@ -50,8 +50,17 @@ int linear_ksplit(int M, int N, int Ktot);
 // y[M,N] = epi( sum_s A_s[M,K_s] * W_s[N,K_s]^T + bias (+bias2) ).  K_s % 4 == 0, lda/ldw % 4 == 0.
 // If `raw_slabs` is non-null the reduce pass is skipped and the caller receives the split-K
 // partial slabs ([ksplit][M][N]) -- used by the LSTM cell whose pointwise kernel reduces them.
+// `packed_w` (with raw_slabs only): per segment, the weight matrix as the packed bf16 image of pack_bf16.  When the shape
+// is bf16w_supported (and the strict fp32 switch is off) the product runs on gemm_nt_bf16w_kernel with those weights
+// instead of W_s; otherwise the argument is ignored.
 int linear_nt(const Seg* segs, int nseg, int M, int N, const LinearOut& out, float* ws,
-              size_t ws_floats, hipStream_t st, float** raw_slabs = nullptr, int* ksplit_out = nullptr);
+              size_t ws_floats, hipStream_t st, float** raw_slabs = nullptr, int* ksplit_out = nullptr,
+              const void* const* packed_w = nullptr);
+
+// bf16 weight storage of the gate product (include/sf_hip.h: sf_gate_product_bf16_weights)
+bool bf16w_supported(int M, int N, const int* K, int nseg);
+size_t pack_bf16_bytes(int rows, int K);                                                  // 0: K % 64 != 0 (or empty)
+int pack_bf16(const float* w, int ld, int rows, int K, void* out, hipStream_t st);        // rne, torch's float -> bfloat16
 
 // y[M,N] (+)= A[M,K] * W[K,N]      (W row-major [K,N]; N % 4 == 0; lda % 4 == 0, A zero-padded to K%4)
 int gemm_nn(const float* A, int lda, const float* W, int ldw, int M, int N, int K, float* y,

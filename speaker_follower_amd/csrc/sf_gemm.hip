@@ -397,16 +397,33 @@ __global__ __launch_bounds__(512) void gemm_nt_tiled_kernel(NtArgs a) {
 // the 160 KB at 112 rows).  The split + LDS stores of stage s+1 and the global loads of stage s+3 sit between
 // the MFMAs of stage s: one barrier per stage.  The K halves meet in LDS as in the fp32 kernel.
 // ------------------------------------------------------------------------------------------------
+//
+// BW (gemm_nt_bf16w_kernel, sf_gate_product_bf16_weights): the weight operand is ONE bf16 plane, rounded and packed once by
+// pack_bf16_kernel -- half the bytes of the fp32 rows and no split in the loop.  The activation side is the same error-free
+// three-way split, so a product is three MFMAs (a1 w into hi; a2 w, a3 w into lo) and equals the fp32-accurate product of
+// the unrounded activations with bf16(W).  Everything else -- block shape, stages, K splits, prefetch ring, epilogue -- is
+// the code below, shared.
+// ------------------------------------------------------------------------------------------------
 constexpr int SPL_ROWB = 128;             // bytes per row and plane (64 bf16)
 
-template <int MT>
-__global__ __launch_bounds__(512) void gemm_nt_split_kernel(NtArgs a) {
+// The packed bf16 weight image of one [rows, K] matrix (K % 64 == 0; rows padded with zeros to a multiple of 16):
+// [n-tile of 16 rows][64-deep stage][K half][lane = 16 kk + li][8 bf16].  The 16 bytes of lane (li, kk) are what that lane
+// feeds one v_mfma_f32_16x16x32_bf16 for row 16 tile + li: k = 32 half + 4 kk .. + 3 and 32 half + 16 + 4 kk .. + 3, the K
+// order of the activation planes in LDS.  A wave's fragment of a stage is one global_load_dwordx4 over 1 KB of whole lines.
+constexpr int BW_STAGE_BYTES = 2 * 64 * 16;          // per n-tile and stage
+struct NtPackedW {
+    const void* p[3];
+};
+
+template <int MT, bool BW>
+__device__ __forceinline__ void nt_split_body(const NtArgs a, const NtPackedW pk) {   // (by value: the code of <MT, false> stays what it was as a kernel)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
     constexpr int APASS = (MT + 1) / 2;                  // 32 rows x 16 float4 per staging pass
     constexpr int AROWS = APASS * 32;                    // (whole passes: every staging store is unconditional)
     constexpr int PLANE_A = AROWS * SPL_ROWB;
     constexpr int BUF = 3 * PLANE_A;                     // bytes per stage buffer (A only: W never touches LDS)
-    constexpr int NPIECE = APASS + 2;                    // loads per thread and stage: APASS of A, 2 of W
+    constexpr int NW = BW ? 1 : 2;                       // 16-byte loads of a W fragment (8 bf16, or 8 fp32)
+    constexpr int NPIECE = APASS + NW;                   // loads per thread and stage: APASS of A, NW of W
     const int tid = threadIdx.x, lane = tid & 63, wave8 = tid >> 6;
     const int wave = wave8 & 3, khalf = wave8 >> 2;      // n-tile of 16 columns, K-half of a stage
     const int li = lane & 15, kk = lane >> 4;
@@ -437,7 +454,7 @@ __global__ __launch_bounds__(512) void gemm_nt_split_kernel(NtArgs a) {
     // of 1-2 us under load.  Loads return in order, so "at most N newer loads outstanding" means this one has landed.
     struct Regs {
         f32x4 a[APASS];          // A: this thread's float4 of rows 32 p + ldrow (shared through LDS)
-        f32x4 w[2];              // W: THIS WAVE's fragment rows (n-tile, K-half), never shared: registers only
+        f32x4 w[NW];             // W: THIS WAVE's fragment rows (n-tile, K-half), never shared: registers only
     };
     struct StageSrc {
         const float* A;          // wave-uniform bases (SGPR pairs): the row offset travels in one VGPR
@@ -447,16 +464,18 @@ __global__ __launch_bounds__(512) void gemm_nt_split_kernel(NtArgs a) {
     // The segment of a stage is picked with mask arithmetic on values that sit in SGPRs: no branch (a stage's whole
     // body stays ONE basic block the scheduler can interleave), no load (a select of loaded values is turned into a
     // load from a selected address, i.e. a memory round trip at the head of every stage).
-    const unsigned long long pa0 = (unsigned long long)a.seg[0].A, pw0 = (unsigned long long)a.seg[0].W,
-                             pa1 = (unsigned long long)a.seg[1].A, pw1 = (unsigned long long)a.seg[1].W,
-                             pa2 = (unsigned long long)a.seg[2].A, pw2 = (unsigned long long)a.seg[2].W;
-    const unsigned lda0 = a.seg[0].lda, ldw0 = a.seg[0].ldw, lda1 = a.seg[1].lda, ldw1 = a.seg[1].ldw, lda2 = a.seg[2].lda,
-                   ldw2 = a.seg[2].ldw;
+    // (BW: the W base is the segment's packed image and `ldw` its stage count -- the stride of an n-tile in stages)
+    const unsigned long long pa0 = (unsigned long long)a.seg[0].A, pw0 = (unsigned long long)(BW ? pk.p[0] : a.seg[0].W),
+                             pa1 = (unsigned long long)a.seg[1].A, pw1 = (unsigned long long)(BW ? pk.p[1] : a.seg[1].W),
+                             pa2 = (unsigned long long)a.seg[2].A, pw2 = (unsigned long long)(BW ? pk.p[2] : a.seg[2].W);
+    const unsigned lda0 = a.seg[0].lda, ldw0 = BW ? st0n : a.seg[0].ldw, lda1 = a.seg[1].lda, ldw1 = BW ? st1n : a.seg[1].ldw,
+                   lda2 = a.seg[2].lda, ldw2 = BW ? st2n : a.seg[2].ldw;
     auto stage_src = [&](int s) {
         const unsigned long long m0 = s < st0n ? ~0ull : 0ull, m2 = s >= st0n + st1n ? ~0ull : 0ull, m1 = ~(m0 | m2);
         const int k0 = (s - (int)((unsigned)st0n & (unsigned)~m0) - (int)((unsigned)st1n & (unsigned)m2)) * TBK;
         return StageSrc{reinterpret_cast<const float*>((pa0 & m0) | (pa1 & m1) | (pa2 & m2)) + k0,
-                        reinterpret_cast<const float*>((pw0 & m0) | (pw1 & m1) | (pw2 & m2)) + k0,
+                        reinterpret_cast<const float*>((pw0 & m0) | (pw1 & m1) | (pw2 & m2)) +
+                            (BW ? (BW_STAGE_BYTES / 4 / TBK) * k0 : k0),
                         (int)((lda0 & (unsigned)m0) | (lda1 & (unsigned)m1) | (lda2 & (unsigned)m2)),
                         (int)((ldw0 & (unsigned)m0) | (ldw1 & (unsigned)m1) | (ldw2 & (unsigned)m2))};
     };
@@ -467,13 +486,17 @@ __global__ __launch_bounds__(512) void gemm_nt_split_kernel(NtArgs a) {
     // k = 4 kk .. 4 kk + 3 and 16 + 4 kk .. 16 + 4 kk + 3: a W fragment is then two 16-byte loads per lane whose 16-lane
     // groups read FULL 64-byte lines of a row (the straight 8-consecutive-k mapping reads half of every line twice).
     const int wrow = min(n0 + wave * 16 + li, a.N - 1);
+    const int wtile = min((n0 >> 4) + wave, ((a.N + 15) >> 4) - 1);  // BW: this wave's n-tile of the packed image
     auto gpiece = [&](Regs& r, const StageSrc& ss, int piece) {       // one global load of the staging set
         if (piece < APASS) {
             const int row = min(piece * 32 + ldrow, a.M - 1);
             gld(r.a[piece < APASS ? piece : 0], ss.A, (unsigned)(row * ss.lda + 4 * ldc4) * 4u);
         } else if (piece < NPIECE) {
             const int e = piece - APASS;
-            gld(r.w[e & 1], ss.W, (unsigned)(wrow * ss.ldw + 32 * khalf + 16 * e + 4 * kk) * 4u);
+            if constexpr (BW)
+                gld(r.w[0], ss.W, (unsigned)(wtile * ss.ldw) * (unsigned)BW_STAGE_BYTES + (unsigned)(khalf * 64 + lane) * 16u);
+            else
+                gld(r.w[e & 1], ss.W, (unsigned)(wrow * ss.ldw + 32 * khalf + 16 * e + 4 * kk) * 4u);
         }
     };
     // piece `piece` of `r` has landed once at most `newer` younger loads are outstanding
@@ -494,21 +517,36 @@ __global__ __launch_bounds__(512) void gemm_nt_split_kernel(NtArgs a) {
         *reinterpret_cast<uint2*>(d + 2 * PLANE_A) = p3;
     };
     struct BFrag {
-        bf16x8 p[3];
+        bf16x8 p[BW ? 1 : 3];
     };
     auto split_w = [&](const Regs& r, BFrag& f) {                     // this wave's W fragment of the next stage
-        uint2 x1, x2, x3, y1, y2, y3;
-        split3_f4(make_float4(r.w[0][0], r.w[0][1], r.w[0][2], r.w[0][3]), x1, x2, x3);
-        split3_f4(make_float4(r.w[1][0], r.w[1][1], r.w[1][2], r.w[1][3]), y1, y2, y3);
-        f.p[0] = __builtin_bit_cast(bf16x8, uint4{x1.x, x1.y, y1.x, y1.y});
-        f.p[1] = __builtin_bit_cast(bf16x8, uint4{x2.x, x2.y, y2.x, y2.y});
-        f.p[2] = __builtin_bit_cast(bf16x8, uint4{x3.x, x3.y, y3.x, y3.y});
+        if constexpr (BW) {
+            // packed: the 16 bytes ARE the fragment -- but COPIED out of the staging register by instructions of their own.
+            // A fragment that merely aliases it lets the register allocator give the reload (issued right behind this) a
+            // fresh register and move that one into place at the loop's back edge, i.e. read it before its load has landed.
+            f32x4 v;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float o;
+                const float i = r.w[0][c];
+                asm volatile("v_mov_b32 %0, %1" : "=v"(o) : "v"(i));
+                v[c] = o;
+            }
+            f.p[0] = __builtin_bit_cast(bf16x8, v);
+        } else {
+            uint2 x1, x2, x3, y1, y2, y3;
+            split3_f4(make_float4(r.w[0][0], r.w[0][1], r.w[0][2], r.w[0][3]), x1, x2, x3);
+            split3_f4(make_float4(r.w[1][0], r.w[1][1], r.w[1][2], r.w[1][3]), y1, y2, y3);
+            f.p[0] = __builtin_bit_cast(bf16x8, uint4{x1.x, x1.y, y1.x, y1.y});
+            f.p[1] = __builtin_bit_cast(bf16x8, uint4{x2.x, x2.y, y2.x, y2.y});
+            f.p[2] = __builtin_bit_cast(bf16x8, uint4{x3.x, x3.y, y3.x, y3.y});
+        }
     };
     const int fchunk = 4 * khalf + kk;
     auto frag = [&](const unsigned char* plane, int row) {
         return *reinterpret_cast<const bf16x8*>(plane + row * SPL_ROWB + (((fchunk ^ (row >> 1)) & 7) << 4));
     };
-    // One stage: 6 MT MFMAs on buffer `buf` with the W fragment `bc`.  `rs` holds the raw operands of the NEXT stage:
+    // One stage: 6 MT (BW: 3 MT) MFMAs on buffer `buf` with the W fragment `bc`.  `rs` holds the raw operands of the NEXT stage:
     // its A pieces are split into LDS buffer `sbuf`, its W pieces into the fragment `bn`, and every register is
     // reloaded with its piece of stage `s_next` right behind its use.
     auto compute = [&](int buf, const BFrag& bc, Regs& rs, BFrag& bn, int s_next, int sbuf) {
@@ -523,13 +561,13 @@ __global__ __launch_bounds__(512) void gemm_nt_split_kernel(NtArgs a) {
                 spiece_a(rs, sbuf, t);
             } else if (t == APASS) {
                 SPL_LANDED(rs.w[0], NPIECE + APASS);
-                SPL_LANDED(rs.w[1], NPIECE + APASS);
+                SPL_LANDED(rs.w[NW - 1], NPIECE + APASS);
                 split_w(rs, bn);
             }
         };
         auto stage_work_b = [&](int t) {
             if (t < APASS) gpiece(rs, ss, t);
-            else if (t == APASS) { gpiece(rs, ss, APASS); gpiece(rs, ss, APASS + 1); }
+            else if (t == APASS) { gpiece(rs, ss, APASS); gpiece(rs, ss, APASS + 1); }   // (BW: piece APASS + 1 does not exist)
         };
         // Tiles go in PAIRS with their MFMAs interleaved (consecutive MFMAs never share an accumulator) and the
         // fragments of the next pair are requested before the current pair's MFMAs are issued.
@@ -553,17 +591,23 @@ __global__ __launch_bounds__(512) void gemm_nt_split_kernel(NtArgs a) {
 #define SPL_MM(acc, t, pa, pb) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[pr][(t) - t0][pa], bc.p[pb], acc[t], 0, 0, 0)
             SPL_MM(lo, t0, 2, 0);
             if (two) SPL_MM(lo, t1, 2, 0);
-            SPL_MM(lo, t0, 0, 2);
-            if (two) SPL_MM(lo, t1, 0, 2);
+            if constexpr (!BW) {
+                SPL_MM(lo, t0, 0, 2);
+                if (two) SPL_MM(lo, t1, 0, 2);
+            }
             stage_work_a(t0);
-            SPL_MM(lo, t0, 1, 1);
-            if (two) SPL_MM(lo, t1, 1, 1);
+            if constexpr (!BW) {
+                SPL_MM(lo, t0, 1, 1);
+                if (two) SPL_MM(lo, t1, 1, 1);
+            }
             SPL_MM(lo, t0, 1, 0);
             if (two) SPL_MM(lo, t1, 1, 0);
             stage_work_b(t0);
             if (two) stage_work_a(t1);
-            SPL_MM(lo, t0, 0, 1);
-            if (two) SPL_MM(lo, t1, 0, 1);
+            if constexpr (!BW) {
+                SPL_MM(lo, t0, 0, 1);
+                if (two) SPL_MM(lo, t1, 0, 1);
+            }
             SPL_MM(hi, t0, 0, 0);
             if (two) SPL_MM(hi, t1, 0, 0);
             if (two) stage_work_b(t1);
@@ -571,7 +615,7 @@ __global__ __launch_bounds__(512) void gemm_nt_split_kernel(NtArgs a) {
         }
         if (MT <= APASS) {                                            // (MT = 1: the W pieces did not fit above)
             SPL_LANDED(rs.w[0], NPIECE + APASS);
-            SPL_LANDED(rs.w[1], NPIECE + APASS);
+            SPL_LANDED(rs.w[NW - 1], NPIECE + APASS);
             split_w(rs, bn);
             gpiece(rs, ss, APASS);
             gpiece(rs, ss, APASS + 1);
@@ -598,7 +642,7 @@ __global__ __launch_bounds__(512) void gemm_nt_split_kernel(NtArgs a) {
             spiece_a(ra, 0, piece);
         }
         SPL_LANDED(ra.w[0], NPIECE);
-        SPL_LANDED(ra.w[1], NPIECE);
+        SPL_LANDED(ra.w[NW - 1], NPIECE);
         split_w(ra, b0);
         gload(ra, min(s_lo + 2, last));
         __syncthreads();
@@ -646,6 +690,43 @@ __global__ __launch_bounds__(512) void gemm_nt_split_kernel(NtArgs a) {
                 *o = (a.accumulate && a.ksplit == 1) ? *o + v : v;
             }
         }
+}
+
+template <int MT>
+__global__ __launch_bounds__(512) void gemm_nt_split_kernel(NtArgs a) {
+    nt_split_body<MT, false>(a, NtPackedW{});
+}
+
+template <int MT>
+__global__ __launch_bounds__(512) void gemm_nt_bf16w_kernel(NtArgs a, NtPackedW pk) {
+    nt_split_body<MT, true>(a, pk);
+}
+
+// fp32 [rows, K] (leading dimension ld) -> the packed bf16 image above: one thread per lane fragment (two float4 in,
+// 16 bytes out).  Round to nearest even on the bit pattern, the arithmetic of torch's float -> bfloat16 conversion
+// (subnormals are rounded like any other value, a NaN becomes the quiet NaN 0x7FC0); rows past `rows` are zeros.
+__device__ __forceinline__ unsigned bf16_rne_bits(float f) {
+    const unsigned u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+__global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict__ w, int ld, int rows, int K,
+                                                        uint4* __restrict__ out, unsigned total) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;      // = ((tile * stages + stage) * 2 + half) * 64 + lane
+    if (i >= total) return;
+    const unsigned lane = i & 63u, half = (i >> 6) & 1u, ts = i >> 7;
+    const unsigned stages = (unsigned)K / TBK, tile = ts / stages, stage = ts % stages;
+    const unsigned row = tile * 16u + (lane & 15u), k = stage * TBK + half * 32u + 4u * (lane >> 4);
+    uint4 o = make_uint4(0u, 0u, 0u, 0u);
+    if (row < (unsigned)rows) {
+        const float* src = w + (size_t)row * ld + k;
+        const float4 x = ld4(src), y = ld4(src + 16);
+        o.x = bf16_rne_bits(x.x) | (bf16_rne_bits(x.y) << 16);
+        o.y = bf16_rne_bits(x.z) | (bf16_rne_bits(x.w) << 16);
+        o.z = bf16_rne_bits(y.x) | (bf16_rne_bits(y.y) << 16);
+        o.w = bf16_rne_bits(y.z) | (bf16_rne_bits(y.w) << 16);
+    }
+    out[i] = o;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1826,8 +1907,66 @@ static int nt_big_launch(const NtBigArgs& b, hipStream_t st) {
     return launch_status();
 }
 
+bool bf16w_supported(int M, int N, const int* K, int nseg) {
+    bool ok = M >= 1 && M <= 128 && N >= 1 && nseg >= 1 && nseg <= 3;
+    for (int s = 0; ok && s < nseg; ++s) ok = K[s] > 0 && K[s] % TBK == 0;
+    return ok;
+}
+
+size_t pack_bf16_bytes(int rows, int K) {
+    if (rows <= 0 || K <= 0 || K % TBK) return 0;
+    return (size_t)ceil_div(rows, 16) * (K / TBK) * BW_STAGE_BYTES;
+}
+
+int pack_bf16(const float* w, int ld, int rows, int K, void* out, hipStream_t st) {
+    const size_t bytes = pack_bf16_bytes(rows, K);
+    SF_CHECK_ARG(w && out && bytes && bytes / 16 < (1ull << 32) && ld >= K && ld % 4 == 0 &&
+                 ((uintptr_t)w | (uintptr_t)out) % 16 == 0);
+    const unsigned total = (unsigned)(bytes / 16);
+    SF_LAUNCH(pack_bf16_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w, ld, rows, K, (uint4*)out, total);
+    return launch_status();
+}
+
+// The gate product with bf16-stored weights (gemm_nt_bf16w_kernel): raw slabs only, the K splits of nt_shape (what the
+// caller's workspace was sized for), all rows in one block.
+static int linear_nt_bf16w(const NtArgs& base, int chunks, const void* const* packed, float* ws, size_t ws_floats,
+                           hipStream_t st, float** raw_slabs, int* ksplit_out) {
+    NtArgs a = base;
+    int mt, mblocks, ks;
+    nt_shape(a.M, a.N, chunks, &mt, &mblocks, &ks);
+    mt = ceil_div(a.M, 16);
+    if (!ws || ws_floats < (size_t)ks * a.M * a.N) return SF_ERR_WORKSPACE;
+    a.chunks_total = chunks;
+    a.ksplit = ks;
+    a.epi = EPI_NONE;
+    a.out = ws;
+    a.ldo = a.N;
+    NtPackedW pk{};
+    for (int s = 0; s < a.nseg; ++s) pk.p[s] = packed[s];
+    const dim3 grid(ceil_div(a.N, 64), ks);
+    const size_t lds = std::max<size_t>((size_t)2 * 3 * (((mt + 1) / 2) * 32) * SPL_ROWB, (size_t)4 * mt * 64 * 16);
+#define SF_BF16W(MTV)                                                                              \
+    case MTV: {                                                                                    \
+        static bool attr_set = false;                                                              \
+        if (!attr_set) {                                                                           \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_bf16w_kernel<MTV>),    \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
+            attr_set = true;                                                                       \
+        }                                                                                          \
+        SF_LAUNCH(gemm_nt_bf16w_kernel<MTV>, grid, dim3(512), lds, st, a, pk);                     \
+    } break;
+    switch (mt) {
+        SF_BF16W(1) SF_BF16W(2) SF_BF16W(3) SF_BF16W(4) SF_BF16W(5) SF_BF16W(6) SF_BF16W(7) SF_BF16W(8)
+        default: return SF_ERR_UNSUPPORTED;
+    }
+#undef SF_BF16W
+    if (ksplit_out) *ksplit_out = ks;
+    *raw_slabs = ws;
+    return launch_status();
+}
+
 int linear_nt(const Seg* segs, int nseg, int M, int N, const LinearOut& out, float* ws,
-              size_t ws_floats, hipStream_t st, float** raw_slabs, int* ksplit_out) {
+              size_t ws_floats, hipStream_t st, float** raw_slabs, int* ksplit_out, const void* const* packed_w) {
     SF_CHECK_ARG(nseg >= 1 && nseg <= 3 && M > 0 && N > 0);
     NtArgs a{};
     a.nseg = nseg;
@@ -1837,6 +1976,15 @@ int linear_nt(const Seg* segs, int nseg, int M, int N, const LinearOut& out, flo
                      segs[s].ldw % 4 == 0);
         a.seg[s] = segs[s];
         chunks += ceil_div(segs[s].K, 16);
+    }
+    if (packed_w && raw_slabs && !g_nt_force_f32) {
+        int Ks[3] = {0, 0, 0};
+        for (int s = 0; s < nseg; ++s) Ks[s] = segs[s].K;
+        if (bf16w_supported(M, N, Ks, nseg)) {
+            a.M = M;
+            a.N = N;
+            return linear_nt_bf16w(a, chunks, packed_w, ws, ws_floats, st, raw_slabs, ksplit_out);
+        }
     }
     int mt, mblocks, ks;
     SmallPlan sp;

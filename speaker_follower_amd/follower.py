@@ -22,7 +22,7 @@ from ._lib import call
 from .features import cand_sincos
 from .model import (decoder_params, decoder_w_struct, decoder_fold, _encoder_structs, _TAPE_KEYS,
                     grad_ptr, trainable_embedding, bi_encoder_tapes, bi_encoder_fwd, bi_encoder_bwd)
-from .runtime import ptr, stream, ws_args, wgrad_ws_args, ensure_workspace, dropout_arg, fill_regions, take_fault, PersistentLaunchFault, concurrent_stream, graph_capture, WeightsMoved, transposed
+from .runtime import ptr, stream, ws_args, wgrad_ws_args, ensure_workspace, dropout_arg, fill_regions, take_fault, PersistentLaunchFault, concurrent_stream, graph_capture, WeightsMoved, transposed, check_gate_weights, gate_weights_pass, register_bf16_weights
 from .dp import collectives_on
 
 byref = C.byref
@@ -265,12 +265,40 @@ class FollowerEngine:
         self.episode_call = True        # the whole decode loop (and its backward) as ONE C call
         self.fused_env_step = True      # nav.DeviceNavBatch: the env step inside the scoring + glue launch
         self.fallbacks = 0              # rollouts re-issued on the per-step kernels after a persistent-launch fault (run)
+        self._gate_weights = 'fp32'
+
+    # How the decoder LSTM's weights are stored for the gate product of INFERENCE passes: 'fp32' (default) or 'bf16'
+    # (include/sf_hip.h: sf_gate_product_bf16_weights -- the product of the unrounded activations with the weights rounded
+    # to bf16 once; half the bytes per decode step).  A pass that keeps a tape for a backward (train mode, or parameters that
+    # require grad under grad mode) ignores it: a forward on rounded weights against a backward on unrounded ones would be
+    # wrong.  A captured rollout keeps the mode it was captured with.
+    @property
+    def gate_weights(self):
+        return self._gate_weights
+
+    @gate_weights.setter
+    def gate_weights(self, mode):
+        self._gate_weights = check_gate_weights(mode)
+
+    def pass_gate_weights(self, train=None):
+        """The weight storage a rollout issued NOW with `train` runs its gate products on."""
+        if self._gate_weights == 'fp32':
+            return 'fp32'
+        enc, dec = self.encoder, self.decoder
+        taped = (dec.training if train is None else train) or (torch.is_grad_enabled() and any(
+            p.requires_grad for p in list(enc.parameters()) + list(dec.parameters())))
+        return 'fp32' if taped else self._gate_weights
 
     # ------------------------------------------------------------------------------ forward
     def rollout(self, batch, steps, feedback='argmax', train=None, finalize=True):
         """Runs encoder + `steps` decode steps.  Returns a RolloutState with
         .logits [S,B,A] (masked), .actions [S,B], .step_scores [S,B], .loss (0-dim tensor,
         differentiable when parameters require grad and grad mode is on), .h, .c, .ctx."""
+        lstm = self.decoder.lstm
+        with gate_weights_pass(self.pass_gate_weights(train), lstm.weight_ih, lstm.weight_hh):
+            return self._rollout(batch, steps, feedback, train, finalize)
+
+    def _rollout(self, batch, steps, feedback, train, finalize):
         enc, dec, store = self.encoder, self.decoder, self.store
         dev = store.device
         B, A, S = batch.batch_size, batch.a_max, steps
@@ -553,9 +581,10 @@ class FollowerEngine:
             st.loss = st.loss_buf.reshape(())
         return st
 
-    def _baked_pointers(self):
+    def _baked_pointers(self, gate_weights='fp32'):
         """Every weight-side device pointer a captured rollout bakes into its hipGraph: the parameters
-        and their derived copies (transposed layouts, the encoder's [vocab,4H] table).  Building the
+        and their derived copies (transposed layouts, the encoder's [vocab,4H] table, with
+        gate_weights = 'bf16' the packed images of the decoder LSTM's weights).  Building the
         structs also refreshes stale derived copies IN PLACE, on the current stream."""
         enc = self.encoder
         if enc.num_directions == 2:
@@ -566,16 +595,21 @@ class FollowerEngine:
             ew = bytes(_encoder_structs(enc))
         dw = decoder_w_struct(decoder_params(self.decoder))
         fold = bytes(decoder_fold(self.decoder)) if (self.fold_inference or (self.fold_text and self.fold_chain)) else b''
-        return ew + bytes(dw) + fold
+        packed = b''
+        if gate_weights == 'bf16':
+            lstm = self.decoder.lstm
+            packed = repr(tuple(t.data_ptr() for t in register_bf16_weights(lstm.weight_ih, lstm.weight_hh))).encode()
+        return ew + bytes(dw) + fold + packed
 
     def _guarded(self, graph_replay):
-        baked = self._baked_pointers()
+        mode = self._gate_weights          # (the captured rollouts ran train=False under no_grad: this mode, for good)
+        baked = self._baked_pointers(mode)
 
         def replay():
             # weights updated since capture (optimizer.step, load_state_dict)?  Their derived copies are
             # rebuilt in place here, ahead of the replay on the same stream, so the graph reads current
             # data everywhere.  A MOVED tensor cannot be patched into the graph: refuse.
-            if self._baked_pointers() != baked:
+            if self._baked_pointers(mode) != baked:
                 raise WeightsMoved('a weight (or one of its cached layouts) moved since this rollout was '
                                    'captured; capture() again')
             graph_replay()

@@ -403,6 +403,7 @@ def _setup_space(agent, load_next_minibatch, key_fields=4, graph_cap=0):
         fd.load(ctx, seq_mask, h_t, c_t)
     else:
         fd = search.FlatDecoder(agent.decoder, agent.store, ctx, seq_mask)
+        fd.gate_weights = getattr(agent, 'gate_weights', 'fp32')
         fd.seed(h_t, c_t)
     return env, space, fd
 

@@ -196,6 +196,119 @@ class strict_gate_product:
         return False
 
 
+# ---- bf16 weight storage of the gate product (include/sf_hip.h: sf_gate_product_bf16_weights) ----------------
+class bf16_gate_weights:
+    """`with runtime.bf16_gate_weights():` -- the LSTM gate products of REGISTERED weight pairs (`register_bf16_weights`)
+    read their weights as one bf16 plane, rounded to nearest even once, instead of splitting the fp32 rows at every step.
+    Inference only: the backward knows nothing of it.  Process-wide switch; restores the previous setting on exit; the
+    strict switch wins over it.  Captured graphs keep the kernels they were captured with."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.prev = int(lib.sf_gate_product_bf16_weights_is_on())
+        lib.sf_gate_product_bf16_weights(int(self.on))
+        return self
+
+    def __exit__(self, *exc):
+        lib.sf_gate_product_bf16_weights(self.prev)
+        return False
+
+
+GATE_WEIGHTS = ('fp32', 'bf16')
+
+
+def check_gate_weights(mode):
+    """The `gate_weights` attribute of engines, decoders and agents: 'fp32' (default) or 'bf16'."""
+    if not isinstance(mode, str) or mode not in GATE_WEIGHTS:
+        raise ValueError("gate_weights must be 'fp32' or 'bf16', not %r" % (mode,))
+    return mode
+
+
+def gate_mode_key(mode):
+    """What a cache of captured inference graphs adds to its key: a graph keeps the gate-product kernel it was captured
+    with, so the weight-storage mode and the strict switch both tell graphs apart (the strict flag stays the key's last
+    element, where it has always been)."""
+    return (check_gate_weights(mode), int(lib.sf_gate_product_is_strict()))
+
+
+_packed_bf16 = {}
+_bf16_pairs = {}
+
+
+def packed_bf16(w):
+    """The packed bf16 image of a 2-D fp32 weight (sf_pack_bf16), rebuilt IN PLACE, on the current stream, only when
+    the weight changed: a captured hipGraph keeps pointing at live memory, as with `transposed`."""
+    import weakref
+    key = w.data_ptr()
+    hit = _packed_bf16.get(key)
+    if hit is not None and hit[0]() is w and hit[1] == (w._version, _cache_epoch):
+        return hit[2]
+    R, K = w.shape
+    n = int(lib.sf_pack_bf16_bytes(R, K))
+    if n == 0:
+        raise ValueError('bf16 weight storage needs a reduction depth that is a multiple of 64, not %d' % K)
+    out = hit[2] if (hit is not None and hit[0]() is w and hit[2].numel() == n and hit[2].device == w.device) \
+        else torch.empty(n, device=w.device, dtype=torch.uint8)
+    src = w.detach()
+    _lib.call('sf_pack_bf16', ptr(src), src.stride(0), R, K, C.c_void_p(out.data_ptr()), stream())
+    if len(_packed_bf16) > 64:
+        for k in [k for k, v in _packed_bf16.items() if v[0]() is None]:
+            del _packed_bf16[k]
+    _packed_bf16[key] = (weakref.ref(w), (w._version, _cache_epoch), out)
+    return out
+
+
+def _forget_bf16_pair(key):
+    if _bf16_pairs.pop(key, None) is not None:
+        lib.sf_lstm_weights_bf16(C.c_void_p(key[0]), C.c_void_p(key[1]), None, None)
+
+
+def register_bf16_weights(w_ih, w_hh):
+    """Packs (or refreshes in place) both weights of an LSTM cell and tells the library which packed images belong to
+    the pair of fp32 addresses (sf_lstm_weights_bf16).  The pair is forgotten when either weight dies.  Returns the two
+    packed buffers (what a captured graph bakes besides the weights)."""
+    import weakref
+    p_ih, p_hh = packed_bf16(w_ih), packed_bf16(w_hh)
+    key = (w_ih.data_ptr(), w_hh.data_ptr())
+    val = (p_ih.data_ptr(), p_hh.data_ptr())
+    hit = _bf16_pairs.get(key)
+    if hit is None or hit[0] != val or hit[1]() is not w_ih or hit[2]() is not w_hh:
+        gone = lambda ref, w: ref() is None or ref() is w  # noqa: E731
+        for k in [k for k, v in _bf16_pairs.items() if k != key and (gone(v[1], w_ih) or gone(v[2], w_hh))]:
+            _forget_bf16_pair(k)                                 # (a weight that moved: its old addresses mean nothing now)
+        _lib.call('sf_lstm_weights_bf16', ptr(w_ih.detach()), ptr(w_hh.detach()), C.c_void_p(val[0]), C.c_void_p(val[1]))
+        for w in (w_ih, w_hh):
+            weakref.finalize(w, _forget_bf16_pair, key)
+        _bf16_pairs[key] = (val, weakref.ref(w_ih), weakref.ref(w_hh))
+    return p_ih, p_hh
+
+
+class gate_weights_pass:
+    """What an inference pass of an LSTM cell runs under: `with runtime.gate_weights_pass(mode, cell.weight_ih,
+    cell.weight_hh):`.  'bf16' registers the pair (refreshing stale packed images in place) and turns the switch on;
+    'fp32' turns it OFF -- a pass that keeps a tape for a backward is always issued as 'fp32', so that it never meets
+    rounded weights, whatever the caller of the pass has set.  Restores the switch on exit."""
+
+    def __init__(self, mode, w_ih, w_hh):
+        self.on = check_gate_weights(mode) == 'bf16'
+        self.w = (w_ih, w_hh)
+
+    def __enter__(self):
+        if self.on:
+            register_bf16_weights(*self.w)
+        self.prev = int(lib.sf_gate_product_bf16_weights_is_on())
+        if self.prev != int(self.on):
+            lib.sf_gate_product_bf16_weights(int(self.on))
+        return self
+
+    def __exit__(self, *exc):
+        if self.prev != int(self.on):
+            lib.sf_gate_product_bf16_weights(self.prev)
+        return False
+
+
 # ---- the fault word of the persistent launches (include/sf_hip.h: sf_workspace_fault_offset) ----------------
 FAULT_ENC_FWD, FAULT_ENC_BWD, FAULT_SPEAKER, FAULT_LOCK = 1, 2, 4, 8
 

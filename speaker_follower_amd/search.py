@@ -36,7 +36,7 @@ from ._lib import call
 from .features import cand_sincos
 from .follower import batch_instructions_from_encoded, EOS, BOS
 from .model import decoder_params, decoder_w_struct, decoder_tape, tape_struct
-from .runtime import ptr, stream, ws_args, gc_paused, graph_capture, ensure_workspace
+from .runtime import ptr, stream, ws_args, gc_paused, graph_capture, ensure_workspace, check_gate_weights, gate_weights_pass, register_bf16_weights, gate_mode_key
 
 byref = C.byref
 
@@ -122,10 +122,26 @@ class _Pool:
         return base, self.buf[base:base + n]
 
 
-class FlatDecoder:
-    """One follower decoder step over a flat list of search states (a6 without the glue)."""
+def _gate_pass(obj):
+    """The gate-product mode `obj` (a decoder-step object with .dec and .gate_weights) issues its inference steps under."""
+    return gate_weights_pass(obj.gate_weights, obj.dec.lstm.weight_ih, obj.dec.lstm.weight_hh)
 
-    def __init__(self, decoder, store, ctx, mask):
+
+def _baked_weights(obj):
+    """The weight-side pointers a captured step of `obj` bakes (stale cached layouts are refreshed in place): the decoder
+    struct and, with gate_weights = 'bf16', the packed images of the LSTM weights."""
+    wb = bytes(decoder_w_struct(decoder_params(obj.dec)))
+    if obj.gate_weights == 'bf16':
+        wb += repr(tuple(t.data_ptr() for t in register_bf16_weights(obj.dec.lstm.weight_ih, obj.dec.lstm.weight_hh))).encode()
+    return wb
+
+
+class FlatDecoder:
+    """One follower decoder step over a flat list of search states (a6 without the glue).  `gate_weights`: 'fp32' or 'bf16'
+    (FollowerEngine.gate_weights; steps of more than 128 states run the fp32-weight kernels in either mode)."""
+
+    def __init__(self, decoder, store, ctx, mask, gate_weights='fp32'):
+        self.gate_weights = check_gate_weights(gate_weights)
         self.dec, self.store = decoder, store
         self.ctx, self.mask = ctx.contiguous(), mask.to(torch.uint8).contiguous()
         self.dev = store.device
@@ -220,9 +236,10 @@ class FlatDecoder:
         pano = st.pano(vp, view)
         cnd = st.cands(vp, cv, sc, a_num, A)
         tp = tape_struct(tape)
-        call('sf_attn_decoder_fwd', byref(self.w), byref(pano), byref(cnd), N, self.H, self.D, self.T,
-             None, ptr(h0), ptr(c0), ptr(self.ctx), ptr(self.mask), ptr(crow), byref(tp), None,
-             None, 0, *ws_args(dev))
+        with _gate_pass(self):
+            call('sf_attn_decoder_fwd', byref(self.w), byref(pano), byref(cnd), N, self.H, self.D, self.T,
+                 None, ptr(h0), ptr(c0), ptr(self.ctx), ptr(self.mask), ptr(crow), byref(tp), None,
+                 None, 0, *ws_args(dev))
         idx = torch.empty(N, k, dtype=torch.int32, device=dev)
         logp = new(N, k)
         call('sf_logprob_topk', ptr(tape['logit']), A, N, A, ptr(a_num), k, ptr(idx), ptr(logp), s)
@@ -266,7 +283,8 @@ class GraphStep:
     captured once per (decoder, store, navigation table, sizes) and re-captured only when a weight (or one of its
     cached layouts) moved or the state pool had to grow."""
 
-    def __init__(self, decoder, store, nav, n_inst, cap, t_max, pool_rows=1 << 14):
+    def __init__(self, decoder, store, nav, n_inst, cap, t_max, pool_rows=1 << 14, gate_weights='fp32'):
+        self.gate_weights = check_gate_weights(gate_weights)
         dev = store.device
         self.dec, self.store, self.nav, self.dev = decoder, store, nav, dev
         self.n_inst, self.cap, self.T, self.A = n_inst, cap, t_max, nav.A
@@ -306,7 +324,7 @@ class GraphStep:
         self.hpool[:B].copy_(h)
         self.cpool[:B].copy_(c)
         self.n = B
-        w = bytes(decoder_w_struct(decoder_params(self.dec)))        # (also refreshes stale cached layouts in place)
+        w = _baked_weights(self)                                     # (also refreshes stale cached layouts in place)
         if self.graph is None or w != self.baked:
             self._capture()
 
@@ -332,9 +350,10 @@ class GraphStep:
         cnd = st.cands(cur['vp'], cur['cand_view'], cur['sincos'], cur['a_num'], A)
         w = decoder_w_struct(decoder_params(self.dec))
         tp = tape_struct(self.tape)
-        call('sf_attn_decoder_fwd', byref(w), byref(pano), byref(cnd), cap, self.H, self.D, self.T,
-             None, ptr(self.h0), ptr(self.c0), ptr(self.ctx), ptr(self.mask), ptr(crow), byref(tp), None,
-             None, 0, *ws_args(self.dev))
+        with _gate_pass(self):
+            call('sf_attn_decoder_fwd', byref(w), byref(pano), byref(cnd), cap, self.H, self.D, self.T,
+                 None, ptr(self.h0), ptr(self.c0), ptr(self.ctx), ptr(self.mask), ptr(crow), byref(tp), None,
+                 None, 0, *ws_args(self.dev))
         call('sf_logprob_topk', ptr(self.tape['logit']), A, cap, A, ptr(cur['a_num']), A, None, ptr(self.logp), s)
         sca = (_lib.RowMove * 3)(*(_lib.RowMove(src.data_ptr(), pool.data_ptr(), dst.data_ptr(), width, width, width, 1)
                                    for src, pool, width in ((self.tape['h1'], self.hpool, H), (self.tape['c1'], self.cpool, H),
@@ -356,7 +375,7 @@ class GraphStep:
                 self._issue()
         torch.cuda.current_stream().wait_stream(side)
         self.graph, self._stream = graph, side                       # (the graph bakes the capture stream's workspace)
-        self.baked = bytes(decoder_w_struct(decoder_params(self.dec)))
+        self.baked = _baked_weights(self)
 
     # ---- the native loop (sim/frontier_core.cpp: run_graph) launches the graph itself
     def native_loop_ready(self):
@@ -422,16 +441,22 @@ def _hip_entry_points():
     return _HIP_ENTRY[0]
 
 
+def graph_step_key(agent, nav, n_inst, cap, t_max, gate_weights):
+    return (id(agent.decoder), id(agent.store), id(nav), n_inst, cap, t_max) + gate_mode_key(gate_weights)
+
+
 def graph_step_for(agent, nav, n_inst, cap):
     """The agent's GraphStep for these sizes (built on first use, kept on the agent)."""
     t_max = agent.max_instruction_length
-    # (a captured step keeps the gate-product kernel it was captured with: runtime.strict_gate_product)
-    key = (id(agent.decoder), id(agent.store), id(nav), n_inst, cap, t_max, int(_lib.lib.sf_gate_product_is_strict()))
+    # (a captured step keeps the gate-product kernel it was captured with: runtime.strict_gate_product, and the weight
+    # storage of Seq2SeqAgent.gate_weights)
+    mode = getattr(agent, 'gate_weights', 'fp32')
+    key = graph_step_key(agent, nav, n_inst, cap, t_max, mode)
     cache = agent.__dict__.setdefault('_graph_steps', {})
     gs = cache.get(key)
     if gs is None or gs.dec is not agent.decoder or gs.store is not agent.store or gs.nav is not nav:
         cache.clear()                                                # (one live configuration: the pools are ~100 MB)
-        gs = cache[key] = GraphStep(agent.decoder, agent.store, nav, n_inst, cap, t_max)
+        gs = cache[key] = GraphStep(agent.decoder, agent.store, nav, n_inst, cap, t_max, gate_weights=mode)
     return gs
 
 
@@ -778,7 +803,8 @@ class DeviceFollowerBeam:
     MAX_BEAM = 64
     N_INT = 6                                     # history arrays besides the attention: parent action rank sid psid score
 
-    def __init__(self, decoder, store, nav, B, beam_size, episode_len, t_max, chunk=2, graphs=True):
+    def __init__(self, decoder, store, nav, B, beam_size, episode_len, t_max, chunk=2, graphs=True, gate_weights='fp32'):
+        self.gate_weights = check_gate_weights(gate_weights)
         if not self.supports(beam_size, decoder):
             raise ValueError('DeviceFollowerBeam: beam_size %d > %d, or a decoder without visual attention'
                              % (beam_size, self.MAX_BEAM))
@@ -863,9 +889,10 @@ class DeviceFollowerBeam:
             # (the previous action's embedding straight into the first half of the LSTM input rows)
             call('sf_gather_actions_ld', byref(ucand), R, ptr(self.act), ptr(self.tape['xin']), 2 * st.F, s)
             call('sf_move_rows', gat, 2, R, s)
-            call('sf_attn_decoder_fwd', byref(w), byref(pano), byref(cnd), R, H, self.D, self.T,
-                 None, ptr(self.h0), ptr(self.c0), ptr(self.ctx), ptr(self.mask), ptr(self.crow), byref(tp), None,
-                 None, 0, *ws_args(self.dev))
+            with _gate_pass(self):
+                call('sf_attn_decoder_fwd', byref(w), byref(pano), byref(cnd), R, H, self.D, self.T,
+                     None, ptr(self.h0), ptr(self.c0), ptr(self.ctx), ptr(self.mask), ptr(self.crow), byref(tp), None,
+                     None, 0, *ws_args(self.dev))
             call('sf_logprob_topk', ptr(self.tape['logit']), A, R, A, ptr(cur['a_num']), self.k, ptr(self.idx),
                  ptr(self.logp), s)
             call('sf_follower_beam_select', byref(fb), ptr(self.idx), ptr(self.logp), ptr(self.tape['alpha']), s)
@@ -902,7 +929,7 @@ class DeviceFollowerBeam:
         Tm = ctx.shape[1]
         if ctx.shape[0] != B or Tm > self.T:
             raise ValueError('DeviceFollowerBeam built for %d instructions of <= %d tokens' % (B, self.T))
-        wb = bytes(decoder_w_struct(decoder_params(self.dec)))          # (also refreshes stale cached layouts in place)
+        wb = _baked_weights(self)                                        # (also refreshes stale cached layouts in place)
         if wb != self.baked:                                             # a weight (or its cached layout) moved
             self.graph, self.baked = None, wb
         if self.graphs and self.graph is None:
@@ -958,20 +985,26 @@ class DeviceFollowerBeam:
         return out
 
 
+def follower_beam_key(agent, nav, B, beam_size, t_max, chunk, graphs, gate_weights):
+    return (id(agent.decoder), id(agent.store), id(nav), B, beam_size, agent.episode_len, t_max, int(chunk),
+            bool(graphs)) + gate_mode_key(gate_weights)
+
+
 def follower_beam_for(agent, nav, B, beam_size, chunk, graphs):
     """The agent's DeviceFollowerBeam for these sizes (buffers and captured graph; built on first use, kept on the
     agent the way graph_step_for keeps its step)."""
     t_max = agent.max_instruction_length
-    # (a captured step keeps the gate-product kernel it was captured with: runtime.strict_gate_product)
-    key = (id(agent.decoder), id(agent.store), id(nav), B, beam_size, agent.episode_len, t_max, int(chunk), bool(graphs),
-           int(_lib.lib.sf_gate_product_is_strict()))
+    # (a captured step keeps the gate-product kernel it was captured with: runtime.strict_gate_product, and the weight
+    # storage of Seq2SeqAgent.gate_weights)
+    mode = getattr(agent, 'gate_weights', 'fp32')
+    key = follower_beam_key(agent, nav, B, beam_size, t_max, chunk, graphs, mode)
     cache = agent.__dict__.setdefault('_device_beams', {})
     db = cache.get(key)
     if db is None or db.dec is not agent.decoder or db.store is not agent.store or db.nav is not nav:
         if len(cache) >= 4:
             cache.clear()
         db = cache[key] = DeviceFollowerBeam(agent.decoder, agent.store, nav, B, beam_size, agent.episode_len, t_max,
-                                             chunk, graphs)
+                                             chunk, graphs, gate_weights=mode)
     return db
 
 
