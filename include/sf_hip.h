@@ -187,7 +187,11 @@ const char* sf_status_string(int status);
 const char* sf_last_error_string(void);
 
 /* ---- nn.Linear (model.py:64, 99, 117-119, 306-307, 338-340, 419, 485) ------------------------
- * y[M,N] = act(x[M,K] w[N,K]^T + b);  act: 0 none, 1 tanh.  K % 4 == 0, ldx % 4 == 0. */
+ * y[M,N] = act(x[M,K] w[N,K]^T + b);  act: 0 none, 1 tanh.  K % 4 == 0, ldx % 4 == 0.
+ * Outside the operands the call reads and writes NOTHING: of x only rows < M and columns < K (the K..ldx-1 padding of
+ * a row and whatever lies behind row M-1 belong to someone else -- the engines pass views into wider rows -- and may
+ * hold NaN), of y only rows < M and columns < N are written (columns N..ldy-1 and the rows behind keep their
+ * contents).  tests/test_gpu_gemm_dispatch.py holds every kernel of the dispatch to this. */
 int sf_linear_fwd(const float* x, int ldx, const float* w, const float* b, int M, int N, int K,
                   int act, float* y, int ldy, void* ws, size_t ws_bytes, sf_stream stream);
 /* The product alone, as split-K partial slabs (what the LSTM cell consumes: its pointwise kernel
@@ -199,7 +203,10 @@ int sf_linear_slabs_fwd(const float* x, int ldx, const float* w, int K1, const f
                         const float* u, int K2, int M, int N, int* ksplit, void* ws, size_t ws_bytes,
                         sf_stream stream);
 /* dy is the gradient wrt the activation output; y is the saved output (needed for act = tanh).
- * dx [M,K] overwritten (accumulate_dx = 0) or added to; dw [N,K], db [N] accumulated. */
+ * dx [M,K] overwritten (accumulate_dx = 0) or added to; dw [N,K], db [N] accumulated.
+ * As for sf_linear_fwd, nothing outside the operands is read or written: x [M,K], y and dy [M,N] are read at rows < M
+ * and columns < K resp. N only (padding columns up to ldx / ldy / lddy and rows behind M-1 may hold NaN); of dx only
+ * rows < M, columns < K are written (columns K..lddx-1 and the rows behind keep their contents). */
 int sf_linear_bwd(const float* x, int ldx, const float* w, const float* y, int ldy,
                   const float* dy, int lddy, int M, int N, int K, int act, float* dx, int lddx,
                   int accumulate_dx, float* dw, float* db, void* ws, size_t ws_bytes,

@@ -41,6 +41,7 @@ def rnd(rng, *shape, scale=1.0):
 
 
 # ------------------------------------------------------------------------------------ GEMMs
+# (every kernel of the GEMM dispatch on its own, exact at its tile edges and under row strides: test_gpu_gemm_dispatch.py)
 @pytest.mark.parametrize('M,N,K', [(100, 2048, 4864), (8, 256, 2176), (128, 2048, 4352), (33, 64, 2048),
                                    (100, 2048, 512), (8, 256, 512), (3, 512, 1024), (100, 991, 512),
                                    (7, 2048, 300), (128, 64, 16), (250, 2048, 300), (1, 16, 4),
