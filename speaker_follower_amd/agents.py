@@ -21,7 +21,8 @@ from . import _lib
 from ._lib import call
 from .lazydict import LazyDict
 from .follower import batch_instructions_from_encoded, FEEDBACK, PAD, EOS, BOS
-from .runtime import ptr, stream, require_gpu, cands_dense, PersistentLaunchFault, gc_paused, WeightsMoved
+from .runtime import (ptr, stream, require_gpu, cands_dense, gc_paused, WeightsMoved, take_fault, fault_views, fault_bits,
+                      per_step_kernels, reissue_per_step)
 
 byref = C.byref
 
@@ -182,9 +183,8 @@ class Seq2SeqAgent(BaseAgent):
         return table_for(self.env, self.store)
 
     def _rollout_on_device(self, table=None, reissue=False):
-        """One rollout on the device-resident environment.  `FollowerEngine.run` checks the fault word of the
-        persistent encoder launch at its sync and re-issues the rollout on the per-step kernels by itself;
-        reissue=True (train(): a fault raised by the BACKWARD) replays the current minibatch that way."""
+        """One rollout on the device-resident environment (`FollowerEngine.run`: the fault protocol of DESIGN.md
+        inside).  reissue=True (train(): a fault raised by the BACKWARD): the current minibatch again, per-step kernels."""
         from .nav import DeviceNavBatch
         if not reissue:
             self.env.reset(sort=True)
@@ -213,14 +213,9 @@ class Seq2SeqAgent(BaseAgent):
                 self._rollout_ahead = (nav, nxt, DeviceNavBatch(nav, nxt, self.episode_len,
                                                                 max_length=self.max_instruction_length,
                                                                 reverse=self.reverse_instruction))
-        keep = getattr(self.encoder, 'persistent', True)
-        if reissue:
-            self.encoder.persistent = False
-        try:
+        with per_step_kernels(self.encoder if reissue else None):
             st = self._engine.run(batch, self.episode_len, self.feedback, train=self.decoder.training,
                                   while_running=None if reissue else prepare_next)
-        finally:
-            self.encoder.persistent = keep
         self.loss = st.loss
         traj = batch.trajectories(st)                   # the one host sync of the rollout
         for tr, it in zip(traj, items):
@@ -248,7 +243,6 @@ class Seq2SeqAgent(BaseAgent):
         the minibatch's longest: equal up to the summation order of the padded attention columns).  `self.loss` is a
         host tensor on this path."""
         from .nav import DeviceNavBatch
-        from .runtime import take_fault, fault_views
         eng, dev = self._engine, self._device()
         key = self._test_graph_key(nav, eng, len(items))
         graphs = self.__dict__.setdefault('_test_graphs', {})  # (train.py alternates between its validation environments)
@@ -311,18 +305,13 @@ class Seq2SeqAgent(BaseAgent):
         if any(fpin.tolist()):
             self.__dict__.pop('_rollout_inflight', None)      # (what was issued ahead is not trusted either: reloaded next)
             torch.cuda.synchronize(dev)
-            take_fault(dev)                                   # (read and cleared)
+            bits = take_fault(dev)                            # (read and cleared)
             batch.load(items)
-            keep = getattr(self.encoder, 'persistent', True)
-            self.encoder.persistent = False
-            try:
+
+            def eagerly():
                 with torch.no_grad():
-                    st2 = eng.rollout(batch, S, 'argmax', train=False)
-            finally:
-                self.encoder.persistent = keep
-            if take_fault(dev):
-                raise PersistentLaunchFault('the per-step re-issue of an inference rollout raised a fault again')
-            eng.fallbacks += 1
+                    return eng.rollout(batch, S, 'argmax', train=False)
+            st2 = reissue_per_step(self.encoder, eng, dev, 'an inference rollout', eagerly, bits)
             rows, views = batch.row[:S + 1].cpu().numpy(), batch.view[:S + 1].cpu().numpy()
             acts, sc, loss = st2.actions.cpu().numpy(), st2.step_scores.cpu().numpy(), st2.loss_buf.cpu().numpy()
         self.loss = torch.tensor(float(loss.reshape(-1)[0]))        # (a host tensor: a copy to the device would queue behind the replay issued ahead)
@@ -536,7 +525,6 @@ class Seq2SeqAgent(BaseAgent):
         starved persistent encoder launch re-issues the whole call on the per-step kernels (FollowerEngine.run).
         `last_host_reads` counts the host synchronisations of the call."""
         from .follower import DeviceFollowerBatch, route_index_batch, scored_route_outputs
-        from .runtime import fault_views, take_fault
         B = len(path_obs)
         eng, dev = self._scoring_engine(store), store.device
         training = self.decoder.training
@@ -571,18 +559,13 @@ class Seq2SeqAgent(BaseAgent):
         site, it = eng.site_next, eng.iteration
         st, flat = issue()
         reads = 1
-        if flat[3 * S * B + 1:].any():
-            take_fault(dev)                                         # (read and cleared)
-            eng.fallbacks += 1
-            keep = getattr(self.encoder, 'persistent', True)
-            self.encoder.persistent, eng.site_next, eng.iteration = False, site, it
-            try:
-                st, flat = issue()
-            finally:
-                self.encoder.persistent = keep
-            reads += 2
-            if flat[3 * S * B + 1:].any():
-                raise PersistentLaunchFault('the per-step re-issue of a route scoring pass raised a fault again')
+        raised = [int(w) for w in flat[3 * S * B + 1:].tolist() if w]
+        if raised:
+            for w in fault_views(dev):                              # (read with the results: cleared here)
+                w.zero_()
+            eng.site_next, eng.iteration = site, it
+            st, flat = reissue_per_step(self.encoder, eng, dev, 'a route scoring pass', issue, int(np.bitwise_or.reduce(raised)))
+            reads += 2                                              # (its download, and the helper's look at the fault words)
         self.last_host_reads = reads
         res = flat[:3 * S * B].numpy().reshape(3, S, B)
         traj = scored_route_outputs(path_obs, path_actions, res[0], res[1], res[2])
@@ -614,25 +597,26 @@ class Seq2SeqAgent(BaseAgent):
         for _ in range(1, n_iters + 1):
             encoder_optimizer.zero_grad()
             decoder_optimizer.zero_grad()
+            eng = self._engine if self._device_table() is not None else None
+            where = (eng.site_next, eng.iteration) if eng is not None else None
             self._rollout_with_loss()
             self.loss.backward()
             # a starved persistent launch of the BACKWARD has poisoned the gradients: never step on them -- replay
             # the minibatch on the per-step kernels (the forward's own check sits inside FollowerEngine.run)
-            if _persistent_fault(self._device()):
+            bits = fault_bits(self._device())
+            if bits:
                 encoder_optimizer.zero_grad()
                 decoder_optimizer.zero_grad()
                 self.losses.pop()
-                keep = getattr(self.encoder, 'persistent', True)
-                self.encoder.persistent = False
-                try:
+                if where is not None:
+                    eng.site_next, eng.iteration = where       # (the masks / samples the poisoned rollout drew)
+
+                def again():
                     # (the device environment replays the SAME minibatch; the per-step host loop cannot rewind its
                     # simulators and trains on the next one)
                     self._rollout_with_loss(reissue=True)
                     self.loss.backward()
-                finally:
-                    self.encoder.persistent = keep
-                if _persistent_fault(self._device()):
-                    raise PersistentLaunchFault('the per-step re-issue of a training iteration raised a fault again')
+                reissue_per_step(self.encoder, eng, self._device(), 'a training iteration', again, bits)
             encoder_optimizer.step()
             decoder_optimizer.step()
 
@@ -667,7 +651,6 @@ class Seq2SeqAgent(BaseAgent):
         loss and re-issues that iteration on the per-step kernels.  Same sites, same numbers as the eager loop
         (tests/test_gpu_agents.py)."""
         from .nav import DeviceNavBatch
-        from .runtime import take_fault
         table, eng, dev = self._device_table(), self._engine, self._device()
         given = (encoder_optimizer, decoder_optimizer)
         opts = tuple(self._fused_for(o) for o in given)
@@ -700,7 +683,6 @@ class Seq2SeqAgent(BaseAgent):
 
     def _replay_iterations(self, opts, n_iters, table, eng, dev):
         from .nav import DeviceNavBatch
-        from .runtime import take_fault
         encoder_optimizer, decoder_optimizer = opts
         # (a captured iteration holds the optimizers' hyper-parameters as kernel arguments: a changed learning rate is a
         # new graph)
@@ -743,39 +725,37 @@ class Seq2SeqAgent(BaseAgent):
                 nxt = list(self.env.batch)
                 ahead = (nxt, batch._host_arrays(nxt) if len(nxt) == batch.batch_size else None)
             loss = float(st.loss_buf)                         # the iteration's one host sync
-            bits = take_fault(dev)
-            if eng.group is not None:
-                # every rank takes the same decision (MAX: RCCL has no bitwise reductions): a re-issue launches
-                # collectives, and those only match if all ranks re-issue
-                t_ = torch.tensor([bits], device=dev, dtype=torch.int32)
-                torch.distributed.all_reduce(t_, op=torch.distributed.ReduceOp.MAX, group=eng.group)
-                bits = int(t_.item())
+            bits = fault_bits(dev, eng.group)                 # (every rank takes the same decision)
             if bits:
                 # a persistent launch starved: the guarded optimizer steps did nothing.  The same minibatch again on
                 # the per-step kernels, launch by launch
                 if eng.grad_sync is not None:
                     eng.grad_sync.abort()                     # (nothing of the faulted round is in flight: replays wait)
-                for o, b in zip(opts, before):
-                    o.set_host_steps(b)
-                    o.zero_grad()
-                eng.site_next, eng.iteration = where          # (the re-issue draws the masks / samples the replay drew)
-                keep = getattr(self.encoder, 'persistent', True)
-                self.encoder.persistent = False
-                try:
-                    st = eng.rollout(batch, self.episode_len, self.feedback, train=True)
-                    st.loss.backward()
-                finally:
-                    self.encoder.persistent = keep
-                if eng.grad_sync is not None:
-                    eng.grad_sync.wait()
+                st = self._reissue_training_iteration(opts, eng, dev, batch, before, where, bits)
                 loss = float(st.loss_buf)
-                if take_fault(dev):
-                    raise PersistentLaunchFault('the per-step re-issue of a training iteration raised a fault again')
-                eng.fallbacks += 1
-                for o in opts:
-                    o.step()
             self.loss = st.loss_buf.reshape(())
             self.losses.append(loss)
+
+    def _reissue_training_iteration(self, opts, eng, dev, batch, steps_before, where, bits):
+        """A replayed training iteration whose persistent launch raised fault `bits` (its guarded optimizer steps did
+        nothing), again on the per-step kernels, launch by launch: the optimizers' host steps and the dropout / sampling
+        sites (`where`) as they were in front of the replay, so that it draws the masks and samples the replay drew, over
+        what `batch` holds.  Steps the optimizers and returns the rollout's state (runtime.reissue_per_step)."""
+        for o, b in zip(opts, steps_before):
+            o.set_host_steps(b)
+            o.zero_grad()
+        eng.site_next, eng.iteration = where
+
+        def launch_by_launch():
+            st = eng.rollout(batch, self.episode_len, self.feedback, train=True)
+            st.loss.backward()
+            if eng.grad_sync is not None:
+                eng.grad_sync.wait()
+            return st
+        st = reissue_per_step(self.encoder, eng, dev, 'a training iteration', launch_by_launch, bits)
+        for o in opts:
+            o.step()
+        return st
 
     pipeline_replays = True      # train() on graphs: replay i + 1 is queued before the loss of replay i is read
 
@@ -788,7 +768,6 @@ class Seq2SeqAgent(BaseAgent):
         faulted minibatch on the per-step kernels and queues the other one again.  Same minibatches in the same order,
         same sites, same steps: losses and weights of the serial loop (tests/test_gpu_nav.py)."""
         import collections
-        from .runtime import take_fault, fault_views
         _, tg, batch = cached
         def pins_for(n_words):
             # (one fault word per workspace; a workspace created later -- a side stream of the per-step fallback --
@@ -836,26 +815,11 @@ class Seq2SeqAgent(BaseAgent):
                 ev.synchronize()
                 if any(pins[slot][1].tolist()):
                     torch.cuda.synchronize(dev)               # (the replay queued behind it did nothing either)
-                    take_fault(dev)
-                    for o, b in zip(opts, before_f[0]):
-                        o.set_host_steps(b)
-                        o.zero_grad()
-                    # the same sites too: the faulted replay and the one queued behind it advanced the host mirrors
-                    eng.site_next, eng.iteration = before_f[1], before_f[2]
+                    bits = take_fault(dev)
                     batch.load(items_f)
-                    keep = getattr(self.encoder, 'persistent', True)
-                    self.encoder.persistent = False
-                    try:
-                        st2 = eng.rollout(batch, self.episode_len, self.feedback, train=True)
-                        st2.loss.backward()
-                    finally:
-                        self.encoder.persistent = keep
+                    # (the sites of the faulted replay: it and the one queued behind it advanced the host mirrors)
+                    st2 = self._reissue_training_iteration(opts, eng, dev, batch, before_f[0], before_f[1:], bits)
                     self.losses.append(float(st2.loss_buf))
-                    if take_fault(dev):
-                        raise PersistentLaunchFault('the per-step re-issue of a training iteration raised a fault again')
-                    eng.fallbacks += 1
-                    for o in opts:
-                        o.step()
                     if cur is not None:                       # queue the other one again, in front of what was drawn since
                         todo.appendleft((cur[3], None))
                         issued -= 1
@@ -879,12 +843,6 @@ class Seq2SeqAgent(BaseAgent):
         ep, dp = self._encoder_and_decoder_paths(path)
         self.encoder.load_state_dict(torch.load(ep, **kwargs))
         self.decoder.load_state_dict(torch.load(dp, **kwargs))
-
-
-def _persistent_fault(device):
-    """Fault bits of the persistent launches since the last check (runtime.take_fault); one small D2H copy."""
-    from .runtime import take_fault
-    return take_fault(device) if device.type == 'cuda' else 0
 
 
 class _SpeakerGlueFn(torch.autograd.Function):
@@ -1116,7 +1074,7 @@ class Seq2SeqSpeaker(object):
         S = self._score_steps(encoded_instructions, feedback)
         batch = spk.DeviceSpeakerBatch.from_synth(self._index_batch(n, pair_rows, encoded_instructions, 0, B),
                                                   device=store.device, max_length=self.instruction_len)
-        st = eng.run(batch, S, feedback, train=training)                   # (fault check + per-step re-issue inside)
+        st = eng.run(batch, S, feedback, train=training)                   # (fault check and re-issue inside)
         both = torch.cat((st.words[1:].to(torch.float32), st.step_scores), dim=0).cpu().numpy()   # (the one host sync)
         mark('downloaded')
         return self._score_outputs(instr_ids, both, S, st.loss, None, store.device, mark)
@@ -1201,7 +1159,6 @@ class Seq2SeqSpeaker(object):
         return pend
 
     def _finish_scores(self, pend, instr_ids, mark=lambda name: None):
-        from .runtime import take_fault
         eng, dev = self._engine, pend.store.device
         swept = None
         if pend.graphs is not None:
@@ -1212,15 +1169,8 @@ class Seq2SeqSpeaker(object):
         parts = pend.parts
         if bits:                                                              # a starved persistent launch: per-step kernels
             swept = None                                                      # (everything again, launch by launch)
-            eng.fallbacks += 1
-            keep, eng.persistent, eng.site_next = eng.persistent, False, pend.site
-            try:
-                parts = pend.sweep()
-            finally:
-                eng.persistent = keep
-            again = take_fault(dev)
-            if again:
-                raise PersistentLaunchFault('fault bits %d, and %d after the per-step re-issue' % (bits, again))
+            eng.site_next = pend.site
+            parts = reissue_per_step(eng, eng, dev, 'a scoring sweep', pend.sweep, bits)
         if swept is not None:
             w16, sc, cnt = swept                                              # [n,S,128] int16 / f32, [n,S,2]
             S_ = pend.S
@@ -1500,7 +1450,6 @@ class Seq2SeqSpeaker(object):
                 and getattr(self.env, 'host_table', 1) is None and hasattr(self.env, 'graphs')):
             return False
         from . import speaker as spk
-        from .runtime import take_fault
         if getattr(self, '_engine', None) is None or self._engine.store is not store:
             self._engine = spk.SpeakerEngine(self.encoder, self.decoder, store)
         eng, dev = self._engine, store.device
@@ -1522,20 +1471,19 @@ class Seq2SeqSpeaker(object):
         nxt = peek(False) if peek is not None else None
         if nxt is not None:
             self._routes_ahead = (self.feedback, nxt, self._routes_of(nxt, store))
-        if take_fault(dev):                                   # the iteration's host sync
+        bits = take_fault(dev)                                # the iteration's host sync
+        if bits:
             for m in (self.encoder, self.decoder):
                 for p_ in m.parameters():
                     if p_.grad is not None:
                         p_.grad.zero_()
-            keep, eng.persistent, eng.site_next = eng.persistent, False, site
-            eng.fallbacks += 1
-            try:
+            eng.site_next = site
+
+            def again():
                 st = eng.score(batch, S, self.feedback, train=True)
                 st.loss.backward()
-            finally:
-                eng.persistent = keep
-            if take_fault(dev):
-                raise PersistentLaunchFault('the per-step re-issue of a training iteration raised a fault again')
+                return st
+            st = reissue_per_step(eng, eng, dev, 'a training iteration', again, bits)
         self.loss = st.loss
         self.losses.append(float(st.loss.detach()))
         return True
@@ -1559,23 +1507,17 @@ class Seq2SeqSpeaker(object):
             # starved BACKWARD has poisoned the gradients -- never step on them; train this iteration on the next
             # minibatch with the per-step kernels instead (the forward's own check sits inside SpeakerEngine.run)
             dev = next(self.decoder.parameters()).device
-            if _persistent_fault(dev):
+            bits = fault_bits(dev)
+            if bits:
                 encoder_optimizer.zero_grad()
                 decoder_optimizer.zero_grad()
                 self.losses.pop()
                 eng = getattr(self, '_engine', None)
-                keep = eng.persistent if eng is not None else True
-                if eng is not None:
-                    eng.persistent = False
-                    eng.fallbacks += 1
-                try:
+
+                def again():
                     self.rollout()
                     self.loss.backward()
-                finally:
-                    if eng is not None:
-                        eng.persistent = keep
-                if _persistent_fault(dev):
-                    raise PersistentLaunchFault('the per-step re-issue of a training iteration raised a fault again')
+                reissue_per_step(eng, eng, dev, 'a training iteration', again, bits)
             encoder_optimizer.step()
             decoder_optimizer.step()
 

@@ -22,7 +22,7 @@ from ._lib import call
 from .features import cand_sincos
 from .model import (decoder_params, decoder_w_struct, decoder_fold, _encoder_structs, _TAPE_KEYS,
                     grad_ptr, trainable_embedding, bi_encoder_tapes, bi_encoder_fwd, bi_encoder_bwd)
-from .runtime import ptr, stream, ws_args, wgrad_ws_args, ensure_workspace, dropout_arg, fill_regions, take_fault, PersistentLaunchFault, concurrent_stream, graph_capture, WeightsMoved, transposed, check_gate_weights, gate_weights_pass, register_bf16_weights
+from .runtime import ptr, stream, ws_args, wgrad_ws_args, ensure_workspace, dropout_arg, fill_regions, fault_bits, reissue_per_step, concurrent_stream, graph_capture, WeightsMoved, transposed, check_gate_weights, gate_weights_pass, register_bf16_weights
 from .dp import collectives_on
 
 byref = C.byref
@@ -519,35 +519,27 @@ class FollowerEngine:
 
     def run(self, batch, steps, feedback='argmax', train=None, backward=False, while_running=None):
         """`rollout` (and, with backward=True, `loss.backward()`) + the fault check of the persistent encoder
-        launches (include/sf_hip.h: sf_workspace_fault_offset): ONE host sync; a launch that gave up a bounded wait
-        (co-residency lost to another process) has poisoned its outputs with NaN, so the SAME rollout -- same
-        dropout / sampling sites -- is re-issued in this process with the per-step encoder kernels
-        (SF_ENC_PER_STEP), after zeroing the gradients the poisoned backward accumulated.  Under a process group
-        the decision is taken on the MAX of all ranks' fault words, so every rank re-issues together; gradient
-        buckets the poisoned backward had launched are waited for and re-armed (`BucketedGrads.abort`) first.  Raises PersistentLaunchFault if a fault is still raised afterwards.
+        launches: ONE host sync, and the fault protocol of DESIGN.md (runtime.reissue_per_step) -- the SAME rollout,
+        same dropout / sampling sites, again with the per-step encoder kernels (SF_ENC_PER_STEP), after zeroing the
+        gradients the poisoned backward accumulated.  Under a process group the decision is taken on the MAX of all
+        ranks' fault words, so every rank re-issues together; gradient buckets the poisoned backward had launched are
+        waited for and re-armed (`BucketedGrads.abort`) first.
         `while_running()`: host work the caller wants done between the issue and the sync (the next minibatch)."""
         dev = self.store.device
         site, it = self.site_next, self.iteration
+        group = self.group if self.group is not None and collectives_on(self.group) else None
 
-        def once():
+        def issue():
             st = self.rollout(batch, steps, feedback, train)
             if backward:
                 st.loss.backward()
-            nonlocal while_running
-            if while_running is not None:
-                while_running, cb = None, while_running
-                cb()
-            bits = take_fault(dev)
-            if self.group is not None and collectives_on(self.group):
-                # (MAX, not BOR: RCCL has no bitwise reductions; the caller only needs "some rank faulted")
-                t = torch.tensor([bits], device=dev, dtype=torch.int32)
-                torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX, group=self.group)
-                bits = int(t.item())
-            return st, bits
+            return st
 
-        st, bits = once()
+        st = issue()
+        if while_running is not None:
+            while_running()
+        bits = fault_bits(dev, group)
         if bits:
-            self.fallbacks += 1
             if backward:
                 # the poisoned backward has already launched its gradient buckets (on every rank alike): let them
                 # land before the buffer is zeroed, and re-arm the buckets for the re-issued backward
@@ -556,14 +548,8 @@ class FollowerEngine:
                 for p_ in st.all_params:
                     if p_.grad is not None:
                         p_.grad.zero_()
-            keep = getattr(self.encoder, 'persistent', True)
-            self.encoder.persistent, self.site_next, self.iteration = False, site, it
-            try:
-                st, again = once()
-            finally:
-                self.encoder.persistent = keep
-            if again:
-                raise PersistentLaunchFault('fault bits %d, and %d after the per-step re-issue' % (bits, again))
+            self.site_next, self.iteration = site, it
+            st = reissue_per_step(self.encoder, self, dev, 'a rollout', issue, bits, group)
         return st
 
     def finish(self, st, total=None):

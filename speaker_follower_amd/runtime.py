@@ -5,6 +5,7 @@ PyTorch is used for device memory and streams only; every arithmetic op on the h
 path goes through libsf_hip.so.  There is no CPU implementation: tensors that are
 not on a GPU raise.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -358,6 +359,51 @@ def take_fault(device):
             w.zero_()
             bits |= b
     return bits
+
+
+def fault_bits(device, group=None):
+    """`take_fault(device)`; 0 for a device that is not a GPU, without a read.  With a process group: the MAX of all
+    ranks' bits (RCCL has no bitwise reductions, and the callers only need "some rank faulted"), so that every rank
+    takes the same decision -- a re-issue launches collectives, and those only match if all ranks re-issue."""
+    bits = take_fault(device) if device.type == 'cuda' else 0
+    if group is not None:
+        t = torch.tensor([bits], device=device, dtype=torch.int32)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX, group=group)
+        bits = int(t.item())
+    return bits
+
+
+@contextlib.contextmanager
+def per_step_kernels(owner):
+    """`with per_step_kernels(encoder):` -- the persistent launches of `owner` (an EncoderLSTM, a SpeakerEngine; None:
+    nothing to switch) ruled out for the duration: `owner.persistent` is False inside and back at its previous value
+    (on, where it was never set) afterwards, also when the body raises."""
+    if owner is None:
+        yield
+        return
+    keep = getattr(owner, 'persistent', True)
+    owner.persistent = False
+    try:
+        yield
+    finally:
+        owner.persistent = keep
+
+
+def reissue_per_step(owner, counter, device, what, body, bits=0, group=None):
+    """The re-issue of a pass whose persistent launch raised fault `bits` ("The fault protocol"): counts
+    it in `counter.fallbacks` (None: nobody counts), runs `body()` under `per_step_kernels(owner)`, reads the fault
+    words again (`fault_bits(device, group)`: a host sync) and returns what `body()` returned -- or raises
+    PersistentLaunchFault if a fault is raised still.  What a pass has to put back before it can be issued again
+    (gradients, dropout / sampling sites, optimizer steps, the minibatch) is the caller's, in front of this call or in
+    `body`."""
+    if counter is not None:
+        counter.fallbacks += 1
+    with per_step_kernels(owner):
+        out = body()
+    again = fault_bits(device, group)
+    if again:
+        raise PersistentLaunchFault('fault bits %d, and %d after the per-step re-issue of %s' % (bits, again, what))
+    return out
 
 
 def dropout_arg(p, seed, row0=0, site_dev=None, site_mul=1):

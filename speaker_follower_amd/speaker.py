@@ -19,7 +19,7 @@ from ._lib import call
 from .features import cand_sincos
 from .follower import batch_instructions_from_encoded, FEEDBACK, PAD, EOS, BOS
 from .model import _grads, trainable_embedding
-from .runtime import ptr, stream, ws_args, ensure_workspace, dropout_arg, fill_regions, visual_query_fold, struct_of, transposed, take_fault, PersistentLaunchFault, graph_capture, WeightsMoved
+from .runtime import ptr, stream, ws_args, ensure_workspace, dropout_arg, fill_regions, visual_query_fold, struct_of, transposed, take_fault, fault_bits, reissue_per_step, PersistentLaunchFault, graph_capture, WeightsMoved
 
 byref = C.byref
 
@@ -425,24 +425,15 @@ class SpeakerEngine:
         return TrainingGraph(self, body, opts, self.store.device)
 
     def run(self, batch, steps, feedback='teacher', train=None):
-        """`score` + the fault check of the persistent word loop (include/sf_hip.h: sf_workspace_fault_offset): one
-        host sync; if the launch gave up a bounded wait (co-residency lost to another process: its outputs are
-        NaN-poisoned) the SAME pass -- same dropout / sampling sites -- is re-issued on the per-step kernels in this
-        process.  Raises PersistentLaunchFault if a fault is still raised afterwards."""
+        """`score` + the fault check of the persistent word loop: one host sync, and the fault protocol of DESIGN.md
+        (runtime.reissue_per_step) -- the SAME pass, same dropout / sampling sites, again on the per-step kernels."""
         site = self.site_next
         st = self.score(batch, steps, feedback, train)
         dev = self.store.device
-        bits = take_fault(dev)
+        bits = fault_bits(dev)
         if bits:
-            self.fallbacks += 1
-            keep, self.persistent, self.site_next = self.persistent, False, site
-            try:
-                st = self.score(batch, steps, feedback, train)
-            finally:
-                self.persistent = keep
-            again = take_fault(dev)
-            if again:
-                raise PersistentLaunchFault('fault bits %d, and %d after the per-step re-issue' % (bits, again))
+            self.site_next = site
+            st = reissue_per_step(self, self, dev, 'a scoring pass', lambda: self.score(batch, steps, feedback, train), bits)
         return st
 
     def _backward(self, st, dloss):
@@ -648,7 +639,6 @@ class SpeakerSweep:
         sc = torch.empty(n, self.S, self.B, dtype=torch.float32).pin_memory() if self.with_scores else None
         cnt = torch.empty(n, self.S, 2, dtype=torch.float32).pin_memory() if self.with_scores else None
         self.host_pack_s = 0.0
-        from .runtime import take_fault
         take_fault(dev)
         for s_ in self.streams:                                  # (the weights' derived layouts are refreshed on the caller's stream)
             s_.wait_stream(torch.cuda.current_stream(dev))
@@ -687,17 +677,17 @@ class SpeakerSweep:
     def finish(self, handle, check_faults=True):
         """Waits for the sweep `issue` started; a sweep that saw a persistent-launch fault is re-run -- all of it -- on
         the per-step kernels (check_faults=False: the caller reads the fault words itself, runtime.take_fault)."""
-        from .runtime import take_fault
         dev = self.store.device
         for s in self.streams:
             s.synchronize()
         bits = take_fault(dev) if check_faults else 0
         if bits:
             if not handle['persistent']:
-                raise PersistentLaunchFault('fault bits %d raised by a sweep on the per-step kernels' % bits)
+                raise PersistentLaunchFault('fault bits %d, and %d after the per-step re-issue of a sweep'
+                                            % (handle.get('faulted', 0), bits))
             # a starved persistent launch poisoned some minibatch: the whole sweep again on the per-step kernels
             self.fallbacks += 1
-            return self.finish(self.issue(handle['batches'], _persistent=False))
+            return self.finish(dict(self.issue(handle['batches'], _persistent=False), faulted=bits))
         if self.with_scores:
             return handle['out'].numpy(), handle['scores'].numpy(), handle['cnt'].numpy()
         return handle['out'].numpy()
