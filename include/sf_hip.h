@@ -970,6 +970,30 @@ int sf_lstm_weights_bf16(const float* w_ih, const float* w_hh, const void* packe
 void sf_gate_product_bf16_weights(int on);
 int sf_gate_product_bf16_weights_is_on(void);
 int sf_gate_product_bf16_supported(int M, int K1, int K2, int N);
+/* FP16 STORAGE for the feature table (opt-in, additive to ABI 9).
+ *
+ * Contract: a table registered here holds IEEE binary16 [n_viewpoints, V, IMG] (half the bytes of the fp32 table; IMG % 4 ==
+ * 0), and every entry point that reads table rows by index -- sf_pano / sf_cands with dense == NULL, forward and backward,
+ * the gathers, sf_gather_path_actions -- widens each value to fp32 as it loads it (exact, subnormals included) and then runs
+ * the arithmetic of the fp32 kernels: the results are, bit for bit, those of an fp32 table holding the widened values.
+ * loc_table, dense sources and every output stay fp32.  The table must hold finite values only (as the fp32 table must).
+ * sf_pano and sf_cands keep their layout: the table is known by its ADDRESS, as sf_lstm_weights_bf16 knows weights.
+ *
+ *   sf_feature_table_f16(table, on)
+ *                                 on != 0: the table at this address holds binary16; on == 0 forgets the address (unknown:
+ *                                 nothing to do).  A few (16) addresses are remembered, under a mutex; SF_ERR_UNSUPPORTED when
+ *                                 full, SF_ERR_ARG on NULL.  An owner of an FP32 table should call it with on == 0 once for
+ *                                 its address: an allocator may hand out the address of a freed binary16 table again.
+ *                                 LIFETIME: the lookup happens when a call is ENQUEUED (or captured), and selects the kernel.
+ *                                 The registration, like the table itself, must therefore outlive every call that names the
+ *                                 table and every captured hipGraph that ran with it; a graph keeps the kernels it was
+ *                                 captured with, whatever is registered at replay.
+ *   sf_feature_table_is_f16(table)
+ *                                 1 when the address is registered, else 0.
+ * No entry point reads a registered table as fp32 (that would run off its end): each launcher picks the binary16
+ * instantiation of its kernel from the source's tag, and returns before launching where it has none. */
+int sf_feature_table_f16(const void* table, int on);
+int sf_feature_table_is_f16(const void* table);
 /* Older name of the same switch (tools/, A/B timing): on != 0 runs the large LSTM gate products (K >= 2048, M <= 128: sf_lstm_cell_fwd, the decode
  * step) on the fp32 MFMA (v_mfma_f32_16x16x4_f32, rounds 1-3) instead of the bf16 matrix cores with three-way
  * error-free operand splitting (csrc/sf_gemm.hip: gemm_nt_split_kernel; same fp32 accuracy class, measured closer

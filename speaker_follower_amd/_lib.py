@@ -197,6 +197,8 @@ _SIGNATURES = {
     'sf_gate_product_bf16_weights': (None, [C.c_int]),
     'sf_gate_product_bf16_weights_is_on': (C.c_int, []),
     'sf_gate_product_bf16_supported': (C.c_int, [i32, i32, i32, i32]),
+    'sf_feature_table_f16': (C.c_int, [c_p, C.c_int]),
+    'sf_feature_table_is_f16': (C.c_int, [c_p]),
     'sf_debug_tn_split_min_rows': (None, [C.c_int]),
     'sf_workspace_fault_offset': (C.c_size_t, [C.c_size_t]),
     'sf_debug_trace': (None, [C.c_void_p]),

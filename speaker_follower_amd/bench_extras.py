@@ -400,7 +400,7 @@ def real_env_full(enc, dec, store, device, batch=100, steps=20, train_iters=6):
     out = dict(what='student-forced rollouts on the FULL real environment: %d scans, %d viewpoints (feature table '
                     '%.2f GB), %d x 36 states x <=%d candidates tabulated on the device; batch %d from %d scans, '
                     '%d decode steps, encoder included; every step executed for every row'
-                    % (len(nt.scans), nt.n_rows, store.table.numel() * 4 / 1e9, nt.n_rows, nt.A, batch,
+                    % (len(nt.scans), nt.n_rows, store.table.numel() * store.table.element_size() / 1e9, nt.n_rows, nt.A, batch,
                        len({it['scan'] for it in items}), steps),
                unit='agent-steps/s', host_build_seconds=build_s)
     enc.eval()

@@ -62,7 +62,7 @@ class MeanPooledImageFeatures(ImageFeatures):
     def get_features(self, state):
         """[36, 2048] numpy block of the state's viewpoint (env.py:380-383), for dictionary-style callers."""
         row = self.store.row(state.scanId, state.location.viewpointId)
-        return self.store.table[row].cpu().numpy()
+        return self.store.rows_f32(row).cpu().numpy()
 
 
 class R2RBatch(R2RIndexEnv):

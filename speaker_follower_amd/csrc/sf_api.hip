@@ -83,12 +83,28 @@ inline Arena arena(void* ws, size_t bytes) {
 }
 inline hipStream_t S(sf_stream s) { return (hipStream_t)s; }
 
+// ---- fp16 storage of the feature table (include/sf_hip.h: sf_feature_table_f16) ----------------------------------------
+// The C structs carry no storage tag (ABI 9 pins their layout): a table is known to hold binary16 by its ADDRESS.
+constexpr int F16_TABLES = 16;
+const void* g_f16_tables[F16_TABLES];
+int g_f16_ntables = 0;
+std::mutex g_f16_mutex;
+int table_is_f16(const void* table) {
+    if (!table) return 0;
+    std::lock_guard<std::mutex> lock(g_f16_mutex);
+    for (int i = 0; i < g_f16_ntables; ++i)
+        if (g_f16_tables[i] == table) return 1;
+    return 0;
+}
+
+// the ONLY places that turn the C structs into the kernels' sources: a dense source is never half
 inline PanoSrc pano(const sf_pano* p) {
-    return PanoSrc{p->dense, p->table, p->loc_table, p->vp, p->view, p->V, p->IMG, p->LOC};
+    return PanoSrc{p->dense, p->table, p->loc_table, p->vp, p->view, p->V, p->IMG, p->LOC,
+                   p->dense ? 0 : table_is_f16(p->table)};
 }
 inline CandSrc cands(const sf_cands* c) {
     return CandSrc{c->dense, c->table, c->vp, c->cand_view, c->cand_sincos, c->a_num,
-                   c->A, c->V, c->IMG, c->LOC};
+                   c->A, c->V, c->IMG, c->LOC, c->dense ? 0 : table_is_f16(c->table)};
 }
 
 inline FGlue make_glue(const CandSrc& src, int B, float* logit, const sf_follower_glue* g) {
@@ -557,6 +573,22 @@ int sf_lstm_weights_bf16(const float* w_ih, const float* w_hh, const void* packe
     g_bf16_pairs[at] = Bf16Pair{w_ih, w_hh, packed_ih, packed_hh};
     return SF_OK;
 }
+int sf_feature_table_f16(const void* table, int on) {
+    SF_CHECK_ARG(table);
+    std::lock_guard<std::mutex> lock(g_f16_mutex);
+    int at = -1;
+    for (int i = 0; i < g_f16_ntables; ++i)
+        if (g_f16_tables[i] == table) at = i;
+    if (!on) {                                                  // forget the address (unknown: nothing to do)
+        if (at >= 0) g_f16_tables[at] = g_f16_tables[--g_f16_ntables];
+        return SF_OK;
+    }
+    if (at >= 0) return SF_OK;
+    if (g_f16_ntables == F16_TABLES) return SF_ERR_UNSUPPORTED;
+    g_f16_tables[g_f16_ntables++] = table;
+    return SF_OK;
+}
+int sf_feature_table_is_f16(const void* table) { return table_is_f16(table); }
 void sf_gate_product_bf16_weights(int on) { g_bf16w_on.store(on ? 1 : 0, std::memory_order_relaxed); }
 int sf_gate_product_bf16_weights_is_on(void) { return g_bf16w_on.load(std::memory_order_relaxed); }
 int sf_gate_product_bf16_supported(int M, int K1, int K2, int N) {
@@ -2062,7 +2094,8 @@ int sf_gather_path_actions(const float* table, int V, int IMG, int LOC, const in
                            sf_stream stream) {
     SF_ENTER();
     SF_CHECK_ARG(table && vp && act_view && act_sincos && act && out && N > 0 && V > 0 && ld_out >= IMG + LOC);
-    return gather_path_actions(table, V, IMG, LOC, vp, act_view, act_sincos, act, N, out, ld_out, S(stream));
+    return gather_path_actions(table, V, IMG, LOC, vp, act_view, act_sincos, act, N, out, ld_out, S(stream),
+                               table_is_f16(table));
 }
 
 // ---- search helpers -----------------------------------------------------------------------

@@ -42,7 +42,7 @@ __device__ __forceinline__ double wave_max_f64(double v) {
     return v;
 }
 
-template <int MODE>
+template <int MODE, bool H16 = false>
 __device__ __forceinline__ void visual_attn_body(const VisArgs& a, int b) {
     __shared__ float4 slots[VIS_SLOTS][VIS_CPL * 64];
     __shared__ float s_score[64];
@@ -50,7 +50,7 @@ __device__ __forceinline__ void visual_attn_body(const VisArgs& a, int b) {
     const int V = a.src.V;
     const int n4 = (a.src.IMG + a.src.LOC) >> 2;
 
-    const PanoRow prow = pano_row(a.src, b);
+    const PanoRow prow = pano_row<H16>(a.src, b);
     float4 x[VIS_RPW][VIS_CPL];
 #pragma unroll
     for (int r = 0; r < VIS_RPW; ++r) {
@@ -58,7 +58,7 @@ __device__ __forceinline__ void visual_attn_body(const VisArgs& a, int b) {
 #pragma unroll
         for (int i = 0; i < VIS_CPL; ++i) {
             const int c = lane + 64 * i;
-            x[r][i] = pano_load(prow, v, c, v < V && c < n4, V, n4);
+            x[r][i] = pano_load<H16>(prow, v, c, v < V && c < n4, V, n4);
         }
     }
 
@@ -160,9 +160,9 @@ __device__ __forceinline__ void visual_attn_body(const VisArgs& a, int b) {
     });
 }
 
-template <int MODE>
+template <int MODE, bool H16 = false>
 __global__ __launch_bounds__(VIS_NW * 64) void visual_attn_kernel(VisArgs a) {
-    visual_attn_body<MODE>(a, blockIdx.x);
+    visual_attn_body<MODE, H16>(a, blockIdx.x);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -200,7 +200,7 @@ __device__ __forceinline__ void vis_stamp(const VisSplit& sp, int block, int slo
 //          accumulated in float64; a group's record holds its scores RELATIVE to its own maximum (small numbers:
 //          exact in fp32 to 1e-7 of the softmax weight, where a raw score of +-80 would carry 4e-6) and that maximum as a
 //          float64 in two dwords.
-template <int PHASE, bool F64 = false>
+template <int PHASE, bool F64 = false, bool H16 = false>
 __device__ __forceinline__ void visual_split_body(const VisArgs& a, const VisSplit& sp, int g, int b) {
     __shared__ float4 slots[VSP_SLOTS][VIS_CPL * 64];
     __shared__ float s_score[64];
@@ -215,7 +215,7 @@ __device__ __forceinline__ void visual_split_body(const VisArgs& a, const VisSpl
 
     if (PHASE != 2) {
     vis_stamp(sp, b * VSP_G + g, 0);
-    const PanoRow prow = pano_row(a.src, b);
+    const PanoRow prow = pano_row<H16>(a.src, b);
     float4 x[VIS_RPW][VIS_CPL];
 #pragma unroll
     for (int r = 0; r < VIS_RPW; ++r) {
@@ -223,7 +223,7 @@ __device__ __forceinline__ void visual_split_body(const VisArgs& a, const VisSpl
 #pragma unroll
         for (int i = 0; i < VIS_CPL; ++i) {
             const int c = lane + 64 * i;
-            x[r][i] = pano_load(prow, v, c, v < V && c < n4, V, n4);
+            x[r][i] = pano_load<H16>(prow, v, c, v < V && c < n4, V, n4);
         }
     }
     float s, m, e;          // F64: s = score - m (relative), m unused (md holds the maximum)
@@ -408,11 +408,13 @@ __device__ __forceinline__ void visual_split_body(const VisArgs& a, const VisSpl
     }
 }
 
+template <bool H16>
 __global__ __launch_bounds__(VSP_NW * 64) void visual_attn_split_kernel(VisArgs a, VisSplit sp) {
-    visual_split_body<0>(a, sp, blockIdx.x, blockIdx.y);
+    visual_split_body<0, false, H16>(a, sp, blockIdx.x, blockIdx.y);
 }
+template <bool H16>
 __global__ __launch_bounds__(VSP_NW * 64) void visual_attn_split_f64_kernel(VisArgs a, VisSplit sp) {
-    visual_split_body<0, true>(a, sp, blockIdx.x, blockIdx.y);
+    visual_split_body<0, true, H16>(a, sp, blockIdx.x, blockIdx.y);
 }
 
 // =================================================================================================
@@ -612,13 +614,14 @@ __device__ __forceinline__ float score_const(const ScoreArgs& a, int b, int lane
     return wave_sum(c) + a.b_out[0];
 }
 
+template <bool H16>
 __global__ __launch_bounds__(SC_NW * 64) void score_fwd_kernel(ScoreArgs a) {
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int A = a.src.A;
     if (wave >= A) return;
     const int n4 = (a.src.IMG + a.src.LOC) >> 2;
-    const CandRow row = cand_row(a.src, b, wave);
+    const CandRow row = cand_row<H16>(a.src, b, wave);
     const float4* rv = reinterpret_cast<const float4*>(a.r + (size_t)b * a.ldr);
     float4 x[SC_CPL], q[SC_CPL];
 #pragma unroll
@@ -627,7 +630,7 @@ __global__ __launch_bounds__(SC_NW * 64) void score_fwd_kernel(ScoreArgs a) {
 #pragma unroll
         for (int i = 0; i < SC_CPL; ++i) {
             const int c = lane + 64 * i;
-            x[i] = cand_load(row, c, c < n4, n4);
+            x[i] = cand_load<H16>(row, c, c < n4, n4);
             q[i] = rv[min(c, n4 - 1)];
         }
     }
@@ -644,13 +647,14 @@ __global__ __launch_bounds__(SC_NW * 64) void score_fwd_kernel(ScoreArgs a) {
 // Scoring + per-step glue fused (one dependent stage instead of two): wave a keeps candidate a's row
 // in registers, the 16 logits meet in LDS, wave 0 masks / soft-maxes / picks the action, and the wave
 // that owns the chosen row writes dropout(u_next) straight into the next step's LSTM input.
+template <bool H16 = false>
 __device__ __forceinline__ void score_glue_body(const ScoreArgs& a, const FGlue& g, int b) {
     __shared__ float s_logit[64];
     __shared__ int s_at;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int A = a.src.A;
     const int n4 = (a.src.IMG + a.src.LOC) >> 2;
-    const CandRow row = cand_row(a.src, b, wave);
+    const CandRow row = cand_row<H16>(a.src, b, wave);
     const FGlueIn gin = follower_glue_load(g, b);               // (used by wave 0; cheap for the rest)
     const float4* rv = reinterpret_cast<const float4*>(a.r + (size_t)b * a.ldr);
     float4 x[SC_CPL], q[SC_CPL];
@@ -661,7 +665,7 @@ __device__ __forceinline__ void score_glue_body(const ScoreArgs& a, const FGlue&
 #pragma unroll
         for (int i = 0; i < SC_CPL; ++i) {
             const int c = lane + 64 * i;
-            x[i] = cand_load(row, c, c < n4, n4);
+            x[i] = cand_load<H16>(row, c, c < n4, n4);
             q[i] = rv[min(c, n4 - 1)];
         }
     }
@@ -689,8 +693,10 @@ __device__ __forceinline__ void score_glue_body(const ScoreArgs& a, const FGlue&
     }
 }
 
-__global__ __launch_bounds__(SC_NW * 64) void score_glue_kernel(ScoreArgs a, FGlue g) { score_glue_body(a, g, blockIdx.x); }
+template <bool H16>
+__global__ __launch_bounds__(SC_NW * 64) void score_glue_kernel(ScoreArgs a, FGlue g) { score_glue_body<H16>(a, g, blockIdx.x); }
 
+template <bool H16>
 __global__ __launch_bounds__(SC_NW * 64) void score_bwd_kernel(ScoreArgs a) {
     __shared__ float4 slots[SC_SLOTS][SC_CPL * 64];
     const int b = blockIdx.x;
@@ -713,7 +719,7 @@ __global__ __launch_bounds__(SC_NW * 64) void score_bwd_kernel(ScoreArgs a) {
         w = a.logit[(size_t)b * A + min(wave, A - 1)];
         dlv = a.logit[(size_t)b * A + min(lane, A - 1)];
     }
-    const CandRow row = cand_row(a.src, b, wave);
+    const CandRow row = cand_row<H16>(a.src, b, wave);
     float4 p[SC_CPL];
 #pragma unroll
     for (int i = 0; i < SC_CPL; ++i) p[i] = f4zero();
@@ -721,7 +727,7 @@ __global__ __launch_bounds__(SC_NW * 64) void score_bwd_kernel(ScoreArgs a) {
 #pragma unroll
         for (int i = 0; i < SC_CPL; ++i) {
             const int c = lane + 64 * i;
-            f4fma(p[i], w, cand_load(row, c, c < n4, n4));
+            f4fma(p[i], w, cand_load<H16>(row, c, c < n4, n4));
         }
     }
     if (wave == 0) {
@@ -769,19 +775,19 @@ __global__ __launch_bounds__(TXT_NW * 64) void pair_small_text_kernel(SmallArgs 
 // Folded inference step (sf_decoder_fold): the attention partials of step t+1 ride beside the TEXT
 // attention of step t.  512-thread blocks: the attention body needs its 163 registers per lane, so the
 // text body runs with 8 waves x RPW context rows (L <= 8 RPW) instead of 16 x RPW/2.
-template <int RPW>
+template <int RPW, bool H16 = false>
 __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_vis_text_kernel(VisArgs v, VisSplit sp, int nv,
                                                                         TxtArgs t) {
     const int bid = blockIdx.x;
     if (bid < nv) {
         if (threadIdx.x >= VSP_NW * 64) return;
-        visual_split_body<1>(v, sp, bid % VSP_G, bid / VSP_G);
+        visual_split_body<1, false, H16>(v, sp, bid % VSP_G, bid / VSP_G);
     } else {
         text_attn_body<RPW, 0, SMALL_WAVES>(t, bid - nv);
     }
 }
 
-template <int MT, int CPW, int PHASE, bool APRO = false>
+template <int MT, int CPW, int PHASE, bool APRO = false, bool H16 = false>
 __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_vis_small_kernel(VisArgs v, VisSplit sp,
                                                                          int nv, SmallArgs b,
                                                                          int gxb) {
@@ -791,7 +797,7 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_vis_small_kernel(VisArg
         if (PHASE == 2)
             visual_split_body<2>(v, sp, 0, bid);
         else
-            visual_split_body<PHASE>(v, sp, bid % VSP_G, bid / VSP_G);
+            visual_split_body<PHASE, false, H16>(v, sp, bid % VSP_G, bid / VSP_G);
     } else {
         small_gemm_body<MT, CPW, false, false, APRO>(b, (bid - nv) % gxb, (bid - nv) / gxb);
     }
@@ -800,10 +806,12 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_vis_small_kernel(VisArg
 
 // scoring + glue of step t beside the merge of the attention partials of step t+1 (folded inference chain: the two
 // halves of the next step's LSTM input -- u_next from the glue, the attended feature from the merge -- land in one launch)
+// (H16 is the CANDIDATE table's storage: the phase-2 merge reads partials, never the table)
+template <bool H16>
 __global__ __launch_bounds__(SC_NW * 64) void pair_score_merge_kernel(ScoreArgs a, FGlue g, int nb, VisArgs v, VisSplit sp) {
     const int bid = blockIdx.x;
     if (bid < nb) {
-        score_glue_body(a, g, bid);
+        score_glue_body<H16>(a, g, bid);
     } else {
         if (threadIdx.x >= VSP_NW * 64) return;
         visual_split_body<2>(v, sp, 0, bid - nb);
@@ -1070,12 +1078,12 @@ __global__ __launch_bounds__(1024) void ctx_grad_kernel(const float* alpha, cons
 // Backward: the visual-attention backward of a step (needs the input gradient of the LSTM) beside the
 // recurrent data gradient dh0 = dgates W_hh (needs only dgates): independent, one launch.
 // Blocks [0, nv): attention backward (12 waves); the rest: the small product (threads >= 512 leave).
-template <int MT, int CPW>
+template <int MT, int CPW, bool H16 = false>
 __global__ __launch_bounds__(VIS_NW * 64) void pair_visbwd_small_kernel(VisArgs v, int nv, SmallArgs b,
                                                                        int gxb) {
     const int bid = blockIdx.x;
     if (bid < nv) {
-        visual_attn_body<1>(v, bid);
+        visual_attn_body<1, H16>(v, bid);
     } else {
         if (threadIdx.x >= SMALL_WAVES * 64) return;
         small_gemm_body<MT, CPW>(b, (bid - nv) % gxb, (bid - nv) / gxb);
@@ -1083,6 +1091,23 @@ __global__ __launch_bounds__(VIS_NW * 64) void pair_visbwd_small_kernel(VisArgs 
 }
 
 }  // namespace
+
+// Storage dispatch.  EVERY launcher below that takes a PanoSrc / CandSrc launches through one of these two macros (or
+// returns before launching), so a table registered as binary16 can only reach an instantiation that reads 8-byte chunks:
+// an fp32 read of it would run off the end of the table.  A half source in dense form is a caller's error.  The fp32
+// branch keeps the launch text -- and with it the name the in-process profile reports -- it always had.
+#define SF_LAUNCH_H16(half, k32, k16, ...)         \
+    do {                                           \
+        if (half) SF_LAUNCH(k16, __VA_ARGS__);     \
+        else SF_LAUNCH(k32, __VA_ARGS__);          \
+    } while (0)
+#define SF_LAUNCH_H16_AS(half, name, K, ...)                         \
+    do {                                                             \
+        if (half) SF_LAUNCH_AS(name "<f16>", K<true>, __VA_ARGS__);  \
+        else SF_LAUNCH_AS(name, K<false>, __VA_ARGS__);              \
+    } while (0)
+template <typename Src>
+static inline bool half_misuse(const Src& s) { return s.half && s.dense; }
 
 size_t visual_attn_split_floats(int B, int F) { return (size_t)B * VSP_G * (F + 64); }
 
@@ -1100,25 +1125,26 @@ int visual_attn(int mode, const PanoSrc& src, int B, const float* vec, int ldvec
     if (src.V > VIS_RPW * VIS_NW || src.V > 64 || F > VIS_CPL * 256 || (F & 3) ||
         (!src.dense && ((src.IMG & 3) || (src.LOC & 3))) || (ldvec & 3) || (ldo & 3))
         return SF_ERR_UNSUPPORTED;
+    if (half_misuse(src)) return SF_ERR_ARG;
     VisArgs a{src, vec, ldvec, alpha, out, ldo, drop, drop_col0, vec64, mode == 1 ? vec_slabs : 0, vec_slab_stride};
     if (mode != 1 && vec_slabs > 1) return SF_ERR_UNSUPPORTED;
     if (vec64) {        // float64 scores: the two-workgroup forward only (callers check visual_attn_f64_supported)
         if (mode != 0 || !split_part || !split_counter || !visual_attn_f64_supported(src, B)) return SF_ERR_UNSUPPORTED;
-        SF_LAUNCH(visual_attn_split_f64_kernel, dim3(VSP_G, B), dim3(VSP_NW * 64), 0, st, a,
-                  VisSplit{split_part, split_counter, nullptr});
+        SF_LAUNCH_H16_AS(src.half, "visual_attn_split_f64_kernel", visual_attn_split_f64_kernel, dim3(VSP_G, B),
+                         dim3(VSP_NW * 64), 0, st, a, VisSplit{split_part, split_counter, nullptr});
         return launch_status();
     }
     // small batches: two workgroups per sample (see visual_attn_split_kernel)
     if (mode == 0 && split_part && split_counter && src.V > (VSP_G - 1) * VSP_RPG &&
         src.V <= VSP_G * VSP_RPG && B <= VIS_SPLIT_MAX_B) {
-        SF_LAUNCH(visual_attn_split_kernel, dim3(VSP_G, B), dim3(VSP_NW * 64), 0, st, a,
-                           VisSplit{split_part, split_counter, nullptr});
+        SF_LAUNCH_H16_AS(src.half, "visual_attn_split_kernel", visual_attn_split_kernel, dim3(VSP_G, B),
+                         dim3(VSP_NW * 64), 0, st, a, VisSplit{split_part, split_counter, nullptr});
         return launch_status();
     }
     if (mode == 0)
-        SF_LAUNCH(visual_attn_kernel<0>, dim3(B), dim3(VIS_NW * 64), 0, st, a);
+        SF_LAUNCH_H16(src.half, visual_attn_kernel<0>, (visual_attn_kernel<0, true>), dim3(B), dim3(VIS_NW * 64), 0, st, a);
     else
-        SF_LAUNCH(visual_attn_kernel<1>, dim3(B), dim3(VIS_NW * 64), 0, st, a);
+        SF_LAUNCH_H16(src.half, visual_attn_kernel<1>, (visual_attn_kernel<1, true>), dim3(B), dim3(VIS_NW * 64), 0, st, a);
     return launch_status();
 }
 
@@ -1173,8 +1199,9 @@ int score_fwd(const CandSrc& src, int B, int D, const float* r, const float* wt,
     if (src.A > SC_NW || src.A < 1 || F > SC_CPL * 256 || (F & 3) ||
         (!src.dense && ((src.IMG & 3) || (src.LOC & 15))))
         return SF_ERR_UNSUPPORTED;
+    if (half_misuse(src)) return SF_ERR_ARG;
     ScoreArgs a{src, ldr, cst, r, wt, b_a, b_out, D, logit, nullptr, nullptr, CeSrc{}};
-    SF_LAUNCH(score_fwd_kernel, dim3(B), dim3(SC_NW * 64), 0, st, a);
+    SF_LAUNCH_H16_AS(src.half, "score_fwd_kernel", score_fwd_kernel, dim3(B), dim3(SC_NW * 64), 0, st, a);
     return launch_status();
 }
 
@@ -1186,8 +1213,9 @@ int score_glue_fwd(const CandSrc& src, int B, int D, const float* r, const float
     if (src.A > SC_NW || src.A < 1 || F > SC_CPL * 256 || (F & 3) ||
         (!src.dense && ((src.IMG & 3) || (src.LOC & 15))))
         return SF_ERR_UNSUPPORTED;
+    if (half_misuse(src)) return SF_ERR_ARG;
     ScoreArgs a{src, ldr, cst, r, wt, b_a, b_out, D, g.logit, nullptr, nullptr, CeSrc{}};
-    SF_LAUNCH(score_glue_kernel, dim3(B), dim3(SC_NW * 64), 0, st, a, g);
+    SF_LAUNCH_H16_AS(src.half, "score_glue_kernel", score_glue_kernel, dim3(B), dim3(SC_NW * 64), 0, st, a, g);
     return launch_status();
 }
 
@@ -1201,10 +1229,12 @@ int pair_score_merge(const CandSrc& src, int B, int D, const float* r, const flo
         return SF_ERR_UNSUPPORTED;
     if (!split_part || psrc.V <= (VSP_G - 1) * VSP_RPG || psrc.V > VSP_G * VSP_RPG || B > VIS_SPLIT_MAX_B || (ldo & 3))
         return SF_ERR_UNSUPPORTED;
+    if (half_misuse(src) || half_misuse(psrc)) return SF_ERR_ARG;
     ScoreArgs a{src, ldr, cst, r, wt, b_a, b_out, D, g.logit, nullptr, nullptr, CeSrc{}};
     VisArgs va{psrc, nullptr, 0, alpha, out, ldo, drop, drop_col0};
     const VisSplit sp{split_part, nullptr, g_trace};
-    SF_LAUNCH(pair_score_merge_kernel, dim3(2 * B), dim3(SC_NW * 64), 0, st, a, g, B, va, sp);
+    SF_LAUNCH_H16_AS(src.half, "pair_score_merge_kernel", pair_score_merge_kernel, dim3(2 * B), dim3(SC_NW * 64), 0, st, a,
+                     g, B, va, sp);
     return launch_status();
 }
 
@@ -1216,8 +1246,8 @@ int score_bwd(const CandSrc& src, int B, const float* dlogit, float* dr, float* 
         return SF_ERR_UNSUPPORTED;
     ScoreArgs a{src, F, nullptr, nullptr, nullptr, nullptr, nullptr, 0, const_cast<float*>(dlogit), dr, dc,
                 ce ? *ce : CeSrc{}};
-    if (ce && ce->ld < src.A) return SF_ERR_ARG;
-    SF_LAUNCH(score_bwd_kernel, dim3(B), dim3(SC_NW * 64), 0, st, a);
+    if ((ce && ce->ld < src.A) || half_misuse(src)) return SF_ERR_ARG;
+    SF_LAUNCH_H16_AS(src.half, "score_bwd_kernel", score_bwd_kernel, dim3(B), dim3(SC_NW * 64), 0, st, a);
     return launch_status();
 }
 
@@ -1300,17 +1330,20 @@ int pair_vis_text(const PanoSrc& src, int B, const float* vec, int ldvec, float*
         return SF_ERR_UNSUPPORTED;
     if (H > TXT_CPL * 256 || (H & 3) || (ldt & 3) || (ldwc & 3) || L < 1 || L > SMALL_WAVES * 10)
         return SF_ERR_UNSUPPORTED;
+    if (half_misuse(src)) return SF_ERR_ARG;
     VisArgs va{src, vec, ldvec, alpha, out, ldo, drop, drop_col0};
     const VisSplit sp{split_part, nullptr, g_trace};
     TxtArgs ta{ctx, mask, L, H, t, ldt, nullptr, 0, talpha, wc, ldwc, nullptr, ctx_row, nullptr};
     const int nv = VSP_G * B;
     const dim3 grid(nv + B), block(SMALL_WAVES * 64);
+#define SF_PVT(R) SF_LAUNCH_H16(src.half, (pair_vis_text_kernel<R>), (pair_vis_text_kernel<R, true>), grid, block, 0, st, va, sp, nv, ta)
     if (L <= SMALL_WAVES * 2)
-        SF_LAUNCH((pair_vis_text_kernel<2>), grid, block, 0, st, va, sp, nv, ta);
+        SF_PVT(2);
     else if (L <= SMALL_WAVES * 5)
-        SF_LAUNCH((pair_vis_text_kernel<5>), grid, block, 0, st, va, sp, nv, ta);
+        SF_PVT(5);
     else
-        SF_LAUNCH((pair_vis_text_kernel<10>), grid, block, 0, st, va, sp, nv, ta);
+        SF_PVT(10);
+#undef SF_PVT
     return launch_status();
 }
 
@@ -1342,10 +1375,11 @@ int pair_visbwd_small(const PanoSrc& src, int B, const float* vec, int ldvec, fl
     if (src.V > VIS_RPW * VIS_NW || src.V > 64 || F > VIS_CPL * 256 || (F & 3) ||
         (!src.dense && ((src.IMG & 3) || (src.LOC & 3))) || (ldvec & 3) || (ldo & 3))
         return SF_ERR_UNSUPPORTED;
+    if (half_misuse(src)) return SF_ERR_ARG;
     VisArgs va{src, vec, ldvec, alpha, out, ldo, drop, drop_col0, nullptr, vec_slabs, vec_slab_stride};
     const int nb = b.gx * b.gy;
-    SF_LAUNCH((pair_visbwd_small_kernel<1, 16>), dim3(B + nb), dim3(VIS_NW * 64), 0, st, va, B,
-                       b.args, b.gx);
+    SF_LAUNCH_H16(src.half, (pair_visbwd_small_kernel<1, 16>), (pair_visbwd_small_kernel<1, 16, true>), dim3(B + nb),
+                  dim3(VIS_NW * 64), 0, st, va, B, b.args, b.gx);
     return launch_status();
 }
 
@@ -1362,18 +1396,22 @@ int pair_vis_apro(const PanoSrc* src, int B, const float* vec, int ldvec, float*
         if (!split_part || src->V <= (VSP_G - 1) * VSP_RPG || src->V > VSP_G * VSP_RPG || B > VIS_SPLIT_MAX_B || F > VIS_CPL * 256 ||
             (F & 3) || (!src->dense && ((src->IMG & 3) || (src->LOC & 3))) || (ldvec & 3))
             return SF_ERR_UNSUPPORTED;
+        if (half_misuse(*src)) return SF_ERR_ARG;
         va = VisArgs{*src, vec, ldvec, nullptr, nullptr, 0, Dropout{}, 0};
         nv = VSP_G * B;
     }
     const VisSplit sp{split_part, nullptr, g_trace};
     const int nb = b.gx * b.gy;
     const dim3 grid(nv + nb), block(SMALL_WAVES * 64);
+    const int h16 = src ? src->half : 0;
+#define SF_PVA(M) SF_LAUNCH_H16(h16, (pair_vis_small_kernel<M, 4, 1, true>), (pair_vis_small_kernel<M, 4, 1, true, true>), grid, block, 0, st, va, sp, nv, b.args, b.gx)
     if (b.mt == 4)
-        SF_LAUNCH((pair_vis_small_kernel<4, 4, 1, true>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVA(4);
     else if (b.mt == 2)
-        SF_LAUNCH((pair_vis_small_kernel<2, 4, 1, true>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVA(2);
     else
-        SF_LAUNCH((pair_vis_small_kernel<1, 4, 1, true>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVA(1);
+#undef SF_PVA
     return launch_status();
 }
 
@@ -1392,30 +1430,36 @@ int pair_vis_small(const PanoSrc& src, int B, const float* vec, int ldvec, float
         F > VIS_CPL * 256 || (F & 3) || (!src.dense && ((src.IMG & 3) || (src.LOC & 3))) ||
         (ldvec & 3) || (ldo & 3))
         return SF_ERR_UNSUPPORTED;
+    if (half_misuse(src)) return SF_ERR_ARG;
     VisArgs va{src, vec, ldvec, alpha, out, ldo, drop, drop_col0};
     const int nv = (phase == 2 ? 1 : VSP_G) * B, nb = b.gx * b.gy;
     const dim3 grid(nv + nb), block(SMALL_WAVES * 64);
     const VisSplit sp{split_part, split_counter, g_trace};
+    // (phase 2 only merges partials and never reads the table: its one instantiation serves both storages)
+#define SF_PVS(M, C, P)                                                                                                 \
+    SF_LAUNCH_H16(src.half && P != 2, (pair_vis_small_kernel<M, C, P>), (pair_vis_small_kernel<M, C, P, false, P != 2>), grid, \
+                  block, 0, st, va, sp, nv, b.args, b.gx)
     if (wide && b.mt == 4 && phase == 0)
-        SF_LAUNCH((pair_vis_small_kernel<4, 2, 0>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVS(4, 2, 0);
     else if (wide && b.mt == 4)
-        SF_LAUNCH((pair_vis_small_kernel<4, 2, 1>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVS(4, 2, 1);
     else if (wide && b.mt == 2 && phase == 0)
-        SF_LAUNCH((pair_vis_small_kernel<2, 2, 0>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVS(2, 2, 0);
     else if (wide && b.mt == 2)
-        SF_LAUNCH((pair_vis_small_kernel<2, 2, 1>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVS(2, 2, 1);
     else if (wide && phase == 0)
-        SF_LAUNCH((pair_vis_small_kernel<1, 2, 0>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVS(1, 2, 0);
     else if (wide)
-        SF_LAUNCH((pair_vis_small_kernel<1, 2, 1>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVS(1, 2, 1);
     else if (phase == 0)
-        SF_LAUNCH((pair_vis_small_kernel<1, 8, 0>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVS(1, 8, 0);
     else if (phase == 1)
-        SF_LAUNCH((pair_vis_small_kernel<1, 8, 1>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVS(1, 8, 1);
     else if (b.cpw == 8)
-        SF_LAUNCH((pair_vis_small_kernel<1, 8, 2>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVS(1, 8, 2);
     else
-        SF_LAUNCH((pair_vis_small_kernel<1, 4, 2>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+        SF_PVS(1, 4, 2);
+#undef SF_PVS
     return launch_status();
 }
 

@@ -183,7 +183,8 @@ int gather_panorama(const PanoSrc& s, int B, float* out, hipStream_t st);
 int gather_candidates(const CandSrc& s, int B, float* all_u, float* is_valid, hipStream_t st);
 int gather_actions(const CandSrc& s, int B, const int* a, float* out, hipStream_t st, int ldo = 0);   // ldo: row stride of out (0 = F)
 int gather_path_actions(const float* table, int V, int IMG, int LOC, const int* vp, const int* act_view,
-                        const float* sincos, const int* act, int N, float* out, int ldo, hipStream_t st);
+                        const float* sincos, const int* act, int N, float* out, int ldo, hipStream_t st,
+                        int half = 0);     // half: `table` holds binary16 (sf_feature_table_f16)
 
 // bidirectional encoder on the per-step kernels: tokens in per-row reversed order, [forward | reverse] assembly of ctx
 // (+ dropout) and its transpose (sf_pointwise.hip)

@@ -250,6 +250,8 @@ __global__ __launch_bounds__(TPB) void embedding_rows_kernel(const float* table,
 }
 
 // ---- batched gathers from the HBM feature table (a11) -------------------------------------------
+// (H16: the table holds binary16, see sf_rows.h; chosen by the launchers)
+template <bool H16>
 __global__ __launch_bounds__(TPB) void gather_pano_kernel(PanoSrc s, int B, float* out) {
     const int n4 = (s.IMG + s.LOC) >> 2;
     const size_t total = (size_t)B * s.V * n4;
@@ -257,9 +259,10 @@ __global__ __launch_bounds__(TPB) void gather_pano_kernel(PanoSrc s, int B, floa
         const int c = (int)(i % n4);
         const size_t bv = i / n4;
         const int v = (int)(bv % s.V), b = (int)(bv / s.V);
-        reinterpret_cast<float4*>(out)[i] = pano_chunk(s, b, v, c);
+        reinterpret_cast<float4*>(out)[i] = pano_chunk<H16>(s, b, v, c);
     }
 }
+template <bool H16>
 __global__ __launch_bounds__(TPB) void gather_cand_kernel(CandSrc s, int B, float* all_u,
                                                           float* is_valid) {
     const int n4 = (s.IMG + s.LOC) >> 2;
@@ -268,10 +271,11 @@ __global__ __launch_bounds__(TPB) void gather_cand_kernel(CandSrc s, int B, floa
         const int c = (int)(i % n4);
         const size_t ba = i / n4;
         const int a = (int)(ba % s.A), b = (int)(ba / s.A);
-        reinterpret_cast<float4*>(all_u)[i] = cand_chunk(s, b, a, c);
+        reinterpret_cast<float4*>(all_u)[i] = cand_chunk<H16>(s, b, a, c);
         if (c == 0 && is_valid) is_valid[ba] = a < s.a_num[b] ? 1.f : 0.f;
     }
 }
+template <bool H16>
 __global__ __launch_bounds__(TPB) void gather_action_kernel(CandSrc s, int B, const int* act,
                                                             float* out, int ldo4) {     // ldo4: row stride in float4
     const int n4 = (s.IMG + s.LOC) >> 2;
@@ -279,14 +283,15 @@ __global__ __launch_bounds__(TPB) void gather_action_kernel(CandSrc s, int B, co
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < total; i += (size_t)gridDim.x * TPB) {
         const int c = (int)(i % n4), b = (int)(i / n4);
         const int a = act[b];
-        const CandRow row = cand_row(s, b, a);                   // a <= 0, padding or vp < 0: zeros
-        reinterpret_cast<float4*>(out)[(size_t)b * ldo4 + c] = cand_load(row, c, a > 0 && !row.zero, n4);
+        const CandRow row = cand_row<H16>(s, b, a);              // a <= 0, padding or vp < 0: zeros
+        reinterpret_cast<float4*>(out)[(size_t)b * ldo4 + c] = cand_load<H16>(row, c, a > 0 && !row.zero, n4);
     }
 }
 
 // The chosen-action embeddings of ALL path steps of a speaker batch (speaker.py:87-104: `action_embedding[a]` of
 // every (step, path), zeros for stop actions and padded steps) in one launch, written with a row stride -- i.e.
 // straight into the first half of the encoder's LSTM inputs.  Row n: table[vp[n], act_view[n]] || sin/cos groups.
+template <bool H16>
 __global__ __launch_bounds__(TPB) void gather_path_actions_kernel(const float* table, int V, int IMG, int LOC, const int* vp,
                                                                   const int* act_view, const float* sincos, const int* act,
                                                                   int N, float* out, int ldo) {
@@ -299,10 +304,14 @@ __global__ __launch_bounds__(TPB) void gather_path_actions_kernel(const float* t
         CandRow r;
         r.I4 = IMG >> 2;
         r.g4 = max(LOC >> 4, 1);
-        r.img = reinterpret_cast<const float4*>(table) + ((size_t)max(v, 0) * V + min(max(view, 0), V - 1)) * r.I4;
+        const size_t at = ((size_t)max(v, 0) * V + min(max(view, 0), V - 1)) * r.I4;
+        if (H16)
+            r.img16 = reinterpret_cast<const uint2*>(table) + at;
+        else
+            r.img = reinterpret_cast<const float4*>(table) + at;
         r.s0 = sc.x; r.s1 = sc.y; r.s2 = sc.z; r.s3 = sc.w;
         r.zero = false;
-        reinterpret_cast<float4*>(out + (size_t)n * ldo)[c] = cand_load(r, c, act[n] > 0 && v >= 0, n4);
+        reinterpret_cast<float4*>(out + (size_t)n * ldo)[c] = cand_load<H16>(r, c, act[n] > 0 && v >= 0, n4);
     }
 }
 
@@ -443,6 +452,7 @@ __global__ __launch_bounds__(TPB) void logprob_topk_kernel(float* logit, int ld,
 }
 
 // ---- follower per-step glue (follower.py:476-505): one wave per sample -----------------------------
+template <bool H16>
 __global__ __launch_bounds__(TPB) void follower_glue_kernel(FGlue g) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
@@ -454,11 +464,11 @@ __global__ __launch_bounds__(TPB) void follower_glue_kernel(FGlue g) {
     if (g.nav.on && lane < A) nav_advance_slot(g.nav, b, lane, at, gin.was_ended || at == 0);
     if (g.u_next) {                                              // follower.py:502
         const int n4 = (g.src.IMG + g.src.LOC) >> 2;
-        const CandRow row = cand_row(g.src, b, at);
+        const CandRow row = cand_row<H16>(g.src, b, at);
         for (int c0 = 0; c0 < n4; c0 += 64 * 9) {               // 9 straight-line loads per pass
             float4 x[9];
 #pragma unroll
-            for (int i = 0; i < 9; ++i) x[i] = cand_load(row, c0 + lane + 64 * i, !row.zero, n4);
+            for (int i = 0; i < 9; ++i) x[i] = cand_load<H16>(row, c0 + lane + 64 * i, !row.zero, n4);
 #pragma unroll
             for (int i = 0; i < 9; ++i) {
                 const int c = c0 + lane + 64 * i;
@@ -1063,14 +1073,23 @@ int embedding_rows(const float* table, int E, const int64_t* idx, int B, float* 
                        table, E, idx, B, out);
     return launch_status();
 }
+// Storage dispatch: every launcher that hands table rows to a kernel goes through this macro, so a table registered as
+// binary16 (src.half) only ever reaches the instantiation that reads 8-byte chunks.  The fp32 branch keeps its name.
+#define SF_LAUNCH_H16_AS(half, name, K, ...)                         \
+    do {                                                             \
+        if (half) SF_LAUNCH_AS(name "<f16>", K<true>, __VA_ARGS__);  \
+        else SF_LAUNCH_AS(name, K<false>, __VA_ARGS__);              \
+    } while (0)
 int gather_panorama(const PanoSrc& s, int B, float* out, hipStream_t st) {
-    SF_LAUNCH(gather_pano_kernel,
+    if (s.half && (s.dense || (s.IMG & 3) || (s.LOC & 3))) return SF_ERR_ARG;
+    SF_LAUNCH_H16_AS(s.half, "gather_pano_kernel", gather_pano_kernel,
                        dim3(grid1d((size_t)B * s.V * ((s.IMG + s.LOC) >> 2))), dim3(TPB), 0, st, s, B,
                        out);
     return launch_status();
 }
 int gather_candidates(const CandSrc& s, int B, float* all_u, float* is_valid, hipStream_t st) {
-    SF_LAUNCH(gather_cand_kernel,
+    if (s.half && (s.dense || (s.IMG & 3))) return SF_ERR_ARG;
+    SF_LAUNCH_H16_AS(s.half, "gather_cand_kernel", gather_cand_kernel,
                        dim3(grid1d((size_t)B * s.A * ((s.IMG + s.LOC) >> 2))), dim3(TPB), 0, st, s, B,
                        all_u, is_valid);
     return launch_status();
@@ -1079,14 +1098,15 @@ int gather_actions(const CandSrc& s, int B, const int* a, float* out, hipStream_
     const int F = s.IMG + s.LOC;
     if (ldo == 0) ldo = F;
     if ((ldo & 3) || ldo < F) return SF_ERR_UNSUPPORTED;
-    SF_LAUNCH(gather_action_kernel, dim3(grid1d((size_t)B * (F >> 2))),
+    if (s.half && (s.dense || (s.IMG & 3))) return SF_ERR_ARG;
+    SF_LAUNCH_H16_AS(s.half, "gather_action_kernel", gather_action_kernel, dim3(grid1d((size_t)B * (F >> 2))),
                        dim3(TPB), 0, st, s, B, a, out, ldo >> 2);
     return launch_status();
 }
 int gather_path_actions(const float* table, int V, int IMG, int LOC, const int* vp, const int* act_view,
-                        const float* sincos, const int* act, int N, float* out, int ldo, hipStream_t st) {
+                        const float* sincos, const int* act, int N, float* out, int ldo, hipStream_t st, int half) {
     if ((IMG & 3) || (LOC & 15) || (ldo & 3)) return SF_ERR_UNSUPPORTED;
-    SF_LAUNCH(gather_path_actions_kernel, dim3(grid1d((size_t)N * ((IMG + LOC) >> 2))), dim3(TPB), 0, st, table, V, IMG,
+    SF_LAUNCH_H16_AS(half, "gather_path_actions_kernel", gather_path_actions_kernel, dim3(grid1d((size_t)N * ((IMG + LOC) >> 2))), dim3(TPB), 0, st, table, V, IMG,
               LOC, vp, act_view, sincos, act, N, out, ldo);
     return launch_status();
 }
@@ -1186,7 +1206,8 @@ int logprob_topk(float* logit, int ld, int N, int n, const int* n_valid, int k, 
 }
 int follower_glue_fwd(const FGlue& g, hipStream_t st) {
     if (g.src.A > 64) return SF_ERR_UNSUPPORTED;
-    SF_LAUNCH(follower_glue_kernel, dim3(ceil_div(g.B, TPB / 64)), dim3(TPB), 0, st, g);
+    if (g.src.half && g.src.dense) return SF_ERR_ARG;
+    SF_LAUNCH_H16_AS(g.src.half, "follower_glue_kernel", follower_glue_kernel, dim3(ceil_div(g.B, TPB / 64)), dim3(TPB), 0, st, g);
     return launch_status();
 }
 int softmax_ce_bwd(int B, int N, int ld, const float* logit, const int64_t* target, int ignore,

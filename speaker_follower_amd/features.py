@@ -12,6 +12,7 @@ import csv
 import ctypes as C
 import json
 import sys
+import weakref
 
 import numpy as np
 import torch
@@ -52,9 +53,36 @@ def cand_sincos(rel_heading, rel_elevation):
     return np.stack((np.sin(h), np.cos(h), np.sin(e), np.cos(e)), axis=-1).astype(np.float32)
 
 
-def tsv_to_bin(tsv_path, bin_path):
+DTYPES = {'fp32': torch.float32, 'fp16': torch.float16}
+FILE_DTYPES = {'fp32': 'float32', 'fp16': 'float16'}     # the "dtype" key of '<bin>.json' (absent: float32)
+CHECK_ROWS = 256        # viewpoint rows rounded / checked at a time (never a second copy of the whole table)
+
+
+def _dtype_name(dtype):
+    if dtype not in DTYPES:
+        raise ValueError("dtype must be 'fp32' or 'fp16' (got %r)" % (dtype,))
+    return dtype
+
+
+def round_to_fp16(rows, row0=0):
+    """fp32 [r, V, IMG] tensor -> torch.float16 by torch's own conversion (round to nearest even).  The kernels blend
+    table rows with x * 0 and rely on finite features, so a NaN in the input or a magnitude that rounds to inf is a
+    ValueError naming the first offending row (`row0` + its index in `rows`)."""
+    half = rows.to(torch.float16)
+    bad = ~torch.isfinite(half.reshape(half.shape[0], -1)).all(dim=1)
+    if bool(bad.any()):
+        r = int(torch.nonzero(bad)[0, 0])
+        raise ValueError('feature table row %d does not fit fp16 storage: it holds a NaN, an infinity or a magnitude '
+                         'that rounds to infinity (fp16 max is 65504)' % (row0 + r))
+    return half
+
+
+def tsv_to_bin(tsv_path, bin_path, dtype='fp32'):
     """One-shot converter (N4): the reference's ResNet TSV -> flat little-endian fp32 file
-    [n][36][2048] + '<bin>.json' {ids, shape}.  Streams row by row (the full table is 3.1 GB)."""
+    [n][36][2048] + '<bin>.json' {ids, shape}.  Streams row by row (the full table is 3.1 GB).
+    dtype='fp16' writes binary16 rows (rounded like FeatureStore(dtype='fp16') rounds) and records
+    "dtype": "float16" in the json; a json without the key describes an fp32 file."""
+    half = _dtype_name(dtype) == 'fp16'
     csv.field_size_limit(sys.maxsize)
     names = ['scanId', 'viewpointId', 'image_w', 'image_h', 'vfov', 'features']
     ids = []
@@ -63,21 +91,59 @@ def tsv_to_bin(tsv_path, bin_path):
             buf = base64.b64decode(item['features'])
             if len(buf) != NUM_VIEWS * MEAN_POOLED_DIM * 4:
                 raise ValueError('row %s_%s: %d feature bytes' % (item['scanId'], item['viewpointId'], len(buf)))
+            if half:
+                row = torch.from_numpy(np.frombuffer(buf, np.float32).reshape(1, NUM_VIEWS, MEAN_POOLED_DIM).copy())
+                buf = round_to_fp16(row, len(ids)).numpy().tobytes()
             out.write(buf)
             ids.append(item['scanId'] + '_' + item['viewpointId'])
+    meta = {'ids': ids, 'shape': [len(ids), NUM_VIEWS, MEAN_POOLED_DIM]}
+    if half:
+        meta['dtype'] = FILE_DTYPES['fp16']
     with open(bin_path + '.json', 'w') as f:
-        json.dump({'ids': ids, 'shape': [len(ids), NUM_VIEWS, MEAN_POOLED_DIM]}, f)
+        json.dump(meta, f)
     return len(ids)
 
 
 class FeatureStore:
-    """The feature table in HBM + viewpoint-id index."""
+    """The feature table in HBM + viewpoint-id index.
 
-    def __init__(self, table, ids=None, device='cuda', loc=LOC_DIM):
+    dtype='fp16' keeps the table as torch.float16 (half the HBM bytes and half of what every table kernel reads): it
+    is rounded ONCE, with torch's `.to(torch.float16)`, and the kernels widen each value exactly as they load it, so
+    the store behaves bit for bit like an fp32 store built from `table.half().float()`.  `table` stays the device
+    tensor in its storage dtype (`rows_f32` widens rows); the location table, the dense materialisations and every
+    output are fp32.  The library knows an fp16 table by its address (sf_feature_table_f16): the store registers it
+    here and forgets it when it is collected, so a store must outlive every captured graph that ran with it -- as it
+    must for its memory anyway."""
+
+    def __init__(self, table, ids=None, device='cuda', loc=LOC_DIM, dtype='fp32'):
+        self.dtype = _dtype_name(dtype)
         if isinstance(table, np.ndarray):
-            table = torch.from_numpy(np.ascontiguousarray(table, np.float32))
-        self.table = table.to(device=device, dtype=torch.float32).contiguous()
+            if table.dtype != np.float16:
+                table = np.ascontiguousarray(table, np.float32)
+            table = torch.from_numpy(np.ascontiguousarray(table))
+        if table.dim() != 3:
+            raise ValueError('feature table must be [n, V, IMG] (got %s)' % (tuple(table.shape),))
+        if self.dtype == 'fp16' and table.dtype != torch.float16:
+            # rounded and checked chunk by chunk into the one preallocated fp16 tensor
+            out = torch.empty(table.shape, dtype=torch.float16, device=device)
+            for r0 in range(0, table.shape[0], CHECK_ROWS):
+                out[r0:r0 + CHECK_ROWS].copy_(round_to_fp16(table[r0:r0 + CHECK_ROWS].to(torch.float32), r0))
+            self.table = out
+        else:
+            self.table = table.to(device=device, dtype=DTYPES[self.dtype]).contiguous()
+            if self.dtype == 'fp16':            # already binary16 (from_bin): nothing to round, finiteness still holds
+                for r0 in range(0, self.table.shape[0], CHECK_ROWS):
+                    round_to_fp16(self.table[r0:r0 + CHECK_ROWS], r0)
         self.n, self.V, self.IMG = self.table.shape
+        if self.dtype == 'fp16' and self.IMG % 4:
+            raise ValueError('fp16 storage needs IMG %% 4 == 0 (got %d)' % self.IMG)
+        # The library tells the storage by the table's ADDRESS.  An fp32 store clears its address too: the caching
+        # allocator can hand the address of a collected fp16 table to an fp32 one.
+        if self.table.numel():
+            addr = self.table.data_ptr()
+            call('sf_feature_table_f16', C.c_void_p(addr), 1 if self.dtype == 'fp16' else 0)
+            if self.dtype == 'fp16':
+                weakref.finalize(self, _lib.lib.sf_feature_table_f16, C.c_void_p(addr), 0)
         self.LOC = loc
         self.F = self.IMG + loc
         self.device = self.table.device
@@ -85,7 +151,7 @@ class FeatureStore:
         self.index = {k: i for i, k in enumerate(ids)} if ids is not None else None
 
     @classmethod
-    def from_tsv(cls, path, device='cuda'):
+    def from_tsv(cls, path, device='cuda', dtype='fp32'):
         """Reads the reference's ResNet-152 TSV (scanId, viewpointId, image_w, image_h, vfov,
         base64 fp32 36x2048; env.py:359-370, scripts/precompute_img_features.py:31)."""
         csv.field_size_limit(sys.maxsize)
@@ -96,25 +162,39 @@ class FeatureStore:
                 ids.append(item['scanId'] + '_' + item['viewpointId'])       # env.py:377-378
                 buf = base64.b64decode(item['features'])
                 rows.append(np.frombuffer(buf, np.float32).reshape(NUM_VIEWS, MEAN_POOLED_DIM))
-        return cls(np.stack(rows), ids, device)
+        return cls(np.stack(rows), ids, device, dtype=dtype)
 
     @classmethod
-    def from_bin(cls, path, device='cuda', chunk_rows=512):
+    def from_bin(cls, path, device='cuda', chunk_rows=512, dtype=None):
         """Flat table written by `tsv_to_bin` (path + '.json' holds the ids and shape): the file is
         memory-mapped and uploaded in chunks straight into ONE preallocated HBM tensor, so start-up
-        costs a sequential read instead of minutes of TSV / base64 parsing."""
+        costs a sequential read instead of minutes of TSV / base64 parsing.  dtype=None keeps the
+        file's storage (the json's "dtype"; absent: fp32); naming the other one converts chunk by
+        chunk during the upload (fp32 -> fp16 rounds and checks like the constructor does)."""
         with open(path + '.json') as f:
             meta = json.load(f)
         n, V, IMG = meta['shape']
-        mm = np.memmap(path, dtype=np.float32, mode='r', shape=(n, V, IMG))
-        table = torch.empty(n, V, IMG, dtype=torch.float32, device=device)
+        stored = meta.get('dtype', FILE_DTYPES['fp32'])
+        if stored not in FILE_DTYPES.values():
+            raise ValueError('%s.json: unknown dtype %r' % (path, stored))
+        file16 = stored == FILE_DTYPES['fp16']
+        dtype = _dtype_name(('fp16' if file16 else 'fp32') if dtype is None else dtype)
+        mm = np.memmap(path, dtype=np.float16 if file16 else np.float32, mode='r', shape=(n, V, IMG))
+        table = torch.empty(n, V, IMG, dtype=DTYPES[dtype], device=device)
         for r0 in range(0, n, chunk_rows):
             r1 = min(n, r0 + chunk_rows)
-            table[r0:r1].copy_(torch.from_numpy(np.array(mm[r0:r1])))
-        return cls(table, meta['ids'], device)
+            rows = torch.from_numpy(np.array(mm[r0:r1]))
+            if dtype == 'fp16':
+                rows = round_to_fp16(rows, r0)       # (a binary16 file: only the finiteness check)
+            table[r0:r1].copy_(rows)
+        return cls(table, meta['ids'], device, dtype=dtype)
 
     def row(self, scan_id, viewpoint_id):
         return self.index[scan_id + '_' + viewpoint_id]
+
+    def rows_f32(self, idx):
+        """table[idx] widened to fp32 (exact), on the table's device."""
+        return self.table[idx].to(torch.float32)
 
     # ---- pointer structs for the C ABI (tensors must stay alive while the call is enqueued) -----
     def pano(self, vp, view):
