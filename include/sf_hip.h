@@ -639,10 +639,12 @@ int sf_speaker_decoder_fwd(const sf_spk_decoder_w* w, int B, int E, int H, int T
  * (seed, stream, row0 + b) -- csrc/sf_sampling.h; oracle/rng.py mirrors it.  `stream` names the word step (callers
  * pass site + t; sf_speaker_decode uses stream + t for its step t); row0 = global id of local row 0 (data-parallel
  * shards draw what the unsharded batch would).
- * LIMIT: the draw is two-level over at most 32 x 32 probabilities -- feedback 2 (`sample`) needs vocab <= 1024 in
- * sf_speaker_glue_fwd and sf_speaker_decode (SF_ERR_UNSUPPORTED above; the host classes raise NotImplementedError).
- * The live vocabularies fit (train_vocab.txt 991, sub_train_vocab.txt 935); trainval_vocab.txt (1 086) does not:
- * teacher / argmax passes over it run on the per-step entry points (tests/test_gpu_speaker.py). */
+ * LIMIT: the draw is two-level over ceil(vocab / 32) slots of 32 columns.  vocab <= 1024 (32 slots; the live
+ * vocabularies train_vocab.txt 991 and sub_train_vocab.txt 935): the SAME draw in the persistent word loop
+ * (sf_speaker_decode) and in the per-step glue (sf_speaker_glue_fwd, sf_speaker_words_fwd).  1025 ... 4096
+ * (trainval_vocab.txt: 1 086; sf_speaker_sample_max_vocab()): the per-step glue only -- sf_speaker_decode returns
+ * SF_ERR_UNSUPPORTED there for every feedback, as it always has.  Above 4096 feedback 2 is SF_ERR_UNSUPPORTED everywhere.
+ * The host classes run `sample` above 1024 only when asked to (SpeakerEngine.wide_sample; NotImplementedError otherwise). */
 typedef struct sf_sample {
     uint32_t seed, stream;
     int32_t row0;
@@ -678,6 +680,8 @@ int sf_speaker_decoder_bwd(const sf_spk_decoder_w* w, const sf_spk_decoder_g* g,
 int sf_speaker_glue_fwd(int B, int vocab, int ldv, const float* logit, const int64_t* target,
                         int feedback, int pad_idx, int eos_idx, uint8_t* ended, int64_t* w_t,
                         float* score, float* nll_term, float* live, const sf_sample* sample, sf_stream stream);
+/* The widest vocabulary feedback 2 draws over in sf_speaker_glue_fwd / sf_speaker_words_fwd: 4096 (see sf_sample). */
+int sf_speaker_sample_max_vocab(void);
 /* The speaker's loss from the per-step (NLL sum, live count) table (speaker.py:182, 192-197): the step means are added
  * only up to and including the first step at which EVERY row has produced EOS (the reference leaves its word loop
  * there); gscale[t] = 1 / count for those steps, 0 behind them.  words [T+1,B] as written by the glue / the decode

@@ -283,6 +283,7 @@ _SIGNATURES = {
                                    i64p, c_p, c_f, c_f, c_f, c_f, c_f, c_f, c_f, P(Sample)] + WS),
     'sf_speaker_glue_fwd': (C.c_int, [i32, i32, i32, c_f, i64p, i32, i32, i32, c_p, i64p, c_f, c_f,
                                       c_f, P(Sample), c_p]),
+    'sf_speaker_sample_max_vocab': (C.c_int, []),
     'sf_speaker_loss_finalize': (C.c_int, [c_f, i64p, i32, i32, i32, c_f, c_f, c_p]),
     'sf_speaker_glue_bwd': (C.c_int, [i32, i32, i32, c_f, i64p, i32, c_f, c_f, c_p]),
     'sf_speaker_encoder_fwd': (C.c_int, [P(VisualW), P(LstmW), c_f, c_f, P(Pano), i32, i32, i32, i32, c_f, c_f, c_f, c_f,

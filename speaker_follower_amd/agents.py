@@ -1001,6 +1001,19 @@ class Seq2SeqSpeaker(object):
         feats = getattr(self.env, 'image_features_list', None) or [None]
         return getattr(feats[0], 'store', None) or getattr(self, 'store', None)
 
+    # `sample` feedback over a vocabulary of more than 1024 words (trainval_vocab.txt: 1 086): drawn by the per-step glue
+    # kernel over up to sf_speaker_sample_max_vocab() words (speaker.check_sample_vocab).  Off by default: such a pass
+    # raises NotImplementedError, as it always has.
+    wide_sample = False
+
+    def _speaker_engine(self, store):
+        """The agent's speaker.SpeakerEngine over `store` (kept between calls), with the agent's switches."""
+        from . import speaker as spk
+        if getattr(self, '_engine', None) is None or self._engine.store is not store:
+            self._engine = spk.SpeakerEngine(self.encoder, self.decoder, store)
+        self._engine.wide_sample = self.wide_sample
+        return self._engine
+
     SCORE_CHUNK = 128          # rows of one persistent word-loop launch (csrc/sf_persist.hip)
     # large teacher-forced scoring sweeps: the full chunks as replayed graphs on two streams (speaker.SpeakerSweep) instead
     # of launch-by-launch issue: -3.5 ms per minibatch of 64 instructions once every (stream, path-step count) graph is
@@ -1063,8 +1076,7 @@ class Seq2SeqSpeaker(object):
         (vp_row, viewIndex, absViewIndex, rel_heading, rel_elevation, is_stop) of routes lo..hi-1, route-major."""
         from . import speaker as spk
         B = len(n)
-        if getattr(self, '_engine', None) is None or self._engine.store is not store:
-            self._engine = spk.SpeakerEngine(self.encoder, self.decoder, store)
+        self._speaker_engine(store)
         eng = self._engine
         training = self.decoder.training
         chunked = B > 2 * self.SCORE_CHUNK and not training and not torch.is_grad_enabled() and eng.group is None
@@ -1109,8 +1121,7 @@ class Seq2SeqSpeaker(object):
     def _issue_scores(self, n, rows_of, encoded_instructions, feedback, store, mark=lambda name: None):
         """Issues the chunked scoring sweep (no host sync) and returns what _finish_scores needs to collect it."""
         from . import speaker as spk
-        if getattr(self, '_engine', None) is None or self._engine.store is not store:
-            self._engine = spk.SpeakerEngine(self.encoder, self.decoder, store)
+        self._speaker_engine(store)
         eng = self._engine
         B = len(n)
         S = self._score_steps(encoded_instructions, feedback)
@@ -1140,11 +1151,12 @@ class Seq2SeqSpeaker(object):
             # the full chunks as replayed graphs on two streams (speaker.SpeakerSweep: one captured pass per stream and
             # path-step count; the encoder steps of one chunk run beside the other stream's word recurrence), the
             # remainder issued launch by launch behind them
-            key = (id(store), S, self.instruction_len)
+            key = (id(store), S, self.instruction_len, self.wide_sample)
             sw = self.__dict__.setdefault('_score_sweeps', {}).get(key)
             if sw is None or sw.enc is not self.encoder or sw.dec is not self.decoder:
                 sw = self._score_sweeps[key] = spk.SpeakerSweep(self.encoder, self.decoder, store, self.SCORE_CHUNK, S,
-                                                                feedback='teacher', Lmax=self.instruction_len, with_scores=True)
+                                                                feedback='teacher', Lmax=self.instruction_len, with_scores=True,
+                                                                wide_sample=self.wide_sample)
             full = [self._index_batch(n, rows_of, encoded_instructions, lo, lo + self.SCORE_CHUNK)
                     for lo in range(0, n_full * self.SCORE_CHUNK, self.SCORE_CHUNK)]
             pend.graphs = (sw, sw.issue(full))
@@ -1227,9 +1239,7 @@ class Seq2SeqSpeaker(object):
             stale = self.__dict__.pop('_pending_scores', None)
             if stale is not None:
                 torch.cuda.synchronize()
-            from . import speaker as spk
-            if getattr(self, '_engine', None) is None or self._engine.store is not store:
-                self._engine = spk.SpeakerEngine(self.encoder, self.decoder, store)
+            self._speaker_engine(store)
             if self._engine.group is not None:
                 return None
             first = np.concatenate(([0], np.cumsum(n)))
@@ -1264,6 +1274,9 @@ class Seq2SeqSpeaker(object):
                 raise RuntimeError('index-form observations need a features.FeatureStore (env.image_features_list[0].store '
                                    'or speaker.store)')
             return self._score_on_device(path_obs, path_actions, encoded_instructions, feedback, store)
+        if feedback == 'sample':                              # (before the encoder runs: nothing is launched for a refusal)
+            from .speaker import check_sample_vocab
+            check_sample_vocab(self.decoder.vocab_size, self.wide_sample)
         start_obs, feats, acts, path_mask, _, encoded_instructions, perm = \
             self._batch_observations_and_actions(path_obs, path_actions, encoded_instructions)
         dev = self._device()
@@ -1380,12 +1393,12 @@ class Seq2SeqSpeaker(object):
                 if it['instr_id'] in ids:
                     looped = True
                 ids.add(it['instr_id'])
-        key = (id(store), B, self.instruction_len)
+        key = (id(store), B, self.instruction_len, self.wide_sample)
         cached = self.__dict__.get('_test_sweep')
         if cached is None or cached[0] != key:
             cached = self._test_sweep = (key, spk.SpeakerSweep(self.encoder, self.decoder, store, B, self.instruction_len,
                                                                feedback='argmax', Lmax=self.instruction_len,
-                                                               with_scores=True), store)
+                                                               with_scores=True, wide_sample=self.wide_sample), store)
         sweep = cached[1]
         words, scores, cnt = sweep.run([self._routes_of(items, store)[0] for items in drawn])
         S = self.instruction_len
@@ -1450,8 +1463,7 @@ class Seq2SeqSpeaker(object):
                 and getattr(self.env, 'host_table', 1) is None and hasattr(self.env, 'graphs')):
             return False
         from . import speaker as spk
-        if getattr(self, '_engine', None) is None or self._engine.store is not store:
-            self._engine = spk.SpeakerEngine(self.encoder, self.decoder, store)
+        self._speaker_engine(store)
         eng, dev = self._engine, store.device
         if eng.group is not None:
             return False

@@ -2270,6 +2270,7 @@ int sf_speaker_glue_fwd(int B, int vocab, int ldv, const float* logit, const int
     return speaker_glue_fwd(B, vocab, ldv, logit, target, feedback, pad_idx, eos_idx, ended, w_t,
                             score, nll_term, live, S(stream), sample);
 }
+int sf_speaker_sample_max_vocab(void) { return speaker_sample_max_vocab(); }
 
 // ---- a8 SpeakerEncoderLSTM.forward (model.py:437-457), all path steps in one call -------------------------------------
 static int speaker_encoder_fwd_i(const sf_visual_fold64* fold64, const sf_visual_w* vw, const sf_lstm_w* lw, const float* w_e2d, const float* b_e2d,

@@ -253,6 +253,7 @@ int speaker_glue_fwd(int B, int vocab, int ldv, const float* logit, const int64_
                      int feedback, int pad_idx, int eos_idx, uint8_t* ended, int64_t* w_t,
                      float* score, float* nll_term, float* live, hipStream_t st, const sf_sample* sample = nullptr,
                      int rps = 0);      // rps > 0: S stacked steps of rps rows each (row m sets ended[m % rps])
+int speaker_sample_max_vocab();         // widest vocabulary feedback 2 draws over (speaker_glue_wide_sample_kernel)
 int speaker_loss_finalize(const float* sum_cnt, const int64_t* words, int eos, int T, int B, float* loss, float* gscale,
                           hipStream_t st);
 int reduce_terms(const float* term, const float* live, int T, int B, float* sum_cnt,

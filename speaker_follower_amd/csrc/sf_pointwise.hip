@@ -620,6 +620,136 @@ __global__ __launch_bounds__(TPB) void speaker_glue_kernel(SGlue g) {
         if (w == g.eos_idx) g.ended[g.rps ? b % g.rps : b] = 1;  // speaker.py:190-191
     }
 }
+// feedback 2 over 1024 < vocab <= 4096 (trainval_vocab.txt: 1 086): the same draw over ns = ceil(vocab / 32) slots,
+// in panels of 1024 columns.  In panel p lane l holds columns [1024 p + 16 l, + 16): slot s = 32 p + (l >> 1), the
+// lane-to-column map of speaker_sample_row.  Level 1's prefix is carried from panel to panel in slot order; every
+// panel keeps its slots' level-2 pick (one register per lane), so no column is read again once the slot is known.
+// Max, arg max and lse are formed in the column order of speaker_glue_kernel (lane + 64 i): nll_term and live are
+// bit for bit what a teacher / argmax launch writes for the same logits.
+constexpr int WIDE_PANELS = 4;
+constexpr int WIDE_SAMPLE_MAX_VOCAB = 1024 * WIDE_PANELS;
+__global__ __launch_bounds__(TPB) void speaker_glue_wide_sample_kernel(SGlue g) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
+    if (b >= g.B) return;
+    const float* row = g.logit + (size_t)b * g.ldv;
+    constexpr int NV = 16;
+    float v[WIDE_PANELS][NV];
+#pragma unroll
+    for (int p = 0; p < WIDE_PANELS; ++p) {
+        if (1024 * p < g.vocab) {                                // wave-uniform
+#pragma unroll
+            for (int i = 0; i < NV; ++i) v[p][i] = row[min(lane + 64 * (NV * p + i), g.vocab - 1)];
+        }
+    }
+    const int64_t tgt = g.target[b];
+    const float ltgt = row[min(max((int)tgt, 0), g.vocab - 1)];
+    float m = -INFINITY;
+    int am = 0;
+#pragma unroll
+    for (int p = 0; p < WIDE_PANELS; ++p) {
+        if (1024 * p < g.vocab) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int n = lane + 64 * (NV * p + i);
+                if (n < g.vocab && v[p][i] > m) { m = v[p][i]; am = n; }
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float om = __shfl_xor(m, off, WAVE);
+        const int oa = __shfl_xor(am, off, WAVE);
+        if (om > m || (om == m && oa < am)) { m = om; am = oa; }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int p = 0; p < WIDE_PANELS; ++p) {
+        if (1024 * p < g.vocab) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) s += (lane + 64 * (NV * p + i) < g.vocab) ? expf(v[p][i] - m) : 0.f;
+        }
+    }
+    const float lse = m + logf(wave_sum(s));
+    float u1, u2;
+    sample_uniforms(g.sample_seed + 0x9E3779B9u * site_value(g.sample_site), g.sample_stream, (uint32_t)(g.sample_row0 + b), &u1, &u2);
+    float ps[WIDE_PANELS], cdf[WIDE_PANELS];
+    int pick[WIDE_PANELS];
+    float carry = 0.f;                                           // level 1's inclusive prefix behind the panels so far
+#pragma unroll
+    for (int p = 0; p < WIDE_PANELS; ++p) {
+        ps[p] = 0.f;
+        cdf[p] = 0.f;
+        pick[p] = 0;
+        if (1024 * p < g.vocab) {
+            const int c0 = 1024 * p + 16 * lane;
+            float x[16], e[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) x[j] = row[min(c0 + j, g.vocab - 1)];
+            float ml = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) ml = c0 + j < g.vocab ? fmaxf(ml, x[j]) : ml;
+            const float ms = fmaxf(ml, __shfl_xor(ml, 1, WAVE));
+            float sl = 0.f;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                e[j] = c0 + j < g.vocab ? wexp(x[j], ms) : 0.f;   // (a slot of all -inf: every weight 0, not NaN)
+                sl += e[j];
+            }
+            const float so = __shfl_xor(sl, 1, WAVE);
+            const float zs = (lane & 1) ? so + sl : sl + so;
+            // level 2: this slot's column
+            const float thr2 = u2 * zs;
+            float cum = (lane & 1) ? so : 0.f;
+            int pk = 0x7FFFFFFF;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                cum += e[j];
+                if (pk == 0x7FFFFFFF && cum > thr2 && e[j] > 0.f) pk = c0 + j;
+            }
+            pk = min(pk, __shfl_xor(pk, 1, WAVE));
+            if (pk == 0x7FFFFFFF) pk = min(32 * (32 * p + (lane >> 1)) + 31, g.vocab - 1);
+            pick[p] = pk;
+            // level 1: this panel's slots behind the prefix of the panels before it
+            const float w = (lane & 1) ? 0.f : zs * wexp(ms, m);
+            float c = w;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const float up = __shfl_up(c, off, WAVE);
+                if (lane >= off) c += up;
+            }
+            c += carry;
+            carry = __shfl(c, 63, WAVE);
+            ps[p] = w;
+            cdf[p] = c;
+        }
+    }
+    const float thr1 = u1 * carry;                               // carry = Z
+    int ws = -1;
+#pragma unroll
+    for (int p = 0; p < WIDE_PANELS; ++p) {
+        if (1024 * p < g.vocab && ws < 0) {                      // wave-uniform: ballots and broadcasts
+            const unsigned long long hit = __ballot(ps[p] > 0.f && cdf[p] > thr1);
+            if (hit) ws = __shfl(pick[p], (int)__ffsll((long long)hit) - 1, WAVE);
+        }
+    }
+    if (ws < 0) {                                                // the threshold rounded up to Z: the arg max's slot
+#pragma unroll
+        for (int p = 0; p < WIDE_PANELS; ++p)
+            if (p == (am >> 10)) ws = __shfl(pick[p], 2 * ((am >> 5) & 31), WAVE);
+    }
+    ws = min(max(ws, 0), g.vocab - 1);                           // (every pick already lies inside the row)
+    const float lws = row[ws];
+    if (lane == 0) {
+        const int64_t w = (int64_t)ws;
+        g.w_t[b] = w;
+        g.score[b] = (w != g.pad_idx) ? lws - lse : 0.f;         // speaker.py:179-180 (per-step term)
+        const bool lv = tgt != g.pad_idx;
+        g.nll_term[b] = lv ? lse - ltgt : 0.f;                   // speaker.py:182
+        g.live[b] = lv ? 1.f : 0.f;
+        if (w == g.eos_idx) g.ended[g.rps ? b % g.rps : b] = 1;  // speaker.py:190-191
+    }
+}
 
 // deterministic per-step reduction of the loss terms: sum_cnt[t] = (sum_b term, sum_b live)
 __global__ __launch_bounds__(64) void reduce_terms_kernel(const float* term, const float* live,
@@ -1219,13 +1349,17 @@ int softmax_ce_bwd(int B, int N, int ld, const float* logit, const int64_t* targ
 int speaker_glue_fwd(int B, int vocab, int ldv, const float* logit, const int64_t* target,
                      int feedback, int pad_idx, int eos_idx, uint8_t* ended, int64_t* w_t,
                      float* score, float* nll_term, float* live, hipStream_t st, const sf_sample* sample, int rps) {
-    if (feedback == 2 && (!sample || vocab > 1024)) return feedback == 2 && !sample ? SF_ERR_ARG : SF_ERR_UNSUPPORTED;
+    if (feedback == 2 && (!sample || vocab > WIDE_SAMPLE_MAX_VOCAB)) return feedback == 2 && !sample ? SF_ERR_ARG : SF_ERR_UNSUPPORTED;
     SGlue g{B, vocab, ldv, logit, target, feedback, pad_idx, eos_idx, ended, w_t, score, nll_term,
             live, sample ? sample->seed : 0u, sample ? sample->stream : 0u, sample ? sample->row0 : 0,
             sample && sample->stream_dev ? sample->stream_dev : site_zero(), rps};
-    SF_LAUNCH(speaker_glue_kernel, dim3(ceil_div(B, TPB / 64)), dim3(TPB), 0, st, g);
+    if (feedback == 2 && vocab > 1024)                            // the draw over more than 32 slots: its own kernel
+        SF_LAUNCH(speaker_glue_wide_sample_kernel, dim3(ceil_div(B, TPB / 64)), dim3(TPB), 0, st, g);
+    else
+        SF_LAUNCH(speaker_glue_kernel, dim3(ceil_div(B, TPB / 64)), dim3(TPB), 0, st, g);
     return launch_status();
 }
+int speaker_sample_max_vocab() { return WIDE_SAMPLE_MAX_VOCAB; }
 int reduce_terms(const float* term, const float* live, int T, int B, float* sum_cnt,
                  hipStream_t st) {
     SF_LAUNCH(reduce_terms_kernel, dim3(T), dim3(64), 0, st, term, live, B, sum_cnt);

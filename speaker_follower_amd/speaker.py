@@ -61,6 +61,20 @@ class SpeakerState:
     pass
 
 
+def check_sample_vocab(vocab, wide):
+    """`sample` feedback over `vocab` words: up to 1024 the two-level draw of sf_sampling.h runs everywhere; above that
+    only the per-step glue draws (up to sf_speaker_sample_max_vocab() words), and only when asked to -- `wide` is the
+    caller's `wide_sample` switch.  No device work: raises NotImplementedError or returns."""
+    limit = int(_lib.lib.sf_speaker_sample_max_vocab())
+    if vocab > limit:
+        raise NotImplementedError('sample feedback draws with the two-level sampler of sf_sampling.h: vocab <= %d '
+                                  '(%d here)' % (limit, vocab))
+    if vocab > 1024 and not wide:
+        raise NotImplementedError('sample feedback draws with the two-level sampler of sf_sampling.h: vocab <= 1024 '
+                                  '(%d here); wide_sample = True decodes vocabularies up to %d words on the per-step '
+                                  'kernels' % (vocab, limit))
+
+
 class _SpeakerLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, engine, state, *params):
@@ -107,6 +121,10 @@ class _StepNllFn(torch.autograd.Function):
 
 
 class SpeakerEngine:
+    # `sample` feedback over more than 1024 words (trainval_vocab.txt: 1 086): the per-step glue draws over up to
+    # sf_speaker_sample_max_vocab() words (sf_sampling.h).  Off by default: such a pass raises NotImplementedError
+    wide_sample = False
+
     def __init__(self, encoder, decoder, store, group=None):
         self.encoder, self.decoder, self.store = encoder, decoder, store
         self.group = group
@@ -123,11 +141,16 @@ class SpeakerEngine:
         self.fold_query = True          # inference: the path encoder's attention query through the float64 fold (runtime.visual_query_fold)
         self.fallbacks = 0              # passes re-issued on the per-step kernels after a persistent-launch fault (run)
 
+    def _check_feedback(self, feedback):
+        if feedback == 'sample':
+            check_sample_vocab(self.decoder.vocab_size, self.wide_sample)
+
     def capture(self, batch, steps, feedback='teacher'):
         """hipGraph of one inference scoring / decoding pass: returns (replay, state); the state's
         tensors are overwritten by every replay (same contract as FollowerEngine.capture)."""
         # `sample` feedback: the sampling stream must differ between replays, and kernel arguments are frozen in a graph --
         # the pass reads it from a device word that replay() writes first (sf_sample.stream_dev)
+        self._check_feedback(feedback)
         sampled = feedback == 'sample'
         ctl = torch.zeros(4, dtype=torch.int32, device=self.store.device) if sampled else None
         with torch.no_grad():
@@ -237,6 +260,7 @@ class SpeakerEngine:
     def score(self, batch, steps, feedback='teacher', train=None):
         """Returns a SpeakerState: .words [S,B], .logits [S,B,vocab], .step_scores [S,B],
         .loss (differentiable), .ctx [B,Tp,H]."""
+        self._check_feedback(feedback)
         if getattr(self.decoder, 'use_input_att_feed', False):
             return self._score_modules(batch, steps, feedback, train)
         enc, dec, store = self.encoder, self.decoder, self.store
@@ -427,6 +451,7 @@ class SpeakerEngine:
     def run(self, batch, steps, feedback='teacher', train=None):
         """`score` + the fault check of the persistent word loop: one host sync, and the fault protocol of DESIGN.md
         (runtime.reissue_per_step) -- the SAME pass, same dropout / sampling sites, again on the per-step kernels."""
+        self._check_feedback(feedback)
         site = self.site_next
         st = self.score(batch, steps, feedback, train)
         dev = self.store.device
@@ -582,12 +607,16 @@ class SpeakerSweep:
     persistent launch of one 4-wave workgroup per CU that leaves most issue slots idle.  Every persistent launch is
     checked through the fault word at the end (runtime.take_fault); a sweep that saw a fault is re-run -- all of it -- on
     graphs captured with the per-step kernels (`fallbacks` counts them).  `sample` feedback needs vocab <= 1024 (the
-    two-level draw of sf_sampling.h); the pinned staging buffers grow with the longest path met."""
+    two-level draw of sf_sampling.h), or `wide_sample=True` (check_sample_vocab: the graphs then hold the per-step
+    kernels); the pinned staging buffers grow with the longest path met."""
 
     def __init__(self, encoder, decoder, store, batch_size, words, feedback='argmax', Lmax=80, n_streams=1, slots=2,
-                 with_scores=False):
+                 with_scores=False, wide_sample=False):
         """with_scores: every minibatch also returns its per-word scores [S,B] and its per-step (sum, count) table [S,2]
         (teacher-forced scoring sweeps: Seq2SeqSpeaker._issue_scores)."""
+        if feedback == 'sample':
+            check_sample_vocab(decoder.vocab_size, wide_sample)
+        self.wide_sample = wide_sample
         self.with_scores = with_scores
         self.enc, self.dec, self.store = encoder, decoder, store
         self.B, self.S, self.Lmax, self.feedback = batch_size, words, Lmax, feedback
@@ -595,9 +624,6 @@ class SpeakerSweep:
         self.slots = slots
         self.graphs = {}                 # (stream index, Tp, persistent) -> (replay, state, device staging buffer)
         self.fallbacks = 0               # sweeps re-run on the per-step kernels after a persistent-launch fault
-        if feedback == 'sample' and decoder.vocab_size > 1024:
-            raise NotImplementedError('sample feedback draws with the two-level sampler of sf_sampling.h: vocab <= 1024 '
-                                      '(%d here)' % decoder.vocab_size)
         cap = packed_layout(batch_size, 16, Lmax)['bytes']
         self.pinned = [[torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(slots)] for _ in self.streams]
         self.free_ev = [[None] * slots for _ in self.streams]
@@ -617,6 +643,7 @@ class SpeakerSweep:
             with torch.cuda.stream(self.streams[si]):
                 eng = SpeakerEngine(self.enc, self.dec, self.store)
                 eng.persistent = persistent
+                eng.wide_sample = self.wide_sample
                 replay, st = eng.capture(batch, self.S, self.feedback)
                 words16 = torch.empty(self.S, self.B, dtype=torch.int16, device=dev)
             torch.cuda.synchronize(dev)
