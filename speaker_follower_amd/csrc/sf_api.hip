@@ -782,36 +782,6 @@ int sf_eltwise_prod_scoring_bwd(const sf_scoring_w* w, const sf_scoring_g* g, co
                          S(stream));
 }
 
-// ---- a6 AttnDecoderLSTM.forward (model.py:377-397) -------------------------------------------------
-int sf_attn_decoder_fwd(const sf_decoder_w* w, const sf_pano* X, const sf_cands* U, int B, int H,
-                        int D, int L, const float* u_prev, const float* h0, const float* c0,
-                        const float* ctx, const uint8_t* ctx_mask, const int32_t* ctx_row,
-                        const sf_decoder_tape* tp, const sf_follower_glue* glue,
-                        const sf_dropout* drop, uint32_t step_id,
-                        void* ws, size_t ws_bytes, sf_stream stream) {
-    SF_ENTER();
-    SF_CHECK_ARG(w && X && U && h0 && c0 && ctx && tp && B > 0 && L > 0 && (!glue || glue_ok(U, glue)));
-    Arena ar = arena(ws, ws_bytes);
-    hipStream_t st = S(stream);
-    const PanoSrc xs = pano(X);
-    const int F = xs.IMG + xs.LOC;
-    const Dropout d_in = make_dropout(drop, 2 * step_id, 2), d_h = make_dropout(drop, 2 * step_id + 1, 2);
-    // model.py:389  feature, alpha_v = visual_attention(h_0, X)  -> straight into xin[:, F:2F]
-    TRY(visual_fwd_i(&w->visual, xs, B, H, D, h0, tp->xin + F, 2 * F, tp->alpha_v, tp->t_v, tp->q,
-                     d_in, F, ar, st, w->fold));
-    // model.py:391-392  drop(cat(u_prev, feature))
-    if (u_prev) TRY(dropout_copy(u_prev, F, B, F, tp->xin, 2 * F, d_in, 0, st));
-    // model.py:393-394  LSTMCell; dropout(h_1) lands in cat2[:, H:2H]
-    TRY(lstm_fwd_i(&w->lstm, B, 2 * F, H, tp->xin, 2 * F, h0, c0, tp->h1, tp->c1, tp->gates,
-                   tp->cat2 + H, 2 * H, d_h, ar, st));
-    // model.py:395  text attention
-    TRY(softdot_fwd_i(&w->text, B, L, H, nullptr, 0, ctx, ctx_mask, tp->h_tilde, tp->alpha, tp->cat2,
-                      tp->t_text, ar, st, ctx_row));
-    // model.py:396  action logits
-    return scoring_fwd_i(&w->action, cands(U), B, H, D, tp->h_tilde, tp->logit, tp->t_a, tp->wt,
-                         tp->r, ar, st, glue, w->fold);
-}
-
 // ---- a6, software-pipelined across steps ---------------------------------------------------------------
 // head(t)   = visual half of step t: t_v, q, visual attention -> tape->xin[:, F:2F], alpha_v
 // tail(t)   = LSTM cell, text attention, scoring (+ glue) of step t, and -- when X_next is given --
@@ -826,17 +796,12 @@ static int decoder_head_a(const sf_decoder_w* w, const sf_pano* X, int B, int H,
     return visual_fwd_i(&w->visual, xs, B, H, D, h0, tp->xin + F, 2 * F, tp->alpha_v, tp->t_v, tp->q,
                         make_dropout(drop, 2 * step_id, 2), F, ar, S(stream), w->fold);
 }
-static int decoder_head_i(const sf_decoder_w* w, const sf_pano* X, int B, int H, int D,
-                          const float* h0, const sf_decoder_tape* tp, const sf_dropout* drop,
-                          uint32_t step_id, void* ws, size_t ws_bytes, sf_stream stream) {
-    return decoder_head_a(w, X, B, H, D, h0, tp, drop, step_id, arena(ws, ws_bytes), stream);
-}
 
 int sf_attn_decoder_head_fwd(const sf_decoder_w* w, const sf_pano* X, int B, int H, int D,
                              const float* h0, const sf_decoder_tape* tp, const sf_dropout* drop,
                              uint32_t step_id, void* ws, size_t ws_bytes, sf_stream stream) {
     SF_ENTER();
-    return decoder_head_i(w, X, B, H, D, h0, tp, drop, step_id, ws, ws_bytes, stream);
+    return decoder_head_a(w, X, B, H, D, h0, tp, drop, step_id, arena(ws, ws_bytes), stream);
 }
 
 static int plan_linear(const float* x, int ldx, const float* wgt, int ldw, const float* b, int M,
@@ -854,6 +819,322 @@ struct TextFold {
     const sf_decoder_fold* mats;      // optional (sf_follower_episode.chain_fold): the THREE-launch chain
 };
 
+// ---- tail(t): what every launch chain of the step reads (decoder_tail_i builds it behind the cell, tail_dispatch picks
+// ONE chain).  A chain is a function of two parts: a PLAN that launches nothing (plan_linear / linear_small_plan, scratch
+// takes, shape limits) and the ISSUE of its launches.  So SF_ERR_UNSUPPORTED from a chain means "nothing was launched,
+// try the next chain" -- never a half-issued step -- and any other status ends the step.
+struct TailStep {
+    const sf_decoder_w* w;
+    CandSrc us;
+    int B, H, D, L, F;
+    const sf_decoder_tape *tp, *tn;     // the tape of this step; of the next one (null: nothing of it is prepared here)
+    const sf_follower_glue* glue;
+    Dropout d_h, dn_in;                 // of h1 (into cat2[:, H:]); of the next step's LSTM input
+    PanoSrc xn;                         // the panorama of the next step, where `has_xn`
+    bool has_xn;
+    bool paired, query_only, last_step;
+    const float* ctx;
+    const uint8_t* ctx_mask;
+    const int32_t* ctx_row;
+    Arena ar;
+    hipStream_t st;
+};
+
+// a launch BEHIND a chain's first one: the step is half issued, "unsupported" can no longer mean "try the next chain"
+static inline int issued(int rc) { return rc == SF_ERR_UNSUPPORTED ? SF_ERR_LAUNCH : rc; }
+
+// the second body of a paired launch left empty (no next step to prepare)
+static SmallPlan empty_plan(SmallPlan p) {
+    p.gx = p.gy = 0;
+    return p;
+}
+
+// the visual attention of step t+1 on its query tn->q -- beside the small product `b` (phases: pair_vis_small) ...
+static int vis_next_beside(const TailStep& s, float* part, unsigned* counter, const SmallPlan& b, int phase = 0) {
+    return pair_vis_small(s.xn, s.B, s.tn->q, s.F, s.tn->alpha_v, s.tn->xin + s.F, 2 * s.F, s.dn_in, s.F, part, counter, b,
+                          s.st, phase);
+}
+// ... or as a launch of its own
+static int vis_next_alone(const TailStep& s, float* part, const Arena& ar) {
+    return visual_attn(0, s.xn, s.B, s.tn->q, s.F, s.tn->alpha_v, s.tn->xin + s.F, 2 * s.F, s.dn_in, s.F, s.st, part,
+                       part ? ar.tickets() : nullptr);
+}
+
+static int score_tail(const TailStep& s, const Arena& ar, const sf_decoder_fold* fold, bool t_a_done = false) {
+    const sf_decoder_tape* tp = s.tp;
+    return scoring_fwd_i(&s.w->action, s.us, s.B, s.H, s.D, tp->h_tilde, tp->logit, tp->t_a, tp->wt, tp->r, ar, s.st, s.glue,
+                         fold, t_a_done);
+}
+
+// scratch of the two folded chains
+struct FoldScratch {
+    float *tpart, *ybuf, *zbuf, *rext, *part;
+    unsigned* tcount;
+    int ldp;
+    bool ok;         // everything was there, and B within the split attention's limit
+};
+// `af` is the chain's own COPY of the step's arena: a chain that declines hands the whole workspace to the next one
+// (B = 300 fits only because of this).  rext_n: the [r | c] rows of the three-launch chain (0: none).
+static FoldScratch fold_scratch(const TailStep& s, Arena& af, size_t rext_n) {
+    FoldScratch f{};
+    f.tpart = af.take(text_fold_part_floats(s.B, s.H));
+    // (leading dimension H + 16: rows of a power-of-two stride share a few cache sets, CHANGELOG round 5 "2c")
+    f.ldp = s.H + 16;
+    f.ybuf = af.take((size_t)s.B * f.ldp);
+    f.zbuf = af.take((size_t)s.B * f.ldp);
+    f.rext = rext_n ? af.take(rext_n) : nullptr;
+    f.tcount = af.tickets() ? af.tickets() + TEXT_TICKET : nullptr;
+    f.part = (s.paired && s.B <= 1024) ? af.take(visual_attn_split_floats(s.B, s.F)) : nullptr;
+    f.ok = f.tpart && f.ybuf && f.zbuf && (f.rext || !rext_n) && (f.part || !s.paired) && f.tcount && s.B <= VIS_SPLIT_MAX_B;
+    return f;
+}
+
+// the last launch of a folded chain: logit = u . r (+ the folded constant, or the biases through wt) -- with the glue and
+// the merge of the next step's attention partials `merge_part` in the same launch, with the glue alone, or bare
+static int fold_score(const TailStep& s, float* merge_part, const float* r, int ldr, const float* cst, const float* wt) {
+    const sf_scoring_w& a = s.w->action;
+    const float *b_a = wt ? a.b_a : nullptr, *b_out = wt ? a.b_out : nullptr;
+    if (merge_part)
+        return pair_score_merge(s.us, s.B, s.D, r, wt, b_a, b_out, make_glue(s.us, s.B, s.tp->logit, s.glue), s.xn,
+                                s.tn->alpha_v, s.tn->xin + s.F, 2 * s.F, s.dn_in, s.F, merge_part, s.st, ldr, cst);
+    if (s.glue)
+        return score_glue_fwd(s.us, s.B, s.D, r, wt, b_a, b_out, make_glue(s.us, s.B, s.tp->logit, s.glue), s.st, ldr, cst);
+    return score_fwd(s.us, s.B, s.D, r, wt, b_a, b_out, s.tp->logit, s.st, ldr, cst);
+}
+
+// Folded text stage + folded query / scoring products (sf_decoder_fold through sf_follower_episode.chain_fold):
+// THREE dependent launches behind the cell --
+//   (1) folded text attention  ||  y = W_out[:, H:] h1  ||  q' = M_v h1 + c_v      (t_v' is never formed)
+//   (2) [r | c] = M_a tanh(z + y) + c_a (A-prologue)   ||  visual-attention partials of step t+1
+//   (3) scoring + glue (logit = u . r + c)             ||  merge of the partials
+// (a device-resident environment: (2) is the product alone, the attention follows the environment step)
+static int tail_fold3(const TailStep& s, const TextFold& tf) {
+    const sf_decoder_fold* fm = tf.mats;
+    const sf_decoder_tape *tp = s.tp, *tn = s.tn;
+    const int B = s.B, H = s.H, F = s.F;
+    // ---- plan
+    Arena af = s.ar;
+    const FoldScratch f = fold_scratch(s, af, (size_t)B * (F + 4));
+    SmallPlan py, pq, pm;
+    bool ok = f.ok && fm->m_v && fm->c_v && fm->m_a && fm->c_a &&
+              plan_linear(tp->cat2 + H, 2 * H, s.w->text.w_out + H, 2 * H, nullptr, B, H, H, EPI_NONE, f.ybuf, f.ldp, &py) == SF_OK;
+    if (ok && !s.last_step) ok = plan_linear(tp->h1, H, fm->m_v, H, fm->c_v, B, F, H, EPI_NONE, tn->q, F, &pq) == SF_OK;
+    else if (ok) pq = empty_plan(py);
+    if (ok) {
+        Seg sg{f.ybuf, f.ldp, fm->m_a, H, H};
+        LinearOut o{};
+        o.y = f.rext; o.ldy = F + 4; o.bias = fm->c_a; o.epi = EPI_NONE;
+        ok = linear_small_plan(&sg, 1, B, F + 4, o, &pm) && pm.cpw == 4 && py.mt == 1 && py.cpw == 4 && pq.cpw == 4;
+        pm.args.apro_part = f.zbuf;
+        pm.args.apro_stride = f.ldp;
+    }
+    if (!ok) return SF_ERR_UNSUPPORTED;          // (shapes outside the instantiations: the four-launch chain)
+    // ---- issue (the first launch checks its shapes before it launches: it may still decline)
+    TRY(pair_textfold_small_small(tf.ctx_q, tf.ctx_o, s.ctx_mask, B, s.L, H, tp->cat2 + H, 2 * H, f.tpart, f.tcount, f.zbuf,
+                                  f.ldp, tp->alpha, py, pq, s.st));
+    TRY(issued(pair_vis_apro(s.paired ? &s.xn : nullptr, B, s.paired ? tn->q : nullptr, F, f.part, pm, s.st)));
+    if (s.paired && !s.glue)                     // (no glue: the module-API step; merge by its own launch)
+        TRY(issued(vis_next_beside(s, f.part, nullptr, empty_plan(py), 2)));
+    return issued(fold_score(s, s.paired && s.glue ? f.part : nullptr, f.rext, F + 4, f.rext + F, nullptr));
+}
+
+// Folded text stage (inference; sf_attention.hip: text_fold_body): FOUR dependent launches behind the cell
+// instead of six:
+//   (1) folded text attention (4 groups per sample, merged by the last arriver)  ||  y = W_out[:, H:] h1  ||  t_v' = W_h h1 + b_h
+//   (2) t_a = W_h tanh(z + y) + b_h, wt = t_a * w_out (A-prologue)   ||  q' = W_v^T t_v'
+//   (3) r = W_a^T wt            ||  visual attention of step t+1 (partials, ticket, merge by the last arriver)
+//   (4) scoring + glue
+// (query_only -- a device-resident environment: the panorama of step t+1 is not known yet -- stage (3) is the
+// r product alone and the attention follows the environment step, sf_attn_decoder_attend_fwd)
+static int tail_fold4(const TailStep& s, const TextFold& tf) {
+    const sf_visual_w* vw = &s.w->visual;
+    const sf_scoring_w* aw = &s.w->action;
+    const sf_decoder_tape *tp = s.tp, *tn = s.tn;
+    const int B = s.B, H = s.H, D = s.D, F = s.F;
+    // ---- plan
+    Arena af = s.ar;
+    const FoldScratch f = fold_scratch(s, af, 0);
+    SmallPlan py, pv, pta, pq, pr;
+    bool ok = f.ok &&
+        plan_linear(tp->cat2 + H, 2 * H, s.w->text.w_out + H, 2 * H, nullptr, B, H, H, EPI_NONE, f.ybuf, f.ldp, &py) == SF_OK &&
+        plan_linear(tp->wt, D, aw->w_a_t, D, nullptr, B, F, D, EPI_NONE, tp->r, F, &pr) == SF_OK;
+    if (ok && !s.last_step) {
+        ok = plan_linear(tp->h1, H, vw->w_h, H, vw->b_h, B, D, H, EPI_NONE, tn->t_v, D, &pv) == SF_OK &&
+             plan_linear(tn->t_v, D, vw->w_v_t, D, nullptr, B, F, D, EPI_NONE, tn->q, F, &pq) == SF_OK;
+    } else if (ok) {                                       // no next step: the second bodies of (1) and (2) are empty
+        pv = empty_plan(py);
+        pq = empty_plan(pr);
+    }
+    if (ok) {
+        Seg sg{f.ybuf, f.ldp, aw->w_h, H, H};
+        LinearOut o{};
+        o.y = tp->wt; o.ldy = D; o.bias = aw->b_h; o.mul = aw->w_out; o.y_pre = tp->t_a;
+        o.ldy_pre = D; o.epi = EPI_MUL;
+        ok = linear_small_plan(&sg, 1, B, D, o, &pta) && pta.mt == 1 && pta.cpw == 4 && pq.cpw == 2 && pr.cpw == 2;
+        pta.args.apro_part = f.zbuf;                            // (the merged attention sum of launch (1))
+        pta.args.apro_stride = f.ldp;
+    }
+    if (!ok) return SF_ERR_UNSUPPORTED;          // (shapes outside the instantiations: the unfolded stages)
+    // ---- issue (the first launch checks its shapes before it launches: it may still decline)
+    TRY(pair_textfold_small_small(tf.ctx_q, tf.ctx_o, s.ctx_mask, B, s.L, H, tp->cat2 + H, 2 * H, f.tpart, f.tcount, f.zbuf,
+                                  f.ldp, tp->alpha, py, pv, s.st));
+    TRY(issued(pair_apro_small(pta, pq, s.st)));
+    // sf_debug_fold_merge_with_glue: partials beside r, their merge beside the scoring + glue launch (same depth, no
+    // in-launch ticket; its shape limits are score_glue_fwd's and pair_vis_small's)
+    const bool merge_late = s.paired && s.glue && g_fold_merge_with_glue;
+    if (merge_late) TRY(issued(vis_next_beside(s, f.part, nullptr, pr, 1)));
+    else if (s.paired) TRY(issued(vis_next_beside(s, f.part, af.tickets(), pr, 0)));
+    else TRY(issued(launch_small_plan_x(pr, s.st)));
+    return issued(fold_score(s, merge_late ? f.part : nullptr, tp->r, 0, nullptr, tp->wt));
+}
+
+// Folded inference step (sf_decoder_fold): two dependent stages fewer, and the attention
+// partials of step t+1 ride beside the text attention (the longest small stage) instead of
+// stretching the h~ product:
+//   (1) t_text = W_in h1                  ||  q' = M_v h1 + c_v
+//   (2) text attention                    ||  visual-attention partials of step t+1
+//   (3) h~ = tanh(W_out [wc ; h1])        ||  merge of the partials
+//   (4) [r | c] = M_a h~ + c_a            (5) scoring + glue
+// (never declines: a stage whose paired launch has no instantiation is issued as its plain launches)
+static int tail_decoder_fold(const TailStep& s) {
+    const sf_softdot_w* tw = &s.w->text;
+    const sf_decoder_fold* fm = s.w->fold;
+    const sf_decoder_tape *tp = s.tp, *tn = s.tn;
+    const int B = s.B, H = s.H, L = s.L, F = s.F;
+    // ---- plan (stage (1) keeps the whole arena, the later ones what the partials leave)
+    Arena ar = s.ar;
+    SmallPlan pa, pb, ph;
+    const bool ok1 =
+        plan_linear(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, &pa) == SF_OK &&
+        plan_linear(tp->h1, H, fm->m_v, H, fm->c_v, B, F, H, EPI_NONE, tn->q, F, &pb) == SF_OK;
+    float* part = B <= 1024 ? ar.take(visual_attn_split_floats(B, F)) : nullptr;
+    const bool ok3 = part && plan_linear(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H, EPI_TANH,
+                                         tp->h_tilde, H, &ph) == SF_OK;
+    // ---- issue
+    if (!ok1 || pair_small_small(pa, pb, s.st) != SF_OK) {
+        TRY(linear_plain(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, s.ar, s.st));
+        TRY(linear_plain(tp->h1, H, fm->m_v, H, fm->c_v, B, F, H, EPI_NONE, tn->q, F, s.ar, s.st));
+    }
+    bool split = false;
+    if (ok3) {
+        const int rc = pair_vis_text(s.xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, s.dn_in, F, part, s.ctx,
+                                     s.ctx_mask, L, H, tp->t_text, H, tp->alpha, tp->cat2, 2 * H, s.ctx_row, s.st);
+        if (rc == SF_OK) split = true;
+        else if (rc != SF_ERR_UNSUPPORTED) return rc;
+    }
+    if (split && vis_next_beside(s, part, nullptr, ph, 2) != SF_OK)
+        return SF_ERR_LAUNCH;            // the partials exist: the merge must not be skipped
+    if (!split) {
+        TRY(text_attn_fwd(s.ctx, s.ctx_mask, B, L, H, tp->t_text, H, tp->alpha, tp->cat2, 2 * H, s.st, s.ctx_row));
+        TRY(linear_plain(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H, EPI_TANH, tp->h_tilde, H, ar, s.st));
+        TRY(vis_next_alone(s, part, ar));
+    }
+    return score_tail(s, ar, fm);
+}
+
+// Stages (1) and (2) of the unfolded chains, each as one paired launch or -- where that has no instantiation -- as its
+// two plain launches (the paired chain and its query-only variant):
+//   (1) t_text = W_in dropout(h1)   ||   t_v' = W_h h1 + b_h
+//   (2) text attention              ||   q' = W_v^T t_v'
+static int text_and_query(const TailStep& s) {
+    const sf_softdot_w* tw = &s.w->text;
+    const sf_visual_w* vw = &s.w->visual;
+    const sf_decoder_tape *tp = s.tp, *tn = s.tn;
+    const int B = s.B, H = s.H, D = s.D, L = s.L, F = s.F;
+    SmallPlan pa, pb;
+    const bool ok1 =
+        plan_linear(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, &pa) == SF_OK &&
+        plan_linear(tp->h1, H, vw->w_h, H, vw->b_h, B, D, H, EPI_NONE, tn->t_v, D, &pb) == SF_OK;
+    if (!ok1 || pair_small_small(pa, pb, s.st) != SF_OK) {
+        TRY(linear_plain(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, s.ar, s.st));
+        TRY(linear_plain(tp->h1, H, vw->w_h, H, vw->b_h, B, D, H, EPI_NONE, tn->t_v, D, s.ar, s.st));
+    }
+    const bool ok2 = plan_linear(tn->t_v, D, vw->w_v_t, D, nullptr, B, F, D, EPI_NONE, tn->q, F, &pa) == SF_OK;
+    if (!ok2 || pair_small_text(pa, s.ctx, s.ctx_mask, B, L, H, tp->t_text, H, tp->alpha, tp->cat2,
+                                2 * H, s.ctx_row, s.st) != SF_OK) {
+        TRY(text_attn_fwd(s.ctx, s.ctx_mask, B, L, H, tp->t_text, H, tp->alpha, tp->cat2, 2 * H, s.st, s.ctx_row));
+        TRY(linear_plain(tn->t_v, D, vw->w_v_t, D, nullptr, B, F, D, EPI_NONE, tn->q, F, s.ar, s.st));
+    }
+    return SF_OK;
+}
+
+// The paired unfolded chain: (1), (2) above, then
+//   (3) h~ = tanh(W_out [wc ; h1])   ||   visual attention of step t+1, per-group partials
+//   (4) t_a = W_h h~ + b_h, wt = t_a * w_out   ||   ... merge of the partials
+// (the attention is not needed before the next gate product: its two halves ride with two
+// stages of the text / scoring chain instead of stretching one of them)
+// (never declines: (3) / (4) fall back to h~ beside the whole attention, then to the two plain launches)
+static int tail_paired(const TailStep& s) {
+    const sf_softdot_w* tw = &s.w->text;
+    const sf_scoring_w* aw = &s.w->action;
+    const sf_decoder_tape* tp = s.tp;
+    const int B = s.B, H = s.H, D = s.D, F = s.F;
+    // ---- plan of (3) and (4) ((1) and (2) keep the whole arena, the later stages what the partials leave)
+    Arena ar = s.ar;
+    float* part = B <= 1024 ? ar.take(visual_attn_split_floats(B, F)) : nullptr;
+    SmallPlan ph, pc;
+    const bool ok3 = part && plan_linear(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H,
+                                         EPI_TANH, tp->h_tilde, H, &ph) == SF_OK;
+    bool ok4 = false;
+    if (ok3) {
+        Seg sg{tp->h_tilde, H, aw->w_h, H, H};
+        LinearOut o{};
+        o.y = tp->wt; o.ldy = D; o.bias = aw->b_h; o.mul = aw->w_out; o.y_pre = tp->t_a;
+        o.ldy_pre = D; o.epi = EPI_MUL;
+        ok4 = linear_small_plan(&sg, 1, B, D, o, &pc) && pc.mt == 1 && (pc.cpw == 4 || pc.cpw == 8);
+    }
+    // ---- issue
+    TRY(text_and_query(s));
+    if (ok4 && vis_next_beside(s, part, nullptr, ph, 1) == SF_OK) {
+        TRY(vis_next_beside(s, part, nullptr, pc, 2));
+        return score_tail(s, ar, nullptr, true);
+    }
+    if (!ok3 || vis_next_beside(s, part, ar.tickets(), ph) != SF_OK) {
+        TRY(linear_plain(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H, EPI_TANH, tp->h_tilde, H, ar, s.st));
+        TRY(vis_next_alone(s, part, ar));
+    }
+    return score_tail(s, ar, nullptr);
+}
+
+// tape_next WITHOUT X_next: the next panorama is not known yet (it depends on this step's action: a
+// device-resident environment).  Only the query of the next step's visual attention (t_v', q': they need
+// nothing but h1) rides beside the text stages; the attention itself follows the environment step
+// (sf_attn_decoder_attend_fwd).
+static int tail_query_only(const TailStep& s) {
+    const sf_decoder_tape* tp = s.tp;
+    TRY(text_and_query(s));
+    TRY(linear_plain(tp->cat2, 2 * s.H, s.w->text.w_out, 2 * s.H, nullptr, s.B, s.H, 2 * s.H, EPI_TANH, tp->h_tilde, s.H,
+                     s.ar, s.st));
+    return score_tail(s, s.ar, nullptr);
+}
+
+// The plain step: text attention and scoring, and -- with a next panorama but no transposed W_v to pair its query
+// with -- the whole visual half of step t+1 behind them.
+static int tail_plain(const TailStep& s) {
+    const sf_decoder_tape *tp = s.tp, *tn = s.tn;
+    TRY(softdot_fwd_i(&s.w->text, s.B, s.L, s.H, nullptr, 0, s.ctx, s.ctx_mask, tp->h_tilde, tp->alpha, tp->cat2,
+                      tp->t_text, s.ar, s.st, s.ctx_row));
+    if (s.has_xn)
+        TRY(visual_fwd_i(&s.w->visual, s.xn, s.B, s.H, s.D, tp->h1, tn->xin + s.F, 2 * s.F, tn->alpha_v, tn->t_v, tn->q,
+                         s.dn_in, s.F, s.ar, s.st, s.w->fold));
+    return score_tail(s, s.ar, s.w->fold);
+}
+
+// The order of preference.  The folded chains (inference: no dropout of h1, no row indirection of the context, the
+// episode's TextFold) may decline -- before their first launch, see TailStep -- and hand the step to the next one.
+static int tail_dispatch(const TailStep& s, const TextFold* tf) {
+    const bool foldable = (s.paired || s.query_only || s.last_step) && tf && !s.w->fold && !s.ctx_row && !s.d_h.on() &&
+                          s.w->text.w_out;
+    int rc = SF_ERR_UNSUPPORTED;
+    if (foldable && tf->mats && g_fold_chain3) rc = tail_fold3(s, *tf);
+    if (rc == SF_ERR_UNSUPPORTED && foldable && s.w->action.w_a_t) rc = tail_fold4(s, *tf);
+    if (rc != SF_ERR_UNSUPPORTED) return rc;
+    if (s.paired && s.w->fold) return tail_decoder_fold(s);
+    if (s.paired) return tail_paired(s);
+    if (s.query_only) return tail_query_only(s);
+    return tail_plain(s);
+}
+
 static int decoder_tail_i(const sf_decoder_w* w, const sf_cands* U, int B, int H, int D, int L,
                           const float* u_prev, const float* h0, const float* c0, const float* ctx,
                           const uint8_t* ctx_mask, const int32_t* ctx_row, const sf_decoder_tape* tp,
@@ -862,261 +1143,24 @@ static int decoder_tail_i(const sf_decoder_w* w, const sf_cands* U, int B, int H
                           sf_stream stream, const TextFold* tf = nullptr) {
     SF_CHECK_ARG(w && U && h0 && c0 && ctx && tp && B > 0 && L > 0 && (!glue || glue_ok(U, glue)) &&
                  (!X_next || tn));
-    Arena ar = arena(ws, ws_bytes);
-    hipStream_t st = S(stream);
-    const CandSrc us = cands(U);
-    // tape_next WITHOUT X_next: the next panorama is not known yet (it depends on this step's action: a
-    // device-resident environment).  Only the query of the next step's visual attention (t_v', q': they need
-    // nothing but h1) rides beside the text stages; the attention itself follows the environment step
-    // (sf_attn_decoder_attend_fwd).
-    const bool query_only = !X_next && tn && w->visual.w_v_t && !w->fold;
-    const int F = us.IMG + us.LOC;
-    const Dropout d_in = make_dropout(drop, 2 * step_id, 2), d_h = make_dropout(drop, 2 * step_id + 1, 2);
-    if (u_prev) TRY(dropout_copy(u_prev, F, B, F, tp->xin, 2 * F, d_in, 0, st));
-    TRY(lstm_fwd_i(&w->lstm, B, 2 * F, H, tp->xin, 2 * F, h0, c0, tp->h1, tp->c1, tp->gates,
-                   tp->cat2 + H, 2 * H, d_h, ar, st));
-    const sf_softdot_w* tw = &w->text;
-    const sf_visual_w* vw = &w->visual;
-    bool paired = X_next && vw->w_v_t;     // (a scoring fold, if any, is applied by scoring_fwd_i)
-    const bool last_step = !X_next && !tn;      // (nothing of a next step to prepare: the text chain alone)
-    if ((paired || query_only || last_step) && tf && tf->mats && g_fold_chain3 && !w->fold && !ctx_row && !d_h.on() &&
-        tw->w_out) {
-        // Folded text stage + folded query / scoring products (sf_decoder_fold through sf_follower_episode.chain_fold):
-        // THREE dependent launches behind the cell --
-        //   (1) folded text attention  ||  y = W_out[:, H:] h1  ||  q' = M_v h1 + c_v      (t_v' is never formed)
-        //   (2) [r | c] = M_a tanh(z + y) + c_a (A-prologue)   ||  visual-attention partials of step t+1
-        //   (3) scoring + glue (logit = u . r + c)             ||  merge of the partials
-        // (a device-resident environment: (2) is the product alone, the attention follows the environment step)
-        const sf_decoder_fold* fm = tf->mats;
-        const PanoSrc xn = paired ? pano(X_next) : PanoSrc{};
-        const Dropout dn_in = make_dropout(drop, 2 * (step_id + 1), 2);
-        Arena af = ar;
-        float* tpart = af.take(text_fold_part_floats(B, H));
-        // (leading dimension H + 16: rows of a power-of-two stride share a few cache sets, CHANGELOG round 5 "2c")
-        const int ldp = H + 16;
-        float* ybuf = af.take((size_t)B * ldp);
-        float* zbuf = af.take((size_t)B * ldp);
-        float* rext = af.take((size_t)B * (F + 4));
-        unsigned* tcount = af.tickets() ? af.tickets() + TEXT_TICKET : nullptr;
-        float* part = (paired && B <= 1024) ? af.take(visual_attn_split_floats(B, F)) : nullptr;
-        SmallPlan py, pq, pm;
-        bool ok = tpart && ybuf && zbuf && rext && (part || !paired) && tcount && B <= VIS_SPLIT_MAX_B && fm->m_v &&
-                  fm->c_v && fm->m_a &&
-                  fm->c_a &&
-                  plan_linear(tp->cat2 + H, 2 * H, tw->w_out + H, 2 * H, nullptr, B, H, H, EPI_NONE, ybuf, ldp, &py) == SF_OK;
-        if (ok && !last_step) {
-            ok = plan_linear(tp->h1, H, fm->m_v, H, fm->c_v, B, F, H, EPI_NONE, tn->q, F, &pq) == SF_OK;
-        } else if (ok) {
-            pq = py;
-            pq.gx = pq.gy = 0;
-        }
-        if (ok) {
-            Seg sg{ybuf, ldp, fm->m_a, H, H};
-            LinearOut o{};
-            o.y = rext; o.ldy = F + 4; o.bias = fm->c_a; o.epi = EPI_NONE;
-            ok = linear_small_plan(&sg, 1, B, F + 4, o, &pm) && pm.cpw == 4 && py.mt == 1 && py.cpw == 4 && pq.cpw == 4;
-            pm.args.apro_part = zbuf;
-            pm.args.apro_stride = ldp;
-        }
-        if (ok) {
-            const int rc = pair_textfold_small_small(tf->ctx_q, tf->ctx_o, ctx_mask, B, L, H, tp->cat2 + H, 2 * H, tpart,
-                                                     tcount, zbuf, ldp, tp->alpha, py, pq, st);
-            if (rc == SF_OK) {
-                TRY(pair_vis_apro(paired ? &xn : nullptr, B, paired ? tn->q : nullptr, F, part, pm, st));
-                if (paired && glue)
-                    return pair_score_merge(us, B, D, rext, nullptr, nullptr, nullptr, make_glue(us, B, tp->logit, glue), xn,
-                                            tn->alpha_v, tn->xin + F, 2 * F, dn_in, F, part, st, F + 4, rext + F);
-                if (paired) {                               // (no glue: the module-API step; merge by its own launch)
-                    SmallPlan none = py;
-                    none.gx = none.gy = 0;
-                    TRY(pair_vis_small(xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, dn_in, F, part, nullptr, none, st, 2));
-                }
-                if (glue)
-                    return score_glue_fwd(us, B, D, rext, nullptr, nullptr, nullptr, make_glue(us, B, tp->logit, glue), st,
-                                          F + 4, rext + F);
-                return score_fwd(us, B, D, rext, nullptr, nullptr, nullptr, tp->logit, st, F + 4, rext + F);
-            }
-            if (rc != SF_ERR_UNSUPPORTED) return rc;
-        }
-        // (shapes outside the instantiations: the four-launch chain below)
-    }
-    if ((paired || query_only || last_step) && tf && !w->fold && !ctx_row && !d_h.on() && tw->w_out && w->action.w_a_t) {
-        // Folded text stage (inference; sf_attention.hip: text_fold_body): FOUR dependent launches behind the cell
-        // instead of six:
-        //   (1) folded text attention (4 groups per sample, merged by the last arriver)  ||  y = W_out[:, H:] h1  ||  t_v' = W_h h1 + b_h
-        //   (2) t_a = W_h tanh(z + y) + b_h, wt = t_a * w_out (A-prologue)   ||  q' = W_v^T t_v'
-        //   (3) r = W_a^T wt            ||  visual attention of step t+1 (partials, ticket, merge by the last arriver)
-        //   (4) scoring + glue
-        // (query_only -- a device-resident environment: the panorama of step t+1 is not known yet -- stage (3) is the
-        // r product alone and the attention follows the environment step, sf_attn_decoder_attend_fwd)
-        const PanoSrc xn = paired ? pano(X_next) : PanoSrc{};
-        const Dropout dn_in = make_dropout(drop, 2 * (step_id + 1), 2);
-        Arena af = ar;                                           // (released when this branch is left)
-        float* tpart = af.take(text_fold_part_floats(B, H));
-        // (leading dimension H + 16: rows of a power-of-two stride share a few cache sets, CHANGELOG round 5 "2c")
-        const int ldp = H + 16;
-        float* ybuf = af.take((size_t)B * ldp);
-        float* zbuf = af.take((size_t)B * ldp);
-        unsigned* tcount = af.tickets() ? af.tickets() + TEXT_TICKET : nullptr;
-        float* part = (paired && B <= 1024) ? af.take(visual_attn_split_floats(B, F)) : nullptr;
-        SmallPlan py, pv, pta, pq, pr;
-        bool ok = tpart && ybuf && zbuf && (part || !paired) && tcount && B <= VIS_SPLIT_MAX_B &&
-            plan_linear(tp->cat2 + H, 2 * H, tw->w_out + H, 2 * H, nullptr, B, H, H, EPI_NONE, ybuf, ldp, &py) == SF_OK &&
-            plan_linear(tp->wt, D, w->action.w_a_t, D, nullptr, B, F, D, EPI_NONE, tp->r, F, &pr) == SF_OK;
-        if (ok && !last_step) {
-            ok = plan_linear(tp->h1, H, vw->w_h, H, vw->b_h, B, D, H, EPI_NONE, tn->t_v, D, &pv) == SF_OK &&
-                 plan_linear(tn->t_v, D, vw->w_v_t, D, nullptr, B, F, D, EPI_NONE, tn->q, F, &pq) == SF_OK;
-        } else if (ok) {                                       // no next step: the second bodies of (1) and (2) are empty
-            pv = py;
-            pv.gx = pv.gy = 0;
-            pq = pr;
-            pq.gx = pq.gy = 0;
-        }
-        if (ok) {
-            Seg sg{ybuf, ldp, w->action.w_h, H, H};
-            LinearOut o{};
-            o.y = tp->wt; o.ldy = D; o.bias = w->action.b_h; o.mul = w->action.w_out; o.y_pre = tp->t_a;
-            o.ldy_pre = D; o.epi = EPI_MUL;
-            ok = linear_small_plan(&sg, 1, B, D, o, &pta) && pta.mt == 1 && pta.cpw == 4 && pq.cpw == 2 && pr.cpw == 2;
-            pta.args.apro_part = zbuf;                            // (the merged attention sum of launch (1))
-            pta.args.apro_stride = ldp;
-        }
-        if (ok) {
-            const int rc = pair_textfold_small_small(tf->ctx_q, tf->ctx_o, ctx_mask, B, L, H, tp->cat2 + H, 2 * H, tpart,
-                                                     tcount, zbuf, ldp, tp->alpha, py, pv, st);
-            if (rc == SF_OK) {
-                TRY(pair_apro_small(pta, pq, st));
-                if (paired && glue && g_fold_merge_with_glue) {
-                    // partials beside r, their merge beside the scoring + glue launch (same depth, no in-launch ticket)
-                    TRY(pair_vis_small(xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, dn_in, F, part, nullptr, pr, st, 1));
-                    const int rc2 = pair_score_merge(us, B, D, tp->r, tp->wt, w->action.b_a, w->action.b_out,
-                                                     make_glue(us, B, tp->logit, glue), xn, tn->alpha_v, tn->xin + F, 2 * F,
-                                                     dn_in, F, part, st);
-                    return rc2;                 // (its shape limits are score_glue_fwd's and pair_vis_small's)
-                } else if (paired) {
-                    TRY(pair_vis_small(xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, dn_in, F, part, af.tickets(), pr, st, 0));
-                } else {
-                    TRY(launch_small_plan_x(pr, st));
-                }
-                if (glue)
-                    return score_glue_fwd(us, B, D, tp->r, tp->wt, w->action.b_a, w->action.b_out,
-                                          make_glue(us, B, tp->logit, glue), st);
-                return score_fwd(us, B, D, tp->r, tp->wt, w->action.b_a, w->action.b_out, tp->logit, st);
-            }
-            if (rc != SF_ERR_UNSUPPORTED) return rc;
-        }
-        // (shapes outside the instantiations: the unfolded stages below)
-    }
-    if (paired && w->fold) {
-        // Folded inference step (sf_decoder_fold): two dependent stages fewer, and the attention
-        // partials of step t+1 ride beside the text attention (the longest small stage) instead of
-        // stretching the h~ product:
-        //   (1) t_text = W_in h1                  ||  q' = M_v h1 + c_v
-        //   (2) text attention                    ||  visual-attention partials of step t+1
-        //   (3) h~ = tanh(W_out [wc ; h1])        ||  merge of the partials
-        //   (4) [r | c] = M_a h~ + c_a            (5) scoring + glue
-        const PanoSrc xn = pano(X_next);
-        const Dropout dn_in = make_dropout(drop, 2 * (step_id + 1), 2);
-        SmallPlan pa, pb;
-        const bool ok1 =
-            plan_linear(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, &pa) == SF_OK &&
-            plan_linear(tp->h1, H, w->fold->m_v, H, w->fold->c_v, B, F, H, EPI_NONE, tn->q, F, &pb) == SF_OK;
-        if (!ok1 || pair_small_small(pa, pb, st) != SF_OK) {
-            TRY(linear_plain(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, ar, st));
-            TRY(linear_plain(tp->h1, H, w->fold->m_v, H, w->fold->c_v, B, F, H, EPI_NONE, tn->q, F, ar, st));
-        }
-        float* part = B <= 1024 ? ar.take(visual_attn_split_floats(B, F)) : nullptr;
-        const bool ok3 = part && plan_linear(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H, EPI_TANH,
-                                             tp->h_tilde, H, &pb) == SF_OK;
-        bool split = false;
-        if (ok3) {
-            const int rc = pair_vis_text(xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, dn_in, F, part, ctx,
-                                         ctx_mask, L, H, tp->t_text, H, tp->alpha, tp->cat2, 2 * H, ctx_row, st);
-            if (rc == SF_OK) split = true;
-            else if (rc != SF_ERR_UNSUPPORTED) return rc;
-        }
-        if (split && pair_vis_small(xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, dn_in, F, part, nullptr, pb,
-                                    st, 2) != SF_OK)
-            return SF_ERR_LAUNCH;            // the partials exist: the merge must not be skipped
-        if (!split) {
-            TRY(text_attn_fwd(ctx, ctx_mask, B, L, H, tp->t_text, H, tp->alpha, tp->cat2, 2 * H, st, ctx_row));
-            TRY(linear_plain(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H, EPI_TANH, tp->h_tilde, H, ar, st));
-            TRY(visual_attn(0, xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, dn_in, F, st, part,
-                            part ? ar.tickets() : nullptr));
-        }
-    } else if (paired) {
-        const PanoSrc xn = pano(X_next);
-        const Dropout dn_in = make_dropout(drop, 2 * (step_id + 1), 2);
-        SmallPlan pa, pb;
-        // (1) t_text = W_in dropout(h1)   ||   t_v' = W_h h1 + b_h
-        const bool ok1 =
-            plan_linear(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, &pa) == SF_OK &&
-            plan_linear(tp->h1, H, vw->w_h, H, vw->b_h, B, D, H, EPI_NONE, tn->t_v, D, &pb) == SF_OK;
-        if (!ok1 || pair_small_small(pa, pb, st) != SF_OK) {
-            TRY(linear_plain(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, ar, st));
-            TRY(linear_plain(tp->h1, H, vw->w_h, H, vw->b_h, B, D, H, EPI_NONE, tn->t_v, D, ar, st));
-        }
-        // (2) text attention   ||   q' = W_v^T t_v'
-        const bool ok2 = plan_linear(tn->t_v, D, vw->w_v_t, D, nullptr, B, F, D, EPI_NONE, tn->q, F, &pa) == SF_OK;
-        if (!ok2 || pair_small_text(pa, ctx, ctx_mask, B, L, H, tp->t_text, H, tp->alpha, tp->cat2,
-                                    2 * H, ctx_row, st) != SF_OK) {
-            TRY(text_attn_fwd(ctx, ctx_mask, B, L, H, tp->t_text, H, tp->alpha, tp->cat2, 2 * H, st, ctx_row));
-            TRY(linear_plain(tn->t_v, D, vw->w_v_t, D, nullptr, B, F, D, EPI_NONE, tn->q, F, ar, st));
-        }
-        // (3) h~ = tanh(W_out [wc ; h1])   ||   visual attention of step t+1, per-group partials
-        // (4) t_a = W_h h~ + b_h, wt = t_a * w_out   ||   ... merge of the partials
-        // (the attention is not needed before the next gate product: its two halves ride with two
-        // stages of the text / scoring chain instead of stretching one of them)
-        float* part = B <= 1024 ? ar.take(visual_attn_split_floats(B, F)) : nullptr;
-        const bool ok3 = part && plan_linear(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H,
-                                             EPI_TANH, tp->h_tilde, H, &pb) == SF_OK;
-        SmallPlan pc;
-        bool ok4 = false;
-        if (ok3 && !w->fold) {
-            Seg sg{tp->h_tilde, H, w->action.w_h, H, H};
-            LinearOut o{};
-            o.y = tp->wt; o.ldy = D; o.bias = w->action.b_h; o.mul = w->action.w_out; o.y_pre = tp->t_a;
-            o.ldy_pre = D; o.epi = EPI_MUL;
-            ok4 = linear_small_plan(&sg, 1, B, D, o, &pc) && pc.mt == 1 && (pc.cpw == 4 || pc.cpw == 8);
-        }
-        if (ok4 && pair_vis_small(xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, dn_in, F, part,
-                                  nullptr, pb, st, 1) == SF_OK) {
-            TRY(pair_vis_small(xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, dn_in, F, part, nullptr,
-                               pc, st, 2));
-            return scoring_fwd_i(&w->action, us, B, H, D, tp->h_tilde, tp->logit, tp->t_a, tp->wt, tp->r,
-                                 ar, st, glue, nullptr, true);
-        }
-        if (!ok3 || pair_vis_small(xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, dn_in, F, part,
-                                   ar.tickets(), pb, st) != SF_OK) {
-            TRY(linear_plain(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H, EPI_TANH, tp->h_tilde, H, ar, st));
-            TRY(visual_attn(0, xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, dn_in, F, st, part,
-                            part ? ar.tickets() : nullptr));
-        }
-    } else if (query_only) {
-        SmallPlan pa, pb;
-        const bool ok1 =
-            plan_linear(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, &pa) == SF_OK &&
-            plan_linear(tp->h1, H, vw->w_h, H, vw->b_h, B, D, H, EPI_NONE, tn->t_v, D, &pb) == SF_OK;
-        if (!ok1 || pair_small_small(pa, pb, st) != SF_OK) {
-            TRY(linear_plain(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, ar, st));
-            TRY(linear_plain(tp->h1, H, vw->w_h, H, vw->b_h, B, D, H, EPI_NONE, tn->t_v, D, ar, st));
-        }
-        const bool ok2 = plan_linear(tn->t_v, D, vw->w_v_t, D, nullptr, B, F, D, EPI_NONE, tn->q, F, &pa) == SF_OK;
-        if (!ok2 || pair_small_text(pa, ctx, ctx_mask, B, L, H, tp->t_text, H, tp->alpha, tp->cat2,
-                                    2 * H, ctx_row, st) != SF_OK) {
-            TRY(text_attn_fwd(ctx, ctx_mask, B, L, H, tp->t_text, H, tp->alpha, tp->cat2, 2 * H, st, ctx_row));
-            TRY(linear_plain(tn->t_v, D, vw->w_v_t, D, nullptr, B, F, D, EPI_NONE, tn->q, F, ar, st));
-        }
-        TRY(linear_plain(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H, EPI_TANH, tp->h_tilde, H, ar, st));
-    } else {
-        TRY(softdot_fwd_i(tw, B, L, H, nullptr, 0, ctx, ctx_mask, tp->h_tilde, tp->alpha, tp->cat2,
-                          tp->t_text, ar, st, ctx_row));
-        if (X_next)
-            TRY(visual_fwd_i(vw, pano(X_next), B, H, D, tp->h1, tn->xin + F, 2 * F, tn->alpha_v,
-                             tn->t_v, tn->q, make_dropout(drop, 2 * (step_id + 1), 2), F, ar, st, w->fold));
-    }
-    return scoring_fwd_i(&w->action, us, B, H, D, tp->h_tilde, tp->logit, tp->t_a, tp->wt, tp->r, ar,
-                         st, glue, w->fold);
+    TailStep s{};
+    s.w = w; s.us = cands(U); s.B = B; s.H = H; s.D = D; s.L = L; s.F = s.us.IMG + s.us.LOC;
+    s.tp = tp; s.tn = tn; s.glue = glue;
+    s.ctx = ctx; s.ctx_mask = ctx_mask; s.ctx_row = ctx_row;
+    s.ar = arena(ws, ws_bytes);
+    s.st = S(stream);
+    s.d_h = make_dropout(drop, 2 * step_id + 1, 2);
+    s.dn_in = make_dropout(drop, 2 * (step_id + 1), 2);
+    s.has_xn = X_next != nullptr;
+    if (X_next) s.xn = pano(X_next);
+    s.paired = X_next && w->visual.w_v_t;      // (a scoring fold, if any, is applied by scoring_fwd_i)
+    s.query_only = !X_next && tn && w->visual.w_v_t && !w->fold;      // (tail_query_only)
+    s.last_step = !X_next && !tn;              // (nothing of a next step to prepare: the text chain alone)
+    const Dropout d_in = make_dropout(drop, 2 * step_id, 2);
+    if (u_prev) TRY(dropout_copy(u_prev, s.F, B, s.F, tp->xin, 2 * s.F, d_in, 0, s.st));
+    TRY(lstm_fwd_i(&w->lstm, B, 2 * s.F, H, tp->xin, 2 * s.F, h0, c0, tp->h1, tp->c1, tp->gates,
+                   tp->cat2 + H, 2 * H, s.d_h, s.ar, s.st));
+    return tail_dispatch(s, tf);
 }
 
 // tail(t) WITHOUT the head of step t+1 (that runs on another stream): LSTM cell, then -- after
@@ -1163,6 +1207,22 @@ int sf_attn_decoder_tail_fwd(const sf_decoder_w* w, const sf_cands* U, int B, in
     SF_ENTER();
     return decoder_tail_i(w, U, B, H, D, L, u_prev, h0, c0, ctx, ctx_mask, ctx_row, tp, glue, drop,
                           step_id, X_next, tn, ws, ws_bytes, stream);
+}
+
+// ---- a6 AttnDecoderLSTM.forward (model.py:377-397) -------------------------------------------------
+int sf_attn_decoder_fwd(const sf_decoder_w* w, const sf_pano* X, const sf_cands* U, int B, int H,
+                        int D, int L, const float* u_prev, const float* h0, const float* c0,
+                        const float* ctx, const uint8_t* ctx_mask, const int32_t* ctx_row,
+                        const sf_decoder_tape* tp, const sf_follower_glue* glue,
+                        const sf_dropout* drop, uint32_t step_id,
+                        void* ws, size_t ws_bytes, sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(w && X && U && h0 && c0 && ctx && tp && B > 0 && L > 0 && (!glue || glue_ok(U, glue)));
+    // model.py:389  feature, alpha_v = visual_attention(h_0, X)  -> straight into xin[:, F:2F]: head(t);
+    // model.py:391-396  drop(cat(u_prev, feature)), LSTMCell, text attention, action logits: the plain tail(t)
+    TRY(decoder_head_a(w, X, B, H, D, h0, tp, drop, step_id, arena(ws, ws_bytes), stream));
+    return decoder_tail_i(w, U, B, H, D, L, u_prev, h0, c0, ctx, ctx_mask, ctx_row, tp, glue, drop, step_id, nullptr,
+                          nullptr, ws, ws_bytes, stream);
 }
 
 int sf_decoder_fold_build(const sf_decoder_w* w, int H, int D, int F, float* m_v, float* c_v,
@@ -1390,6 +1450,39 @@ sf_decoder_gtape gtape_view(const sf_decoder_gtape* g, const sf_follower_episode
     v.dh1d = adv(g->dh1d, t * B * H);
     return v;
 }
+
+// the state entering step t: the episode's initial one, or what step t - 1 left in its tape slot
+struct StepState {
+    const float *h, *c;
+};
+StepState state_in(const sf_follower_episode* e, int t) {
+    const size_t off = (size_t)(t - 1) * e->B * e->H;
+    return t == 0 ? StepState{e->h_init, e->c_init} : StepState{e->tape.h1 + off, e->tape.c1 + off};
+}
+
+// `later` waits for everything `earlier` holds so far
+int order_behind(hipStream_t later, hipStream_t earlier, hipEvent_t ev) {
+    return hipEventRecord(ev, earlier) == hipSuccess && hipStreamWaitEvent(later, ev, 0) == hipSuccess ? SF_OK : SF_ERR_LAUNCH;
+}
+// "Fork a side stream behind the main one, join it back."  Whatever leaves the scope with the fork still open -- every
+// error return -- joins it here: inside a capture an unjoined fork invalidates the graph, outside one the side stream
+// would keep writing workspace the caller believes free.
+struct SideFork {
+    hipStream_t main, side = nullptr;       // side: null while no fork is open
+    hipEvent_t ev_join = nullptr;
+    int fork(hipStream_t side_st, hipEvent_t ev_fork, hipEvent_t ev_back) {
+        TRY(order_behind(side_st, main, ev_fork));
+        side = side_st;
+        ev_join = ev_back;
+        return SF_OK;
+    }
+    int join() {
+        hipStream_t from = side;
+        side = nullptr;
+        return order_behind(main, from, ev_join);
+    }
+    ~SideFork() { if (side) (void)join(); }
+};
 }  // namespace
 }  // extern "C++"
 
@@ -1399,10 +1492,8 @@ int sf_follower_episode_fwd(const sf_decoder_w* w, const sf_follower_episode* e,
     SF_CHECK_ARG(w && e && e->S > 0 && e->B > 0 && e->h_init && e->c_init && e->ctx && e->tape.xin &&
                  e->tape.h1 && e->tape.c1 && e->glue.target && e->glue.ended);
     const sf_dropout* drop = e->drop.p > 0.f ? &e->drop : nullptr;
-    const size_t BH = (size_t)e->B * e->H;
     StepView cur = step_view(e, 0);
-    hipEvent_t fold_join = nullptr;
-    hipStream_t fold_side = nullptr;
+    SideFork fold_fork{S(stream)};
     // the folded text attention (ABI 9): ctx_q = ctx W_in, ctx_o = ctx W_out[:, :H]^T, once per episode
     TextFold tfold{e->ctx_q, e->ctx_o, e->chain_fold};
     const TextFold* tf = nullptr;
@@ -1410,63 +1501,37 @@ int sf_follower_episode_fwd(const sf_decoder_w* w, const sf_follower_episode* e,
         const int M = e->B * e->L, H = e->H;
         Arena ar = arena(ws, ws_bytes);
         hipStream_t ms = S(stream), bs = ms;
-        std::vector<hipEvent_t>* ev = nullptr;
         if (e->side_stream && e->side_stream != stream && g_fold_build_overlap) {
             // the two products need nothing but the encoder's context: on the caller's SECOND stream beside step 0's
             // attention (one fork here, one join in front of the first decode step; the last quarter of the workspace is
             // theirs, the head keeps the front)
-            ev = &event_pool(2);
-            if (ev->size() >= 2 && ar.cap > ((size_t)8 << 20)) {
+            std::vector<hipEvent_t>& ev = event_pool(2);
+            if (ev.size() >= 2 && ar.cap > ((size_t)8 << 20)) {
                 bs = S(e->side_stream);
                 const size_t side_n = ar.cap / 4;
                 ar = Arena{(float*)ws + (ar.cap - side_n), side_n, 0, ar.tk};
-                if (hipEventRecord((*ev)[0], ms) != hipSuccess || hipStreamWaitEvent(bs, (*ev)[0], 0) != hipSuccess)
-                    return SF_ERR_LAUNCH;
+                TRY(fold_fork.fork(bs, ev[0], ev[1]));
             }
         }
         TRY(linear_plain(e->ctx, H, w->text.w_in_t, H, nullptr, M, H, H, EPI_NONE, e->ctx_q, H, ar, bs));
         TRY(linear_plain(e->ctx, H, w->text.w_out, 2 * H, nullptr, M, H, H, EPI_NONE, e->ctx_o, H, ar, bs));
         tf = &tfold;
-        if (bs != ms) {
-            // (the head -- issued below on `stream` -- runs beside them; join behind it)
-            fold_join = (*ev)[1];
-            fold_side = bs;
-        }
     }
     {
         // (beside the fold products the head keeps the FRONT three quarters of the workspace -- and the same ticket words)
         Arena ha = arena(ws, ws_bytes);
-        if (fold_side) ha.cap -= ha.cap / 4;
+        if (fold_fork.side) ha.cap -= ha.cap / 4;
         TRY(decoder_head_a(w, &cur.X, e->B, e->H, e->D, e->h_init, &cur.tp, drop, e->step0, ha, stream));
     }
-    if (fold_side) {
-        if (hipEventRecord(fold_join, fold_side) != hipSuccess || hipStreamWaitEvent(S(stream), fold_join, 0) != hipSuccess)
-            return SF_ERR_LAUNCH;
-    }
-    if (e->glue.nav) {
-        // A device-resident environment (sf_nav_io of step 0 in glue.nav; state buffers stacked [S + 1][...]): the
-        // panorama of step t + 1 is only known once the glue of step t has chosen its action and stepped the
-        // environment (inside the scoring + glue launch), so its attention cannot ride beside tail(t); its QUERY can
-        // (tape_next without X_next), and the attention follows as its own launch -- the schedule the host loop of
-        // FollowerEngine.rollout issues call by call, here without host work between the launches.
-        SF_CHECK_ARG(!w->fold && w->visual.w_v_t);
-        for (int t = 0; t < e->S; ++t) {
-            const bool more = t + 1 < e->S;
-            StepView nxt = more ? step_view(e, t + 1) : cur;
-            const sf_nav_io nv = nav_view(e->glue.nav, e, t);
-            cur.glue.nav = &nv;
-            const float* h0 = t == 0 ? e->h_init : e->tape.h1 + (size_t)(t - 1) * BH;
-            const float* c0 = t == 0 ? e->c_init : e->tape.c1 + (size_t)(t - 1) * BH;
-            TRY(decoder_tail_i(w, &cur.U, e->B, e->H, e->D, e->L, nullptr, h0, c0, e->ctx, e->ctx_mask,
-                               nullptr, &cur.tp, &cur.glue, drop, e->step0 + t, nullptr, more ? &nxt.tp : nullptr, ws,
-                               ws_bytes, stream, tf));
-            if (more)
-                TRY(sf_attn_decoder_attend_fwd(&nxt.X, e->B, &nxt.tp, drop, e->step0 + t + 1, ws, ws_bytes, stream));
-            cur = nxt;
-        }
-        return SF_OK;
-    }
-    if (e->side_stream && e->side_stream != stream && !w->fold && e->S > 1 && !tf) {
+    if (fold_fork.side) TRY(fold_fork.join());      // (the head ran beside the fold products: join behind it)
+    // A device-resident environment (sf_nav_io of step 0 in glue.nav; state buffers stacked [S + 1][...]): the
+    // panorama of step t + 1 is only known once the glue of step t has chosen its action and stepped the
+    // environment (inside the scoring + glue launch), so its attention cannot ride beside tail(t); its QUERY can
+    // (tape_next without X_next), and the attention follows as its own launch -- the schedule the host loop of
+    // FollowerEngine.rollout issues call by call, here without host work between the launches.
+    const sf_nav_io* nav0 = e->glue.nav;
+    if (nav0) SF_CHECK_ARG(!w->fold && w->visual.w_v_t);
+    if (!nav0 && e->side_stream && e->side_stream != stream && !w->fold && e->S > 1 && !tf) {
         // Two chains, ONE fork and ONE join per episode, ordered per step by device flags
         // (flag_wait / flag_set kernels) instead of events:
         //   main:  [wait feat(t)] gate product, cell, [set h1(t)], t_text, text attention, h~, scoring + glue
@@ -1483,38 +1548,37 @@ int sf_follower_episode_fwd(const sf_decoder_w* w, const sf_follower_episode* e,
         const size_t main_bytes = (whole.cap - side_n) * sizeof(float);
         TRY(flag_set(flag_h1, 0u, ms));
         TRY(flag_set(flag_ft, 0u, ms));
-        if (hipEventRecord(ev[0], ms) != hipSuccess || hipStreamWaitEvent(ss, ev[0], 0) != hipSuccess) return SF_ERR_LAUNCH;
+        SideFork fk{ms};
+        TRY(fk.fork(ss, ev[0], ev[1]));
         for (int t = 0; t < e->S; ++t) {
             const bool more = t + 1 < e->S;
             StepView nxt = more ? step_view(e, t + 1) : cur;
-            const float* h0 = t == 0 ? e->h_init : e->tape.h1 + (size_t)(t - 1) * BH;
-            const float* c0 = t == 0 ? e->c_init : e->tape.c1 + (size_t)(t - 1) * BH;
+            const StepState in = state_in(e, t);
             if (t > 0) TRY(flag_wait(flag_ft, (unsigned)t, ms));
-            TRY(decoder_tail_split_i(w, &cur.U, e->B, e->H, e->D, e->L, h0, c0, e->ctx, e->ctx_mask, &cur.tp,
+            TRY(decoder_tail_split_i(w, &cur.U, e->B, e->H, e->D, e->L, in.h, in.c, e->ctx, e->ctx_mask, &cur.tp,
                                      &cur.glue, drop, e->step0 + t, more ? flag_h1 : nullptr, (unsigned)(t + 1), ws,
                                      main_bytes, whole.tk, ms));
             if (more) {
                 TRY(flag_wait(flag_h1, (unsigned)(t + 1), ss));
                 Arena sar{(float*)side_ws, side_n, 0, whole.tk};
-                const PanoSrc xs = pano(&nxt.X);
-                const int F = xs.IMG + xs.LOC;
-                TRY(visual_fwd_i(&w->visual, xs, e->B, e->H, e->D, cur.tp.h1, nxt.tp.xin + F, 2 * F, nxt.tp.alpha_v,
-                                 nxt.tp.t_v, nxt.tp.q, make_dropout(drop, 2 * (e->step0 + t + 1), 2), F, sar, ss, nullptr));
+                TRY(decoder_head_a(w, &nxt.X, e->B, e->H, e->D, cur.tp.h1, &nxt.tp, drop, e->step0 + t + 1, sar, e->side_stream));
                 TRY(flag_set(flag_ft, (unsigned)(t + 1), ss));
             }
             cur = nxt;
         }
-        if (hipEventRecord(ev[1], ss) != hipSuccess || hipStreamWaitEvent(ms, ev[1], 0) != hipSuccess) return SF_ERR_LAUNCH;
-        return SF_OK;
+        return fk.join();
     }
     for (int t = 0; t < e->S; ++t) {
         const bool more = t + 1 < e->S;
         StepView nxt = more ? step_view(e, t + 1) : cur;
-        const float* h0 = t == 0 ? e->h_init : e->tape.h1 + (size_t)(t - 1) * BH;
-        const float* c0 = t == 0 ? e->c_init : e->tape.c1 + (size_t)(t - 1) * BH;
-        TRY(decoder_tail_i(w, &cur.U, e->B, e->H, e->D, e->L, nullptr, h0, c0, e->ctx, e->ctx_mask,
-                           nullptr, &cur.tp, &cur.glue, drop, e->step0 + t, more ? &nxt.X : nullptr,
+        const sf_nav_io nv = nav0 ? nav_view(nav0, e, t) : sf_nav_io{};
+        if (nav0) cur.glue.nav = &nv;
+        const StepState in = state_in(e, t);
+        TRY(decoder_tail_i(w, &cur.U, e->B, e->H, e->D, e->L, nullptr, in.h, in.c, e->ctx, e->ctx_mask,
+                           nullptr, &cur.tp, &cur.glue, drop, e->step0 + t, more && !nav0 ? &nxt.X : nullptr,
                            more ? &nxt.tp : nullptr, ws, ws_bytes, stream, tf));
+        if (nav0 && more)
+            TRY(sf_attn_decoder_attend_fwd(&nxt.X, e->B, &nxt.tp, drop, e->step0 + t + 1, ws, ws_bytes, stream));
         cur = nxt;
     }
     return SF_OK;
@@ -1538,7 +1602,6 @@ int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episo
                  e->S > 0 && e->B > 0 && 0 <= t_lo && t_lo < t_hi && t_hi <= e->S &&
                  (t_hi == e->S || (dh_in && dc_in)) && (!dh_in) == (!dc_in));
     const sf_dropout* drop = e->drop.p > 0.f ? &e->drop : nullptr;
-    const size_t BH = (size_t)e->B * e->H;
     sf_decoder_gtape gt_all = *gtape;          // the deferred context gradient only where it is covered
     if (!(gt_all.dcat2 && gt_all.ds && dctx && ctx_grad_supported(e->S, e->L, e->H)))
         gt_all.dcat2 = gt_all.ds = nullptr;
@@ -1572,9 +1635,7 @@ int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episo
         Arena head_ar{(float*)ws + (usable - head_n), head_n, 0, whole.tk};
         // (only the first chunk orders the side stream behind the caller's stream -- the forward pass; the heads
         // of a later chunk need nothing from the tails of the chunk before it and keep running ahead)
-        if (t_hi == e->S &&
-            (hipEventRecord(ev[e->S], main_st) != hipSuccess || hipStreamWaitEvent(side_st, ev[e->S], 0) != hipSuccess))
-            return SF_ERR_LAUNCH;
+        if (t_hi == e->S) TRY(order_behind(side_st, main_st, ev[e->S]));
         // ALL heads are issued first (they depend on nothing the tails produce), each followed by
         // its event; then the tails, each behind the event of its head.  (Measured on MI355X: work of
         // two queues overlaps only where a kernel leaves CUs unoccupied -- tools/overlap_probe.py: an
@@ -1618,8 +1679,7 @@ int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episo
             if (g_bptt_part == 1) continue;
             StepView v = step_view(e, t);
             const sf_decoder_gtape g = gtape_view(gtape, e, t);
-            const float* h0 = t == 0 ? e->h_init : e->tape.h1 + (size_t)(t - 1) * BH;
-            const float* c0 = t == 0 ? e->c_init : e->tape.c1 + (size_t)(t - 1) * BH;
+            const StepState in = state_in(e, t);
             // the last product of this tail completes dh1 of step t - 1: that step's pointwise backward (it needs the
             // head of step t - 1 as well) rides in its epilogue
             LstmPwBwd next_pw{};
@@ -1630,11 +1690,10 @@ int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episo
             if (try_fuse) {
                 StepView vn = step_view(e, t - 1);
                 const sf_decoder_gtape gn = gtape_view(gtape, e, t - 1);
-                const float* c0n = t - 1 == 0 ? e->c_init : e->tape.c1 + (size_t)(t - 2) * BH;
                 d_next = make_dropout(drop, 2 * (e->step0 + t - 1) + 1, 2);
-                next_pw = cell_pw_bwd(vn.tp.gates, c0n, vn.tp.c1, nullptr, gn.dh1d, dco, e->B, e->H, gn.dgates, dcn, &d_next);
+                next_pw = cell_pw_bwd(vn.tp.gates, state_in(e, t - 1).c, vn.tp.c1, nullptr, gn.dh1d, dco, e->B, e->H, gn.dgates, dcn, &d_next);
             }
-            TRY(decoder_bwd_tail_i(w, nullptr, &v.X, e->B, e->H, e->D, h0, c0, &v.tp, &g, dh1, g.dh1d, dc1,
+            TRY(decoder_bwd_tail_i(w, nullptr, &v.X, e->B, e->H, e->D, in.h, in.c, &v.tp, &g, dh1, g.dh1d, dc1,
                                    dho, dco, drop, e->step0 + t, tail_ar, main_st, try_fuse ? &next_pw : nullptr,
                                    &next_fused, cell_done));
             cell_done = next_fused;
@@ -1647,12 +1706,11 @@ int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episo
         for (int t = t_hi - 1; t >= t_lo; --t) {
             StepView v = step_view(e, t);
             const sf_decoder_gtape g = gtape_view(gtape, e, t);
-            const float* h0 = t == 0 ? e->h_init : e->tape.h1 + (size_t)(t - 1) * BH;
-            const float* c0 = t == 0 ? e->c_init : e->tape.c1 + (size_t)(t - 1) * BH;
+            const StepState in = state_in(e, t);
             // the cross-entropy backward (softmax - onehot, scaled by 1 / live rows of the step) is
             // formed inside the scoring backward: one dependent launch less per step
             const CeSrc ce{v.tp.logit, v.glue.target_used, gscale + t, -1, (int)e->A};
-            TRY(decoder_bwd_i(w, nullptr, &v.X, &v.U, e->B, e->H, e->D, e->L, h0, c0, e->ctx, &v.tp, &g,
+            TRY(decoder_bwd_i(w, nullptr, &v.X, &v.U, e->B, e->H, e->D, e->L, in.h, in.c, e->ctx, &v.tp, &g,
                               dlogit, dh1, dc1, dho, dco, dctx, drop, e->step0 + t, ws, ws_bytes, stream,
                               &ce));
             dh1 = dho;

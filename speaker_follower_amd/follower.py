@@ -866,29 +866,31 @@ class FollowerEngine:
         # gemm_tn_group.  The many-row weight-gradient tiles -- 512 threads x 188 VGPRs, 96 KB LDS -- cannot sit beside the
         # persistent encoder backward's 256-VGPR workgroup on a CU.  NOTE: rocprofv3 --kernel-trace serialises the queues;
         # its timelines show no overlap at all and must not be read for concurrency, tools/bptt_overlap_probe.py.)
-        if overlap and not self.encoder_backward_first:
-            self._issue_wgrad(side, third, dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, dev, sync)
-        elif not overlap:
-            self._decoder_wgrad(dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, wgrad_ws_args(dev), sync)
-        if enc.num_directions == 2:
-            bi_encoder_bwd(enc, batch.seq, batch.lengths_dev, T, dropout_arg(*st.drop_enc_bi), st.site_rel,
-                           st.enc_table, st.enc_tape, st.h_init, dctx, dh1, dc1)
-        else:
-            etp = _lib.EncoderTape(*(st.enc_tape[k].data_ptr() for k in ('emb', 'xg', 'gates', 'hs', 'cs')))
-            ew = _encoder_structs(enc, table=st.enc_table)
-            eg = _encoder_structs(enc, grad=True, seq=None if st.enc_table else batch.seq)
-            call('sf_encoder_lstm_bwd', byref(ew), byref(eg), B, T, E, H, ptr(batch.lengths_dev),
-                 ptr(st.h_init), ptr(dctx), ptr(dh1), ptr(dc1), byref(etp), dropout_arg(*st.drop_enc),
-                 st.site_rel, *ws)
-        if sync is not None:
-            sync.launch(2)                       # encoder gradients: complete behind sf_encoder_lstm_bwd
-        if overlap and self.encoder_backward_first:
-            self._issue_wgrad(side, third, dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, dev, sync)
-        if overlap:
-            torch.cuda.current_stream().wait_stream(side)
-            if third is not None:
-                torch.cuda.current_stream().wait_stream(third)
-            self._open_forks = []
+        try:
+            if overlap and not self.encoder_backward_first:
+                self._issue_wgrad(side, third, dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, dev, sync)
+            elif not overlap:
+                self._decoder_wgrad(dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, wgrad_ws_args(dev), sync)
+            if enc.num_directions == 2:
+                bi_encoder_bwd(enc, batch.seq, batch.lengths_dev, T, dropout_arg(*st.drop_enc_bi), st.site_rel,
+                               st.enc_table, st.enc_tape, st.h_init, dctx, dh1, dc1)
+            else:
+                etp = _lib.EncoderTape(*(st.enc_tape[k].data_ptr() for k in ('emb', 'xg', 'gates', 'hs', 'cs')))
+                ew = _encoder_structs(enc, table=st.enc_table)
+                eg = _encoder_structs(enc, grad=True, seq=None if st.enc_table else batch.seq)
+                call('sf_encoder_lstm_bwd', byref(ew), byref(eg), B, T, E, H, ptr(batch.lengths_dev),
+                     ptr(st.h_init), ptr(dctx), ptr(dh1), ptr(dc1), byref(etp), dropout_arg(*st.drop_enc),
+                     st.site_rel, *ws)
+            if sync is not None:
+                sync.launch(2)                       # encoder gradients: complete behind sf_encoder_lstm_bwd
+            if overlap and self.encoder_backward_first:
+                self._issue_wgrad(side, third, dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, dev, sync)
+            if overlap:
+                torch.cuda.current_stream().wait_stream(side)
+                if third is not None:
+                    torch.cuda.current_stream().wait_stream(third)
+        finally:
+            self._open_forks = []        # (also when the backward raises: a later segmented capture must not join stale forks)
 
     def _issue_wgrad(self, side, third, dw, dg, params, M, H, D, F, st, tp0, gt0, dev, sync):
         """The decoder's weight gradients on the side stream(s) (which already wait for the backward through time)."""

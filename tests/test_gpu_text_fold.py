@@ -16,17 +16,7 @@ pytestmark = pytest.mark.gpu
 
 from speaker_follower_amd import synth                                # noqa: E402
 from oracle import np_env, np_model                                   # noqa: E402
-
-
-def _models(seed=77):
-    from speaker_follower_amd import model
-    d = synth.FULL
-    enc_w, dec_w = synth.follower_weights_peaky(seed)
-    enc = model.EncoderLSTM(d.vocab, d.word, d.hidden, 0, 0.5, glove=enc_w['embedding.weight'])
-    dec = model.AttnDecoderLSTM(d.feat, d.hidden, 0.5, feature_size=d.feat)
-    enc.load_state_dict({k: torch.tensor(v) for k, v in enc_w.items()})
-    dec.load_state_dict({k: torch.tensor(v) for k, v in dec_w.items()})
-    return enc.cuda().eval(), dec.cuda().eval(), enc_w, dec_w
+from tests.follower_models import full_size_models as _models        # noqa: E402
 
 
 @pytest.mark.parametrize('chain', [True, False])
