@@ -119,7 +119,7 @@ def _oracle_grads(state):
 # --------------------------------------------------------------------------------------------------------- follower
 
 def _follower(B, S, *, train, seed=11, weights='plain', glove=True, bidir=False, two_stream=True, chunks=1,
-              persistent=True, min_len=10, max_len=79, a_max=14, stop_prob=1.0 / 6.0, mutate=None):
+              persistent=True, min_len=10, max_len=79, a_max=14, stop_prob=1.0 / 6.0, mutate=None, max_length=80):
     from speaker_follower_amd import model, features, follower as fol
     if bidir:
         enc_w = synth.bidirectional_encoder_weights(seed)
@@ -141,7 +141,7 @@ def _follower(B, S, *, train, seed=11, weights='plain', glove=True, bidir=False,
         mutate(fb)
     table = synth.feature_table(seed + 3, 256)
     store = features.FeatureStore(table)
-    batch = fol.DeviceFollowerBatch.from_synth(fb)
+    batch = fol.DeviceFollowerBatch.from_synth(fb, max_length=max_length)
 
     def run(persistent=persistent, two_stream=two_stream):
         """One training pass through a fresh engine (same sites, same masks): (state, {enc/dec: gradients})."""
@@ -161,7 +161,7 @@ def _follower(B, S, *, train, seed=11, weights='plain', glove=True, bidir=False,
     logits = st.logits.detach().cpu().numpy()
     loss = float(st.loss.detach())
 
-    seq, mask, lens = np_env.batch_instructions_from_encoded(fb.instr, 80, reverse=True)
+    seq, mask, lens = np_env.batch_instructions_from_encoded(fb.instr, max_length, reverse=True)
     T, rows, site0 = max(lens), np.arange(B), st.site0
     loc = np_env.static_loc_embeddings()
     H, F, E = D.hidden, D.feat, D.word
@@ -173,8 +173,8 @@ def _follower(B, S, *, train, seed=11, weights='plain', glove=True, bidir=False,
                 torch.tensor(orng.dropout_mask(SEED, 2 * (site0 + t) + 1, rows, H, 0.5)))
     drop_emb = None
     if train and not glove:
-        drop_emb = torch.tensor(orng.dropout_mask(SEED ^ ENC_SEED_XOR, site0 ^ EMB_STREAM_XOR, rows, 80 * E, 0.5)
-                                .reshape(B, 80, E))
+        drop_emb = torch.tensor(orng.dropout_mask(SEED ^ ENC_SEED_XOR, site0 ^ EMB_STREAM_XOR, rows, max_length * E, 0.5)
+                                .reshape(B, max_length, E))
     out = {}
     for dt in (torch.float64, torch.float32):
         e = torch_ref.to_torch(enc_w, True, frozen=('embedding.weight',) if glove else (), dtype=dt)
