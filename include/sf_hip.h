@@ -998,6 +998,81 @@ int sf_gate_product_bf16_supported(int M, int K1, int K2, int N);
  * instantiation of its kernel from the source's tag, and returns before launching where it has none. */
 int sf_feature_table_f16(const void* table, int on);
 int sf_feature_table_is_f16(const void* table);
+/* PROJECTED FEATURE TABLES for the inference decode step (opt-in, additive to ABI 9).
+ *
+ * The decode step dots 36 panorama rows with q = M_v h1 + c_v and up to 16 candidate rows with r = M_a h~ (+ constants;
+ * sf_decoder_fold).  Both products only carry the hidden state out to feature space.  In inference the rows are rows of the
+ * HBM-resident feature table and the weights are constant, so the association is turned round ONCE per (table, weights):
+ *     x . (M_v h1 + c_v) = (x^T M_v) . h1 + x . c_v            u . (M_a h~ + c_a) = (u^T M_a) . h~ + u . c_a
+ * and the brackets are rows of four tables.  With F = IMG + LOC, ld = sf_projected_ld(H) = H + 1 rounded up to 4 floats
+ * (rows are 16-byte aligned; the padding columns hold zeros):
+ *     pv [n_rows, ld]   row n = [x_n^T M_v[:IMG, :] | x_n . c_v[:IMG]]                (n_rows = n_viewpoints * V)
+ *     pa [n_rows, ld]   row n = [x_n^T M_a[:IMG, :] | x_n . c_a[:IMG]]
+ *     lv [V * V, ld]    the same of the location-embedding table's rows with M_v[IMG:, :], c_v[IMG:]
+ *     la [5, ld]        rows 0..3: [sum_{j in block g} M_a[IMG + j, :] | sum_{j in block g} c_a[IMG + j]] for the four
+ *                       sin/cos groups of a candidate's location part (each value repeated LOC/4 times, contiguous);
+ *                       row 4: [m | c0], the constant row of the scoring fold (m_a row F, c_a[F])
+ * A decode step then needs TWO dependent launches behind the LSTM cell instead of four: (1) folded text attention || y;
+ * (2) scoring + glue on pa / la with h~ formed in the body || the attention of step t + 1 scored from pv / lv and h1
+ * (sf_debug_projected_partials_late below moves its partials into (1)).  Step 0's attention is one launch from h_init.
+ * The products q, t_v', t_a, wt and r are not issued and their tape slots are NOT written.
+ *
+ * MEMORY AND COST: pv and pa take n_rows * ld * 4 bytes each -- 0.79 GB each (1.57 GB together) for the 10 567 viewpoints
+ * of the full R2R table at H = 512 -- and the build is 2 * n_rows * IMG * ld * 2 flop = 1.6 Tflop of fp32-class products
+ * (13 ms measured on MI355X).  Worth it for a rollout that is replayed, not for one.
+ *
+ *   sf_projected_build(fold, table, n_rows, loc_table, V, IMG, LOC, H, pv, pa, lv, la, ws, ws_bytes, stream)
+ *                                 fills the four tables from the fold matrices of sf_decoder_fold_build and the fp32 table
+ *                                 (SF_ERR_UNSUPPORTED for a table registered as binary16), 16 384 table rows per product,
+ *                                 64-bit row offsets, straight into the tables.  IMG % 4 == 0, LOC % 16 == 0, H % 4 == 0.
+ *   sf_projected_register(table, p)
+ *                                 the tables of `table` (p == NULL forgets the address).  sf_pano / sf_cands keep their
+ *                                 layout: like sf_feature_table_f16 the library knows the tables by the table's ADDRESS.
+ *                                 One entry per address, 16 addresses, under a mutex.  key_v / key_a name the decoder the
+ *                                 tables were built for (sf_visual_w.w_h and sf_scoring_w.w_h): a step of another decoder,
+ *                                 another location table or other V / IMG / LOC does not take them.
+ *                                 LIFETIME: the lookup happens when a step is ENQUEUED (or captured); the caller keeps the
+ *                                 tables alive, and their contents current (rebuild in place when a weight changes), for
+ *                                 as long as they are registered and any captured hipGraph that ran with them may replay.
+ *   sf_projected_registered(table, out)   1 and *out (optional) when the address is registered, else 0.
+ *   sf_projected_use(on) / _is_used()     process-wide switch (default on): off, no step looks the tables up.
+ *   sf_projected_steps()                  decode steps issued on the projected chain since the library was loaded (step 0's
+ *                                         one-launch head is not a step and is not counted).
+ *                                         Both are PROCESS-WIDE: a caller that toggles the switch around a call, or reads the
+ *                                         counter before and after it to learn which chain ran, must not have another
+ *                                         thread issuing decode steps meanwhile.
+ * cand_sincos must be INITIALISED (finite) for every slot of [B, A], padding slots included: the scoring body blends a
+ * padded slot's values arithmetically (times 0) where the unprojected kernels select.
+ * The chain is taken by sf_follower_episode_fwd only (sf_attn_decoder_tail_fwd has no folded context to hand it), when ALL
+ * of these hold, and declines -- before
+ * its first launch -- to the chain the step takes today otherwise: the folded text stage applies (inference, ctx_q / ctx_o
+ * given); panorama and candidates are index-form rows of the registered fp32 table; the next panorama is known (X_next) or
+ * this is the last step; a glue is given; B <= 256. */
+typedef struct sf_projected {
+    const float *pv, *pa, *lv, *la;
+    const float* loc_table;      /* the location-embedding table lv was built from */
+    const float *key_v, *key_a;  /* sf_visual_w.w_h, sf_scoring_w.w_h of the decoder the tables belong to */
+    int32_t H, ld, V, IMG, LOC, reserved;
+} sf_projected;
+int sf_projected_ld(int H);
+int sf_projected_build(const sf_decoder_fold* fold, const float* table, long long n_rows, const float* loc_table, int V, int IMG,
+                       int LOC, int H, float* pv, float* pa, float* lv, float* la, void* ws, size_t ws_bytes,
+                       sf_stream stream);
+int sf_projected_register(const void* table, const sf_projected* p);
+int sf_projected_registered(const void* table, sf_projected* out);
+void sf_projected_use(int on);
+int sf_projected_is_used(void);
+long long sf_projected_steps(void);
+/* 1 when a decode step of this shape on index-form fp32 rows can take the projected chain (what a caller asks BEFORE it
+ * spends the memory and the build; the step itself still checks its small-product plan and declines if that fails). */
+int sf_projected_supported(int B, int H, int L, int A, int V, int IMG, int LOC);
+/* Test switch: table rows per product of sf_projected_build (default 16 384; rows <= 0 restores it), so that a build of
+ * several chunks -- the 64-bit row offsets between them -- can be checked on a small table. */
+void sf_debug_projected_chunk_rows(int rows);
+/* A/B switch of the projected chain: on != 0 (the default: measured faster) puts the attention partials of step
+ * t + 1 into launch (2) (partials, ticket and merge beside the scoring; launch (1) is the text stage and y alone); 0 puts
+ * them into launch (1) and leaves launch (2) their merge. */
+void sf_debug_projected_partials_late(int on);
 /* Older name of the same switch (tools/, A/B timing): on != 0 runs the large LSTM gate products (K >= 2048, M <= 128: sf_lstm_cell_fwd, the decode
  * step) on the fp32 MFMA (v_mfma_f32_16x16x4_f32, rounds 1-3) instead of the bf16 matrix cores with three-way
  * error-free operand splitting (csrc/sf_gemm.hip: gemm_nt_split_kernel; same fp32 accuracy class, measured closer

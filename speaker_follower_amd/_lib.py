@@ -54,6 +54,12 @@ ScoringW = _ptr_struct('ScoringW', ['w_h', 'b_h', 'w_a', 'b_a', 'w_out', 'b_out'
 DecoderFold = _ptr_struct('DecoderFold', ['m_v', 'c_v', 'm_a', 'c_a'])
 
 
+class Projected(C.Structure):
+    """sf_projected: the projected feature tables of one (feature table, decoder)."""
+    _fields_ = [(n, c_p) for n in ('pv', 'pa', 'lv', 'la', 'loc_table', 'key_v', 'key_a')] + \
+               [(n, C.c_int32) for n in ('H', 'ld', 'V', 'IMG', 'LOC', 'reserved')]
+
+
 class DecoderW(C.Structure):
     _fields_ = [('lstm', LstmW), ('visual', VisualW), ('text', SoftdotW), ('action', ScoringW),
                 ('fold', C.POINTER(DecoderFold))]
@@ -199,6 +205,17 @@ _SIGNATURES = {
     'sf_gate_product_bf16_supported': (C.c_int, [i32, i32, i32, i32]),
     'sf_feature_table_f16': (C.c_int, [c_p, C.c_int]),
     'sf_feature_table_is_f16': (C.c_int, [c_p]),
+    'sf_projected_ld': (C.c_int, [C.c_int]),
+    'sf_projected_build': (C.c_int, [C.POINTER(DecoderFold), c_f, C.c_longlong, c_f, i32, i32, i32, i32, c_f, c_f, c_f,
+                                     c_f] + WS),
+    'sf_projected_register': (C.c_int, [c_p, C.POINTER(Projected)]),
+    'sf_projected_registered': (C.c_int, [c_p, C.POINTER(Projected)]),
+    'sf_projected_use': (None, [C.c_int]),
+    'sf_projected_is_used': (C.c_int, []),
+    'sf_projected_steps': (C.c_longlong, []),
+    'sf_debug_projected_partials_late': (None, [C.c_int]),
+    'sf_projected_supported': (C.c_int, [i32] * 7),
+    'sf_debug_projected_chunk_rows': (None, [C.c_int]),
     'sf_debug_tn_split_min_rows': (None, [C.c_int]),
     'sf_workspace_fault_offset': (C.c_size_t, [C.c_size_t]),
     'sf_debug_trace': (None, [C.c_void_p]),

@@ -97,6 +97,30 @@ int table_is_f16(const void* table) {
     return 0;
 }
 
+// ---- projected feature tables (include/sf_hip.h: sf_projected_register) -------------------------------------------------
+// Like the storage tag above, the tables reach the library by the ADDRESS of the feature table they were built from: no
+// struct of ABI 9 changes layout.  One entry per table; an entry also names the decoder it belongs to (two of its weights)
+// and the location table, and a step whose decoder or location table is another one does not see it.
+constexpr int PROJ_TABLES = 16;
+struct ProjEntry { const void* table; sf_projected p; };
+ProjEntry g_proj[PROJ_TABLES];
+int g_proj_n = 0;
+std::mutex g_proj_mutex;
+std::atomic<int> g_proj_use{1};             // sf_projected_use
+std::atomic<long long> g_proj_steps{0};     // sf_projected_steps: decode steps issued on the projected chain
+static int g_proj_partials_late = 1;        // sf_debug_projected_partials_late (0: the attention partials in launch (1))
+bool projected_lookup(const void* table, sf_projected* out) {
+    if (!table || !g_proj_use.load(std::memory_order_relaxed)) return false;
+    std::lock_guard<std::mutex> lock(g_proj_mutex);
+    for (int i = 0; i < g_proj_n; ++i)
+        if (g_proj[i].table == table) {
+            *out = g_proj[i].p;
+            return true;
+        }
+    return false;
+}
+inline int projected_ld(int H) { return (H + 1 + 3) & ~3; }
+
 // the ONLY places that turn the C structs into the kernels' sources: a dense source is never half
 inline PanoSrc pano(const sf_pano* p) {
     return PanoSrc{p->dense, p->table, p->loc_table, p->vp, p->view, p->V, p->IMG, p->LOC,
@@ -589,6 +613,94 @@ int sf_feature_table_f16(const void* table, int on) {
     return SF_OK;
 }
 int sf_feature_table_is_f16(const void* table) { return table_is_f16(table); }
+int sf_projected_ld(int H) { return H > 0 ? projected_ld(H) : 0; }
+int sf_projected_register(const void* table, const sf_projected* p) {
+    SF_CHECK_ARG(table);
+    if (p)
+        SF_CHECK_ARG(p->pv && p->pa && p->lv && p->la && p->loc_table && p->key_v && p->key_a && p->H > 0 && p->H % 4 == 0 &&
+                     p->ld == projected_ld(p->H) && p->V > 0 && p->IMG > 0 && p->LOC > 0);
+    std::lock_guard<std::mutex> lock(g_proj_mutex);
+    int at = -1;
+    for (int i = 0; i < g_proj_n; ++i)
+        if (g_proj[i].table == table) at = i;
+    if (!p) {                                                   // forget the address (unknown: nothing to do)
+        if (at >= 0) g_proj[at] = g_proj[--g_proj_n];
+        return SF_OK;
+    }
+    if (at < 0) {
+        if (g_proj_n == PROJ_TABLES) return SF_ERR_UNSUPPORTED;
+        at = g_proj_n++;
+    }
+    g_proj[at] = ProjEntry{table, *p};
+    return SF_OK;
+}
+int sf_projected_registered(const void* table, sf_projected* out) {
+    std::lock_guard<std::mutex> lock(g_proj_mutex);
+    for (int i = 0; i < g_proj_n; ++i)
+        if (table && g_proj[i].table == table) {
+            if (out) *out = g_proj[i].p;
+            return 1;
+        }
+    return 0;
+}
+void sf_projected_use(int on) { g_proj_use.store(on ? 1 : 0, std::memory_order_relaxed); }
+int sf_projected_is_used(void) { return g_proj_use.load(std::memory_order_relaxed); }
+long long sf_projected_steps(void) { return g_proj_steps.load(std::memory_order_relaxed); }
+void sf_debug_projected_partials_late(int on) { g_proj_partials_late = on; }
+// rows of the feature table one product of the build takes (its output, the largest thing in flight, is 34 MB)
+constexpr long long PROJ_CHUNK_ROWS = 16384;
+static long long g_proj_chunk_rows = PROJ_CHUNK_ROWS;      // sf_debug_projected_chunk_rows
+void sf_debug_projected_chunk_rows(int rows) { g_proj_chunk_rows = rows > 0 ? rows : PROJ_CHUNK_ROWS; }
+// the shape test of the chain (proj_chain_supported) for a caller that has not built anything yet: 1 when a step of this
+// shape on index-form fp32 rows can take the chain (the small-product plan of y is still the step's to check)
+int sf_projected_supported(int B, int H, int L, int A, int V, int IMG, int LOC) {
+    if (H <= 0 || IMG <= 0 || LOC <= 0 || V <= 0) return 0;
+    static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
+    static const int idummy[1] = {0};
+    CandSrc us{};
+    us.table = dummy; us.a_num = idummy; us.A = A; us.V = V; us.IMG = IMG; us.LOC = LOC;
+    PanoSrc xn{};
+    xn.table = dummy; xn.V = V; xn.IMG = IMG; xn.LOC = LOC;
+    const ProjTables pt{dummy, dummy, dummy, dummy, projected_ld(H), H};
+    return proj_chain_supported(us, &xn, B, H, L, pt) ? 1 : 0;
+}
+int sf_projected_build(const sf_decoder_fold* fold, const float* table, long long n_rows, const float* loc_table, int V, int IMG,
+                       int LOC, int H, float* pv, float* pa, float* lv, float* la, void* ws, size_t ws_bytes,
+                       sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(fold && fold->m_v && fold->c_v && fold->m_a && fold->c_a && table && loc_table && pv && pa && lv && la &&
+                 n_rows > 0 && V > 0 && IMG > 0 && IMG % 4 == 0 && LOC > 0 && LOC % 16 == 0 && H > 0 && H % 4 == 0);
+    if (table_is_f16(table)) return SF_ERR_UNSUPPORTED;
+    const int F = IMG + LOC, Fa = F + 4, ld = projected_ld(H), Ks = LOC + 4, g = LOC / 4;
+    Arena ar = arena(ws, ws_bytes);
+    hipStream_t st = S(stream);
+    // the folds transposed to the [N, K] layout of the products below, the constant as row H, zero rows up to ld:
+    //   wt_v [ld, F]     = [M_v^T ; c_v ; 0]
+    //   wt_a [ld, F + 4] = [M_a^T ; c_a ; 0]   (column F of M_a^T is m, c_a[F] is c0: sf_decoder_fold_build)
+    float* wt_v = ar.take((size_t)ld * F);
+    float* wt_a = ar.take((size_t)ld * Fa);
+    float* sel = ar.take((size_t)5 * Ks);      // rows 0..3: ones over block g of the location part; row 4: one at column F
+    NEED(wt_v && wt_a && sel);
+    TRY(fill(wt_v + (size_t)H * F, (size_t)(ld - H) * F, 0.f, st));
+    TRY(fill(wt_a + (size_t)H * Fa, (size_t)(ld - H) * Fa, 0.f, st));
+    TRY(transpose(fold->m_v, F, H, wt_v, st));
+    TRY(transpose(fold->m_a, Fa, H, wt_a, st));
+    TRY(add2(fold->c_v, F, nullptr, 0, 1, F, wt_v + (size_t)H * F, F, st));
+    TRY(add2(fold->c_a, Fa, nullptr, 0, 1, Fa, wt_a + (size_t)H * Fa, Fa, st));
+    TRY(fill(sel, (size_t)5 * Ks, 0.f, st));
+    for (int q = 0; q < 4; ++q) TRY(fill(sel + (size_t)q * Ks + (size_t)q * g, (size_t)g, 1.f, st));
+    TRY(fill(sel + (size_t)4 * Ks + LOC, 1, 1.f, st));
+    // the two large tables, PROJ_CHUNK_ROWS rows of the feature table per product (64-bit row offsets; the products write
+    // straight into the tables: no temporary beyond the transposed folds above)
+    for (long long r0 = 0; r0 < n_rows; r0 += g_proj_chunk_rows) {
+        const int m = (int)std::min<long long>(g_proj_chunk_rows, n_rows - r0);
+        const float* x = table + (size_t)r0 * IMG;
+        TRY(linear_plain(x, IMG, wt_v, F, nullptr, m, ld, IMG, EPI_NONE, pv + (size_t)r0 * ld, ld, ar, st));
+        TRY(linear_plain(x, IMG, wt_a, Fa, nullptr, m, ld, IMG, EPI_NONE, pa + (size_t)r0 * ld, ld, ar, st));
+    }
+    TRY(linear_plain(loc_table, LOC, wt_v + IMG, F, nullptr, V * V, ld, LOC, EPI_NONE, lv, ld, ar, st));
+    return linear_plain(sel, Ks, wt_a + IMG, Fa, nullptr, 5, ld, Ks, EPI_NONE, la, ld, ar, st);
+}
 void sf_gate_product_bf16_weights(int on) { g_bf16w_on.store(on ? 1 : 0, std::memory_order_relaxed); }
 int sf_gate_product_bf16_weights_is_on(void) { return g_bf16w_on.load(std::memory_order_relaxed); }
 int sf_gate_product_bf16_supported(int M, int K1, int K2, int N) {
@@ -902,6 +1014,52 @@ static int fold_score(const TailStep& s, float* merge_part, const float* r, int 
     return score_fwd(s.us, s.B, s.D, r, wt, b_a, b_out, s.tp->logit, s.st, ldr, cst);
 }
 
+// Projected chain (inference; tables of sf_projected_build registered for the step's feature table and decoder): TWO
+// dependent launches behind the cell --
+//   (1) folded text attention  ||  y = W_out[:, H:] h1  ||  attention partials of step t+1, scores from projected rows and h1
+//   (2) scoring + glue on projected candidate rows, h~ = tanh(z + y) formed in the body  ||  merge of the partials
+// q, t_v', t_a, wt and r are never formed (and their tape slots not written: nothing runs backward through this step).
+// PLACEMENT of the partials (sf_debug_projected_partials_late, default 1): in (2) -- partials, ticket and merge beside the
+// scoring (pair_proj_score_kernel<0>), (1) the text stage and y alone -- because the attention body's ~190 registers per
+// lane hold every block of the grid it is compiled into to one workgroup per CU: measured at B = 100, (1) with the
+// partials 23.2 us + (2) 7.2 us against 10.2 us + 17.9 us with them in (2) (1.523 against 1.480 ms per rollout).
+// the registered tables of (candidate table, decoder) where the chain's shapes hold for them (xn: the panorama whose
+// attention rides along, or null)
+static bool projected_for(const sf_decoder_w* w, const CandSrc& us, const PanoSrc* xn, int B, int H, int L, ProjTables* pt) {
+    sf_projected reg;
+    if (us.dense || us.half || !projected_lookup(us.table, &reg)) return false;
+    if (reg.key_v != w->visual.w_h || reg.key_a != w->action.w_h || reg.V != us.V || reg.IMG != us.IMG || reg.LOC != us.LOC ||
+        (xn && xn->loc_table != reg.loc_table))
+        return false;
+    *pt = ProjTables{reg.pv, reg.pa, reg.lv, reg.la, reg.ld, reg.H};
+    return proj_chain_supported(us, xn, B, H, L, *pt);
+}
+
+static int tail_proj(const TailStep& s, const TextFold& tf) {
+    const sf_decoder_tape *tp = s.tp, *tn = s.tn;
+    const int B = s.B, H = s.H, F = s.F;
+    // ---- plan
+    ProjTables pt;
+    if (!s.glue || s.query_only || !(s.paired || s.last_step) ||
+        !projected_for(s.w, s.us, s.paired ? &s.xn : nullptr, B, H, s.L, &pt))
+        return SF_ERR_UNSUPPORTED;
+    Arena af = s.ar;
+    const FoldScratch f = fold_scratch(s, af, 0);
+    SmallPlan py;
+    const bool ok = f.ok &&
+        plan_linear(tp->cat2 + H, 2 * H, s.w->text.w_out + H, 2 * H, nullptr, B, H, H, EPI_NONE, f.ybuf, f.ldp, &py) == SF_OK &&
+        py.mt == 1 && py.cpw == 4 && (!s.paired || af.tickets());
+    if (!ok) return SF_ERR_UNSUPPORTED;
+    // ---- issue (the first launch checks its shapes before it launches: it may still decline)
+    const bool late = s.paired && g_proj_partials_late;
+    TRY(pair_proj_textfold(tf.ctx_q, tf.ctx_o, s.ctx_mask, B, s.L, H, tp->cat2 + H, 2 * H, f.tpart, f.tcount, f.zbuf, f.ldp,
+                           tp->alpha, py, s.us, s.paired && !late ? &s.xn : nullptr, pt, tp->h1, H, f.part, s.st));
+    g_proj_steps.fetch_add(1, std::memory_order_relaxed);
+    return issued(pair_proj_score(s.us, B, H, s.L, pt, f.zbuf, f.ldp, f.ybuf, f.ldp, make_glue(s.us, B, tp->logit, s.glue),
+                                  s.paired ? &s.xn : nullptr, late ? 0 : 2, tp->h1, H, s.paired ? tn->alpha_v : nullptr,
+                                  s.paired ? tn->xin + F : nullptr, 2 * F, s.dn_in, F, f.part, af.tickets(), s.st));
+}
+
 // Folded text stage + folded query / scoring products (sf_decoder_fold through sf_follower_episode.chain_fold):
 // THREE dependent launches behind the cell --
 //   (1) folded text attention  ||  y = W_out[:, H:] h1  ||  q' = M_v h1 + c_v      (t_v' is never formed)
@@ -1126,7 +1284,8 @@ static int tail_dispatch(const TailStep& s, const TextFold* tf) {
     const bool foldable = (s.paired || s.query_only || s.last_step) && tf && !s.w->fold && !s.ctx_row && !s.d_h.on() &&
                           s.w->text.w_out;
     int rc = SF_ERR_UNSUPPORTED;
-    if (foldable && tf->mats && g_fold_chain3) rc = tail_fold3(s, *tf);
+    if (foldable) rc = tail_proj(s, *tf);
+    if (rc == SF_ERR_UNSUPPORTED && foldable && tf->mats && g_fold_chain3) rc = tail_fold3(s, *tf);
     if (rc == SF_ERR_UNSUPPORTED && foldable && s.w->action.w_a_t) rc = tail_fold4(s, *tf);
     if (rc != SF_ERR_UNSUPPORTED) return rc;
     if (s.paired && s.w->fold) return tail_decoder_fold(s);
@@ -1521,7 +1680,23 @@ int sf_follower_episode_fwd(const sf_decoder_w* w, const sf_follower_episode* e,
         // (beside the fold products the head keeps the FRONT three quarters of the workspace -- and the same ticket words)
         Arena ha = arena(ws, ws_bytes);
         if (fold_fork.side) ha.cap -= ha.cap / 4;
-        TRY(decoder_head_a(w, &cur.X, e->B, e->H, e->D, e->h_init, &cur.tp, drop, e->step0, ha, stream));
+        // the projected chain's head: attention straight from h_init through the projected rows, ONE launch instead of
+        // t_v', q' and the attention (same conditions as the steps: tail_proj)
+        const PanoSrc x0 = pano(&cur.X);
+        ProjTables pt;
+        float* part = nullptr;
+        bool head_done = false;
+        if (tf && !e->glue.nav && e->B <= VIS_SPLIT_MAX_B && projected_for(w, cands(&cur.U), &x0, e->B, e->H, e->L, &pt) &&
+            (part = ha.take(visual_attn_split_floats(e->B, x0.IMG + x0.LOC))) && ha.tickets()) {
+            const int F = x0.IMG + x0.LOC;
+            const int rc = visual_attn_proj(cands(&cur.U), x0, e->B, e->H, e->L, pt, e->h_init, e->H, cur.tp.alpha_v,
+                                            cur.tp.xin + F, 2 * F, make_dropout(drop, 2 * e->step0, 2), F, part, ha.tickets(),
+                                            S(stream));
+            if (rc == SF_OK) head_done = true;
+            else if (rc != SF_ERR_UNSUPPORTED) return rc;
+        }
+        if (!head_done)
+            TRY(decoder_head_a(w, &cur.X, e->B, e->H, e->D, e->h_init, &cur.tp, drop, e->step0, ha, stream));
     }
     if (fold_fork.side) TRY(fold_fork.join());      // (the head ran beside the fold products: join behind it)
     // A device-resident environment (sf_nav_io of step 0 in glue.nav; state buffers stacked [S + 1][...]): the

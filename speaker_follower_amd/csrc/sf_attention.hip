@@ -29,6 +29,10 @@ struct VisArgs {
     const double* vec64;   // the query in float64 (visual_split_body<0, true>: scores accumulated in float64), or null
     int vec_slabs;         // MODE 1: `vec` is the sum of this many K-split slabs (0 / 1: a plain vector) ...
     long vec_slab_stride;  // ... `vec_slab_stride` floats apart: the workgroup adds them up itself (no reduce launch)
+    // PROJ bodies only (visual_split_body<.., PROJ>): the scores come from PROJECTED rows -- `vec` is h1 [B, ldvec], not q
+    const float* pv;       // [n_vp * V, ldp]: row n = [x_n^T M_v[:IMG, :] | x_n . c_v[:IMG]]
+    const float* lv;       // [V * V, ldp]: the same of the location-embedding table's rows
+    int ldp, pH;           // row stride of both (floats, a multiple of 4); H (the constant sits at column H)
 };
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
@@ -200,7 +204,12 @@ __device__ __forceinline__ void vis_stamp(const VisSplit& sp, int block, int slo
 //          accumulated in float64; a group's record holds its scores RELATIVE to its own maximum (small numbers:
 //          exact in fp32 to 1e-7 of the softmax weight, where a raw score of +-80 would carry 4e-6) and that maximum as a
 //          float64 in two dwords.
-template <int PHASE, bool F64 = false, bool H16 = false>
+// PROJ (the projected decode chain, sf_api.hip: tail_proj): x_v . q with q = M_v h1 + c_v is re-associated to
+//          (x_v^T M_v) . h1 + x_v . c_v, and the bracket is a row of a table built once per (feature table, weights):
+//          score_v = (PV[row_v][:H] + LV[view * V + v][:H]) . h1 + PV[row_v][H] + LV[..][H].  The query q is never
+//          formed; the rows themselves are still loaded (the weighted sum needs them) and the record is unchanged.
+constexpr int PRJ_CPL = 2;                             // float4 per lane of a projected row: H <= 512
+template <int PHASE, bool F64 = false, bool H16 = false, bool PROJ = false>
 __device__ __forceinline__ void visual_split_body(const VisArgs& a, const VisSplit& sp, int g, int b) {
     __shared__ float4 slots[VSP_SLOTS][VIS_CPL * 64];
     __shared__ float s_score[64];
@@ -261,9 +270,35 @@ __device__ __forceinline__ void visual_split_body(const VisArgs& a, const VisSpl
         m = 0.f;
         e = sd > -INFINITY ? expf(s) : 0.f;
     } else {
-    float dot[VIS_RPW];
+    float dot[VIS_RPW], cadd[VIS_RPW];
 #pragma unroll
-    for (int r = 0; r < VIS_RPW; ++r) dot[r] = 0.f;
+    for (int r = 0; r < VIS_RPW; ++r) dot[r] = cadd[r] = 0.f;
+    if (PROJ) {
+        // straight-line loads on clamped indices like the rows above: all of them are in flight together
+        const int n4h = a.pH >> 2;
+        const size_t r_img = (size_t)max(a.src.vp[b], 0) * V, r_loc = (size_t)a.src.view[b] * V;
+        float4 hv[PRJ_CPL];
+#pragma unroll
+        for (int i = 0; i < PRJ_CPL; ++i) {
+            const int c = lane + 64 * i;
+            const float4 t = reinterpret_cast<const float4*>(a.vec + (size_t)b * a.ldvec)[min(c, n4h - 1)];
+            hv[i] = c < n4h ? t : f4zero();
+        }
+#pragma unroll
+        for (int r = 0; r < VIS_RPW; ++r) {
+            const int v = min(g * VSP_RPG + wave * VIS_RPW + r, V - 1);
+            const float* pr = a.pv + (r_img + v) * (size_t)a.ldp;
+            const float* lr = a.lv + (r_loc + v) * (size_t)a.ldp;
+#pragma unroll
+            for (int i = 0; i < PRJ_CPL; ++i) {
+                const int cc = min(lane + 64 * i, n4h - 1);
+                float4 t = reinterpret_cast<const float4*>(pr)[cc];
+                f4add(t, reinterpret_cast<const float4*>(lr)[cc]);
+                dot[r] += dot4(t, hv[i]);                          // (hv is zero beyond H)
+            }
+            cadd[r] = pr[a.pH] + lr[a.pH];
+        }
+    } else {
 #pragma unroll
     for (int i = 0; i < VIS_CPL; ++i) {
         const int c = lane + 64 * i;
@@ -272,9 +307,11 @@ __device__ __forceinline__ void visual_split_body(const VisArgs& a, const VisSpl
 #pragma unroll
         for (int r = 0; r < VIS_RPW; ++r) dot[r] += dot4(x[r][i], q);
     }
+    }
 #pragma unroll
     for (int r = 0; r < VIS_RPW; ++r) {
-        const float sw = wave_sum(dot[r]);
+        float sw = wave_sum(dot[r]);
+        if (PROJ) sw = prow.zero ? 0.f : sw + cadd[r];            // (an all-zero panorama scores 0 everywhere, as x . q does)
         const int vl = wave * VIS_RPW + r;
         if (lane == 0) s_score[vl] = (g * VSP_RPG + vl < V) ? sw : -INFINITY;
     }
@@ -411,6 +448,10 @@ __device__ __forceinline__ void visual_split_body(const VisArgs& a, const VisSpl
 template <bool H16>
 __global__ __launch_bounds__(VSP_NW * 64) void visual_attn_split_kernel(VisArgs a, VisSplit sp) {
     visual_split_body<0, false, H16>(a, sp, blockIdx.x, blockIdx.y);
+}
+// the whole split attention on PROJECTED rows as a launch of its own (step 0's head of the projected chain: vec = h_init)
+__global__ __launch_bounds__(VSP_NW * 64) void visual_attn_split_proj_kernel(VisArgs a, VisSplit sp) {
+    visual_split_body<0, false, false, true>(a, sp, blockIdx.x, blockIdx.y);
 }
 template <bool H16>
 __global__ __launch_bounds__(VSP_NW * 64) void visual_attn_split_f64_kernel(VisArgs a, VisSplit sp) {
@@ -820,6 +861,126 @@ __global__ __launch_bounds__(SC_NW * 64) void pair_score_merge_kernel(ScoreArgs 
 
 
 // =================================================================================================
+// Scoring on PROJECTED candidate rows (the projected decode chain, sf_api.hip: tail_proj).
+// logit[b,a] = u_a . r + c with [r | c] = M_a h~ + c_a (sf_decoder_fold) re-associated to (u_a^T M_a) . h~ + u_a . c_a + c:
+// the image part of the bracket is row (vp, cand_view) of PA -- candidate rows are rows of the same panoramas -- and the
+// location part, four values each repeated LOC/4 times (cand_load), is sum_g sc_g LA[g].  LA[4] = [m | c0] is the
+// constant row of the fold (c = m . h~ + c0), which is all a zero row (stop, padding, padded sample) gets.
+// h~ = tanh(z + y) is formed here from the two buffers the A-prologue of the unprojected chains reads (apro_form).
+// 8 waves, two candidate slots per wave (A <= 16): a projected row is 2 KB, so nothing about it is register-bound.
+// The chosen action's UNPROJECTED row (the next gate product needs all of it) is gathered behind the choice.
+// =================================================================================================
+struct ProjScoreArgs {
+    CandSrc src;
+    const float* pa;       // [n_vp * V, ldp]: row n = [x_n^T M_a[:IMG, :] | x_n . c_a[:IMG]]
+    const float* la;       // [5, ldp]: the four sin/cos groups of the location part, then [m | c0]
+    int ldp, H;
+    const float* z;        // [B, ldz] merged text-attention sum (text_fold_body)
+    const float* y;        // [B, ldy] W_out[:, H:] h1
+    int ldz, ldy;
+};
+
+__device__ __forceinline__ void proj_score_glue_body(const ProjScoreArgs& a, const FGlue& g, int b) {
+    constexpr int NW = SMALL_WAVES, SLOTS = 2;
+    __shared__ float s_logit[64];
+    __shared__ int s_at;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int A = a.src.A, V = a.src.V, H = a.H, n4h = H >> 2;
+    const size_t ldp = (size_t)a.ldp;
+    const FGlueIn gin = follower_glue_load(g, b);               // (used by wave 0; cheap for the rest)
+    // every wave keeps the sample's candidate list with lane a holding candidate a: the slots below and the gather
+    // behind the choice take theirs by shuffle, not by a second round trip
+    const int vp = a.src.vp[b], an = a.src.a_num[b];
+    const int cvl = a.src.cand_view[(size_t)b * A + min(lane, A - 1)];
+    const float4 scl = reinterpret_cast<const float4*>(a.src.cand_sincos)[(size_t)b * A + min(lane, A - 1)];
+    float4 zv[PRJ_CPL], yv[PRJ_CPL], lav[5][PRJ_CPL], pav[SLOTS][PRJ_CPL];
+    float lac[5], pac[SLOTS];
+#pragma unroll
+    for (int i = 0; i < PRJ_CPL; ++i) {
+        const int cc = min(lane + 64 * i, n4h - 1);
+        zv[i] = reinterpret_cast<const float4*>(a.z + (size_t)b * a.ldz)[cc];
+        yv[i] = reinterpret_cast<const float4*>(a.y + (size_t)b * a.ldy)[cc];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) lav[q][i] = reinterpret_cast<const float4*>(a.la + q * ldp)[cc];
+    }
+#pragma unroll
+    for (int q = 0; q < 5; ++q) lac[q] = a.la[q * ldp + H];
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) {
+        const int view = __shfl(cvl, min(wave + NW * k, A - 1), WAVE);
+        const float* pr = a.pa + ((size_t)max(vp, 0) * V + min(max(view, 0), V - 1)) * ldp;
+#pragma unroll
+        for (int i = 0; i < PRJ_CPL; ++i) pav[k][i] = reinterpret_cast<const float4*>(pr)[min(lane + 64 * i, n4h - 1)];
+        pac[k] = pr[H];
+    }
+    float4 ht[PRJ_CPL];
+#pragma unroll
+    for (int i = 0; i < PRJ_CPL; ++i) ht[i] = lane + 64 * i < n4h ? apro_form(yv[i], zv[i]) : f4zero();
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) {
+        const int ac = wave + NW * k, acc = min(ac, A - 1);
+        const float s0 = __shfl(scl.x, acc, WAVE), s1 = __shfl(scl.y, acc, WAVE), s2 = __shfl(scl.z, acc, WAVE),
+                    s3 = __shfl(scl.w, acc, WAVE);
+        // (blended arithmetically, never branched on: rows are finite, a zero row keeps the constant row alone)
+        const float hm = (ac < A && ac != 0 && ac < an && vp >= 0) ? 1.f : 0.f;
+        float d = 0.f;
+#pragma unroll
+        for (int i = 0; i < PRJ_CPL; ++i) {
+            float4 w = pav[k][i];
+            f4fma(w, s0, lav[0][i]);
+            f4fma(w, s1, lav[1][i]);
+            f4fma(w, s2, lav[2][i]);
+            f4fma(w, s3, lav[3][i]);
+            float4 t = lav[4][i];
+            f4fma(t, hm, w);
+            d += dot4(t, ht[i]);
+        }
+        d = wave_sum(d);
+        const float cst = lac[4] + hm * (pac[k] + s0 * lac[0] + s1 * lac[1] + s2 * lac[2] + s3 * lac[3]);
+        if (lane == 0 && ac < A) s_logit[ac] = d + cst;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const int at = follower_glue_row(g, b, lane < A ? s_logit[lane] : 0.f, gin);
+        if (lane == 0) s_at = at;
+        if (g.nav.on && lane < A) nav_advance_slot(g.nav, b, lane, at, gin.was_ended || at == 0);
+    }
+    __syncthreads();
+    if (g.u_next) {                                              // block-uniform
+        const int at = min(max(s_at, 0), A - 1);
+        const int n4 = (a.src.IMG + a.src.LOC) >> 2;
+        CandRow row;
+        row.zero = at == 0 || at >= an || vp < 0;
+        row.I4 = a.src.IMG >> 2;
+        row.g4 = max(a.src.LOC >> 4, 1);
+        const int view = __shfl(cvl, at, WAVE);
+        row.img = reinterpret_cast<const float4*>(a.src.table) + ((size_t)max(vp, 0) * V + min(max(view, 0), V - 1)) * row.I4;
+        row.img16 = nullptr;
+        row.s0 = __shfl(scl.x, at, WAVE); row.s1 = __shfl(scl.y, at, WAVE);
+        row.s2 = __shfl(scl.z, at, WAVE); row.s3 = __shfl(scl.w, at, WAVE);
+        for (int c = tid; c < n4; c += NW * 64) store_u_next(g, b, c, cand_load<false>(row, c, !row.zero, n4));
+    }
+}
+
+// launch (2) of the projected chain: scoring + glue beside the attention of step t + 1 --
+//   VPHASE 2: the merge of the partials launch (1) left (the default placement);
+//   VPHASE 0: partials, ticket and merge here (sf_debug_projected_partials_late: launch (1) is the text stage alone)
+template <int VPHASE>
+__global__ __launch_bounds__(SMALL_WAVES * 64) void pair_proj_score_kernel(ProjScoreArgs a, FGlue g, int nb, VisArgs v, VisSplit sp,
+                                                                         int nv) {
+    const int bid = blockIdx.x;
+    if (VPHASE == 0) {                                           // (the long blocks first)
+        if (bid >= nv) return proj_score_glue_body(a, g, bid - nv);
+        if (threadIdx.x >= VSP_NW * 64) return;
+        visual_split_body<0, false, false, true>(v, sp, bid % VSP_G, bid / VSP_G);
+    } else {
+        if (bid < nb) return proj_score_glue_body(a, g, bid);
+        if (threadIdx.x >= VSP_NW * 64) return;
+        visual_split_body<2>(v, sp, 0, bid - nb);
+    }
+}
+
+// =================================================================================================
 // The text attention in FOLDED form (inference only: nothing here is taped for a backward).
 // model.py:129-141 per decode step: t = W_in h1, s_l = ctx_l . t, alpha = softmax(s), wc = sum alpha_l ctx_l,
 // h~ = tanh(W_out [wc ; h1]).  The context does not change during an episode, so two products leave the per-step
@@ -1014,6 +1175,24 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_textfold_small_wide_ker
         small_gemm_body<1, 4>(a, (bid - nt) % gxa, (bid - nt) / gxa);
     else
         small_gemm_body<MTB, 4>(b, (bid - nt - na) % gxb, (bid - nt - na) / gxb);
+}
+
+// launch (1) of the projected chain: [projected attention partials of step t + 1 | text_fold groups | y = W_out[:, H:] h1]
+// (the partials blocks pull the most bytes: first in the grid).  VIS false: the instantiation without the partials body
+// (nv == 0: an episode's last step, or the partials ride in launch (2)) -- the attention body's ~190 registers per lane
+// would otherwise hold every text block of the grid to one workgroup per CU.
+template <int RPW, bool VIS>
+__global__ __launch_bounds__(SMALL_WAVES * 64) void pair_proj_textfold_kernel(VisArgs v, VisSplit sp, int nv, TxtFoldArgs t, int nt,
+                                                                            SmallArgs a, int gxa) {
+    const int bid = blockIdx.x;
+    if (VIS && bid < nv) {
+        if (threadIdx.x >= VSP_NW * 64) return;
+        visual_split_body<1, false, false, true>(v, sp, bid % VSP_G, bid / VSP_G);
+    } else if (bid < nv + nt) {
+        text_fold_body<RPW>(t, (bid - nv) % TXF_G, (bid - nv) / TXF_G);
+    } else {
+        small_gemm_body<1, 4>(a, (bid - nv - nt) % gxa, (bid - nv - nt) / gxa);
+    }
 }
 
 // t_a = W_h tanh(z + y) + b (A-prologue: z = the merged attention sum of the text_fold launch) beside q' = W_v^T t_v'
@@ -1412,6 +1591,79 @@ int pair_vis_apro(const PanoSrc* src, int B, const float* vec, int ldvec, float*
     else
         SF_PVA(1);
 #undef SF_PVA
+    return launch_status();
+}
+
+// ---- the projected decode chain (sf_api.hip: tail_proj).  proj_chain_supported is the PLAN: both launchers below check
+// it again and return SF_ERR_UNSUPPORTED before launching, but tail_proj asks first so that it declines as a whole.
+bool proj_chain_supported(const CandSrc& us, const PanoSrc* xn, int B, int H, int L, const ProjTables& pt) {
+    const int F = us.IMG + us.LOC;
+    if (!pt.pv || !pt.pa || !pt.lv || !pt.la || pt.H != H || (pt.ld & 3) || pt.ld < H + 1) return false;
+    if (H > PRJ_CPL * 256 || (H & 3) || H < 4 || L < 1 || L > TXF_G * SMALL_WAVES * 5 || B < 1 || B > VIS_SPLIT_MAX_B) return false;
+    if (us.dense || us.half || !us.table || !us.a_num || us.A > 2 * SMALL_WAVES || us.A < 1 || F > SC_CPL * 256 ||
+        (us.IMG & 3) || (us.LOC & 15))
+        return false;
+    if (xn && (xn->dense || xn->half || xn->table != us.table || xn->V != us.V || xn->IMG != us.IMG || xn->LOC != us.LOC ||
+               xn->V <= (VSP_G - 1) * VSP_RPG || xn->V > VSP_G * VSP_RPG || F > VIS_CPL * 256))
+        return false;
+    return true;
+}
+
+static VisArgs proj_vis_args(const PanoSrc& xn, const ProjTables& pt, const float* h1, int ldh1, float* alpha, float* out,
+                             int ldo, const Dropout& drop, int drop_col0) {
+    VisArgs va{xn, h1, ldh1, alpha, out, ldo, drop, drop_col0};
+    va.pv = pt.pv; va.lv = pt.lv; va.ldp = pt.ld; va.pH = pt.H;
+    return va;
+}
+
+// step 0's head: the visual attention straight from h through PV / LV, one launch (no t_v', no q)
+int visual_attn_proj(const CandSrc& us, const PanoSrc& x, int B, int H, int L, const ProjTables& pt, const float* h, int ldh,
+                     float* alpha, float* out, int ldo, const Dropout& drop, int drop_col0, float* split_part,
+                     unsigned* counter, hipStream_t st) {
+    if (!proj_chain_supported(us, &x, B, H, L, pt) || (ldh & 3) || (ldo & 3) || !split_part || !counter) return SF_ERR_UNSUPPORTED;
+    const VisArgs va = proj_vis_args(x, pt, h, ldh, alpha, out, ldo, drop, drop_col0);
+    SF_LAUNCH(visual_attn_split_proj_kernel, dim3(VSP_G, B), dim3(VSP_NW * 64), 0, st, va, VisSplit{split_part, counter, nullptr});
+    return launch_status();
+}
+
+// launch (1): folded text attention (+ its in-launch merge)  ||  y  ||  projected partials of step t + 1 (`xn` null: none)
+int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* mask, int B, int L, int H, const float* vec,
+                       int ldvec, float* part, unsigned* counter, float* z, int ldz, float* alpha, const SmallPlan& y,
+                       const CandSrc& us, const PanoSrc* xn, const ProjTables& pt, const float* h1, int ldh1, float* split_part,
+                       hipStream_t st) {
+    if (!(y.mt == 1 && y.cpw == 4) || !proj_chain_supported(us, xn, B, H, L, pt)) return SF_ERR_UNSUPPORTED;
+    if ((ldvec & 3) || (ldh1 & 3) || !counter || !z || (ldz & 3) || ldz < H || (xn && !split_part)) return SF_ERR_UNSUPPORTED;
+    const TxtFoldArgs ta{ctx_q, ctx_o, mask, L, H, vec, ldvec, part, counter, z, ldz, alpha};
+    const VisArgs va = xn ? proj_vis_args(*xn, pt, h1, ldh1, nullptr, nullptr, 0, Dropout{}, 0) : VisArgs{};
+    const VisSplit sp{split_part, nullptr, g_trace};
+    const int nv = xn ? VSP_G * B : 0, nt = TXF_G * B, na = y.gx * y.gy;
+    const dim3 grid(nv + nt + na), block(SMALL_WAVES * 64);
+    const int rpw = (L + TXF_G * SMALL_WAVES - 1) / (TXF_G * SMALL_WAVES);
+#define SF_PPT(R)                                                                                                      \
+    do {                                                                                                               \
+        if (nv) SF_LAUNCH((pair_proj_textfold_kernel<R, true>), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx);  \
+        else SF_LAUNCH((pair_proj_textfold_kernel<R, false>), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx);    \
+    } while (0)
+    if (rpw <= 1) SF_PPT(1); else if (rpw <= 2) SF_PPT(2); else if (rpw <= 3) SF_PPT(3); else SF_PPT(5);
+#undef SF_PPT
+    return launch_status();
+}
+
+// launch (2): scoring + glue on projected candidate rows  ||  vphase 2: merge of launch (1)'s partials; 0: the whole
+// projected attention of step t + 1 (needs `counter`); `xn` null: the scoring alone
+int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt, const float* z, int ldz, const float* y, int ldy,
+                    const FGlue& g, const PanoSrc* xn, int vphase, const float* h1, int ldh1, float* alpha, float* out, int ldo,
+                    const Dropout& drop, int drop_col0, float* split_part, unsigned* counter, hipStream_t st) {
+    if (!proj_chain_supported(us, xn, B, H, L, pt) || (ldz & 3) || (ldy & 3) || (ldh1 & 3)) return SF_ERR_UNSUPPORTED;
+    if (xn && (!split_part || (ldo & 3) || (vphase != 0 && vphase != 2) || (vphase == 0 && !counter))) return SF_ERR_UNSUPPORTED;
+    const ProjScoreArgs a{us, pt.pa, pt.la, pt.ld, H, z, y, ldz, ldy};
+    const VisArgs va = xn ? proj_vis_args(*xn, pt, h1, ldh1, alpha, out, ldo, drop, drop_col0) : VisArgs{};
+    const VisSplit sp{split_part, counter, g_trace};
+    const dim3 block(SMALL_WAVES * 64);
+    if (xn && vphase == 0)
+        SF_LAUNCH((pair_proj_score_kernel<0>), dim3(VSP_G * B + B), block, 0, st, a, g, B, va, sp, VSP_G * B);
+    else
+        SF_LAUNCH((pair_proj_score_kernel<2>), dim3(xn ? 2 * B : B), block, 0, st, a, g, B, va, sp, 0);
     return launch_status();
 }
 

@@ -240,6 +240,23 @@ int pair_score_merge(const CandSrc& src, int B, int D, const float* r, const flo
 int pair_vis_apro(const PanoSrc* src, int B, const float* vec, int ldvec, float* split_part, const SmallPlan& b,
                   hipStream_t st);
 
+// the projected decode chain (sf_attention.hip): the tables of sf_projected_build as the kernels take them
+struct ProjTables {
+    const float *pv, *pa, *lv, *la;
+    int ld, H;
+};
+bool proj_chain_supported(const CandSrc& us, const PanoSrc* xn, int B, int H, int L, const ProjTables& pt);
+int visual_attn_proj(const CandSrc& us, const PanoSrc& x, int B, int H, int L, const ProjTables& pt, const float* h, int ldh,
+                     float* alpha, float* out, int ldo, const Dropout& drop, int drop_col0, float* split_part,
+                     unsigned* counter, hipStream_t st);
+int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* mask, int B, int L, int H, const float* vec,
+                       int ldvec, float* part, unsigned* counter, float* z, int ldz, float* alpha, const SmallPlan& y,
+                       const CandSrc& us, const PanoSrc* xn, const ProjTables& pt, const float* h1, int ldh1, float* split_part,
+                       hipStream_t st);
+int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt, const float* z, int ldz, const float* y, int ldy,
+                    const FGlue& g, const PanoSrc* xn, int vphase, const float* h1, int ldh1, float* alpha, float* out, int ldo,
+                    const Dropout& drop, int drop_col0, float* split_part, unsigned* counter, hipStream_t st);
+
 struct FGlue;
 int follower_glue_fwd(const FGlue& g, hipStream_t st);
 // scoring + glue in one launch (sf_attention.hip); g.logit receives the masked logits

@@ -104,6 +104,16 @@ def tsv_to_bin(tsv_path, bin_path, dtype='fp32'):
     return len(ids)
 
 
+def _forget_projected(addr, pv):
+    """Drops the library's projected-table entry of the table at `addr` -- when `pv` is given, only if it still is the
+    entry whose pv table lives there (a collected decoder must not unregister the tables of another one)."""
+    if pv is not None:
+        cur = _lib.Projected()
+        if not _lib.lib.sf_projected_registered(C.c_void_p(addr), C.byref(cur)) or cur.pv != pv:
+            return
+    _lib.lib.sf_projected_register(C.c_void_p(addr), None)
+
+
 class FeatureStore:
     """The feature table in HBM + viewpoint-id index.
 
@@ -144,6 +154,9 @@ class FeatureStore:
             call('sf_feature_table_f16', C.c_void_p(addr), 1 if self.dtype == 'fp16' else 0)
             if self.dtype == 'fp16':
                 weakref.finalize(self, _lib.lib.sf_feature_table_f16, C.c_void_p(addr), 0)
+            # ... and a projected-table entry of a collected store that lived at this address (`projected` below)
+            call('sf_projected_register', C.c_void_p(addr), None)
+        self._projected = weakref.WeakKeyDictionary()       # decoder module -> its projected tables (see `projected`)
         self.LOC = loc
         self.F = self.IMG + loc
         self.device = self.table.device
@@ -195,6 +208,63 @@ class FeatureStore:
     def rows_f32(self, idx):
         """table[idx] widened to fp32 (exact), on the table's device."""
         return self.table[idx].to(torch.float32)
+
+    # ---- projected tables (include/sf_hip.h: sf_projected_build) ---------------------------------
+    def projected(self, decoder, build=True):
+        """The projected feature tables of (this store, `decoder`): every table row carried through the decoder's folded
+        query / scoring matrices ONCE, so that an inference decode step needs two dependent launches behind the LSTM cell
+        instead of four (include/sf_hip.h).  A derived copy of the weights like `runtime.transposed` and
+        `model.decoder_fold`: cached here per decoder, rebuilt IN PLACE (same addresses: a captured hipGraph keeps pointing
+        at them) when the version counter of a weight they depend on changes, dropped when the store or the decoder is
+        collected.  Costs 2 * n * V * (H + 4) * 4 bytes (1.57 GB for the full R2R table) and about 13 ms on MI355X, which a
+        replayed rollout repays and a single one does not: `build=False` returns the tables only if they exist already
+        (refreshed), else None.  None for an fp16 store.  Also tells the library that THIS decoder's tables are the ones
+        of the table's address (it holds one entry per address)."""
+        from .model import decoder_fold, decoder_params          # (model imports this module)
+        from .runtime import weight_key, ws_args
+        if self.dtype != 'fp32' or not self.table.numel() or self.IMG % 4 or self.LOC % 16:
+            return None
+        hit = self._projected.get(decoder)
+        if hit is None and not build:
+            return None
+        params = decoder_params(decoder)
+        key = weight_key(*(params[i] for i in (4, 5, 6, 10, 11, 12, 13, 14, 15))) + \
+            (self.table.data_ptr(), self.table._version, self.loc_table.data_ptr())
+        if hit is None or hit['key'] != key:
+            H = decoder.hidden_size
+            if H % 4 or decoder.feature_size != self.F:
+                return None
+            ld, rows = int(_lib.lib.sf_projected_ld(H)), self.n * self.V
+            new = lambda r: torch.empty(r, ld, device=self.device, dtype=torch.float32)  # noqa: E731
+            bufs = hit['bufs'] if hit is not None and hit['bufs'][0].shape == (rows, ld) else \
+                (new(rows), new(rows), new(self.V * self.V), new(5))
+            fold = decoder_fold(decoder)                           # (itself rebuilt in place per weight version)
+            rc = _lib.lib.sf_projected_build(C.byref(fold), ptr(self.table), rows, ptr(self.loc_table), self.V, self.IMG,
+                                             self.LOC, H, *(ptr(b) for b in bufs), *ws_args(self.device))
+            if rc == _lib.SF_ERR_UNSUPPORTED and hit is None:      # (a shape the products do not take: no tables, no error)
+                return None
+            _lib.check(rc, 'sf_projected_build')
+            struct = _lib.Projected(*(b.data_ptr() for b in bufs), self.loc_table.data_ptr(), params[4].data_ptr(),
+                                    params[10].data_ptr(), H, ld, self.V, self.IMG, self.LOC, 0)
+            first = hit is None
+            hit = dict(key=key, bufs=bufs, struct=struct, builds=(0 if first else hit['builds']) + 1)
+            self._projected[decoder] = hit
+            if first:
+                addr = self.table.data_ptr()
+                weakref.finalize(decoder, _forget_projected, addr, bufs[0].data_ptr())
+                weakref.finalize(self, _forget_projected, addr, None)
+        call('sf_projected_register', C.c_void_p(self.table.data_ptr()), C.byref(hit['struct']))
+        return hit
+
+    def note_unprojected(self, decoder):
+        """An inference rollout of (this store, `decoder`) has just run WITHOUT projected tables under the 'auto' policy.
+        From then on 'auto' leaves the pair alone (`seen_unprojected`): a rollout captured later replays the bits of the
+        eager rollouts made before it, as it always did; `project = True` still builds."""
+        if decoder not in self._projected:
+            self._projected[decoder] = None
+
+    def seen_unprojected(self, decoder):
+        return decoder in self._projected and self._projected[decoder] is None
 
     # ---- pointer structs for the C ABI (tensors must stay alive while the call is enqueued) -----
     def pano(self, vp, view):

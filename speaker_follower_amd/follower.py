@@ -10,6 +10,7 @@
   Training: `engine.rollout(...).loss.backward()` runs BPTT through the C-ABI backward
   entry points, accumulating weight gradients in place.
 """
+import contextlib
 import ctypes as C
 import os
 from dataclasses import dataclass
@@ -222,6 +223,28 @@ class _RolloutLossFn(torch.autograd.Function):
         return (None, None) + (None,) * (len(ctx.needs_input_grad) - 2)
 
 
+PROJECT_MAX_B = 256         # largest batch of the projected decode chain (the split attention's limit, csrc/sf_kernels.h)
+
+
+class projected_pass:
+    """`with projected_pass(on):` -- whether the decode steps issued inside look the projected tables up
+    (sf_projected_use; process-wide like the gate product's switches).  Restores the switch on exit."""
+
+    def __init__(self, on):
+        self.on = int(bool(on))
+
+    def __enter__(self):
+        self.prev = int(_lib.lib.sf_projected_is_used())
+        if self.prev != self.on:
+            _lib.lib.sf_projected_use(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        if self.prev != self.on:
+            _lib.lib.sf_projected_use(self.prev)
+        return False
+
+
 class FollowerEngine:
     def __init__(self, encoder, decoder, store, group=None):
         self.encoder, self.decoder, self.store = encoder, decoder, store
@@ -266,6 +289,51 @@ class FollowerEngine:
         self.fused_env_step = True      # nav.DeviceNavBatch: the env step inside the scoring + glue launch
         self.fallbacks = 0              # rollouts re-issued on the per-step kernels after a persistent-launch fault (run)
         self._gate_weights = 'fp32'
+        self._project = 'auto'
+        self._capturing = False         # inside capture() / capture_sharded(): 'auto' builds the projected tables
+
+    # Whether inference rollouts score and attend on the PROJECTED feature tables of (store, decoder) -- two dependent
+    # launches per decode step behind the cell instead of four (include/sf_hip.h: sf_projected_build;
+    # features.FeatureStore.projected).  The tables cost 1.57 GB for the full R2R table and about 13 ms to build, so:
+    #   'auto' (default)  capture() / capture_sharded() build them (a captured rollout is replayed many times); an eager
+    #                     rollout() USES tables that exist already for its (store, decoder) -- it then launches the kernels
+    #                     a replay does -- but never builds them.  One exception keeps "a replay equals the eager rollout"
+    #                     true in both orders: once a pair has run an inference rollout unprojected, a later capture()
+    #                     leaves it unprojected too (FeatureStore.note_unprojected) -- for the life of the pair, and only
+    #                     `state.projected` shows it.  Capture first, or set True, to get the two-launch chain
+    #   True              built on first use, by an eager rollout too
+    #   False             never used
+    # Only a rollout that takes the folded text stage can be projected (inference, index-form fp32 store, B <= 256, not a
+    # device-resident environment); every other one runs the chain it always ran.  `state.projected` says which ran.
+    # The switch reaches the library as a PROCESS-WIDE flag set around the episode call (projected_pass), and
+    # `state.projected` is read off a process-wide step counter: engines that issue rollouts concurrently from several host
+    # threads must agree on `project` (the library's other switches -- gate_weights_pass -- have the same limit).
+    @property
+    def project(self):
+        return self._project
+
+    @project.setter
+    def project(self, mode):
+        if not (mode is True or mode is False or mode == 'auto'):
+            raise ValueError("project must be 'auto', True or False, not %r" % (mode,))
+        self._project = mode
+
+    def _projected_tables(self, B, build=None, T=1, A=1):
+        """The (store, decoder) tables this engine's policy lets a rollout of batch B (context width T, A candidate slots)
+        use now, or None.  Nothing is built -- and the pair is not marked -- for a shape or a store the chain declines."""
+        store = self.store
+        if self._project is False or B > PROJECT_MAX_B or store.dtype != 'fp32':
+            return None
+        if not _lib.lib.sf_projected_supported(B, self.decoder.hidden_size, T, A, store.V, store.IMG, store.LOC):
+            return None
+        if build is None:
+            # 'auto' builds inside capture() -- unless this (store, decoder) has already handed out unprojected inference
+            # results in this process: the replay then stays, bit for bit, the eager rollout made before the capture
+            build = self._project is True or (self._capturing and not self.store.seen_unprojected(self.decoder))
+        hit = self.store.projected(self.decoder, build=build)
+        if hit is None and self._project == 'auto' and not self._capturing:
+            self.store.note_unprojected(self.decoder)
+        return hit
 
     # How the decoder LSTM's weights are stored for the gate product of INFERENCE passes: 'fp32' (default) or 'bf16'
     # (include/sf_hip.h: sf_gate_product_bf16_weights -- the product of the unrounded activations with the weights rounded
@@ -403,6 +471,7 @@ class FollowerEngine:
             batch.advance(-1)                           # slot 0 = the initial observation
         pipelined = self.pipelined and not on_device_env
         st.episode = None
+        st.projected, st.projected_tables = False, None
         # the same one-call episode for a device-resident environment (the env step inside every scoring + glue launch,
         # the attention of step t + 1 behind it): no host work between the launches of a TRAINING rollout either, and
         # the backward takes the two-stream episode path
@@ -452,7 +521,13 @@ class FollowerEngine:
                     # version): three dependent launches behind the cell instead of four
                     st.chain_fold = decoder_fold(dec)
                     ep.chain_fold = C.cast(C.pointer(st.chain_fold), C.c_void_p)
-            call('sf_follower_episode_fwd', byref(dw), byref(ep), *ws)
+            # ... on the projected tables of (store, decoder) where the policy has them (`project` above): the library
+            # takes the two-launch chain for every step it applies to and says how many it issued
+            st.projected_tables = self._projected_tables(B, T=T, A=A) if (st.text_folded and not nav_episode) else None
+            with projected_pass(st.projected_tables is not None):
+                before = _lib.lib.sf_projected_steps()
+                call('sf_follower_episode_fwd', byref(dw), byref(ep), *ws)
+                st.projected = _lib.lib.sf_projected_steps() > before
             st.episode = (ep, dw)
         tapes = [] if st.episode else [_lib.DecoderTape(*(st.tape[k][t].data_ptr() for k in _TAPE_KEYS))
                                        for t in range(S)]
@@ -567,7 +642,7 @@ class FollowerEngine:
             st.loss = st.loss_buf.reshape(())
         return st
 
-    def _baked_pointers(self, gate_weights='fp32'):
+    def _baked_pointers(self, gate_weights='fp32', projected=False):
         """Every weight-side device pointer a captured rollout bakes into its hipGraph: the parameters
         and their derived copies (transposed layouts, the encoder's [vocab,4H] table, with
         gate_weights = 'bf16' the packed images of the decoder LSTM's weights).  Building the
@@ -585,17 +660,31 @@ class FollowerEngine:
         if gate_weights == 'bf16':
             lstm = self.decoder.lstm
             packed = repr(tuple(t.data_ptr() for t in register_bf16_weights(lstm.weight_ih, lstm.weight_hh))).encode()
-        return ew + bytes(dw) + fold + packed
+        tables = b''
+        if projected:
+            # (refreshed in place here when a weight they depend on changed; re-allocated or gone: the bytes differ)
+            hit = self.store.projected(self.decoder, build=False)
+            tables = b'projected' + (bytes(hit['struct']) if hit is not None else b'')
+        return ew + bytes(dw) + fold + packed + tables
 
-    def _guarded(self, graph_replay):
+    @contextlib.contextmanager
+    def _capture_policy(self):
+        """What `project = 'auto'` means inside capture(): the rollouts issued here build the projected tables."""
+        prev, self._capturing = self._capturing, True
+        try:
+            yield
+        finally:
+            self._capturing = prev
+
+    def _guarded(self, graph_replay, projected=False):
         mode = self._gate_weights          # (the captured rollouts ran train=False under no_grad: this mode, for good)
-        baked = self._baked_pointers(mode)
+        baked = self._baked_pointers(mode, projected)
 
         def replay():
             # weights updated since capture (optimizer.step, load_state_dict)?  Their derived copies are
             # rebuilt in place here, ahead of the replay on the same stream, so the graph reads current
             # data everywhere.  A MOVED tensor cannot be patched into the graph: refuse.
-            if self._baked_pointers(mode) != baked:
+            if self._baked_pointers(mode, projected) != baked:
                 raise WeightsMoved('a weight (or one of its cached layouts) moved since this rollout was '
                                    'captured; capture() again')
             graph_replay()
@@ -617,8 +706,8 @@ class FollowerEngine:
         # frozen in a graph): every replay draws new actions (sf_follower_glue.sample_site_dev)
         sampled = feedback == 'sample'
         ctl = torch.zeros(4, dtype=torch.int32, device=self.store.device) if sampled else None
-        with torch.no_grad():
-            self.rollout(batch, steps, feedback, train=False)          # warm-up: allocations, caches
+        with torch.no_grad(), self._capture_policy():
+            self.rollout(batch, steps, feedback, train=False)          # warm-up: allocations, caches, projected tables
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             side = torch.cuda.Stream()
@@ -646,7 +735,7 @@ class FollowerEngine:
                 self.site_next += st.site_stride
                 self.iteration += 1
             graph.replay()
-        return self._guarded(graph_replay), st
+        return self._guarded(graph_replay, st.projected), st
 
     def capture_training(self, batch, steps, feedback='sample', optimizers=(), zero=None):
         """hipGraph of ONE WHOLE TRAINING ITERATION (follower.py:1001-1020 + train.py:263-268): zero the gradients,
@@ -721,7 +810,7 @@ class FollowerEngine:
         dev = self.store.device
         streams = [torch.cuda.Stream() for _ in shards]
         graphs, states = [], []
-        with torch.no_grad():
+        with torch.no_grad(), self._capture_policy():
             for sh, s in zip(shards, streams):
                 s.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(s):
@@ -749,7 +838,7 @@ class FollowerEngine:
                 call('sf_add_f32', ptr(total), ptr(st.sum_cnt), total.numel(), stream())
             call('sf_loss_finalize', ptr(total), steps, ptr(loss_buf), ptr(gscale), stream())
 
-        return self._guarded(replay_all), states, loss_buf
+        return self._guarded(replay_all, any(st.projected for st in states)), states, loss_buf
 
     # ------------------------------------------------------------------------------ backward
     def _backward(self, st, dloss):
