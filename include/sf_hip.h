@@ -1012,9 +1012,10 @@ int sf_feature_table_is_f16(const void* table);
  *     la [5, ld]        rows 0..3: [sum_{j in block g} M_a[IMG + j, :] | sum_{j in block g} c_a[IMG + j]] for the four
  *                       sin/cos groups of a candidate's location part (each value repeated LOC/4 times, contiguous);
  *                       row 4: [m | c0], the constant row of the scoring fold (m_a row F, c_a[F])
- * A decode step then needs TWO dependent launches behind the LSTM cell instead of four: (1) folded text attention || y;
- * (2) scoring + glue on pa / la with h~ formed in the body || the attention of step t + 1 scored from pv / lv and h1
- * (sf_debug_projected_partials_late below moves its partials into (1)).  Step 0's attention is one launch from h_init.
+ * A decode step then needs TWO dependent launches behind the LSTM cell instead of four: (1) folded text attention || y
+ * || the attention partials of step t + 1 scored from pv / lv and h1; (2) scoring + glue on pa / la with h~ formed in the
+ * body || the merge of the partials (sf_debug_projected_partials_late below moves the partials into (2)).  Step 0's
+ * attention is one launch from h_init.
  * The products q, t_v', t_a, wt and r are not issued and their tape slots are NOT written.
  *
  * MEMORY AND COST: pv and pa take n_rows * ld * 4 bytes each -- 0.79 GB each (1.57 GB together) for the 10 567 viewpoints
@@ -1069,10 +1070,19 @@ int sf_projected_supported(int B, int H, int L, int A, int V, int IMG, int LOC);
 /* Test switch: table rows per product of sf_projected_build (default 16 384; rows <= 0 restores it), so that a build of
  * several chunks -- the 64-bit row offsets between them -- can be checked on a small table. */
 void sf_debug_projected_chunk_rows(int rows);
-/* A/B switch of the projected chain: on != 0 (the default: measured faster) puts the attention partials of step
- * t + 1 into launch (2) (partials, ticket and merge beside the scoring; launch (1) is the text stage and y alone); 0 puts
- * them into launch (1) and leaves launch (2) their merge. */
+/* A/B switch of the projected chain: 0 (the default: measured faster, 1.429 against 1.474 ms per headline rollout)
+ * puts the attention partials of step t + 1 into launch (1), beside the text stage, and leaves launch (2) their merge;
+ * on != 0 puts them into launch (2) (partials, ticket and merge beside the scoring; launch (1) is the text stage and y
+ * alone).  A panorama with ceil(IMG / 256) + ceil(LOC / 256) > 9 takes the second placement whatever the switch says. */
 void sf_debug_projected_partials_late(int on);
+/* Test entry: the attention of the projected chain's launches (1) and (2) alone, on caller buffers -- the same two kernels
+ * with empty text, product and scoring parts, so that panorama shapes no engine is built for (V below 36, tiny rows, small
+ * H) reach them.  X: index-form fp32 panorama (V in 19..36); pv [n_vp * V, ld], lv [V * V, ld] as sf_projected_build
+ * lays them out (ld % 4 == 0, ld >= H + 1); h1 [B, ldh1]; alpha [B, V]; out [B, ldo], the weighted row sum, no dropout.
+ * late == 0: partials in launch (1), merge in launch (2); else partials, ticket and merge in launch (2). */
+int sf_debug_projected_attention(const sf_pano* X, int B, int H, const float* pv, const float* lv, int ld, const float* h1,
+                                 int ldh1, float* alpha, float* out, int ldo, int late, void* ws, size_t ws_bytes,
+                                 sf_stream stream);
 /* Older name of the same switch (tools/, A/B timing): on != 0 runs the large LSTM gate products (K >= 2048, M <= 128: sf_lstm_cell_fwd, the decode
  * step) on the fp32 MFMA (v_mfma_f32_16x16x4_f32, rounds 1-3) instead of the bf16 matrix cores with three-way
  * error-free operand splitting (csrc/sf_gemm.hip: gemm_nt_split_kernel; same fp32 accuracy class, measured closer

@@ -108,7 +108,7 @@ int g_proj_n = 0;
 std::mutex g_proj_mutex;
 std::atomic<int> g_proj_use{1};             // sf_projected_use
 std::atomic<long long> g_proj_steps{0};     // sf_projected_steps: decode steps issued on the projected chain
-static int g_proj_partials_late = 1;        // sf_debug_projected_partials_late (0: the attention partials in launch (1))
+static int g_proj_partials_late = 0;        // sf_debug_projected_partials_late (0: the attention partials in launch (1))
 bool projected_lookup(const void* table, sf_projected* out) {
     if (!table || !g_proj_use.load(std::memory_order_relaxed)) return false;
     std::lock_guard<std::mutex> lock(g_proj_mutex);
@@ -647,6 +647,18 @@ void sf_projected_use(int on) { g_proj_use.store(on ? 1 : 0, std::memory_order_r
 int sf_projected_is_used(void) { return g_proj_use.load(std::memory_order_relaxed); }
 long long sf_projected_steps(void) { return g_proj_steps.load(std::memory_order_relaxed); }
 void sf_debug_projected_partials_late(int on) { g_proj_partials_late = on; }
+int sf_debug_projected_attention(const sf_pano* X, int B, int H, const float* pv, const float* lv, int ld, const float* h1,
+                                 int ldh1, float* alpha, float* out, int ldo, int late, void* ws, size_t ws_bytes,
+                                 sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(X && pv && lv && h1 && alpha && out && B > 0 && H > 0);
+    const PanoSrc x = pano(X);
+    Arena ar = arena(ws, ws_bytes);
+    float* part = ar.take(visual_attn_split_floats(B, x.IMG + x.LOC));
+    if (!part || !ar.tickets()) return SF_ERR_WORKSPACE;
+    return proj_attention_alone(x, B, ProjTables{pv, nullptr, lv, nullptr, ld, H}, h1, ldh1, alpha, out, ldo, late, part,
+                                ar.tickets(), S(stream));
+}
 // rows of the feature table one product of the build takes (its output, the largest thing in flight, is 34 MB)
 constexpr long long PROJ_CHUNK_ROWS = 16384;
 static long long g_proj_chunk_rows = PROJ_CHUNK_ROWS;      // sf_debug_projected_chunk_rows
@@ -1019,10 +1031,14 @@ static int fold_score(const TailStep& s, float* merge_part, const float* r, int 
 //   (1) folded text attention  ||  y = W_out[:, H:] h1  ||  attention partials of step t+1, scores from projected rows and h1
 //   (2) scoring + glue on projected candidate rows, h~ = tanh(z + y) formed in the body  ||  merge of the partials
 // q, t_v', t_a, wt and r are never formed (and their tape slots not written: nothing runs backward through this step).
-// PLACEMENT of the partials (sf_debug_projected_partials_late, default 1): in (2) -- partials, ticket and merge beside the
-// scoring (pair_proj_score_kernel<0>), (1) the text stage and y alone -- because the attention body's ~190 registers per
-// lane hold every block of the grid it is compiled into to one workgroup per CU: measured at B = 100, (1) with the
-// partials 23.2 us + (2) 7.2 us against 10.2 us + 17.9 us with them in (2) (1.523 against 1.480 ms per rollout).
+// PLACEMENT of the partials (sf_debug_projected_partials_late, default 0): in (1), beside the text stage.  They need only
+// h1, not the text attention or the chosen action, so there they leave the chain cell -> text -> score -> next gate
+// product; (2) keeps their merge.  Their body (sf_attention.hip: proj_partials_body) fits 128 registers per lane, so the
+// grid of (1) runs two 512-thread workgroups per CU: measured at B = 100, (1) 18.7 us + (2) 7.4 us against 10.3 us +
+// 18.0 us with partials, ticket and merge in (2) (pair_proj_score_kernel<0>), 1.429 against 1.474 ms per rollout
+// (profiles/partials_early_ab.txt).  With visual_split_body's ~190 registers in (1) -- one workgroup per CU for every block
+// of that grid -- it was 23.6 us + 7.3 us and the late placement won.  A panorama whose row layout the body does not take
+// (proj_partials_supported) keeps the late placement.
 // the registered tables of (candidate table, decoder) where the chain's shapes hold for them (xn: the panorama whose
 // attention rides along, or null)
 static bool projected_for(const sf_decoder_w* w, const CandSrc& us, const PanoSrc* xn, int B, int H, int L, ProjTables* pt) {
@@ -1051,7 +1067,7 @@ static int tail_proj(const TailStep& s, const TextFold& tf) {
         py.mt == 1 && py.cpw == 4 && (!s.paired || af.tickets());
     if (!ok) return SF_ERR_UNSUPPORTED;
     // ---- issue (the first launch checks its shapes before it launches: it may still decline)
-    const bool late = s.paired && g_proj_partials_late;
+    const bool late = s.paired && (g_proj_partials_late || !proj_partials_supported(s.xn));
     TRY(pair_proj_textfold(tf.ctx_q, tf.ctx_o, s.ctx_mask, B, s.L, H, tp->cat2 + H, 2 * H, f.tpart, f.tcount, f.zbuf, f.ldp,
                            tp->alpha, py, s.us, s.paired && !late ? &s.xn : nullptr, pt, tp->h1, H, f.part, s.st));
     g_proj_steps.fetch_add(1, std::memory_order_relaxed);

@@ -458,6 +458,201 @@ __global__ __launch_bounds__(VSP_NW * 64) void visual_attn_split_f64_kernel(VisA
     visual_split_body<0, true, H16>(a, sp, blockIdx.x, blockIdx.y);
 }
 
+// -------------------------------------------------------------------------------------------------
+// The partials of the projected decode chain as a body of their own (launch (1), pair_proj_textfold_kernel<R, true>;
+// merged by proj_merge_body in launch (2)).  visual_split_body<1, .., PROJ> keeps three rows, their accumulators and the
+// projected rows of three views per wave: ~190 registers per lane, one 512-thread workgroup per CU for EVERY block of the
+// grid it is compiled into.  This body fits 128 registers, so a CU holds two workgroups and the text groups of the same
+// grid fill the slots the attention blocks leave:
+//   - a row wave owns TWO rows (72 registers of row data) and forms the weighted sum in the first row's registers;
+//   - it never holds a projected row: the block's other two waves (which visual_split_body sends home at once) form the
+//     group's scores from the projected rows while the feature rows are on their way;
+//   - a lane's nine chunks of a row are TYPED per slot, not per lane: slots [0, NI) are image chunks lane + 64 i, the
+//     rest location chunks lane + 64 (i - NI).  Row and table are wave-uniform, so every load is a scalar base plus one
+//     32-bit lane offset (the per-lane select between two 64-bit addresses of pano_load cost ~40 registers here and the
+//     compiler then made the loads wait for one another).  Needs ceil(I4 / 64) + ceil(L4 / 64) <= VIS_CPL
+//     (proj_partials_supported; the launcher declines otherwise and the partials ride in launch (2)).
+// Nothing is masked on the way in: indices are clamped, a slot position past its part is never emitted, a view past V
+// has weight e = 0 (feature values are finite), a padded sample's weights are zeroed for the sum alone.
+// A sample is PPB_G = 3 groups of 12 views (V <= 36); the record of a group is laid out as visual_split_body's
+// (P | scores | m, l), a group beyond V is (0 | -inf.. | -inf, 0) and merges to weight 0.  Plain stores: the kernel
+// boundary is the hand-off, there is no ticket, so the group count need be no power of two.  No trace stamps
+// (sf_debug_trace buffers are sized for VSP_G blocks per sample).
+// -------------------------------------------------------------------------------------------------
+constexpr int PPB_G = 3, PPB_NW = 6, PPB_RPW = 2, PPB_RPG = PPB_NW * PPB_RPW, PPB_SLOTS = 3;
+constexpr int PPB_SW = SMALL_WAVES - PPB_NW, PPB_SPW = PPB_RPG / PPB_SW;   // score waves, views scored per score wave
+static_assert(PPB_G * PPB_RPG >= VSP_G * VSP_RPG, "covers every V the split attention takes");
+static_assert(PPB_RPG <= 32, "a group's scores live in 32 record slots");
+static_assert(PPB_SW >= 1 && PPB_SW * PPB_SPW == PPB_RPG, "the score waves share a group's views evenly");
+constexpr int SPLIT_MAX_G = PPB_G > VSP_G ? PPB_G : VSP_G;      // records per sample the scratch is sized for
+
+// Every thread of a SMALL_WAVES * 64 block must call this (it synchronises).
+__device__ __forceinline__ void proj_partials_body(const VisArgs& a, const VisSplit& sp, int g, int b) {
+    __shared__ float4 slots[PPB_SLOTS][VIS_CPL * 64];
+    __shared__ float s_score[PPB_RPG];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // (uniform to the compiler too: scalar row addresses)
+    const int V = a.src.V, I4 = a.src.IMG >> 2, L4 = a.src.LOC >> 2;
+    const int F = a.src.IMG + a.src.LOC;
+    const int NI = (I4 + 63) >> 6;
+    float* rec = sp.part + ((size_t)b * PPB_G + g) * (F + 64);
+    const int vp = a.src.vp[b], view = a.src.view[b];
+    const bool zero = vp < 0;                                      // padded sample: all-zero panorama
+
+    float4 x[PPB_RPW][VIS_CPL];
+    if (wave < PPB_NW) {
+        // ---- row waves: every load of both rows in flight at once
+        const float4* img = reinterpret_cast<const float4*>(a.src.table) + (size_t)max(vp, 0) * V * I4;
+        const float4* loc = reinterpret_cast<const float4*>(a.src.loc_table) + (size_t)view * V * L4;
+#pragma unroll
+        for (int r = 0; r < PPB_RPW; ++r) {
+            const int v = min(g * PPB_RPG + wave * PPB_RPW + r, V - 1);
+            const float4* ri = img + (size_t)v * I4;
+            const float4* rl = L4 ? loc + (size_t)v * L4 : ri;     // (no location part: those slots are never emitted)
+            const int nl = L4 ? L4 : I4;
+#pragma unroll
+            for (int i = 0; i < VIS_CPL; ++i) {
+                const bool im = i < NI;
+                const float4* base = im ? ri : rl;
+                const int at = min(lane + 64 * (im ? i : i - NI), (im ? I4 : nl) - 1);
+                x[r][i] = base[at];
+            }
+        }
+    } else {
+        // ---- score waves: score_v = (PV[row_v][:H] + LV[view * V + v][:H]) . h1 + PV[row_v][H] + LV[..][H]
+        const int n4h = a.pH >> 2;
+        const size_t r_img = (size_t)max(vp, 0) * V, r_loc = (size_t)view * V;
+        float4 hv[PRJ_CPL], pj[PPB_SPW][PRJ_CPL], lj[PPB_SPW][PRJ_CPL];
+        // (the constants at column H: lane r fetches view r's, one load per table instead of a register per view)
+        const int vc = min(g * PPB_RPG + (wave - PPB_NW) * PPB_SPW + min(lane, PPB_SPW - 1), V - 1);
+        const float cst = a.pv[(r_img + vc) * (size_t)a.ldp + a.pH] + a.lv[(r_loc + vc) * (size_t)a.ldp + a.pH];
+#pragma unroll
+        for (int i = 0; i < PRJ_CPL; ++i)
+            hv[i] = reinterpret_cast<const float4*>(a.vec + (size_t)b * a.ldvec)[min(lane + 64 * i, n4h - 1)];
+#pragma unroll
+        for (int r = 0; r < PPB_SPW; ++r) {
+            const int v = min(g * PPB_RPG + (wave - PPB_NW) * PPB_SPW + r, V - 1);
+            const float* pr = a.pv + (r_img + v) * (size_t)a.ldp;
+            const float* lr = a.lv + (r_loc + v) * (size_t)a.ldp;
+#pragma unroll
+            for (int i = 0; i < PRJ_CPL; ++i) {
+                const int cc = min(lane + 64 * i, n4h - 1);
+                pj[r][i] = reinterpret_cast<const float4*>(pr)[cc];
+                lj[r][i] = reinterpret_cast<const float4*>(lr)[cc];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < PPB_SPW; ++r) {
+            float d = 0.f;
+#pragma unroll
+            for (int i = 0; i < PRJ_CPL; ++i) {
+                float4 t = pj[r][i];
+                f4add(t, lj[r][i]);
+                d += (lane + 64 * i < n4h ? 1.f : 0.f) * dot4(t, hv[i]);      // (clamped lanes beyond H count for nothing)
+            }
+            // (an all-zero panorama scores 0 everywhere -- blended, not branched on: the loads above stay unconditional)
+            const float sw = (zero ? 0.f : 1.f) * (wave_sum(d) + __shfl(cst, r, WAVE));
+            const int vl = (wave - PPB_NW) * PPB_SPW + r;
+            if (lane == 0) s_score[vl] = (g * PPB_RPG + vl < V) ? sw : -INFINITY;
+        }
+    }
+    __syncthreads();
+    const float s = lane < PPB_RPG ? s_score[lane] : -INFINITY;
+    const float m = wave_max(s);                                   // -inf: the group lies beyond V
+    const float e = s > -INFINITY ? expf(s - m) : 0.f;
+    const float l = wave_sum(e);
+
+    // the weighted sum in place: p = e0 x0 takes the first row's registers, the second row is folded into them
+    float4 p[VIS_CPL];
+    if (wave < PPB_NW) {
+        const float ew = zero ? 0.f : e;
+        const float e0 = __shfl(ew, wave * PPB_RPW, WAVE);
+#pragma unroll
+        for (int i = 0; i < VIS_CPL; ++i)
+            p[i] = make_float4(e0 * x[0][i].x, e0 * x[0][i].y, e0 * x[0][i].z, e0 * x[0][i].w);
+#pragma unroll
+        for (int r = 1; r < PPB_RPW; ++r) {
+            const float er = __shfl(ew, wave * PPB_RPW + r, WAVE);
+#pragma unroll
+            for (int i = 0; i < VIS_CPL; ++i) f4fma(p[i], er, x[r][i]);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < VIS_CPL; ++i) p[i] = f4zero();
+    }
+    // (slot position k = lane + 64 i of the sum is chunk k of the image part, or chunk k - 64 NI of the location part)
+    block_row_sum<VIS_CPL, SMALL_WAVES, PPB_SLOTS>(p, slots, VIS_CPL * 64, [&](int k, float4 t) {
+        const bool im = k < 64 * NI;
+        const int c = im ? k : k - 64 * NI;
+        if (c < (im ? I4 : L4)) reinterpret_cast<float4*>(rec)[im ? c : I4 + c] = t;
+    });
+    if (wave == 0) {
+        if (lane < 32) rec[F + lane] = s;
+        if (lane == 0) {
+            rec[F + 32] = m;
+            rec[F + 33] = l;
+        }
+    }
+}
+
+// The merge of proj_partials_body's G records per sample (RPG views each) into alpha [V] and the normalised weighted sum:
+// visual_split_body<2> on another record count.  Plain loads (the records come from the launch before); no barrier, so
+// every thread of the block takes part.
+template <int G, int RPG>
+__device__ __forceinline__ void proj_merge_body(const VisArgs& a, const VisSplit& sp, int b) {
+    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+    const int tid = threadIdx.x;
+    const int V = a.src.V;
+    const int F = a.src.IMG + a.src.LOC, n4 = F >> 2;
+    const int pstride = F + 64;
+    float* r0 = sp.part + (size_t)b * G * pstride;
+    float mg[G], kk[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) mg[k] = r0[(size_t)k * pstride + F + 32];
+    float M = mg[0];                                             // (group 0 is never empty)
+#pragma unroll
+    for (int k = 1; k < G; ++k) M = fmaxf(M, mg[k]);
+    float L = 0.f;                                               // m = -inf (empty group): weight 0, l = 0
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+        kk[k] = expf(mg[k] - M);
+        L += r0[(size_t)k * pstride + F + 33] * kk[k];
+    }
+    const float inv = 1.0f / L;
+    if (tid < V) {
+        const int gk = tid / RPG;
+        const float sc = r0[(size_t)gk * pstride + F + (tid - gk * RPG)];
+        a.alpha[(size_t)b * V + tid] = expf(sc - M) * inv;
+    }
+#pragma unroll
+    for (int k = 0; k < G; ++k) kk[k] *= inv;
+    float* orow = a.out + (size_t)b * a.ldo;
+    const Dropout dr = a.drop;
+    const uint32_t rkey = drop_key(dr, (uint32_t)(dr.row0 + b));
+    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(r0, 0, G * pstride * 4, 0x00020000);
+    for (int c = tid; c < n4; c += SMALL_WAVES * 64) {
+        v4u pk[G];
+#pragma unroll
+        for (int k = 0; k < G; ++k) pk[k] = __builtin_amdgcn_raw_buffer_load_b128(rs0, k * pstride * 4 + c * 16, 0, 0);
+        float4 t = f4zero();
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+            t.x += kk[k] * __uint_as_float(pk[k].x);
+            t.y += kk[k] * __uint_as_float(pk[k].y);
+            t.z += kk[k] * __uint_as_float(pk[k].z);
+            t.w += kk[k] * __uint_as_float(pk[k].w);
+        }
+        if (dr.on()) {
+            const uint32_t col = (uint32_t)(a.drop_col0 + 4 * c);
+            t.x = dropout_keep(rkey, col + 0, dr.thresh) ? t.x * dr.scale : 0.f;
+            t.y = dropout_keep(rkey, col + 1, dr.thresh) ? t.y * dr.scale : 0.f;
+            t.z = dropout_keep(rkey, col + 2, dr.thresh) ? t.z * dr.scale : 0.f;
+            t.w = dropout_keep(rkey, col + 3, dr.thresh) ? t.w * dr.scale : 0.f;
+        }
+        reinterpret_cast<float4*>(orow)[c] = t;
+    }
+}
+
 // =================================================================================================
 // Text / path-context attention core (model.py:129-139): L rows of H floats, CPL = 2 (H <= 512).
 // forward : s_l = ctx_l . t (masked -> -inf), alpha = softmax, wc = sum alpha_l ctx_l
@@ -963,7 +1158,7 @@ __device__ __forceinline__ void proj_score_glue_body(const ProjScoreArgs& a, con
 }
 
 // launch (2) of the projected chain: scoring + glue beside the attention of step t + 1 --
-//   VPHASE 2: the merge of the partials launch (1) left (the default placement);
+//   VPHASE 2: the merge of the PPB_G records per sample launch (1) left (proj_partials_body; the default placement);
 //   VPHASE 0: partials, ticket and merge here (sf_debug_projected_partials_late: launch (1) is the text stage alone)
 template <int VPHASE>
 __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_proj_score_kernel(ProjScoreArgs a, FGlue g, int nb, VisArgs v, VisSplit sp,
@@ -975,8 +1170,7 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_proj_score_kernel(ProjS
         visual_split_body<0, false, false, true>(v, sp, bid % VSP_G, bid / VSP_G);
     } else {
         if (bid < nb) return proj_score_glue_body(a, g, bid);
-        if (threadIdx.x >= VSP_NW * 64) return;
-        visual_split_body<2>(v, sp, 0, bid - nb);
+        proj_merge_body<PPB_G, PPB_RPG>(v, sp, bid - nb);
     }
 }
 
@@ -1178,16 +1372,15 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_textfold_small_wide_ker
 }
 
 // launch (1) of the projected chain: [projected attention partials of step t + 1 | text_fold groups | y = W_out[:, H:] h1]
-// (the partials blocks pull the most bytes: first in the grid).  VIS false: the instantiation without the partials body
-// (nv == 0: an episode's last step, or the partials ride in launch (2)) -- the attention body's ~190 registers per lane
-// would otherwise hold every text block of the grid to one workgroup per CU.
+// (the partials blocks pull the most bytes: first in the grid; proj_partials_body keeps the kernel within 128 registers,
+// two workgroups per CU).  VIS false: the instantiation without the partials body (nv == 0: an episode's last step, or
+// the partials ride in launch (2)) -- the text groups alone need far fewer registers and run three or more to a CU.
 template <int RPW, bool VIS>
 __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_proj_textfold_kernel(VisArgs v, VisSplit sp, int nv, TxtFoldArgs t, int nt,
                                                                             SmallArgs a, int gxa) {
     const int bid = blockIdx.x;
     if (VIS && bid < nv) {
-        if (threadIdx.x >= VSP_NW * 64) return;
-        visual_split_body<1, false, false, true>(v, sp, bid % VSP_G, bid / VSP_G);
+        proj_partials_body(v, sp, bid % PPB_G, bid / PPB_G);
     } else if (bid < nv + nt) {
         text_fold_body<RPW>(t, (bid - nv) % TXF_G, (bid - nv) / TXF_G);
     } else {
@@ -1288,7 +1481,9 @@ __global__ __launch_bounds__(VIS_NW * 64) void pair_visbwd_small_kernel(VisArgs 
 template <typename Src>
 static inline bool half_misuse(const Src& s) { return s.half && s.dense; }
 
-size_t visual_attn_split_floats(int B, int F) { return (size_t)B * VSP_G * (F + 64); }
+// (sized for the body with the most records per sample: proj_partials_body and proj_merge_body index the same scratch
+//  with PPB_G records, every visual_split_body with VSP_G)
+size_t visual_attn_split_floats(int B, int F) { return (size_t)B * SPLIT_MAX_G * (F + 64); }
 
 bool visual_attn_f64_supported(const PanoSrc& src, int B) {
     const int F = src.IMG + src.LOC;
@@ -1609,6 +1804,11 @@ bool proj_chain_supported(const CandSrc& us, const PanoSrc* xn, int B, int H, in
     return true;
 }
 
+// proj_partials_body types a lane's VIS_CPL row slots as image or location chunks: both parts must fit side by side
+bool proj_partials_supported(const PanoSrc& xn) {
+    return xn.IMG >= 4 && ((xn.IMG >> 2) + 63) / 64 + ((xn.LOC >> 2) + 63) / 64 <= VIS_CPL;
+}
+
 static VisArgs proj_vis_args(const PanoSrc& xn, const ProjTables& pt, const float* h1, int ldh1, float* alpha, float* out,
                              int ldo, const Dropout& drop, int drop_col0) {
     VisArgs va{xn, h1, ldh1, alpha, out, ldo, drop, drop_col0};
@@ -1633,10 +1833,11 @@ int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* ma
                        hipStream_t st) {
     if (!(y.mt == 1 && y.cpw == 4) || !proj_chain_supported(us, xn, B, H, L, pt)) return SF_ERR_UNSUPPORTED;
     if ((ldvec & 3) || (ldh1 & 3) || !counter || !z || (ldz & 3) || ldz < H || (xn && !split_part)) return SF_ERR_UNSUPPORTED;
+    if (xn && !proj_partials_supported(*xn)) return SF_ERR_UNSUPPORTED;
     const TxtFoldArgs ta{ctx_q, ctx_o, mask, L, H, vec, ldvec, part, counter, z, ldz, alpha};
     const VisArgs va = xn ? proj_vis_args(*xn, pt, h1, ldh1, nullptr, nullptr, 0, Dropout{}, 0) : VisArgs{};
     const VisSplit sp{split_part, nullptr, g_trace};
-    const int nv = xn ? VSP_G * B : 0, nt = TXF_G * B, na = y.gx * y.gy;
+    const int nv = xn ? PPB_G * B : 0, nt = TXF_G * B, na = y.gx * y.gy;
     const dim3 grid(nv + nt + na), block(SMALL_WAVES * 64);
     const int rpw = (L + TXF_G * SMALL_WAVES - 1) / (TXF_G * SMALL_WAVES);
 #define SF_PPT(R)                                                                                                      \
@@ -1664,6 +1865,32 @@ int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt
         SF_LAUNCH((pair_proj_score_kernel<0>), dim3(VSP_G * B + B), block, 0, st, a, g, B, va, sp, VSP_G * B);
     else
         SF_LAUNCH((pair_proj_score_kernel<2>), dim3(xn ? 2 * B : B), block, 0, st, a, g, B, va, sp, 0);
+    return launch_status();
+}
+
+// The attention of launches (1) and (2) ALONE, on caller buffers (sf_debug_projected_attention: tests at panorama shapes
+// an engine cannot be built for): the same two kernels with empty text, product and scoring parts -- late == 0 the
+// partials in launch (1) and their merge in launch (2), else partials, ticket and merge in launch (2).
+int proj_attention_alone(const PanoSrc& x, int B, const ProjTables& pt, const float* h1, int ldh1, float* alpha, float* out,
+                         int ldo, int late, float* split_part, unsigned* counter, hipStream_t st) {
+    const int F = x.IMG + x.LOC;
+    if (x.dense || x.half || !x.table || !x.loc_table || !x.vp || !x.view || !pt.pv || !pt.lv || !h1 || !alpha || !out ||
+        !split_part)
+        return SF_ERR_ARG;
+    if (B < 1 || B > VIS_SPLIT_MAX_B || x.V <= (VSP_G - 1) * VSP_RPG || x.V > VSP_G * VSP_RPG || F > VIS_CPL * 256 ||
+        (x.IMG & 3) || (x.LOC & 3) || pt.H > PRJ_CPL * 256 || (pt.H & 3) || pt.H < 4 || (pt.ld & 3) || pt.ld < pt.H + 1 ||
+        (ldh1 & 3) || ldh1 < pt.H || (ldo & 3) || ldo < F || (late ? !counter : !proj_partials_supported(x)))
+        return SF_ERR_UNSUPPORTED;
+    const VisArgs va = proj_vis_args(x, pt, h1, ldh1, alpha, out, ldo, Dropout{}, 0);
+    const VisSplit sp{split_part, late ? counter : nullptr, nullptr};
+    const dim3 block(SMALL_WAVES * 64);
+    if (late) {
+        SF_LAUNCH((pair_proj_score_kernel<0>), dim3(VSP_G * B), block, 0, st, ProjScoreArgs{}, FGlue{}, 0, va, sp, VSP_G * B);
+    } else {
+        SF_LAUNCH((pair_proj_textfold_kernel<1, true>), dim3(PPB_G * B), block, 0, st, va, sp, PPB_G * B, TxtFoldArgs{}, 0,
+                  SmallArgs{}, 1);
+        SF_LAUNCH((pair_proj_score_kernel<2>), dim3(B), block, 0, st, ProjScoreArgs{}, FGlue{}, 0, va, sp, 0);
+    }
     return launch_status();
 }
 

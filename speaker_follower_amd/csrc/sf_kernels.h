@@ -246,6 +246,11 @@ struct ProjTables {
     int ld, H;
 };
 bool proj_chain_supported(const CandSrc& us, const PanoSrc* xn, int B, int H, int L, const ProjTables& pt);
+// whether launch (1) can carry the attention partials of a panorama of this row layout (pair_proj_textfold with `xn`);
+// where it cannot they ride in launch (2) (pair_proj_score, vphase 0)
+bool proj_partials_supported(const PanoSrc& xn);
+int proj_attention_alone(const PanoSrc& x, int B, const ProjTables& pt, const float* h1, int ldh1, float* alpha, float* out,
+                         int ldo, int late, float* split_part, unsigned* counter, hipStream_t st);
 int visual_attn_proj(const CandSrc& us, const PanoSrc& x, int B, int H, int L, const ProjTables& pt, const float* h, int ldh,
                      float* alpha, float* out, int ldo, const Dropout& drop, int drop_col0, float* split_part,
                      unsigned* counter, hipStream_t st);

@@ -1,6 +1,6 @@
 """A/B of the projected decode chain on the headline batch (100 x 20 steps, hipGraph replay, ms per rollout), both
 chains in ONE process, interleaved: the four-launch folded chain (project = False), the projected chain with the attention
-partials in launch (2) (the default) and with the partials in launch (1) (sf_debug_projected_partials_late(0)).
+partials in launch (1) (the default) and with the partials in launch (2) (sf_debug_projected_partials_late(1)).
 Reports median / min / max over the rounds, the table build, and -- from one eager rollout each under the library's launch
 profile -- the per-kernel times of the decode step."""
 import os, sys, time, statistics
@@ -10,6 +10,7 @@ sys.argv = ['bench.py']
 import bench
 from speaker_follower_amd import synth, features, follower, _lib
 ROUNDS = int(os.environ.get('SF_AB_ROUNDS', '7'))
+DEFAULT_LATE = 0         # csrc/sf_api.hip: g_proj_partials_late
 dev = torch.device('cuda', 0)
 enc, dec, _, _ = bench.build_models(101, dev)
 enc.eval(); dec.eval()
@@ -41,8 +42,8 @@ for label in ('first build (allocates 2 x %.2f GB)', 'rebuild in place'):
     runtime.invalidate_caches()
 
 LEGS = (('folded, four launches (project = False)', False, 0),
-        ('projected, partials in launch (2) [default]', True, 1),
-        ('projected, partials in launch (1)', True, 0))
+        ('projected, partials in launch (2)', True, 1),
+        ('projected, partials in launch (1) [default]', True, 0))
 runs = {}
 for name, project, late in LEGS:
     _lib.lib.sf_debug_projected_partials_late(late)
@@ -53,7 +54,7 @@ for name, project, late in LEGS:
     replay()
     torch.cuda.synchronize()
     runs[name] = (replay, st, st.actions.clone(), st.logits.clone(), [])
-_lib.lib.sf_debug_projected_partials_late(1)
+_lib.lib.sf_debug_projected_partials_late(DEFAULT_LATE)
 for _ in range(ROUNDS):                      # interleaved: a drift of the box hits every leg alike
     for name, _, _ in LEGS:
         runs[name][4].append(timed(runs[name][0]))
@@ -84,4 +85,4 @@ for name, project, late in LEGS:
     for k, r in sorted(prof.rows.items(), key=lambda kv: -kv[1]['total_us']):
         if r['calls'] >= 19:
             print('    %-86s %3d x %6.2f us (min %.2f, max %.2f)' % (k[:86], r['calls'], r['avg_us'], r['min_us'], r['max_us']))
-_lib.lib.sf_debug_projected_partials_late(1)
+_lib.lib.sf_debug_projected_partials_late(DEFAULT_LATE)
