@@ -548,7 +548,8 @@ int sf_encoder_lstm_fwd(const sf_encoder_w* w, int B, int Lpad, int T, int E, in
                         float* decoder_init, float* c_t, const sf_encoder_tape* tape,
                         const sf_dropout* drop, uint32_t drop_stream, void* ws, size_t ws_bytes,
                         sf_stream stream);
-/* dctx [B,T,H] (gradient wrt the dropped ctx), d_init, d_ct [B,H] in (NULL = zero). */
+/* dctx [B,T,H] (gradient wrt the dropped ctx), d_init, d_ct [B,H] in (NULL = zero).  ctx beyond a row's length is the
+ * constant 0 (model.py:101), so what dctx holds there is ignored: it reaches no state and no weight gradient. */
 int sf_encoder_lstm_bwd(const sf_encoder_w* w, const sf_encoder_g* g, int B, int T, int E, int H,
                         const int32_t* lengths, const float* decoder_init, const float* dctx,
                         const float* d_init, const float* d_ct, const sf_encoder_tape* tape,
@@ -660,7 +661,9 @@ typedef struct sf_sample {
  * optional outputs (NULL = skip): logits [S,B,ldv], alpha [S,B,Tp], h1_tape / c1_tape [S,B,H].
  * Needs w->xw_table and w->attn.w_in_t.  The attention is evaluated in the folded form
  * cq = ctx W_in, cw = ctx W_c^T (same function, fp32 re-association).  SF_ERR_UNSUPPORTED (H != 512,
- * B > 128, Tp > 12, vocab > 1024, fewer than 256 CUs): run the per-step entry points instead. */
+ * B > 128, Tp > 12, vocab < 32, vocab > 1024, fewer than 256 CUs; w->xw_table or w->attn.w_in_t missing): run the
+ * per-step entry points instead; nothing has been written.  SF_ERR_ARG comes first: feedback outside 0..2, feedback 2
+ * without `sample`, one of h1_tape / c1_tape without the other. */
 int sf_speaker_decode(const sf_spk_decoder_w* w, int B, int H, int Tp, int vocab, int S, int feedback,
                       int pad_idx, int eos_idx, const int64_t* targets, const float* h_init,
                       const float* c_init, const float* ctx, const uint8_t* ctx_mask, int64_t* words,

@@ -1216,7 +1216,7 @@ __global__ __launch_bounds__(BWS_WAVES * 64) void lstm_bwd_step_fused_kernel(Lst
             const uint32_t rk = drop_key(p.ctx_drop, (uint32_t)(p.ctx_drop.row0 + qb));
             v = dropout_keep(rk, (uint32_t)(p.t * H + pj), p.ctx_drop.thresh) ? v * p.ctx_drop.scale : 0.f;
         }
-        dh += v;
+        dh += dead ? 0.f : v;                                    // (ctx beyond a row's length is the constant 0)
     }
 
     f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};

@@ -49,7 +49,7 @@ __device__ __forceinline__ void lstm_pw_bwd_elem(const LstmPwBwd& a, int b, int 
             v = dropout_keep(rk, (uint32_t)(a.t * H + j), a.ctx_drop.thresh)
                     ? v * a.ctx_drop.scale : 0.f;
         }
-        dh += v;
+        dh += dead ? 0.f : v;                         // (ctx beyond a row's length is the constant 0)
     }
     float* dg = a.dgates + (size_t)b * 4 * H + j;
     const float tc = tanhf(c1);

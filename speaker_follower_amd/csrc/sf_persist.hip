@@ -502,12 +502,12 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_persist_kernel(EncBwdPersistAr
         g_i = gp[0]; g_f = gp[H]; g_g = gp[2 * H]; g_o = gp[3 * H];
         c0v = cs[(size_t)t * BH + (size_t)eb * H + ej];
         c1v = cs[(size_t)(t + 1) * BH + (size_t)eb * H + ej];
-        if (NDIR == 1)
-            dcx = p.dctx ? p.dctx[(size_t)eb * p.dctx_sb + (size_t)t * p.dctx_st + ej] : 0.f;
-        else if (dir)                             // reverse: position len_b - 1 - t; a step beyond the length has none
+        // ctx beyond a row's length is the constant 0 (model.py:101): whatever dctx holds there reaches nothing, in
+        // either direction
+        if (NDIR == 2 && dir)                     // reverse: position len_b - 1 - t; a step beyond the length has none
             dcx = (p.dctx && t < len_b) ? p.dctx[(size_t)eb * p.dctx_sb + (size_t)(len_b - 1 - t) * p.dctx_st + H + ej] : 0.f;
         else
-            dcx = p.dctx ? p.dctx[(size_t)eb * p.dctx_sb + (size_t)t * p.dctx_st + ej] : 0.f;
+            dcx = (p.dctx && t < len_b) ? p.dctx[(size_t)eb * p.dctx_sb + (size_t)t * p.dctx_st + ej] : 0.f;
     };
     fetch(T - 1);
 

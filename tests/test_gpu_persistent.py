@@ -13,6 +13,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from speaker_follower_amd import synth                                # noqa: E402
+from tests.persist_cases import _encoder_f64                          # noqa: E402  (the float64 recurrence: shared with test_gpu_persistent_edges.py)
 
 
 def encoder(seed=101):
@@ -49,27 +50,6 @@ def run(enc, seq, lens, persistent, train=False):
               *ws_args(seq.device))
     out.pop('xg')            # the per-step path with a table never writes it either
     return out
-
-
-def _encoder_f64(enc, seq, lens):
-    """The recurrence in float64 on the host (model.py:81-104, eval mode): hs [T+1,B,H], cs."""
-    w = {k: v.detach().double().cpu() for k, v in enc.state_dict().items()}
-    B, T, H = seq.shape[0], max(lens), enc.hidden_size
-    x = w['embedding.weight'][seq.cpu()[:, :T]]                       # [B,T,E]
-    h = torch.zeros(B, H, dtype=torch.float64)
-    c = torch.zeros(B, H, dtype=torch.float64)
-    hs, cs = [h], [c]
-    ln = torch.tensor(lens)
-    for t in range(T):
-        g = x[:, t] @ w['lstm.weight_ih_l0'].T + w['lstm.bias_ih_l0'] + h @ w['lstm.weight_hh_l0'].T + w['lstm.bias_hh_l0']
-        i, f, gg, o = g.chunk(4, 1)
-        c1 = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-        h1 = torch.sigmoid(o) * torch.tanh(c1)
-        live = (t < ln)[:, None]
-        h, c = torch.where(live, h1, h), torch.where(live, c1, c)
-        hs.append(h)
-        cs.append(c)
-    return torch.stack(hs), torch.stack(cs)
 
 
 @pytest.mark.parametrize('B,min_len,max_len,train', [(100, 10, 79, False), (100, 10, 79, True), (8, 3, 19, False),
