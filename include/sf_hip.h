@@ -446,10 +446,13 @@ typedef struct sf_follower_episode {
     sf_follower_glue glue;
     sf_dropout drop;              /* p == 0: no dropout */
     uint32_t step0;               /* dropout / sampling site of step 0 */
-    /* optional, backward only: a second stream.  With it (and gtape.dcat2 / ds / dh1d) the scoring and
+    /* optional: a second stream.  BACKWARD: with it (and gtape.dcat2 / ds / dh1d) the scoring and
      * text-attention backward of step t-1 run on it while the LSTM / visual backward of step t runs on
      * `stream` (they only meet at the LSTM pointwise backward); the two are ordered with events and the
-     * call leaves `stream` behind all of the side stream's work. */
+     * call leaves `stream` behind all of the side stream's work.  FORWARD: it means exactly one thing, the two-chain
+     * schedule -- the visual half of step t + 1 on it beside the rest of step t on `stream`, ordered per step by device
+     * flags, one fork and one join per episode -- taken for pre-drawn observations, S > 1, no w->fold and no
+     * ctx_q / ctx_o; every other forward pass ignores it. */
     sf_stream side_stream;
     /* ABI 9, optional, INFERENCE ONLY (drop.p == 0, no backward through this pass: t_text / cat2[:H] / h_tilde of the
      * tape are NOT written; alpha is): two [B,L,H] scratch tensors.  With them sf_follower_episode_fwd forms
@@ -457,8 +460,8 @@ typedef struct sf_follower_episode {
      * attention of every step but the last in folded form -- scores ctx_q[l] . h1, h~ = tanh(sum alpha_l ctx_o[l] +
      * W_out[:, H:] h1): the same function (fp32 re-association, like q = W_v^T t_v), two dependent launches fewer per
      * decode step.  Needs w->text.w_in_t and w->action.w_a_t; pre-drawn observations or a device-resident environment
-     * (glue.nav).  With ctx_q / ctx_o, `side_stream` (if given) only carries the two fold products beside step 0's
-     * attention (one fork, one join); the two-chain forward schedule is not taken. */
+     * (glue.nav).  The two fold products run on `stream` in front of step 0's attention; with ctx_q / ctx_o the
+     * two-chain forward schedule of `side_stream` is not taken. */
     float *ctx_q, *ctx_o;
     /* ... and, with the folded matrices of sf_decoder_fold (built once per weight version, sf_decoder_fold_build): the next
      * step's visual query as ONE product q' = M_v h1 + c_v beside the folded attention, the scoring vector / constant as
@@ -1091,13 +1094,8 @@ int sf_debug_projected_attention(const sf_pano* X, int B, int H, const float* pv
  * error-free operand splitting (csrc/sf_gemm.hip: gemm_nt_split_kernel; same fp32 accuracy class, measured closer
  * to the exact sum, 6/16 of the matrix-pipe time).  For A/B timing and for the accuracy tests. */
 void sf_debug_gate_product_f32(int on);
-/* folded inference chain (ABI 9): 1 (default) = attention partials beside r and their merge beside scoring + glue;
- * 0 = partials, ticket and merge in one launch beside r */
-void sf_debug_fold_merge_with_glue(int on);
 /* 0: the four-launch folded chain even when sf_follower_episode.chain_fold is given (A/B switch) */
 void sf_debug_fold_chain3(int on);
-/* 1 (default): with sf_follower_episode.side_stream the two fold products run on it beside step 0's attention */
-void sf_debug_fold_build_overlap(int on);
 /* A/B switch (round 5): on == 0 sends the many-row products (M >= 512: the speaker's teacher-forced head over all S*B rows,
  * the beam search's flat steps) back to the register-streaming kernel of rounds 1-4 instead of the LDS-tiled 128 x 128
  * bf16x6 kernel (csrc/sf_gemm.hip: gemm_nt_big_kernel; the default).  Bit 1 of `on` (on == 3) keeps the kernel but turns off
@@ -1112,20 +1110,6 @@ void sf_debug_grouped_weight_gradients(int on);
  * backward of a decoder step (the default: the attention backward adds up the K-split slabs of d(feature) itself --
  * same order, same bits). */
 void sf_debug_slab_consumers(int on);
-/* Experiment switch (round 5): on != 0 runs the LSTM cell's pointwise backward of a decoder step as the epilogue of the
- * small product that completes that step's dh1 (the last launch of the backward step before it) instead of its own
- * launch: same arithmetic, same bits (tested), one launch fewer per step -- and no faster (4.81 vs 4.79 ms). */
-void sf_debug_fused_cell_backward(int on);
-/* Experiment switch: the two-stream backward through time issues the head of step t - steps right before the tail of
- * step t (steps >= 1) instead of every head first (steps < 0, the default). */
-void sf_debug_bptt_lookahead(int steps);
-/* Experiment switch (round 5): on != 0 orders the two chains of the two-stream backward through time (heads: scoring /
- * text attention; tails: LSTM / visual attention) with one-shot device flags instead of events (a flag wait that gives
- * up raises bit 16 of the fault word).  Measured equal. */
-void sf_debug_bptt_flags(int on);
-/* Experiment switch (tools/bptt_overlap_probe.py): 1 = the two-stream backward issues its heads only, 2 = its tails only
- * (no waits): the two chains as separately captured graphs. */
-void sf_debug_bptt_part(int part);
 /* A/B switch: on == 0 makes sf_speaker_encoder_fwd run its visual attention on the fp32 kernels (rounds 1-4) instead
  * of the float64 query / score path (sf_visual_attention_fwd_f64; the default). */
 void sf_debug_precise_attention(int on);

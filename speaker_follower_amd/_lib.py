@@ -179,17 +179,11 @@ _SIGNATURES = {
     'sf_build_id': (C.c_char_p, []),
     'sf_debug_persist_timeout': (None, [C.c_longlong]),
     'sf_debug_gate_product_f32': (None, [C.c_int]),
-    'sf_debug_fold_merge_with_glue': (None, [C.c_int]),
     'sf_debug_fold_chain3': (None, [C.c_int]),
-    'sf_debug_fold_build_overlap': (None, [C.c_int]),
     'sf_debug_precise_attention': (None, [C.c_int]),
     'sf_debug_many_row_product': (None, [C.c_int]),
     'sf_debug_grouped_weight_gradients': (None, [C.c_int]),
     'sf_debug_slab_consumers': (None, [C.c_int]),
-    'sf_debug_fused_cell_backward': (None, [C.c_int]),
-    'sf_debug_bptt_lookahead': (None, [C.c_int]),
-    'sf_debug_bptt_flags': (None, [C.c_int]),
-    'sf_debug_bptt_part': (None, [C.c_int]),
     'sf_site_advance': (C.c_int, [c_p, u32, c_p]),
     'sf_store_u32x4': (C.c_int, [c_p, u32, u32, u32, u32, c_p]),
     'sf_adam_step_dev': (C.c_int, [c_f, c_f, c_f, c_f, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_double,

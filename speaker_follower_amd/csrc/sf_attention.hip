@@ -1035,7 +1035,7 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_vis_small_kernel(VisArg
         else
             visual_split_body<PHASE, false, H16>(v, sp, bid % VSP_G, bid / VSP_G);
     } else {
-        small_gemm_body<MT, CPW, false, false, APRO>(b, (bid - nv) % gxb, (bid - nv) / gxb);
+        small_gemm_body<MT, CPW, false, APRO>(b, (bid - nv) % gxb, (bid - nv) / gxb);
     }
 }
 
@@ -1393,7 +1393,7 @@ template <int MTB>
 __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_apro_small_kernel(SmallArgs a, int gxa, int na, SmallArgs b, int gxb) {
     const int bid = blockIdx.x;
     if (bid < na)
-        small_gemm_body<1, 4, false, false, true>(a, bid % gxa, bid / gxa);
+        small_gemm_body<1, 4, false, true>(a, bid % gxa, bid / gxa);
     else
         small_gemm_body<MTB, 2>(b, (bid - na) % gxb, (bid - na) / gxb);
 }

@@ -149,7 +149,6 @@ int cotenant(int blocks, int threads, int lds_bytes, long long ticks, float* sin
 // device-flag ordering between two streams (sf_pointwise.hip)
 int flag_wait(const unsigned* flag, unsigned target, hipStream_t st);
 int flag_set(unsigned* flag, unsigned value, hipStream_t st);
-int flag_wait_clear(unsigned* flag, unsigned* fault, unsigned fault_code, hipStream_t st);   // one-shot: wait for != 0, then clear
 int adam_step(float* p, const float* g, float* m, float* v, size_t n, double lr, double beta1,
               double beta2, double eps, double wd, int step, hipStream_t st);
 // the same with the 1-based step counter ON THE DEVICE (incremented by the call; coef: 2 floats of scratch)

@@ -1,6 +1,5 @@
-// The LSTM cell's pointwise backward (model.py:393 / LSTMCell): its parameter block and the arithmetic of ONE element,
-// shared by the stand-alone kernel (sf_pointwise.hip: lstm_pw_bwd_kernel) and the epilogue of the small product that
-// completes dh1 in the decoder's backward through time (sf_gemm.hip: gemm_nt_small_pw_kernel).
+// The LSTM cell's pointwise backward (model.py:393 / LSTMCell): its parameter block (sf_kernels.h: lstm_pointwise_bwd)
+// and the arithmetic of ONE element (sf_pointwise.hip: lstm_pw_bwd_kernel).
 #pragma once
 #include "sf_common.h"
 

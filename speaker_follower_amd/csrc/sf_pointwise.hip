@@ -1023,24 +1023,6 @@ __global__ void flag_wait_kernel(const unsigned* flag, unsigned target) {
 __global__ void flag_set_kernel(unsigned* flag, unsigned value) {
     if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// Consumer side of a one-shot flag: spin until the word is non-zero, then clear it for the next use.  A wait that gives
-// up (0.5 s) raises `fault_code` in the fault word: the host re-issues the pass (runtime.take_fault).
-__global__ void flag_wait_clear_kernel(unsigned* flag, unsigned* fault, unsigned fault_code) {
-    if (threadIdx.x != 0) return;
-    const long long t0 = wall_clock64();
-    while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-        __builtin_amdgcn_s_sleep(4);
-        if (wall_clock64() - t0 > 50000000LL) {           // never hang a stream
-            if (fault) atomicOr(fault, fault_code);
-            break;
-        }
-    }
-    __hip_atomic_store(flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-int flag_wait_clear(unsigned* flag, unsigned* fault, unsigned fault_code, hipStream_t st) {
-    SF_LAUNCH(flag_wait_clear_kernel, dim3(1), dim3(64), 0, st, flag, fault, fault_code);
-    return launch_status();
-}
 int flag_wait(const unsigned* flag, unsigned target, hipStream_t st) {
     SF_LAUNCH(flag_wait_kernel, dim3(1), dim3(64), 0, st, flag, target);
     return launch_status();

@@ -12,7 +12,6 @@
 """
 import contextlib
 import ctypes as C
-import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -262,14 +261,7 @@ class FollowerEngine:
         # over all S*B rows at the end, 5.49 with 2 or 4 chunks, 5.7 with 10 (tools/train_time.py) -- a
         # chip-filling product does not hide beside the dependent chain, it delays it.  Off (1).
         self.wgrad_chunks = 1
-        # the eight small weight-gradient products on a third stream beside the two LSTM ones: measured no gain
-        # (5.29 vs 5.26 ms per iteration): off
-        self.split_wgrad_streams = False
-        self.encoder_backward_first = os.environ.get('SF_ENC_BWD_FIRST', '0') == '1'   # (experiment switch, see _backward)
         self.grad_sync = None            # dp.BucketedGrads(dp.follower_buckets(enc, dec)): all-reduce launched from the backward
-        # the fold's two products on a second stream beside step 0's attention: built, correct, SLOWER -- the fork and the
-        # join inside the replayed graph cost more than the 25 us they hide (1.813 against 1.759 ms per rollout): off
-        self.fold_build_overlap = False
         self._open_forks = []            # side streams forked from the current one and not joined yet (_backward)
         # ... with q' = M_v h1 + c_v and [r | c] = M_a h~ + c_a as single products (ABI 9 chain_fold): three launches behind
         # the cell instead of four -- BUILT, CORRECT, SLOWER (round 6: 2.03 ms per rollout against 1.77: the [100 x 512] x
@@ -507,12 +499,6 @@ class FollowerEngine:
             # differentiable or train-mode rollout; one stream only.
             st.text_folded = (self.fold_text and not st.differentiable and not training and fold is None
                               and ep.side_stream is None and S > 1 and T <= 80)
-            if st.text_folded and self.fold_build_overlap:
-                # the two fold products (they need the encoder's context only) on a second stream beside step 0's attention
-                if self._side_stream is None:
-                    self._side_stream = concurrent_stream(dev)
-                    ensure_workspace(self._side_stream, dev)
-                ep.side_stream = self._side_stream.cuda_stream
             if st.text_folded:
                 st.ctx_fold = new(2, B, T, H)
                 ep.ctx_q, ep.ctx_o = st.ctx_fold[0].data_ptr(), st.ctx_fold[1].data_ptr()
@@ -908,10 +894,6 @@ class FollowerEngine:
                         call('sf_attn_decoder_wgrad', byref(dw), byref(dg), (hi - lo) * B, H, D, F, ptr(st.hs[lo:]),
                              byref(tpk), byref(gtk), *ws_args(dev))
                     st.wgrad_done_from = lo
-        if getattr(self, '_bptt_only', False):          # (tools/bptt_overlap_probe.py times the backward through time alone)
-            if self._side_stream is not None:
-                torch.cuda.current_stream().wait_stream(self._side_stream)
-            return
         for t in range(S - 1 if st.episode is None else -1, -1, -1):
             pano = store.pano(batch.vp[t], batch.view[t])
             cnd = store.cands(batch.vp[t], batch.cand_view[t], batch.sincos[t], batch.a_num[t], A)
@@ -941,24 +923,15 @@ class FollowerEngine:
                 side = self._side_stream = concurrent_stream(dev)
             side.wait_stream(torch.cuda.current_stream())
             self._open_forks = [side]                    # (a segmented capture joins / re-opens these at its cuts)
-            third = None
-            if self.split_wgrad_streams:
-                # the eight small products (25 TFLOP/s between them) beside the two LSTM ones (dW_ih alone fills the chip
-                # at 0.76 of the matrix peak) instead of behind them: two streams, same accumulation targets
-                if self._wgrad_stream is None:
-                    self._wgrad_stream = concurrent_stream(dev, exclude=[x for x in (self._side_stream,) if x is not None])
-                third = self._wgrad_stream if self._wgrad_stream is not side else self._side_stream
-                third.wait_stream(torch.cuda.current_stream())
-                self._open_forks.append(third)
         # (Measured in round 5 by wall clock: the encoder first, the two latency-bound pieces side by side, a third stream
         # and chunked weight gradients are all equal or slower than this order; what shortened the tail was fewer launches,
         # gemm_tn_group.  The many-row weight-gradient tiles -- 512 threads x 188 VGPRs, 96 KB LDS -- cannot sit beside the
         # persistent encoder backward's 256-VGPR workgroup on a CU.  NOTE: rocprofv3 --kernel-trace serialises the queues;
-        # its timelines show no overlap at all and must not be read for concurrency, tools/bptt_overlap_probe.py.)
+        # its timelines show no overlap at all and must not be read for concurrency; DESIGN.md, "Retired experiments".)
         try:
-            if overlap and not self.encoder_backward_first:
-                self._issue_wgrad(side, third, dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, dev, sync)
-            elif not overlap:
+            if overlap:
+                self._issue_wgrad(side, dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, dev, sync)
+            else:
                 self._decoder_wgrad(dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, wgrad_ws_args(dev), sync)
             if enc.num_directions == 2:
                 bi_encoder_bwd(enc, batch.seq, batch.lengths_dev, T, dropout_arg(*st.drop_enc_bi), st.site_rel,
@@ -972,40 +945,28 @@ class FollowerEngine:
                      st.site_rel, *ws)
             if sync is not None:
                 sync.launch(2)                       # encoder gradients: complete behind sf_encoder_lstm_bwd
-            if overlap and self.encoder_backward_first:
-                self._issue_wgrad(side, third, dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, dev, sync)
             if overlap:
                 torch.cuda.current_stream().wait_stream(side)
-                if third is not None:
-                    torch.cuda.current_stream().wait_stream(third)
         finally:
             self._open_forks = []        # (also when the backward raises: a later segmented capture must not join stale forks)
 
-    def _issue_wgrad(self, side, third, dw, dg, params, M, H, D, F, st, tp0, gt0, dev, sync):
-        """The decoder's weight gradients on the side stream(s) (which already wait for the backward through time)."""
+    def _issue_wgrad(self, side, dw, dg, params, M, H, D, F, st, tp0, gt0, dev, sync):
+        """The decoder's weight gradients on the side stream (which already waits for the backward through time)."""
         with torch.cuda.stream(side):
-            self._decoder_wgrad(dw, dg, params, M, H, D, F, st, tp0, gt0, wgrad_ws_args(dev), sync,
-                                part='lstm' if third is not None else 'all')
-        if third is not None:
-            with torch.cuda.stream(third):
-                self._decoder_wgrad(dw, dg, params, M, H, D, F, st, tp0, gt0, wgrad_ws_args(dev), sync, part='rest')
+            self._decoder_wgrad(dw, dg, params, M, H, D, F, st, tp0, gt0, wgrad_ws_args(dev), sync)
 
     @staticmethod
-    def _decoder_wgrad(dw, dg, params, M, H, D, F, st, tp0, gt0, ws, sync, part='all'):
-        """sf_attn_decoder_wgrad on the current stream: `part` = 'lstm' (the two LSTM products + bias sums: the
-        40 MB gradient bucket), 'rest' (the other decoder weights) or 'all' (LSTM first).  With a gradient-bucket
-        sync each part's all-reduce is launched behind it."""
-        if sync is None and part == 'all':
+    def _decoder_wgrad(dw, dg, params, M, H, D, F, st, tp0, gt0, ws, sync):
+        """sf_attn_decoder_wgrad on the current stream.  With a gradient-bucket sync it is two calls -- the two LSTM
+        products + bias sums (the 40 MB gradient bucket), then the other decoder weights -- and each part's all-reduce is
+        launched behind it."""
+        if sync is None:
             call('sf_attn_decoder_wgrad', byref(dw), byref(dg), M, H, D, F, ptr(st.hs), byref(tp0), byref(gt0), *ws)
             return
         g_lstm, g_rest = _lib.DecoderW(), _lib.DecoderW()
         g_lstm.lstm = dg.lstm
         g_rest.visual, g_rest.text, g_rest.action = dg.visual, dg.text, dg.action
-        if part in ('all', 'lstm'):
-            call('sf_attn_decoder_wgrad', byref(dw), byref(g_lstm), M, H, D, F, ptr(st.hs), byref(tp0), byref(gt0), *ws)
-            if sync is not None:
-                sync.launch(0)
-        if part in ('all', 'rest'):
-            call('sf_attn_decoder_wgrad', byref(dw), byref(g_rest), M, H, D, F, ptr(st.hs), byref(tp0), byref(gt0), *ws)
-            if sync is not None:
-                sync.launch(1)
+        call('sf_attn_decoder_wgrad', byref(dw), byref(g_lstm), M, H, D, F, ptr(st.hs), byref(tp0), byref(gt0), *ws)
+        sync.launch(0)
+        call('sf_attn_decoder_wgrad', byref(dw), byref(g_rest), M, H, D, F, ptr(st.hs), byref(tp0), byref(gt0), *ws)
+        sync.launch(1)

@@ -244,14 +244,12 @@ def test_grouped_weight_gradients_match_the_reference_and_the_single_products(fo
         m.zero_grad(set_to_none=True)
 
 
-@pytest.mark.parametrize('switch', ['sf_debug_slab_consumers', 'sf_debug_fused_cell_backward'])
+@pytest.mark.parametrize('switch', ['sf_debug_slab_consumers'])
 def test_launches_taken_off_the_backward_chain_leave_the_same_bits(follower_modules, golden, switch):
-    """Two launches less on the critical chain of every backward step, each with an A/B switch: the feature half of
+    """One launch less on the critical chain of every backward step, with an A/B switch: the feature half of
     d(LSTM input) reaches the visual-attention backward as the K-split slabs of its product and is added up there
-    (sf_debug_slab_consumers); the LSTM cell's pointwise backward of step t - 1 is the epilogue of the product that
-    completes its dh1, the last launch of step t (sf_debug_fused_cell_backward).  Same order of additions, same
-    arithmetic: the SAME bits as the launches they replace, on one stream and on two, with dropout, and the reference's
-    gradients (G4, B = 100)."""
+    (sf_debug_slab_consumers).  Same order of additions, same arithmetic: the SAME bits as the launch it replaces, on
+    one stream and on two, with dropout, and the reference's gradients (G4, B = 100)."""
     from speaker_follower_amd import _lib
     enc, dec, _, _ = follower_modules
     fb = synth.follower_batch(seed=0, batch=100, steps=20, n_viewpoints=256)
@@ -262,7 +260,7 @@ def test_launches_taken_off_the_backward_chain_leave_the_same_bits(follower_modu
     for two_stream in (True, False):
         engine.two_stream_backward = two_stream
         grads = {}
-        default = {'sf_debug_slab_consumers': 1, 'sf_debug_fused_cell_backward': 0}[switch]
+        default = {'sf_debug_slab_consumers': 1}[switch]
         for on in (1, 0):
             getattr(_lib.lib, switch)(on)
             try:

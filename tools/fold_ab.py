@@ -1,12 +1,12 @@
 """A/B of the inference decode chain on the headline batch (100 x 20 steps, hipGraph replay, ms per rollout):
-unfolded (round 5's six launches behind the cell), folded text attention with four launches (partials + ticket merge in the r
-launch | partials beside r, merge beside scoring + glue), and the three-launch chain over the M_v / M_a products."""
+unfolded (round 5's six launches behind the cell), folded text attention with four launches (partials beside r, merge
+beside scoring + glue), and the three-launch chain over the M_v / M_a products."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 sys.argv = ['bench.py']
 import bench
-from speaker_follower_amd import synth, features, follower, _lib
+from speaker_follower_amd import synth, features, follower
 dev = torch.device('cuda', 0)
 enc, dec, _, _ = bench.build_models(101, dev)
 enc.eval(); dec.eval()
@@ -27,11 +27,9 @@ def timed(replay, n=40):
 
 
 ref = None
-for name, fold, chain, merge in (('unfolded (six launches behind the cell)', False, False, 1),
-                                 ('folded, partials + ticket merge beside r', True, False, 0),
-                                 ('folded, partials beside r, merge beside the glue', True, False, 1),
-                                 ('folded, three launches (M_v / M_a products)', True, True, 1)):
-    _lib.lib.sf_debug_fold_merge_with_glue(merge)
+for name, fold, chain in (('unfolded (six launches behind the cell)', False, False),
+                          ('folded, partials beside r, merge beside the glue', True, False),
+                          ('folded, three launches (M_v / M_a products)', True, True)):
     eng = follower.FollowerEngine(enc, dec, store)
     eng.fold_text, eng.fold_chain = fold, chain
     replay, st = eng.capture(batch, 20, 'argmax')
@@ -41,4 +39,3 @@ for name, fold, chain, merge in (('unfolded (six launches behind the cell)', Fal
         ref = acts
     print('%-52s %.4f ms per rollout (best of 3; %.4f .. %.4f) = %7.0f agent-steps/s, actions equal: %s'
           % (name, min(ms), min(ms), max(ms), 2000 / (min(ms) * 1e-3), bool(torch.equal(acts, ref))), flush=True)
-_lib.lib.sf_debug_fold_merge_with_glue(1)
