@@ -1081,6 +1081,17 @@ void sf_debug_projected_chunk_rows(int rows);
  * on != 0 puts them into launch (2) (partials, ticket and merge beside the scoring; launch (1) is the text stage and y
  * alone).  A panorama with ceil(IMG / 256) + ceil(LOC / 256) > 9 takes the second placement whatever the switch says. */
 void sf_debug_projected_partials_late(int on);
+/* Text groups per sample of launch (1) when it carries the attention partials.  The rule (a pure function of B, L and the
+ * device): TWO groups of 8 * RPW positions iff the partials ride in the launch, L <= 80 and the four-group grid
+ * 3 B + 4 B + product_blocks exceeds `slots`, the workgroups of that launch the device holds at once (CUs x the runtime's
+ * occupancy of the four-group kernel: 512 on an MI355X, so B >= 69 at H = 512); four groups otherwise.  Every launch adds
+ * 4 tickets per sample whatever its count, so launches of both kinds share a workspace.
+ * sf_projected_text_groups_plan is the rule alone, no device needed: returns the count (0: bad arguments) and, with
+ * `grid`, the launch's block count; product_blocks = blocks of y = W_out[:, H:] h1 (32 at H = 512); slots 0 = unknown,
+ * four groups.  sf_debug_projected_text_groups: 0 the rule (default), 2 or 4 that count wherever it is legal (2: with
+ * partials and L <= 80 only) -- for A/B timing and the tests. */
+int sf_projected_text_groups_plan(int B, int L, int with_partials, int slots, int product_blocks, int* grid);
+void sf_debug_projected_text_groups(int groups);
 /* Test entry: the attention of the projected chain's launches (1) and (2) alone, on caller buffers -- the same two kernels
  * with empty text, product and scoring parts, so that panorama shapes no engine is built for (V below 36, tiny rows, small
  * H) reach them.  X: index-form fp32 panorama (V in 19..36); pv [n_vp * V, ld], lv [V * V, ld] as sf_projected_build

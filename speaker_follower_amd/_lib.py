@@ -208,6 +208,8 @@ _SIGNATURES = {
     'sf_projected_is_used': (C.c_int, []),
     'sf_projected_steps': (C.c_longlong, []),
     'sf_debug_projected_partials_late': (None, [C.c_int]),
+    'sf_debug_projected_text_groups': (None, [C.c_int]),
+    'sf_projected_text_groups_plan': (C.c_int, [i32, i32, i32, i32, i32, P(C.c_int)]),
     'sf_debug_projected_attention': (C.c_int, [P(Pano), i32, i32, c_f, c_f, i32, c_f, i32, c_f, c_f, i32, i32] + WS),
     'sf_projected_supported': (C.c_int, [i32] * 7),
     'sf_debug_projected_chunk_rows': (None, [C.c_int]),

@@ -608,6 +608,11 @@ void sf_projected_use(int on) { g_proj_use.store(on ? 1 : 0, std::memory_order_r
 int sf_projected_is_used(void) { return g_proj_use.load(std::memory_order_relaxed); }
 long long sf_projected_steps(void) { return g_proj_steps.load(std::memory_order_relaxed); }
 void sf_debug_projected_partials_late(int on) { g_proj_partials_late = on; }
+void sf_debug_projected_text_groups(int groups) { sf::g_proj_text_groups = groups == 2 || groups == 4 ? groups : 0; }
+int sf_projected_text_groups_plan(int B, int L, int with_partials, int slots, int product_blocks, int* grid) {
+    if (B < 1 || L < 1 || slots < 0 || product_blocks < 0) return 0;
+    return sf::proj_text_groups_plan(B, L, with_partials != 0, product_blocks, slots, 0, grid);
+}
 int sf_debug_projected_attention(const sf_pano* X, int B, int H, const float* pv, const float* lv, int ld, const float* h1,
                                  int ldh1, float* alpha, float* out, int ldo, int late, void* ws, size_t ws_bytes,
                                  sf_stream stream) {
@@ -647,6 +652,7 @@ int sf_projected_build(const sf_decoder_fold* fold, const float* table, long lon
     const int F = IMG + LOC, Fa = F + 4, ld = projected_ld(H), Ks = LOC + 4, g = LOC / 4;
     Arena ar = arena(ws, ws_bytes);
     hipStream_t st = S(stream);
+    sf::proj_text_slots_warm();       // (launch (1)'s group rule reads the device once, here: never inside a capture)
     // the folds transposed to the [N, K] layout of the products below, the constant as row H, zero rows up to ld:
     //   wt_v [ld, F]     = [M_v^T ; c_v ; 0]
     //   wt_a [ld, F + 4] = [M_a^T ; c_a ; 0]   (column F of M_a^T is m, c_a[F] is c0: sf_decoder_fold_build)

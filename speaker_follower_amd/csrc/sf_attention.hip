@@ -1,5 +1,6 @@
 // The three soft attentions of the speaker/follower path, forward and backward.
 // One workgroup per sample, row set resident in registers (see sf_rows.h).
+#include <atomic>
 #include "sf_kernels.h"
 #include "sf_rows.h"
 #include "sf_glue.h"
@@ -1189,7 +1190,7 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_proj_score_kernel(ProjS
 // (m, l, unnormalised z); the last arriver of a sample merges them in the same launch (measured, round 6: two groups
 // merged by the consumer's prologue: stage 10.3 us + consumer 9.4 us; four groups merged here: 10.9 + 7.4).
 // =================================================================================================
-constexpr int TXF_G = 4;          // workgroups per sample (fixed: the per-sample ticket arithmetic counts in fours)
+constexpr int TXF_G = 4;          // workgroups per sample; tickets a LAUNCH adds per sample (the tickets count in fours)
 
 struct TxtFoldArgs {
     const float* ctx_q;    // [B, L, H]
@@ -1198,7 +1199,7 @@ struct TxtFoldArgs {
     int L, H;
     const float* vec;      // h1 as the text attention sees it (eval: h1 itself) [B, ldvec]
     int ldvec;
-    float* part;           // [B][TXF_G][H + 64]: z | e[l - g Lg] (<= 62) | m at H + 62 | l at H + 63
+    float* part;           // [B][G][H + 64], G <= TXF_G: z | e[l - g Lg] (<= 62) | m at H + 62 | l at H + 63
     unsigned* counter;     // [B] monotonic tickets (zero before the first launch; every launch adds TXF_G per sample)
     float* z;              // out [B, ldz]: sum_l alpha_l ctx_o[l] (merged, normalised)
     int ldz;
@@ -1208,11 +1209,16 @@ struct TxtFoldArgs {
 // One group's share -- positions [g LG, (g + 1) LG) of sample b: scores, local softmax piece (m, l, e), unnormalised
 // z = sum e_l ctx_o[l] -- published WRITE-THROUGH like the split visual attention's partials (visual_split_body<0>:
 // sc1 stores, drain, agent-scope ticket; no cache-wide fence), and the workgroup that draws the sample's LAST ticket
-// merges the TXF_G pieces (sc1 loads) into z [H] and alpha [L]: no spinning, no extra launch.
-template <int RPW>
+// merges the G pieces (sc1 loads) into z [H] and alpha [L]: no spinning, no extra launch.
+// G is the group count of the launch: TXF_G everywhere but in launch (1) of the projected chain at a batch whose
+// four-group grid does not fit the device at once (proj_text_groups_plan).  The tickets stay aligned whatever launches
+// share a workspace: a block adds TXF_G / G, so EVERY launch adds TXF_G per sample and the last arriver is the one that
+// reads TXF_G - TXF_G / G in the low bits.  The records are [B][G][H + 64] in a scratch sized for TXF_G.
+template <int RPW, int G>
 __device__ __forceinline__ void text_fold_body(const TxtFoldArgs& a, int g, int b) {
     constexpr int NW = SMALL_WAVES, SL = 4, LG = NW * RPW;
     static_assert(LG <= 62, "a group's weights live in 62 record slots");
+    static_assert(G >= 1 && G <= TXF_G && TXF_G % G == 0, "a launch adds TXF_G tickets per sample; the scratch holds TXF_G");
     typedef unsigned v4u __attribute__((ext_vector_type(4)));
     __shared__ float4 slots[SL][TXT_CPL * 64];
     __shared__ float s_score[LG];
@@ -1280,7 +1286,7 @@ __device__ __forceinline__ void text_fold_body(const TxtFoldArgs& a, int g, int 
         for (int i = 0; i < TXT_CPL; ++i) f4fma(p[i], er, xo[r][i]);
     }
     }   // !empty
-    float* r0 = a.part + (size_t)b * TXF_G * pstride;
+    float* r0 = a.part + (size_t)b * G * pstride;
     float* rec = r0 + (size_t)g * pstride;
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(rec, 0, pstride * 4, 0x00020000);
     block_row_sum<TXT_CPL, NW, SL>(p, slots, n4, [&](int c, float4 t) {
@@ -1297,44 +1303,44 @@ __device__ __forceinline__ void text_fold_body(const TxtFoldArgs& a, int g, int 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // EVERY storing wave drains
     __syncthreads();
     if (tid == 0)
-        s_last = (__hip_atomic_fetch_add(a.counter + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &
-                  (unsigned)(TXF_G - 1)) == (unsigned)(TXF_G - 1);
+        s_last = (__hip_atomic_fetch_add(a.counter + b, (unsigned)(TXF_G / G), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &
+                  (unsigned)(TXF_G - 1)) == (unsigned)(TXF_G - TXF_G / G);
     __syncthreads();
     if (!s_last) return;
 
     // ---- the sample's last arriver merges the pieces
     auto ldf = [&](float* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    float mg[TXF_G], kk[TXF_G];
+    float mg[G], kk[G];
     float M = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < TXF_G; ++k) {
+    for (int k = 0; k < G; ++k) {
         mg[k] = ldf(r0 + (size_t)k * pstride + H + 62);
         M = fmaxf(M, mg[k]);
     }
     float Lsum = 0.f;
 #pragma unroll
-    for (int k = 0; k < TXF_G; ++k) {
+    for (int k = 0; k < G; ++k) {
         kk[k] = mg[k] > -INFINITY ? expf(mg[k] - M) : 0.f;      // an empty group: weight 0 (its l is 0 too)
         Lsum = fmaf(ldf(r0 + (size_t)k * pstride + H + 63), kk[k], Lsum);
     }
     const float inv = 1.0f / Lsum;                              // (a sample always has an unmasked position)
 #pragma unroll
-    for (int k = 0; k < TXF_G; ++k) kk[k] *= inv;
+    for (int k = 0; k < G; ++k) kk[k] *= inv;
     if (a.alpha) {
         for (int l = tid; l < L; l += NW * 64) {
             const int gk = l / LG;
             float w = kk[0];
 #pragma unroll
-            for (int k = 1; k < TXF_G; ++k) w = gk == k ? kk[k] : w;
+            for (int k = 1; k < G; ++k) w = gk == k ? kk[k] : w;
             a.alpha[(size_t)b * L + l] = ldf(r0 + (size_t)gk * pstride + H + (l - gk * LG)) * w;
         }
     }
-    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(r0, 0, TXF_G * pstride * 4, 0x00020000);
+    const auto rs0 = __builtin_amdgcn_make_buffer_rsrc(r0, 0, G * pstride * 4, 0x00020000);
     float4* zrow = reinterpret_cast<float4*>(a.z + (size_t)b * a.ldz);
     for (int c = tid; c < n4; c += NW * 64) {
         float4 t = f4zero();
 #pragma unroll
-        for (int k = 0; k < TXF_G; ++k) {
+        for (int k = 0; k < G; ++k) {
             const v4u pk = __builtin_amdgcn_raw_buffer_load_b128(rs0, k * pstride * 4 + c * 16, 0, 16);
             t.x = fmaf(kk[k], __uint_as_float(pk.x), t.x);
             t.y = fmaf(kk[k], __uint_as_float(pk.y), t.y);
@@ -1351,7 +1357,7 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_textfold_small_small_ke
                                                                                     int gxa, int na, SmallArgs b, int gxb) {
     const int bid = blockIdx.x;
     if (bid < nt)
-        text_fold_body<RPW>(t, bid % TXF_G, bid / TXF_G);
+        text_fold_body<RPW, TXF_G>(t, bid % TXF_G, bid / TXF_G);
     else if (bid < nt + na)
         small_gemm_body<1, 4>(a, (bid - nt) % gxa, (bid - nt) / gxa);
     else
@@ -1364,7 +1370,7 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_textfold_small_wide_ker
                                                                                    int gxa, int na, SmallArgs b, int gxb) {
     const int bid = blockIdx.x;
     if (bid < nt)
-        text_fold_body<RPW>(t, bid % TXF_G, bid / TXF_G);
+        text_fold_body<RPW, TXF_G>(t, bid % TXF_G, bid / TXF_G);
     else if (bid < nt + na)
         small_gemm_body<1, 4>(a, (bid - nt) % gxa, (bid - nt) / gxa);
     else
@@ -1375,14 +1381,15 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_textfold_small_wide_ker
 // (the partials blocks pull the most bytes: first in the grid; proj_partials_body keeps the kernel within 128 registers,
 // two workgroups per CU).  VIS false: the instantiation without the partials body (nv == 0: an episode's last step, or
 // the partials ride in launch (2)) -- the text groups alone need far fewer registers and run three or more to a CU.
-template <int RPW, bool VIS>
+// G: text groups per sample (proj_text_groups_plan; last, so that the profile name still reads <RPW, true, ...>).
+template <int RPW, bool VIS, int G = TXF_G>
 __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_proj_textfold_kernel(VisArgs v, VisSplit sp, int nv, TxtFoldArgs t, int nt,
                                                                             SmallArgs a, int gxa) {
     const int bid = blockIdx.x;
     if (VIS && bid < nv) {
         proj_partials_body(v, sp, bid % PPB_G, bid / PPB_G);
     } else if (bid < nv + nt) {
-        text_fold_body<RPW>(t, (bid - nv) % TXF_G, (bid - nv) / TXF_G);
+        text_fold_body<RPW, G>(t, (bid - nv) % G, (bid - nv) / G);
     } else {
         small_gemm_body<1, 4>(a, (bid - nv - nt) % gxa, (bid - nv - nt) / gxa);
     }
@@ -1826,6 +1833,56 @@ int visual_attn_proj(const CandSrc& us, const PanoSrc& x, int B, int H, int L, c
     return launch_status();
 }
 
+// ---- text groups per sample of launch (1).  With the partials the kernel holds proj_partials_body's ~125 registers, two
+// workgroups per CU: at batch 100 the four-group grid (300 + 400 + 32 blocks) is 732 blocks on 512 resident slots, and the
+// text groups of the second round pay their load -> reduce -> ticket -> merge latency behind a first-round block, on the
+// chain cell -> text -> score -> next gate product.  TWO groups of 8 * RPW positions (RPW <= 5: L <= 80) make it 532.
+// The rule is a pure function of (B, L, device) -- a captured replay and an eager rollout of one shape choose alike:
+// two groups iff the partials ride in this launch, L <= 80, and the four-group grid exceeds the resident slots.
+// force (sf_debug_projected_text_groups): 0 the rule, 2 / 4 that count where it is legal.  na: blocks of the y product.
+int g_proj_text_groups = 0;
+constexpr int TXF_G2_MAX_L = 2 * SMALL_WAVES * 5;
+static_assert(TXF_G == 4, "pair_proj_textfold names its instantiations <R, true, 2> and <R, true, 4>");
+int proj_text_groups_plan(int B, int L, bool with_partials, int na, int slots, int force, int* grid) {
+    const int nv = with_partials ? PPB_G * B : 0;
+    const bool legal = with_partials && L <= TXF_G2_MAX_L;
+    const bool crowded = slots > 0 && nv + TXF_G * B + na > slots;
+    const int G = legal && (force == 2 || (force != TXF_G && crowded)) ? 2 : TXF_G;
+    if (grid) *grid = nv + G * B + na;
+    return G;
+}
+
+// resident workgroups of the four-group launch (1) with partials on the current device: CUs x what the runtime's
+// occupancy query gives pair_proj_textfold_kernel<R, true, TXF_G> (R: the four-group ladder's rung for L).  Asked once
+// per device and kept (sf_projected_build asks ahead of any capture: proj_text_slots_warm); 0 = unknown, four groups.
+static int text_rung(int L, int G) {
+    const int rpw = (L + G * SMALL_WAVES - 1) / (G * SMALL_WAVES);
+    return rpw <= 1 ? 0 : rpw <= 2 ? 1 : rpw <= 3 ? 2 : 3;
+}
+static int proj_text_slots(int rung) {
+    constexpr int kMaxDev = 64;
+    static std::atomic<int> cache[kMaxDev][4];                   // slots + 1 (0: not asked yet)
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (cache[dev][0].load(std::memory_order_acquire) == 0) {
+        int cus = 0, per[4] = {0, 0, 0, 0};
+        bool ok = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess;
+#define SF_OCC(i, R)                                                                                               \
+    ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per[i], pair_proj_textfold_kernel<R, true, TXF_G>,   \
+                                                            SMALL_WAVES * 64, 0) == hipSuccess
+        SF_OCC(0, 1); SF_OCC(1, 2); SF_OCC(2, 3); SF_OCC(3, 5);
+#undef SF_OCC
+        if (!ok) (void)hipGetLastError();
+        for (int r = 3; r >= 0; --r)                                 // (rung 0 last: it is the "asked" mark read above)
+            cache[dev][r].store((ok && cus > 0 && per[r] > 0 ? cus * per[r] : 0) + 1, std::memory_order_release);
+    }
+    return cache[dev][rung].load(std::memory_order_acquire) - 1;
+}
+void proj_text_slots_warm() { (void)proj_text_slots(0); }
+
 // launch (1): folded text attention (+ its in-launch merge)  ||  y  ||  projected partials of step t + 1 (`xn` null: none)
 int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* mask, int B, int L, int H, const float* vec,
                        int ldvec, float* part, unsigned* counter, float* z, int ldz, float* alpha, const SmallPlan& y,
@@ -1837,15 +1894,21 @@ int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* ma
     const TxtFoldArgs ta{ctx_q, ctx_o, mask, L, H, vec, ldvec, part, counter, z, ldz, alpha};
     const VisArgs va = xn ? proj_vis_args(*xn, pt, h1, ldh1, nullptr, nullptr, 0, Dropout{}, 0) : VisArgs{};
     const VisSplit sp{split_part, nullptr, g_trace};
-    const int nv = xn ? PPB_G * B : 0, nt = TXF_G * B, na = y.gx * y.gy;
-    const dim3 grid(nv + nt + na), block(SMALL_WAVES * 64);
-    const int rpw = (L + TXF_G * SMALL_WAVES - 1) / (TXF_G * SMALL_WAVES);
-#define SF_PPT(R)                                                                                                      \
-    do {                                                                                                               \
-        if (nv) SF_LAUNCH((pair_proj_textfold_kernel<R, true>), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx);  \
-        else SF_LAUNCH((pair_proj_textfold_kernel<R, false>), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx);    \
+    const int nv = xn ? PPB_G * B : 0, na = y.gx * y.gy;
+    const int force = g_proj_text_groups;
+    // (the slots are asked for only where the rule can say two: no runtime query on a path that never takes them)
+    const int slots = xn && L <= TXF_G2_MAX_L && force == 0 ? proj_text_slots(text_rung(L, TXF_G)) : 0;
+    int blocks = 0;
+    const int G = proj_text_groups_plan(B, L, xn != nullptr, na, slots, force, &blocks);
+    const int nt = G * B, rung = text_rung(L, G);
+    const dim3 grid(blocks), block(SMALL_WAVES * 64);
+#define SF_PPT(R)                                                                                                          \
+    do {                                                                                                                   \
+        if (nv && G == 2) SF_LAUNCH((pair_proj_textfold_kernel<R, true, 2>), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx); \
+        else if (nv) SF_LAUNCH((pair_proj_textfold_kernel<R, true, 4>), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx);      \
+        else SF_LAUNCH((pair_proj_textfold_kernel<R, false>), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx);        \
     } while (0)
-    if (rpw <= 1) SF_PPT(1); else if (rpw <= 2) SF_PPT(2); else if (rpw <= 3) SF_PPT(3); else SF_PPT(5);
+    if (rung == 0) SF_PPT(1); else if (rung == 1) SF_PPT(2); else if (rung == 2) SF_PPT(3); else SF_PPT(5);
 #undef SF_PPT
     return launch_status();
 }

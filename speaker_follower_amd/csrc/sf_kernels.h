@@ -253,6 +253,11 @@ int proj_attention_alone(const PanoSrc& x, int B, const ProjTables& pt, const fl
 int visual_attn_proj(const CandSrc& us, const PanoSrc& x, int B, int H, int L, const ProjTables& pt, const float* h, int ldh,
                      float* alpha, float* out, int ldo, const Dropout& drop, int drop_col0, float* split_part,
                      unsigned* counter, hipStream_t st);
+// text groups per sample of launch (1) and its grid (sf_attention.hip; the launcher's own rule, callable without a device):
+// na = blocks of the y product, slots = resident workgroups of the four-group launch (0: unknown), force = 0 / 2 / 4
+extern int g_proj_text_groups;        // sf_debug_projected_text_groups (default 0: the rule)
+int proj_text_groups_plan(int B, int L, bool with_partials, int na, int slots, int force, int* grid);
+void proj_text_slots_warm();          // asks the device for `slots` once (ahead of any capture)
 int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* mask, int B, int L, int H, const float* vec,
                        int ldvec, float* part, unsigned* counter, float* z, int ldz, float* alpha, const SmallPlan& y,
                        const CandSrc& us, const PanoSrc* xn, const ProjTables& pt, const float* h1, int ldh1, float* split_part,

@@ -1,6 +1,8 @@
 """A/B of the projected decode chain on the headline batch (100 x 20 steps, hipGraph replay, ms per rollout), both
 chains in ONE process, interleaved: the four-launch folded chain (project = False), the projected chain with the attention
-partials in launch (1) (the default) and with the partials in launch (2) (sf_debug_projected_partials_late(1)).
+partials in launch (1) (the default) and with the partials in launch (2) (sf_debug_projected_partials_late(1)) -- and
+launch (1) with four text groups per sample forced (sf_debug_projected_text_groups(4)) against the library's rule
+(two groups where the four-group grid does not fit the device at once: this batch).
 Reports median / min / max over the rounds, the table build, and -- from one eager rollout each under the library's launch
 profile -- the per-kernel times of the decode step."""
 import os, sys, time, statistics
@@ -41,12 +43,14 @@ for label in ('first build (allocates 2 x %.2f GB)', 'rebuild in place'):
     print('projected tables, %-36s %.2f ms' % ((label % gb) if '%' in label else label, 1e3 * (time.perf_counter() - t0)), flush=True)
     runtime.invalidate_caches()
 
-LEGS = (('folded, four launches (project = False)', False, 0),
-        ('projected, partials in launch (2)', True, 1),
-        ('projected, partials in launch (1) [default]', True, 0))
+LEGS = (('folded, four launches (project = False)', False, 0, 0),
+        ('projected, partials in launch (2)', True, 1, 0),
+        ('projected, partials in (1), four text groups', True, 0, 4),
+        ('projected, partials in (1), rule [default]', True, 0, 0))
 runs = {}
-for name, project, late in LEGS:
+for name, project, late, groups in LEGS:
     _lib.lib.sf_debug_projected_partials_late(late)
+    _lib.lib.sf_debug_projected_text_groups(groups)
     eng = follower.FollowerEngine(enc, dec, store)
     eng.project = project
     replay, st = eng.capture(batch, 20, 'argmax')
@@ -55,11 +59,12 @@ for name, project, late in LEGS:
     torch.cuda.synchronize()
     runs[name] = (replay, st, st.actions.clone(), st.logits.clone(), [])
 _lib.lib.sf_debug_projected_partials_late(DEFAULT_LATE)
+_lib.lib.sf_debug_projected_text_groups(0)
 for _ in range(ROUNDS):                      # interleaved: a drift of the box hits every leg alike
-    for name, _, _ in LEGS:
+    for name, _, _, _ in LEGS:
         runs[name][4].append(timed(runs[name][0]))
 base = runs[LEGS[0][0]]
-for name, _, _ in LEGS:
+for name, _, _, _ in LEGS:
     ms = runs[name][4]
     fin = torch.isfinite(base[3])
     d = float((runs[name][3][fin] - base[3][fin]).abs().max())
@@ -70,8 +75,9 @@ for name, _, _ in LEGS:
              bool(torch.equal(runs[name][2], base[2])), d, scale, 3e-5 * scale), flush=True)
 
 # per-kernel times of one eager rollout per leg (the launches of the 20 decode steps and what surrounds them)
-for name, project, late in LEGS:
+for name, project, late, groups in LEGS:
     _lib.lib.sf_debug_projected_partials_late(late)
+    _lib.lib.sf_debug_projected_text_groups(groups)
     eng = follower.FollowerEngine(enc, dec, store)
     eng.project = project
     with torch.no_grad():
@@ -86,3 +92,4 @@ for name, project, late in LEGS:
         if r['calls'] >= 19:
             print('    %-86s %3d x %6.2f us (min %.2f, max %.2f)' % (k[:86], r['calls'], r['avg_us'], r['min_us'], r['max_us']))
 _lib.lib.sf_debug_projected_partials_late(DEFAULT_LATE)
+_lib.lib.sf_debug_projected_text_groups(0)
