@@ -1224,6 +1224,71 @@ typedef struct sf_fol_beam {
 int sf_follower_beam_select(const sf_fol_beam* s, const int32_t* top_a, const float* top_lp, const float* alpha,
                             sf_stream stream);
 
+/* One iteration of the state-factored search's bookkeeping (follower.py:783-905; sim/frontier_core.cpp: advance_raw +
+ * fill_inputs_raw) for all instances, all state in device memory: what search.DeviceStateFactored issues after
+ * sf_attn_decoder_fwd + sf_logprob_topk (column order, k = A) + the scatter of the new states' rows, in its device
+ * iteration loop (additive to ABI 9).  A hypothesis ("node") of instance b is row b * node_cap + local of the node
+ * arrays, local = 0 (the root), 1, .. in the order the instance creates them: ids do not depend on scheduling.
+ *   status      [8] int32: [0] frontier size N, [1] base = pool row of frontier column 0, [2] iterations done, [3] the
+ *               overflow flags (SF_SEARCH_OVF_*), rest reserved.  A call with N == 0 or a flag set changes nothing.
+ *   inst        [B,8] per instance: number of nodes, of "open" slots, of "held" slots, of completed end states, of
+ *               visits, of its frontier columns, the first of its frontier columns (columns are compact and
+ *               instance-major: the prefix sum of the counts), the overflow flags it raised.
+ *   frontier    [B, successor_size]: the instance's frontier nodes, column order.
+ *   dictionaries "open" (states to expand) and "held" (finished hypotheses waiting their turn), each a dense
+ *               [B, n_keys] key -> slot table (-1: none) plus slot-ordered key / node / pick [B, slot_cap]; slots are
+ *               handed out in insertion order; pick = the entry's score while it waits, -inf once expanded.
+ *   successors  of instance b's frontier columns r (node f, state st = node_sid[f]) and actions a < a_num[st]:
+ *               score = node_score[f] + logp[(first + r) * ld_logp + a] (float32 add), in descending score, ties in
+ *               generation order (r, then a); nxt = next_row[st, a]; the state stays st when a == 0 or nxt == st / V,
+ *               else becomes nxt * V + cand_view[st, a]; key = the parent's when it stays, else key_of (key_fields 4:
+ *               local_row * V + view; 3: local_row * 12 + view % 12; 2: local_row; 1: 0; local_row = row - base_row[b]);
+ *               final = a == 0 or count == episode_len.  Per (key, final) only the first successor in that order may
+ *               enter, and does when its dictionary (held if final, else open) holds nothing for the key or a node of
+ *               strictly smaller score: a new node (parent f, born = iterations done + 1, pool = base + first + r,
+ *               start_pose = the parent's and it stays) replaces / takes the next slot, in that order.
+ *   picks       successor_size rounds of first-maximum of pick over open and held (held only when strictly greater;
+ *               nothing above -inf: the rounds end); a pick's entry gets pick = -inf.  Held picks complete their key:
+ *               comp_node[b, key] = the node (kept if one of no smaller score is there), a first completion appends
+ *               the key to comp_order [B, completion_size + successor_size].  Open picks of an instance still below
+ *               completion_size form its next frontier and are appended to visits [B, visit_cap].  An instance that
+ *               has its completions does nothing.
+ *   pack        (second launch, one workgroup) base += N; the counts' prefix sum; dev_in [8, cap] int32 = what
+ *               fill_inputs_raw writes for the new frontier: rows nav row, parent's nav row, view, parent's view,
+ *               action (0 for a root), pool row, instance, base + column; columns beyond the frontier repeat column 0
+ *               with destination -1; an empty frontier pads with instance 0's root and destination -1.
+ *   overflow    a capacity that does not hold what an iteration adds (node_cap, slot_cap, visit_cap, a key outside
+ *               [0, n_keys), base + N > pool_rows): the flag is set, the frontier emptied (N = 0, padding columns),
+ *               nothing is written past a bound; the tables of that search are then unspecified.
+ * No workgroup waits for another; every loop is bounded by a capacity.
+ * SF_ERR_ARG on NULL pointers, non-positive sizes, key_fields outside 1..4, cap < B * successor_size,
+ * ld_logp < nav.A, B * node_cap >= 2^31; SF_ERR_UNSUPPORTED for successor_size * nav.A > 1024 (the successors of an
+ * instance are ranked in one workgroup's LDS), successor_size > 64 or B > 256 (one lane per instance in the pack). */
+enum {
+    SF_SEARCH_OVF_NODES = 1, SF_SEARCH_OVF_SLOTS = 2, SF_SEARCH_OVF_VISITS = 4, SF_SEARCH_OVF_POOL = 8,
+    SF_SEARCH_OVF_KEY = 16
+};
+typedef struct sf_state_search {
+    int32_t B, successor_size, completion_size, episode_len, key_fields, n_keys;
+    int32_t node_cap, slot_cap, visit_cap, cap, pool_rows, reserved;
+    sf_nav_table nav;          /* a_num, next_row, cand_view, A, V are read */
+    const int32_t* base_row;   /* [B] first nav row of the instance's scan */
+    int32_t* status;           /* [8] */
+    int32_t* inst;             /* [B,8] */
+    int32_t* frontier;         /* [B, successor_size] */
+    int32_t *node_parent, *node_sid, *node_key, *node_action, *node_count, *node_pool, *node_start, *node_born;
+    float* node_score;         /* node arrays: [B, node_cap] */
+    int32_t *open_slot, *open_key, *open_node;
+    float* open_pick;
+    int32_t *held_slot, *held_key, *held_node;
+    float* held_pick;
+    int32_t* comp_node;        /* [B, n_keys], -1: not completed */
+    int32_t* comp_order;       /* [B, completion_size + successor_size] */
+    int32_t* visits;           /* [B, visit_cap] */
+} sf_state_search;
+int sf_state_factored_select(const sf_state_search* s, const float* logp, int ld_logp, int32_t* dev_in,
+                             sf_stream stream);
+
 /* In-process kernel timing (no reference counterpart; what bench.py's `roofline.kernels` table is
  * measured with).  Between sf_profile_begin() and sf_profile_end() every kernel ANY host thread of the
  * process launches through this library (torch runs backward() on its own thread) carries a start and a stop event on its own dispatch, so a

@@ -168,6 +168,19 @@ class FolBeam(C.Structure):
                                     'hist_action', 'hist_rank', 'hist_sid', 'hist_psid', 'hist_score', 'hist_attn')] +
                 [('ld_hist', C.c_int64), ('done_rec', c_p), ('done_score', c_p)])
 
+
+class StateSearch(C.Structure):
+    """sf_state_search: the tables of the state-factored search's device loop (sf_state_factored_select)."""
+    SIZES = ('B', 'successor_size', 'completion_size', 'episode_len', 'key_fields', 'n_keys', 'node_cap', 'slot_cap',
+             'visit_cap', 'cap', 'pool_rows', 'reserved')
+    POINTERS = ('base_row', 'status', 'inst', 'frontier', 'node_parent', 'node_sid', 'node_key', 'node_action',
+                'node_count', 'node_pool', 'node_start', 'node_born', 'node_score', 'open_slot', 'open_key', 'open_node',
+                'open_pick', 'held_slot', 'held_key', 'held_node', 'held_pick', 'comp_node', 'comp_order', 'visits')
+    _fields_ = [(n, C.c_int32) for n in SIZES] + [('nav', NavTableS)] + [(n, c_p) for n in POINTERS]
+
+
+SEARCH_OVF_NODES, SEARCH_OVF_SLOTS, SEARCH_OVF_VISITS, SEARCH_OVF_POOL, SEARCH_OVF_KEY = 1, 2, 4, 8, 16
+
 i32, u32, i64p = C.c_int, C.c_uint32, C.c_void_p
 P = C.POINTER
 WS = [c_p, C.c_size_t, c_p]          # ws, ws_bytes, stream
@@ -288,6 +301,7 @@ _SIGNATURES = {
     'sf_logprob_topk': (C.c_int, [c_f, i32, i32, i32, c_p, i32, c_p, c_f, c_p]),
     'sf_speaker_beam_select': (C.c_int, [P(SpkBeam), c_p, c_f, c_f, c_p]),
     'sf_follower_beam_select': (C.c_int, [P(FolBeam), c_p, c_f, c_f, c_p]),
+    'sf_state_factored_select': (C.c_int, [P(StateSearch), c_f, i32, c_p, c_p]),
     'sf_speaker_decoder_fwd': (C.c_int, [P(SpkDecoderW), i32, i32, i32, i32, i32, i64p, c_f, c_f,
                                          c_f, c_p, c_p, P(SpkDecoderTape), P(Dropout), u32] + WS),
     'sf_speaker_decoder_bwd': (C.c_int, [P(SpkDecoderW), P(SpkDecoderG), i32, i32, i32, i32, i32, i64p,

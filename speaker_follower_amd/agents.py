@@ -374,6 +374,21 @@ class Seq2SeqAgent(BaseAgent):
         from . import search
         return search.beam_search(self, beam_size, load_next_minibatch, mask_undo)
 
+    # state_factored_search with its iteration loop on the device (search.DeviceStateFactored: the bookkeeping of
+    # sim/frontier_core.cpp in sf_state_factored_select, chunks of `search_chunk` iterations as replayed hipGraphs -- or
+    # issued eagerly with search_graphs = False --, one small status read per chunk).  Off by default.  Same results as the host loop, bit for bit (the decoder step sees
+    # the same rows in the same positions); inference only.  search_backend = 'numpy', a tie_log, a decoder without the
+    # visual attention, a shape beyond the kernel (search.DeviceStateFactored.supports) or a search that overflows
+    # `search_node_cap` nodes / `search_slot_cap` dictionary entries per instance runs the host loop from its start and
+    # counts a fallback.
+    search_on_device = False
+    search_chunk = 4
+    search_graphs = True
+    search_node_cap = 2048
+    search_slot_cap = 1024
+    search_fallbacks = 0
+    device_search = None
+
     def state_factored_search(self, completion_size, successor_size, load_next_minibatch=True,
                               mask_undo=False, first_n_ws_key=4):
         """follower.py:720-980."""

@@ -2302,6 +2302,23 @@ int sf_follower_beam_select(const sf_fol_beam* s, const int32_t* top_a, const fl
     SF_CHECK_ARG(s->ld_hist >= R && (!s->hist_attn || s->ld_hist >= R * s->T));
     return follower_beam_select(*s, top_a, top_lp, alpha, S(stream));
 }
+int sf_state_factored_select(const sf_state_search* s, const float* logp, int ld_logp, int32_t* dev_in,
+                             sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(s && logp && dev_in);
+    SF_CHECK_ARG(s->B > 0 && s->successor_size > 0 && s->completion_size > 0 && s->episode_len > 0 &&
+                 s->key_fields >= 1 && s->key_fields <= 4 && s->n_keys > 0 && s->node_cap > 0 && s->slot_cap > 0 &&
+                 s->visit_cap > 0 && s->pool_rows > 0);
+    SF_CHECK_ARG(s->nav.a_num && s->nav.next_row && s->nav.cand_view && s->nav.A > 0 && s->nav.V > 0 &&
+                 ld_logp >= s->nav.A);
+    SF_CHECK_ARG((int64_t)s->cap >= (int64_t)s->B * s->successor_size &&
+                 (int64_t)s->B * s->node_cap < ((int64_t)1 << 31) && (int64_t)s->B * s->n_keys < ((int64_t)1 << 40));
+    SF_CHECK_ARG(s->base_row && s->status && s->inst && s->frontier && s->node_parent && s->node_sid && s->node_key &&
+                 s->node_action && s->node_count && s->node_pool && s->node_start && s->node_born && s->node_score &&
+                 s->open_slot && s->open_key && s->open_node && s->open_pick && s->held_slot && s->held_key &&
+                 s->held_node && s->held_pick && s->comp_node && s->comp_order && s->visits);
+    return state_factored_select(*s, logp, ld_logp, dev_in, S(stream));
+}
 
 // ---- a9 SpeakerDecoderLSTM.forward (model.py:497-519) -----------------------------------------------------
 int sf_speaker_decoder_fwd(const sf_spk_decoder_w* w, int B, int E, int H, int Tp, int vocab,

@@ -257,7 +257,364 @@ __global__ __launch_bounds__(BEAM_WAVE) void follower_beam_select_kernel(sf_fol_
     }
 }
 
+// ---- the state-factored search (reference: Seq2SeqAgent.state_factored_search, tasks/R2R/follower.py:783-905;
+// sim/frontier_core.cpp: advance_raw + fill_inputs_raw; search.DeviceStateFactored), layout contract:
+// include/sf_hip.h, sf_state_factored_select.
+//
+// One workgroup per instance.  The instance's successors (frontier column r, action a: index g = r * A + a, the
+// generation order) sit in LDS; the reference's stable descending sort is a rank -- the number of successors that come
+// before g -- counted by g's own lane, and so are "first of its (key, final) group", the number of new nodes before a
+// new node and of new slots before a new slot: every lane decides for its own successors, nothing is ordered by
+// arrival.  Distinct groups touch distinct dictionary entries, so the entries are checked and replaced in parallel.
+constexpr int SFS_THREADS = 256;        // 4 wavefronts
+constexpr int SFS_MAX_SUCC = 1024;      // successor_size * A
+constexpr int SFS_MAX_S = 64;           // successor_size
+constexpr int SFS_MAX_B = SFS_THREADS;  // one lane per instance in the pack launch
+
+// ordering key of a score: a NaN sorts last, the order stays total
+__device__ __forceinline__ float sfs_ordkey(float x) { return x != x ? -INFINITY : x; }
+
+// First maximum above -inf over the workgroup: every lane brings the first maximum (v, i) of its own strided scan
+// (i = -1: none); every lane gets the greatest v, the lowest i among equals.  sv / si: 4 words of LDS each.
+__device__ __forceinline__ int sfs_first_max(float& v, int i, float* sv, int* si) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(v, off, 64);
+        const int oi = __shfl_xor(i, off, 64);
+        if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) {
+            v = ov;
+            i = oi;
+        }
+    }
+    __syncthreads();                                      // (the scratch words of the previous call have been read)
+    if ((threadIdx.x & 63) == 0) {
+        sv[threadIdx.x >> 6] = v;
+        si[threadIdx.x >> 6] = i;
+    }
+    __syncthreads();
+    v = sv[0];
+    i = si[0];
+#pragma unroll
+    for (int w = 1; w < SFS_THREADS / 64; ++w) {
+        const float ov = sv[w];
+        const int oi = si[w];
+        if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) {
+            v = ov;
+            i = oi;
+        }
+    }
+    return i;
+}
+
+__global__ __launch_bounds__(SFS_THREADS) void state_factored_select_kernel(sf_state_search s, const float* logp,
+                                                                            int ld) {
+    __shared__ float s_score[SFS_MAX_SUCC];
+    __shared__ int s_key[SFS_MAX_SUCC], s_nsid[SFS_MAX_SUCC], s_rank[SFS_MAX_SUCC], s_flag[SFS_MAX_SUCC];
+    __shared__ int s_win[SFS_MAX_SUCC], s_slot[SFS_MAX_SUCC];
+    __shared__ int s_f[SFS_MAX_S], s_fsid[SFS_MAX_S], s_fkey[SFS_MAX_S], s_fcount[SFS_MAX_S], s_fstart[SFS_MAX_S];
+    __shared__ int s_fna[SFS_MAX_S];
+    __shared__ float s_fscore[SFS_MAX_S];
+    __shared__ int s_cnt[4];                              // new nodes, new open slots, new held slots, bad key
+    __shared__ float s_rv[SFS_THREADS / 64];
+    __shared__ int s_ri[SFS_THREADS / 64];
+    __shared__ int s_pk[SFS_MAX_S], s_pn[SFS_MAX_S], s_ph[SFS_MAX_S];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (s.status[0] <= 0 || s.status[3] != 0) return;    // an empty frontier, or an overflow: no change
+    int32_t* in = s.inst + 8 * b;
+    int n_nodes = in[0], n_open = in[1], n_held = in[2];
+    const int n_comp = in[3], n_vis = in[4], first = in[6];
+    const int nf = min(max(in[5], 0), s.successor_size);
+    if (n_comp >= s.completion_size) return;             // it has its completions
+    const int A = s.nav.A, V = s.nav.V, S = s.successor_size, K = s.n_keys;
+    const int base = s.status[1], born = s.status[2] + 1;
+    const size_t kb = (size_t)b * K, sb = (size_t)b * s.slot_cap;
+    const int node0 = b * s.node_cap;
+
+    // ---- the frontier's nodes
+    if (tid < 4) s_cnt[tid] = 0;
+    if (tid < nf) {
+        const int f = s.frontier[b * S + tid];
+        const int sid = s.node_sid[f];
+        s_f[tid] = f;
+        s_fsid[tid] = sid;
+        s_fkey[tid] = s.node_key[f];
+        s_fcount[tid] = s.node_count[f];
+        s_fstart[tid] = s.node_start[f];
+        s_fscore[tid] = s.node_score[f];
+        s_fna[tid] = min(s.nav.a_num[sid], A);
+    }
+    __syncthreads();
+
+    // ---- successors in generation order
+    const int M = nf * A;
+    for (int g = tid; g < M; g += SFS_THREADS) {
+        const int r = g / A, a = g - r * A;
+        int flag = 0, key = 0, nsid = 0;
+        float score = 0.f;
+        if (a < s_fna[r]) {
+            const int st = s_fsid[r];
+            const int nxt = s.nav.next_row[(size_t)st * A + a];
+            const bool stay = a == 0 || nxt == st / V;                       // env.py:126-146
+            nsid = stay ? st : nxt * V + s.nav.cand_view[(size_t)st * A + a];
+            if (stay) {
+                key = s_fkey[r];
+            } else {                                                         // follower.py:722, 843: world_state[0:n]
+                const int local_row = nsid / V - s.base_row[b];
+                key = s.key_fields == 4 ? local_row * V + nsid % V
+                    : s.key_fields == 3 ? local_row * 12 + nsid % 12
+                    : s.key_fields == 2 ? local_row : 0;
+            }
+            const bool fin = a == 0 || s_fcount[r] + 1 == s.episode_len;
+            score = s_fscore[r] + logp[(size_t)(first + r) * ld + a];        // float32 add (follower.py:826)
+            flag = 1 | (fin ? 2 : 0) | (stay ? 4 : 0);
+            if (key < 0 || key >= K) atomicOr(&s_cnt[3], 1);
+        }
+        s_flag[g] = flag;
+        s_key[g] = key;
+        s_nsid[g] = nsid;
+        s_score[g] = score;
+    }
+    __syncthreads();
+    if (s_cnt[3]) {
+        if (tid == 0) in[7] |= SF_SEARCH_OVF_KEY;
+        return;
+    }
+
+    // ---- rank in the stable descending sort; is it the first of its (key, final) group
+    for (int g = tid; g < M; g += SFS_THREADS) {
+        const int fg = s_flag[g];
+        int rank = -1, win = 0;
+        if (fg & 1) {
+            const float kg = sfs_ordkey(s_score[g]);
+            const int key = s_key[g];
+            bool lead = true;
+            rank = 0;
+            for (int h = 0; h < M; ++h) {
+                const int fh = s_flag[h];
+                if (!(fh & 1)) continue;
+                const float kh = sfs_ordkey(s_score[h]);
+                if (kh > kg || (kh == kg && h < g)) {
+                    ++rank;
+                    if (s_key[h] == key && !((fh ^ fg) & 2)) lead = false;   // a better one came first
+                }
+            }
+            // ---- it enters if its dictionary holds nothing for the key, or a strictly smaller score
+            if (lead) {
+                const bool fin = fg & 2;
+                const int slot = (fin ? s.held_slot : s.open_slot)[kb + key];
+                s_slot[g] = slot;
+                if (slot < 0) {
+                    win = 2;
+                } else {
+                    const int cur = (fin ? s.held_node : s.open_node)[sb + slot];
+                    win = s.node_score[cur] < s_score[g] ? 1 : 0;
+                }
+                if (win) atomicAdd(&s_cnt[0], 1);
+                if (win == 2) atomicAdd(&s_cnt[fin ? 2 : 1], 1);
+            }
+        }
+        s_rank[g] = rank;
+        s_win[g] = win;
+    }
+    __syncthreads();
+    const int n_new = s_cnt[0], new_open = s_cnt[1], new_held = s_cnt[2];
+    {
+        int ovf = 0;
+        if (n_nodes + n_new > s.node_cap) ovf |= SF_SEARCH_OVF_NODES;
+        if (n_open + new_open > s.slot_cap || n_held + new_held > s.slot_cap) ovf |= SF_SEARCH_OVF_SLOTS;
+        if (ovf) {                                        // nothing of this iteration is written
+            if (tid == 0) in[7] |= ovf;
+            return;
+        }
+    }
+
+    // ---- the new nodes and their entries, numbered in processing order
+    for (int g = tid; g < M; g += SFS_THREADS) {
+        const int win = s_win[g];
+        if (!win) continue;
+        const int fg = s_flag[g], rank = s_rank[g];
+        const bool fin = fg & 2;
+        int before = 0, slots_before = 0;
+        for (int h = 0; h < M; ++h) {
+            const int wh = s_win[h];
+            if (wh && s_rank[h] < rank) {
+                ++before;
+                if (wh == 2 && !((s_flag[h] ^ fg) & 2)) ++slots_before;
+            }
+        }
+        const int r = g / A, a = g - r * A;
+        const int id = node0 + n_nodes + before;
+        s.node_parent[id] = s_f[r];
+        s.node_sid[id] = s_nsid[g];
+        s.node_key[id] = s_key[g];
+        s.node_action[id] = a;
+        s.node_count[id] = s_fcount[r] + 1;
+        s.node_pool[id] = base + first + r;
+        s.node_start[id] = (s_fstart[r] && (fg & 4)) ? 1 : 0;
+        s.node_born[id] = born;
+        s.node_score[id] = s_score[g];
+        int slot = s_slot[g];
+        if (win == 2) {
+            slot = (fin ? n_held : n_open) + slots_before;
+            (fin ? s.held_slot : s.open_slot)[kb + s_key[g]] = slot;
+            (fin ? s.held_key : s.open_key)[sb + slot] = s_key[g];
+        }
+        (fin ? s.held_node : s.open_node)[sb + slot] = id;
+        (fin ? s.held_pick : s.open_pick)[sb + slot] = s_score[g];
+    }
+    n_nodes += n_new;
+    n_open += new_open;
+    n_held += new_held;
+    __syncthreads();
+
+    // ---- the `successor_size` best entries not expanded yet (heapq.nlargest over chain(cache, holding),
+    // follower.py:861-865: equal scores go to the state to expand, then to the older entry)
+    int n_picks = 0;
+    for (; n_picks < S; ++n_picks) {
+        float mo = -INFINITY, mh = -INFINITY;
+        int ao = -1, ah = -1;
+        for (int i = tid; i < n_open; i += SFS_THREADS) {
+            const float p = s.open_pick[sb + i];
+            if (p > mo) {
+                mo = p;
+                ao = i;
+            }
+        }
+        for (int i = tid; i < n_held; i += SFS_THREADS) {
+            const float p = s.held_pick[sb + i];
+            if (p > mh) {
+                mh = p;
+                ah = i;
+            }
+        }
+        ao = sfs_first_max(mo, ao, s_rv, s_ri);
+        ah = sfs_first_max(mh, ah, s_rv, s_ri);
+        if (ao < 0 && ah < 0) break;
+        const bool use_h = ah >= 0 && (ao < 0 || mh > mo);
+        if (tid == 0) {
+            const int slot = use_h ? ah : ao;
+            (use_h ? s.held_pick : s.open_pick)[sb + slot] = -INFINITY;     // expanded
+            s_pk[n_picks] = (use_h ? s.held_key : s.open_key)[sb + slot];
+            s_pn[n_picks] = (use_h ? s.held_node : s.open_node)[sb + slot];
+            s_ph[n_picks] = use_h;
+        }
+        __syncthreads();
+    }
+
+    // ---- completions, the next frontier, the visits
+    if (tid == 0) {
+        int nc = n_comp, nv = n_vis, cnt = 0, ovf = 0;
+        const int comp_cap = s.completion_size + S;
+        for (int p = 0; p < n_picks; ++p) {
+            if (!s_ph[p]) continue;
+            const int key = s_pk[p], node = s_pn[p];
+            const int old = s.comp_node[kb + key];
+            if (old < 0) {
+                s.comp_node[kb + key] = node;
+                if (nc < comp_cap) s.comp_order[(size_t)b * comp_cap + nc] = key;
+                ++nc;
+            } else if (s.node_score[old] < s.node_score[node]) {
+                s.comp_node[kb + key] = node;
+            }
+        }
+        for (int p = 0; p < n_picks; ++p) {
+            if (s_ph[p] || nc >= s.completion_size) continue;
+            if (nv >= s.visit_cap) {
+                ovf = SF_SEARCH_OVF_VISITS;
+                break;
+            }
+            s.frontier[b * S + cnt++] = s_pn[p];
+            s.visits[(size_t)b * s.visit_cap + nv++] = s_pn[p];
+        }
+        in[0] = n_nodes;
+        in[1] = n_open;
+        in[2] = n_held;
+        in[3] = nc;
+        in[4] = nv;
+        in[5] = cnt;
+        if (ovf) in[7] |= ovf;
+    }
+}
+
+// Column i of the decoder step's [8, cap] input block for node f (frontier_core.cpp: fill_inputs_raw).
+__device__ __forceinline__ void sfs_write_column(const sf_state_search& s, int32_t* o, int i, int f, int dst) {
+    const int cap = s.cap, V = s.nav.V;
+    const int sid = s.node_sid[f], p = s.node_parent[f];
+    const int ps = p >= 0 ? s.node_sid[p] : sid;
+    o[0 * cap + i] = sid / V;
+    o[1 * cap + i] = ps / V;
+    o[2 * cap + i] = sid % V;
+    o[3 * cap + i] = ps % V;
+    o[4 * cap + i] = p >= 0 ? s.node_action[f] : 0;
+    o[5 * cap + i] = s.node_pool[f];
+    o[6 * cap + i] = f / s.node_cap;
+    o[7 * cap + i] = dst;
+}
+
+// The second launch: one workgroup, lane b = instance b.  Prefix sum of the instances' frontier counts, the overflow
+// flags, base, and the next input block.
+__global__ __launch_bounds__(SFS_THREADS) void state_factored_pack_kernel(sf_state_search s, int32_t* dev_in) {
+    __shared__ int s_sum[SFS_THREADS];
+    __shared__ int s_flags, s_head;
+    const int tid = threadIdx.x, B = s.B, S = s.successor_size;
+    const int n_old = s.status[0], base_old = s.status[1], iters = s.status[2];
+    if (n_old <= 0 || s.status[3] != 0) return;          // an empty frontier, or an overflow: no change
+    int cnt = 0, fl = 0;
+    if (tid < B) {
+        cnt = min(max(s.inst[8 * tid + 5], 0), S);
+        fl = s.inst[8 * tid + 7];
+    }
+    s_sum[tid] = cnt;
+    if (tid == 0) {
+        s_flags = 0;
+        s_head = 0;                                       // instance 0's root
+    }
+    __syncthreads();
+    if (fl) atomicOr(&s_flags, fl);
+    for (int d = 1; d < SFS_THREADS; d <<= 1) {
+        const int v = tid >= d ? s_sum[tid - d] : 0;
+        __syncthreads();
+        s_sum[tid] += v;
+        __syncthreads();
+    }
+    const int first = s_sum[tid] - cnt;
+    int N = s_sum[SFS_THREADS - 1];
+    const int base = base_old + n_old;
+    int flags = s_flags;
+    if (!flags && N > 0 && base + N > s.pool_rows) flags = SF_SEARCH_OVF_POOL;
+    if (flags) {                                          // the frontier is emptied
+        N = 0;
+        cnt = 0;
+    }
+    if (tid < B) {
+        s.inst[8 * tid + 5] = cnt;
+        s.inst[8 * tid + 6] = first;
+    }
+    if (cnt > 0 && first == 0) s_head = s.frontier[tid * S];                 // (one lane: the owner of column 0)
+    __syncthreads();
+    for (int j = 0; j < cnt; ++j) sfs_write_column(s, dev_in, first + j, s.frontier[tid * S + j], base + first + j);
+    const int head = s_head;
+    for (int i = N + tid; i < s.cap; i += SFS_THREADS) sfs_write_column(s, dev_in, i, head, -1);
+    if (tid == 0) {
+        s.status[0] = N;
+        s.status[1] = base;
+        s.status[2] = iters + 1;
+        s.status[3] = flags;
+    }
+}
+
 }  // namespace
+
+bool state_factored_select_supported(const sf_state_search& s) {
+    return (int64_t)s.successor_size * s.nav.A <= SFS_MAX_SUCC && s.successor_size <= SFS_MAX_S && s.B <= SFS_MAX_B;
+}
+
+int state_factored_select(const sf_state_search& s, const float* logp, int ld_logp, int32_t* dev_in, hipStream_t st) {
+    if (!state_factored_select_supported(s)) return SF_ERR_UNSUPPORTED;
+    SF_LAUNCH(state_factored_select_kernel, dim3(s.B), dim3(SFS_THREADS), 0, st, s, logp, ld_logp);
+    SF_LAUNCH(state_factored_pack_kernel, dim3(1), dim3(SFS_THREADS), 0, st, s, dev_in);
+    return launch_status();
+}
 
 int speaker_beam_select(const sf_spk_beam& s, const int32_t* top_w, const float* top_lp, const float* alpha,
                         hipStream_t st) {

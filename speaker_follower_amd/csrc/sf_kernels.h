@@ -204,6 +204,9 @@ int speaker_beam_select(const sf_spk_beam& s, const int32_t* top_w, const float*
 // the follower's (sf_follower_beam_select)
 int follower_beam_select(const sf_fol_beam& s, const int32_t* top_a, const float* top_lp, const float* alpha,
                          hipStream_t st);
+// one iteration of the state-factored search on the device (sf_state_factored_select): select, then pack
+int state_factored_select(const sf_state_search& s, const float* logp, int ld_logp, int32_t* dev_in, hipStream_t st);
+bool state_factored_select_supported(const sf_state_search& s);
 
 // paired launches (see sf_attention.hip); SF_ERR_UNSUPPORTED = not pairable, launch separately
 struct SmallPlan;

@@ -638,6 +638,14 @@ def state_factored_search(agent, completion_size, successor_size, load_next_mini
     mark('iterations')
     t = Hypotheses.from_arrays(*core.hypotheses())
     completed, visits = core.results()
+    return state_factored_outputs(agent, fd, t, space, completed, visits, mark)
+
+
+def state_factored_outputs(agent, fd, t, space, completed, visits, mark=lambda name: None):
+    """The results of the state-factored search (follower.py:907-980), shared by the host iteration loop above and the
+    device one (search.state_factored_search_device): the hypothesis table `t`, per instance its completed hypotheses
+    best first and the successively expanded ones followed by those.  fd: what answers `attention_rows(rows)` for the
+    `pool` rows of `t`."""
     # (results first: a candidates_hook issues device work the rest of this function then runs beside)
     trajs = _trajectories(fd, t, space, completed, agent.episode_len, getattr(agent, 'candidates_hook', None),
                           fp32_steps=True)
@@ -645,6 +653,42 @@ def state_factored_search(agent, completion_size, successor_size, load_next_mini
     traversed = _Walks(t, space, visits, agent.episode_len)
     mark('walks')
     return trajs, [HypList(t, space, lst) for lst in completed], traversed
+
+
+SEARCH_NODE_FIELDS = ('parent', 'sid', 'key', 'action', 'count', 'pool', 'start', 'born', 'score')
+
+
+def hypotheses_from_search_tables(tab, B, completion_size):
+    """The device iteration loop's tables (include/sf_hip.h: sf_state_factored_select; search.DeviceStateFactored.run)
+    as the host loop's hypothesis table, node for node.  tab: node_cap; inst [>= B, 8] (number of nodes, .., of
+    completed end states [3], of visits [4]); one [>= B, >= nodes] array per SEARCH_NODE_FIELDS (int32, score float32;
+    parents as device ids instance * node_cap + local); comp [>= B, ..] the completed nodes in the order their end
+    states were first completed; visits [>= B, ..].  The host loop numbers its nodes in creation order: the roots, then
+    iteration after iteration (`born`) the instances in turn, each instance's nodes in the order it made them (local).
+    Returns (Hypotheses, completed lists -- best first, stable, at most completion_size --, visits + completed)."""
+    node_cap = int(tab['node_cap'])
+    inst = np.asarray(tab['inst'])[:B]
+    local, owner = _ragged_arange(inst[:, 0].astype(np.int64))
+    order = np.lexsort((local, owner, tab['born'][owner, local]))
+    owner, local = owner[order], local[order]
+    new_of = np.full((B, max(int(inst[:, 0].max()), 1)), -1, np.int64)
+    new_of[owner, local] = np.arange(len(owner))
+
+    def renumber(ids):
+        ids = np.asarray(ids, np.int64)
+        return np.where(ids >= 0, new_of[np.maximum(ids, 0) // node_cap, np.maximum(ids, 0) % node_cap], -1)
+
+    col = {f: np.asarray(tab[f])[owner, local] for f in SEARCH_NODE_FIELDS}
+    t = Hypotheses.from_arrays(renumber(col['parent']), owner.astype(np.int64),
+                               *(col[f].astype(np.int64) for f in ('sid', 'key', 'action', 'count', 'pool')),
+                               col['score'].astype(F32), col['start'])
+    completed, visits = [], []
+    for b in range(B):
+        nodes = renumber(tab['comp'][b, :inst[b, 3]])
+        nodes = nodes[np.lexsort((np.arange(len(nodes)), -t.score[nodes]))][:completion_size].tolist()
+        completed.append(nodes)
+        visits.append(renumber(tab['visits'][b, :inst[b, 4]]).tolist() + nodes)
+    return t, completed, visits
 
 
 def _state_factored_search_numpy(agent, completion_size, successor_size, load_next_minibatch=True, mask_undo=False,

@@ -35,6 +35,7 @@ from . import _lib
 from ._lib import call
 from .features import cand_sincos
 from .follower import batch_instructions_from_encoded, EOS, BOS
+from .frontier import SEARCH_NODE_FIELDS
 from .model import decoder_params, decoder_w_struct, decoder_tape, tape_struct
 from .runtime import ptr, stream, ws_args, gc_paused, graph_capture, ensure_workspace, check_gate_weights, gate_weights_pass, register_bf16_weights, gate_mode_key
 
@@ -329,9 +330,15 @@ class GraphStep:
             self._capture()
 
     def _issue(self):
+        self.dev_in.copy_(self.pin_in, non_blocking=True)
+        self._chain()
+        self.pin_out.copy_(self.logp, non_blocking=True)
+
+    def _chain(self):
+        """The launches of one decoder step between the upload of the input block and the download of the
+        log-probabilities: `dev_in` -> `logp`, the new states' rows scattered to the pools."""
         st, nav, cap, A = self.store, self.nav, self.cap, self.A
         s = stream()
-        self.dev_in.copy_(self.pin_in, non_blocking=True)
         act, hrow, crow, dst = (self.dev_in[j] for j in range(4, 8))
         ns = nav.struct()
         # rows 0-1 of the block: nav rows of the states, then of their parents; rows 2-3 their views (fill_inputs)
@@ -359,7 +366,6 @@ class GraphStep:
                                    for src, pool, width in ((self.tape['h1'], self.hpool, H), (self.tape['c1'], self.cpool, H),
                                                             (self.tape['alpha'], self.apool, self.T))))
         call('sf_move_rows', sca, 3, cap, s)
-        self.pin_out.copy_(self.logp, non_blocking=True)
         self._keep = (ns, ucand, pano, cnd, w, tp, gat, sca)
 
     def _capture(self):
@@ -441,8 +447,10 @@ def _hip_entry_points():
     return _HIP_ENTRY[0]
 
 
-def graph_step_key(agent, nav, n_inst, cap, t_max, gate_weights):
-    return (id(agent.decoder), id(agent.store), id(nav), n_inst, cap, t_max) + gate_mode_key(gate_weights)
+def graph_step_key(agent, nav, n_inst, cap, t_max, gate_weights, device_loop=None):
+    """device_loop: the sizes of a DeviceStateFactored (its graphs hold other launches than the host loop's step)."""
+    key = (id(agent.decoder), id(agent.store), id(nav), n_inst, cap, t_max) + gate_mode_key(gate_weights)
+    return key if device_loop is None else key + ('device_loop',) + tuple(device_loop)
 
 
 def graph_step_for(agent, nav, n_inst, cap):
@@ -458,6 +466,270 @@ def graph_step_for(agent, nav, n_inst, cap):
         cache.clear()                                                # (one live configuration: the pools are ~100 MB)
         gs = cache[key] = GraphStep(agent.decoder, agent.store, nav, n_inst, cap, t_max, gate_weights=mode)
     return gs
+
+
+class DeviceStateFactored(GraphStep):
+    """The state-factored search (follower.py:720-980) with its iteration loop on the device: GraphStep's launch chain
+    without the upload of the input block and without the download of the log-probabilities, followed by
+    sf_state_factored_select (include/sf_hip.h) -- the bookkeeping of sim/frontier_core.cpp (advance_raw +
+    fill_inputs_raw) over tables in device memory, which leaves the next iteration's [8, cap] block in `dev_in`.
+
+    A chunk of `chunk` iterations is ONE replayed hipGraph (graphs = False: issued eagerly); the host reads the status
+    words and the per-instance counters once per chunk (`host_reads`) and the used part of the tables once at the end.
+    An iteration issued with an empty frontier changes nothing, so every chunk size gives the same tables.  A capacity
+    that does not hold a search (node_cap, slot_cap, the state pool) sets an overflow flag: `run` returns None and the
+    caller runs the host loop.  The graph is re-captured when a weight (or one of its cached layouts) moved or the pool
+    grew, as GraphStep's is.
+
+    Inference only; successor_size * A <= MAX_SUCC, successor_size <= MAX_S, instances <= MAX_B (the lane mapping of the
+    kernels) and a decoder with the visual attention."""
+    MAX_SUCC, MAX_S, MAX_B = 1024, 64, 256
+    NODE_FIELDS = SEARCH_NODE_FIELDS
+    SLOT_FIELDS = ('open_key', 'open_node', 'open_pick', 'held_key', 'held_node', 'held_pick')
+
+    def __init__(self, decoder, store, nav, n_inst, completion_size, successor_size, episode_len, key_fields, t_max,
+                 chunk=4, graphs=True, node_cap=2048, slot_cap=1024, pool_rows=1 << 14, gate_weights='fp32'):
+        if not self.supports(successor_size, n_inst, nav.A, decoder):
+            raise ValueError('DeviceStateFactored: %d instances x %d successors x %d candidates is beyond the kernel, or a '
+                             'decoder without visual attention' % (n_inst, successor_size, nav.A))
+        GraphStep.__init__(self, decoder, store, nav, n_inst, n_inst * successor_size, t_max, pool_rows, gate_weights)
+        self.completion, self.successor, self.E, self.key_fields = completion_size, successor_size, episode_len, key_fields
+        self.chunk, self.graphs = max(1, int(chunk)), bool(graphs)
+        self.node_cap, self.slot_cap, self.visit_cap = int(node_cap), int(slot_cap), int(node_cap)
+        # (a visit is a node of its own, so the visits fit whenever the nodes do)
+        self.comp_cap = completion_size + successor_size
+        per = {4: 36, 3: 12, 2: 1, 1: 0}[key_fields]
+        self.n_keys = K = max(nav.scan_rows.values()) * per + 2      # every minibatch's StateSpace.n_keys fits
+        B, S = n_inst, successor_size
+        segs = [('status', (8,)), ('inst', (B, 8)), ('frontier', (B, S)), ('base_row', (B,)),
+                ('comp_order', (B, self.comp_cap)), ('visits', (B, self.visit_cap)),
+                ('nodes', (len(self.NODE_FIELDS), B, self.node_cap)), ('slots', (len(self.SLOT_FIELDS), B, self.slot_cap)),
+                ('key_tables', (3, B, K))]
+        total = sum(int(np.prod(sh)) for _, sh in segs)
+        self.state = torch.zeros(total, device=self.dev, dtype=torch.int32)
+        self.seg, o = {}, 0
+        for name, sh in segs:
+            n = int(np.prod(sh))
+            self.seg[name] = self.state[o:o + n].view(*sh)
+            o += n
+        self.o_keys = total - 3 * B * K
+        self.n_head = 8 + 8 * B                                      # status + inst: what is read once per chunk
+        self.pin_head = torch.zeros(self.n_head, dtype=torch.int32).pin_memory()
+        self.captures = 0
+        self.host_reads = self.last_host_reads = 0
+        self.minibatches, self.last_run_s, self.last_iterations, self.last_flags = 0, 0.0, 0, 0
+        self.last = None                                    # what the last run returned
+
+    @classmethod
+    def supports(cls, successor_size, n_inst=1, A=1, decoder=None):
+        return (1 <= successor_size <= cls.MAX_S and successor_size * A <= cls.MAX_SUCC and 1 <= n_inst <= cls.MAX_B
+                and (decoder is None or hasattr(decoder, 'visual_attention_layer')))
+
+    def _struct(self):
+        g = self.seg
+        nodes = {f: g['nodes'][j] for j, f in enumerate(self.NODE_FIELDS)}
+        slots = {f: g['slots'][j] for j, f in enumerate(self.SLOT_FIELDS)}
+        open_slot, held_slot, comp_node = g['key_tables']
+        p = dict(base_row=g['base_row'], status=g['status'], inst=g['inst'], frontier=g['frontier'],
+                 open_slot=open_slot, held_slot=held_slot, comp_node=comp_node, comp_order=g['comp_order'],
+                 visits=g['visits'], **{'node_' + f: v for f, v in nodes.items()}, **slots)
+        return _lib.StateSearch(self.n_inst, self.successor, self.completion, self.E, self.key_fields, self.n_keys,
+                                self.node_cap, self.slot_cap, self.visit_cap, self.cap, self.pool_rows, 0,
+                                self.nav.struct(), *(p[n].data_ptr() for n in _lib.StateSearch.POINTERS))
+
+    def _issue_steps(self, n_steps):
+        s = stream()
+        ss = self._struct()
+        for _ in range(n_steps):
+            self._chain()
+            call('sf_state_factored_select', byref(ss), ptr(self.logp), self.A, ptr(self.dev_in), s)
+        self._keep_search = ss
+
+    def _capture(self):
+        # an empty frontier for the warm-up and the capture: the selection changes nothing, no pool row is written
+        self.state.zero_()
+        self.dev_in.zero_()
+        self.dev_in[7].fill_(-1)
+        side = torch.cuda.Stream(device=self.dev)
+        side.wait_stream(torch.cuda.current_stream())
+        graph = 'eager'
+        with torch.no_grad(), torch.cuda.stream(side):
+            self._issue_steps(1)                                     # warm-up: workspace, cached layouts
+            side.synchronize()
+            if self.graphs:
+                graph = torch.cuda.CUDAGraph()
+                with graph_capture(graph, side):
+                    self._issue_steps(self.chunk)
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph, self._stream = graph, side                       # (the graph bakes the capture stream's workspace)
+        self.baked = _baked_weights(self)
+        self.captures += 1
+
+    # ---- per search
+    def initial_tables(self, space):
+        """The search's start as one int32 vector (uploaded in one copy): the roots as node 0 of every instance, in
+        "open" with pick -inf, as the first visit and the first frontier; the first input block (fill_inputs_raw).
+        Instances beyond the minibatch have their completions from the start: they do nothing."""
+        Bn, S, nc = self.n_inst, self.successor, self.node_cap
+        B = len(space.items)
+        if B > Bn or space.n_keys > self.n_keys:
+            raise ValueError('DeviceStateFactored built for %d instances and %d state keys' % (Bn, self.n_keys))
+        base = self.n
+        sid, key = np.zeros(Bn, np.int64), np.zeros(Bn, np.int64)
+        sid[:B], key[:B] = space.root_sid, space.root_key
+        root = np.arange(Bn, dtype=np.int64) * nc
+        live = np.arange(Bn) < B
+        status = np.zeros(8, np.int64)
+        status[0], status[1] = B, base
+        inst = np.zeros((Bn, 8), np.int64)
+        inst[:, 0], inst[:, 1], inst[:, 4], inst[:, 5], inst[:, 6] = 1, 1, 1, live, np.arange(Bn)
+        inst[~live, 3] = self.completion
+        frontier = np.zeros((Bn, S), np.int64)
+        frontier[:, 0] = root
+        base_row = np.zeros(Bn, np.int64)
+        base_row[:B] = space.base_row
+        nodes = np.zeros((len(self.NODE_FIELDS), Bn), np.int64)      # parent sid key action count pool start born score
+        nodes[0], nodes[1], nodes[2], nodes[3], nodes[5], nodes[6] = -1, sid, key, -1, np.arange(Bn), 1
+        slots = np.zeros((len(self.SLOT_FIELDS), Bn), np.int64)      # open key node pick, held key node pick
+        slots[0], slots[1] = key, root
+        slots[2] = int(np.array(-np.inf, np.float32).view(np.int32))
+        block = np.zeros((8, self.cap), np.int64)
+        col = np.where(np.arange(self.cap) < B, np.arange(self.cap), 0)
+        s = sid[col]
+        block[0], block[1], block[2], block[3] = s // 36, s // 36, s % 36, s % 36
+        block[5], block[6] = col, col
+        block[7] = np.where(np.arange(self.cap) < B, base + np.arange(self.cap), -1)
+        parts = dict(head=np.concatenate((status, inst.reshape(-1), frontier.reshape(-1), base_row)), root=root,
+                     nodes=nodes.reshape(-1), slots=slots.reshape(-1), block=block.reshape(-1))
+        return parts, np.arange(Bn, dtype=np.int64) * self.n_keys + key
+
+    def _reset(self, space):
+        parts, key_at = self.initial_tables(space)
+        sizes = [len(v) for v in parts.values()]
+        up = torch.from_numpy(np.concatenate(list(parts.values())).astype(np.int32)).to(self.dev)
+        head, root, nodes, slots, block = torch.split(up, sizes)
+        Bn, g = self.n_inst, self.seg
+        self.state[:self.o_keys].zero_()
+        self.state[self.o_keys:].fill_(-1)
+        self.state[:len(head)].copy_(head)                           # status, inst, frontier, base_row
+        g['visits'][:, 0].copy_(root)
+        g['nodes'][:, :, 0].copy_(nodes.view(-1, Bn))
+        g['slots'][:, :, 0].copy_(slots.view(-1, Bn))
+        g['key_tables'][0].view(-1).index_fill_(0, torch.from_numpy(key_at).to(self.dev), 0)     # the roots' open slot
+        self.dev_in.copy_(block.view(8, self.cap))
+
+    def run(self, space):
+        """One search from the loaded encoder outputs (GraphStep.load) over the minibatch `space`.  Returns the tables
+        frontier.hypotheses_from_search_tables reads (host arrays), or None after an overflow flag (`last_flags`)."""
+        t0 = time.perf_counter()
+        B = len(space.items)
+        self._reset(space)
+        reads = 0
+        while True:
+            if self.graphs:
+                self.graph.replay()
+            else:
+                self._issue_steps(self.chunk)
+            self.pin_head.copy_(self.state[:self.n_head], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            reads += 1
+            n, base, iters, flags = (int(x) for x in self.pin_head[:4])
+            if n == 0 or flags:
+                break
+        self.last_iterations, self.last_flags = iters, flags
+        tab = None
+        if not flags:
+            inst = self.pin_head[8:].view(self.n_inst, 8).numpy().copy()
+            n_nodes, n_vis = max(int(inst[:B, 0].max()), 1), max(int(inst[:B, 4].max()), 1)
+            g = self.seg
+            comp = g['key_tables'][2].gather(1, g['comp_order'].clamp(0, self.n_keys - 1).to(torch.int64))
+            flat = torch.cat((g['nodes'][:, :B, :n_nodes].reshape(-1), comp[:B].reshape(-1),
+                              g['visits'][:B, :n_vis].reshape(-1))).cpu().numpy()      # the one download of the tables
+            reads += 1
+            nf = len(self.NODE_FIELDS)
+            o1 = nf * B * n_nodes
+            o2 = o1 + B * self.comp_cap
+            nodes = flat[:o1].reshape(nf, B, n_nodes)
+            tab = dict(node_cap=self.node_cap, inst=inst, comp=flat[o1:o2].reshape(B, self.comp_cap),
+                       visits=flat[o2:].reshape(B, n_vis), **{f: nodes[j] for j, f in enumerate(self.NODE_FIELDS)})
+            tab['score'] = nodes[nf - 1].view(np.float32)
+            self.n = base
+        self.last_host_reads = reads
+        self.host_reads += reads
+        self.minibatches += 1
+        self.last_run_s = time.perf_counter() - t0
+        self.last = tab
+        return tab
+
+
+def device_search_for(agent, nav, n_inst, completion_size, successor_size, key_fields, chunk=None, graphs=None):
+    """The agent's DeviceStateFactored for these sizes (buffers and captured graph; built on first use, kept on the
+    agent beside -- not among -- the host loop's graph_step_for steps)."""
+    t_max = agent.max_instruction_length
+    mode = getattr(agent, 'gate_weights', 'fp32')
+    chunk = agent.search_chunk if chunk is None else chunk
+    graphs = getattr(agent, 'search_graphs', True) if graphs is None else graphs
+    sizes = (completion_size, successor_size, agent.episode_len, key_fields, int(chunk), bool(graphs),
+             int(agent.search_node_cap), int(agent.search_slot_cap))
+    key = graph_step_key(agent, nav, n_inst, n_inst * successor_size, t_max, mode, device_loop=sizes)
+    cache = agent.__dict__.setdefault('_device_searches', {})
+    ds = cache.get(key)
+    if ds is None or ds.dec is not agent.decoder or ds.store is not agent.store or ds.nav is not nav:
+        cache.clear()                                                # (one live configuration: the pools are ~100 MB)
+        ds = cache[key] = DeviceStateFactored(agent.decoder, agent.store, nav, n_inst, completion_size, successor_size,
+                                              agent.episode_len, key_fields, t_max, chunk, graphs,
+                                              node_cap=agent.search_node_cap, slot_cap=agent.search_slot_cap,
+                                              gate_weights=mode)
+    return ds
+
+
+@gc_paused
+def state_factored_search_device(agent, completion_size, successor_size, load_next_minibatch=True, mask_undo=False,
+                                 first_n_ws_key=4):
+    """Seq2SeqAgent.state_factored_search (follower.py:720-980) through DeviceStateFactored: what
+    frontier.state_factored_search returns, assembled by the same code (frontier.state_factored_outputs) from the
+    hypothesis table rebuilt out of the device tables.  Returns None when a capacity overflowed (the minibatch is
+    loaded; the caller runs the host loop over it).  `agent.device_search` is the DeviceStateFactored used last.
+    mask_undo is accepted and ignored, as in the host loop."""
+    from . import frontier, nav
+    env = agent.env
+    _require_store(agent)
+    env.reset(sort=True, beamed=True, load_next_minibatch=load_next_minibatch)
+    assert env.beam_size >= successor_size
+    items = list(env.batch)
+    table = nav.table_for(env, agent.store)
+    space = frontier.StateSpace(env, table, items, first_n_ws_key)
+    ctx, seq_mask, h_t, c_t = _encode_items(agent, items)
+    n_inst = getattr(env, 'batch_size', None) or len(items)
+    with torch.no_grad():
+        ds = device_search_for(agent, table, n_inst, completion_size, successor_size, first_n_ws_key)
+        agent.device_search = ds
+        ds.load(ctx, seq_mask, h_t, c_t)
+        tab = ds.run(space)
+        if tab is None:
+            if ds.last_flags & _lib.SEARCH_OVF_POOL:                 # the next minibatch finds a larger pool
+                ds._grow(2 * ds.pool_rows)
+            return None
+    t, completed, visits = frontier.hypotheses_from_search_tables(tab, len(items), completion_size)
+    return frontier.state_factored_outputs(agent, ds, t, space, completed, visits)
+
+
+def _search_shape(agent):
+    """(instances per minibatch, widest candidate list) of the agent's searches, for DeviceStateFactored.supports."""
+    from . import nav
+    env = agent.env
+    return getattr(env, 'batch_size', None) or len(env.batch), nav.table_for(env, agent.store).A
+
+
+def device_search_applies(agent, successor_size):
+    """Whether state_factored_search runs the device loop for this agent (Seq2SeqAgent.search_on_device is on): the
+    native backend, no tie_log, a decoder with the visual attention, a shape the kernel takes."""
+    if getattr(agent, 'search_backend', 'native') == 'numpy' or getattr(agent, 'tie_log', None) is not None:
+        return False
+    if not hasattr(agent.decoder, 'visual_attention_layer') or getattr(agent, 'store', None) is None:
+        return False
+    n_inst, A = _search_shape(agent)
+    return DeviceStateFactored.supports(successor_size, n_inst, A, agent.decoder)
 
 
 def _require_store(agent):
@@ -1047,8 +1319,19 @@ def beam_search(agent, beam_size, load_next_minibatch=True, mask_undo=False):
 
 def state_factored_search(agent, completion_size, successor_size, load_next_minibatch=True,
                           mask_undo=False, first_n_ws_key=4):
-    """follower.py:720-980.  Returns (trajs, completed_list, traversed_lists)."""
+    """follower.py:720-980.  Returns (trajs, completed_list, traversed_lists).  With `agent.search_on_device` the
+    iteration loop runs on the device (state_factored_search_device); a search it does not take (the numpy backend, a
+    tie_log, a decoder or shape the kernel does not cover) or that overflowed one of its capacities runs the host loop
+    from its start and is counted in `agent.search_fallbacks`."""
     from . import frontier
+    if getattr(agent, 'search_on_device', False):
+        if device_search_applies(agent, successor_size):
+            out = state_factored_search_device(agent, completion_size, successor_size, load_next_minibatch, mask_undo,
+                                               first_n_ws_key)
+            if out is not None:
+                return out
+            load_next_minibatch = False                              # (the minibatch is loaded: the host loop re-reads it)
+        agent.search_fallbacks += 1
     return frontier.state_factored_search(agent, completion_size, successor_size, load_next_minibatch, mask_undo,
                                           first_n_ws_key)
 
