@@ -9,6 +9,11 @@
 // sf_logprob_topk already in descending order (ties: lower column first), so slot i's candidates
 // score[i] + lp[i, j] are sorted by (score desc, flat index i*k+j asc) and the beam_size best of the instance are
 // a merge of at most 64 sorted lists: beam_size rounds of a wave-wide arg-max over the list heads.
+//
+// Both kernels are the same four stages -- beam_merge, beam_place, beam_copy_attention, beam_close -- around what is
+// their own: what ends a successor list, what a selection carries (a word; an action and the state it leads to) and
+// which slot arrays the next step reads.  A stage takes the kernel's struct as a template parameter where it touches
+// the fields sf_spk_beam and sf_fol_beam share by name.
 #include "sf_kernels.h"
 
 namespace sf {
@@ -22,145 +27,25 @@ __device__ __forceinline__ bool beam_before(float os, int of, float bs, int bf) 
     return os > bs || (os == bs && of < bf);
 }
 
-__global__ __launch_bounds__(BEAM_WAVE) void speaker_beam_select_kernel(sf_spk_beam s, const int32_t* top_w,
-                                                                        const float* top_lp, const float* alpha) {
-    __shared__ int s_row[BEAM_WAVE], s_word[BEAM_WAVE];
-    __shared__ float s_score[BEAM_WAVE];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int W = s.beam_size, k = s.k, R = s.B * W, base = b * W;
-    int32_t* inst = s.inst + 3 * b;
-    const int live = inst[0], n_done = inst[1], t = inst[2];
-    if (live <= 0 || t >= s.T) return;                  // ended instance (or steps issued past the end): no change
-    const size_t hist = (size_t)t * (size_t)s.ld_hist;
-
-    // ---- selection: merge of the live slots' sorted successor lists
-    const int32_t* my_w = top_w + (size_t)(base + lane) * k;
-    const float* my_lp = top_lp + (size_t)(base + lane) * k;
-    const float my_score = lane < live ? s.score[base + lane] : 0.f;
+// The merge of the live slots' sorted successor lists.  my_score / my_lp: this lane's hypothesis score and its k
+// log-probabilities; valid(j): rank j is a successor (a list ends at the first rank that is none).  Leaves (slot inside
+// the instance, rank, score) of selection q in s_row / s_rank / s_score [q] and returns the number of selections, after
+// a barrier: every global read the caller made before the call happened before any write it makes after it.
+template <class Valid>
+__device__ __forceinline__ int beam_merge(int lane, int live, int W, int k, float my_score, const float* my_lp,
+                                          Valid valid, int* s_row, int* s_rank, float* s_score) {
     int j = 0;
-    float head = -INFINITY;                               // the head's score (float32 add, as speaker.py:277)
-    int head_flat = 0x7fffffff;
-    if (lane < live) {
-        head = my_score + my_lp[0];
-        head_flat = lane * k;
-    }
-    int nsel = 0;
-    for (; nsel < W; ++nsel) {
-        float bs = fmaxf(head, -INFINITY);                // (ordering key: a NaN sorts last, the order stays total)
-        int bf = head_flat;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float os = __shfl_xor(bs, off, BEAM_WAVE);
-            const int of = __shfl_xor(bf, off, BEAM_WAVE);
-            if (beam_before(os, of, bs, bf)) {
-                bs = os;
-                bf = of;
-            }
+    float head;                                           // the head's score (one float32 add, as the reference's)
+    int head_flat;
+    auto load_head = [&] {
+        head = -INFINITY;
+        head_flat = 0x7fffffff;
+        if (lane < live && j < k && valid(j)) {
+            head = my_score + my_lp[j];
+            head_flat = lane * k + j;
         }
-        if (bf == 0x7fffffff) break;                      // every list is exhausted (live * k < beam_size)
-        if (bf == head_flat) {                            // this lane's head won: record it, advance the list
-            s_row[nsel] = lane;
-            s_word[nsel] = my_w[j];
-            s_score[nsel] = head;
-            ++j;
-            if (j < k) {
-                head = my_score + my_lp[j];
-                head_flat = lane * k + j;
-            } else {
-                head = -INFINITY;
-                head_flat = 0x7fffffff;
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- finals (EOS or the last word step) after the continuing hypotheses, both in selection order
-    const bool sel = lane < nsel;
-    const int word = sel ? s_word[lane] : 0;
-    const bool fin = sel && (word == s.eos || t == s.T - 1);
-    const unsigned long long m_fin = __ballot(fin), m_cont = __ballot(sel && !fin);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const int n_fin = __popcll(m_fin), n_cont = __popcll(m_cont);
-    const int pos = fin ? n_cont + __popcll(m_fin & below) : __popcll(m_cont & below);
-    const int done_after = n_done + n_fin;
-    const int live_next = done_after >= W ? 0 : n_cont;  // speaker.py:281-290: a full completion list stops the path
-    if (sel) {
-        const int h = base + pos;
-        s.hist_word[hist + h] = word;
-        s.hist_parent[hist + h] = base + s_row[lane];
-        s.hist_score[hist + h] = s_score[lane];
-        if (fin) {
-            const int d = b * 2 * W + n_done + __popcll(m_fin & below);     // n_done < W, n_fin <= W
-            s.done_rec[d] = t * R + h;
-            s.done_score[d] = s_score[lane];
-        }
-    }
-    // the attention rows of this step's live slots (the alpha of the step that chose the new words)
-    if (s.hist_attn) {
-        const int Tp = s.Tp;
-        for (int e = lane; e < live * Tp; e += BEAM_WAVE) {
-            const int r = e / Tp, c = e - r * Tp;
-            s.hist_attn[hist + (size_t)(base + r) * Tp + c] = alpha[(size_t)(base + r) * Tp + c];
-        }
-    }
-
-    // ---- the next step's slots: continuing hypotheses compacted to the front in selection order, the rest dead
-    // (slot p of the next step is history position base + p of this step: the backchain needs no other map)
-    if (sel && !fin && live_next > 0) {
-        s.words[base + pos] = (int64_t)word;
-        s.parent[base + pos] = base + s_row[lane];
-        s.score[base + pos] = s_score[lane];
-    }
-    if (lane >= live_next && lane < W) {
-        s.words[base + lane] = (int64_t)s.eos;           // (a valid word id: dead slots are decoded and ignored)
-        s.parent[base + lane] = -1;                      // (zero h / c)
-        s.score[base + lane] = 0.f;
-    }
-    if (lane == 0) {
-        inst[0] = live_next;
-        inst[1] = done_after;
-        inst[2] = t + 1;
-        if (live_next > 0) atomicAdd(s.live_total + t, live_next);
-    }
-}
-
-// The follower's step.  A slot's state is (row, view) of the navigation table, sid = row * V + view; a successor list
-// ends at the first rank that is no candidate of the state (an action >= a_num -- sf_logprob_topk returns the masked
-// columns as (column, -inf) behind the valid ones -- or a negative action: the is_valid filter of follower.py:626), so
-// every list stays sorted and the merge above applies unchanged.
-__global__ __launch_bounds__(BEAM_WAVE) void follower_beam_select_kernel(sf_fol_beam s, const int32_t* top_a,
-                                                                         const float* top_lp, const float* alpha) {
-    __shared__ int s_row[BEAM_WAVE], s_act[BEAM_WAVE], s_sid[BEAM_WAVE];
-    __shared__ float s_score[BEAM_WAVE];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int W = s.beam_size, k = s.k, R = s.B * W, base = b * W;
-    const int A = s.nav.A, V = s.nav.V;
-    int32_t* inst = s.inst + 3 * b;
-    const int live = inst[0], n_done = inst[1], t = inst[2];
-    if (live <= 0 || t >= s.episode_len) return;        // ended instance (or steps issued past the end): no change
-    const size_t hist = (size_t)t * (size_t)s.ld_hist;
-
-    // ---- selection: merge of the live slots' sorted successor lists
-    const int32_t* my_a = top_a + (size_t)(base + lane) * k;
-    const float* my_lp = top_lp + (size_t)(base + lane) * k;
-    float my_score = 0.f;
-    int my_anum = 0;
-    if (lane < live) {
-        const int sid = s.row[base + lane] * V + s.view[base + lane];
-        s_sid[lane] = sid;
-        my_score = s.score[base + lane];
-        my_anum = s.nav.a_num[sid];
-    }
-    int j = 0;
-    float head = -INFINITY;                               // the head's score (float32 add, as follower.py:629)
-    int head_flat = 0x7fffffff, head_act = -1;
-    if (lane < live) {
-        head_act = my_a[0];
-        if (head_act >= 0 && head_act < my_anum) {
-            head = my_score + my_lp[0];
-            head_flat = lane * k;
-        }
-    }
+    };
+    load_head();
     int nsel = 0;
     for (; nsel < W; ++nsel) {
         float bs = fmaxf(head, -INFINITY);                // (ordering key: a NaN sorts last, the order stays total)
@@ -177,25 +62,144 @@ __global__ __launch_bounds__(BEAM_WAVE) void follower_beam_select_kernel(sf_fol_
         if (bf == 0x7fffffff) break;                      // every list is exhausted (fewer successors than beam_size)
         if (bf == head_flat) {                            // this lane's head won: record it, advance the list
             s_row[nsel] = lane;
-            s_act[nsel] = head_act;
+            s_rank[nsel] = j;
             s_score[nsel] = head;
             ++j;
-            head = -INFINITY;
-            head_flat = 0x7fffffff;
-            if (j < k) {
-                head_act = my_a[j];
-                if (head_act >= 0 && head_act < my_anum) {
-                    head = my_score + my_lp[j];
-                    head_flat = lane * k + j;
-                }
-            }
+            load_head();
         }
     }
     __syncthreads();
+    return nsel;
+}
 
-    // ---- successor states (StateSpace.successors) and finals (stop, or the last step), both in selection order
+// Where selection `lane` goes: the continuing hypotheses first, then the finals, both in selection order.
+struct BeamPlace {
+    int h;                                                // its history position (and, continuing, its next slot)
+    int done_after, live_next;                            // the instance's completions and live slots after the step
+};
+
+// `fin` implies `sel`.  Appends the finals to the instance's completion list (done_rec / done_score).
+template <class S>
+__device__ __forceinline__ BeamPlace beam_place(const S& s, int b, int lane, int t, int n_done, bool sel, bool fin,
+                                                float score) {
+    const int W = s.beam_size;
+    const unsigned long long m_fin = __ballot(fin), m_cont = __ballot(sel && !fin);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int n_fin = __popcll(m_fin), n_cont = __popcll(m_cont);
+    BeamPlace p;
+    p.h = b * W + (fin ? n_cont + __popcll(m_fin & below) : __popcll(m_cont & below));
+    p.done_after = n_done + n_fin;
+    p.live_next = p.done_after >= W ? 0 : n_cont;        // a full completion list stops the instance
+    if (fin) {
+        const int d = b * 2 * W + n_done + __popcll(m_fin & below);         // n_done < W, n_fin <= W
+        s.done_rec[d] = t * s.B * W + p.h;
+        s.done_score[d] = score;
+    }
+    return p;
+}
+
+// The attention rows of this step's live slots (the alpha of the step that chose the selections); `width` columns.
+__device__ __forceinline__ void beam_copy_attention(float* hist_attn, const float* alpha, int base, int live, int width,
+                                                    int lane) {
+    if (!hist_attn) return;
+    for (int e = lane; e < live * width; e += BEAM_WAVE) {
+        const int r = e / width, c = e - r * width;
+        hist_attn[(size_t)(base + r) * width + c] = alpha[(size_t)(base + r) * width + c];
+    }
+}
+
+// The end of a step: the slots behind the continuing ones are dead (no parent = zero h / c, score 0; the kernel adds
+// what else a dead slot of its own needs), and lane 0 moves the instance on.
+template <class S>
+__device__ __forceinline__ void beam_close(const S& s, int32_t* inst, int base, int lane, int t, const BeamPlace& p) {
+    if (lane >= p.live_next && lane < s.beam_size) {
+        s.parent[base + lane] = -1;
+        s.score[base + lane] = 0.f;
+    }
+    if (lane == 0) {
+        inst[0] = p.live_next;
+        inst[1] = p.done_after;
+        inst[2] = t + 1;
+        if (p.live_next > 0) atomicAdd(s.live_total + t, p.live_next);
+    }
+}
+
+__global__ __launch_bounds__(BEAM_WAVE) void speaker_beam_select_kernel(sf_spk_beam s, const int32_t* top_w,
+                                                                        const float* top_lp, const float* alpha) {
+    __shared__ int s_row[BEAM_WAVE], s_rank[BEAM_WAVE];
+    __shared__ float s_score[BEAM_WAVE];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int W = s.beam_size, k = s.k, base = b * W;
+    int32_t* inst = s.inst + 3 * b;
+    const int live = inst[0], n_done = inst[1], t = inst[2];
+    if (live <= 0 || t >= s.T) return;                  // ended instance (or steps issued past the end): no change
+    const size_t hist = (size_t)t * (size_t)s.ld_hist;
+
+    // ---- selection: every rank of a live slot is a successor
+    const float my_score = lane < live ? s.score[base + lane] : 0.f;
+    const int nsel = beam_merge(lane, live, W, k, my_score, top_lp + (size_t)(base + lane) * k,
+                                [](int) { return true; }, s_row, s_rank, s_score);
+
+    // ---- finals: EOS or the last word step (speaker.py:281-290)
     const bool sel = lane < nsel;
-    const int prow = sel ? s_row[lane] : 0, act = sel ? s_act[lane] : 0;
+    const int prow = sel ? s_row[lane] : 0;
+    const float score = sel ? s_score[lane] : 0.f;
+    const int word = sel ? top_w[(size_t)(base + prow) * k + s_rank[lane]] : 0;
+    const bool fin = sel && (word == s.eos || t == s.T - 1);
+    const BeamPlace p = beam_place(s, b, lane, t, n_done, sel, fin, score);
+    if (sel) {
+        s.hist_word[hist + p.h] = word;
+        s.hist_parent[hist + p.h] = base + prow;
+        s.hist_score[hist + p.h] = score;
+    }
+    beam_copy_attention(s.hist_attn ? s.hist_attn + hist : nullptr, alpha, base, live, s.Tp, lane);
+
+    // ---- the next step's slots (slot p of the next step is history position base + p of this step: the backchain
+    // needs no other map)
+    if (sel && !fin && p.live_next > 0) {
+        s.words[p.h] = (int64_t)word;
+        s.parent[p.h] = base + prow;
+        s.score[p.h] = score;
+    }
+    // (dead slots are decoded and ignored: a valid word id)
+    if (lane >= p.live_next && lane < W) s.words[base + lane] = (int64_t)s.eos;
+    beam_close(s, inst, base, lane, t, p);
+}
+
+// The follower's step.  A slot's state is (row, view) of the navigation table, sid = row * V + view; a successor list
+// ends at the first rank that is no candidate of the state (an action >= a_num -- sf_logprob_topk returns the masked
+// columns as (column, -inf) behind the valid ones -- or a negative action: the is_valid filter of follower.py:626), so
+// every list stays sorted and the merge applies unchanged.
+__global__ __launch_bounds__(BEAM_WAVE) void follower_beam_select_kernel(sf_fol_beam s, const int32_t* top_a,
+                                                                         const float* top_lp, const float* alpha) {
+    __shared__ int s_row[BEAM_WAVE], s_rank[BEAM_WAVE], s_sid[BEAM_WAVE];
+    __shared__ float s_score[BEAM_WAVE];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int W = s.beam_size, k = s.k, R = s.B * W, base = b * W;
+    const int A = s.nav.A, V = s.nav.V;
+    int32_t* inst = s.inst + 3 * b;
+    const int live = inst[0], n_done = inst[1], t = inst[2];
+    if (live <= 0 || t >= s.episode_len) return;        // ended instance (or steps issued past the end): no change
+    const size_t hist = (size_t)t * (size_t)s.ld_hist;
+
+    // ---- selection: a rank is a successor while its action is a candidate of the slot's state
+    const int32_t* my_a = top_a + (size_t)(base + lane) * k;
+    float my_score = 0.f;
+    int my_anum = 0;
+    if (lane < live) {
+        const int sid = s.row[base + lane] * V + s.view[base + lane];
+        s_sid[lane] = sid;
+        my_score = s.score[base + lane];
+        my_anum = s.nav.a_num[sid];
+    }
+    const int nsel = beam_merge(lane, live, W, k, my_score, top_lp + (size_t)(base + lane) * k,
+                                [&](int j) { return my_a[j] >= 0 && my_a[j] < my_anum; }, s_row, s_rank, s_score);
+
+    // ---- successor states (StateSpace.successors); finals: stop, or the last step (follower.py:674)
+    const bool sel = lane < nsel;
+    const int prow = sel ? s_row[lane] : 0;
+    const float score = sel ? s_score[lane] : 0.f;
+    const int act = sel ? top_a[(size_t)(base + prow) * k + s_rank[lane]] : 0;
     const int psid = sel ? s_sid[prow] : 0;
     int nsid = psid;
     if (sel && act != 0) {
@@ -203,58 +207,31 @@ __global__ __launch_bounds__(BEAM_WAVE) void follower_beam_select_kernel(sf_fol_
         if (nxt != psid / V) nsid = nxt * V + s.nav.cand_view[(size_t)psid * A + act];
     }
     const bool fin = sel && (act == 0 || t == s.episode_len - 1);
-    const unsigned long long m_fin = __ballot(fin), m_cont = __ballot(sel && !fin);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const int n_fin = __popcll(m_fin), n_cont = __popcll(m_cont);
-    const int pos = fin ? n_cont + __popcll(m_fin & below) : __popcll(m_cont & below);
-    const int done_after = n_done + n_fin;
-    const int live_next = done_after >= W ? 0 : n_cont;  // follower.py:674: a full completion list stops the instance
+    const BeamPlace p = beam_place(s, b, lane, t, n_done, sel, fin, score);
     if (sel) {
-        const int h = base + pos;
-        s.hist_parent[hist + h] = base + prow;
-        s.hist_action[hist + h] = act;
-        s.hist_rank[hist + h] = lane;
-        s.hist_sid[hist + h] = nsid;
-        s.hist_psid[hist + h] = psid;
-        s.hist_score[hist + h] = s_score[lane];
-        if (fin) {
-            const int d = b * 2 * W + n_done + __popcll(m_fin & below);     // n_done < W, n_fin <= W
-            s.done_rec[d] = t * R + h;
-            s.done_score[d] = s_score[lane];
-        }
+        s.hist_parent[hist + p.h] = base + prow;
+        s.hist_action[hist + p.h] = act;
+        s.hist_rank[hist + p.h] = lane;
+        s.hist_sid[hist + p.h] = nsid;
+        s.hist_psid[hist + p.h] = psid;
+        s.hist_score[hist + p.h] = score;
     }
-    // the attention rows of this step's live slots (the alpha of the step that chose the actions)
-    if (s.hist_attn) {
-        const int T = s.T;
-        for (int e = lane; e < live * T; e += BEAM_WAVE) {
-            const int r = e / T, c = e - r * T;
-            s.hist_attn[hist + (size_t)(base + r) * T + c] = alpha[(size_t)(base + r) * T + c];
-        }
-    }
+    beam_copy_attention(s.hist_attn ? s.hist_attn + hist : nullptr, alpha, base, live, s.T, lane);
 
-    // ---- the next step's slots: continuing hypotheses compacted to the front in selection order, the rest dead
-    // (slot p of the next step is history position base + p of this step; every read of row / view / score above
-    // happened before the barrier)
-    if (sel && !fin && live_next > 0) {
-        s.row[base + pos] = nsid / V;
-        s.view[base + pos] = nsid % V;
-        s.row[R + base + pos] = psid / V;                // the parent's state and the action: the previous action's
-        s.view[R + base + pos] = psid % V;               // embedding is looked up from them (sf_gather_actions_ld)
-        s.act[base + pos] = act;
-        s.parent[base + pos] = base + prow;
-        s.score[base + pos] = s_score[lane];
+    // ---- the next step's slots (slot p of the next step is history position base + p of this step; every read of
+    // row / view / score above happened before the merge's barrier)
+    if (sel && !fin && p.live_next > 0) {
+        s.row[p.h] = nsid / V;
+        s.view[p.h] = nsid % V;
+        s.row[R + p.h] = psid / V;                       // the parent's state and the action: the previous action's
+        s.view[R + p.h] = psid % V;                      // embedding is looked up from them (sf_gather_actions_ld)
+        s.act[p.h] = act;
+        s.parent[p.h] = base + prow;
+        s.score[p.h] = score;
     }
-    if (lane >= live_next && lane < W) {
-        s.act[base + lane] = 0;                          // (zero embedding; row / view keep a valid state: dead slots
-        s.parent[base + lane] = -1;                      // are decoded and ignored)
-        s.score[base + lane] = 0.f;
-    }
-    if (lane == 0) {
-        inst[0] = live_next;
-        inst[1] = done_after;
-        inst[2] = t + 1;
-        if (live_next > 0) atomicAdd(s.live_total + t, live_next);
-    }
+    // (dead slots are decoded and ignored: a zero embedding; row / view keep a valid state)
+    if (lane >= p.live_next && lane < W) s.act[base + lane] = 0;
+    beam_close(s, inst, base, lane, t, p);
 }
 
 // ---- the state-factored search (reference: Seq2SeqAgent.state_factored_search, tasks/R2R/follower.py:783-905;

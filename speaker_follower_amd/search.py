@@ -137,6 +137,175 @@ def _baked_weights(obj):
     return wb
 
 
+class _DeviceLoop:
+    """What the searches with their steps on the device share (GraphStep, DeviceStateFactored, DeviceSpeakerBeam,
+    DeviceFollowerBeam): the capture of a chunk of steps as one hipGraph, the replay-or-issue chunk loop and the
+    counters of its host reads.  A subclass has `dev`, `chunk` and `_issue_steps(n)`, which issues n steps on the
+    current stream."""
+    _side = None                                          # the capture stream: ONE per object, for its lifetime
+    captures = 0
+    host_reads = last_host_reads = minibatches = 0
+    last_run_s = 0.0                                      # (the step loop and its download, seconds)
+
+    def _capture_steps(self, n_steps, graphs=True):
+        """`n_steps` steps as one hipGraph (graphs = False: 'eager', nothing captured), after one eager warm-up step
+        (cached layouts, lazy tables).  The caller has put the buffers into a state in which a step changes nothing.
+        Every capture of the object runs on its one side stream: a graph bakes that stream's workspace, and a stream
+        per capture would leave one workspace behind per re-capture (runtime._workspaces)."""
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.dev)
+        side = self._side
+        ensure_workspace(side, self.dev)                  # (before the capture: runtime.workspace)
+        side.wait_stream(torch.cuda.current_stream())
+        graph = 'eager'
+        with torch.no_grad(), torch.cuda.stream(side):
+            self._issue_steps(1)
+            side.synchronize()
+            if graphs:
+                graph = torch.cuda.CUDAGraph()
+                with graph_capture(graph, side):
+                    self._issue_steps(n_steps)
+        torch.cuda.current_stream().wait_stream(side)
+        self.captures += 1
+        return graph
+
+    def _step_chunk(self, graph):
+        """One chunk of steps: the captured graph's replay, or (graph None / 'eager') issued launch by launch."""
+        if graph is None or graph == 'eager':
+            self._issue_steps(self.chunk)
+        else:
+            graph.replay()
+
+    def _run_chunks(self, graph, limit, live_total):
+        """Chunks until `limit` steps are issued or the chunk's last step left nothing live (live_total: the device
+        array of the live count after every step; one 4-byte read per chunk).  Returns (steps to download, reads)."""
+        reads = issued = 0
+        while issued < limit:
+            self._step_chunk(graph)
+            issued += self.chunk
+            if issued >= limit:
+                break
+            reads += 1
+            if int(live_total[issued - 1].item()) == 0:
+                break
+        return min(issued, limit), reads
+
+    def _count_run(self, reads, t0):
+        self.last_host_reads = reads
+        self.host_reads += reads
+        self.minibatches += 1
+        self.last_run_s = time.perf_counter() - t0
+
+
+class BeamRecord:
+    """The layout of a beam search's record, one int32 buffer downloaded once at the end (host arithmetic only):
+
+        [inst B x 3 | live_total steps | done_rec B x 2 beam | done_score B x 2 beam], padded to 4 words, then per step
+        [one plane of R = B * beam words per name in `planes` | attention R x width]
+
+    The last of `planes` (the score) and the attention are float32, the rest int32."""
+
+    def __init__(self, B, beam, steps, planes, width):
+        self.B, self.beam, self.steps, self.planes, self.width = B, beam, steps, tuple(planes), width
+        self.R = B * beam
+        self.o_live = 3 * B
+        self.o_done = self.o_live + steps
+        self.o_dscore = self.o_done + 2 * beam * B
+        self.hdr = (self.o_dscore + 2 * beam * B + 3) & ~3
+        self.stride = self.R * (len(self.planes) + width)
+        self.size = self.hdr + steps * self.stride
+
+    def head0(self):
+        """The header at the start of a search: one live slot per instance, nothing done, t = 0."""
+        head = np.zeros(self.hdr, np.int32)
+        head[0:3 * self.B:3] = 1
+        return head
+
+    def pointers(self, base):
+        """(inst, live_total, one pointer per plane, attention, ld_hist, done_rec, done_score) of a record at device
+        address `base`: the tail of the SpkBeam / FolBeam constructors."""
+        steps = base + 4 * self.hdr
+        return (base, base + 4 * self.o_live, *(steps + 4 * j * self.R for j in range(len(self.planes) + 1)),
+                self.stride, base + 4 * self.o_done, base + 4 * self.o_dscore)
+
+    def split(self, flat, attn='attn'):
+        """A downloaded record (int32, header and at least the steps that ran) as host arrays: inst [B,3], done_rec /
+        done_score [B, 2 beam], every plane [t_end, R] under its name, the attention [t_end, R, width] under `attn`;
+        t_end: the step after the last one any instance ran."""
+        B, R, W2 = self.B, self.R, 2 * self.beam
+        inst = flat[:3 * B].reshape(B, 3)
+        t_end = int(inst[:, 2].max())
+        fl = flat.view(np.float32)
+        st = flat[self.hdr:self.hdr + t_end * self.stride].reshape(t_end, self.stride)
+        stf = fl[self.hdr:self.hdr + t_end * self.stride].reshape(t_end, self.stride)
+        out = dict(inst=inst, done_rec=flat[self.o_done:self.o_dscore].reshape(B, W2),
+                   done_score=fl[self.o_dscore:self.o_dscore + W2 * B].reshape(B, W2))
+        n = len(self.planes)
+        for j, name in enumerate(self.planes):
+            out[name] = (stf if j == n - 1 else st)[:, j * R:(j + 1) * R]
+        out[attn] = stf[:, n * R:].reshape(t_end, R, self.width)
+        return out
+
+
+def _owner_cache(owner, name, key, limit, build, **same):
+    """The object `owner` keeps under `key` in its dictionary `name` (buffers and captured graphs; built on first use).
+    `same`: attributes of the kept object that must still BE these objects (a key holds ids, and an id can come back
+    on another object).  A cache of `limit` entries is emptied before one more goes in."""
+    cache = owner.__dict__.setdefault(name, {})
+    obj = cache.get(key)
+    if obj is None or any(getattr(obj, a) is not v for a, v in same.items()):
+        if len(cache) >= limit:
+            cache.clear()
+        obj = cache[key] = build()
+    return obj
+
+
+def _observation_buffers(n, A, dev):
+    """Outputs of sf_nav_step over 2n states: the observations of n states [0] and of their parents [1] as halves of
+    one [2n] look-up.  Returns (the whole block, its two halves)."""
+    i32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.int32)                 # noqa: E731
+    obs2 = dict(row=i32(2 * n), vp=i32(2 * n), view=i32(2 * n), a_num=i32(2 * n), cand_view=i32(2 * n, A),
+                sincos=torch.zeros(2 * n, A, 4, device=dev, dtype=torch.float32))
+    return obs2, [{k: v[j * n:(j + 1) * n] for k, v in obs2.items()} for j in range(2)]
+
+
+def _follower_steps(obj, n_steps, n, rows, views, act, hsrc, csrc, hrow, crow, k, idx, logp, then):
+    """`n_steps` follower decode steps over the n fixed rows of `obj` (a GraphStep or a DeviceFollowerBeam: store, nav,
+    dec, obs2 / obs, tape, h0 / c0, ctx / mask, H / D / T / A), per step
+
+        sf_nav_step over the [2n] block (rows, views) -> obj.obs2; the previous action's embedding out of the parents'
+        candidates straight into the first half of the LSTM input rows (sf_gather_actions_ld; action 0 = zeros =
+        u_begin: no copy in the step); h0 / c0 = hsrc / csrc [hrow] (sf_move_rows); sf_attn_decoder_fwd with
+        instruction rows `crow` under the object's gate-product mode; sf_logprob_topk (k columns, n_valid = a_num) ->
+        idx (or None) / logp; then(stream): what the search does with them.
+
+    Returns the pointer structs of the launches: the caller keeps them for as long as a captured graph may replay."""
+    st, A, H = obj.store, obj.A, obj.H
+    s = stream()
+    o = obj.obs2
+    cur, par = obj.obs
+    ns = obj.nav.struct()
+    ucand = st.cands(par['vp'], par['cand_view'], par['sincos'], par['a_num'], A)
+    gat = (_lib.RowMove * 2)(_lib.RowMove(hsrc.data_ptr(), obj.h0.data_ptr(), hrow.data_ptr(), H, H, H, 0),
+                             _lib.RowMove(csrc.data_ptr(), obj.c0.data_ptr(), hrow.data_ptr(), H, H, H, 0))
+    pano = st.pano(cur['vp'], cur['view'])
+    cnd = st.cands(cur['vp'], cur['cand_view'], cur['sincos'], cur['a_num'], A)
+    w = decoder_w_struct(decoder_params(obj.dec))
+    tp = tape_struct(obj.tape)
+    for _ in range(n_steps):
+        call('sf_nav_step', byref(ns), 2 * n, ptr(rows), ptr(views), None, None, None, 0, None,
+             ptr(o['row']), ptr(o['vp']), ptr(o['view']), ptr(o['a_num']), ptr(o['cand_view']), ptr(o['sincos']), None, s)
+        call('sf_gather_actions_ld', byref(ucand), n, ptr(act), ptr(obj.tape['xin']), 2 * st.F, s)
+        call('sf_move_rows', gat, 2, n, s)
+        with _gate_pass(obj):
+            call('sf_attn_decoder_fwd', byref(w), byref(pano), byref(cnd), n, H, obj.D, obj.T,
+                 None, ptr(obj.h0), ptr(obj.c0), ptr(obj.ctx), ptr(obj.mask), ptr(crow), byref(tp), None,
+                 None, 0, *ws_args(obj.dev))
+        call('sf_logprob_topk', ptr(obj.tape['logit']), A, n, A, ptr(cur['a_num']), k, ptr(idx), ptr(logp), s)
+        then(s)
+    return ns, ucand, pano, cnd, w, tp, gat
+
+
 class FlatDecoder:
     """One follower decoder step over a flat list of search states (a6 without the glue).  `gate_weights`: 'fp32' or 'bf16'
     (FollowerEngine.gate_weights; steps of more than 128 states run the fp32-weight kernels in either mode)."""
@@ -267,7 +436,7 @@ class FlatDecoder:
         return list(self.apool.buf[r].cpu().numpy())
 
 
-class GraphStep:
+class GraphStep(_DeviceLoop):
     """The decoder step of the state-factored search as ONE hipGraph over fixed buffers (follower.py:783-836 per
     iteration: observations of the expanded states, `h_t[flat_indices]`, the AttnDecoderLSTM step, log_softmax).
 
@@ -297,10 +466,7 @@ class GraphStep:
         self.inputs = self.pin_in.numpy()                                            # what fill_inputs writes
         self.dev_in = i32(8, cap)
         A = self.A
-        # observations of the states [0] and of their parents [1]: halves of one [2 cap] look-up
-        self.obs2 = dict(row=i32(2 * cap), vp=i32(2 * cap), view=i32(2 * cap), a_num=i32(2 * cap),
-                         cand_view=i32(2 * cap, A), sincos=f32(2 * cap, A, 4))
-        self.obs = [{k: v[j * cap:(j + 1) * cap] for k, v in self.obs2.items()} for j in range(2)]
+        self.obs2, self.obs = _observation_buffers(cap, A, dev)
         self.h0, self.c0 = f32(cap, self.H), f32(cap, self.H)
         self.tape = decoder_tape(cap, self.H, store.F, self.D, store.V, t_max, A, dev)
         self.logp = f32(cap, A)
@@ -311,7 +477,7 @@ class GraphStep:
         self.pool_rows = pool_rows
         self.hpool, self.cpool, self.apool = f32(pool_rows, self.H), f32(pool_rows, self.H), f32(pool_rows, t_max)
         self.n = 0
-        self.graph = self.baked = self._stream = None
+        self.graph = self.baked = None
 
     # ---- per search
     def load(self, ctx, mask, h, c):
@@ -329,58 +495,33 @@ class GraphStep:
         if self.graph is None or w != self.baked:
             self._capture()
 
-    def _issue(self):
-        self.dev_in.copy_(self.pin_in, non_blocking=True)
-        self._chain()
-        self.pin_out.copy_(self.logp, non_blocking=True)
+    def _issue_steps(self, n_steps):
+        for _ in range(n_steps):
+            self.dev_in.copy_(self.pin_in, non_blocking=True)
+            self._chain()
+            self.pin_out.copy_(self.logp, non_blocking=True)
 
-    def _chain(self):
-        """The launches of one decoder step between the upload of the input block and the download of the
-        log-probabilities: `dev_in` -> `logp`, the new states' rows scattered to the pools."""
-        st, nav, cap, A = self.store, self.nav, self.cap, self.A
-        s = stream()
-        act, hrow, crow, dst = (self.dev_in[j] for j in range(4, 8))
-        ns = nav.struct()
+    def _chain(self, n_steps=1, then=None):
+        """The launches of a decoder step between the upload of the input block and the download of the
+        log-probabilities: `dev_in` -> `logp` over the whole candidate row, the new states' rows scattered to the
+        pools, then(stream) if given."""
         # rows 0-1 of the block: nav rows of the states, then of their parents; rows 2-3 their views (fill_inputs)
-        o = self.obs2
-        call('sf_nav_step', byref(ns), 2 * cap, ptr(self.dev_in[0]), ptr(self.dev_in[2]), None, None, None, 0, None,
-             ptr(o['row']), ptr(o['vp']), ptr(o['view']), ptr(o['a_num']), ptr(o['cand_view']), ptr(o['sincos']), None, s)
-        cur, par = self.obs
-        ucand = st.cands(par['vp'], par['cand_view'], par['sincos'], par['a_num'], A)
-        # (the previous action's embedding straight into the first half of the LSTM input rows: no copy in the step)
-        call('sf_gather_actions_ld', byref(ucand), cap, ptr(act), ptr(self.tape['xin']), 2 * st.F, s)
-        H = self.H
-        gat = (_lib.RowMove * 2)(_lib.RowMove(self.hpool.data_ptr(), self.h0.data_ptr(), hrow.data_ptr(), H, H, H, 0),
-                                 _lib.RowMove(self.cpool.data_ptr(), self.c0.data_ptr(), hrow.data_ptr(), H, H, H, 0))
-        call('sf_move_rows', gat, 2, cap, s)
-        pano = st.pano(cur['vp'], cur['view'])
-        cnd = st.cands(cur['vp'], cur['cand_view'], cur['sincos'], cur['a_num'], A)
-        w = decoder_w_struct(decoder_params(self.dec))
-        tp = tape_struct(self.tape)
-        with _gate_pass(self):
-            call('sf_attn_decoder_fwd', byref(w), byref(pano), byref(cnd), cap, self.H, self.D, self.T,
-                 None, ptr(self.h0), ptr(self.c0), ptr(self.ctx), ptr(self.mask), ptr(crow), byref(tp), None,
-                 None, 0, *ws_args(self.dev))
-        call('sf_logprob_topk', ptr(self.tape['logit']), A, cap, A, ptr(cur['a_num']), A, None, ptr(self.logp), s)
-        sca = (_lib.RowMove * 3)(*(_lib.RowMove(src.data_ptr(), pool.data_ptr(), dst.data_ptr(), width, width, width, 1)
+        d, H = self.dev_in, self.H
+        sca = (_lib.RowMove * 3)(*(_lib.RowMove(src.data_ptr(), pool.data_ptr(), d[7].data_ptr(), width, width, width, 1)
                                    for src, pool, width in ((self.tape['h1'], self.hpool, H), (self.tape['c1'], self.cpool, H),
                                                             (self.tape['alpha'], self.apool, self.T))))
-        call('sf_move_rows', sca, 3, cap, s)
-        self._keep = (ns, ucand, pano, cnd, w, tp, gat, sca)
+
+        def scatter(s):
+            call('sf_move_rows', sca, 3, self.cap, s)
+            if then is not None:
+                then(s)
+        self._keep = (sca, _follower_steps(self, n_steps, self.cap, d[0], d[2], d[4], self.hpool, self.cpool, d[5], d[6],
+                                           self.A, None, self.logp, scatter))
 
     def _capture(self):
         self.pin_in.zero_()
         self.pin_in[7].fill_(-1)                                     # (a warm-up that writes no pool row)
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.no_grad(), torch.cuda.stream(side):
-            self._issue()                                            # warm-up: workspace, cached layouts
-            side.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with graph_capture(graph, side):
-                self._issue()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph, self._stream = graph, side                       # (the graph bakes the capture stream's workspace)
+        self.graph = self._capture_steps(1)
         self.baked = _baked_weights(self)
 
     # ---- the native loop (sim/frontier_core.cpp: run_graph) launches the graph itself
@@ -460,12 +601,10 @@ def graph_step_for(agent, nav, n_inst, cap):
     # storage of Seq2SeqAgent.gate_weights)
     mode = getattr(agent, 'gate_weights', 'fp32')
     key = graph_step_key(agent, nav, n_inst, cap, t_max, mode)
-    cache = agent.__dict__.setdefault('_graph_steps', {})
-    gs = cache.get(key)
-    if gs is None or gs.dec is not agent.decoder or gs.store is not agent.store or gs.nav is not nav:
-        cache.clear()                                                # (one live configuration: the pools are ~100 MB)
-        gs = cache[key] = GraphStep(agent.decoder, agent.store, nav, n_inst, cap, t_max, gate_weights=mode)
-    return gs
+    # (one live configuration: the pools are ~100 MB)
+    return _owner_cache(agent, '_graph_steps', key, 1,
+                        lambda: GraphStep(agent.decoder, agent.store, nav, n_inst, cap, t_max, gate_weights=mode),
+                        dec=agent.decoder, store=agent.store, nav=nav)
 
 
 class DeviceStateFactored(GraphStep):
@@ -515,9 +654,7 @@ class DeviceStateFactored(GraphStep):
         self.o_keys = total - 3 * B * K
         self.n_head = 8 + 8 * B                                      # status + inst: what is read once per chunk
         self.pin_head = torch.zeros(self.n_head, dtype=torch.int32).pin_memory()
-        self.captures = 0
-        self.host_reads = self.last_host_reads = 0
-        self.minibatches, self.last_run_s, self.last_iterations, self.last_flags = 0, 0.0, 0, 0
+        self.last_iterations, self.last_flags = 0, 0
         self.last = None                                    # what the last run returned
 
     @classmethod
@@ -538,11 +675,9 @@ class DeviceStateFactored(GraphStep):
                                 self.nav.struct(), *(p[n].data_ptr() for n in _lib.StateSearch.POINTERS))
 
     def _issue_steps(self, n_steps):
-        s = stream()
         ss = self._struct()
-        for _ in range(n_steps):
-            self._chain()
-            call('sf_state_factored_select', byref(ss), ptr(self.logp), self.A, ptr(self.dev_in), s)
+        self._chain(n_steps, lambda s: call('sf_state_factored_select', byref(ss), ptr(self.logp), self.A,
+                                            ptr(self.dev_in), s))
         self._keep_search = ss
 
     def _capture(self):
@@ -550,20 +685,8 @@ class DeviceStateFactored(GraphStep):
         self.state.zero_()
         self.dev_in.zero_()
         self.dev_in[7].fill_(-1)
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream())
-        graph = 'eager'
-        with torch.no_grad(), torch.cuda.stream(side):
-            self._issue_steps(1)                                     # warm-up: workspace, cached layouts
-            side.synchronize()
-            if self.graphs:
-                graph = torch.cuda.CUDAGraph()
-                with graph_capture(graph, side):
-                    self._issue_steps(self.chunk)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph, self._stream = graph, side                       # (the graph bakes the capture stream's workspace)
+        self.graph = self._capture_steps(self.chunk, self.graphs)
         self.baked = _baked_weights(self)
-        self.captures += 1
 
     # ---- per search
     def initial_tables(self, space):
@@ -626,10 +749,7 @@ class DeviceStateFactored(GraphStep):
         self._reset(space)
         reads = 0
         while True:
-            if self.graphs:
-                self.graph.replay()
-            else:
-                self._issue_steps(self.chunk)
+            self._step_chunk(self.graph)
             self.pin_head.copy_(self.state[:self.n_head], non_blocking=True)
             torch.cuda.current_stream().synchronize()
             reads += 1
@@ -654,10 +774,7 @@ class DeviceStateFactored(GraphStep):
                        visits=flat[o2:].reshape(B, n_vis), **{f: nodes[j] for j, f in enumerate(self.NODE_FIELDS)})
             tab['score'] = nodes[nf - 1].view(np.float32)
             self.n = base
-        self.last_host_reads = reads
-        self.host_reads += reads
-        self.minibatches += 1
-        self.last_run_s = time.perf_counter() - t0
+        self._count_run(reads, t0)
         self.last = tab
         return tab
 
@@ -672,15 +789,13 @@ def device_search_for(agent, nav, n_inst, completion_size, successor_size, key_f
     sizes = (completion_size, successor_size, agent.episode_len, key_fields, int(chunk), bool(graphs),
              int(agent.search_node_cap), int(agent.search_slot_cap))
     key = graph_step_key(agent, nav, n_inst, n_inst * successor_size, t_max, mode, device_loop=sizes)
-    cache = agent.__dict__.setdefault('_device_searches', {})
-    ds = cache.get(key)
-    if ds is None or ds.dec is not agent.decoder or ds.store is not agent.store or ds.nav is not nav:
-        cache.clear()                                                # (one live configuration: the pools are ~100 MB)
-        ds = cache[key] = DeviceStateFactored(agent.decoder, agent.store, nav, n_inst, completion_size, successor_size,
-                                              agent.episode_len, key_fields, t_max, chunk, graphs,
-                                              node_cap=agent.search_node_cap, slot_cap=agent.search_slot_cap,
-                                              gate_weights=mode)
-    return ds
+    # (one live configuration: the pools are ~100 MB)
+    return _owner_cache(agent, '_device_searches', key, 1,
+                        lambda: DeviceStateFactored(agent.decoder, agent.store, nav, n_inst, completion_size,
+                                                    successor_size, agent.episode_len, key_fields, t_max, chunk, graphs,
+                                                    node_cap=agent.search_node_cap, slot_cap=agent.search_slot_cap,
+                                                    gate_weights=mode),
+                        dec=agent.decoder, store=agent.store, nav=nav)
 
 
 @gc_paused
@@ -818,7 +933,7 @@ class FlatSpeakerDecoder:
         return list(self.apool.buf[torch.tensor(rows, dtype=torch.int64, device=self.dev)].cpu().numpy())
 
 
-class DeviceSpeakerBeam:
+class DeviceSpeakerBeam(_DeviceLoop):
     """The speaker's beam search (speaker.py:211-318) with its word loop on the device: R = B * beam_size fixed
     hypothesis slots (instance b owns slots b*beam_size ..), per word step
 
@@ -859,28 +974,22 @@ class DeviceSpeakerBeam:
         self.words = torch.full((R,), EOS, device=dev, dtype=torch.int64)
         self.parent = torch.full((R,), -1, device=dev, dtype=torch.int32)
         self.ctx_row = torch.arange(R, device=dev, dtype=torch.int32) // beam_size
-        # the record: [inst B x 3 | live_total T | done_rec B x 2 beam | done_score B x 2 beam] then per word step
-        # [hist_word R | hist_parent R | hist_score R | hist_attn R x Tp] -- one download at the end
-        self.o_live = 3 * B
-        self.o_done = self.o_live + T
-        self.o_dscore = self.o_done + 2 * beam_size * B
-        self.hdr = (self.o_dscore + 2 * beam_size * B + 3) & ~3
-        self.head0 = torch.zeros(self.hdr, dtype=torch.int32)
-        self.head0[0:3 * B:3] = 1                                      # one live slot per path, nothing done, t = 0
-        self.head0 = self.head0.to(dev)
+        self.head0 = torch.from_numpy(self._record(0).head0()).to(dev)
         self.words0 = self.words.clone()
         self.words0[::beam_size] = BOS
         self.parent0 = self.parent.clone()
         self.parent0[::beam_size] = torch.arange(0, R, beam_size, device=dev, dtype=torch.int32)
-        self.Tp_cap = 0
+        self.Tp = self.Tp_cap = 0                           # the path length of the run at hand, the widest so far
         self.graph_by_tp = {}
-        self.baked = self._side = None
-        self.host_reads = self.last_host_reads = 0
-        self.minibatches, self.last_run_s = 0, 0.0          # (last_run_s: the word loop and its download, seconds)
+        self.baked = None
 
     @classmethod
     def supports(cls, beam_size):
         return 1 <= beam_size <= cls.MAX_BEAM
+
+    def _record(self, Tp):
+        """The record's layout at path length Tp (the header does not depend on it): one download at the end."""
+        return BeamRecord(self.B, self.beam, self.T, ('hist_word', 'hist_parent', 'hist_score'), Tp)
 
     # ---- buffers that depend on the path length (grown, never shrunk: the graphs hold their addresses)
     def _reserve(self, Tp):
@@ -891,7 +1000,7 @@ class DeviceSpeakerBeam:
         self.ctx_buf = torch.zeros(B * Tp * self.H, device=dev, dtype=torch.float32)
         self.mask_buf = torch.ones(B * Tp, device=dev, dtype=torch.uint8)
         self.alpha_buf = torch.zeros(R * Tp, device=dev, dtype=torch.float32)
-        self.rec = torch.zeros(self.hdr + self.T * R * (3 + Tp), device=dev, dtype=torch.int32)
+        self.rec = torch.zeros(self._record(Tp).size, device=dev, dtype=torch.int32)
         self.graph_by_tp = {}
 
     def _views(self, Tp):
@@ -901,31 +1010,21 @@ class DeviceSpeakerBeam:
         alpha = self.alpha_buf[:R * Tp].view(R, Tp)
         return ctx, mask, alpha
 
-    def _structs(self, Tp):
-        R, S = self.R, self.R * (3 + Tp)
-        rec, base = self.rec, self.rec.data_ptr()
-        steps = base + 4 * self.hdr
-        sb = _lib.SpkBeam(self.B, self.beam, self.k, self.T, Tp, EOS,
-                          self.score.data_ptr(), self.words.data_ptr(), self.parent.data_ptr(), base,
-                          base + 4 * self.o_live, steps, steps + 4 * R, steps + 8 * R, steps + 12 * R, S,
-                          base + 4 * self.o_done, base + 4 * self.o_dscore)
-        _, _, alpha = self._views(Tp)
+    def _issue_steps(self, n_steps):
+        s, Tp, H = stream(), self.Tp, self.H
+        ctx, mask, alpha = self._views(Tp)
+        rec = self._record(Tp)
+        assert self.rec.numel() >= rec.size
+        sb = _lib.SpkBeam(self.B, self.beam, self.k, self.T, Tp, EOS, self.score.data_ptr(), self.words.data_ptr(),
+                          self.parent.data_ptr(), *rec.pointers(self.rec.data_ptr()))
         tape = dict(self.tape, alpha=alpha)
         tp = _lib.SpkDecoderTape(*(tape[key].data_ptr() for key in self.keys))
-        H = self.H
         gat = (_lib.RowMove * 2)(_lib.RowMove(tape['h1'].data_ptr(), self.h0.data_ptr(), self.parent.data_ptr(), H, H, H, 0),
                                  _lib.RowMove(tape['c1'].data_ptr(), self.c0.data_ptr(), self.parent.data_ptr(), H, H, H, 0))
-        assert rec.numel() >= self.hdr + self.T * S
-        return sb, tp, gat
-
-    def _issue(self, Tp, n_steps):
-        s = stream()
-        ctx, mask, alpha = self._views(Tp)
-        sb, tp, gat = self._structs(Tp)
         w = self.w
         for _ in range(n_steps):
             call('sf_move_rows', gat, 2, self.R, s)
-            call('sf_speaker_decoder_fwd', byref(w), self.R, self.E, self.H, Tp, self.vocab, ptr(self.words),
+            call('sf_speaker_decoder_fwd', byref(w), self.R, self.E, H, Tp, self.vocab, ptr(self.words),
                  ptr(self.h0), ptr(self.c0), ptr(ctx), ptr(mask), ptr(self.ctx_row), byref(tp), None, 0,
                  *ws_args(self.dev))
             call('sf_logprob_topk', ptr(self.tape['logit']), self.ldv, self.R, self.vocab, None, self.k, ptr(self.idx),
@@ -933,24 +1032,12 @@ class DeviceSpeakerBeam:
             call('sf_speaker_beam_select', byref(sb), ptr(self.idx), ptr(self.logp), ptr(alpha), s)
         self._keep = (sb, tp, gat, w)
 
-    def _capture(self, Tp):
+    def _capture(self):
         # dead slots for the warm-up step (every instance ended: the selection changes nothing)
-        self.rec[:self.hdr].zero_()
+        self.rec[:len(self.head0)].zero_()
         self.words.fill_(EOS)
         self.parent.fill_(-1)
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.dev)              # (one capture stream: its workspace is baked)
-            ensure_workspace(self._side, self.dev)
-        side = self._side
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.no_grad(), torch.cuda.stream(side):
-            self._issue(Tp, 1)                                           # warm-up: cached layouts, lazy tables
-            side.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with graph_capture(graph, side):
-                self._issue(Tp, self.chunk)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph_by_tp[Tp] = graph
+        graph = self.graph_by_tp[self.Tp] = self._capture_steps(self.chunk)
         return graph
 
     # ---- per minibatch
@@ -959,54 +1046,32 @@ class DeviceSpeakerBeam:
         arrays (inst [B,3], done_rec / done_score [B, 2 beam], hist_word / hist_parent / hist_score [t_end, R],
         hist_attn [t_end, R, Tp])."""
         t0 = time.perf_counter()
-        B, R, Tp = self.B, self.R, ctx.shape[1]
+        B, Tp = self.B, ctx.shape[1]
         if ctx.shape[0] != B:
             raise ValueError('DeviceSpeakerBeam built for %d paths, got %d' % (B, ctx.shape[0]))
         self._reserve(Tp)
+        self.Tp = Tp
         self.w = self.dec._w_struct()
         wb = bytes(self.w)
         if wb != self.baked:                                             # a weight (or its cached table) moved
             self.graph_by_tp, self.baked = {}, wb
         graph = None
         if self.graphs:
-            graph = self.graph_by_tp.get(Tp) or self._capture(Tp)
+            graph = self.graph_by_tp.get(Tp) or self._capture()
         cv, mv, _ = self._views(Tp)
         cv.copy_(ctx)
         mv.copy_(path_mask.to(torch.uint8))
         self.tape['h1'].view(B, self.beam, self.H)[:, 0].copy_(h)
         self.tape['c1'].view(B, self.beam, self.H)[:, 0].copy_(c)
-        self.rec[:self.hdr].copy_(self.head0)
+        rec = self._record(Tp)
+        self.rec[:rec.hdr].copy_(self.head0)
         self.words.copy_(self.words0)
         self.parent.copy_(self.parent0)
         self.score.zero_()
-        reads, issued = 0, 0
-        while issued < self.T:
-            if graph is not None:
-                graph.replay()
-            else:
-                self._issue(Tp, self.chunk)
-            issued += self.chunk
-            if issued >= self.T:
-                break
-            reads += 1
-            if int(self.rec[self.o_live + issued - 1].item()) == 0:     # nothing live after the chunk's last step
-                break
-        S = R * (3 + Tp)
-        flat = self.rec[:self.hdr + min(issued, self.T) * S].cpu().numpy()       # the one download of the results
-        reads += 1
-        self.last_host_reads = reads
-        self.host_reads += reads
-        self.minibatches += 1
-        self.last_run_s = time.perf_counter() - t0
-        inst = flat[:3 * B].reshape(B, 3)
-        t_end = int(inst[:, 2].max())                                    # (the step after the last one any path ran)
-        fl = flat.view(np.float32)
-        done_rec = flat[self.o_done:self.o_dscore].reshape(B, 2 * self.beam)
-        done_score = fl[self.o_dscore:self.o_dscore + 2 * self.beam * B].reshape(B, 2 * self.beam)
-        st = flat[self.hdr:self.hdr + t_end * S].reshape(t_end, S)
-        stf = fl[self.hdr:self.hdr + t_end * S].reshape(t_end, S)
-        return dict(inst=inst, done_rec=done_rec, done_score=done_score, hist_word=st[:, :R], hist_parent=st[:, R:2 * R],
-                    hist_score=stf[:, 2 * R:3 * R], hist_attn=stf[:, 3 * R:].reshape(t_end, R, Tp))
+        steps, reads = self._run_chunks(graph, self.T, self.rec[rec.o_live:])
+        flat = self.rec[:rec.hdr + steps * rec.stride].cpu().numpy()     # the one download of the results
+        self._count_run(reads + 1, t0)
+        return rec.split(flat, attn='hist_attn')
 
 
 def speaker_beam_nodes(hist, B, beam_size):
@@ -1041,12 +1106,8 @@ def speaker_beam_search_device(speaker, beam_size, path_obs, path_actions, chunk
     with torch.no_grad():
         ctx, h_t, c_t = speaker.encoder(acts, feats)
         key = (id(speaker.decoder), B, beam_size, speaker.instruction_len, int(chunk), bool(graphs))
-        cache = speaker.__dict__.setdefault('_device_beams', {})
-        db = cache.get(key)
-        if db is None or db.dec is not speaker.decoder:
-            if len(cache) >= 4:
-                cache.clear()
-            db = cache[key] = DeviceSpeakerBeam(speaker.decoder, B, beam_size, speaker.instruction_len, chunk, graphs)
+        db = _owner_cache(speaker, '_device_beams', key, 4, lambda: DeviceSpeakerBeam(
+            speaker.decoder, B, beam_size, speaker.instruction_len, chunk, graphs), dec=speaker.decoder)
         speaker.device_beam = db
         hist = db.run(ctx.detach().contiguous(), path_mask, h_t.detach(), c_t.detach())
     done, P, W, S, rows = speaker_beam_nodes(hist, B, beam_size)
@@ -1055,7 +1116,7 @@ def speaker_beam_search_device(speaker, beam_size, path_obs, path_actions, chunk
                                          lambda r: list(att[r]) if r else [], getattr(speaker.env, 'tokenizer', None))
 
 
-class DeviceFollowerBeam:
+class DeviceFollowerBeam(_DeviceLoop):
     """The follower's beam search (follower.py:541-718) with its step loop on the device: R = B * beam_size fixed
     hypothesis slots (instance b owns slots b*beam_size ..), per decode step
 
@@ -1073,7 +1134,7 @@ class DeviceFollowerBeam:
 
     Inference only; beam_size <= MAX_BEAM (one wavefront per instance in the selection kernel)."""
     MAX_BEAM = 64
-    N_INT = 6                                     # history arrays besides the attention: parent action rank sid psid score
+    PLANES = ('parent', 'action', 'rank', 'sid', 'psid', 'score')     # the history arrays besides the attention
 
     def __init__(self, decoder, store, nav, B, beam_size, episode_len, t_max, chunk=2, graphs=True, gate_weights='fp32'):
         self.gate_weights = check_gate_weights(gate_weights)
@@ -1094,9 +1155,7 @@ class DeviceFollowerBeam:
         # slot state: (row, view) of the slots [0, R) and of their parents [R, 2R), previous action, parent slot, score
         self.rv = i32(2, 2 * R)
         self.act, self.parent, self.score = i32(R), i32(R), f32(R)
-        self.obs2 = dict(row=i32(2 * R), vp=i32(2 * R), view=i32(2 * R), a_num=i32(2 * R),
-                         cand_view=i32(2 * R, A), sincos=f32(2 * R, A, 4))
-        self.obs = [{k: v[j * R:(j + 1) * R] for k, v in self.obs2.items()} for j in range(2)]
+        self.obs2, self.obs = _observation_buffers(R, A, dev)
         self.h0, self.c0 = f32(R, H), f32(R, H)
         self.tape = decoder_tape(R, H, store.F, self.D, store.V, T, A, dev)
         for v in self.tape.values():
@@ -1106,90 +1165,36 @@ class DeviceFollowerBeam:
         self.crow = (torch.arange(R, device=dev, dtype=torch.int32) // beam_size).contiguous()
         self.ctx = f32(B, T, H)
         self.mask = torch.ones(B, T, dtype=torch.uint8, device=dev)
-        # the record: [inst B x 3 | live_total E | done_rec B x 2 beam | done_score B x 2 beam] then per step
-        # [parent R | action R | rank R | sid R | psid R | score R | attention R x T] -- one download at the end
-        self.o_live = 3 * B
-        self.o_done = self.o_live + episode_len
-        self.o_dscore = self.o_done + 2 * beam_size * B
-        self.hdr = (self.o_dscore + 2 * beam_size * B + 3) & ~3
-        self.S = R * (self.N_INT + T)
-        self.rec = i32(self.hdr + episode_len * self.S)
+        self.record = BeamRecord(B, beam_size, episode_len, self.PLANES, T)        # one download at the end
+        self.rec = i32(self.record.size)
         self.pin = torch.zeros(self.rec.numel(), dtype=torch.int32).pin_memory()
-        head0 = torch.zeros(self.hdr, dtype=torch.int32)
-        head0[0:3 * B:3] = 1                                           # one live slot per instance, nothing done, t = 0
-        self.head0 = head0.to(dev)
+        self.head0 = torch.from_numpy(self.record.head0()).to(dev)
         self.parent0 = torch.full((R,), -1, device=dev, dtype=torch.int32)
         self.parent0[::beam_size] = torch.arange(0, R, beam_size, device=dev, dtype=torch.int32)
-        self.graph = self.baked = self._side = None
-        self.captures = 0
-        self.host_reads = self.last_host_reads = 0
-        self.minibatches, self.last_run_s = 0, 0.0          # (last_run_s: the step loop and its download, seconds)
+        self.graph = self.baked = None
         self.last = None                                    # what the last run returned
 
     @classmethod
     def supports(cls, beam_size, decoder=None):
         return 1 <= beam_size <= cls.MAX_BEAM and (decoder is None or hasattr(decoder, 'visual_attention_layer'))
 
-    def _struct(self):
-        R, base = self.R, self.rec.data_ptr()
-        steps = base + 4 * self.hdr
-        return _lib.FolBeam(self.B, self.beam, self.k, self.E, self.T, 0, self.nav.struct(),
-                            self.score.data_ptr(), self.rv[0].data_ptr(), self.rv[1].data_ptr(), self.act.data_ptr(),
-                            self.parent.data_ptr(), base, base + 4 * self.o_live,
-                            *(steps + 4 * j * R for j in range(self.N_INT + 1)), self.S,
-                            base + 4 * self.o_done, base + 4 * self.o_dscore)
-
-    def _issue(self, n_steps):
-        st, R, A, H = self.store, self.R, self.A, self.H
-        s = stream()
-        ns = self.nav.struct()
-        o = self.obs2
-        cur, par = self.obs
-        fb = self._struct()
-        ucand = st.cands(par['vp'], par['cand_view'], par['sincos'], par['a_num'], A)
-        pano = st.pano(cur['vp'], cur['view'])
-        cnd = st.cands(cur['vp'], cur['cand_view'], cur['sincos'], cur['a_num'], A)
-        w = decoder_w_struct(decoder_params(self.dec))
-        tp = tape_struct(self.tape)
-        gat = (_lib.RowMove * 2)(
-            _lib.RowMove(self.tape['h1'].data_ptr(), self.h0.data_ptr(), self.parent.data_ptr(), H, H, H, 0),
-            _lib.RowMove(self.tape['c1'].data_ptr(), self.c0.data_ptr(), self.parent.data_ptr(), H, H, H, 0))
-        for _ in range(n_steps):
-            call('sf_nav_step', byref(ns), 2 * R, ptr(self.rv[0]), ptr(self.rv[1]), None, None, None, 0, None,
-                 ptr(o['row']), ptr(o['vp']), ptr(o['view']), ptr(o['a_num']), ptr(o['cand_view']), ptr(o['sincos']),
-                 None, s)
-            # (the previous action's embedding straight into the first half of the LSTM input rows)
-            call('sf_gather_actions_ld', byref(ucand), R, ptr(self.act), ptr(self.tape['xin']), 2 * st.F, s)
-            call('sf_move_rows', gat, 2, R, s)
-            with _gate_pass(self):
-                call('sf_attn_decoder_fwd', byref(w), byref(pano), byref(cnd), R, H, self.D, self.T,
-                     None, ptr(self.h0), ptr(self.c0), ptr(self.ctx), ptr(self.mask), ptr(self.crow), byref(tp), None,
-                     None, 0, *ws_args(self.dev))
-            call('sf_logprob_topk', ptr(self.tape['logit']), A, R, A, ptr(cur['a_num']), self.k, ptr(self.idx),
-                 ptr(self.logp), s)
-            call('sf_follower_beam_select', byref(fb), ptr(self.idx), ptr(self.logp), ptr(self.tape['alpha']), s)
-        self._keep = (ns, fb, ucand, pano, cnd, w, tp, gat)
+    def _issue_steps(self, n_steps):
+        fb = _lib.FolBeam(self.B, self.beam, self.k, self.E, self.T, 0, self.nav.struct(),
+                          self.score.data_ptr(), self.rv[0].data_ptr(), self.rv[1].data_ptr(), self.act.data_ptr(),
+                          self.parent.data_ptr(), *self.record.pointers(self.rec.data_ptr()))
+        # (h / c of every slot from its parent slot; crow = the slot's instance)
+        self._keep = (fb, _follower_steps(
+            self, n_steps, self.R, self.rv[0], self.rv[1], self.act, self.tape['h1'], self.tape['c1'], self.parent,
+            self.crow, self.k, self.idx, self.logp,
+            lambda s: call('sf_follower_beam_select', byref(fb), ptr(self.idx), ptr(self.logp), ptr(self.tape['alpha']), s)))
 
     def _capture(self):
         # dead slots for the warm-up step (every instance ended: the selection changes nothing)
-        self.rec[:self.hdr].zero_()
+        self.rec[:self.record.hdr].zero_()
         self.rv.zero_()
         self.act.zero_()
         self.parent.fill_(-1)
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.dev)              # (one capture stream: its workspace is baked)
-            ensure_workspace(self._side, self.dev)
-        side = self._side
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.no_grad(), torch.cuda.stream(side):
-            self._issue(1)                                               # warm-up: cached layouts, lazy tables
-            side.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with graph_capture(graph, side):
-                self._issue(self.chunk)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = graph
-        self.captures += 1
+        self.graph = self._capture_steps(self.chunk)
 
     # ---- per minibatch
     def run(self, ctx, mask, h, c, root_sid):
@@ -1197,7 +1202,7 @@ class DeviceFollowerBeam:
         [B].  Returns host arrays: inst [B,3], done_rec / done_score [B, 2 beam], parent / action / rank / sid / psid
         / score [t_end, R], attn [t_end, R, T] (views of one pinned buffer: valid until the next run)."""
         t0 = time.perf_counter()
-        B, R, W = self.B, self.R, self.beam
+        B, R, W, rec = self.B, self.R, self.beam, self.record
         Tm = ctx.shape[1]
         if ctx.shape[0] != B or Tm > self.T:
             raise ValueError('DeviceFollowerBeam built for %d instructions of <= %d tokens' % (B, self.T))
@@ -1214,47 +1219,19 @@ class DeviceFollowerBeam:
         sid = np.repeat(np.asarray(root_sid, np.int64), W)               # every slot starts on a valid state
         rv0 = np.stack((np.tile(sid // 36, 2), np.tile(sid % 36, 2))).astype(np.int32)
         self.rv.copy_(torch.from_numpy(rv0))
-        self.rec[:self.hdr].copy_(self.head0)
-        self.rec[self.hdr:].zero_()                                      # (nothing of an earlier search in the download)
-        self.rec[self.hdr:].view(self.E, self.S)[:, R:2 * R].fill_(-1)  # hist_action: -1 = no selection there
+        self.rec[:rec.hdr].copy_(self.head0)
+        self.rec[rec.hdr:].zero_()                                       # (nothing of an earlier search in the download)
+        self.rec[rec.hdr:].view(self.E, rec.stride)[:, R:2 * R].fill_(-1)     # action: -1 = no selection there
         self.act.zero_()
         self.parent.copy_(self.parent0)
         self.score.zero_()
-        reads, issued = 0, 0
-        while issued < self.E:
-            if self.graphs:
-                self.graph.replay()
-            else:
-                self._issue(self.chunk)
-            issued += self.chunk
-            if issued >= self.E:
-                break
-            reads += 1
-            if int(self.rec[self.o_live + issued - 1].item()) == 0:     # nothing live after the chunk's last step
-                break
-        n = self.hdr + min(issued, self.E) * self.S
+        steps, reads = self._run_chunks(self.graph, self.E, self.rec[rec.o_live:])
+        n = rec.hdr + steps * rec.stride
         self.pin[:n].copy_(self.rec[:n], non_blocking=True)              # the one download of the results
         torch.cuda.current_stream().synchronize()
-        reads += 1
-        self.last_host_reads = reads
-        self.host_reads += reads
-        self.minibatches += 1
-        self.last_run_s = time.perf_counter() - t0
-        flat = self.pin.numpy()
-        inst = flat[:3 * B].reshape(B, 3)
-        t_end = int(inst[:, 2].max())                                    # (the step after the last one any instance ran)
-        fl = flat.view(np.float32)
-        S, NI = self.S, self.N_INT
-        st = flat[self.hdr:self.hdr + t_end * S].reshape(t_end, S)
-        stf = fl[self.hdr:self.hdr + t_end * S].reshape(t_end, S)
-        out = dict(inst=inst, done_rec=flat[self.o_done:self.o_dscore].reshape(B, 2 * W),
-                   done_score=fl[self.o_dscore:self.o_dscore + 2 * W * B].reshape(B, 2 * W))
-        for j, name in enumerate(('parent', 'action', 'rank', 'sid', 'psid')):
-            out[name] = st[:, j * R:(j + 1) * R]
-        out['score'] = stf[:, (NI - 1) * R:NI * R]
-        out['attn'] = stf[:, NI * R:].reshape(t_end, R, self.T)
-        self.last = out
-        return out
+        self._count_run(reads + 1, t0)
+        self.last = rec.split(self.pin.numpy())
+        return self.last
 
 
 def follower_beam_key(agent, nav, B, beam_size, t_max, chunk, graphs, gate_weights):
@@ -1270,14 +1247,10 @@ def follower_beam_for(agent, nav, B, beam_size, chunk, graphs):
     # storage of Seq2SeqAgent.gate_weights)
     mode = getattr(agent, 'gate_weights', 'fp32')
     key = follower_beam_key(agent, nav, B, beam_size, t_max, chunk, graphs, mode)
-    cache = agent.__dict__.setdefault('_device_beams', {})
-    db = cache.get(key)
-    if db is None or db.dec is not agent.decoder or db.store is not agent.store or db.nav is not nav:
-        if len(cache) >= 4:
-            cache.clear()
-        db = cache[key] = DeviceFollowerBeam(agent.decoder, agent.store, nav, B, beam_size, agent.episode_len, t_max,
-                                             chunk, graphs, gate_weights=mode)
-    return db
+    return _owner_cache(agent, '_device_beams', key, 4,
+                        lambda: DeviceFollowerBeam(agent.decoder, agent.store, nav, B, beam_size, agent.episode_len, t_max,
+                                                   chunk, graphs, gate_weights=mode),
+                        dec=agent.decoder, store=agent.store, nav=nav)
 
 
 @gc_paused

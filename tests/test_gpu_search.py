@@ -445,6 +445,14 @@ def test_graph_step_equals_host_issued_steps_and_survives_pool_growth(world):
     Tn = fd.apool.buf.shape[1]
     np.testing.assert_allclose(gs.apool[B:B + n, :Tn].cpu().numpy(), fd.apool.buf[base:base + n].cpu().numpy(), atol=2e-5)
     assert float(gs.apool[B:B + n, Tn:].abs().max()) == 0.0                        # padded instruction positions: weight 0
+    # a second growth re-captures on the object's ONE capture stream: no further workspace is left behind
+    from speaker_follower_amd import runtime
+    side, n_ws, captures, rows = gs._side, len(runtime._workspaces), gs.captures, gs.pool_rows
+    assert side is not None and captures >= 2                                      # (load, then the growth above)
+    gs._grow(rows + 1)
+    assert gs.pool_rows > rows and gs.captures == captures + 1
+    assert gs._side is side
+    assert len(runtime._workspaces) == n_ws
     agent.__dict__.pop('_graph_steps', None)
 
 
