@@ -517,7 +517,9 @@ typedef struct sf_encoder_w {
      * has >= 256 CUs, the T recurrent steps run as ONE persistent launch (csrc/sf_persist.hip: W_hh in
      * registers, the batch partitioned across the XCDs, h exchanged inside a partition); results are
      * bit-identical to the one-launch-per-step path for B > 16 (same summation order as its
-     * 32-row kernel; within 2e-6 of its 16-row kernel below that).  SF_ENC_PER_STEP forces per-step. */
+     * 32-row kernel; within 2e-6 of its 16-row kernel below that).  SF_ENC_PER_STEP forces per-step.
+     * LIMIT of the per-step path: its kernels cover a reduction of at most 64 chunks of 16, i.e. H <= 1024 (H % 16 == 0);
+     * above that sf_encoder_lstm_fwd returns SF_ERR_UNSUPPORTED (tests/test_gpu_lstm_steps.py pins it at H = 1040). */
     int32_t flags;
 } sf_encoder_w;
 #define SF_ENC_PER_STEP 1
