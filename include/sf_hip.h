@@ -1291,6 +1291,66 @@ typedef struct sf_state_search {
 int sf_state_factored_select(const sf_state_search* s, const float* logp, int ld_logp, int32_t* dev_in,
                              sf_stream stream);
 
+/* Scoring of navigation results (tasks/R2R/eval.py:23-139; speaker_follower_amd/evaluation.py), additive to ABI 9.
+ *
+ * sf_eval_distances: the all-pairs shortest-path distances of n_scans graphs in ONE launch.  A graph is given as the
+ * CSR of its IN-edges with nodes in local index order: scan k owns the global nodes node_off[k] .. node_off[k+1] - 1
+ * (m_k of them), global node g the edges edge_off[g] .. edge_off[g+1] - 1, edge e comes from LOCAL node edge_src[e]
+ * of the same scan with weight edge_w[e] > 0.  The result of scan k is the float64 block D[src][dst], m_k x m_k
+ * row-major, at element dist_off[k] of `table`: the fixed point of D[s][s] = 0, D[s][v] = min(D[s][v], min over
+ * in-edges (u, v) of D[s][u] + w(u, v)), iterated synchronously from +inf until a round changes nothing -- with
+ * positive weights and monotone rounding that system has ONE solution, the numbers a Dijkstra search accumulating
+ * d + w outward from s produces, to the last bit.  One float64 add and one compare per edge and
+ * round, no fused multiply-add, no re-association; pairs without a path stay +inf.  One wavefront per source, its
+ * distance vector (two copies) in LDS; after at most m_k rounds the loop ends, and err[0] is set to 1 if round m_k
+ * still changed a value (impossible with positive weights).  err[0] is only ever raised: the caller zeroes it.
+ *   n_nodes = node_off[n_scans], max_nodes = the largest m_k (host copies: the launcher sizes the grid from them).
+ *   SF_ERR_ARG on NULL pointers, n_scans < 1, n_nodes < 1, max_nodes < 1 or > n_nodes; SF_ERR_UNSUPPORTED, with
+ *   nothing launched, for max_nodes > sf_eval_max_nodes() = SF_EVAL_MAX_NODES (512: 8 KB of LDS per source; the
+ *   largest R2R scan has 348 viewpoints) -- the caller then computes the scans above the limit on the host and
+ *   issues the others.  sf_debug_eval_max_nodes(n) lowers the limit (n in 1..512; anything else restores it), for tests.
+ * sf_eval_distances_bytes: the bytes of a table that holds n_scans blocks back to back, 8 * sum of m[k]^2 over the
+ *   HOST array m [n_scans]; 0 for NULL, n_scans < 1 or a negative m[k]. */
+#define SF_EVAL_MAX_NODES 512
+typedef struct sf_eval_graphs {
+    int32_t n_scans, n_nodes, max_nodes, reserved;
+    const int32_t* node_off;   /* [n_scans + 1] */
+    const int32_t* edge_off;   /* [n_nodes + 1] */
+    const int32_t* edge_src;   /* [n_edges] local index of the edge's source node */
+    const double* edge_w;      /* [n_edges] */
+    const int64_t* dist_off;   /* [n_scans] first element of the scan's block in the table */
+} sf_eval_graphs;
+size_t sf_eval_distances_bytes(const int32_t* m, int n_scans);
+int sf_eval_max_nodes(void);
+void sf_debug_eval_max_nodes(int n);
+int sf_eval_distances(const sf_eval_graphs* g, double* table, int32_t* err, sf_stream stream);
+/* sf_eval_score: eval.py:46-84 for the B episodes of a rollout, one thread each.  row [S+1,B] are the nav rows the
+ * rollout visited, actions [S,B] what it chose; sample b's scan owns the nav rows scan_base[b] .. scan_base[b] +
+ * m[b] - 1 and the block at element dist_off[b] of `table` (local index = row - scan_base[b]).
+ *   n             index of the first action 0 (stop) plus 1, else S: the path is row[0..n]
+ *   nav_error     D[row[n]][goal_row[b]]
+ *   oracle_error  the FIRST minimum of D[row[t]][goal] over t = 0..n (strict <, from t = 0)
+ *   length        0.0 + D[row[0]][row[1]] + ... + D[row[n-1]][row[n]], added in path order
+ *   steps = n, success = nav_error < margin, oracle_success = oracle_error < margin
+ * written at slot[b] of the six arrays ([n_slots]: three float64, three int32); slot[b] == -1 writes nothing.  A row
+ * or goal outside its scan, or a slot outside [-1, n_slots), writes nothing and sets err[0] = 1 (only ever raised).
+ * SF_ERR_ARG on NULL pointers, S < 1, B < 1, n_slots < 1. */
+typedef struct sf_eval_episodes {
+    int32_t S, B, n_slots, reserved;
+    const int32_t* row;        /* [S+1, B] */
+    const int64_t* actions;    /* [S, B] */
+    const int32_t* goal_row;   /* [B] nav row of the goal */
+    const int32_t* scan_base;  /* [B] */
+    const int32_t* m;          /* [B] */
+    const int64_t* dist_off;   /* [B] */
+    const int32_t* slot;       /* [B] */
+    const double* table;
+    double margin;
+    double *nav_error, *oracle_error, *length;      /* [n_slots] */
+    int32_t *steps, *success, *oracle_success;      /* [n_slots] */
+} sf_eval_episodes;
+int sf_eval_score(const sf_eval_episodes* e, int32_t* err, sf_stream stream);
+
 /* In-process kernel timing (no reference counterpart; what bench.py's `roofline.kernels` table is
  * measured with).  Between sf_profile_begin() and sf_profile_end() every kernel ANY host thread of the
  * process launches through this library (torch runs backward() on its own thread) carries a start and a stop event on its own dispatch, so a

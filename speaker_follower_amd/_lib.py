@@ -179,6 +179,20 @@ class StateSearch(C.Structure):
     _fields_ = [(n, C.c_int32) for n in SIZES] + [('nav', NavTableS)] + [(n, c_p) for n in POINTERS]
 
 
+class EvalGraphs(C.Structure):
+    """sf_eval_graphs: the in-edge CSR of the scans whose distances sf_eval_distances builds."""
+    _fields_ = ([(n, C.c_int32) for n in ('n_scans', 'n_nodes', 'max_nodes', 'reserved')] +
+                [(n, c_p) for n in ('node_off', 'edge_off', 'edge_src', 'edge_w', 'dist_off')])
+
+
+class EvalEpisodes(C.Structure):
+    """sf_eval_episodes: one rollout's episodes and the six per-split arrays sf_eval_score fills."""
+    _fields_ = ([(n, C.c_int32) for n in ('S', 'B', 'n_slots', 'reserved')] +
+                [(n, c_p) for n in ('row', 'actions', 'goal_row', 'scan_base', 'm', 'dist_off', 'slot', 'table')] +
+                [('margin', C.c_double)] +
+                [(n, c_p) for n in ('nav_error', 'oracle_error', 'length', 'steps', 'success', 'oracle_success')])
+
+
 SEARCH_OVF_NODES, SEARCH_OVF_SLOTS, SEARCH_OVF_VISITS, SEARCH_OVF_POOL, SEARCH_OVF_KEY = 1, 2, 4, 8, 16
 
 i32, u32, i64p = C.c_int, C.c_uint32, C.c_void_p
@@ -339,6 +353,11 @@ _SIGNATURES = {
     'sf_embedding_fwd': (C.c_int, [c_f, i32, i64p, i32, c_f, c_p]),
     'sf_transpose': (C.c_int, [c_f, i32, i32, c_f, c_p]),
     'sf_nav_step': (C.c_int, [P(NavTableS), i32] + [c_p] * 5 + [i32] + [c_p] * 8 + [c_p]),
+    'sf_eval_distances_bytes': (C.c_size_t, [P(C.c_int32), C.c_int]),
+    'sf_eval_max_nodes': (C.c_int, []),
+    'sf_debug_eval_max_nodes': (None, [C.c_int]),
+    'sf_eval_distances': (C.c_int, [P(EvalGraphs), c_p, c_p, c_p]),
+    'sf_eval_score': (C.c_int, [P(EvalEpisodes), c_p, c_p]),
     'sf_profile_begin': (C.c_int, []),
     'sf_profile_end': (C.c_long, [C.c_char_p, C.c_size_t]),
 }

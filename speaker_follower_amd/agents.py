@@ -231,6 +231,22 @@ class Seq2SeqAgent(BaseAgent):
         return (id(nav), id(eng), self.episode_len, n_items, self.max_instruction_length,
                 self.reverse_instruction) + gate_mode_key(eng.gate_weights)
 
+    def _capture_test_rollout(self, nav, items, key, host=None):
+        """Captures the inference rollout of `key` over a fixed-shape batch holding `items` and keeps it (at most three
+        captures are kept): (replay, state, batch, nav, pinned result buffers)."""
+        from .nav import DeviceNavBatch
+        graphs = self.__dict__.setdefault('_test_graphs', {})
+        S = self.episode_len
+        batch = DeviceNavBatch(nav, items, S, max_length=self.max_instruction_length,
+                               reverse=self.reverse_instruction, fixed_shapes=True, host=host)
+        replay, st = self._engine.capture(batch, S, 'argmax')
+        pinned = [torch.empty(t.shape, dtype=t.dtype).pin_memory()
+                  for t in (batch.row[:S + 1], batch.view[:S + 1], st.actions, st.step_scores, st.loss_buf)]
+        while len(graphs) >= 3:
+            graphs.pop(next(iter(graphs)))
+        graphs[key] = (replay, st, batch, nav, pinned)  # (nav kept alive: the key holds its id)
+        return graphs[key]
+
     def _rollout_on_graph(self, nav, items, host=None):
         """An inference rollout (agent.test, follower.py:987-999) as ONE graph replay over a fixed-shape minibatch: the
         items are written into the captured batch's tensors (one pinned copy), the next minibatch is peeked and encoded
@@ -258,14 +274,7 @@ class Seq2SeqAgent(BaseAgent):
         for attempt in () if hit else (0, 1):
             cached = graphs.get(key)
             if cached is None:
-                batch = DeviceNavBatch(nav, items, S, max_length=self.max_instruction_length,
-                                       reverse=self.reverse_instruction, fixed_shapes=True, host=host)
-                replay, st = eng.capture(batch, S, 'argmax')
-                pinned = [torch.empty(t.shape, dtype=t.dtype).pin_memory()
-                          for t in (batch.row[:S + 1], batch.view[:S + 1], st.actions, st.step_scores, st.loss_buf)]
-                while len(graphs) >= 3:
-                    graphs.pop(next(iter(graphs)))
-                graphs[key] = (replay, st, batch, nav, pinned)  # (nav kept alive: the key holds its id)
+                replay, st, batch, _, pinned = self._capture_test_rollout(nav, items, key, host)
             else:
                 replay, st, batch, _, pinned = cached
                 batch.load(items, host)

@@ -1,0 +1,2 @@
+"""`import eval` (train.py:17; `eval.Evaluation([split])`, train.py:206) / `from eval import Evaluation` (plot.py:7)."""
+from speaker_follower_amd.evaluation import Evaluation, EvalResult      # noqa: F401

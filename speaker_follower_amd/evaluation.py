@@ -1,0 +1,470 @@
+"""Scoring of navigation results (tasks/R2R/eval.py:23-139): navigation error = shortest-path distance from the LAST
+viewpoint of a trajectory to the goal, oracle error = from the closest viewpoint on it, success = error < 3 m, the
+summary averages over the instructions '<path_id>_0' .. '_2' of the split.
+
+  * `DistanceTable`   the all-pairs distances of a set of scans as ONE float64 table, scan blocks back to back,
+                      D[src][dst] over the INCLUDED viewpoints in connectivity-file order (the local order of
+                      nav.NavTable's rows).  Built once: by sf_eval_distances (csrc/sf_eval.hip) when a GPU is
+                      present, else from env.NavGraph.shortest -- the same numbers to the last bit,
+                      source-major: D[a][b] and D[b][a] differ in their last bits for half of all pairs.
+  * `Evaluation`      eval.py's class: `_score_item`, `score_results`, `score_file` with the reference's contract, and
+                      `score_agent`: agent.test() + score_results as one device sweep with one host sync.
+
+The reference takes its table from networkx (all_pairs_dijkstra_path_length); nothing here imports it.
+"""
+import ctypes as C
+import json
+import os
+import random
+from collections import defaultdict, namedtuple
+
+import numpy as np
+
+EvalResult = namedtuple('EvalResult', 'nav_error, oracle_error, trajectory_steps, trajectory_length, success, '
+                                      'oracle_success')                                          # eval.py:18-20
+
+DATA_JSON = 'tasks/R2R/data/R2R_%s.json'                                 # utils.py:54-59
+CONNECTIVITY = 'connectivity'
+
+_LISTS = ('nav_errors', 'oracle_errors', 'trajectory_steps', 'trajectory_lengths', 'success', 'oracle_success')
+
+
+class DistanceTable:
+    """scan -> m x m float64 block D[src][dst] of one flat table (`host`; `dev` when it was built on the device)."""
+
+    def __init__(self, graphs, device=None):
+        """graphs: scan -> env.NavGraph.  device: where to build the table and keep it (None: the current GPU when there
+        is one, else 'cpu': NavGraph.shortest, host copy only)."""
+        self.scans = sorted(graphs)
+        self.graphs = graphs
+        self.nodes, self.index, self.m, self.off = {}, {}, {}, {}
+        total = 0
+        for s in self.scans:
+            g = graphs[s]
+            nodes = [v for v, inc in zip(g.ids, g.included) if inc]
+            self.nodes[s], self.index[s] = nodes, {v: i for i, v in enumerate(nodes)}
+            self.m[s], self.off[s] = len(nodes), total
+            total += len(nodes) ** 2
+        self.host = np.full(total, np.inf, np.float64)
+        self.dev = None
+        self.on_host = []                                    # scans whose block came from NavGraph.shortest
+        import torch
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else 'cpu'
+        device = torch.device(device)
+        if device.type == 'cuda' and total:
+            self._build_on_device(device)
+        else:
+            for s in self.scans:
+                self._fill_from_host(s)
+
+    def block(self, scan):
+        m = self.m[scan]
+        return self.host[self.off[scan]:self.off[scan] + m * m].reshape(m, m)
+
+    def _fill_from_host(self, scan):
+        """The scan's block from NavGraph.shortest(src): Dijkstra accumulating d + w outward from the source."""
+        g, ix, D = self.graphs[scan], self.index[scan], self.block(scan)
+        for i, v in enumerate(self.nodes[scan]):
+            for u, d in g.shortest(v)[0].items():
+                D[i, ix[u]] = d
+        self.on_host.append(scan)
+
+    def in_edge_csr(self, scans):
+        """The in-edge CSR sf_eval_distances reads (include/sf_hip.h: sf_eval_graphs) of `scans`, as host arrays."""
+        node_off, edge_off, src, w, dist_off = [0], [0], [], [], []
+        for s in scans:
+            ix, into = self.index[s], {v: [] for v in self.nodes[s]}
+            for u, nb in self.graphs[s].adj.items():
+                for v, wt in nb.items():
+                    into[v].append((ix[u], wt))
+            for v in self.nodes[s]:
+                src += [u for u, _ in into[v]]
+                w += [wt for _, wt in into[v]]
+                edge_off.append(len(src))
+            node_off.append(node_off[-1] + self.m[s])
+            dist_off.append(self.off[s])
+        return (np.asarray(node_off, np.int32), np.asarray(edge_off, np.int32), np.asarray(src, np.int32),
+                np.asarray(w, np.float64), np.asarray(dist_off, np.int64))
+
+    def _build_on_device(self, device):
+        import torch
+        from . import _lib
+        from .runtime import stream
+        limit = _lib.lib.sf_eval_max_nodes()
+        small = [s for s in self.scans if 0 < self.m[s] <= limit]
+        with torch.cuda.device(device):
+            self.dev = torch.full((len(self.host),), float('inf'), dtype=torch.float64, device=device)
+            if small:
+                arrays = self.in_edge_csr(small)
+                up = [torch.from_numpy(a).to(device) for a in arrays]
+                err = torch.zeros(1, dtype=torch.int32, device=device)
+                g = _lib.EvalGraphs(len(small), int(arrays[0][-1]), max(self.m[s] for s in small), 0,
+                                    *[t.data_ptr() for t in up])
+                _lib.call('sf_eval_distances', C.byref(g), C.c_void_p(self.dev.data_ptr()),
+                          C.c_void_p(err.data_ptr()), stream())
+                self.host[:] = self.dev.cpu().numpy()
+                if int(err.item()):
+                    raise RuntimeError('sf_eval_distances: a graph did not settle in as many rounds as it has nodes '
+                                       '(an edge weight that is not positive?)')
+            big = [s for s in self.scans if self.m[s] > limit]
+            for s in big:                                    # above the kernel's LDS budget: this block from the host
+                self._fill_from_host(s)
+            if big:
+                self.dev.copy_(torch.from_numpy(self.host))
+
+
+def _load_graphs(scans, nav_graph_path=CONNECTIVITY):
+    from .env import NavGraph
+    return {s: NavGraph(os.path.join(nav_graph_path, s + '_connectivity.json')) for s in sorted(scans)}
+
+
+class Evaluation(object):
+    """eval.py:23-139.  Results: {instr_id: {'instr_id', 'trajectory': [(viewpoint_id, heading, elevation), ...]}}.
+
+    Evaluation(splits)                 reads tasks/R2R/data/R2R_<split>.json and connectivity/ relative to the working
+                                       directory, as compat/env.py does (the reference's form)
+    Evaluation(env=env)                the items and graphs of an env.R2RIndexEnv / compat R2RBatch
+    Evaluation(items=..., graphs=...)  items with 'path_id', 'scan', 'path'; graphs: scan -> env.NavGraph"""
+
+    def __init__(self, splits=None, env=None, items=None, graphs=None, nav_graph_path=CONNECTIVITY, device=None):
+        self.error_margin = 3.0
+        if env is not None:
+            items = list(env.data) if items is None else items
+            graphs = env.graphs if graphs is None else graphs
+            splits = list(getattr(env, 'splits', [])) if splits is None else splits
+        elif items is None:
+            items = []
+            for split in splits:
+                with open(DATA_JSON % split) as f:
+                    items += json.load(f)
+        self.splits = list(splits) if splits is not None else []
+        self.gt, self.instr_ids, self.scans = {}, [], []
+        for item in items:
+            if item['path_id'] in self.gt:                   # (an env holds one item per instruction)
+                continue
+            self.gt[item['path_id']] = item
+            self.scans.append(item['scan'])
+            self.instr_ids += ['%d_%d' % (item['path_id'], i) for i in range(3)]                  # eval.py:36-38
+        self.scans = set(self.scans)
+        self.instr_ids = set(self.instr_ids)
+        self._graphs_given, self._nav_graph_path, self._device = graphs, nav_graph_path, device
+        self._table = None
+        self._checked_navs = {}
+        self.fallbacks = 0
+        self.host_syncs = self.last_host_syncs = self.sweeps = 0
+        self._sweep_buffers = {}
+
+    # ---- distances: built once, on first use
+    @property
+    def graphs(self):
+        if self._graphs_given is None:
+            self._graphs_given = _load_graphs(self.scans, self._nav_graph_path)
+        return self._graphs_given
+
+    @property
+    def table(self):
+        if self._table is None:
+            graphs = self.graphs
+            self._table = DistanceTable({s: graphs[s] for s in self.scans}, device=self._device)
+        return self._table
+
+    def distance(self, scan, a, b):
+        """eval.py's distances[scan][a][b]: FROM a TO b."""
+        t = self.table
+        return float(t.block(scan)[t.index[scan][a], t.index[scan][b]])
+
+    # ---- eval.py:46-84
+    def _score_rows(self, scan, rows, goal):
+        """One path as LOCAL node indices of its scan."""
+        D = self.table.block(scan)
+        to_goal = D[rows, goal].tolist()
+        nav_error, oracle_error = to_goal[-1], to_goal[0]
+        for d in to_goal:                                    # the first minimum (eval.py:46-54)
+            if d < oracle_error:
+                oracle_error = d
+        length = 0
+        for d in D[rows[:-1], rows[1:]].tolist():            # in path order (eval.py:69-73)
+            length += d
+        return EvalResult(nav_error=nav_error, oracle_error=oracle_error, trajectory_steps=len(rows) - 1,
+                          trajectory_length=length, success=nav_error < self.error_margin,
+                          oracle_success=oracle_error < self.error_margin)
+
+    def _score_item(self, instr_id, path):
+        gt = self.gt[int(instr_id.split('_')[0])]
+        assert gt['path'][0] == path[0][0], 'Result trajectories should include the start position'
+        ix = self.table.index[gt['scan']]
+        return self._score_rows(gt['scan'], np.fromiter((ix[p[0]] for p in path), np.int64, len(path)),
+                                ix[gt['path'][-1]])
+
+    def _local_rows(self, nav, scan):
+        """First nav row of `scan` in `nav`, after checking ONCE that the table's rows of that scan are this table's
+        nodes in this table's order."""
+        key = (id(nav), scan)
+        if key not in self._checked_navs:
+            t, b = self.table, nav.base[scan]
+            if [v for _, v in nav.vp_of[b:b + nav.scan_rows[scan]]] != t.nodes[scan]:
+                raise ValueError('the navigation table orders the viewpoints of scan %s differently' % scan)
+            self._checked_navs[key] = (nav, b)               # (nav kept alive: the key holds its id)
+        return self._checked_navs[key][1]
+
+    def _score_device_results(self, found):
+        """[(instr_id, result of a device rollout)] -> EvalResults, from the integer nav rows the results hold:
+        vectorised look-ups into the host table, no 'trajectory' built."""
+        t = self.table
+        N = len(found)
+        paths = [res.nav_rows() for _, res in found]
+        n = np.array([len(r) - 1 for _, r in paths], np.int64)
+        L = int(n.max()) + 1
+        local = np.zeros((N, L), np.int64)                   # local node index of every pose, the last one repeated
+        goal, m, off = np.zeros(N, np.int64), np.zeros(N, np.int64), np.zeros(N, np.int64)
+        for i, ((instr_id, _), (nav, rows)) in enumerate(zip(found, paths)):
+            gt = self.gt[int(instr_id.split('_')[0])]
+            scan = gt['scan']
+            assert nav.row_of[(scan, gt['path'][0])] == rows[0], 'Result trajectories should include the start position'
+            local[i, :len(rows)] = np.asarray(rows, np.int64) - self._local_rows(nav, scan)
+            local[i, len(rows):] = local[i, len(rows) - 1]
+            m[i], off[i], goal[i] = t.m[scan], t.off[scan], t.index[scan][gt['path'][-1]]
+        if (local < 0).any() or (local >= m[:, None]).any():
+            raise ValueError('a result holds a nav row outside its scan')
+        every = np.arange(N)
+        row_at = off[:, None] + local * m[:, None]                                 # element of D[pose][0]
+        to_goal = t.host[row_at + goal[:, None]]                                   # [N, L]
+        nav_error = to_goal[every, n]
+        on_path = np.arange(L)[None, :] <= n[:, None]
+        oracle_error = np.where(on_path, to_goal, np.inf).min(1)                   # (the value of the first minimum)
+        length = np.zeros(N, np.float64)
+        for s in range(L - 1):                                                     # in path order (eval.py:69-73)
+            length = length + np.where(s < n, t.host[row_at[:, s] + local[:, s + 1]], 0.0)
+        margin = self.error_margin
+        return [EvalResult(a, b, c, d, a < margin, b < margin)
+                for a, b, c, d in zip(nav_error.tolist(), oracle_error.tolist(), n.tolist(), length.tolist())]
+
+    # ---- eval.py:86-145
+    def score_results(self, results):
+        """results: instr_id -> dictionary with (at least) 'trajectory' -- or a result of a device rollout
+        (nav._Trajectory), which is scored from its nav rows."""
+        self.scores = defaultdict(list)
+        model_scores = []
+        instr_ids = set(self.instr_ids)
+        taken, on_device = [], []
+        for instr_id, result in results.items():
+            if instr_id in instr_ids:
+                instr_ids.remove(instr_id)
+                if hasattr(result, 'nav_rows'):
+                    on_device.append((instr_id, result))
+                    taken.append(None)
+                else:
+                    taken.append(self._score_item(instr_id, result['trajectory']))
+                if 'score' in result:
+                    model_scores.append(result['score'])
+        if on_device:
+            scored = iter(self._score_device_results(on_device))
+            taken = [next(scored) if r is None else r for r in taken]
+        for r in taken:
+            for name, v in zip(_LISTS, (r.nav_error, r.oracle_error, r.trajectory_steps, r.trajectory_length,
+                                        r.success, r.oracle_success)):
+                self.scores[name].append(v)
+        return self._summary(instr_ids, len(taken), model_scores), self.scores
+
+    def _summary(self, missing, instr_count, model_scores):
+        assert len(missing) == 0, 'Missing %d of %d instruction ids from %s' % (
+            len(missing), len(self.instr_ids), ','.join(self.splits))
+        sc = self.scores
+        assert len(sc['nav_errors']) == len(self.instr_ids)
+        summary = {
+            'nav_error': np.average(sc['nav_errors']),
+            'oracle_error': np.average(sc['oracle_errors']),
+            'steps': np.average(sc['trajectory_steps']),
+            'lengths': np.average(sc['trajectory_lengths']),
+            'success_rate': float(sum(sc['success']) / len(sc['success'])),
+            'oracle_rate': float(sum(sc['oracle_success']) / len(sc['oracle_success'])),
+        }
+        if len(model_scores) > 0:
+            assert len(model_scores) == instr_count
+            summary['model_score'] = np.average(model_scores)
+        return summary
+
+    def score_file(self, output_file):
+        with open(output_file) as f:
+            return self.score_results(json.load(f))
+
+    # ---- agent.test() + score_results as one device sweep
+    def _sweepable(self, agent, use_dropout, feedback):
+        """The navigation table to sweep on -- or None where `Seq2SeqAgent._rollout_on_graph` would not take the agent
+        (a process group, no device table, test_graph = False, feedback other than argmax, dropout on) or the
+        distances are not on the device."""
+        if feedback != 'argmax' or use_dropout or not getattr(agent, 'test_graph', False):
+            return None
+        nav = agent._device_table() if hasattr(agent, '_device_table') else None
+        if nav is None or agent._engine is None or agent._engine.group is not None or self.table.dev is None:
+            return None
+        return nav
+
+    def _by_test(self, agent, use_dropout, feedback):
+        self.fallbacks += 1
+        agent.test(use_dropout=use_dropout, feedback=feedback)
+        return self.score_results(agent.results)
+
+    def _buffers(self, dev, K, S, B, keep):
+        """Device arrays and pinned mirrors of a sweep of at most K minibatches, kept between sweeps (a sweep ends with
+        a host sync: nothing of the previous one is in flight when the next one writes them)."""
+        import torch
+        key = (str(dev), K, S, B, len(self.instr_ids))
+        buf = self._sweep_buffers.get(key)
+        if buf is None:
+            n = len(self.instr_ids)
+            d = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)                      # noqa: E731
+            p = lambda *s, dt: torch.empty(*s, dtype=dt).pin_memory()                     # noqa: E731
+            i32, i64, f32, f64 = torch.int32, torch.int64, torch.float32, torch.float64
+            buf = dict(per32=d(K, 4, B, dt=i32), per64=d(K, B, dt=i64), per32_h=p(K, 4, B, dt=i32), per64_h=p(K, B, dt=i64),
+                       out64=d(3, n, dt=f64), out32=d(3, n, dt=i32), out64_h=p(3, n, dt=f64), out32_h=p(3, n, dt=i32),
+                       loss=d(K, dt=f32), loss_h=p(K, dt=f32), sc=d(K, S, B, dt=f32), sc_h=p(K, S, B, dt=f32),
+                       err=d(1, dt=i32), err_h=p(1, dt=i32))
+            self._sweep_buffers = {key: buf}
+        if keep and 'rows_h' not in buf:
+            import torch
+            p = lambda *s, dt: torch.empty(*s, dtype=dt).pin_memory()                     # noqa: E731
+            buf.update(rows_h=p(K, S + 1, B, dt=torch.int32), views_h=p(K, S + 1, B, dt=torch.int32),
+                       acts_h=p(K, S, B, dt=torch.int64))
+        return buf
+
+    def score_agent(self, agent, use_dropout=False, feedback='argmax', keep_results=False):
+        """What `agent.test(use_dropout, feedback)` followed by `score_results(agent.results)` returns, as ONE sweep on
+        the device: the environment is walked exactly as BaseAgent.test walks it (reset_epoch, reset(sort=True) until an
+        id repeats, the first occurrence of an id wins -- `env.ix` and `random` end where test() leaves them), every
+        minibatch's captured rollout is replayed back to back with sf_eval_score behind it on the same stream (ids
+        already issued, and ids outside `instr_ids`, write nothing), and the host waits ONCE, after the last minibatch
+        (`last_host_syncs`; the capture of a rollout nobody has captured yet synchronises on its own).  `agent.losses`
+        is set as test() sets it; `agent.results` stays empty unless keep_results (the row / view / action downloads per
+        minibatch, still without a wait in between).  A raised fault word, or an agent `_rollout_on_graph` does not
+        take, means agent.test() + score_results instead (`fallbacks`): a faulting sweep is never scored, and the
+        environment's item order and `random` are put back first, so that test() walks what the sweep walked."""
+        nav = self._sweepable(agent, use_dropout, feedback)
+        if nav is None:
+            return self._by_test(agent, use_dropout, feedback)
+        import torch
+        from . import _lib
+        from .nav import DeviceNavBatch
+        from .runtime import stream, fault_views, take_fault, WeightsMoved
+        env, eng, t = agent.env, agent._engine, self.table
+        dev = agent._device()
+        agent.feedback = feedback
+        for mod in (agent.encoder, agent.decoder):
+            mod.eval()
+        agent.set_beam_size(1)
+        agent.__dict__.pop('_rollout_inflight', None)         # (nothing issued ahead by an earlier loop is ours)
+        S, B = agent.episode_len, min(env.batch_size, max(1, len(env.data)))
+        K = -(-len(env.data) // B) + 1                        # an id repeats in minibatch ceil(N / B) + 1 at the latest
+        buf = self._buffers(dev, K, S, B, keep_results)
+        per32, per64 = buf['per32_h'].numpy(), buf['per64_h'].numpy()
+        walk0 = (list(env.data), random.getstate())          # (a faulting sweep is undone: test() then walks from here)
+        env.reset_epoch()
+        agent.losses, agent.results = [], {}
+        syncs = 0
+        for w in fault_views(dev):                            # (whatever an earlier pass left behind is not ours)
+            w.zero_()
+        buf['err'].zero_()
+        order, where, seen, issued, looped = [], [], set(), [], False
+        ptr_of = lambda x: x.data_ptr()                       # noqa: E731
+        with torch.no_grad():
+            while not looped:
+                env.reset(sort=True)
+                items = list(env.batch)
+                k = len(issued)
+                if len(items) != B or k >= K:
+                    raise RuntimeError('score_agent: minibatch %d holds %d items (batches of %d, at most %d)'
+                                       % (k, len(items), B, K))
+                for b, it in enumerate(items):
+                    iid, scan = it['instr_id'], it['scan']
+                    slot = -1
+                    if iid in seen:
+                        looped = True
+                    else:
+                        seen.add(iid)
+                        if iid in self.instr_ids:
+                            slot = len(order)
+                            order.append(iid)
+                            where.append((k, b))
+                    goal = self.gt.get(it.get('path_id'), it)['path'][-1]
+                    per32[k, 0, b], per32[k, 1, b] = nav.row_of[(scan, goal)], self._local_rows(nav, scan)
+                    per32[k, 2, b], per32[k, 3, b] = t.m[scan], slot
+                    per64[k, b] = t.off[scan]
+                host = DeviceNavBatch.host_arrays_for(nav, items, agent.max_instruction_length,
+                                                      agent.reverse_instruction, True)
+                key = agent._test_graph_key(nav, eng, B)
+                for attempt in (0, 1):
+                    cached = agent.__dict__.setdefault('_test_graphs', {}).get(key)
+                    if cached is None:
+                        cached = agent._capture_test_rollout(nav, items, key, host)
+                    else:
+                        mirrors = cached[2].__dict__.setdefault('_sweep_mirrors', [])
+                        while len(mirrors) <= k:
+                            mirrors.append(cached[2].new_mirror())
+                        cached[2].load(items, host, mirror=mirrors[k])
+                    try:
+                        cached[0]()
+                        break
+                    except WeightsMoved:                      # (a weight moved since the capture: capture again)
+                        if attempt:
+                            raise
+                        agent._test_graphs.pop(key, None)
+                st, batch = cached[1], cached[2]
+                buf['per32'][k].copy_(buf['per32_h'][k], non_blocking=True)
+                buf['per64'][k].copy_(buf['per64_h'][k], non_blocking=True)
+                d32, o64, o32 = buf['per32'][k], buf['out64'], buf['out32']
+                ep = _lib.EvalEpisodes(S, B, len(self.instr_ids), 0, ptr_of(batch.row), ptr_of(st.actions),
+                                       ptr_of(d32[0]), ptr_of(d32[1]), ptr_of(d32[2]), ptr_of(buf['per64'][k]),
+                                       ptr_of(d32[3]), ptr_of(t.dev), self.error_margin, ptr_of(o64[0]), ptr_of(o64[1]),
+                                       ptr_of(o64[2]), ptr_of(o32[0]), ptr_of(o32[1]), ptr_of(o32[2]))
+                _lib.call('sf_eval_score', C.byref(ep), C.c_void_p(buf['err'].data_ptr()), stream())
+                buf['loss'][k:k + 1].copy_(st.loss_buf.reshape(1))
+                buf['sc'][k].copy_(st.step_scores[:S])
+                if keep_results:
+                    buf['rows_h'][k].copy_(batch.row[:S + 1], non_blocking=True)
+                    buf['views_h'][k].copy_(batch.view[:S + 1], non_blocking=True)
+                    buf['acts_h'][k].copy_(st.actions[:S], non_blocking=True)
+                issued.append(items)
+            n_mb = len(issued)
+            for name in ('out64', 'out32', 'loss', 'sc', 'err'):
+                buf[name + '_h'].copy_(buf[name], non_blocking=True)
+            faults = fault_views(dev)
+            fpin = torch.empty(len(faults), dtype=torch.int32).pin_memory()
+            fpin.copy_(torch.cat(faults) if len(faults) > 1 else faults[0], non_blocking=True)
+            torch.cuda.current_stream().synchronize()         # the one host sync of the sweep
+            syncs += 1
+        self.sweeps += 1
+        if any(fpin.tolist()):
+            take_fault(dev)                                   # (read and cleared: test() starts clean)
+            self.last_host_syncs = syncs + 1
+            self.host_syncs += syncs + 1
+            env.data[:] = walk0[0]
+            random.setstate(walk0[1])
+            return self._by_test(agent, use_dropout, feedback)
+        self.last_host_syncs = syncs
+        self.host_syncs += syncs
+        if int(buf['err_h'][0]):
+            raise RuntimeError('sf_eval_score: a rollout left its scan, or a slot its array')
+        M = len(order)
+        o64, o32 = buf['out64_h'].numpy(), buf['out32_h'].numpy()
+        self.scores = defaultdict(list)
+        self.scores['nav_errors'] = o64[0, :M].tolist()
+        self.scores['oracle_errors'] = o64[1, :M].tolist()
+        self.scores['trajectory_steps'] = o32[0, :M].tolist()
+        self.scores['trajectory_lengths'] = o64[2, :M].tolist()
+        self.scores['success'] = (o32[1, :M] != 0).tolist()
+        self.scores['oracle_success'] = (o32[2, :M] != 0).tolist()
+        # 'score' of a result: the sequential float32 sum of its step scores up to the stop (nav.trajectories_from)
+        sc = buf['sc_h'].numpy()[:n_mb]
+        totals = np.cumsum(sc, axis=1, dtype=np.float32)
+        kb = np.asarray(where, np.int64).reshape(M, 2)
+        model_scores = totals[kb[:, 0], o32[0, :M] - 1, kb[:, 1]].tolist()
+        agent.losses = buf['loss_h'][:n_mb].tolist()
+        agent.loss = torch.tensor(agent.losses[-1])
+        if keep_results:
+            for k, items in enumerate(issued):
+                rows, views, acts = (buf[x][k].numpy().copy() for x in ('rows_h', 'views_h', 'acts_h'))
+                for tr, it in zip(cached[2].trajectories_from(items, S, rows, views, acts, sc[k].copy()), items):
+                    tr['instr_encoding'] = it['instr_encoding']
+                    agent.results.setdefault(tr['instr_id'], tr)
+        return self._summary(self.instr_ids - set(order), M, model_scores), self.scores

@@ -265,16 +265,34 @@ class DeviceNavBatch:
         return dict(seq=np.ascontiguousarray(seq), mask=np.ascontiguousarray(mask.astype(np.uint8)),
                     lengths=np.asarray(lengths, np.int32), rows=rows, views=views, hop=hop, base=base)
 
-    def load(self, items, host=None):
+    def new_mirror(self):
+        """A pinned host mirror of the packed minibatch of the caller's own, for `load(..., mirror=)`."""
+        host = torch.empty_like(self._pack_host).pin_memory()
+        base = self._pack_host.data_ptr()
+        views = {}
+        for key, own in self._pack_np.items():
+            o = own.__array_interface__['data'][0] - base
+            views[key] = host[o:o + own.nbytes].view(torch.from_numpy(own).dtype).view(own.shape).numpy()
+        return host, views
+
+    def load(self, items, host=None, mirror=None):
         """The next minibatch INTO the same device tensors (fixed_shapes only): seven small H2D copies on the current
         stream; the observation slots are rewritten by the rollout itself.  `host`: what `_host_arrays(items)` returned
-        earlier (the agents' training loop forms it while the device still runs the previous iteration)."""
+        earlier (the agents' training loop forms it while the device still runs the previous iteration).  `mirror`
+        (`new_mirror()`): the copy goes through that pinned buffer instead of the batch's own and nothing is waited
+        for here -- the caller leaves the mirror alone until the copy has run (a sweep that issues many minibatches
+        and synchronises once keeps one per minibatch)."""
         if not self.fixed:
             raise ValueError('DeviceNavBatch.load needs fixed_shapes=True')
         if len(items) != self.batch_size:
             raise ValueError('DeviceNavBatch.load: %d items for a batch of %d' % (len(items), self.batch_size))
         h = host if host is not None else self._host_arrays(items)
         self.items, self.lengths = items, h['lengths'].tolist()
+        if mirror is not None:
+            for key, dst in mirror[1].items():
+                np.copyto(dst, h[key], casting='same_kind')
+            self._pack_dev.copy_(mirror[0], non_blocking=True)
+            return
         if getattr(self, '_pack_dev', None) is not None:
             # ONE pinned mirror, rewritten per minibatch: the previous asynchronous copy OUT of it must have completed
             # before the host writes it again.  Nothing in the pipelined training loop guarantees that by itself (the
@@ -348,6 +366,11 @@ class _Trajectory(LazyDict):
         LazyDict.__init__(self, {'instr_id': it['instr_id'], 'actions': acts[:n].tolist(), 'scores': sc[:n].tolist(),
                                  'score': score}, ('trajectory',))
         self._nav, self._it, self._n, self._rows, self._views = nav, it, n, rows, views
+
+    def nav_rows(self):
+        """(the navigation table, the nav rows of the n + 1 poses on the way): what evaluation.Evaluation scores a
+        result from, without 'trajectory' being built."""
+        return self._nav, self._rows[:self._n + 1]
 
     def _make(self, key):
         # (vp, heading, elevation) of every observation on the way: the SNAPPED pose of the simulator state (env.py:783-784),

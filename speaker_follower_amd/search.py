@@ -1402,7 +1402,8 @@ def predict_from_candidates(candidate_lists_by_instr_id, speaker_weights):
 
 def run_rational_speaker(envir, speaker_evaluator, speaker, follower, n_candidates, include_gold=False):
     """rational_speaker.py:140-165 without the file output: candidates, re-ranking for the 21 speaker weights 0, 0.05 ..
-    1, and -- with an evaluator (eval_speaker.py, out of scope here) -- its score summary per weight.  Returns
+    1, and -- with an evaluator (eval_speaker.py's BLEU scoring: not in this package, bring your own object with
+    score_results) -- its score summary per weight.  Returns
     (scores_by_weight or None, results_by_weight)."""
     by_id = generate_and_score_candidates(envir, speaker, follower, n_candidates, include_gold)
     weights = [float(w) for w in np.arange(0, 20 + 1) / 20.0]
@@ -1448,8 +1449,8 @@ def run_rational_follower(envir, evaluator, follower, speaker, beam_size, includ
     """rational_follower.py:12-190 without the file outputs: follower candidates by (state-factored)
     beam search, every candidate route scored by the speaker with teacher forcing (how likely is THIS
     instruction given that route), candidates re-ranked by `rational_mix` for every speaker weight.
-    `evaluator` (eval.py, out of scope here) is optional: with one, returns its score summaries per
-    weight like the reference; without, the chosen candidates per weight."""
+    `evaluator` (eval.py: evaluation.Evaluation of this package) is optional: with one, returns its score
+    summaries per weight like the reference; without, the chosen candidates per weight."""
     follower.env = envir
     envir.reset_epoch()
     for module in (follower.encoder, follower.decoder, speaker.encoder, speaker.decoder):
