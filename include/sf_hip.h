@@ -76,7 +76,7 @@ typedef struct sf_pano {
     const float* table;     /* [n_viewpoints, V, IMG] */
     const float* loc_table; /* [V, V, LOC]  (env.py:78-101) */
     const int32_t* vp;      /* [B]; < 0 => all-zero panorama (speaker.py:93-95 padded step) */
-    const int32_t* view;    /* [B] */
+    const int32_t* view;    /* [B]; clamped into [0, V) */
     int32_t V, IMG, LOC;
 } sf_pano;
 
@@ -328,6 +328,8 @@ typedef struct sf_follower_glue {
      * environment right behind the action choice, instead of a separate sf_nav_step launch */
     const struct sf_nav_io* nav;
 } sf_follower_glue;
+/* SF_ERR_UNSUPPORTED for A > 64 and, with index-form candidates (U->dense == NULL), unless IMG % 4 == 0 && LOC % 16 == 0
+ * (the row layout of u_next, see the batched feature gathers below); nothing is launched, nothing written. */
 int sf_follower_glue_fwd(const sf_cands* U, int B, float* logit, const sf_follower_glue* glue,
                          sf_stream stream);
 /* dlogit[b,a] = gscale[0] * (softmax(logit)[b,a] - [a == target_used[b]]) for live rows, else 0
@@ -590,11 +592,22 @@ int sf_encoder_bilstm_bwd(const sf_encoder_w* fwd, const sf_encoder_w* rev, cons
                           void* ws, size_t ws_bytes, sf_stream stream);
 
 /* ---- batched feature gathers (env.py:380-383, 771-774, 60-75; follower.py:291-320) ------------
- * Materialise the dense tensors the reference builds on the host, from the HBM table. */
+ * Materialise the dense tensors the reference builds on the host, from the HBM table (index form only: X->table,
+ * X->loc_table, X->vp, X->view resp. U->table, U->vp, U->cand_view, U->cand_sincos, U->a_num must all be given,
+ * SF_ERR_ARG otherwise -- for every one of the four entries below).  Table indices are clamped, never trusted:
+ * view[b], cand_view[b,a] into [0, V), a[b] into [0, A); vp < 0 is the zero row.
+ * Shapes: the rows move as float4 chunks and the sin/cos part of a candidate row is laid out as four groups of LOC / 16
+ * float4, which is the reference's layout (each of sin h, cos h, sin e, cos e repeated LOC / 4 times) only for
+ * LOC % 16 == 0.  SF_ERR_UNSUPPORTED, with nothing launched and nothing written, unless
+ *     sf_gather_panorama                                                  IMG % 4 == 0 && LOC % 4 == 0
+ *     sf_gather_candidates, sf_gather_actions, sf_gather_actions_ld       IMG % 4 == 0 && LOC % 16 == 0
+ * for an fp32 table and a binary16 one (sf_feature_table_f16) alike; sf_follower_glue_fwd refuses index-form candidates
+ * outside IMG % 4 == 0 && LOC % 16 == 0 in the same way, as the scoring entries and sf_gather_path_actions always have. */
 int sf_gather_panorama(const sf_pano* X, int B, float* out /* [B,V,F] */, sf_stream stream);
+/* is_valid (optional) [B,A] = a < a_num[b] */
 int sf_gather_candidates(const sf_cands* U, int B, float* all_u /* [B,A,F] */,
                          float* is_valid /* [B,A] */, sf_stream stream);
-/* rows [B,F] of single chosen actions (speaker.py:104): a == 0 / vp < 0 => zeros */
+/* rows [B,F] of single chosen actions (speaker.py:104): a <= 0, a >= a_num[b] or vp < 0 => zeros */
 int sf_gather_actions(const sf_cands* U, int B, const int32_t* a, float* out, sf_stream stream);
 /* The same with a row stride on the output (a multiple of 4, >= F): the previous action's embedding straight into the
  * first half of a decoder step's LSTM input rows (sf_decoder_tape.xin, ld 2F; follower.py:588-590 `u_t_prev`), after which
@@ -871,7 +884,7 @@ int sf_move_rows(const sf_row_move* moves, int n_moves, int n, sf_stream stream)
 
 /* Small utilities used by the host mirror (kept on the stream so rollouts never sync). */
 int sf_fill_f32(float* p, size_t n, float v, sf_stream stream);
-int sf_add_f32(float* dst, const float* src, size_t n, sf_stream stream); /* dst += src */
+int sf_add_f32(float* dst, const float* src, size_t n, sf_stream stream); /* dst += src; n > INT_MAX: SF_ERR_UNSUPPORTED */
 /* Up to SF_FILL_MAX_REGIONS buffers set to a constant each in ONE launch: the initial conditions of a pass -- zero
  * states (model.py:67-79 init_state, :368 u_begin), the <BOS> word of every row (speaker.py:137), cleared `ended`
  * flags (follower.py:380, speaker.py:136) -- which a host mirror would otherwise issue as one fill per tensor.

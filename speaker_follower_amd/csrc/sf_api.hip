@@ -7,6 +7,7 @@
 using namespace sf;
 
 #include <atomic>
+#include <climits>
 #include <map>
 #include <mutex>
 #include <string>
@@ -2238,13 +2239,13 @@ int sf_gather_candidates(const sf_cands* U, int B, float* all_u, float* is_valid
 }
 int sf_gather_actions(const sf_cands* U, int B, const int32_t* a, float* out, sf_stream stream) {
     SF_ENTER();
-    SF_CHECK_ARG(U && a && out && B > 0);
+    SF_CHECK_ARG(U && a && out && B > 0 && U->table && U->vp && U->cand_view && U->cand_sincos && U->a_num);
     return gather_actions(cands(U), B, a, out, S(stream));
 }
 
 int sf_gather_actions_ld(const sf_cands* U, int B, const int32_t* a, float* out, int ld_out, sf_stream stream) {
     SF_ENTER();
-    SF_CHECK_ARG(U && a && out && B > 0 && ld_out > 0);
+    SF_CHECK_ARG(U && a && out && B > 0 && ld_out > 0 && U->table && U->vp && U->cand_view && U->cand_sincos && U->a_num);
     return gather_actions(cands(U), B, a, out, S(stream), ld_out);
 }
 
@@ -2788,6 +2789,7 @@ int sf_add_f32(float* dst, const float* src, size_t n, sf_stream stream) {
     SF_ENTER();
     SF_CHECK_ARG((dst && src) || n == 0);
     if (n == 0) return SF_OK;
+    if (n > (size_t)INT_MAX) return SF_ERR_UNSUPPORTED;       // add2 takes its width as an int
     return add2(dst, 0, src, 0, 1, (int)n, dst, 0, S(stream));
 }
 

@@ -1192,15 +1192,22 @@ int embedding_rows(const float* table, int E, const int64_t* idx, int B, float* 
         if (half) SF_LAUNCH_AS(name "<f16>", K<true>, __VA_ARGS__);  \
         else SF_LAUNCH_AS(name, K<false>, __VA_ARGS__);              \
     } while (0)
+// Index form of the table gathers: the kernels move float4 chunks ((IMG + LOC) >> 2 of them per row), and cand_load lays
+// the location part out as four sin/cos groups of LOC / 16 float4 each -- the reference's LOC / 4 repeats only when
+// LOC % 16 == 0.  Other shapes are refused for both storages, nothing is launched.
+static inline bool pano_index_shape_ok(const PanoSrc& s) { return s.dense || !((s.IMG & 3) || (s.LOC & 3)); }
+static inline bool cand_index_shape_ok(const CandSrc& s) { return s.dense || !((s.IMG & 3) || (s.LOC & 15)); }
 int gather_panorama(const PanoSrc& s, int B, float* out, hipStream_t st) {
-    if (s.half && (s.dense || (s.IMG & 3) || (s.LOC & 3))) return SF_ERR_ARG;
+    if (s.half && s.dense) return SF_ERR_ARG;
+    if (!pano_index_shape_ok(s)) return SF_ERR_UNSUPPORTED;
     SF_LAUNCH_H16_AS(s.half, "gather_pano_kernel", gather_pano_kernel,
                        dim3(grid1d((size_t)B * s.V * ((s.IMG + s.LOC) >> 2))), dim3(TPB), 0, st, s, B,
                        out);
     return launch_status();
 }
 int gather_candidates(const CandSrc& s, int B, float* all_u, float* is_valid, hipStream_t st) {
-    if (s.half && (s.dense || (s.IMG & 3))) return SF_ERR_ARG;
+    if (s.half && s.dense) return SF_ERR_ARG;
+    if (!cand_index_shape_ok(s)) return SF_ERR_UNSUPPORTED;
     SF_LAUNCH_H16_AS(s.half, "gather_cand_kernel", gather_cand_kernel,
                        dim3(grid1d((size_t)B * s.A * ((s.IMG + s.LOC) >> 2))), dim3(TPB), 0, st, s, B,
                        all_u, is_valid);
@@ -1210,7 +1217,8 @@ int gather_actions(const CandSrc& s, int B, const int* a, float* out, hipStream_
     const int F = s.IMG + s.LOC;
     if (ldo == 0) ldo = F;
     if ((ldo & 3) || ldo < F) return SF_ERR_UNSUPPORTED;
-    if (s.half && (s.dense || (s.IMG & 3))) return SF_ERR_ARG;
+    if (s.half && s.dense) return SF_ERR_ARG;
+    if (!cand_index_shape_ok(s)) return SF_ERR_UNSUPPORTED;
     SF_LAUNCH_H16_AS(s.half, "gather_action_kernel", gather_action_kernel, dim3(grid1d((size_t)B * (F >> 2))),
                        dim3(TPB), 0, st, s, B, a, out, ldo >> 2);
     return launch_status();
@@ -1319,6 +1327,7 @@ int logprob_topk(float* logit, int ld, int N, int n, const int* n_valid, int k, 
 int follower_glue_fwd(const FGlue& g, hipStream_t st) {
     if (g.src.A > 64) return SF_ERR_UNSUPPORTED;
     if (g.src.half && g.src.dense) return SF_ERR_ARG;
+    if (!cand_index_shape_ok(g.src)) return SF_ERR_UNSUPPORTED;
     SF_LAUNCH_H16_AS(g.src.half, "follower_glue_kernel", follower_glue_kernel, dim3(ceil_div(g.B, TPB / 64)), dim3(TPB), 0, st, g);
     return launch_status();
 }

@@ -77,7 +77,8 @@ __device__ __forceinline__ PanoRow pano_row(const PanoSrc& s, int b) {
             r.img16 = reinterpret_cast<const uint2*>(s.table) + (size_t)max(vp, 0) * s.V * r.I4;
         else
             r.img = reinterpret_cast<const float4*>(s.table) + (size_t)max(vp, 0) * s.V * r.I4;
-        r.loc = reinterpret_cast<const float4*>(s.loc_table) + (size_t)s.view[b] * s.V * r.L4;
+        // (the agent view index is clamped like every other table index: a stray one reads a row of the table, never beyond it)
+        r.loc = reinterpret_cast<const float4*>(s.loc_table) + (size_t)min(max(s.view[b], 0), s.V - 1) * s.V * r.L4;
     }
     return r;
 }
