@@ -1364,6 +1364,69 @@ typedef struct sf_eval_episodes {
 } sf_eval_episodes;
 int sf_eval_score(const sf_eval_episodes* e, int32_t* err, sf_stream stream);
 
+/* Scoring of speaker results (tasks/R2R/eval_speaker.py:11-122, tasks/R2R/bleu.py:15-72 and the multi-bleu script it
+ * runs; speaker_follower_amd/speaker_evaluation.py), additive to ABI 9.
+ *
+ * sf_bleu_counts: the ten integers corpus BLEU is a function of, per hypothesis, in ONE launch.  Words are ids of an
+ * evaluation-private dictionary 0 .. n_dict - 1 the caller builds BY STRING: every distinct word of the references, of
+ * the vocabulary and of the hypotheses has one id, so a reference word outside the vocabulary has an id of its own and
+ * cannot match a hypothesis word by accident.  Hypothesis b (b < n_hyps) is scored against the n_refs references of
+ * path slot[b]; reference r of slot s is ref_ids[ref_off[s * n_refs + r] .. ref_off[s * n_refs + r + 1]).  Two forms
+ * of hypotheses:
+ *   packed   words == NULL: hypothesis b is hyp_ids[hyp_off[b] .. hyp_off[b + 1]) (dictionary ids)
+ *   matrix   words != NULL: [S, n_hyps] VOCABULARY ids as a decode leaves them, int64 (word_bytes 8) or int16
+ *            (word_bytes 2); hypothesis b is column b up to, not including, its first `eos` -- all S words when there is
+ *            none, a PAD does not end it (utils.Tokenizer.decode_sentence(break_on_eos=True)) -- each word w (in
+ *            [0, n_vocab)) taken through the pair remap[2 w], remap[2 w + 1] to its dictionary ids: (a, -1) one BLEU
+ *            word, (a, b) two (train_vocab.txt holds the token '. .', which the script's re-split of the blank-joined
+ *            line makes two words), (-1, -1) none (an empty string)
+ * rows[slot[b]] = correct_1..4, total_1..4, hyp_len, closest_ref_len (int32 [n_slots, 10]), with for n = 1..4
+ *   total_n      the number of n-grams of the hypothesis, max(hyp_len - n + 1, 0)
+ *   correct_n    the sum over the DISTINCT n-grams of the hypothesis of min(its count in the hypothesis, the largest
+ *                of its counts in the single references)
+ *   closest_ref_len  the length of the reference whose length is closest to hyp_len, the SHORTER one on a tie
+ * and sums[k] += rows[slot[b]][k] (int64 [10], integer atomics: the order is immaterial; the caller zeroes sums, and
+ * gives every slot to at most one hypothesis).  slot[b] == -1 writes nothing.  Anything inconsistent writes nothing
+ * and sets err[0] = 1 (only ever raised; the caller zeroes it): a slot outside [-1, n_slots), an id outside the
+ * dictionary or the vocabulary, a length above the limits, offsets that decrease.
+ * One wavefront per hypothesis, the hypothesis and its references staged in LDS as 16-bit ids: 2 * (SF_BLEU_MAX_HYP +
+ * 4) + 2 * SF_BLEU_MAX_REFS * (SF_BLEU_MAX_REF + 4) = 4 648 bytes per wavefront.  An n-gram is the EXACT packing of
+ * its up to four 16-bit ids into one 64-bit key -- one compare per pair, no hashing, nothing can collide; lane l owns
+ * the start positions l, l + 64, ... of the hypothesis, and a position counts when no earlier position holds the same
+ * n-gram.  Integers throughout: bit-equal to speaker_evaluation.bleu_count_rows by construction.
+ *   max_hyp, max_ref: HOST copies of the longest hypothesis (matrix form: a bound, S or 2 S where remap holds a
+ *   pair; at least S is assumed) and reference.
+ *   SF_ERR_ARG on NULL pointers, n_hyps / n_slots / n_refs / n_dict < 1, matrix form with S < 1, n_vocab < 1 or
+ *   word_bytes other than 2 and 8; SF_ERR_UNSUPPORTED, with nothing launched, for n_dict > sf_bleu_max_dict() (65 536:
+ *   what the key packing holds), a hypothesis above sf_bleu_max_hyp() (256 words; instructions are generated at up to
+ *   80), a reference above sf_bleu_max_ref() (512; the longest of the shipped R2R sub-split has 107) or n_refs >
+ *   sf_bleu_max_refs() (4) -- the caller then counts those paths on the host.  sf_debug_bleu_limits(dict, hyp, ref,
+ *   refs) lowers the limits (each within 1 .. its constant; anything else restores that one), for tests. */
+#define SF_BLEU_MAX_DICT 65536
+#define SF_BLEU_MAX_HYP 256
+#define SF_BLEU_MAX_REF 512
+#define SF_BLEU_MAX_REFS 4
+typedef struct sf_bleu_batch {
+    int32_t n_hyps, n_slots, n_refs, n_dict;
+    int32_t max_hyp, max_ref;          /* host copies of the longest hypothesis (packed form) / reference */
+    int32_t S, word_bytes, eos, n_vocab; /* matrix form */
+    const int32_t* hyp_ids;            /* packed form: [hyp_off[n_hyps]] dictionary ids */
+    const int32_t* hyp_off;            /* packed form: [n_hyps + 1] */
+    const void* words;                 /* matrix form: [S, n_hyps] vocabulary ids */
+    const int32_t* remap;              /* matrix form: [n_vocab, 2] vocabulary id -> its dictionary ids, -1: none */
+    const int32_t* ref_ids;            /* [ref_off[n_slots * n_refs]] dictionary ids */
+    const int32_t* ref_off;            /* [n_slots * n_refs + 1] */
+    const int32_t* slot;               /* [n_hyps] */
+    int32_t* rows;                     /* [n_slots, 10] */
+    int64_t* sums;                     /* [10] */
+} sf_bleu_batch;
+int sf_bleu_max_dict(void);
+int sf_bleu_max_hyp(void);
+int sf_bleu_max_ref(void);
+int sf_bleu_max_refs(void);
+void sf_debug_bleu_limits(int max_dict, int max_hyp, int max_ref, int max_refs);
+int sf_bleu_counts(const sf_bleu_batch* b, int32_t* err, sf_stream stream);
+
 /* In-process kernel timing (no reference counterpart; what bench.py's `roofline.kernels` table is
  * measured with).  Between sf_profile_begin() and sf_profile_end() every kernel ANY host thread of the
  * process launches through this library (torch runs backward() on its own thread) carries a start and a stop event on its own dispatch, so a

@@ -193,6 +193,13 @@ class EvalEpisodes(C.Structure):
                 [(n, c_p) for n in ('nav_error', 'oracle_error', 'length', 'steps', 'success', 'oracle_success')])
 
 
+class BleuBatch(C.Structure):
+    """sf_bleu_batch: hypotheses (packed ids or a decode's word matrix), references and slots of one sf_bleu_counts."""
+    _fields_ = ([(n, C.c_int32) for n in ('n_hyps', 'n_slots', 'n_refs', 'n_dict', 'max_hyp', 'max_ref', 'S', 'word_bytes',
+                                          'eos', 'n_vocab')] +
+                [(n, c_p) for n in ('hyp_ids', 'hyp_off', 'words', 'remap', 'ref_ids', 'ref_off', 'slot', 'rows', 'sums')])
+
+
 SEARCH_OVF_NODES, SEARCH_OVF_SLOTS, SEARCH_OVF_VISITS, SEARCH_OVF_POOL, SEARCH_OVF_KEY = 1, 2, 4, 8, 16
 
 i32, u32, i64p = C.c_int, C.c_uint32, C.c_void_p
@@ -358,6 +365,12 @@ _SIGNATURES = {
     'sf_debug_eval_max_nodes': (None, [C.c_int]),
     'sf_eval_distances': (C.c_int, [P(EvalGraphs), c_p, c_p, c_p]),
     'sf_eval_score': (C.c_int, [P(EvalEpisodes), c_p, c_p]),
+    'sf_bleu_max_dict': (C.c_int, []),
+    'sf_bleu_max_hyp': (C.c_int, []),
+    'sf_bleu_max_ref': (C.c_int, []),
+    'sf_bleu_max_refs': (C.c_int, []),
+    'sf_debug_bleu_limits': (None, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'sf_bleu_counts': (C.c_int, [P(BleuBatch), c_p, c_p]),
     'sf_profile_begin': (C.c_int, []),
     'sf_profile_end': (C.c_long, [C.c_char_p, C.c_size_t]),
 }

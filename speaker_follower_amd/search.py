@@ -1402,8 +1402,8 @@ def predict_from_candidates(candidate_lists_by_instr_id, speaker_weights):
 
 def run_rational_speaker(envir, speaker_evaluator, speaker, follower, n_candidates, include_gold=False):
     """rational_speaker.py:140-165 without the file output: candidates, re-ranking for the 21 speaker weights 0, 0.05 ..
-    1, and -- with an evaluator (eval_speaker.py's BLEU scoring: not in this package, bring your own object with
-    score_results) -- its score summary per weight.  Returns
+    1, and -- with an evaluator (eval_speaker.py's BLEU scoring: speaker_evaluation.SpeakerEvaluation, or any object
+    with score_results) -- its score summary per weight.  Returns
     (scores_by_weight or None, results_by_weight)."""
     by_id = generate_and_score_candidates(envir, speaker, follower, n_candidates, include_gold)
     weights = [float(w) for w in np.arange(0, 20 + 1) / 20.0]

@@ -655,10 +655,22 @@ class SpeakerSweep:
         [n, S, B] of generated word ids (pinned host memory); with_scores: (words, scores [n,S,B] f32, sum_cnt [n,S,2])."""
         return self.finish(self.issue(batches, _persistent))
 
-    def issue(self, batches, _persistent=True):
+    def ensure_slots(self, n):
+        """At least n pinned staging buffers per stream: a sweep of up to n minibatches per stream then never waits
+        for an earlier copy to leave its buffer."""
+        for si in range(len(self.streams)):
+            cap = max(p.numel() for p in self.pinned[si])
+            while len(self.pinned[si]) < n:
+                self.pinned[si].append(torch.empty(cap, dtype=torch.uint8).pin_memory())
+                self.free_ev[si].append(None)
+        self.slots = max(self.slots, n)
+
+    def issue(self, batches, _persistent=True, after=None, clear_faults=True):
         """Everything of `run` that does not wait: packs, copies and replays every minibatch on its stream and returns
         the handle `finish` collects (the host is free in between: Seq2SeqSpeaker's pragmatic scoring builds its result
-        dictionaries there)."""
+        dictionaries there).  after(i, state): called behind minibatch i's replay with its stream current -- what it
+        launches reads the state's tensors before the next replay overwrites them.  clear_faults=False: the caller has
+        cleared the fault words itself (take_fault is a host sync)."""
         import time
         dev = self.store.device
         n = len(batches)
@@ -666,7 +678,8 @@ class SpeakerSweep:
         sc = torch.empty(n, self.S, self.B, dtype=torch.float32).pin_memory() if self.with_scores else None
         cnt = torch.empty(n, self.S, 2, dtype=torch.float32).pin_memory() if self.with_scores else None
         self.host_pack_s = 0.0
-        take_fault(dev)
+        if clear_faults:
+            take_fault(dev)
         for s_ in self.streams:                                  # (the weights' derived layouts are refreshed on the caller's stream)
             s_.wait_stream(torch.cuda.current_stream(dev))
         # a path-step count met for the first time is captured for EVERY stream at once (a capture is tens of
@@ -694,6 +707,8 @@ class SpeakerSweep:
                 ev.record()
                 self.free_ev[si][slot] = ev
                 replay()
+                if after is not None:
+                    after(i, st)
                 words16.copy_(st.words[1:])                      # int64 -> int16 on the device (ids < 2^15)
                 out[i].copy_(words16, non_blocking=True)
                 if self.with_scores:
