@@ -1363,6 +1363,55 @@ typedef struct sf_eval_episodes {
     int32_t *steps, *success, *oracle_success;      /* [n_slots] */
 } sf_eval_episodes;
 int sf_eval_score(const sf_eval_episodes* e, int32_t* err, sf_stream stream);
+/* sf_eval_score_routes (csrc/sf_eval_routes.hip; no reference counterpart for the two new values), additive to ABI 9:
+ * the six values of sf_eval_score -- the same bits: the first minimum, the length added in path order -- plus the two
+ * device quantities of the path-fidelity metrics (SPL, nDTW, SDTW), for B routes in ONE launch,
+ * written at slot[b] of eight [n_slots] arrays.  With P = p_0 .. p_n the poses of route b and R = r_0 .. r_{g-1} its
+ * gold path:
+ *   shortest      D[p_0][r_{g-1}]
+ *   dtw           C[n+1][g] of C[0][0] = 0, C[a][0] = C[0][b] = inf otherwise,
+ *                 C[a][b] = D[p_{a-1}][r_{b-1}] + min(C[a-1][b], C[a][b-1], C[a-1][b-1])
+ * The cost is taken FROM the pose TO the gold node.  A cell is one rounded float64 add of one table element to an exact
+ * three-way minimum: the bits do not depend on the order in which the cells are formed (the host runs the rows, the
+ * kernel the anti-diagonals).  spl, ndtw and sdtw are formed on the host from these (evaluation.path_metrics_of).
+ * Routes are addressed generically: pose t of route b is the nav row row[row_first[b] + t * row_stride], local index =
+ * that - scan_base[b]; `row` holds n_rows elements.  n = n_steps[b] when n_steps is given, else derived from actions
+ * [S,B] as sf_eval_score does (the first 0 plus one, else S).  Two layouts:
+ *   sweep    row [S+1,B] and actions [S,B] as a rollout leaves them: row_stride = B, row_first[b] = b, n_steps = NULL
+ *   ragged   the routes back to back in one array: row_stride = 1, row_first = their offsets, n_steps given (routes of
+ *            any length: the recurrence runs n + g steps)
+ * Gold paths are a ragged table of LOCAL node indices: path k is gold_node[gold_off[k] .. gold_off[k+1]), route b is
+ * scored against path gold_id[b], its goal is that path's last node.  scan_base, m, dist_off, slot, table, margin: as
+ * in sf_eval_episodes.  One wavefront per route, lane l owns gold position l: SF_EVAL_MAX_GOLD = 64 nodes per gold path
+ * (R2R's have at most 7).
+ *   SF_ERR_ARG on NULL pointers (n_steps may be NULL; then actions must not be and S >= 1), B, n_slots, row_stride,
+ *   n_gold, n_gold_nodes, n_rows or max_gold < 1; SF_ERR_UNSUPPORTED, with nothing launched, for max_gold (a HOST copy
+ *   of the longest gold path) > 64 -- the caller then scores on the host.  slot[b] == -1 writes nothing.  A route with
+ *   a pose or gold node outside its scan, a pose index outside `row`, a negative step count, a slot outside
+ *   [-1, n_slots), a gold_id outside [0, n_gold), a gold path of 0 or more than 64 nodes or outside gold_node, or whose
+ *   first pose is not its gold path's first node, writes nothing and sets err[0] = 1 (only ever raised). */
+#define SF_EVAL_MAX_GOLD 64
+typedef struct sf_eval_routes {
+    int32_t S, B, n_slots, row_stride;
+    int32_t n_gold, n_gold_nodes, max_gold, reserved;
+    int64_t n_rows;            /* elements of `row` */
+    const int32_t* row;        /* nav rows */
+    const int64_t* row_first;  /* [B] element of pose 0 */
+    const int32_t* n_steps;    /* [B], or NULL: from actions */
+    const int64_t* actions;    /* [S, B]; read only when n_steps == NULL */
+    const int32_t* gold_off;   /* [n_gold + 1] */
+    const int32_t* gold_node;  /* [n_gold_nodes] local node indices */
+    const int32_t* gold_id;    /* [B] */
+    const int32_t* scan_base;  /* [B] */
+    const int32_t* m;          /* [B] */
+    const int64_t* dist_off;   /* [B] */
+    const int32_t* slot;       /* [B] */
+    const double* table;
+    double margin;
+    double *nav_error, *oracle_error, *length, *shortest, *dtw;   /* [n_slots] */
+    int32_t *steps, *success, *oracle_success;                   /* [n_slots] */
+} sf_eval_routes;
+int sf_eval_score_routes(const sf_eval_routes* e, int32_t* err, sf_stream stream);
 
 /* Scoring of speaker results (tasks/R2R/eval_speaker.py:11-122, tasks/R2R/bleu.py:15-72 and the multi-bleu script it
  * runs; speaker_follower_amd/speaker_evaluation.py), additive to ABI 9.

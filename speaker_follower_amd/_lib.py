@@ -193,6 +193,18 @@ class EvalEpisodes(C.Structure):
                 [(n, c_p) for n in ('nav_error', 'oracle_error', 'length', 'steps', 'success', 'oracle_success')])
 
 
+class EvalRoutes(C.Structure):
+    """sf_eval_routes: B routes (sweep or ragged layout), the gold table and the eight arrays sf_eval_score_routes fills."""
+    _fields_ = ([(n, C.c_int32) for n in ('S', 'B', 'n_slots', 'row_stride', 'n_gold', 'n_gold_nodes', 'max_gold',
+                                          'reserved')] +
+                [('n_rows', C.c_int64)] +
+                [(n, c_p) for n in ('row', 'row_first', 'n_steps', 'actions', 'gold_off', 'gold_node', 'gold_id',
+                                    'scan_base', 'm', 'dist_off', 'slot', 'table')] +
+                [('margin', C.c_double)] +
+                [(n, c_p) for n in ('nav_error', 'oracle_error', 'length', 'shortest', 'dtw', 'steps', 'success',
+                                    'oracle_success')])
+
+
 class BleuBatch(C.Structure):
     """sf_bleu_batch: hypotheses (packed ids or a decode's word matrix), references and slots of one sf_bleu_counts."""
     _fields_ = ([(n, C.c_int32) for n in ('n_hyps', 'n_slots', 'n_refs', 'n_dict', 'max_hyp', 'max_ref', 'S', 'word_bytes',
@@ -365,6 +377,7 @@ _SIGNATURES = {
     'sf_debug_eval_max_nodes': (None, [C.c_int]),
     'sf_eval_distances': (C.c_int, [P(EvalGraphs), c_p, c_p, c_p]),
     'sf_eval_score': (C.c_int, [P(EvalEpisodes), c_p, c_p]),
+    'sf_eval_score_routes': (C.c_int, [P(EvalRoutes), c_p, c_p]),
     'sf_bleu_max_dict': (C.c_int, []),
     'sf_bleu_max_hyp': (C.c_int, []),
     'sf_bleu_max_ref': (C.c_int, []),

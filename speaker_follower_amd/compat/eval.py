@@ -1,2 +1,3 @@
 """`import eval` (train.py:17; `eval.Evaluation([split])`, train.py:206) / `from eval import Evaluation` (plot.py:7)."""
 from speaker_follower_amd.evaluation import Evaluation, EvalResult      # noqa: F401
+from speaker_follower_amd.evaluation import PathEvalResult, path_metrics_of      # noqa: F401

@@ -9,11 +9,15 @@ summary averages over the instructions '<path_id>_0' .. '_2' of the split.
                       source-major: D[a][b] and D[b][a] differ in their last bits for half of all pairs.
   * `Evaluation`      eval.py's class: `_score_item`, `score_results`, `score_file` with the reference's contract, and
                       `score_agent`: agent.test() + score_results as one device sweep with one host sync.
+                      `path_metrics=True` adds SPL, nDTW and SDTW (no reference counterpart: their published
+                      definitions, DESIGN.md section 2) through sf_eval_score_routes (csrc/sf_eval_routes.hip);
+                      `score_routes` scores a batch of routes in one launch.
 
 The reference takes its table from networkx (all_pairs_dijkstra_path_length); nothing here imports it.
 """
 import ctypes as C
 import json
+import math
 import os
 import random
 from collections import defaultdict, namedtuple
@@ -23,10 +27,41 @@ import numpy as np
 EvalResult = namedtuple('EvalResult', 'nav_error, oracle_error, trajectory_steps, trajectory_length, success, '
                                       'oracle_success')                                          # eval.py:18-20
 
+PathEvalResult = namedtuple('PathEvalResult', EvalResult._fields + ('shortest_length', 'dtw', 'spl', 'ndtw', 'sdtw'))
+
 DATA_JSON = 'tasks/R2R/data/R2R_%s.json'                                 # utils.py:54-59
 CONNECTIVITY = 'connectivity'
 
 _LISTS = ('nav_errors', 'oracle_errors', 'trajectory_steps', 'trajectory_lengths', 'success', 'oracle_success')
+_PATH_LISTS = ('shortest_lengths', 'dtw', 'spl', 'ndtw', 'sdtw')
+MAX_GOLD_NODES = 64                                                      # SF_EVAL_MAX_GOLD (include/sf_hip.h)
+
+
+def path_metrics_of(r, shortest, dtw, gold_nodes, margin):
+    """EvalResult `r` + the two device quantities -> PathEvalResult.  THE place where spl, ndtw
+    and sdtw are formed, for the host and the device path alike, per item and with math.exp (np.exp may differ in the
+    last bit).  An unreachable goal has shortest = inf and is never a success: no inf / inf is formed."""
+    if not r.success:
+        spl = 0.0
+    else:
+        longest = max(r.trajectory_length, shortest)
+        spl = 1.0 if longest == 0 else shortest / longest
+    ndtw = math.exp(-dtw / (gold_nodes * margin))
+    return PathEvalResult(*r, shortest_length=shortest, dtw=dtw, spl=spl, ndtw=ndtw, sdtw=ndtw if r.success else 0.0)
+
+
+def dtw_rows(cost):
+    """C[n+1][g] of the warping recurrence over cost[a][b] = D[p_a][r_b] (lists of float), row by row: every cell is
+    one rounded add of one table element to an exact three-way minimum (sf_eval_score_routes runs the anti-diagonals:
+    the same bits)."""
+    inf = math.inf
+    prev = [0.0] + [inf] * len(cost[0])
+    for row in cost:
+        cur = [inf]
+        for b, c in enumerate(row):
+            cur.append(c + min(prev[b + 1], cur[b], prev[b]))
+        prev = cur
+    return prev[-1]
 
 
 class DistanceTable:
@@ -125,10 +160,19 @@ class Evaluation(object):
     Evaluation(splits)                 reads tasks/R2R/data/R2R_<split>.json and connectivity/ relative to the working
                                        directory, as compat/env.py does (the reference's form)
     Evaluation(env=env)                the items and graphs of an env.R2RIndexEnv / compat R2RBatch
-    Evaluation(items=..., graphs=...)  items with 'path_id', 'scan', 'path'; graphs: scan -> env.NavGraph"""
+    Evaluation(items=..., graphs=...)  items with 'path_id', 'scan', 'path'; graphs: scan -> env.NavGraph
 
-    def __init__(self, splits=None, env=None, items=None, graphs=None, nav_graph_path=CONNECTIVITY, device=None):
+    path_metrics=True adds the path-fidelity measures (no reference counterpart): `_score_item` and
+    `score_routes` return PathEvalResult (EvalResult's fields, then shortest_length, dtw, spl, ndtw, sdtw), `scores`
+    gains the lists 'shortest_lengths', 'dtw', 'spl', 'ndtw', 'sdtw' and the summary 'spl', 'ndtw', 'sdtw'.  With the
+    distance table on the device every batch of results is ONE sf_eval_score_routes launch (csrc/sf_eval_routes.hip)
+    and one host sync, else the host loop: the same values to the last bit."""
+
+    def __init__(self, splits=None, env=None, items=None, graphs=None, nav_graph_path=CONNECTIVITY, device=None,
+                 path_metrics=False):
         self.error_margin = 3.0
+        self.path_metrics = bool(path_metrics)
+        self._gold = None
         if env is not None:
             items = list(env.data) if items is None else items
             graphs = env.graphs if graphs is None else graphs
@@ -175,8 +219,16 @@ class Evaluation(object):
         return float(t.block(scan)[t.index[scan][a], t.index[scan][b]])
 
     # ---- eval.py:46-84
-    def _score_rows(self, scan, rows, goal):
-        """One path as LOCAL node indices of its scan."""
+    def _score_rows(self, scan, rows, goal, gold=None):
+        """One path as LOCAL node indices of its scan (`gold`: the gold path likewise, with path_metrics)."""
+        r = self._score_six(scan, rows, goal)
+        if not self.path_metrics:
+            return r
+        D = self.table.block(scan)
+        return path_metrics_of(r, float(D[rows[0], goal]), dtw_rows(D[np.ix_(rows, gold)].tolist()), len(gold),
+                               self.error_margin)
+
+    def _score_six(self, scan, rows, goal):
         D = self.table.block(scan)
         to_goal = D[rows, goal].tolist()
         nav_error, oracle_error = to_goal[-1], to_goal[0]
@@ -195,7 +247,7 @@ class Evaluation(object):
         assert gt['path'][0] == path[0][0], 'Result trajectories should include the start position'
         ix = self.table.index[gt['scan']]
         return self._score_rows(gt['scan'], np.fromiter((ix[p[0]] for p in path), np.int64, len(path)),
-                                ix[gt['path'][-1]])
+                                ix[gt['path'][-1]], [ix[v] for v in gt['path']] if self.path_metrics else None)
 
     def _local_rows(self, nav, scan):
         """First nav row of `scan` in `nav`, after checking ONCE that the table's rows of that scan are this table's
@@ -240,6 +292,110 @@ class Evaluation(object):
         return [EvalResult(a, b, c, d, a < margin, b < margin)
                 for a, b, c, d in zip(nav_error.tolist(), oracle_error.tolist(), n.tolist(), length.tolist())]
 
+    # ---- batches of routes: one sf_eval_score_routes launch (csrc/sf_eval_routes.hip), or the host loop
+    def _gold_table(self):
+        """The gold paths as the ragged table of LOCAL node indices sf_eval_score_routes reads: path_id -> its index,
+        offsets, nodes, the longest path; uploaded once per Evaluation when the distances are on the device."""
+        if self._gold is None:
+            t = self.table
+            ids, off, node = {}, [0], []
+            for pid, gt in self.gt.items():
+                ids[pid] = len(ids)
+                node += [t.index[gt['scan']][v] for v in gt['path']]
+                off.append(len(node))
+            gold = dict(ids=ids, off=np.asarray(off, np.int32), node=np.asarray(node, np.int32),
+                        longest=int(np.diff(off).max()) if ids else 0, dev=None)
+            if t.dev is not None and node:
+                import torch
+                gold['dev'] = tuple(torch.from_numpy(gold[k]).to(t.dev.device) for k in ('off', 'node'))
+            self._gold = gold
+        return self._gold
+
+    def _route_of(self, instr_id, result):
+        """(ground truth, the poses as LOCAL node indices) of a trajectory [(viewpoint, heading, elevation), ...] or of
+        a result of a device rollout, with the reference's assertion on the start."""
+        gt = self.gt[int(instr_id.split('_')[0])]
+        scan = gt['scan']
+        if hasattr(result, 'nav_rows'):
+            nav, rows = result.nav_rows()
+            assert nav.row_of[(scan, gt['path'][0])] == rows[0], 'Result trajectories should include the start position'
+            local = np.asarray(rows, np.int64) - self._local_rows(nav, scan)
+            if (local < 0).any() or (local >= self.table.m[scan]).any():
+                raise ValueError('a result holds a nav row outside its scan')
+            return gt, local
+        assert gt['path'][0] == result[0][0], 'Result trajectories should include the start position'
+        ix = self.table.index[scan]
+        return gt, np.fromiter((ix[p[0]] for p in result), np.int64, len(result))
+
+    def _score_routes(self, routes):
+        """[(ground truth, local poses)] -> results of this evaluator's type: ONE ragged launch and one host sync when
+        the distances are on the device, else -- and where the kernel refuses (`fallbacks`) -- the host loop."""
+        out = self._score_routes_on_device(routes) if routes and self.table.dev is not None else None
+        if out is None:
+            t = self.table
+            out = []
+            for gt, rows in routes:
+                ix = t.index[gt['scan']]
+                out.append(self._score_rows(gt['scan'], rows, ix[gt['path'][-1]],
+                                            [ix[v] for v in gt['path']] if self.path_metrics else None))
+        return out
+
+    def _score_routes_on_device(self, routes):
+        import torch
+        from . import _lib
+        from .runtime import stream
+        t, gold = self.table, self._gold_table()
+        if gold['dev'] is None:
+            return None
+        dev = t.dev.device
+        N = len(routes)
+        n = np.array([len(rows) - 1 for _, rows in routes], np.int64)
+        i32 = np.zeros((5, N), np.int32)                     # n_steps, gold_id, m, slot, scan_base (0: poses are local)
+        i64 = np.zeros((2, N), np.int64)                     # row_first, dist_off
+        i32[0], i32[3] = n, np.arange(N)
+        i64[0, 1:] = np.cumsum(n[:-1] + 1)
+        for i, (gt, _) in enumerate(routes):
+            i32[1, i], i32[2, i], i64[1, i] = gold['ids'][gt['path_id']], t.m[gt['scan']], t.off[gt['scan']]
+        poses = np.concatenate([rows for _, rows in routes]).astype(np.int32)
+        ptr_of = lambda x: x.data_ptr()                       # noqa: E731
+        with torch.cuda.device(dev):
+            d32, d64, rows_d = (torch.from_numpy(a).to(dev) for a in (i32, i64, poses))
+            o64 = torch.empty(5, N, dtype=torch.float64, device=dev)
+            o32 = torch.zeros(3 * N + 1, dtype=torch.int32, device=dev)                   # (the last word: err)
+            e = _lib.EvalRoutes(0, N, N, 1, len(gold['ids']), len(gold['node']), gold['longest'], 0, len(poses),
+                                ptr_of(rows_d), ptr_of(d64[0]), ptr_of(d32[0]), None, ptr_of(gold['dev'][0]),
+                                ptr_of(gold['dev'][1]), ptr_of(d32[1]), ptr_of(d32[4]), ptr_of(d32[2]), ptr_of(d64[1]),
+                                ptr_of(d32[3]), ptr_of(t.dev), self.error_margin, *[ptr_of(o64[k]) for k in range(5)],
+                                *[ptr_of(o32[k * N:]) for k in range(3)])
+            status = _lib.lib.sf_eval_score_routes(C.byref(e), C.c_void_p(ptr_of(o32[3 * N:])), stream())
+            if status == _lib.SF_ERR_UNSUPPORTED:             # a gold path above the kernel's 64 nodes
+                self.fallbacks += 1
+                return None
+            _lib.check(status, 'sf_eval_score_routes')
+            h64 = torch.empty(5, N, dtype=torch.float64).pin_memory()
+            h32 = torch.empty(3 * N + 1, dtype=torch.int32).pin_memory()
+            h64.copy_(o64, non_blocking=True)
+            h32.copy_(o32, non_blocking=True)
+            torch.cuda.current_stream().synchronize()         # the one host sync of the batch
+        self.last_host_syncs = 1
+        self.host_syncs += 1
+        if int(h32[3 * N]):
+            raise RuntimeError('sf_eval_score_routes: a route left its scan or does not start where its gold path does')
+        f, k = h64.numpy(), h32.numpy()[:3 * N].reshape(3, N)
+        margin = self.error_margin
+        six = [EvalResult(a, b, c, d, bool(s), bool(o)) for a, b, c, d, s, o in
+               zip(f[0].tolist(), f[1].tolist(), k[0].tolist(), f[2].tolist(), k[1].tolist(), k[2].tolist())]
+        if not self.path_metrics:
+            return six
+        return [path_metrics_of(r, sh, dtw, len(gt['path']), margin)
+                for r, sh, dtw, (gt, _) in zip(six, f[3].tolist(), f[4].tolist(), routes)]
+
+    def score_routes(self, instr_ids, trajectories):
+        """What `_score_item(instr_id, trajectory)` returns for every pair, as one batch: EvalResult -- PathEvalResult
+        with path_metrics -- per route (a trajectory: [(viewpoint, heading, elevation), ...] or a result of a device
+        rollout)."""
+        return self._score_routes([self._route_of(i, p) for i, p in zip(instr_ids, trajectories)])
+
     # ---- eval.py:86-145
     def score_results(self, results):
         """results: instr_id -> dictionary with (at least) 'trajectory' -- or a result of a device rollout
@@ -251,13 +407,17 @@ class Evaluation(object):
         for instr_id, result in results.items():
             if instr_id in instr_ids:
                 instr_ids.remove(instr_id)
-                if hasattr(result, 'nav_rows'):
+                if self.path_metrics:                        # every result of the batch in one launch (or the host loop)
+                    taken.append(self._route_of(instr_id, result if hasattr(result, 'nav_rows') else result['trajectory']))
+                elif hasattr(result, 'nav_rows'):
                     on_device.append((instr_id, result))
                     taken.append(None)
                 else:
                     taken.append(self._score_item(instr_id, result['trajectory']))
                 if 'score' in result:
                     model_scores.append(result['score'])
+        if self.path_metrics:
+            taken = self._score_routes(taken)
         if on_device:
             scored = iter(self._score_device_results(on_device))
             taken = [next(scored) if r is None else r for r in taken]
@@ -265,6 +425,9 @@ class Evaluation(object):
             for name, v in zip(_LISTS, (r.nav_error, r.oracle_error, r.trajectory_steps, r.trajectory_length,
                                         r.success, r.oracle_success)):
                 self.scores[name].append(v)
+            if self.path_metrics:
+                for name, v in zip(_PATH_LISTS, r[6:]):
+                    self.scores[name].append(v)
         return self._summary(instr_ids, len(taken), model_scores), self.scores
 
     def _summary(self, missing, instr_count, model_scores):
@@ -283,6 +446,9 @@ class Evaluation(object):
         if len(model_scores) > 0:
             assert len(model_scores) == instr_count
             summary['model_score'] = np.average(model_scores)
+        if self.path_metrics:
+            for name in ('spl', 'ndtw', 'sdtw'):
+                summary[name] = np.average(sc[name])
         return summary
 
     def score_file(self, output_file):
@@ -299,6 +465,8 @@ class Evaluation(object):
         nav = agent._device_table() if hasattr(agent, '_device_table') else None
         if nav is None or agent._engine is None or agent._engine.group is not None or self.table.dev is None:
             return None
+        if self.path_metrics and not 1 <= self._gold_table()['longest'] <= MAX_GOLD_NODES:
+            return None                                      # (sf_eval_score_routes would refuse: one lane per gold node)
         return nav
 
     def _by_test(self, agent, use_dropout, feedback):
@@ -317,10 +485,14 @@ class Evaluation(object):
             d = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)                      # noqa: E731
             p = lambda *s, dt: torch.empty(*s, dtype=dt).pin_memory()                     # noqa: E731
             i32, i64, f32, f64 = torch.int32, torch.int64, torch.float32, torch.float64
-            buf = dict(per32=d(K, 4, B, dt=i32), per64=d(K, B, dt=i64), per32_h=p(K, 4, B, dt=i32), per64_h=p(K, B, dt=i64),
-                       out64=d(3, n, dt=f64), out32=d(3, n, dt=i32), out64_h=p(3, n, dt=f64), out32_h=p(3, n, dt=i32),
+            w32, w64 = (5, 5) if self.path_metrics else (4, 3)                            # (+ gold_id; + shortest, dtw)
+            buf = dict(per32=d(K, w32, B, dt=i32), per64=d(K, B, dt=i64), per32_h=p(K, w32, B, dt=i32),
+                       per64_h=p(K, B, dt=i64),
+                       out64=d(w64, n, dt=f64), out32=d(3, n, dt=i32), out64_h=p(w64, n, dt=f64), out32_h=p(3, n, dt=i32),
                        loss=d(K, dt=f32), loss_h=p(K, dt=f32), sc=d(K, S, B, dt=f32), sc_h=p(K, S, B, dt=f32),
                        err=d(1, dt=i32), err_h=p(1, dt=i32))
+            if self.path_metrics:
+                buf['first'] = torch.arange(B, dtype=i64, device=dev)                     # sweep layout: row_first[b] = b
             self._sweep_buffers = {key: buf}
         if keep and 'rows_h' not in buf:
             import torch
@@ -339,7 +511,9 @@ class Evaluation(object):
         is set as test() sets it; `agent.results` stays empty unless keep_results (the row / view / action downloads per
         minibatch, still without a wait in between).  A raised fault word, or an agent `_rollout_on_graph` does not
         take, means agent.test() + score_results instead (`fallbacks`): a faulting sweep is never scored, and the
-        environment's item order and `random` are put back first, so that test() walks what the sweep walked."""
+        environment's item order and `random` are put back first, so that test() walks what the sweep walked.
+        With path_metrics the launch behind every rollout is sf_eval_score_routes in its sweep layout (the same arrays,
+        plus the episode's gold path index): still one host sync."""
         nav = self._sweepable(agent, use_dropout, feedback)
         if nav is None:
             return self._by_test(agent, use_dropout, feedback)
@@ -357,6 +531,7 @@ class Evaluation(object):
         S, B = agent.episode_len, min(env.batch_size, max(1, len(env.data)))
         K = -(-len(env.data) // B) + 1                        # an id repeats in minibatch ceil(N / B) + 1 at the latest
         buf = self._buffers(dev, K, S, B, keep_results)
+        gold = self._gold_table() if self.path_metrics else None
         per32, per64 = buf['per32_h'].numpy(), buf['per64_h'].numpy()
         walk0 = (list(env.data), random.getstate())          # (a faulting sweep is undone: test() then walks from here)
         env.reset_epoch()
@@ -390,6 +565,8 @@ class Evaluation(object):
                     per32[k, 0, b], per32[k, 1, b] = nav.row_of[(scan, goal)], self._local_rows(nav, scan)
                     per32[k, 2, b], per32[k, 3, b] = t.m[scan], slot
                     per64[k, b] = t.off[scan]
+                    if gold is not None:
+                        per32[k, 4, b] = gold['ids'].get(it.get('path_id'), 0)            # (read only where slot >= 0)
                 host = DeviceNavBatch.host_arrays_for(nav, items, agent.max_instruction_length,
                                                       agent.reverse_instruction, True)
                 key = agent._test_graph_key(nav, eng, B)
@@ -413,11 +590,20 @@ class Evaluation(object):
                 buf['per32'][k].copy_(buf['per32_h'][k], non_blocking=True)
                 buf['per64'][k].copy_(buf['per64_h'][k], non_blocking=True)
                 d32, o64, o32 = buf['per32'][k], buf['out64'], buf['out32']
-                ep = _lib.EvalEpisodes(S, B, len(self.instr_ids), 0, ptr_of(batch.row), ptr_of(st.actions),
-                                       ptr_of(d32[0]), ptr_of(d32[1]), ptr_of(d32[2]), ptr_of(buf['per64'][k]),
-                                       ptr_of(d32[3]), ptr_of(t.dev), self.error_margin, ptr_of(o64[0]), ptr_of(o64[1]),
-                                       ptr_of(o64[2]), ptr_of(o32[0]), ptr_of(o32[1]), ptr_of(o32[2]))
-                _lib.call('sf_eval_score', C.byref(ep), C.c_void_p(buf['err'].data_ptr()), stream())
+                if gold is not None:                          # the sweep layout of sf_eval_score_routes: + shortest, dtw
+                    ep = _lib.EvalRoutes(S, B, len(self.instr_ids), B, len(gold['ids']), len(gold['node']),
+                                         gold['longest'], 0, (S + 1) * B, ptr_of(batch.row), ptr_of(buf['first']), None,
+                                         ptr_of(st.actions), ptr_of(gold['dev'][0]), ptr_of(gold['dev'][1]),
+                                         ptr_of(d32[4]), ptr_of(d32[1]), ptr_of(d32[2]), ptr_of(buf['per64'][k]),
+                                         ptr_of(d32[3]), ptr_of(t.dev), self.error_margin,
+                                         *[ptr_of(o64[i]) for i in (0, 1, 2, 3, 4)], *[ptr_of(o32[i]) for i in (0, 1, 2)])
+                    _lib.call('sf_eval_score_routes', C.byref(ep), C.c_void_p(buf['err'].data_ptr()), stream())
+                else:
+                    ep = _lib.EvalEpisodes(S, B, len(self.instr_ids), 0, ptr_of(batch.row), ptr_of(st.actions),
+                                           ptr_of(d32[0]), ptr_of(d32[1]), ptr_of(d32[2]), ptr_of(buf['per64'][k]),
+                                           ptr_of(d32[3]), ptr_of(t.dev), self.error_margin, ptr_of(o64[0]),
+                                           ptr_of(o64[1]), ptr_of(o64[2]), ptr_of(o32[0]), ptr_of(o32[1]), ptr_of(o32[2]))
+                    _lib.call('sf_eval_score', C.byref(ep), C.c_void_p(buf['err'].data_ptr()), stream())
                 buf['loss'][k:k + 1].copy_(st.loss_buf.reshape(1))
                 buf['sc'][k].copy_(st.step_scores[:S])
                 if keep_results:
@@ -444,7 +630,8 @@ class Evaluation(object):
         self.last_host_syncs = syncs
         self.host_syncs += syncs
         if int(buf['err_h'][0]):
-            raise RuntimeError('sf_eval_score: a rollout left its scan, or a slot its array')
+            raise RuntimeError('%s: a rollout left its scan, or a slot its array'
+                               % ('sf_eval_score_routes' if self.path_metrics else 'sf_eval_score'))
         M = len(order)
         o64, o32 = buf['out64_h'].numpy(), buf['out32_h'].numpy()
         self.scores = defaultdict(list)
@@ -454,6 +641,13 @@ class Evaluation(object):
         self.scores['trajectory_lengths'] = o64[2, :M].tolist()
         self.scores['success'] = (o32[1, :M] != 0).tolist()
         self.scores['oracle_success'] = (o32[2, :M] != 0).tolist()
+        if self.path_metrics:                                 # spl, ndtw, sdtw per item by the one function of the host path
+            lists = [self.scores[name] for name in _LISTS]
+            goldn = [len(self.gt[int(iid.split('_')[0])]['path']) for iid in order]
+            full = [path_metrics_of(EvalResult(*six), sh, dtw, g, self.error_margin)
+                    for six, sh, dtw, g in zip(zip(*lists), o64[3, :M].tolist(), o64[4, :M].tolist(), goldn)]
+            for i, name in enumerate(_PATH_LISTS):
+                self.scores[name] = [r[6 + i] for r in full]
         # 'score' of a result: the sequential float32 sum of its step scores up to the stop (nav.trajectories_from)
         sc = buf['sc_h'].numpy()[:n_mb]
         totals = np.cumsum(sc, axis=1, dtype=np.float32)

@@ -1476,16 +1476,21 @@ def run_rational_follower(envir, evaluator, follower, speaker, beam_size, includ
             c['follower_score'], c['speaker_score'] = c['score'], sp['score']
             del c['observations']
         wrapped = False
-        for b, group in enumerate(cands):
-            if physical_traversal:
+        if physical_traversal:
+            for b, group in enumerate(cands):
                 offset = 1 if include_gold else 0       # the gold route is not a search hypothesis
                 for c, hyp in zip(group[offset:], hyps[b]):
                     route = _walked_route(walks[b], hyp)
                     assert route[-1][0] == c['trajectory'][-1][0]
                     c['trajectory'] = route
-            if compute_oracle and evaluator is not None:
-                for c in group:
-                    c['eval_result'] = evaluator._score_item(c['instr_id'], c['trajectory'])._asdict()
+        if compute_oracle and evaluator is not None:
+            if hasattr(evaluator, 'score_routes'):      # every candidate of the minibatch in one batch (one launch)
+                scored = evaluator.score_routes([c['instr_id'] for c in flat], [c['trajectory'] for c in flat])
+            else:
+                scored = [evaluator._score_item(c['instr_id'], c['trajectory']) for c in flat]
+            for c, r in zip(flat, scored):
+                c['eval_result'] = r._asdict()
+        for group in cands:
             instr_id = group[0]['instr_id']
             assert all(c['instr_id'] == instr_id for c in group)
             if instr_id in by_instruction:
