@@ -34,7 +34,6 @@ CONNECTIVITY = 'connectivity'
 
 _LISTS = ('nav_errors', 'oracle_errors', 'trajectory_steps', 'trajectory_lengths', 'success', 'oracle_success')
 _PATH_LISTS = ('shortest_lengths', 'dtw', 'spl', 'ndtw', 'sdtw')
-MAX_GOLD_NODES = 64                                                      # SF_EVAL_MAX_GOLD (include/sf_hip.h)
 
 
 def path_metrics_of(r, shortest, dtw, gold_nodes, margin):
@@ -465,7 +464,8 @@ class Evaluation(object):
         nav = agent._device_table() if hasattr(agent, '_device_table') else None
         if nav is None or agent._engine is None or agent._engine.group is not None or self.table.dev is None:
             return None
-        if self.path_metrics and not 1 <= self._gold_table()['longest'] <= MAX_GOLD_NODES:
+        from . import _lib                                   # (loaded: the distances are on the device)
+        if self.path_metrics and not 1 <= self._gold_table()['longest'] <= _lib.SF_EVAL_MAX_GOLD:
             return None                                      # (sf_eval_score_routes would refuse: one lane per gold node)
         return nav
 

@@ -506,7 +506,7 @@ class FollowerEngine:
                     # ... and the folded query / scoring matrices (model.decoder_fold: rebuilt in place per weight
                     # version): three dependent launches behind the cell instead of four
                     st.chain_fold = decoder_fold(dec)
-                    ep.chain_fold = C.cast(C.pointer(st.chain_fold), C.c_void_p)
+                    ep.chain_fold = C.pointer(st.chain_fold)
             # ... on the projected tables of (store, decoder) where the policy has them (`project` above): the library
             # takes the two-launch chain for every step it applies to and says how many it issued
             st.projected_tables = self._projected_tables(B, T=T, A=A) if (st.text_folded and not nav_episode) else None
