@@ -368,7 +368,7 @@ int visual_bwd_i(const sf_visual_w* w, const sf_visual_g* g, const PanoSrc& X, i
                                          *beside, st, dout_slabs, dout_slab_stride);
         if (rc == SF_OK) paired = true;
         else if (rc != SF_ERR_UNSUPPORTED) return rc;
-        else TRY(launch_small_plan_x(*beside, st));
+        else TRY(launch_small_plan(*beside, st));
     }
     if (!paired) TRY(visual_attn(1, X, B, dout, lddo, const_cast<float*>(alpha), dq, F, drop, col0, st, nullptr, nullptr,
                                  nullptr, dout_slabs, dout_slab_stride));
@@ -1125,7 +1125,7 @@ static int tail_fold4(const TailStep& s, const TextFold& tf) {
     const bool merge_late = s.paired && s.glue;
     if (merge_late) TRY(issued(vis_next_beside(s, f.part, nullptr, pr, 1)));
     else if (s.paired) TRY(issued(vis_next_beside(s, f.part, af.tickets(), pr, 0)));
-    else TRY(issued(launch_small_plan_x(pr, s.st)));
+    else TRY(issued(launch_small_plan(pr, s.st)));
     return issued(fold_score(s, merge_late ? f.part : nullptr, tp->r, 0, nullptr, tp->wt));
 }
 

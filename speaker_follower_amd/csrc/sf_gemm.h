@@ -1,6 +1,7 @@
 // Internal GEMM interface (fp32 in / fp32 accumulate on the gfx950 matrix cores).
 #pragma once
 #include "sf_common.h"
+#include "sf_gemm_plan.h"
 
 namespace sf {
 
@@ -13,13 +14,7 @@ struct Seg {
     int K;
 };
 
-// Epilogue applied by the split-K reduce pass (or inline when there is a single split).
-enum Epi : int {
-    EPI_NONE = 0,    // y = acc + bias
-    EPI_TANH = 1,    // y = tanh(acc + bias)
-    EPI_MUL = 2,     // y = (acc + bias) * mul[n]         (EltwiseProdScoring fold)
-    EPI_TANHBWD = 3, // y = (acc + bias) * (1 - aux[m,n]^2)   (backward through h~ = tanh(.))
-};
+// (enum Epi, the epilogue of a product: sf_gemm_plan.h)
 
 struct LinearOut {
     float* y;          // [M, ldy]
@@ -42,11 +37,6 @@ struct LinearOut {
     const float* r1_v;
 };
 
-// Workspace needed (in floats) for sf::linear_nt on an [M,N] output with total depth K.
-size_t linear_ws_floats(int M, int N, int Ktot);
-// How many K-splits linear_nt will use (1 => no workspace traffic).
-int linear_ksplit(int M, int N, int Ktot);
-
 // y[M,N] = epi( sum_s A_s[M,K_s] * W_s[N,K_s]^T + bias (+bias2) ).  K_s % 4 == 0, lda/ldw % 4 == 0.
 // If `raw_slabs` is non-null the reduce pass is skipped and the caller receives the split-K
 // partial slabs ([ksplit][M][N]) -- used by the LSTM cell whose pointwise kernel reduces them.
@@ -58,7 +48,7 @@ int linear_nt(const Seg* segs, int nseg, int M, int N, const LinearOut& out, flo
               const void* const* packed_w = nullptr);
 
 // bf16 weight storage of the gate product (include/sf_hip.h: sf_gate_product_bf16_weights)
-bool bf16w_supported(int M, int N, const int* K, int nseg);
+// (bf16w_supported: sf_gemm_plan.h)
 size_t pack_bf16_bytes(int rows, int K);                                                  // 0: K % 64 != 0 (or empty)
 int pack_bf16(const float* w, int ld, int rows, int K, void* out, hipStream_t st);        // rne, torch's float -> bfloat16
 
@@ -76,7 +66,7 @@ struct TnJob {                        // one weight gradient out[P,Q] (+)= Y[M,P
     int accumulate;
 };
 int gemm_tn_group(const TnJob* jobs, int n, hipStream_t st, float* ws, size_t ws_floats);
-int gemm_tn_main_columns(int M, int P, int Q);
+// (gemm_tn_main_columns: sf_gemm_plan.h)
 extern int g_tn_group;                // sf_debug_grouped_weight_gradients
 int gemm_tn(const float* Y, int ldy, const float* X, int ldx, int M, int P, int Q, float* out,
             int ldo, int accumulate, hipStream_t st, float* ws = nullptr, size_t ws_floats = 0);

@@ -17,10 +17,12 @@
 // the epilogue writes back as float4.
 #include "sf_gemm.h"
 #include "sf_gemm_small.h"
+#include "sf_kernels.h"
 #include "sf_lstm.h"
 #include "sf_split.h"
 
 #include <cstdlib>
+#include <utility>
 
 namespace sf {
 
@@ -28,6 +30,7 @@ int g_tn_split_min_rows = 4096;   // sf_debug_tn_split_min_rows (tests run the s
 int g_nt_big_ksplit = 1;     // sf_debug_many_row_product(on | 2 * no K splits of the raw-slab many-row products)
 int g_nt_big = 1;            // sf_debug_many_row_product: M >= 512 products on gemm_nt_big_kernel (0: gemm_nt_kernel, rounds 1-4)
 int g_nt_force_f32 = 0;      // sf_debug_gate_product_f32: run the LSTM gate product on v_mfma_f32_16x16x4_f32 (round 1-3 kernel)
+int g_tn_group = 1;          // sf_debug_grouped_weight_gradients (0: one gemm_tn per product, the round-5 first form)
 
 namespace {
 
@@ -193,7 +196,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(NtArgs a) {
 // Row stride 72 dwords: conflict-free for the ds_read_b128 lane groups of gfx950 ({0-3,12-15,20-27},
 // ...: MI355X_MICROARCH.md, LDS table).  68 gave a 2-way conflict in every group
 // (SQ_LDS_BANK_CONFLICT = 35 % of SQ_LDS_IDX_ACTIVE).
-constexpr int TBK = 64, TLD = TBK + 8;
+// (TBK = 64, TLD = TBK + 8: sf_gemm_plan.h)
 
 // 8 waves per block: waves 0-3 take the first half of every 64-deep stage, waves 4-7 the second
 // half (two waves per SIMD hide each other's barrier and LDS latencies); the halves meet in LDS.
@@ -404,13 +407,13 @@ __global__ __launch_bounds__(512) void gemm_nt_tiled_kernel(NtArgs a) {
 // the unrounded activations with bf16(W).  Everything else -- block shape, stages, K splits, prefetch ring, epilogue -- is
 // the code below, shared.
 // ------------------------------------------------------------------------------------------------
-constexpr int SPL_ROWB = 128;             // bytes per row and plane (64 bf16)
+// (SPL_ROWB = 128 bytes per row and plane, 64 bf16: sf_gemm_plan.h)
 
 // The packed bf16 weight image of one [rows, K] matrix (K % 64 == 0; rows padded with zeros to a multiple of 16):
 // [n-tile of 16 rows][64-deep stage][K half][lane = 16 kk + li][8 bf16].  The 16 bytes of lane (li, kk) are what that lane
 // feeds one v_mfma_f32_16x16x32_bf16 for row 16 tile + li: k = 32 half + 4 kk .. + 3 and 32 half + 16 + 4 kk .. + 3, the K
 // order of the activation planes in LDS.  A wave's fragment of a stage is one global_load_dwordx4 over 1 KB of whole lines.
-constexpr int BW_STAGE_BYTES = 2 * 64 * 16;          // per n-tile and stage
+// (BW_STAGE_BYTES = 2 * 64 * 16 per n-tile and stage: sf_gemm_plan.h)
 struct NtPackedW {
     const void* p[3];
 };
@@ -751,7 +754,7 @@ struct NtBigArgs {
     int epi, accumulate;
     int ksplit;            // > 1: grid.y K-splits, split z writes its partial tile to slab y + z * M * N (ldy = N, plain)
 };
-constexpr int NB_T = 128, NB_K = 32, NB_PLANE = NB_T * 64;          // bytes per plane and stage (128 rows x 64 B)
+// (NB_T = 128, NB_K = 32, NB_PLANE = NB_T * 64 bytes per plane and stage, 128 rows x 64 B: sf_gemm_plan.h)
 
 __device__ __forceinline__ void nt_big_body(const NtBigArgs& a, const int tile, const int split_of_block) {
     extern __shared__ __attribute__((aligned(16))) unsigned char nb_smem[];   // [2 buffers][A | W][3 planes][128 rows][64 B]
@@ -903,7 +906,6 @@ __global__ __launch_bounds__(512) void gemm_nt_big_kernel(NtBigArgs a) { nt_big_
 // SEVERAL many-row products in one launch (gemm_tn_group: the decoder's small weight gradients -- each a few dozen tiles,
 // 35 dependent launches of 5-28 us between them when issued one by one): block b belongs to job j with
 // first[j] <= b < first[j + 1]; inside the job blocks walk its tiles, then its K splits.
-constexpr int NB_GROUP = 8;
 struct NtBigGroup {
     NtBigArgs job[NB_GROUP];
     int first[NB_GROUP + 1];
@@ -920,7 +922,6 @@ __global__ __launch_bounds__(512) void gemm_nt_big_group_kernel(NtBigGroup g) {
 }
 
 // Several transposes in one launch: problem p's 32 x 32 tiles are blocks first[p] .. first[p + 1] - 1
-constexpr int TR_GROUP = 16;
 struct TrGroup {
     struct P { const float* src; float* dst; int lds, R, C; } p[TR_GROUP];
     int first[TR_GROUP + 1];
@@ -1523,7 +1524,7 @@ __global__ __launch_bounds__(256) void colsum_finish_kernel(const float* part, i
 // streaming kernel above pulls 2 KB per wave and 16 MFMAs -- at the matrix-pipe rate that is the
 // ~40 GB/s one CU sustains; this one pulls half of that.  A fragment row is 256 contiguous bytes
 // per 16 lanes: conflict-free without padding.
-constexpr int TNT_BM = 16, TNT_B = 128;
+constexpr int TNT_BM = 16;             // (TNT_B = 128: sf_gemm_plan.h)
 
 __global__ __launch_bounds__(256) void gemm_tn_tiled_kernel(TnArgs a) {
     __shared__ float4 Ys[2][TNT_BM][TNT_B / 4];
@@ -1633,9 +1634,9 @@ __global__ __launch_bounds__(256) void gemm_tn_tiled_kernel(TnArgs a) {
 //   planes [column][m]) so that the product kernel only copies.
 //   split-M over grid.z into slabs for small outputs (same reduce_slabs as the fp32 kernels: deterministic order).
 // ------------------------------------------------------------------------------------------------
-constexpr int TNS_B = 128, TNS_K = 64, TNS_ROWB = 128;
+constexpr int TNS_K = 64, TNS_ROWB = 128;             // (TNS_B = 128: sf_gemm_plan.h)
 constexpr int TNS_PLANE = TNS_B * TNS_ROWB;           // one piece plane of one operand: 16 KB
-constexpr int TNS_LDS = 2 * 3 * TNS_PLANE;
+static_assert(TNS_LDS == 2 * 3 * TNS_PLANE, "sf_gemm_plan.h: the stage buffer of gemm_tn_split_kernel");
 
 __global__ __launch_bounds__(256, 1) void gemm_tn_split_kernel(TnArgs a) {
     extern __shared__ __align__(16) unsigned char tns_smem[];
@@ -1744,88 +1745,82 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_split_kernel(TnArgs a) {
     }
 }
 
-int pick_ksplit(int waves_per_split, int chunks) {
-    // aim for ~2 waves per SIMD over the chip (1024 SIMDs), at least 4 16-deep chunks per split,
-    // and at most 8 partial slabs (each split costs one extra write + read of the output)
-    int ks = (2048 + waves_per_split - 1) / waves_per_split;
-    ks = std::min(ks, std::max(1, chunks / 4));
-    return std::max(1, std::min(ks, 8));
+// ------------------------------------------------------------------------------------------------
+// ISSUE.  Every entry below checks its arguments, asks sf_gemm_plan.h for a plan (which kernel, grid, splits, workspace
+// layout: pure host code, tests/test_gemm_plan_host.py), fills the kernel's argument struct from the plan and the
+// pointers, and launches.  Nothing here decides.
+// ------------------------------------------------------------------------------------------------
+static_assert((int)PLAN_OK == (int)SF_OK && (int)PLAN_UNSUPPORTED == (int)SF_ERR_UNSUPPORTED &&
+              (int)PLAN_WORKSPACE == (int)SF_ERR_WORKSPACE, "sf_gemm_plan.h: PlanStatus");
+
+inline GemmSwitches switches() {
+    return GemmSwitches{g_nt_force_f32, g_nt_big, g_nt_big_ksplit, g_tn_split_min_rows, g_tn_group};
+}
+inline dim3 dim(const PlanGrid& g) { return dim3(g.x, g.y, g.z); }
+
+// Calls f(std::integral_constant<int, I>) for the I of [0, N) that equals `want`; false when there is none.  The one
+// place where a planned instantiation (SMALL_INST, 1 .. NT_MT_MAX, NN_INST of sf_gemm_plan.h) becomes a template argument.
+template <class F, int... I>
+bool with_index(int want, F&& f, std::integer_sequence<int, I...>) {
+    return ((I == want && (f(std::integral_constant<int, I>{}), true)) || ...);
+}
+template <int N, class F>
+bool with_index(int want, F&& f) {
+    return with_index(want, f, std::make_integer_sequence<int, N>{});
 }
 
-template <int MT>
-void launch_nt(const NtArgs& a, dim3 grid, hipStream_t st) {
-    static const std::string nm = "gemm_nt_kernel<" + std::to_string(MT) + ">";
-    SF_LAUNCH_AS(nm.c_str(), gemm_nt_kernel<MT>, grid, dim3(256), 0, st, a);
+// "kernel<1, 4>": an instantiation as kernel_profile() spells it (a launch inside a template only sees "<MT, CPW>")
+template <auto Kernel, int... A>
+const char* inst_name(const char* kernel) {
+    static const std::string nm = [kernel] {
+        std::string s = std::string(kernel) + "<";
+        const char* sep = "";
+        ((s += sep + std::to_string(A), sep = ", "), ...);
+        return s + ">";
+    }();
+    return nm.c_str();
 }
 
-template <int MT>
-void launch_nn(const NnArgs& a, dim3 grid, hipStream_t st) {
-    static const std::string nm = "gemm_nn_kernel<" + std::to_string(MT) + ">";
-    SF_LAUNCH_AS(nm.c_str(), gemm_nn_kernel<MT>, grid, dim3(256), 0, st, a);
+// A launch of a kernel that takes more than 64 KB of dynamic LDS: that must be opted into, once per instantiation
+template <auto Kernel, class... Args>
+void launch_big_lds(const char* name, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+    static const hipError_t opted = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)opted;
+    SF_LAUNCH_AS(name, Kernel, grid, block, lds, st, args...);
 }
 
-inline int red_grid(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 2048); }
+// y (+)= epi(sum of the `ks` slabs [M][N] + bias), in a fixed order: deterministic
+void reduce_slabs(const float* slabs, int ks, int M, int N, const LinearOut& o, hipStream_t st) {
+    const RedArgs r{slabs, ks, M, N, o.y, o.ldy, o.bias, o.bias2, o.mul, o.y_pre, o.ldy_pre, o.epi, o.accumulate};
+    SF_LAUNCH(reduce_slabs_kernel, dim3((int)std::min<size_t>(((size_t)M * N + 255) / 256, 2048)), dim3(256), 0, st, r);
+}
+inline LinearOut plain_out(float* y, int ldy, int accumulate) {
+    LinearOut o{};
+    o.y = y; o.ldy = ldy; o.epi = EPI_NONE; o.accumulate = accumulate;
+    return o;
+}
+
+int nt_big_launch(const NtBigArgs& b, const PlanGrid& grid, hipStream_t st) {
+    launch_big_lds<gemm_nt_big_kernel>("gemm_nt_big_kernel", dim(grid), dim3(512), (size_t)2 * 6 * NB_PLANE, st, b);
+    return launch_status();
+}
+
+SmallArgs small_args(const Seg* segs, int nseg, int M, int N, const LinearOut& out) {
+    SmallArgs sa{};
+    sa.sg.s0 = segs[0];
+    sa.sg.n0 = ceil_div(segs[0].K, 16);
+    sa.sg.s1 = nseg == 2 ? segs[1] : segs[0];
+    sa.sg.total = sa.sg.n0 + (nseg == 2 ? ceil_div(segs[1].K, 16) : 0);
+    sa.M = M; sa.N = N; sa.y = out.y; sa.ldy = out.ldy; sa.bias = out.bias; sa.bias2 = out.bias2;
+    sa.epi = out.epi; sa.mul = out.mul; sa.y_pre = out.y_pre; sa.ldy_pre = out.ldy_pre;
+    sa.accumulate = out.accumulate;
+    sa.aux = out.aux; sa.ld_aux = out.ld_aux; sa.addend = out.addend; sa.ld_addend = out.ld_addend;
+    sa.r1_s = out.r1_s; sa.r1_v = out.r1_v;
+    return sa;
+}
 
 }  // namespace
-
-// Short-reduction path: K <= 1024 and a small output (decode-step Linears).  Returns false when the
-// streaming kernel should be used instead.
-static bool small_shape(int M, int N, int chunks, int* mt, int* cpw) {
-    const int mtiles = ceil_div(M, 16), ntiles = ceil_div(N, 16);
-    if (chunks > 144 || (long)mtiles * ntiles > (chunks > 64 ? 512 : 2048)) return false;
-    if (chunks > 128 && (long)mtiles * ntiles > 128) return false;   // (K = 2176 -> 256: the dq / dr products)
-    const int c = ceil_div(chunks, SMALL_WAVES);          // chunks per wave: 1..18
-    *cpw = c <= 2 ? 2 : (c <= 4 ? 4 : (c <= 8 ? 8 : (c <= 16 ? 16 : 18)));
-    int m = std::max(1, std::min(mtiles, 32 / *cpw - 1)); // <= 32 float4 of loads per lane
-    m = m >= 4 ? 4 : (m >= 2 ? 2 : 1);
-    // a CU sustains only ~20-35 GB/s of loads, so what matters is the bytes ONE block pulls
-    // (16 W rows + 16*m A rows, K deep): prefer more, lighter blocks until the chip is covered
-    while (m > 1 && ntiles * ceil_div(mtiles, m) < 224) m >>= 1;
-    *mt = m;
-    return true;
-}
-
-template <int MT, int CPW>
-static void launch_small(const SmallArgs& a, hipStream_t st) {
-    dim3 grid(ceil_div(a.N, 16), ceil_div(ceil_div(a.M, 16), MT));
-    static const std::string tp = "<" + std::to_string(MT) + ", " + std::to_string(CPW) + ">";
-    static const std::string nx = "gemm_nt_small_x_kernel" + tp, nn = "gemm_nt_small_kernel" + tp;
-    if (a.addend || a.r1_s || a.epi == EPI_TANHBWD)
-        SF_LAUNCH_AS(nx.c_str(), (gemm_nt_small_x_kernel<MT, CPW>), grid, dim3(SMALL_WAVES * 64), 0, st, a);
-    else
-        SF_LAUNCH_AS(nn.c_str(), (gemm_nt_small_kernel<MT, CPW>), grid, dim3(SMALL_WAVES * 64), 0, st, a);
-}
-
-static void nt_shape(int M, int N, int Ktot_chunks, int* mt, int* mblocks, int* ks) {
-    const int mtiles = ceil_div(M, 16), ntiles = ceil_div(N, 16);
-    if (Ktot_chunks <= 64) {
-        // short reduction with a large output (the hoisted encoder input product): never split K
-        int m = 1;
-        while (m < 8 && (long)ntiles * ceil_div(mtiles, m) > 4096) m *= 2;
-        *mt = std::min(m, mtiles);
-        *mblocks = ceil_div(mtiles, *mt);
-        *ks = 1;
-        return;
-    }
-    *mt = mtiles <= 8 ? mtiles : 8;
-    *mblocks = ceil_div(mtiles, *mt);
-    *ks = pick_ksplit(ntiles * *mblocks, Ktot_chunks);
-    // the LDS-tiled kernel runs one workgroup per CU: a grid of more than 256 of them (34 n-tiles x 8
-    // splits for the [100,2048] x [2048,2176] input gradient) pays a second, nearly empty round
-    if (*mblocks == 1 && Ktot_chunks >= 128)
-        while (*ks > 1 && ceil_div(N, 64) * *ks > 256) --*ks;
-}
-
-int linear_ksplit(int M, int N, int Ktot) {
-    int mt, mb, ks;
-    nt_shape(M, N, ceil_div(Ktot, 16), &mt, &mb, &ks);
-    return ks;
-}
-
-size_t linear_ws_floats(int M, int N, int Ktot) {
-    const int ks = linear_ksplit(M, N, Ktot);
-    return ks > 1 ? (size_t)ks * M * N : 0;
-}
 
 bool linear_small_plan(const Seg* segs, int nseg, int M, int N, const LinearOut& out,
                        SmallPlan* plan) {
@@ -1835,65 +1830,28 @@ bool linear_small_plan(const Seg* segs, int nseg, int M, int N, const LinearOut&
         if (segs[s].K <= 0 || segs[s].K % 4 || segs[s].lda % 4 || segs[s].ldw % 4) return false;
         chunks += ceil_div(segs[s].K, 16);
     }
-    int mt, cpw;
-    if (!small_shape(M, N, chunks, &mt, &cpw)) return false;
-    SmallArgs& sa = plan->args;
-    sa = SmallArgs{};
-    sa.sg.s0 = segs[0];
-    sa.sg.n0 = ceil_div(segs[0].K, 16);
-    sa.sg.s1 = nseg == 2 ? segs[1] : segs[0];
-    sa.sg.total = chunks;
-    sa.M = M; sa.N = N; sa.y = out.y; sa.ldy = out.ldy; sa.bias = out.bias; sa.bias2 = out.bias2;
-    sa.epi = out.epi; sa.mul = out.mul; sa.y_pre = out.y_pre; sa.ldy_pre = out.ldy_pre;
-    sa.accumulate = out.accumulate;
-    sa.aux = out.aux; sa.ld_aux = out.ld_aux; sa.addend = out.addend; sa.ld_addend = out.ld_addend;
-    sa.r1_s = out.r1_s; sa.r1_v = out.r1_v;
-    plan->mt = mt;
-    plan->cpw = cpw;
+    if (!plan_detail::small_shape(M, N, chunks, &plan->mt, &plan->cpw)) return false;
+    plan->args = small_args(segs, nseg, M, N, out);
     plan->gx = ceil_div(N, 16);
-    plan->gy = ceil_div(ceil_div(M, 16), mt);
+    plan->gy = ceil_div(ceil_div(M, 16), plan->mt);
     return true;
 }
 
-static int launch_small_plan(const SmallPlan& p, hipStream_t st) {
-    const SmallArgs& sa = p.args;
-    switch (p.mt * 32 + p.cpw) {
-        case 1 * 32 + 2: launch_small<1, 2>(sa, st); break;
-        case 1 * 32 + 4: launch_small<1, 4>(sa, st); break;
-        case 1 * 32 + 8: launch_small<1, 8>(sa, st); break;
-        case 1 * 32 + 16: launch_small<1, 16>(sa, st); break;
-        case 1 * 32 + 18: launch_small<1, 18>(sa, st); break;
-        case 2 * 32 + 2: launch_small<2, 2>(sa, st); break;
-        case 2 * 32 + 4: launch_small<2, 4>(sa, st); break;
-        case 2 * 32 + 8: launch_small<2, 8>(sa, st); break;
-        case 4 * 32 + 2: launch_small<4, 2>(sa, st); break;
-        case 4 * 32 + 4: launch_small<4, 4>(sa, st); break;
-        default: return SF_ERR_UNSUPPORTED;
-    }
-    return launch_status();
-}
-
-int launch_small_plan_x(const SmallPlan& p, hipStream_t st) { return launch_small_plan(p, st); }
-
-int transpose_ld(const float* src, int lds, int R, int C, float* dst, hipStream_t st);     // sf_pointwise.hip
-
-static int nt_big_launch(const NtBigArgs& b, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_big_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    const dim3 grid(ceil_div(b.M, NB_T) * ceil_div(b.N, NB_T), b.ksplit > 1 ? b.ksplit : 1);
-    SF_LAUNCH(gemm_nt_big_kernel, grid, dim3(512),
-              (size_t)2 * 6 * NB_PLANE, st, b);
-    return launch_status();
-}
-
-bool bf16w_supported(int M, int N, const int* K, int nseg) {
-    bool ok = M >= 1 && M <= 128 && N >= 1 && nseg >= 1 && nseg <= 3;
-    for (int s = 0; ok && s < nseg; ++s) ok = K[s] > 0 && K[s] % TBK == 0;
-    return ok;
+int launch_small_plan(const SmallPlan& p, hipStream_t st) {
+    const SmallArgs& a = p.args;
+    const bool extras = a.addend || a.r1_s || a.epi == EPI_TANHBWD;
+    const dim3 grid(p.gx, p.gy), block(SMALL_WAVES * 64);
+    const bool known = with_index<SMALL_INSTS>(small_inst(p.mt, p.cpw), [&](auto i) {
+        constexpr int MT = SMALL_INST[decltype(i)::value].mt, CPW = SMALL_INST[decltype(i)::value].cpw;
+        if (extras) {
+            const char* nm = inst_name<gemm_nt_small_x_kernel<MT, CPW>, MT, CPW>("gemm_nt_small_x_kernel");
+            SF_LAUNCH_AS(nm, (gemm_nt_small_x_kernel<MT, CPW>), grid, block, 0, st, a);
+        } else {
+            const char* nm = inst_name<gemm_nt_small_kernel<MT, CPW>, MT, CPW>("gemm_nt_small_kernel");
+            SF_LAUNCH_AS(nm, (gemm_nt_small_kernel<MT, CPW>), grid, block, 0, st, a);
+        }
+    });
+    return known ? launch_status() : SF_ERR_UNSUPPORTED;
 }
 
 size_t pack_bf16_bytes(int rows, int K) {
@@ -1910,216 +1868,74 @@ int pack_bf16(const float* w, int ld, int rows, int K, void* out, hipStream_t st
     return launch_status();
 }
 
-// The gate product with bf16-stored weights (gemm_nt_bf16w_kernel): raw slabs only, the K splits of nt_shape (what the
-// caller's workspace was sized for), all rows in one block.
-static int linear_nt_bf16w(const NtArgs& base, int chunks, const void* const* packed, float* ws, size_t ws_floats,
-                           hipStream_t st, float** raw_slabs, int* ksplit_out) {
-    NtArgs a = base;
-    int mt, mblocks, ks;
-    nt_shape(a.M, a.N, chunks, &mt, &mblocks, &ks);
-    mt = ceil_div(a.M, 16);
-    if (!ws || ws_floats < (size_t)ks * a.M * a.N) return SF_ERR_WORKSPACE;
-    a.chunks_total = chunks;
-    a.ksplit = ks;
-    a.epi = EPI_NONE;
-    a.out = ws;
-    a.ldo = a.N;
-    NtPackedW pk{};
-    for (int s = 0; s < a.nseg; ++s) pk.p[s] = packed[s];
-    const dim3 grid(ceil_div(a.N, 64), ks);
-    const size_t lds = std::max<size_t>((size_t)2 * 3 * (((mt + 1) / 2) * 32) * SPL_ROWB, (size_t)4 * mt * 64 * 16);
-#define SF_BF16W(MTV)                                                                              \
-    case MTV: {                                                                                    \
-        static bool attr_set = false;                                                              \
-        if (!attr_set) {                                                                           \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_bf16w_kernel<MTV>),    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
-            attr_set = true;                                                                       \
-        }                                                                                          \
-        SF_LAUNCH(gemm_nt_bf16w_kernel<MTV>, grid, dim3(512), lds, st, a, pk);                     \
-    } break;
-    switch (mt) {
-        SF_BF16W(1) SF_BF16W(2) SF_BF16W(3) SF_BF16W(4) SF_BF16W(5) SF_BF16W(6) SF_BF16W(7) SF_BF16W(8)
-        default: return SF_ERR_UNSUPPORTED;
-    }
-#undef SF_BF16W
-    if (ksplit_out) *ksplit_out = ks;
-    *raw_slabs = ws;
-    return launch_status();
-}
-
 int linear_nt(const Seg* segs, int nseg, int M, int N, const LinearOut& out, float* ws,
               size_t ws_floats, hipStream_t st, float** raw_slabs, int* ksplit_out, const void* const* packed_w) {
     SF_CHECK_ARG(nseg >= 1 && nseg <= 3 && M > 0 && N > 0);
-    NtArgs a{};
-    a.nseg = nseg;
-    int chunks = 0;
+    NtAsk q{};
     for (int s = 0; s < nseg; ++s) {
         SF_CHECK_ARG(segs[s].K > 0 && segs[s].K % 4 == 0 && segs[s].lda % 4 == 0 &&
                      segs[s].ldw % 4 == 0);
-        a.seg[s] = segs[s];
-        chunks += ceil_div(segs[s].K, 16);
+        q.K[s] = segs[s].K;
     }
-    if (packed_w && raw_slabs && !g_nt_force_f32) {
-        int Ks[3] = {0, 0, 0};
-        for (int s = 0; s < nseg; ++s) Ks[s] = segs[s].K;
-        if (bf16w_supported(M, N, Ks, nseg)) {
-            a.M = M;
-            a.N = N;
-            return linear_nt_bf16w(a, chunks, packed_w, ws, ws_floats, st, raw_slabs, ksplit_out);
-        }
-    }
-    int mt, mblocks, ks;
-    SmallPlan sp;
-    if (!raw_slabs && linear_small_plan(segs, nseg, M, N, out, &sp)) {
-        const int rc = launch_small_plan(sp, st);
-        if (ksplit_out) *ksplit_out = 1;
-        return rc;
-    }
-    // (raw_slabs: the caller sums split-K slabs itself -- the LSTM cell kernel; here ONE slab without bias)
-    bool big = M >= 512 && N >= 64 && chunks >= 4 && !out.r1_s && g_nt_big &&
-               (out.epi == EPI_NONE || out.epi == EPI_TANH) && !(out.accumulate && out.epi != EPI_NONE) &&
-               (!raw_slabs || (ws && ws_floats >= (size_t)M * N));
-    for (int s = 0; s < nseg; ++s) big = big && segs[s].K >= NB_K;        // (a partial last stage per segment is fine)
-    if (big) {
-        // many rows: 128 x 128 tiles through LDS on the bf16 matrix cores (gemm_nt_big_kernel)
+    q.M = M; q.N = N; q.nseg = nseg;
+    q.raw_slabs = raw_slabs; q.ksplit_out = ksplit_out; q.packed_w = packed_w;
+    q.epi = out.epi; q.accumulate = out.accumulate; q.addend = out.addend; q.r1_s = out.r1_s;
+    q.ws_floats = ws ? ws_floats : 0;
+    const NtPlan p = plan_nt(q, switches());
+    if (p.status != PLAN_OK) return p.status;
+    if (ksplit_out) *ksplit_out = p.ksplit;
+    if (raw_slabs) *raw_slabs = ws;
+    if (p.family == NT_SMALL)
+        return launch_small_plan(SmallPlan{small_args(segs, nseg, M, N, out), p.mt, p.cpw, p.grid.x, p.grid.y}, st);
+    if (p.family == NT_BIG) {
         NtBigArgs b{};
         for (int s = 0; s < nseg; ++s) b.seg[s] = segs[s];
-        b.nseg = nseg; b.M = M; b.N = N; b.y = out.y; b.ldy = out.ldy; b.bias = out.bias; b.bias2 = out.bias2;
-        b.addend = out.addend; b.ld_addend = out.ld_addend; b.epi = (int)out.epi; b.accumulate = out.accumulate;
-        int kb = 1;
-        if (raw_slabs) {
-            b.y = ws; b.ldy = N; b.bias = b.bias2 = b.addend = nullptr; b.epi = EPI_NONE; b.accumulate = 0;
-            *raw_slabs = ws;
-            // The consumer adds the slabs up anyway, so K splits are free of a reduce launch: take them when the tile
-            // count wastes a round of the 256 CUs (the beam step's 2 560 x 2 048: 320 tiles = 2 rounds; 3 splits =
-            // 960 units = 4 rounds of a third each).  Cost of a split: one more slab written and read (M N floats).
-            if (ksplit_out && g_nt_big_ksplit) {
-                const int tiles = ceil_div(M, NB_T) * ceil_div(N, NB_T);
-                int stages = 0;
-                for (int s = 0; s < nseg; ++s) stages += ceil_div(segs[s].K, NB_K);
-                double best = (double)ceil_div(tiles, 256);
-                for (int c = 2; c <= 3; ++c) {
-                    if (ws_floats < (size_t)c * M * N || stages < 16 * c) break;
-                    const double t = (double)ceil_div(tiles * c, 256) / c + 0.04 * (c - 1);
-                    if (t < best - 1e-9) { best = t; kb = c; }
-                }
-            }
+        b.nseg = nseg; b.M = M; b.N = N; b.ksplit = p.ksplit;
+        if (p.slabs) {                   // (raw slabs: the caller adds them up, and the bias, itself)
+            b.y = ws; b.ldy = N; b.epi = EPI_NONE;
+        } else {
+            b.y = out.y; b.ldy = out.ldy; b.bias = out.bias; b.bias2 = out.bias2;
+            b.addend = out.addend; b.ld_addend = out.ld_addend; b.epi = (int)out.epi; b.accumulate = out.accumulate;
         }
-        b.ksplit = kb;
-        if (ksplit_out) *ksplit_out = kb;
-        return nt_big_launch(b, st);
+        return nt_big_launch(b, p.grid, st);
     }
-    if (out.addend || out.r1_s || out.epi == EPI_TANHBWD) return SF_ERR_UNSUPPORTED;   // small kernel only
-    nt_shape(M, N, chunks, &mt, &mblocks, &ks);
-    const bool slabs = ks > 1 || raw_slabs;
-    if (slabs) {
-        if (!ws || ws_floats < (size_t)ks * M * N) return SF_ERR_WORKSPACE;
+    NtArgs a{};
+    a.nseg = nseg;
+    for (int s = 0; s < nseg; ++s) {
+        a.seg[s] = segs[s];
+        a.chunks_total += ceil_div(segs[s].K, 16);
     }
-    a.M = M;
-    a.N = N;
-    a.chunks_total = chunks;
-    a.ksplit = ks;
-    a.epi = EPI_NONE;
-    if (slabs) {
-        a.out = ws;
-        a.ldo = N;
-        a.bias = nullptr;
-        a.bias2 = nullptr;
-    } else {
-        a.out = out.y;
-        a.ldo = out.ldy;
-        a.bias = out.bias;
-        a.bias2 = out.bias2;
-        a.epi = out.epi;            // single split: epilogue fused into the GEMM
-        a.accumulate = out.accumulate;
-        a.mul = out.mul;
-        a.y_pre = out.y_pre;
-        a.ldy_pre = out.ldy_pre;
+    a.M = M; a.N = N; a.ksplit = p.ksplit; a.epi = EPI_NONE;
+    if (p.slabs) {
+        a.out = ws; a.ldo = N;
+    } else {                        // single split: bias and epilogue fused into the GEMM
+        a.out = out.y; a.ldo = out.ldy; a.bias = out.bias; a.bias2 = out.bias2; a.epi = out.epi;
+        a.accumulate = out.accumulate; a.mul = out.mul; a.y_pre = out.y_pre; a.ldy_pre = out.ldy_pre;
     }
-    bool launched = false;
-    const NtArgs& k = a;   // raw slabs with ks == 1: slab 0 is written without bias
-    bool tiled = !launched && mblocks == 1 && chunks >= 128 && N % 64 == 0 && a.epi == EPI_NONE;
-    for (int s = 0; s < nseg; ++s) tiled = tiled && segs[s].K % TBK == 0;
-    if (tiled && M <= 128 && !g_nt_force_f32) {
-        // fp32 accuracy on the bf16 matrix cores (gemm_nt_split_kernel): 6/16 of the fp32-MFMA time
-        dim3 tgrid(N / 64, ks);
-        const size_t lds = std::max<size_t>((size_t)2 * 3 * (((mt + 1) / 2) * 32) * SPL_ROWB, (size_t)4 * mt * 64 * 16);
-#define SF_SPLIT(MTV)                                                                               \
-    case MTV: {                                                                                    \
-        static bool attr_set = false;                                                              \
-        if (!attr_set) {                                                                           \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_split_kernel<MTV>),    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
-            attr_set = true;                                                                       \
-        }                                                                                          \
-        SF_LAUNCH(gemm_nt_split_kernel<MTV>, tgrid, dim3(512), lds, st, k);                        \
-    } break;
-        switch (mt) {
-            SF_SPLIT(1) SF_SPLIT(2) SF_SPLIT(3) SF_SPLIT(4) SF_SPLIT(5) SF_SPLIT(6) SF_SPLIT(7) SF_SPLIT(8)
+    NtPackedW pk{};
+    for (int s = 0; p.family == NT_BF16W && s < nseg; ++s) pk.p[s] = packed_w[s];
+    const dim3 grid = dim(p.grid), block(p.block);
+    const bool known = with_index<NT_MT_MAX>(p.mt - 1, [&](auto i) {
+        constexpr int MT = decltype(i)::value + 1;
+        switch (p.family) {
+            case NT_BF16W:
+                launch_big_lds<gemm_nt_bf16w_kernel<MT>>(inst_name<gemm_nt_bf16w_kernel<MT>, MT>("gemm_nt_bf16w_kernel"),
+                                                         grid, block, p.lds, st, a, pk);
+                break;
+            case NT_SPLIT:
+                launch_big_lds<gemm_nt_split_kernel<MT>>(inst_name<gemm_nt_split_kernel<MT>, MT>("gemm_nt_split_kernel"),
+                                                         grid, block, p.lds, st, a);
+                break;
+            case NT_TILED:
+                launch_big_lds<gemm_nt_tiled_kernel<MT>>(inst_name<gemm_nt_tiled_kernel<MT>, MT>("gemm_nt_tiled_kernel"),
+                                                         grid, block, p.lds, st, a);
+                break;
+            default:
+                SF_LAUNCH_AS((inst_name<gemm_nt_kernel<MT>, MT>("gemm_nt_kernel")), gemm_nt_kernel<MT>, grid, block, 0, st, a);
         }
-#undef SF_SPLIT
-    } else if (tiled) {
-        dim3 tgrid(N / 64, ks);
-        const size_t lds = (size_t)2 * (mt * 16 + 64) * TLD * sizeof(float);
-#define SF_TILED(MTV)                                                                              \
-    case MTV: {                                                                                    \
-        static bool attr_set = false;   /* > 64 KB of dynamic LDS must be opted into, once */      \
-        if (!attr_set) {                                                                           \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_tiled_kernel<MTV>),    \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
-            attr_set = true;                                                                       \
-        }                                                                                          \
-        SF_LAUNCH(gemm_nt_tiled_kernel<MTV>, tgrid, dim3(512), lds, st, k);               \
-    } break;
-        switch (mt) {
-            SF_TILED(1) SF_TILED(2) SF_TILED(3) SF_TILED(4) SF_TILED(5) SF_TILED(6) SF_TILED(7)
-            default: {
-                static bool attr8 = false;
-                if (!attr8) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_tiled_kernel<8>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    attr8 = true;
-                }
-                SF_LAUNCH(gemm_nt_tiled_kernel<8>, tgrid, dim3(512), lds, st, k);
-            }
-        }
-#undef SF_TILED
-    } else if (!launched) {
-    dim3 grid(ceil_div(N, 64), ks, mblocks);
-    switch (mt) {
-        case 1: launch_nt<1>(k, grid, st); break;
-        case 2: launch_nt<2>(k, grid, st); break;
-        case 3: launch_nt<3>(k, grid, st); break;
-        case 4: launch_nt<4>(k, grid, st); break;
-        case 5: launch_nt<5>(k, grid, st); break;
-        case 6: launch_nt<6>(k, grid, st); break;
-        case 7: launch_nt<7>(k, grid, st); break;
-        default: launch_nt<8>(k, grid, st); break;
-    }
-    }
-    if (ksplit_out) *ksplit_out = ks;
-    if (raw_slabs) {
-        *raw_slabs = ws;
-        return launch_status();
-    }
-    RedArgs r{};
-    r.M = M;
-    r.N = N;
-    r.y = out.y;
-    r.ldy = out.ldy;
-    r.mul = out.mul;
-    r.y_pre = out.y_pre;
-    r.ldy_pre = out.ldy_pre;
-    r.epi = out.epi;
-    r.accumulate = out.accumulate;
-    if (ks > 1) {
-        r.slabs = ws;
-        r.ks = ks;
-        r.bias = out.bias;
-        r.bias2 = out.bias2;
-        SF_LAUNCH(reduce_slabs_kernel, dim3(red_grid((size_t)M * N)), dim3(256), 0, st, r);
-    }
+    });
+    if (!known) return SF_ERR_UNSUPPORTED;
+    if (p.reduce) reduce_slabs(ws, p.ksplit, M, N, out, st);
     return launch_status();
 }
 
@@ -2167,42 +1983,16 @@ int gemm_nn_ws(const float* A, int lda, const float* W, int ldw, int M, int N, i
                int ldy, int accumulate, float* ws, size_t ws_floats, hipStream_t st) {
     SF_CHECK_ARG(M > 0 && N > 0 && K > 0 && N % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 &&
                  ldy % 4 == 0);
-    const int mtiles = ceil_div(M, 16);
-    int mt = mtiles <= 1 ? 1 : (mtiles <= 2 ? 2 : (mtiles <= 4 ? 4 : 7));
-    if (mtiles > 7) mt = 7;
-    const int mblocks = ceil_div(mtiles, mt);
-    const int chunks = ceil_div(K, 16);
-    int ks = pick_ksplit(ceil_div(N, 64) * mblocks, chunks);
-    if (ks > 1 && (!ws || ws_floats < (size_t)ks * M * N)) ks = 1;   // degrade, still correct
-    NnArgs a{A, lda, W, ldw, M, N, K, ks, ks > 1 ? ws : y, ks > 1 ? N : ldy, accumulate};
-    dim3 grid(ceil_div(N, 256), ks, mblocks);
-    switch (mt) {
-        case 1: launch_nn<1>(a, grid, st); break;
-        case 2: launch_nn<2>(a, grid, st); break;
-        case 4: launch_nn<4>(a, grid, st); break;
-        default: launch_nn<7>(a, grid, st); break;
-    }
-    if (ks > 1) {
-        RedArgs r{};
-        r.slabs = ws;
-        r.ks = ks;
-        r.M = M;
-        r.N = N;
-        r.y = y;
-        r.ldy = ldy;
-        r.epi = EPI_NONE;
-        r.accumulate = accumulate;
-        SF_LAUNCH(reduce_slabs_kernel, dim3(red_grid((size_t)M * N)), dim3(256), 0, st, r);
-    }
+    const NnPlan p = plan_nn(M, N, K, ws ? ws_floats : 0);
+    const bool slabs = p.ks > 1;
+    const NnArgs a{A, lda, W, ldw, M, N, K, p.ks, slabs ? ws : y, slabs ? N : ldy, accumulate};
+    const bool known = with_index<NN_INSTS>(nn_inst(p.mt), [&](auto i) {
+        constexpr int MT = NN_INST[decltype(i)::value];
+        SF_LAUNCH_AS((inst_name<gemm_nn_kernel<MT>, MT>("gemm_nn_kernel")), gemm_nn_kernel<MT>, dim(p.grid), dim3(256), 0, st, a);
+    });
+    if (!known) return SF_ERR_UNSUPPORTED;
+    if (slabs) reduce_slabs(ws, p.ks, M, N, plain_out(y, ldy, accumulate), st);
     return launch_status();
-}
-
-size_t gemm_nn_ws_floats(int M, int N, int K) {
-    const int mtiles = ceil_div(M, 16);
-    int mt = mtiles <= 1 ? 1 : (mtiles <= 2 ? 2 : (mtiles <= 4 ? 4 : 7));
-    const int mblocks = ceil_div(mtiles, mt);
-    const int ks = pick_ksplit(ceil_div(N, 64) * mblocks, ceil_div(K, 16));
-    return ks > 1 ? (size_t)ks * M * N : 0;
 }
 
 int gemm_nn(const float* A, int lda, const float* W, int ldw, int M, int N, int K, float* y,
@@ -2210,111 +2000,104 @@ int gemm_nn(const float* A, int lda, const float* W, int ldw, int M, int N, int 
     return gemm_nn_ws(A, lda, W, ldw, M, N, K, y, ldy, accumulate, nullptr, 0, st);
 }
 
-// The leading columns of a LARGE gemm_tn output [P,Q] that fill whole rounds of the chip's 1024 SIMDs with 64 x 64 wave
-// tiles (dW_ih of the decoder LSTM: 2176 tiles = 2.125 per SIMD, so some SIMDs would run 3); the narrow remainder is a
-// product of its own (a row split or the many-row kernel spreads it over the chip).  Q when the output is not cut.
-int gemm_tn_main_columns(int M, int P, int Q) {
-    const int waves = ceil_div(Q, 64) * ceil_div(P, 64);
-    const int pb = ceil_div(P, 64), qb = ceil_div(Q, 256);
-    const int rem = waves % 1024;
-    if (!(waves > 1024 && rem > 0 && rem <= 384 && rem % (4 * pb) == 0)) return Q;
-    const int r = rem / (4 * pb);                       // column blocks of 256 in the remainder
-    const int q_main = (qb - r) * 256, q_tail = Q - q_main;
-    if (!(r < qb && q_tail > 0)) return Q;
-    const int tail_waves = ceil_div(q_tail, 64) * pb;
-    const int tail_ms = std::min(16, std::max(1, 1024 / tail_waves));
-    if (!(tail_ms > 1 && M / 64 >= tail_ms)) return Q;
-    return q_main;
+namespace {
+
+// The many-row form of a weight gradient (round 5): a SMALL weight matrix with a deep reduction (the eight [256..512] x
+// [512..2176] weight gradients of the decoder over 2 000 stacked rows: 25 TFLOP/s in gemm_tn_kernel, 90 us each) as an NT
+// product of the two TRANSPOSED operands on the LDS-tiled many-row kernel: dW[P,Q] += Y^T[P,M] (X^T[Q,M])^T (bf16x6, 3x
+// closer to float64 than the fp32 kernels), into `ks` K-split slabs or, unsplit, straight into out.  gemm_tn and
+// gemm_tn_group share it; they differ in the tile budget of plan_detail::many_row_ksplit and in who transposes.
+NtBigArgs many_row_args(const TnJob& t, const float* yt, const float* xt, int ks, float* slabs) {
+    NtBigArgs b{};
+    b.seg[0] = Seg{yt, t.M, xt, t.M, t.M};
+    b.nseg = 1; b.M = t.P; b.N = t.Q; b.epi = EPI_NONE; b.ksplit = ks;
+    if (ks > 1) {
+        b.y = slabs; b.ldy = t.Q;
+    } else {
+        b.y = t.out; b.ldy = t.ldo; b.accumulate = t.accumulate;
+    }
+    return b;
 }
 
-// Whether gemm_tn runs this product as an NT product of the transposed operands on the many-row kernel (below)
-static bool tn_as_many_row(int M, int P, int Q) {
-    return g_nt_big && !g_nt_force_f32 && M >= 1024 && M % 4 == 0 && P >= 64 && Q >= 64 &&
-           (size_t)P * Q <= (size_t)1536 * 1024 && !(P % TNS_B == 0 && Q % TNS_B == 0 && M >= g_tn_split_min_rows);
+// A weight-gradient kernel into `splits` row slabs in the workspace and their sum, or straight into out
+template <auto Kernel, bool BIG_LDS>
+int tn_launch(const char* name, size_t lds, const TnJob& t, const TnPart& p, float* ws, hipStream_t st) {
+    const bool slabs = p.splits > 1;
+    const TnArgs a{t.Y, t.ldy, t.X, t.ldx, t.M, t.P, t.Q, slabs ? ws : t.out, slabs ? t.Q : t.ldo,
+                   slabs ? 0 : t.accumulate, p.splits};
+    if constexpr (BIG_LDS)
+        launch_big_lds<Kernel>(name, dim(p.grid), dim3(256), lds, st, a);
+    else
+        SF_LAUNCH_AS(name, Kernel, dim(p.grid), dim3(256), lds, st, a);
+    if (slabs) reduce_slabs(ws, p.splits, t.P, t.Q, plain_out(t.out, t.ldo, t.accumulate), st);
+    return launch_status();
 }
 
-int g_tn_group = 1;          // sf_debug_grouped_weight_gradients (0: one gemm_tn per product, the round-5 first form)
+int tn_issue(const TnJob& t, const TnPart& p, float* ws, hipStream_t st) {
+    switch (p.family) {
+        case TN_MANY_ROW: {
+            // two 32 x 32-tiled transposes into the workspace (~6 us each) + gemm_nt_big_kernel
+            float* xt = ws + p.off_xt;
+            float* slabs = ws + p.off_slabs;
+            int rc = transpose_ld(t.Y, t.ldy, t.M, t.P, ws, st);
+            if (rc != SF_OK) return rc;
+            rc = transpose_ld(t.X, t.ldx, t.M, t.Q, xt, st);
+            if (rc != SF_OK) return rc;
+            rc = nt_big_launch(many_row_args(t, ws, xt, p.splits, slabs), p.grid, st);
+            if (rc != SF_OK || p.splits == 1) return rc;
+            reduce_slabs(slabs, p.splits, t.P, t.Q, plain_out(t.out, t.ldo, t.accumulate), st);
+            return launch_status();
+        }
+        case TN_SPLIT: return tn_launch<gemm_tn_split_kernel, true>("gemm_tn_split_kernel", TNS_LDS, t, p, ws, st);
+        case TN_TILED: return tn_launch<gemm_tn_tiled_kernel, false>("gemm_tn_tiled_kernel", 0, t, p, ws, st);
+        case TN_STREAM: return tn_launch<gemm_tn_kernel, false>("gemm_tn_kernel", 0, t, p, ws, st);
+        default: return SF_ERR_UNSUPPORTED;      // (a column cut is two parts: gemm_tn)
+    }
+}
+
+}  // namespace
 
 // Several weight gradients dW_j[P_j, Q_j] (+)= Y_j^T X_j over the same kind of stacked rows in THREE launches -- all the
 // transposes (an operand two products share is transposed once), all the many-row products (gemm_nt_big_group_kernel),
 // all the slab sums -- instead of four dependent launches per product.  Products outside the many-row form (or when
 // the workspace is short) go through gemm_tn one by one.
 int gemm_tn_group(const TnJob* jobs, int n, hipStream_t st, float* ws, size_t ws_floats) {
-    int pick[NB_GROUP], np = 0;
     for (int i = 0; i < n; ++i) {
         const TnJob& t = jobs[i];
         SF_CHECK_ARG(t.M > 0 && t.P > 0 && t.Q > 0 && t.Q % 4 == 0 && t.ldy % 4 == 0 && t.ldx % 4 == 0 && t.ldo % 4 == 0);
-        if (g_tn_group && ws && np < NB_GROUP && tn_as_many_row(t.M, t.P, t.Q)) pick[np++] = i;
     }
-    // the plan: distinct transposes, K splits (every job alike: ~3 rounds of the chip between them), workspace layout
-    TrGroup tr{};
-    NtBigGroup gg{};
-    RedGroup rg{};
-    size_t off = 0;
-    auto transposed = [&](const float* src, int ld, int M, int C) -> const float* {
-        for (int k = 0; k < tr.n; ++k)
-            if (tr.p[k].src == src && tr.p[k].lds == ld && tr.p[k].R == M && tr.p[k].C == C) return tr.p[k].dst;
-        if (tr.n == TR_GROUP) return nullptr;
-        float* dst = ws + off;
-        off += ((size_t)C * M + 63) & ~(size_t)63;
-        tr.p[tr.n] = TrGroup::P{src, dst, ld, M, C};
-        tr.first[tr.n + 1] = tr.first[tr.n] + ceil_div(C, 32) * ceil_div(M, 32);
-        ++tr.n;
-        return dst;
-    };
-    bool grouped = np >= 2;
-    int tiles_all = 0;
-    for (int k = 0; k < np; ++k) tiles_all += ceil_div(jobs[pick[k]].P, NB_T) * ceil_div(jobs[pick[k]].Q, NB_T);
-    for (int k = 0; grouped && k < np; ++k) {
-        const TnJob& t = jobs[pick[k]];
-        const float* yt = transposed(t.Y, t.ldy, t.M, t.P);
-        const float* xt = yt ? transposed(t.X, t.ldx, t.M, t.Q) : nullptr;
-        if (!xt) { grouped = false; break; }
-        const int stages = ceil_div(t.M, NB_K);
-        const int ks = std::max(1, std::min(std::min(16, 768 / std::max(1, tiles_all)), stages / 4));
-        NtBigArgs& b = gg.job[k];
-        b.seg[0] = Seg{yt, t.M, xt, t.M, t.M};
-        b.nseg = 1; b.M = t.P; b.N = t.Q; b.epi = EPI_NONE; b.ksplit = ks;
-        gg.first[k + 1] = gg.first[k] + ceil_div(t.P, NB_T) * ceil_div(t.Q, NB_T) * ks;
-        if (ks > 1) {
-            b.y = nullptr; b.ldy = t.Q;                  // (slab base: below, behind every transposed operand)
-            rg.j[k] = RedGroup::J{nullptr, t.out, ks, t.P, t.Q, t.ldo, t.accumulate};
-        } else {
-            b.y = t.out; b.ldy = t.ldo; b.accumulate = t.accumulate;
-            rg.j[k] = RedGroup::J{nullptr, nullptr, 0, 0, 0, 0, 0};
+    const TnGroupPlan g = plan_tn_group(jobs, n, ws ? ws_floats : 0, switches());
+    if (g.grouped) {
+        TrGroup tr{};
+        NtBigGroup gg{};
+        RedGroup rg{};
+        for (int j = 0; j < g.ntr; ++j) {
+            const TnJob& t = jobs[g.job[g.tr[j].job]];
+            tr.p[j] = g.tr[j].x ? TrGroup::P{t.X, ws + g.tr[j].off, t.ldx, t.M, t.Q}
+                                : TrGroup::P{t.Y, ws + g.tr[j].off, t.ldy, t.M, t.P};
+            tr.first[j + 1] = tr.first[j] + ceil_div(tr.p[j].C, 32) * ceil_div(t.M, 32);
         }
-    }
-    if (grouped) {
-        size_t most = 1;
-        for (int k = 0; k < np; ++k) {
-            if (gg.job[k].ksplit > 1) {
-                gg.job[k].y = ws + off;
-                rg.j[k].slabs = ws + off;
-                off += (((size_t)gg.job[k].ksplit * gg.job[k].M * gg.job[k].N) + 63) & ~(size_t)63;
-                most = std::max(most, (size_t)gg.job[k].M * gg.job[k].N);
-            }
+        tr.n = g.ntr;
+        for (int k = 0; k < g.n; ++k) {
+            const TnJob& t = jobs[g.job[k]];
+            float* slabs = ws + g.off_slabs[k];
+            gg.job[k] = many_row_args(t, tr.p[g.yt[k]].dst, tr.p[g.xt[k]].dst, g.ks[k], slabs);
+            gg.first[k + 1] = gg.first[k] + ceil_div(t.P, NB_T) * ceil_div(t.Q, NB_T) * g.ks[k];
+            if (g.ks[k] > 1) rg.j[k] = RedGroup::J{slabs, t.out, g.ks[k], t.P, t.Q, t.ldo, t.accumulate};
         }
-        if (off > ws_floats) grouped = false;
-        if (grouped) {
-            gg.n = np;
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_big_group_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr_set = true;
-            }
-            SF_LAUNCH(transpose_group_kernel, dim3(tr.first[tr.n]), dim3(256), 0, st, tr);
-            SF_LAUNCH(gemm_nt_big_group_kernel, dim3(gg.first[np]), dim3(512), (size_t)2 * 6 * NB_PLANE, st, gg);
-            bool any = false;
-            for (int k = 0; k < np; ++k) any = any || gg.job[k].ksplit > 1;
-            if (any) SF_LAUNCH(reduce_slabs_group_kernel, dim3(red_grid(most), np), dim3(256), 0, st, rg);
-            const int rc = launch_status();
-            if (rc != SF_OK) return rc;
-        }
+        gg.n = g.n;
+        SF_LAUNCH(transpose_group_kernel, dim3(tr.first[tr.n]), dim3(256), 0, st, tr);
+        launch_big_lds<gemm_nt_big_group_kernel>("gemm_nt_big_group_kernel", dim3(gg.first[g.n]), dim3(512),
+                                                 (size_t)2 * 6 * NB_PLANE, st, gg);
+        if (g.reduce)
+            SF_LAUNCH(reduce_slabs_group_kernel, dim3((int)std::min<size_t>((g.most + 255) / 256, 2048), g.n), dim3(256), 0,
+                      st, rg);
+        const int rc = launch_status();
+        if (rc != SF_OK) return rc;
     }
     for (int i = 0; i < n; ++i) {
         bool done = false;
-        for (int k = 0; grouped && k < np; ++k) done = done || pick[k] == i;
+        for (int k = 0; g.grouped && k < g.n; ++k) done = done || g.job[k] == i;
         if (done) continue;
         const TnJob& t = jobs[i];
         const int rc = gemm_tn(t.Y, t.ldy, t.X, t.ldx, t.M, t.P, t.Q, t.out, t.ldo, t.accumulate, st, ws, ws_floats);
@@ -2327,134 +2110,25 @@ int gemm_tn(const float* Y, int ldy, const float* X, int ldx, int M, int P, int 
             int ldo, int accumulate, hipStream_t st, float* ws, size_t ws_floats) {
     SF_CHECK_ARG(M > 0 && P > 0 && Q > 0 && Q % 4 == 0 && ldy % 4 == 0 && ldx % 4 == 0 &&
                  ldo % 4 == 0);
-    // Round 5: a SMALL weight matrix with a deep reduction (the eight [256..512] x [512..2176] weight gradients of the decoder
-    // over 2 000 stacked rows: 25 TFLOP/s in gemm_tn_kernel, 90 us each) as an NT product of the two TRANSPOSED operands on
-    // the LDS-tiled many-row kernel: dW[P,Q] += Y^T[P,M] (X^T[Q,M])^T.  Two 32 x 32-tiled transposes into the workspace
-    // (~6 us each) + gemm_nt_big_kernel (bf16x6, 3x closer to float64 than the fp32 kernels).
-    if (tn_as_many_row(M, P, Q) && ws) {
-        const int tiles = ceil_div(P, NB_T) * ceil_div(Q, NB_T), stages = ceil_div(M, NB_K);
-        int ks = std::max(1, std::min(std::min(16, 256 / tiles), stages / 4));
-        const size_t off_x = ((size_t)P * M + 63) & ~(size_t)63, off_s = off_x + (((size_t)Q * M + 63) & ~(size_t)63);
-        if (ws_floats >= off_s + (ks > 1 ? (size_t)ks * P * Q : 0)) {
-            float* yt = ws;
-            float* xt = ws + off_x;
-            int rc = transpose_ld(Y, ldy, M, P, yt, st);
-            if (rc != SF_OK) return rc;
-            rc = transpose_ld(X, ldx, M, Q, xt, st);
-            if (rc != SF_OK) return rc;
-            NtBigArgs b{};
-            b.seg[0] = Seg{yt, M, xt, M, M};
-            b.nseg = 1; b.M = P; b.N = Q; b.epi = EPI_NONE; b.ksplit = ks;
-            if (ks > 1) {
-                b.y = ws + off_s; b.ldy = Q;
-                rc = nt_big_launch(b, st);
-                if (rc != SF_OK) return rc;
-                RedArgs r{};
-                r.slabs = ws + off_s; r.ks = ks; r.M = P; r.N = Q; r.y = out; r.ldy = ldo; r.epi = EPI_NONE;
-                r.accumulate = accumulate;
-                SF_LAUNCH(reduce_slabs_kernel, dim3(red_grid((size_t)P * Q)), dim3(256), 0, st, r);
-                return launch_status();
-            }
-            b.y = out; b.ldy = ldo; b.accumulate = accumulate;
-            return nt_big_launch(b, st);
-        }
-    }
-    // A small weight matrix with a deep reduction (e.g. [256, 2176] over 2000 stacked rows) is a
-    // handful of waves each walking all M rows: split the rows over grid.z into slabs and add them
-    // up (deterministic order) until the chip is covered.
-    if (P % TNS_B == 0 && Q % TNS_B == 0 && M >= g_tn_split_min_rows && !g_nt_force_f32) {
-        // bf16x6 split products (gemm_tn_split_kernel) where they are faster: deep reductions (see the kernel's note)
-        const int blocks = (P / TNS_B) * (Q / TNS_B);
-        int ms = blocks >= 512 ? 1 : std::min(16, std::max(1, std::min(512 / blocks, M / 256)));
-        if (ms > 1 && (!ws || ws_floats < (size_t)ms * P * Q)) ms = 1;
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_split_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_set = true;
-        }
-        dim3 grid(Q / TNS_B, P / TNS_B, ms);
-        if (ms > 1) {
-            TnArgs a{Y, ldy, X, ldx, M, P, Q, ws, Q, 0, ms};
-            SF_LAUNCH(gemm_tn_split_kernel, grid, dim3(256), TNS_LDS, st, a);
-            RedArgs r{};
-            r.slabs = ws; r.ks = ms; r.M = P; r.N = Q; r.y = out; r.ldy = ldo; r.epi = EPI_NONE;
-            r.accumulate = accumulate;
-            SF_LAUNCH(reduce_slabs_kernel, dim3(red_grid((size_t)P * Q)), dim3(256), 0, st, r);
-            return launch_status();
-        }
-        TnArgs a{Y, ldy, X, ldx, M, P, Q, out, ldo, accumulate, 1};
-        SF_LAUNCH(gemm_tn_split_kernel, grid, dim3(256), TNS_LDS, st, a);
-        return launch_status();
-    }
-    if (P >= 128 && Q >= 128 && ldy >= 128 && M >= 4096) {   // (measured: pays for the deep encoder reductions)
-        // LDS-tiled kernel: 128 x 128 per block; small outputs split the batch rows into slabs
-        const int blocks = ceil_div(Q, TNT_B) * ceil_div(P, TNT_B);
-        int ms = std::min(16, std::max(1, 768 / blocks));
-        ms = std::min(ms, std::max(1, M / 64));
-        if (ms > 1 && (!ws || ws_floats < (size_t)ms * P * Q)) ms = 1;
-        dim3 grid(ceil_div(Q, TNT_B), ceil_div(P, TNT_B), ms);
-        if (ms > 1) {
-            TnArgs a{Y, ldy, X, ldx, M, P, Q, ws, Q, 0, ms};
-            SF_LAUNCH(gemm_tn_tiled_kernel, grid, dim3(256), 0, st, a);
-            RedArgs r{};
-            r.slabs = ws; r.ks = ms; r.M = P; r.N = Q; r.y = out; r.ldy = ldo; r.epi = EPI_NONE;
-            r.accumulate = accumulate;
-            SF_LAUNCH(reduce_slabs_kernel, dim3(red_grid((size_t)P * Q)), dim3(256), 0, st, r);
-            return launch_status();
-        }
-        TnArgs a{Y, ldy, X, ldx, M, P, Q, out, ldo, accumulate, 1};
-        SF_LAUNCH(gemm_tn_tiled_kernel, grid, dim3(256), 0, st, a);
-        return launch_status();
-    }
-    const int waves = ceil_div(Q, 64) * ceil_div(P, 64);
-    {
-        // Wave quantisation: a large output whose 64 x 64 wave tiles are a little more than a whole
-        // number of rounds over the chip's 1024 SIMDs (dW_ih of the decoder LSTM: 2176 tiles = 2.125
-        // per SIMD, so some SIMDs run 3) is cut into the columns that fill whole rounds and a
-        // narrow remainder, which the row split below spreads over the chip on its own.
-        const int q_main = gemm_tn_main_columns(M, P, Q), q_tail = Q - q_main;
-        if (q_tail > 0) {
-            const int tail_ms = std::min(16, std::max(1, 1024 / (ceil_div(q_tail, 64) * ceil_div(P, 64))));
-            if (ws && ws_floats >= (size_t)tail_ms * P * q_tail) {
-                const int rc = gemm_tn(Y, ldy, X, ldx, M, P, q_main, out, ldo, accumulate, st, ws, ws_floats);
-                if (rc != SF_OK) return rc;
-                return gemm_tn(Y, ldy, X + q_main, ldx, M, P, q_tail, out + q_main, ldo, accumulate, st, ws,
-                               ws_floats);
-            }
-        }
-    }
-    int ms = std::min(16, std::max(1, 1024 / waves));
-    ms = std::min(ms, std::max(1, M / 64));
-    if (ms > 1 && (!ws || ws_floats < (size_t)ms * P * Q)) ms = 1;
-    if (ms > 1) {
-        TnArgs a{Y, ldy, X, ldx, M, P, Q, ws, Q, 0, ms};
-        dim3 grid(ceil_div(Q, 256), ceil_div(P, 64), ms);
-        SF_LAUNCH(gemm_tn_kernel, grid, dim3(256), 0, st, a);
-        RedArgs r{};
-        r.slabs = ws; r.ks = ms; r.M = P; r.N = Q; r.y = out; r.ldy = ldo; r.epi = EPI_NONE;
-        r.accumulate = accumulate;
-        SF_LAUNCH(reduce_slabs_kernel, dim3(red_grid((size_t)P * Q)), dim3(256), 0, st, r);
-        return launch_status();
-    }
-    TnArgs a{Y, ldy, X, ldx, M, P, Q, out, ldo, accumulate, 1};
-    dim3 grid(ceil_div(Q, 256), ceil_div(P, 64));
-    SF_LAUNCH(gemm_tn_kernel, grid, dim3(256), 0, st, a);
-    return launch_status();
+    const TnJob t{Y, ldy, X, ldx, M, P, Q, out, ldo, accumulate};
+    const TnPlan p = plan_tn(M, P, Q, ldy, ws ? ws_floats : 0, switches());
+    if (p.family != TN_COLUMN_CUT) return tn_issue(t, p, ws, st);
+    TnJob main = t, tail = t;
+    main.Q = p.q_main;
+    tail.X += p.q_main;
+    tail.out += p.q_main;
+    tail.Q = Q - p.q_main;
+    const int rc = tn_issue(main, p.main, ws, st);
+    return rc != SF_OK ? rc : tn_issue(tail, p.tail, ws, st);
 }
 
 int colsum(const float* Y, int ldy, int M, int N, float* out, int accumulate, hipStream_t st,
            float* out2, float* ws, size_t ws_floats) {
     SF_CHECK_ARG(M > 0 && N > 0);
-    const int nb = ceil_div(N, 64);
-    int ms = std::min(32, std::max(1, 256 / nb));
-    ms = std::min(ms, std::max(1, M / 64));
-    if (ms > 1 && (!ws || ws_floats < (size_t)ms * N)) ms = 1;
-    SF_LAUNCH(colsum_kernel, dim3(nb, ms), dim3(1024), 0, st, Y, ldy, M, N, out, out2,
-                       accumulate, ms, ws);
-    if (ms > 1)
-        SF_LAUNCH(colsum_finish_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, st, ws, ms, N,
-                           out, out2, accumulate);
+    const ColsumPlan p = plan_colsum(M, N, ws ? ws_floats : 0);
+    SF_LAUNCH(colsum_kernel, dim(p.grid), dim3(1024), 0, st, Y, ldy, M, N, out, out2, accumulate, p.ms, ws);
+    if (p.ms > 1)
+        SF_LAUNCH(colsum_finish_kernel, dim(p.finish), dim3(256), 0, st, ws, p.ms, N, out, out2, accumulate);
     return launch_status();
 }
 

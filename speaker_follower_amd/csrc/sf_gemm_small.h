@@ -102,8 +102,6 @@ __device__ __forceinline__ void upfront_mma(const Frags<MT, CPW>& f, int cnt, f3
     }
 }
 
-constexpr int SMALL_WAVES = 8;
-
 struct SmallArgs {
     Seg2 sg;
     int M, N;
@@ -211,6 +209,6 @@ struct SmallPlan {
     int gx, gy;           // grid
 };
 bool linear_small_plan(const Seg* segs, int nseg, int M, int N, const LinearOut& out, SmallPlan* plan);
-int launch_small_plan_x(const SmallPlan& p, hipStream_t st);      // launch a plan on its own
+int launch_small_plan(const SmallPlan& p, hipStream_t st);        // launch a plan on its own
 
 }  // namespace sf

@@ -52,7 +52,7 @@ int score_bwd(const CandSrc& src, int B, const float* dlogit, float* dr, float* 
 // ---- sf_gemm.hip (workspace-aware NN) -------------------------------------------------------------
 int gemm_nn_ws(const float* A, int lda, const float* W, int ldw, int M, int N, int K, float* y,
                int ldy, int accumulate, float* ws, size_t ws_floats, hipStream_t st);
-size_t gemm_nn_ws_floats(int M, int N, int K);
+// (gemm_nn_ws_floats: sf_gemm_plan.h)
 
 // ---- sf_pointwise.hip ---------------------------------------------------------------------------
 // LSTM gates: reduce `ks` split-K slabs [ks][B][4H] + biases (+ hoisted xg), activate, update state.

@@ -15,7 +15,9 @@ in whatever order it adds:
 padding columns and in two rows behind the last one for inputs, a sentinel for outputs.
 
 The case tables name, per shape, the kernel(s) of csrc/sf_gemm.hip the dispatch must launch for it (spelled as
-`_lib.kernel_profile()` reports them).  They are the smallest shapes that reach each branch."""
+`_lib.kernel_profile()` reports them).  They are the smallest shapes that reach each branch.  The names are checked
+twice: on the GPU against the profile of the launches, and on the host by tests/test_gemm_plan_host.py, which asks the
+dispatch's plan functions (csrc/sf_gemm_plan.h, pure host code) for the kernels of every row."""
 import math
 from collections import namedtuple
 
