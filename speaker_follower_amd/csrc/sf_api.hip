@@ -1030,10 +1030,10 @@ static int tail_proj(const TailStep& s, const TextFold& tf) {
     SmallPlan py;
     const bool ok = f.ok &&
         plan_linear(tp->cat2 + H, 2 * H, s.w->text.w_out + H, 2 * H, nullptr, B, H, H, EPI_NONE, f.ybuf, f.ldp, &py) == SF_OK &&
-        py.mt == 1 && py.cpw == 4 && (!s.paired || af.tickets());
+        pair_proj_textfold_accepts(py.inst()) && (!s.paired || af.tickets());
     if (!ok) return SF_ERR_UNSUPPORTED;
     // ---- issue (the first launch checks its shapes before it launches: it may still decline)
-    const bool late = s.paired && (g_proj_partials_late || !proj_partials_supported(s.xn));
+    const bool late = s.paired && (g_proj_partials_late || !proj_partials_supported(s.xn.IMG, s.xn.LOC));
     TRY(pair_proj_textfold(tf.ctx_q, tf.ctx_o, s.ctx_mask, B, s.L, H, tp->cat2 + H, 2 * H, f.tpart, f.tcount, f.zbuf, f.ldp,
                            tp->alpha, py, s.us, s.paired && !late ? &s.xn : nullptr, pt, tp->h1, H, f.part, s.st));
     g_proj_steps.fetch_add(1, std::memory_order_relaxed);
@@ -1064,7 +1064,8 @@ static int tail_fold3(const TailStep& s, const TextFold& tf) {
         Seg sg{f.ybuf, f.ldp, fm->m_a, H, H};
         LinearOut o{};
         o.y = f.rext; o.ldy = F + 4; o.bias = fm->c_a; o.epi = EPI_NONE;
-        ok = linear_small_plan(&sg, 1, B, F + 4, o, &pm) && pm.cpw == 4 && py.mt == 1 && py.cpw == 4 && pq.cpw == 4;
+        ok = linear_small_plan(&sg, 1, B, F + 4, o, &pm) && pair_vis_apro_accepts(pm.inst()) &&
+             pair_textfold_small_small_accepts(py.inst(), pq.inst());
         pm.args.apro_part = f.zbuf;
         pm.args.apro_stride = f.ldp;
     }
@@ -1110,7 +1111,9 @@ static int tail_fold4(const TailStep& s, const TextFold& tf) {
         LinearOut o{};
         o.y = tp->wt; o.ldy = D; o.bias = aw->b_h; o.mul = aw->w_out; o.y_pre = tp->t_a;
         o.ldy_pre = D; o.epi = EPI_MUL;
-        ok = linear_small_plan(&sg, 1, B, D, o, &pta) && pta.mt == 1 && pta.cpw == 4 && pq.cpw == 2 && pr.cpw == 2;
+        // (q' and r are both [B, F] over K = D and share one (mt, cpw); stage (3) accepts the same in phases 0 and 1)
+        ok = linear_small_plan(&sg, 1, B, D, o, &pta) && pair_apro_small_accepts(pta.inst(), pq.inst()) &&
+             pair_vis_small_accepts(pr.inst(), 1);
         pta.args.apro_part = f.zbuf;                            // (the merged attention sum of launch (1))
         pta.args.apro_stride = f.ldp;
     }
@@ -1222,7 +1225,7 @@ static int tail_paired(const TailStep& s) {
         LinearOut o{};
         o.y = tp->wt; o.ldy = D; o.bias = aw->b_h; o.mul = aw->w_out; o.y_pre = tp->t_a;
         o.ldy_pre = D; o.epi = EPI_MUL;
-        ok4 = linear_small_plan(&sg, 1, B, D, o, &pc) && pc.mt == 1 && (pc.cpw == 4 || pc.cpw == 8);
+        ok4 = linear_small_plan(&sg, 1, B, D, o, &pc) && pair_vis_small_accepts(pc.inst(), 2);
     }
     // ---- issue
     TRY(text_and_query(s));

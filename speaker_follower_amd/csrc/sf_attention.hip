@@ -16,7 +16,7 @@ namespace {
 // MODE 1 (backward): d_v = x_v . vec, w_v = alpha_v (d_v - sum_u alpha_u d_u)      (vec = dout)
 //                    out = dq = sum_v w_v x_v
 // =================================================================================================
-constexpr int VIS_CPL = 9, VIS_RPW = 3, VIS_NW = 12, VIS_SLOTS = 6;
+// (VIS_CPL, VIS_RPW, VIS_NW, VIS_SLOTS and every tile constant of this file that a dispatch rule reads: sf_attention_plan.h)
 
 struct VisArgs {
     PanoSrc src;
@@ -179,13 +179,6 @@ __global__ __launch_bounds__(VIS_NW * 64) void visual_attn_kernel(VisArgs a) {
 // monotonic per-sample counter; partials are published write-through and read back with sc1
 // loads, so no cache-wide fence is needed) merges: no spinning, no extra launch.
 // -------------------------------------------------------------------------------------------------
-#ifndef SF_VIS_GROUPS
-#define SF_VIS_GROUPS 2
-#endif
-constexpr int VSP_G = SF_VIS_GROUPS;                   // workgroups per sample (2 or 4)
-constexpr int VSP_NW = VIS_NW / VSP_G, VSP_RPG = VSP_NW * VIS_RPW, VSP_SLOTS = VSP_NW < 3 ? VSP_NW : 3;
-static_assert(VSP_G == 2 || VSP_G == 4, "ticket arithmetic assumes a power of two");
-
 struct VisSplit {
     float* part;          // [B][G][F + 64]: P | scores[32] | m, l
     unsigned* counter;    // [B] monotonic tickets (zero before the first launch)
@@ -209,7 +202,6 @@ __device__ __forceinline__ void vis_stamp(const VisSplit& sp, int block, int slo
 //          (x_v^T M_v) . h1 + x_v . c_v, and the bracket is a row of a table built once per (feature table, weights):
 //          score_v = (PV[row_v][:H] + LV[view * V + v][:H]) . h1 + PV[row_v][H] + LV[..][H].  The query q is never
 //          formed; the rows themselves are still loaded (the weighted sum needs them) and the record is unchanged.
-constexpr int PRJ_CPL = 2;                             // float4 per lane of a projected row: H <= 512
 template <int PHASE, bool F64 = false, bool H16 = false, bool PROJ = false>
 __device__ __forceinline__ void visual_split_body(const VisArgs& a, const VisSplit& sp, int g, int b) {
     __shared__ float4 slots[VSP_SLOTS][VIS_CPL * 64];
@@ -480,12 +472,11 @@ __global__ __launch_bounds__(VSP_NW * 64) void visual_attn_split_f64_kernel(VisA
 // boundary is the hand-off, there is no ticket, so the group count need be no power of two.  No trace stamps
 // (sf_debug_trace buffers are sized for VSP_G blocks per sample).
 // -------------------------------------------------------------------------------------------------
-constexpr int PPB_G = 3, PPB_NW = 6, PPB_RPW = 2, PPB_RPG = PPB_NW * PPB_RPW, PPB_SLOTS = 3;
+constexpr int PPB_NW = 6, PPB_RPW = 2, PPB_RPG = PPB_NW * PPB_RPW, PPB_SLOTS = 3;
 constexpr int PPB_SW = SMALL_WAVES - PPB_NW, PPB_SPW = PPB_RPG / PPB_SW;   // score waves, views scored per score wave
 static_assert(PPB_G * PPB_RPG >= VSP_G * VSP_RPG, "covers every V the split attention takes");
 static_assert(PPB_RPG <= 32, "a group's scores live in 32 record slots");
 static_assert(PPB_SW >= 1 && PPB_SW * PPB_SPW == PPB_RPG, "the score waves share a group's views evenly");
-constexpr int SPLIT_MAX_G = PPB_G > VSP_G ? PPB_G : VSP_G;      // records per sample the scratch is sized for
 
 // Every thread of a SMALL_WAVES * 64 block must call this (it synchronises).
 __device__ __forceinline__ void proj_partials_body(const VisArgs& a, const VisSplit& sp, int g, int b) {
@@ -660,7 +651,6 @@ __device__ __forceinline__ void proj_merge_body(const VisArgs& a, const VisSplit
 // backward: d_l = ctx_l . dwc, ds_l = alpha_l (d_l - sum alpha d), dt = sum ds_l ctx_l,
 //           dctx_l += alpha_l dwc + ds_l t
 // =================================================================================================
-constexpr int TXT_CPL = 2, TXT_NW = 16, TXT_SLOTS = 8;
 
 struct TxtArgs {
     const float* ctx;      // [B, L, H]
@@ -820,7 +810,6 @@ __global__ __launch_bounds__(TXT_NW * 64) void text_attn_kernel(TxtArgs a) {
 // forward : logit[b,a] = u_a . r[b] + (wt[b] . b_a + b_out)
 // backward: dr[b] = sum_a dlogit[b,a] u_a ;  dc[b] = sum_a dlogit[b,a]
 // =================================================================================================
-constexpr int SC_CPL = 9, SC_NW = 16, SC_SLOTS = 4;
 
 struct ScoreArgs {
     CandSrc src;
@@ -1190,7 +1179,6 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_proj_score_kernel(ProjS
 // (m, l, unnormalised z); the last arriver of a sample merges them in the same launch (measured, round 6: two groups
 // merged by the consumer's prologue: stage 10.3 us + consumer 9.4 us; four groups merged here: 10.9 + 7.4).
 // =================================================================================================
-constexpr int TXF_G = 4;          // workgroups per sample; tickets a LAUNCH adds per sample (the tickets count in fours)
 
 struct TxtFoldArgs {
     const float* ctx_q;    // [B, L, H]
@@ -1409,7 +1397,6 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_apro_small_kernel(Small
 // dctx[b,l,:] += sum_t ( alpha[t,b,l] dwc[t,b,:] + ds[t,b,l] tt[t,b,:] ).  The per-step form reads and
 // writes the whole [B,L,H] gradient S times (2 x 16 MB per step at the headline shape); this reads each
 // step's two H-vectors once.  One block per sample; thread = one float4 column x every 8th row.
-constexpr int CG_ROWS = 10;        // rows per thread: L <= 8 * CG_ROWS
 
 __global__ __launch_bounds__(1024) void ctx_grad_kernel(const float* alpha, const float* ds,
                                                         const float* dcat2, int lddc, const float* tt,
@@ -1471,14 +1458,19 @@ __global__ __launch_bounds__(VIS_NW * 64) void pair_visbwd_small_kernel(VisArgs 
 
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------
+// LAUNCHERS.  Each one gates on the named rules of sf_attention_plan.h (pure host code, tests/test_attention_plan_host.py)
+// -- their ORDER decides between SF_ERR_UNSUPPORTED and SF_ERR_ARG --, fills the kernels' argument structs, turns a
+// ladder's value into a template argument with with_index, and launches.
 // Storage dispatch.  EVERY launcher below that takes a PanoSrc / CandSrc launches through one of these two macros (or
 // returns before launching), so a table registered as binary16 can only reach an instantiation that reads 8-byte chunks:
-// an fp32 read of it would run off the end of the table.  A half source in dense form is a caller's error.  The fp32
-// branch keeps the launch text -- and with it the name the in-process profile reports -- it always had.
-#define SF_LAUNCH_H16(half, k32, k16, ...)         \
-    do {                                           \
-        if (half) SF_LAUNCH(k16, __VA_ARGS__);     \
-        else SF_LAUNCH(k32, __VA_ARGS__);          \
+// an fp32 read of it would run off the end of the table.  A half source in dense form is a caller's error.  The
+// binary16 instantiation is K<..., true>, or K<true> under the name "<f16>".
+// ------------------------------------------------------------------------------------------------
+#define SF_LAUNCH_INST_H16(half, K, targs, ...)                             \
+    do {                                                                    \
+        if (half) SF_LAUNCH_INST(K, (SF_TARGS targs, true), __VA_ARGS__);   \
+        else SF_LAUNCH_INST(K, targs, __VA_ARGS__);                         \
     } while (0)
 #define SF_LAUNCH_H16_AS(half, name, K, ...)                         \
     do {                                                             \
@@ -1487,65 +1479,49 @@ __global__ __launch_bounds__(VIS_NW * 64) void pair_visbwd_small_kernel(VisArgs 
     } while (0)
 template <typename Src>
 static inline bool half_misuse(const Src& s) { return s.half && s.dense; }
+static inline RowShape shape(const PanoSrc& s) { return RowShape{s.V, s.IMG, s.LOC, s.dense != nullptr, s.half != 0}; }
+static inline RowShape shape(const CandSrc& s) { return RowShape{s.A, s.IMG, s.LOC, s.dense != nullptr, s.half != 0}; }
+// known: with_index found the instantiation (the gate before it accepts nothing else)
+static inline int launched(bool known) { return known ? launch_status() : SF_ERR_UNSUPPORTED; }
 
-// (sized for the body with the most records per sample: proj_partials_body and proj_merge_body index the same scratch
-//  with PPB_G records, every visual_split_body with VSP_G)
-size_t visual_attn_split_floats(int B, int F) { return (size_t)B * SPLIT_MAX_G * (F + 64); }
-
-bool visual_attn_f64_supported(const PanoSrc& src, int B) {
-    const int F = src.IMG + src.LOC;
-    return !(src.V > VIS_RPW * VIS_NW || src.V > 64 || F > VIS_CPL * 256 || (F & 3) ||
-             (!src.dense && ((src.IMG & 3) || (src.LOC & 3)))) &&
-           src.V > (VSP_G - 1) * VSP_RPG && src.V <= VSP_G * VSP_RPG && B <= VIS_SPLIT_MAX_B;
-}
+bool visual_attn_f64_supported(const PanoSrc& src, int B) { return split_rows_fit(shape(src), B); }
 
 int visual_attn(int mode, const PanoSrc& src, int B, const float* vec, int ldvec, float* alpha,
                 float* out, int ldo, const Dropout& drop, int drop_col0, hipStream_t st,
                 float* split_part, unsigned* split_counter, const double* vec64, int vec_slabs, long vec_slab_stride) {
-    const int F = src.IMG + src.LOC;
-    if (src.V > VIS_RPW * VIS_NW || src.V > 64 || F > VIS_CPL * 256 || (F & 3) ||
-        (!src.dense && ((src.IMG & 3) || (src.LOC & 3))) || (ldvec & 3) || (ldo & 3))
-        return SF_ERR_UNSUPPORTED;
+    if (!pano_rows_fit(shape(src)) || !aligned4(ldvec, ldo)) return SF_ERR_UNSUPPORTED;
     if (half_misuse(src)) return SF_ERR_ARG;
     VisArgs a{src, vec, ldvec, alpha, out, ldo, drop, drop_col0, vec64, mode == 1 ? vec_slabs : 0, vec_slab_stride};
     if (mode != 1 && vec_slabs > 1) return SF_ERR_UNSUPPORTED;
-    if (vec64) {        // float64 scores: the two-workgroup forward only (callers check visual_attn_f64_supported)
-        if (mode != 0 || !split_part || !split_counter || !visual_attn_f64_supported(src, B)) return SF_ERR_UNSUPPORTED;
+    // small batches: VSP_G workgroups per sample (see visual_attn_split_kernel)
+    const bool split = mode == 0 && split_part && split_counter && in_split_range(src.V, B);
+    if (vec64 && !split) return SF_ERR_UNSUPPORTED;   // float64 scores: the split forward only (visual_attn_f64_supported)
+    if (vec64)
         SF_LAUNCH_H16_AS(src.half, "visual_attn_split_f64_kernel", visual_attn_split_f64_kernel, dim3(VSP_G, B),
                          dim3(VSP_NW * 64), 0, st, a, VisSplit{split_part, split_counter, nullptr});
-        return launch_status();
-    }
-    // small batches: two workgroups per sample (see visual_attn_split_kernel)
-    if (mode == 0 && split_part && split_counter && src.V > (VSP_G - 1) * VSP_RPG &&
-        src.V <= VSP_G * VSP_RPG && B <= VIS_SPLIT_MAX_B) {
+    else if (split)
         SF_LAUNCH_H16_AS(src.half, "visual_attn_split_kernel", visual_attn_split_kernel, dim3(VSP_G, B),
                          dim3(VSP_NW * 64), 0, st, a, VisSplit{split_part, split_counter, nullptr});
-        return launch_status();
-    }
-    if (mode == 0)
-        SF_LAUNCH_H16(src.half, visual_attn_kernel<0>, (visual_attn_kernel<0, true>), dim3(B), dim3(VIS_NW * 64), 0, st, a);
+    else if (mode == 0)
+        SF_LAUNCH_INST_H16(src.half, visual_attn_kernel, (0), dim3(B), dim3(VIS_NW * 64), 0, st, a);
     else
-        SF_LAUNCH_H16(src.half, visual_attn_kernel<1>, (visual_attn_kernel<1, true>), dim3(B), dim3(VIS_NW * 64), 0, st, a);
+        SF_LAUNCH_INST_H16(src.half, visual_attn_kernel, (1), dim3(B), dim3(VIS_NW * 64), 0, st, a);
     return launch_status();
 }
 
 template <int MODE>
 static int text_attn_launch(const TxtArgs& a, int B, hipStream_t st) {
-    if (a.L <= TXT_NW)
-        SF_LAUNCH((text_attn_kernel<1, MODE>), dim3(B), dim3(TXT_NW * 64), 0, st, a);
-    else if (a.L <= TXT_NW * 5)
-        SF_LAUNCH((text_attn_kernel<5, MODE>), dim3(B), dim3(TXT_NW * 64), 0, st, a);
-    else if (a.L <= TXT_NW * 8)
-        SF_LAUNCH((text_attn_kernel<8, MODE>), dim3(B), dim3(TXT_NW * 64), 0, st, a);
-    else
-        return SF_ERR_UNSUPPORTED;
-    return launch_status();
+    return launched(with_index(text_rpw(a.L), [&](auto r) {
+        constexpr int R = decltype(r)::value;                   // (the profile has always said "MODE" for the second one)
+        SF_LAUNCH_AS((inst_name<text_attn_kernel<R, MODE>, R>("text_attn_kernel", ", MODE")), (text_attn_kernel<R, MODE>),
+                     dim3(B), dim3(TXT_NW * 64), 0, st, a);
+    }, ints<1, 5, 8>{}));
 }
 
 int text_attn_fwd(const float* ctx, const uint8_t* mask, int B, int L, int H, const float* t,
                   int ldt, float* alpha, float* wc, int ldwc, hipStream_t st,
                   const int32_t* ctx_row) {
-    if (H > TXT_CPL * 256 || (H & 3) || (ldt & 3) || (ldwc & 3) || L < 1) return SF_ERR_UNSUPPORTED;
+    if (!text_rows_fit(L, TXT_MAX_L, H, ldt | ldwc)) return SF_ERR_UNSUPPORTED;
     TxtArgs a{ctx, mask, L, H, t, ldt, nullptr, 0, alpha, wc, ldwc, nullptr, ctx_row, nullptr};
     return text_attn_launch<0>(a, B, st);
 }
@@ -1553,21 +1529,14 @@ int text_attn_fwd(const float* ctx, const uint8_t* mask, int B, int L, int H, co
 int text_attn_bwd(const float* ctx, int B, int L, int H, const float* dwc, int lddwc,
                   const float* t, int ldt, const float* alpha, float* dt, int lddt, float* dctx,
                   hipStream_t st, float* ds_out, const int32_t* ctx_row) {
-    if (H > TXT_CPL * 256 || (H & 3) || (ldt & 3) || (lddwc & 3) || (lddt & 3) || L < 1 || (ctx_row && dctx))
-        return SF_ERR_UNSUPPORTED;
+    if (!text_rows_fit(L, TXT_MAX_L, H, ldt | lddwc | lddt) || (ctx_row && dctx)) return SF_ERR_UNSUPPORTED;
     TxtArgs a{ctx, nullptr, L, H, dwc, lddwc, t, ldt, const_cast<float*>(alpha), dt, lddt, dctx, ctx_row, ds_out};
     return text_attn_launch<1>(a, B, st);
 }
 
-bool ctx_grad_supported(int S, int L, int H) {
-    const int n4 = H >> 2;
-    return !(H & 3) && n4 >= 1 && n4 <= 1024 && 1024 % n4 == 0 && L <= (1024 / n4) * CG_ROWS &&
-           (size_t)S * 2 * L * sizeof(float) <= 64 * 1024;
-}
-
 int ctx_grad_accum(const float* alpha, const float* ds, const float* dcat2, int lddc, const float* tt,
                    int S, int B, int L, int H, float* dctx, hipStream_t st) {
-    if (!ctx_grad_supported(S, L, H) || (lddc & 3)) return SF_ERR_UNSUPPORTED;
+    if (!ctx_grad_supported(S, L, H) || !aligned4(lddc)) return SF_ERR_UNSUPPORTED;
     SF_LAUNCH(ctx_grad_kernel, dim3(B), dim3(1024), (size_t)S * 2 * L * sizeof(float), st, alpha,
                        ds, dcat2, lddc, tt, S, B, L, H, dctx);
     return launch_status();
@@ -1575,11 +1544,8 @@ int ctx_grad_accum(const float* alpha, const float* ds, const float* dcat2, int 
 
 int score_fwd(const CandSrc& src, int B, int D, const float* r, const float* wt, const float* b_a,
               const float* b_out, float* logit, hipStream_t st, int ldr, const float* cst) {
-    const int F = src.IMG + src.LOC;
-    if (ldr <= 0) ldr = F;
-    if (src.A > SC_NW || src.A < 1 || F > SC_CPL * 256 || (F & 3) ||
-        (!src.dense && ((src.IMG & 3) || (src.LOC & 15))))
-        return SF_ERR_UNSUPPORTED;
+    if (ldr <= 0) ldr = src.IMG + src.LOC;
+    if (!cand_rows_fit(shape(src))) return SF_ERR_UNSUPPORTED;
     if (half_misuse(src)) return SF_ERR_ARG;
     ScoreArgs a{src, ldr, cst, r, wt, b_a, b_out, D, logit, nullptr, nullptr, CeSrc{}};
     SF_LAUNCH_H16_AS(src.half, "score_fwd_kernel", score_fwd_kernel, dim3(B), dim3(SC_NW * 64), 0, st, a);
@@ -1589,11 +1555,8 @@ int score_fwd(const CandSrc& src, int B, int D, const float* r, const float* wt,
 int score_glue_fwd(const CandSrc& src, int B, int D, const float* r, const float* wt,
                    const float* b_a, const float* b_out, const FGlue& g, hipStream_t st, int ldr,
                    const float* cst) {
-    const int F = src.IMG + src.LOC;
-    if (ldr <= 0) ldr = F;
-    if (src.A > SC_NW || src.A < 1 || F > SC_CPL * 256 || (F & 3) ||
-        (!src.dense && ((src.IMG & 3) || (src.LOC & 15))))
-        return SF_ERR_UNSUPPORTED;
+    if (ldr <= 0) ldr = src.IMG + src.LOC;
+    if (!cand_rows_fit(shape(src))) return SF_ERR_UNSUPPORTED;
     if (half_misuse(src)) return SF_ERR_ARG;
     ScoreArgs a{src, ldr, cst, r, wt, b_a, b_out, D, g.logit, nullptr, nullptr, CeSrc{}};
     SF_LAUNCH_H16_AS(src.half, "score_glue_kernel", score_glue_kernel, dim3(B), dim3(SC_NW * 64), 0, st, a, g);
@@ -1604,12 +1567,9 @@ int score_glue_fwd(const CandSrc& src, int B, int D, const float* r, const float
 int pair_score_merge(const CandSrc& src, int B, int D, const float* r, const float* wt, const float* b_a,
                      const float* b_out, const FGlue& g, const PanoSrc& psrc, float* alpha, float* out, int ldo,
                      const Dropout& drop, int drop_col0, float* split_part, hipStream_t st, int ldr, const float* cst) {
-    const int F = src.IMG + src.LOC;
-    if (ldr <= 0) ldr = F;
-    if (src.A > SC_NW || src.A < 1 || F > SC_CPL * 256 || (F & 3) || (!src.dense && ((src.IMG & 3) || (src.LOC & 15))))
-        return SF_ERR_UNSUPPORTED;
-    if (!split_part || psrc.V <= (VSP_G - 1) * VSP_RPG || psrc.V > VSP_G * VSP_RPG || B > VIS_SPLIT_MAX_B || (ldo & 3))
-        return SF_ERR_UNSUPPORTED;
+    if (ldr <= 0) ldr = src.IMG + src.LOC;
+    if (!cand_rows_fit(shape(src))) return SF_ERR_UNSUPPORTED;
+    if (!split_part || !in_split_range(psrc.V, B) || !aligned4(ldo)) return SF_ERR_UNSUPPORTED;
     if (half_misuse(src) || half_misuse(psrc)) return SF_ERR_ARG;
     ScoreArgs a{src, ldr, cst, r, wt, b_a, b_out, D, g.logit, nullptr, nullptr, CeSrc{}};
     VisArgs va{psrc, nullptr, 0, alpha, out, ldo, drop, drop_col0};
@@ -1621,11 +1581,8 @@ int pair_score_merge(const CandSrc& src, int B, int D, const float* r, const flo
 
 int score_bwd(const CandSrc& src, int B, const float* dlogit, float* dr, float* dc,
               hipStream_t st, const CeSrc* ce) {
-    const int F = src.IMG + src.LOC;
-    if (src.A > SC_NW || src.A < 1 || F > SC_CPL * 256 || (F & 3) ||
-        (!src.dense && ((src.IMG & 3) || (src.LOC & 15))))
-        return SF_ERR_UNSUPPORTED;
-    ScoreArgs a{src, F, nullptr, nullptr, nullptr, nullptr, nullptr, 0, const_cast<float*>(dlogit), dr, dc,
+    if (!cand_rows_fit(shape(src))) return SF_ERR_UNSUPPORTED;
+    ScoreArgs a{src, src.IMG + src.LOC, nullptr, nullptr, nullptr, nullptr, nullptr, 0, const_cast<float*>(dlogit), dr, dc,
                 ce ? *ce : CeSrc{}};
     if ((ce && ce->ld < src.A) || half_misuse(src)) return SF_ERR_ARG;
     SF_LAUNCH_H16_AS(src.half, "score_bwd_kernel", score_bwd_kernel, dim3(B), dim3(SC_NW * 64), 0, st, a);
@@ -1633,71 +1590,48 @@ int score_bwd(const CandSrc& src, int B, const float* dlogit, float* dr, float* 
 }
 
 // ---- paired launches (host side).  SF_ERR_UNSUPPORTED = "not pairable": the caller launches the
-// two kernels one after the other instead.
+// two kernels one after the other instead.  What each accepts of a small product: pair_*_accepts, which the chains of
+// sf_api.hip ask as well.
 int pair_small_small(const SmallPlan& a, const SmallPlan& b, hipStream_t st) {
-    if (!(a.mt == 1 && a.cpw == 4 && b.cpw == 4 && (b.mt == 1 || b.mt == 2 || b.mt == 4))) return SF_ERR_UNSUPPORTED;
+    if (!pair_small_small_accepts(a.inst(), b.inst())) return SF_ERR_UNSUPPORTED;
     const int na = a.gx * a.gy, nb = b.gx * b.gy;
     const dim3 grid(na + nb), block(SMALL_WAVES * 64);
-    if (b.mt == 1)
-        SF_LAUNCH((pair_small_small_kernel<1, 4, 1, 4>), grid, block, 0, st, a.args, a.gx, na, b.args, b.gx);
-    else if (b.mt == 2)
-        SF_LAUNCH((pair_small_small_kernel<1, 4, 2, 4>), grid, block, 0, st, a.args, a.gx, na, b.args, b.gx);
-    else
-        SF_LAUNCH((pair_small_small_kernel<1, 4, 4, 4>), grid, block, 0, st, a.args, a.gx, na, b.args, b.gx);
-    return launch_status();
+    return launched(with_index(b.mt, [&](auto m) {
+        SF_LAUNCH_INST(pair_small_small_kernel, (1, 4, decltype(m)::value, 4), grid, block, 0, st, a.args, a.gx, na, b.args, b.gx);
+    }, ints<1, 2, 4>{}));
 }
-
 
 // The folded text stage of an inference decode step (see text_fold_body): SF_ERR_UNSUPPORTED = shapes outside the
 // instantiations (the caller runs the unfolded stages).
 int pair_textfold_small_small(const float* ctx_q, const float* ctx_o, const uint8_t* mask, int B, int L, int H,
                               const float* vec, int ldvec, float* part, unsigned* counter, float* z, int ldz, float* alpha,
                               const SmallPlan& a, const SmallPlan& b, hipStream_t st) {
-    if (!(a.mt == 1 && a.cpw == 4 && b.cpw == 4 && (b.mt == 1 || b.mt == 2 || b.mt == 4))) return SF_ERR_UNSUPPORTED;
-    if (H > TXT_CPL * 256 || (H & 3) || (ldvec & 3) || L < 1 || L > TXF_G * SMALL_WAVES * 5 || B > 512 || !counter || !z ||
-        (ldz & 3) || ldz < H)
-        return SF_ERR_UNSUPPORTED;
+    if (!pair_textfold_small_small_accepts(a.inst(), b.inst())) return SF_ERR_UNSUPPORTED;
+    if (!text_fold_fits(B, L, H, ldvec, ldz) || !counter || !z) return SF_ERR_UNSUPPORTED;
     const TxtFoldArgs ta{ctx_q, ctx_o, mask, L, H, vec, ldvec, part, counter, z, ldz, alpha};
     const int nt = TXF_G * B, na = a.gx * a.gy, nb = b.gx * b.gy;
     const dim3 grid(nt + na + nb), block(SMALL_WAVES * 64);
-    const int rpw = (L + TXF_G * SMALL_WAVES - 1) / (TXF_G * SMALL_WAVES);
-    if (b.mt > 1) {                                   // (the folded visual query: N = F columns)
-#define SF_TFW(R, M) SF_LAUNCH((pair_textfold_small_wide_kernel<R, M>), grid, block, 0, st, ta, nt, a.args, a.gx, na, b.args, b.gx)
-        if (b.mt == 2) {
-            if (rpw <= 1) SF_TFW(1, 2); else if (rpw <= 2) SF_TFW(2, 2); else if (rpw <= 3) SF_TFW(3, 2); else SF_TFW(5, 2);
-        } else {
-            if (rpw <= 1) SF_TFW(1, 4); else if (rpw <= 2) SF_TFW(2, 4); else if (rpw <= 3) SF_TFW(3, 4); else SF_TFW(5, 4);
-        }
-#undef SF_TFW
-        return launch_status();
-    }
-    if (rpw <= 1)
-        SF_LAUNCH((pair_textfold_small_small_kernel<1>), grid, block, 0, st, ta, nt, a.args, a.gx, na, b.args, b.gx);
-    else if (rpw <= 2)
-        SF_LAUNCH((pair_textfold_small_small_kernel<2>), grid, block, 0, st, ta, nt, a.args, a.gx, na, b.args, b.gx);
-    else if (rpw <= 3)
-        SF_LAUNCH((pair_textfold_small_small_kernel<3>), grid, block, 0, st, ta, nt, a.args, a.gx, na, b.args, b.gx);
-    else
-        SF_LAUNCH((pair_textfold_small_small_kernel<5>), grid, block, 0, st, ta, nt, a.args, a.gx, na, b.args, b.gx);
-    return launch_status();
+    return launched(with_index(fold_rpw(L, TXF_G), [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        if (b.mt == 1)
+            SF_LAUNCH_INST(pair_textfold_small_small_kernel, (R), grid, block, 0, st, ta, nt, a.args, a.gx, na, b.args, b.gx);
+        else                                          // (the folded visual query: N = F columns)
+            with_index(b.mt, [&](auto m) {
+                SF_LAUNCH_INST(pair_textfold_small_wide_kernel, (R, decltype(m)::value), grid, block, 0, st, ta, nt, a.args, a.gx,
+                               na, b.args, b.gx);
+            }, ints<2, 4>{});
+    }, ints<1, 2, 3, 5>{}));
 }
-size_t text_fold_part_floats(int B, int H) { return (size_t)B * TXF_G * (H + 64); }
-
 
 // a: the product whose A operand the prologue forms (a.args.apro_part set by the caller), b: a plain small product
 int pair_apro_small(const SmallPlan& a, const SmallPlan& b, hipStream_t st) {
-    if (!(a.mt == 1 && a.cpw == 4 && b.cpw == 2 && (b.mt == 1 || b.mt == 2 || b.mt == 4)) || !a.args.apro_part ||
-        a.args.sg.total != a.args.sg.n0)
+    if (!pair_apro_small_accepts(a.inst(), b.inst()) || !a.args.apro_part || a.args.sg.total != a.args.sg.n0)
         return SF_ERR_UNSUPPORTED;
     const int na = a.gx * a.gy, nb = b.gx * b.gy;
     const dim3 grid(na + nb), block(SMALL_WAVES * 64);
-    if (b.mt == 4)
-        SF_LAUNCH((pair_apro_small_kernel<4>), grid, block, 0, st, a.args, a.gx, na, b.args, b.gx);
-    else if (b.mt == 2)
-        SF_LAUNCH((pair_apro_small_kernel<2>), grid, block, 0, st, a.args, a.gx, na, b.args, b.gx);
-    else
-        SF_LAUNCH((pair_apro_small_kernel<1>), grid, block, 0, st, a.args, a.gx, na, b.args, b.gx);
-    return launch_status();
+    return launched(with_index(b.mt, [&](auto m) {
+        SF_LAUNCH_INST(pair_apro_small_kernel, (decltype(m)::value), grid, block, 0, st, a.args, a.gx, na, b.args, b.gx);
+    }, ints<1, 2, 4>{}));
 }
 
 // visual-attention partials (phase 1 of the split attention) beside the text attention
@@ -1705,45 +1639,30 @@ int pair_vis_text(const PanoSrc& src, int B, const float* vec, int ldvec, float*
                   const Dropout& drop, int drop_col0, float* split_part, const float* ctx, const uint8_t* mask,
                   int L, int H, const float* t, int ldt, float* talpha, float* wc, int ldwc,
                   const int32_t* ctx_row, hipStream_t st) {
-    const int F = src.IMG + src.LOC;
-    if (!split_part || src.V <= (VSP_G - 1) * VSP_RPG || src.V > VSP_G * VSP_RPG || B > VIS_SPLIT_MAX_B || F > VIS_CPL * 256 ||
-        (F & 3) || (!src.dense && ((src.IMG & 3) || (src.LOC & 3))) || (ldvec & 3) || (ldo & 3))
-        return SF_ERR_UNSUPPORTED;
-    if (H > TXT_CPL * 256 || (H & 3) || (ldt & 3) || (ldwc & 3) || L < 1 || L > SMALL_WAVES * 10)
-        return SF_ERR_UNSUPPORTED;
+    if (!split_part || !split_rows_fit(shape(src), B) || !aligned4(ldvec, ldo)) return SF_ERR_UNSUPPORTED;
+    if (!text_rows_fit(L, PVT_MAX_L, H, ldt | ldwc)) return SF_ERR_UNSUPPORTED;
     if (half_misuse(src)) return SF_ERR_ARG;
     VisArgs va{src, vec, ldvec, alpha, out, ldo, drop, drop_col0};
     const VisSplit sp{split_part, nullptr, g_trace};
     TxtArgs ta{ctx, mask, L, H, t, ldt, nullptr, 0, talpha, wc, ldwc, nullptr, ctx_row, nullptr};
     const int nv = VSP_G * B;
     const dim3 grid(nv + B), block(SMALL_WAVES * 64);
-#define SF_PVT(R) SF_LAUNCH_H16(src.half, (pair_vis_text_kernel<R>), (pair_vis_text_kernel<R, true>), grid, block, 0, st, va, sp, nv, ta)
-    if (L <= SMALL_WAVES * 2)
-        SF_PVT(2);
-    else if (L <= SMALL_WAVES * 5)
-        SF_PVT(5);
-    else
-        SF_PVT(10);
-#undef SF_PVT
-    return launch_status();
+    return launched(with_index(vis_text_rpw(L), [&](auto r) {
+        SF_LAUNCH_INST_H16(src.half, pair_vis_text_kernel, (decltype(r)::value), grid, block, 0, st, va, sp, nv, ta);
+    }, ints<2, 5, 10>{}));
 }
 
 int pair_small_text(const SmallPlan& a, const float* ctx, const uint8_t* mask, int B, int L, int H,
                     const float* t, int ldt, float* alpha, float* wc, int ldwc,
                     const int32_t* ctx_row, hipStream_t st) {
-    if (!(a.mt == 4 && a.cpw == 2)) return SF_ERR_UNSUPPORTED;
-    if (H > TXT_CPL * 256 || (H & 3) || (ldt & 3) || (ldwc & 3) || L < 1 || L > TXT_NW * 8)
-        return SF_ERR_UNSUPPORTED;
+    if (!pair_small_text_accepts(a.inst())) return SF_ERR_UNSUPPORTED;
+    if (!text_rows_fit(L, TXT_MAX_L, H, ldt | ldwc)) return SF_ERR_UNSUPPORTED;
     TxtArgs ta{ctx, mask, L, H, t, ldt, nullptr, 0, alpha, wc, ldwc, nullptr, ctx_row, nullptr};
     const int na = a.gx * a.gy;
     const dim3 grid(na + B), block(TXT_NW * 64);
-    if (L <= TXT_NW)
-        SF_LAUNCH((pair_small_text_kernel<4, 2, 1>), grid, block, 0, st, a.args, a.gx, na, ta);
-    else if (L <= TXT_NW * 5)
-        SF_LAUNCH((pair_small_text_kernel<4, 2, 5>), grid, block, 0, st, a.args, a.gx, na, ta);
-    else
-        SF_LAUNCH((pair_small_text_kernel<4, 2, 8>), grid, block, 0, st, a.args, a.gx, na, ta);
-    return launch_status();
+    return launched(with_index(text_rpw(L), [&](auto r) {
+        SF_LAUNCH_INST(pair_small_text_kernel, (4, 2, decltype(r)::value), grid, block, 0, st, a.args, a.gx, na, ta);
+    }, ints<1, 5, 8>{}));
 }
 
 // visual-attention backward (mode 1 of visual_attn) paired with a small product (mt 1, cpw 16: the
@@ -1751,16 +1670,12 @@ int pair_small_text(const SmallPlan& a, const float* ctx, const uint8_t* mask, i
 int pair_visbwd_small(const PanoSrc& src, int B, const float* vec, int ldvec, float* alpha, float* out,
                       int ldo, const Dropout& drop, int drop_col0, const SmallPlan& b, hipStream_t st, int vec_slabs,
                       long vec_slab_stride) {
-    const int F = src.IMG + src.LOC;
-    if (!(b.mt == 1 && b.cpw == 16)) return SF_ERR_UNSUPPORTED;
-    if (src.V > VIS_RPW * VIS_NW || src.V > 64 || F > VIS_CPL * 256 || (F & 3) ||
-        (!src.dense && ((src.IMG & 3) || (src.LOC & 3))) || (ldvec & 3) || (ldo & 3))
-        return SF_ERR_UNSUPPORTED;
+    if (!pair_visbwd_small_accepts(b.inst())) return SF_ERR_UNSUPPORTED;
+    if (!pano_rows_fit(shape(src)) || !aligned4(ldvec, ldo)) return SF_ERR_UNSUPPORTED;
     if (half_misuse(src)) return SF_ERR_ARG;
     VisArgs va{src, vec, ldvec, alpha, out, ldo, drop, drop_col0, nullptr, vec_slabs, vec_slab_stride};
     const int nb = b.gx * b.gy;
-    SF_LAUNCH_H16(src.half, (pair_visbwd_small_kernel<1, 16>), (pair_visbwd_small_kernel<1, 16, true>), dim3(B + nb),
-                  dim3(VIS_NW * 64), 0, st, va, B, b.args, b.gx);
+    SF_LAUNCH_INST_H16(src.half, pair_visbwd_small_kernel, (1, 16), dim3(B + nb), dim3(VIS_NW * 64), 0, st, va, B, b.args, b.gx);
     return launch_status();
 }
 
@@ -1768,15 +1683,11 @@ int pair_visbwd_small(const PanoSrc& src, int B, const float* vec, int ldvec, fl
 // partials of the visual attention -- or alone (`src` null: a device-resident environment, an episode's last step)
 int pair_vis_apro(const PanoSrc* src, int B, const float* vec, int ldvec, float* split_part, const SmallPlan& b,
                   hipStream_t st) {
-    if (!(b.cpw == 4 && (b.mt == 1 || b.mt == 2 || b.mt == 4)) || !b.args.apro_part || b.args.sg.total != b.args.sg.n0)
-        return SF_ERR_UNSUPPORTED;
+    if (!pair_vis_apro_accepts(b.inst()) || !b.args.apro_part || b.args.sg.total != b.args.sg.n0) return SF_ERR_UNSUPPORTED;
     int nv = 0;
     VisArgs va{};
     if (src) {
-        const int F = src->IMG + src->LOC;
-        if (!split_part || src->V <= (VSP_G - 1) * VSP_RPG || src->V > VSP_G * VSP_RPG || B > VIS_SPLIT_MAX_B || F > VIS_CPL * 256 ||
-            (F & 3) || (!src->dense && ((src->IMG & 3) || (src->LOC & 3))) || (ldvec & 3))
-            return SF_ERR_UNSUPPORTED;
+        if (!split_part || !split_rows_fit(shape(*src), B) || !aligned4(ldvec)) return SF_ERR_UNSUPPORTED;
         if (half_misuse(*src)) return SF_ERR_ARG;
         va = VisArgs{*src, vec, ldvec, nullptr, nullptr, 0, Dropout{}, 0};
         nv = VSP_G * B;
@@ -1785,35 +1696,19 @@ int pair_vis_apro(const PanoSrc* src, int B, const float* vec, int ldvec, float*
     const int nb = b.gx * b.gy;
     const dim3 grid(nv + nb), block(SMALL_WAVES * 64);
     const int h16 = src ? src->half : 0;
-#define SF_PVA(M) SF_LAUNCH_H16(h16, (pair_vis_small_kernel<M, 4, 1, true>), (pair_vis_small_kernel<M, 4, 1, true, true>), grid, block, 0, st, va, sp, nv, b.args, b.gx)
-    if (b.mt == 4)
-        SF_PVA(4);
-    else if (b.mt == 2)
-        SF_PVA(2);
-    else
-        SF_PVA(1);
-#undef SF_PVA
-    return launch_status();
+    return launched(with_index(b.mt, [&](auto m) {
+        SF_LAUNCH_INST_H16(h16, pair_vis_small_kernel, (decltype(m)::value, 4, 1, true), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+    }, ints<1, 2, 4>{}));
 }
 
 // ---- the projected decode chain (sf_api.hip: tail_proj).  proj_chain_supported is the PLAN: both launchers below check
 // it again and return SF_ERR_UNSUPPORTED before launching, but tail_proj asks first so that it declines as a whole.
+// Here: what the rule of sf_attention_plan.h cannot see -- the tables are there, candidates and panorama share one.
 bool proj_chain_supported(const CandSrc& us, const PanoSrc* xn, int B, int H, int L, const ProjTables& pt) {
-    const int F = us.IMG + us.LOC;
-    if (!pt.pv || !pt.pa || !pt.lv || !pt.la || pt.H != H || (pt.ld & 3) || pt.ld < H + 1) return false;
-    if (H > PRJ_CPL * 256 || (H & 3) || H < 4 || L < 1 || L > TXF_G * SMALL_WAVES * 5 || B < 1 || B > VIS_SPLIT_MAX_B) return false;
-    if (us.dense || us.half || !us.table || !us.a_num || us.A > 2 * SMALL_WAVES || us.A < 1 || F > SC_CPL * 256 ||
-        (us.IMG & 3) || (us.LOC & 15))
-        return false;
-    if (xn && (xn->dense || xn->half || xn->table != us.table || xn->V != us.V || xn->IMG != us.IMG || xn->LOC != us.LOC ||
-               xn->V <= (VSP_G - 1) * VSP_RPG || xn->V > VSP_G * VSP_RPG || F > VIS_CPL * 256))
-        return false;
-    return true;
-}
-
-// proj_partials_body types a lane's VIS_CPL row slots as image or location chunks: both parts must fit side by side
-bool proj_partials_supported(const PanoSrc& xn) {
-    return xn.IMG >= 4 && ((xn.IMG >> 2) + 63) / 64 + ((xn.LOC >> 2) + 63) / 64 <= VIS_CPL;
+    if (!pt.pv || !pt.pa || !pt.lv || !pt.la || !us.table || !us.a_num) return false;
+    if (xn && (xn->table != us.table || xn->V != us.V)) return false;
+    const RowShape x = xn ? shape(*xn) : RowShape{};
+    return proj_chain_supported(shape(us), xn ? &x : nullptr, B, H, L, pt.H, pt.ld);
 }
 
 static VisArgs proj_vis_args(const PanoSrc& xn, const ProjTables& pt, const float* h1, int ldh1, float* alpha, float* out,
@@ -1827,38 +1722,18 @@ static VisArgs proj_vis_args(const PanoSrc& xn, const ProjTables& pt, const floa
 int visual_attn_proj(const CandSrc& us, const PanoSrc& x, int B, int H, int L, const ProjTables& pt, const float* h, int ldh,
                      float* alpha, float* out, int ldo, const Dropout& drop, int drop_col0, float* split_part,
                      unsigned* counter, hipStream_t st) {
-    if (!proj_chain_supported(us, &x, B, H, L, pt) || (ldh & 3) || (ldo & 3) || !split_part || !counter) return SF_ERR_UNSUPPORTED;
+    if (!proj_chain_supported(us, &x, B, H, L, pt) || !aligned4(ldh, ldo) || !split_part || !counter) return SF_ERR_UNSUPPORTED;
     const VisArgs va = proj_vis_args(x, pt, h, ldh, alpha, out, ldo, drop, drop_col0);
     SF_LAUNCH(visual_attn_split_proj_kernel, dim3(VSP_G, B), dim3(VSP_NW * 64), 0, st, va, VisSplit{split_part, counter, nullptr});
     return launch_status();
 }
 
-// ---- text groups per sample of launch (1).  With the partials the kernel holds proj_partials_body's ~125 registers, two
-// workgroups per CU: at batch 100 the four-group grid (300 + 400 + 32 blocks) is 732 blocks on 512 resident slots, and the
-// text groups of the second round pay their load -> reduce -> ticket -> merge latency behind a first-round block, on the
-// chain cell -> text -> score -> next gate product.  TWO groups of 8 * RPW positions (RPW <= 5: L <= 80) make it 532.
-// The rule is a pure function of (B, L, device) -- a captured replay and an eager rollout of one shape choose alike:
-// two groups iff the partials ride in this launch, L <= 80, and the four-group grid exceeds the resident slots.
-// force (sf_debug_projected_text_groups): 0 the rule, 2 / 4 that count where it is legal.  na: blocks of the y product.
+// ---- text groups per sample of launch (1): proj_text_groups_plan (sf_attention_plan.h) decides from the resident
+// workgroups of the four-group launch (1) with partials on the current device: CUs x what the runtime's occupancy query
+// gives pair_proj_textfold_kernel<R, true, TXF_G> (R: the four-group ladder's rung for L, text_rung).  Asked once per
+// device and kept (sf_projected_build asks ahead of any capture: proj_text_slots_warm); 0 = unknown, four groups.
 int g_proj_text_groups = 0;
-constexpr int TXF_G2_MAX_L = 2 * SMALL_WAVES * 5;
 static_assert(TXF_G == 4, "pair_proj_textfold names its instantiations <R, true, 2> and <R, true, 4>");
-int proj_text_groups_plan(int B, int L, bool with_partials, int na, int slots, int force, int* grid) {
-    const int nv = with_partials ? PPB_G * B : 0;
-    const bool legal = with_partials && L <= TXF_G2_MAX_L;
-    const bool crowded = slots > 0 && nv + TXF_G * B + na > slots;
-    const int G = legal && (force == 2 || (force != TXF_G && crowded)) ? 2 : TXF_G;
-    if (grid) *grid = nv + G * B + na;
-    return G;
-}
-
-// resident workgroups of the four-group launch (1) with partials on the current device: CUs x what the runtime's
-// occupancy query gives pair_proj_textfold_kernel<R, true, TXF_G> (R: the four-group ladder's rung for L).  Asked once
-// per device and kept (sf_projected_build asks ahead of any capture: proj_text_slots_warm); 0 = unknown, four groups.
-static int text_rung(int L, int G) {
-    const int rpw = (L + G * SMALL_WAVES - 1) / (G * SMALL_WAVES);
-    return rpw <= 1 ? 0 : rpw <= 2 ? 1 : rpw <= 3 ? 2 : 3;
-}
 static int proj_text_slots(int rung) {
     constexpr int kMaxDev = 64;
     static std::atomic<int> cache[kMaxDev][4];                   // slots + 1 (0: not asked yet)
@@ -1888,9 +1763,9 @@ int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* ma
                        int ldvec, float* part, unsigned* counter, float* z, int ldz, float* alpha, const SmallPlan& y,
                        const CandSrc& us, const PanoSrc* xn, const ProjTables& pt, const float* h1, int ldh1, float* split_part,
                        hipStream_t st) {
-    if (!(y.mt == 1 && y.cpw == 4) || !proj_chain_supported(us, xn, B, H, L, pt)) return SF_ERR_UNSUPPORTED;
-    if ((ldvec & 3) || (ldh1 & 3) || !counter || !z || (ldz & 3) || ldz < H || (xn && !split_part)) return SF_ERR_UNSUPPORTED;
-    if (xn && !proj_partials_supported(*xn)) return SF_ERR_UNSUPPORTED;
+    if (!pair_proj_textfold_accepts(y.inst()) || !proj_chain_supported(us, xn, B, H, L, pt)) return SF_ERR_UNSUPPORTED;
+    if (!aligned4(ldvec, ldh1, ldz) || !counter || !z || ldz < H || (xn && !split_part)) return SF_ERR_UNSUPPORTED;
+    if (xn && !proj_partials_supported(xn->IMG, xn->LOC)) return SF_ERR_UNSUPPORTED;
     const TxtFoldArgs ta{ctx_q, ctx_o, mask, L, H, vec, ldvec, part, counter, z, ldz, alpha};
     const VisArgs va = xn ? proj_vis_args(*xn, pt, h1, ldh1, nullptr, nullptr, 0, Dropout{}, 0) : VisArgs{};
     const VisSplit sp{split_part, nullptr, g_trace};
@@ -1900,17 +1775,14 @@ int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* ma
     const int slots = xn && L <= TXF_G2_MAX_L && force == 0 ? proj_text_slots(text_rung(L, TXF_G)) : 0;
     int blocks = 0;
     const int G = proj_text_groups_plan(B, L, xn != nullptr, na, slots, force, &blocks);
-    const int nt = G * B, rung = text_rung(L, G);
+    const int nt = G * B;
     const dim3 grid(blocks), block(SMALL_WAVES * 64);
-#define SF_PPT(R)                                                                                                          \
-    do {                                                                                                                   \
-        if (nv && G == 2) SF_LAUNCH((pair_proj_textfold_kernel<R, true, 2>), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx); \
-        else if (nv) SF_LAUNCH((pair_proj_textfold_kernel<R, true, 4>), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx);      \
-        else SF_LAUNCH((pair_proj_textfold_kernel<R, false>), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx);        \
-    } while (0)
-    if (rung == 0) SF_PPT(1); else if (rung == 1) SF_PPT(2); else if (rung == 2) SF_PPT(3); else SF_PPT(5);
-#undef SF_PPT
-    return launch_status();
+    return launched(with_index(fold_rpw(L, G), [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        if (nv && G == 2) SF_LAUNCH_INST(pair_proj_textfold_kernel, (R, true, 2), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx);
+        else if (nv) SF_LAUNCH_INST(pair_proj_textfold_kernel, (R, true, 4), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx);
+        else SF_LAUNCH_INST(pair_proj_textfold_kernel, (R, false), grid, block, 0, st, va, sp, nv, ta, nt, y.args, y.gx);
+    }, ints<1, 2, 3, 5>{}));
 }
 
 // launch (2): scoring + glue on projected candidate rows  ||  vphase 2: merge of launch (1)'s partials; 0: the whole
@@ -1918,8 +1790,8 @@ int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* ma
 int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt, const float* z, int ldz, const float* y, int ldy,
                     const FGlue& g, const PanoSrc* xn, int vphase, const float* h1, int ldh1, float* alpha, float* out, int ldo,
                     const Dropout& drop, int drop_col0, float* split_part, unsigned* counter, hipStream_t st) {
-    if (!proj_chain_supported(us, xn, B, H, L, pt) || (ldz & 3) || (ldy & 3) || (ldh1 & 3)) return SF_ERR_UNSUPPORTED;
-    if (xn && (!split_part || (ldo & 3) || (vphase != 0 && vphase != 2) || (vphase == 0 && !counter))) return SF_ERR_UNSUPPORTED;
+    if (!proj_chain_supported(us, xn, B, H, L, pt) || !aligned4(ldz, ldy, ldh1)) return SF_ERR_UNSUPPORTED;
+    if (xn && (!split_part || !aligned4(ldo) || (vphase != 0 && vphase != 2) || (vphase == 0 && !counter))) return SF_ERR_UNSUPPORTED;
     const ProjScoreArgs a{us, pt.pa, pt.la, pt.ld, H, z, y, ldz, ldy};
     const VisArgs va = xn ? proj_vis_args(*xn, pt, h1, ldh1, alpha, out, ldo, drop, drop_col0) : VisArgs{};
     const VisSplit sp{split_part, counter, g_trace};
@@ -1936,13 +1808,11 @@ int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt
 // partials in launch (1) and their merge in launch (2), else partials, ticket and merge in launch (2).
 int proj_attention_alone(const PanoSrc& x, int B, const ProjTables& pt, const float* h1, int ldh1, float* alpha, float* out,
                          int ldo, int late, float* split_part, unsigned* counter, hipStream_t st) {
-    const int F = x.IMG + x.LOC;
     if (x.dense || x.half || !x.table || !x.loc_table || !x.vp || !x.view || !pt.pv || !pt.lv || !h1 || !alpha || !out ||
         !split_part)
         return SF_ERR_ARG;
-    if (B < 1 || B > VIS_SPLIT_MAX_B || x.V <= (VSP_G - 1) * VSP_RPG || x.V > VSP_G * VSP_RPG || F > VIS_CPL * 256 ||
-        (x.IMG & 3) || (x.LOC & 3) || pt.H > PRJ_CPL * 256 || (pt.H & 3) || pt.H < 4 || (pt.ld & 3) || pt.ld < pt.H + 1 ||
-        (ldh1 & 3) || ldh1 < pt.H || (ldo & 3) || ldo < F || (late ? !counter : !proj_partials_supported(x)))
+    if (B < 1 || !split_rows_fit(shape(x), B) || !proj_tables_fit(pt.H, pt.ld) || !aligned4(ldh1, ldo) || ldh1 < pt.H ||
+        ldo < x.IMG + x.LOC || (late ? !counter : !proj_partials_supported(x.IMG, x.LOC)))
         return SF_ERR_UNSUPPORTED;
     const VisArgs va = proj_vis_args(x, pt, h1, ldh1, alpha, out, ldo, Dropout{}, 0);
     const VisSplit sp{split_part, late ? counter : nullptr, nullptr};
@@ -1960,49 +1830,35 @@ int proj_attention_alone(const PanoSrc& x, int B, const ProjTables& pt, const fl
 extern "C" void sf_debug_trace(unsigned long long* buf) { g_trace = buf; }
 extern "C" void sf_debug_force_write_through(int on) { g_force_sc1 = on; }
 
+// the split visual attention (phase 0: whole, with the ticket inside the launch; 1: partials; 2: merge) beside the small
+// product b: the instantiations of VIS_SMALL_INST
 int pair_vis_small(const PanoSrc& src, int B, const float* vec, int ldvec, float* alpha, float* out,
                    int ldo, const Dropout& drop, int drop_col0, float* split_part,
                    unsigned* split_counter, const SmallPlan& b, hipStream_t st, int phase) {
-    const int F = src.IMG + src.LOC;
-    // (the r = W_a^T wt product of the folded text chain: K = D = 256 -> two chunks per wave)
-    const bool wide = b.cpw == 2 && (b.mt == 1 || b.mt == 2 || b.mt == 4) && phase != 2;
-    if (!wide && !(b.mt == 1 && (b.cpw == 8 || (phase == 2 && b.cpw == 4)))) return SF_ERR_UNSUPPORTED;
-    if (!split_part || (phase == 0 && !split_counter) || src.V <= (VSP_G - 1) * VSP_RPG || src.V > VSP_G * VSP_RPG ||
-        B > VIS_SPLIT_MAX_B ||
-        F > VIS_CPL * 256 || (F & 3) || (!src.dense && ((src.IMG & 3) || (src.LOC & 3))) ||
-        (ldvec & 3) || (ldo & 3))
+    if (!pair_vis_small_accepts(b.inst(), phase)) return SF_ERR_UNSUPPORTED;
+    if (!split_part || (phase == 0 && !split_counter) || !split_rows_fit(shape(src), B) || !aligned4(ldvec, ldo))
         return SF_ERR_UNSUPPORTED;
     if (half_misuse(src)) return SF_ERR_ARG;
     VisArgs va{src, vec, ldvec, alpha, out, ldo, drop, drop_col0};
     const int nv = (phase == 2 ? 1 : VSP_G) * B, nb = b.gx * b.gy;
     const dim3 grid(nv + nb), block(SMALL_WAVES * 64);
     const VisSplit sp{split_part, split_counter, g_trace};
-    // (phase 2 only merges partials and never reads the table: its one instantiation serves both storages)
-#define SF_PVS(M, C, P)                                                                                                 \
-    SF_LAUNCH_H16(src.half && P != 2, (pair_vis_small_kernel<M, C, P>), (pair_vis_small_kernel<M, C, P, false, P != 2>), grid, \
-                  block, 0, st, va, sp, nv, b.args, b.gx)
-    if (wide && b.mt == 4 && phase == 0)
-        SF_PVS(4, 2, 0);
-    else if (wide && b.mt == 4)
-        SF_PVS(4, 2, 1);
-    else if (wide && b.mt == 2 && phase == 0)
-        SF_PVS(2, 2, 0);
-    else if (wide && b.mt == 2)
-        SF_PVS(2, 2, 1);
-    else if (wide && phase == 0)
-        SF_PVS(1, 2, 0);
-    else if (wide)
-        SF_PVS(1, 2, 1);
-    else if (phase == 0)
-        SF_PVS(1, 8, 0);
-    else if (phase == 1)
-        SF_PVS(1, 8, 1);
-    else if (b.cpw == 8)
-        SF_PVS(1, 8, 2);
-    else
-        SF_PVS(1, 4, 2);
-#undef SF_PVS
-    return launch_status();
+    return launched(with_index<VIS_SMALL_INSTS>(vis_small_inst(b.inst(), phase), [&](auto i) {
+        constexpr VisSmallInst I = VIS_SMALL_INST[decltype(i)::value];
+        constexpr int M = I.mt, C = I.cpw, P = I.phase;
+        // (phase 2 only merges partials and never reads the table: its one instantiation serves both storages; the
+        //  binary16 name is the one the profile has always reported)
+        if constexpr (P != 2) {
+            if (src.half) {
+                SF_LAUNCH_AS((inst_name<pair_vis_small_kernel<M, C, P, false, true>, M, C, P, false>(
+                                 "pair_vis_small_kernel", P ? ", 1 != 2" : ", 0 != 2")),
+                             (pair_vis_small_kernel<M, C, P, false, true>), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+                return;
+            }
+        }
+        SF_LAUNCH_INST(pair_vis_small_kernel, (M, C, P), grid, block, 0, st, va, sp, nv, b.args, b.gx);
+    }));
 }
 
 }  // namespace sf
+

@@ -6,6 +6,8 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/sf_hip.h"
 
@@ -57,6 +59,43 @@ void prof_events(const char* name, hipEvent_t* e0, hipEvent_t* e1);
             hipLaunchKernelGGL(kernel, grid, block, shmem, st, __VA_ARGS__);                     \
         }                                                                                        \
     } while (0)
+
+// Calls f(std::integral_constant<int, V>) for the V of the list that equals `want`; false when there is none.  The one
+// place where a planned value (a position in a table of instantiations -- with_index<N>: [0, N) -- or a ladder's rung,
+// ints<1, 5, 8>) becomes a template argument.
+template <int... V>
+using ints = std::integer_sequence<int, V...>;
+template <class F, int... V>
+bool with_index(int want, F&& f, ints<V...>) {
+    return ((V == want && (f(std::integral_constant<int, V>{}), true)) || ...);
+}
+template <int N, class F>
+bool with_index(int want, F&& f) {
+    return with_index(want, f, std::make_integer_sequence<int, N>{});
+}
+
+// "kernel<1, 4, true>": an instantiation as kernel_profile() spells it (a launch inside a template only sees "<MT, CPW>");
+// `more`: arguments the profile has always reported under another spelling than their value
+template <auto Kernel, auto... A>
+const char* inst_name(const char* kernel, const char* more = "") {
+    static const std::string nm = [=] {
+        std::string s = std::string(kernel) + "<";
+        const char* sep = "";
+        auto put = [&](auto a) {
+            if constexpr (std::is_same_v<decltype(a), bool>) s += std::string(sep) + (a ? "true" : "false");
+            else s += sep + std::to_string(a);
+            sep = ", ";
+        };
+        (put(A), ...);
+        return s + more + ">";
+    }();
+    return nm.c_str();
+}
+// SF_LAUNCH of K<targs> under that name; targs in parentheses: SF_LAUNCH_INST(kernel, (MT, CPW), grid, block, ...)
+#define SF_TARGS(...) __VA_ARGS__
+#define SF_LAUNCH_INST(K, targs, grid, block, shmem, st, ...)                                                        \
+    SF_LAUNCH_AS((sf::inst_name<K<SF_TARGS targs>, SF_TARGS targs>(#K)), (K<SF_TARGS targs>), grid, block, shmem, st, \
+                 __VA_ARGS__)
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 

@@ -1758,29 +1758,7 @@ inline GemmSwitches switches() {
 }
 inline dim3 dim(const PlanGrid& g) { return dim3(g.x, g.y, g.z); }
 
-// Calls f(std::integral_constant<int, I>) for the I of [0, N) that equals `want`; false when there is none.  The one
-// place where a planned instantiation (SMALL_INST, 1 .. NT_MT_MAX, NN_INST of sf_gemm_plan.h) becomes a template argument.
-template <class F, int... I>
-bool with_index(int want, F&& f, std::integer_sequence<int, I...>) {
-    return ((I == want && (f(std::integral_constant<int, I>{}), true)) || ...);
-}
-template <int N, class F>
-bool with_index(int want, F&& f) {
-    return with_index(want, f, std::make_integer_sequence<int, N>{});
-}
-
-// "kernel<1, 4>": an instantiation as kernel_profile() spells it (a launch inside a template only sees "<MT, CPW>")
-template <auto Kernel, int... A>
-const char* inst_name(const char* kernel) {
-    static const std::string nm = [kernel] {
-        std::string s = std::string(kernel) + "<";
-        const char* sep = "";
-        ((s += sep + std::to_string(A), sep = ", "), ...);
-        return s + ">";
-    }();
-    return nm.c_str();
-}
-
+// (with_index / SF_LAUNCH_INST, where a planned SMALL_INST, 1 .. NT_MT_MAX or NN_INST becomes a template argument: sf_common.h)
 // A launch of a kernel that takes more than 64 KB of dynamic LDS: that must be opted into, once per instantiation
 template <auto Kernel, class... Args>
 void launch_big_lds(const char* name, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
@@ -1843,13 +1821,8 @@ int launch_small_plan(const SmallPlan& p, hipStream_t st) {
     const dim3 grid(p.gx, p.gy), block(SMALL_WAVES * 64);
     const bool known = with_index<SMALL_INSTS>(small_inst(p.mt, p.cpw), [&](auto i) {
         constexpr int MT = SMALL_INST[decltype(i)::value].mt, CPW = SMALL_INST[decltype(i)::value].cpw;
-        if (extras) {
-            const char* nm = inst_name<gemm_nt_small_x_kernel<MT, CPW>, MT, CPW>("gemm_nt_small_x_kernel");
-            SF_LAUNCH_AS(nm, (gemm_nt_small_x_kernel<MT, CPW>), grid, block, 0, st, a);
-        } else {
-            const char* nm = inst_name<gemm_nt_small_kernel<MT, CPW>, MT, CPW>("gemm_nt_small_kernel");
-            SF_LAUNCH_AS(nm, (gemm_nt_small_kernel<MT, CPW>), grid, block, 0, st, a);
-        }
+        if (extras) SF_LAUNCH_INST(gemm_nt_small_x_kernel, (MT, CPW), grid, block, 0, st, a);
+        else SF_LAUNCH_INST(gemm_nt_small_kernel, (MT, CPW), grid, block, 0, st, a);
     });
     return known ? launch_status() : SF_ERR_UNSUPPORTED;
 }
@@ -1931,7 +1904,7 @@ int linear_nt(const Seg* segs, int nseg, int M, int N, const LinearOut& out, flo
                                                          grid, block, p.lds, st, a);
                 break;
             default:
-                SF_LAUNCH_AS((inst_name<gemm_nt_kernel<MT>, MT>("gemm_nt_kernel")), gemm_nt_kernel<MT>, grid, block, 0, st, a);
+                SF_LAUNCH_INST(gemm_nt_kernel, (MT), grid, block, 0, st, a);
         }
     });
     if (!known) return SF_ERR_UNSUPPORTED;
@@ -1988,7 +1961,7 @@ int gemm_nn_ws(const float* A, int lda, const float* W, int ldw, int M, int N, i
     const NnArgs a{A, lda, W, ldw, M, N, K, p.ks, slabs ? ws : y, slabs ? N : ldy, accumulate};
     const bool known = with_index<NN_INSTS>(nn_inst(p.mt), [&](auto i) {
         constexpr int MT = NN_INST[decltype(i)::value];
-        SF_LAUNCH_AS((inst_name<gemm_nn_kernel<MT>, MT>("gemm_nn_kernel")), gemm_nn_kernel<MT>, dim(p.grid), dim3(256), 0, st, a);
+        SF_LAUNCH_INST(gemm_nn_kernel, (MT), dim(p.grid), dim3(256), 0, st, a);
     });
     if (!known) return SF_ERR_UNSUPPORTED;
     if (slabs) reduce_slabs(ws, p.ks, M, N, plain_out(y, ldy, accumulate), st);

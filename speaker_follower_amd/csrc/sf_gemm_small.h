@@ -207,6 +207,7 @@ struct SmallPlan {
     SmallArgs args;
     int mt, cpw;          // template parameters of the body
     int gx, gy;           // grid
+    SmallInst inst() const { return SmallInst{mt, cpw}; }     // what the paired launches accept or not (sf_attention_plan.h)
 };
 bool linear_small_plan(const Seg* segs, int nseg, int M, int N, const LinearOut& out, SmallPlan* plan);
 int launch_small_plan(const SmallPlan& p, hipStream_t st);        // launch a plan on its own

@@ -5,19 +5,13 @@
 #include "sf_lstm.h"
 #include "sf_lstm_pw.h"
 #include "sf_rows.h"
+#include "sf_attention_plan.h"     // VIS_SPLIT_MAX_B, the shape rules, scratch sizes and acceptance predicates of sf_attention.hip
 
 namespace sf {
-
-// Largest batch of the split visual attention (two workgroups per sample, per-sample ticket counters) and of the
-// schedules built around it: the paired / folded decode steps and the two-stream backward through time
-// (sf_follower_episode_bwd_range).  Above it the un-split kernels run and those schedules fall back to one launch at a
-// time on one stream.
-constexpr int VIS_SPLIT_MAX_B = 256;
 
 // ---- sf_attention.hip ---------------------------------------------------------------------------
 // split_part / split_counter (optional): scratch ([visual_attn_split_floats] floats) and the
 // per-sample ticket counters that let the forward pass use two workgroups per sample.
-size_t visual_attn_split_floats(int B, int F);
 int visual_attn(int mode, const PanoSrc& src, int B, const float* vec, int ldvec, float* alpha,
                 float* out, int ldo, const Dropout& drop, int drop_col0, hipStream_t st,
                 float* split_part = nullptr, unsigned* split_counter = nullptr, const double* vec64 = nullptr,
@@ -38,8 +32,7 @@ int text_attn_bwd(const float* ctx, int B, int L, int H, const float* dwc, int l
                   const float* t, int ldt, const float* alpha, float* dt, int lddt, float* dctx,
                   hipStream_t st, float* ds_out = nullptr,    // dctx null + ds_out: deferred update
                   const int32_t* ctx_row = nullptr);          // (deferred form only) row b reads ctx row ctx_row[b]
-// dctx[b,l,:] += sum_t (alpha[t,b,l] dcat2[t,b,:H] + ds[t,b,l] tt[t,b,:]) over S stacked steps
-bool ctx_grad_supported(int S, int L, int H);
+// dctx[b,l,:] += sum_t (alpha[t,b,l] dcat2[t,b,:H] + ds[t,b,l] tt[t,b,:]) over S stacked steps (ctx_grad_supported)
 int ctx_grad_accum(const float* alpha, const float* ds, const float* dcat2, int lddc, const float* tt,
                    int S, int B, int L, int H, float* dctx, hipStream_t st);
 int score_fwd(const CandSrc& src, int B, int D, const float* r, const float* wt, const float* b_a,
@@ -232,7 +225,6 @@ int pair_vis_text(const PanoSrc& src, int B, const float* vec, int ldvec, float*
 int pair_textfold_small_small(const float* ctx_q, const float* ctx_o, const uint8_t* mask, int B, int L, int H,
                               const float* vec, int ldvec, float* part, unsigned* counter, float* z, int ldz, float* alpha,
                               const SmallPlan& a, const SmallPlan& b, hipStream_t st);
-size_t text_fold_part_floats(int B, int H);
 int pair_apro_small(const SmallPlan& a, const SmallPlan& b, hipStream_t st);
 struct FGlue;
 int pair_score_merge(const CandSrc& src, int B, int D, const float* r, const float* wt, const float* b_a,
@@ -248,18 +240,13 @@ struct ProjTables {
     int ld, H;
 };
 bool proj_chain_supported(const CandSrc& us, const PanoSrc* xn, int B, int H, int L, const ProjTables& pt);
-// whether launch (1) can carry the attention partials of a panorama of this row layout (pair_proj_textfold with `xn`);
-// where it cannot they ride in launch (2) (pair_proj_score, vphase 0)
-bool proj_partials_supported(const PanoSrc& xn);
 int proj_attention_alone(const PanoSrc& x, int B, const ProjTables& pt, const float* h1, int ldh1, float* alpha, float* out,
                          int ldo, int late, float* split_part, unsigned* counter, hipStream_t st);
 int visual_attn_proj(const CandSrc& us, const PanoSrc& x, int B, int H, int L, const ProjTables& pt, const float* h, int ldh,
                      float* alpha, float* out, int ldo, const Dropout& drop, int drop_col0, float* split_part,
                      unsigned* counter, hipStream_t st);
-// text groups per sample of launch (1) and its grid (sf_attention.hip; the launcher's own rule, callable without a device):
-// na = blocks of the y product, slots = resident workgroups of the four-group launch (0: unknown), force = 0 / 2 / 4
+// text groups per sample of launch (1) and its grid: proj_text_groups_plan (the launcher's own rule)
 extern int g_proj_text_groups;        // sf_debug_projected_text_groups (default 0: the rule)
-int proj_text_groups_plan(int B, int L, bool with_partials, int na, int slots, int force, int* grid);
 void proj_text_slots_warm();          // asks the device for `slots` once (ahead of any capture)
 int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* mask, int B, int L, int H, const float* vec,
                        int ldvec, float* part, unsigned* counter, float* z, int ldz, float* alpha, const SmallPlan& y,

@@ -27,24 +27,24 @@ import numpy as np
 from tests.gemm_cases import SENTINEL, TAIL_ROWS, layout, outside_is_untouched          # noqa: F401
 
 # ------------------------------------------------------------------------------------------ constants
-# (speaker_follower_amd/csrc/sf_attention.hip unless another file is named; the line each value mirrors)
-VIS_CPL, VIS_RPW, VIS_NW = 9, 3, 12           # :18   float4 chunks per lane, rows per wave, waves
-VSP_G = 2                                     # :178  SF_VIS_GROUPS: workgroups per sample of the split forward
-VSP_RPG = VIS_NW // VSP_G * VIS_RPW           # :181  rows per group = 18
-VIS_SPLIT_MAX_B = 256                         # sf_kernels.h:15
-TXT_CPL, TXT_NW = 2, 16                       # :426
-TXT_RPW = (1, 5, 8)                           # :1153-1158  text_attn_launch: L <= 16 RPW
-SC_CPL, SC_NW = 9, 16                         # :586
-CG_ROWS, CG_THREADS, CG_LDS = 10, 1024, 64 * 1024     # :1033, :1183-1184  ctx_grad_kernel
+# (speaker_follower_amd/csrc/sf_attention_plan.h unless another file is named; the symbol each value mirrors)
+VIS_CPL, VIS_RPW, VIS_NW = 9, 3, 12           # VIS_CPL, VIS_RPW, VIS_NW   float4 chunks per lane, rows per wave, waves
+VSP_G = 2                                     # VSP_G  SF_VIS_GROUPS: workgroups per sample of the split forward
+VSP_RPG = VIS_NW // VSP_G * VIS_RPW           # VSP_RPG  rows per group = 18
+VIS_SPLIT_MAX_B = 256                         # VIS_SPLIT_MAX_B
+TXT_CPL, TXT_NW = 2, 16                       # TXT_CPL, TXT_NW
+TXT_RPW = (1, 5, 8)                           # text_rpw  (sf_attention.hip: text_attn_launch): L <= 16 RPW
+SC_CPL, SC_NW = 9, 16                         # SC_CPL, SC_NW
+CG_ROWS, CG_THREADS, CG_LDS = 10, 1024, 64 * 1024     # CG_ROWS, ctx_grad_supported  ctx_grad_kernel
 
-V_MAX = min(VIS_RPW * VIS_NW, 64)             # :1125  36
-V_SPLIT_LO = (VSP_G - 1) * VSP_RPG            # :1138  the split forward runs for V_SPLIT_LO < V <= V_MAX
-F_MAX = VIS_CPL * 256                         # :1125, :1199  2304 (both CPL are 9)
-H_MAX = TXT_CPL * 256                         # :1167  512
-L_MAX = TXT_NW * TXT_RPW[-1]                  # :1157  128
-A_MAX = SC_NW                                 # :1199  16
-SOFTMAX_HALF = 64                             # :498   lane holds positions lane and lane + 64
-SCORE_LOC_MULTIPLE = 16                       # :1200  index form: LOC % 16 == 0
+V_MAX = min(VIS_RPW * VIS_NW, 64)             # pano_rows_fit  36
+V_SPLIT_LO = (VSP_G - 1) * VSP_RPG            # in_split_range  the split forward runs for V_SPLIT_LO < V <= V_MAX
+F_MAX = VIS_CPL * 256                         # row_width_fits  2304 (both CPL are 9)
+H_MAX = TXT_CPL * 256                         # text_rows_fit  512
+L_MAX = TXT_NW * TXT_RPW[-1]                  # TXT_MAX_L  128
+A_MAX = SC_NW                                 # cand_rows_fit  16
+SOFTMAX_HALF = 64                             # sf_attention.hip: text_attn_body   lane holds positions lane and lane + 64
+SCORE_LOC_MULTIPLE = 16                       # cand_rows_fit  index form: LOC % 16 == 0
 
 VIS_FWD, VIS_BWD, VIS_SPLIT, VIS_F64 = ('visual_attn_kernel<0>', 'visual_attn_kernel<1>', 'visual_attn_split_kernel',
                                         'visual_attn_split_f64_kernel')
@@ -59,17 +59,17 @@ def half_name(kernel):
 
 
 def visual_fwd_kernel(V, B, workspace=True):
-    """visual_attn (:1121-1149), forward."""
+    """visual_attn (sf_attention.hip), forward: in_split_range."""
     return VIS_SPLIT if workspace and V_SPLIT_LO < V <= V_MAX and B <= VIS_SPLIT_MAX_B else VIS_FWD
 
 
 def visual_f64_supported(V, B, F):
-    """visual_attn_f64_supported (:1114-1119), dense source."""
+    """visual_attn_f64_supported (split_rows_fit), dense source."""
     return V_SPLIT_LO < V <= V_MAX and B <= VIS_SPLIT_MAX_B and F <= F_MAX and F % 4 == 0
 
 
 def text_kernel(L):
-    """text_attn_launch (:1151-1162); None = SF_ERR_UNSUPPORTED."""
+    """text_attn_launch (text_rpw); None = SF_ERR_UNSUPPORTED."""
     for r in TXT_RPW:
         if L <= TXT_NW * r:
             return TXT % r
@@ -77,7 +77,7 @@ def text_kernel(L):
 
 
 def ctx_grad_supported(S, L, H):
-    """ctx_grad_supported (:1181-1185)."""
+    """ctx_grad_supported."""
     n4 = H >> 2
     return (H % 4 == 0 and 1 <= n4 <= CG_THREADS and CG_THREADS % n4 == 0 and L <= (CG_THREADS // n4) * CG_ROWS and
             S * 2 * L * 4 <= CG_LDS)
