@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define SF_ABI_VERSION 9
+#define SF_ABI_VERSION 10
 
 enum {
     SF_OK = 0,
@@ -128,11 +128,10 @@ typedef struct sf_scoring_w { /* EltwiseProdScoring model.py:335-340 */
 } sf_scoring_w;
 typedef struct sf_scoring_g { float *w_h, *b_h, *w_a, *b_a, *w_out, *b_out, *unused0, *unused1; } sf_scoring_g;
 
-/* Optional INFERENCE-ONLY folding of consecutive Linears (built by sf_decoder_fold_build once per
- * weight version): the visual query q = W_v^T (W_h h + b_h) becomes ONE product q = M_v h + c_v, and
- * the scoring vector / constant r = W_a^T (w_out * (W_h h~ + b_h)), c = wt.b_a + b_out become ONE
- * product [r | c] = M_a h~ + c_a.  Two dependent stages fewer per decode step.  The backward needs
- * the unfolded intermediates, so training calls leave `fold` NULL. */
+/* Consecutive Linears folded into one matrix each (built by sf_decoder_fold_build once per weight
+ * version): the visual query q = W_v^T (W_h h + b_h) is q = M_v h + c_v, and the scoring vector /
+ * constant r = W_a^T (w_out * (W_h h~ + b_h)), c = wt.b_a + b_out are [r | c] = M_a h~ + c_a.
+ * sf_projected_build forms the projected feature tables from them; no decode step reads them. */
 typedef struct sf_decoder_fold {
     const float* m_v; /* [F,H]   = W_v^T W_h */
     const float* c_v; /* [F]     = W_v^T b_h */
@@ -144,9 +143,8 @@ typedef struct sf_decoder_w { /* AttnDecoderLSTM model.py:361-375 */
     sf_visual_w visual;
     sf_softdot_w text;
     sf_scoring_w action;
-    const sf_decoder_fold* fold; /* NULL = unfolded (required for training) */
 } sf_decoder_w;
-typedef struct sf_decoder_g { sf_lstm_g lstm; sf_visual_g visual; sf_softdot_g text; sf_scoring_g action; void* unused; } sf_decoder_g;
+typedef struct sf_decoder_g { sf_lstm_g lstm; sf_visual_g visual; sf_softdot_g text; sf_scoring_g action; } sf_decoder_g;
 
 /* ---- saved activations of one AttnDecoderLSTM step (all written by fwd, read by bwd) ------- */
 typedef struct sf_decoder_tape {
@@ -432,7 +430,7 @@ int sf_attn_decoder_wgrad(const sf_decoder_w* w, const sf_decoder_g* g, int M, i
  *        glue.nav != NULL (sf_nav_io of STEP 0 of a device-resident environment, state buffers stacked
  *        [S + 1][...]): per step sf_attn_decoder_tail_fwd with tape_next but no X_next -- the environment steps
  *        inside its scoring + glue launch -- followed by sf_attn_decoder_attend_fwd over the panorama just chosen
- *        (needs w->visual.w_v_t, no folded weights).
+ *        (needs w->visual.w_v_t).
  * bwd  = per step t = S-1..0: sf_follower_glue_bwd (gscale[t]) + sf_attn_decoder_bwd (g = NULL, dY
  *        operands into the stacked gtape), ping-ponging (dh, dc) between the two buffer pairs;
  *        *result_in_b tells which pair holds d h_init / d c_init; dctx [B,L,H] is ADDED to.
@@ -453,7 +451,7 @@ typedef struct sf_follower_episode {
      * `stream` (they only meet at the LSTM pointwise backward); the two are ordered with events and the
      * call leaves `stream` behind all of the side stream's work.  FORWARD: it means exactly one thing, the two-chain
      * schedule -- the visual half of step t + 1 on it beside the rest of step t on `stream`, ordered per step by device
-     * flags, one fork and one join per episode -- taken for pre-drawn observations, S > 1, no w->fold and no
+     * flags, one fork and one join per episode -- taken for pre-drawn observations, S > 1 and no
      * ctx_q / ctx_o; every other forward pass ignores it. */
     sf_stream side_stream;
     /* ABI 9, optional, INFERENCE ONLY (drop.p == 0, no backward through this pass: t_text / cat2[:H] / h_tilde of the
@@ -465,11 +463,6 @@ typedef struct sf_follower_episode {
      * (glue.nav).  The two fold products run on `stream` in front of step 0's attention; with ctx_q / ctx_o the
      * two-chain forward schedule of `side_stream` is not taken. */
     float *ctx_q, *ctx_o;
-    /* ... and, with the folded matrices of sf_decoder_fold (built once per weight version, sf_decoder_fold_build): the next
-     * step's visual query as ONE product q' = M_v h1 + c_v beside the folded attention, the scoring vector / constant as
-     * ONE product [r | c] = M_a h~ + c_a whose operand h~ the A-prologue forms -- THREE dependent launches behind the cell
-     * (t_v, t_a, wt, r of the tape are not written either).  NULL: the four-launch chain.  `w->fold` stays NULL. */
-    const sf_decoder_fold* chain_fold;
 } sf_follower_episode;
 int sf_follower_episode_fwd(const sf_decoder_w* w, const sf_follower_episode* e, void* ws,
                             size_t ws_bytes, sf_stream stream);
@@ -477,17 +470,6 @@ int sf_follower_episode_bwd(const sf_decoder_w* w, const sf_follower_episode* e,
                             const sf_decoder_gtape* gtape, const float* gscale, float* dlogit,
                             float* dh_a, float* dc_a, float* dh_b, float* dc_b, float* dctx,
                             int* result_in_b, void* ws, size_t ws_bytes, sf_stream stream);
-/* The same over the decode steps [t_lo, t_hi) only (t_hi - 1 first): backpropagation through time in chunks,
- * so that the caller can start the weight-gradient products of the steps that are done (sf_attn_decoder_wgrad
- * over their stacked rows, on another stream) while the earlier steps are still being walked -- the slot is
- * `loss.backward()` of follower.py:1014-1018.  dh_in / dc_in: the gradient arriving from step t_hi (the
- * previous call's result; NULL when t_hi == S).  The call whose t_lo == 0 also forms the deferred context
- * gradient of the whole episode. */
-int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episode* e,
-                                  const sf_decoder_gtape* gtape, const float* gscale, float* dlogit,
-                                  float* dh_a, float* dc_a, float* dh_b, float* dc_b, float* dctx,
-                                  int* result_in_b, int t_lo, int t_hi, const float* dh_in, const float* dc_in,
-                                  void* ws, size_t ws_bytes, sf_stream stream);
 
 /* Loss bookkeeping without host syncs or atomics (deterministic order):
  * sum_cnt[t] = (sum_b term[t,b], sum_b live[t,b]) for t < T;  then, optionally after a
@@ -1120,8 +1102,6 @@ int sf_debug_projected_attention(const sf_pano* X, int B, int H, const float* pv
  * error-free operand splitting (csrc/sf_gemm.hip: gemm_nt_split_kernel; same fp32 accuracy class, measured closer
  * to the exact sum, 6/16 of the matrix-pipe time).  For A/B timing and for the accuracy tests. */
 void sf_debug_gate_product_f32(int on);
-/* 0: the four-launch folded chain even when sf_follower_episode.chain_fold is given (A/B switch) */
-void sf_debug_fold_chain3(int on);
 /* A/B switch (round 5): on == 0 sends the many-row products (M >= 512: the speaker's teacher-forced head over all S*B rows,
  * the beam search's flat steps) back to the register-streaming kernel of rounds 1-4 instead of the LDS-tiled 128 x 128
  * bf16x6 kernel (csrc/sf_gemm.hip: gemm_nt_big_kernel; the default).  Bit 1 of `on` (on == 3) keeps the kernel but turns off

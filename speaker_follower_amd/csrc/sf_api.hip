@@ -244,7 +244,6 @@ int lstm_fwd_i(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx,
     return lstm_pointwise_fwd(p, st);
 }
 
-static int g_fold_chain3 = 1;               // sf_debug_fold_chain3 (0: the four-launch folded chain even with chain_fold)
 static int g_slab_consumers = 1;     // sf_debug_slab_consumers: consumers add up K-split slabs themselves (0: a reduce launch in between)
 
 int lstm_bwd_i(const sf_lstm_w* w, const sf_lstm_g* g, int B, int I, int H, const float* x, int ldx,
@@ -310,10 +309,9 @@ int lstm_bwd_i(const sf_lstm_w* w, const sf_lstm_g* g, int B, int I, int H, cons
 // ---- a1 VisualSoftDotAttention ---------------------------------------------------------------------
 int visual_fwd_i(const sf_visual_w* w, const PanoSrc& X, int B, int H, int D, const float* h,
                  float* out, int ldo, float* alpha, float* t_v, float* q, const Dropout& drop,
-                 int col0, Arena ar, hipStream_t st, const sf_decoder_fold* fold = nullptr, bool precise = false,
-                 const sf_visual_fold64* fold64 = nullptr) {
+                 int col0, Arena ar, hipStream_t st, bool precise = false, const sf_visual_fold64* fold64 = nullptr) {
     const int F = X.IMG + X.LOC;
-    if (precise && !fold && fold64 && fold64->m_v && fold64->c_v && visual_attn_f64_supported(X, B) && !(H & 3)) {
+    if (precise && fold64 && fold64->m_v && fold64->c_v && visual_attn_f64_supported(X, B) && !(H & 3)) {
         // inference through the float64 fold: q = M_v h + c_v in ONE product (t_v is not formed: no backward follows)
         double* q64 = reinterpret_cast<double*>(ar.take((size_t)B * F * 2));
         float* part = ar.take(visual_attn_split_floats(B, F));
@@ -322,7 +320,7 @@ int visual_fwd_i(const sf_visual_w* w, const PanoSrc& X, int B, int H, int D, co
             return visual_attn(0, X, B, q, F, alpha, out, ldo, drop, col0, st, part, ar.tickets(), q64);
         }
     }
-    if (precise && !fold && w->w_v_t && visual_attn_f64_supported(X, B) && !(H & 3) && !(D & 3)) {
+    if (precise && w->w_v_t && visual_attn_f64_supported(X, B) && !(H & 3) && !(D & 3)) {
         // The speaker's path encoder (csrc/sf_precise.hip): t_v, q and the scores in float64 -- each intermediate is
         // rounded ONCE.  t_v / q also land in their fp32 tapes (the backward reads those).
         double* t64 = reinterpret_cast<double*>(ar.take((size_t)B * D * 2));
@@ -333,12 +331,6 @@ int visual_fwd_i(const sf_visual_w* w, const PanoSrc& X, int B, int H, int D, co
             TRY(linear_f64(nullptr, t64, D, w->w_v_t, D, nullptr, B, F, D, q64, F, q, F, st));
             return visual_attn(0, X, B, q, F, alpha, out, ldo, drop, col0, st, part, ar.tickets(), q64);
         }
-    }
-    if (fold) {      // inference: q = M_v h + c_v in one product
-        TRY(linear_plain(h, H, fold->m_v, H, fold->c_v, B, F, H, EPI_NONE, q, F, ar, st));
-        float* part = B <= 1024 ? ar.take(visual_attn_split_floats(B, F)) : nullptr;
-        return visual_attn(0, X, B, q, F, alpha, out, ldo, drop, col0, st, part,
-                           part ? ar.tickets() : nullptr);
     }
     TRY(linear_plain(h, H, w->w_h, H, w->b_h, B, D, H, EPI_NONE, t_v, D, ar, st));
     if (w->w_v_t)   // q = t_v W_v as a K-contiguous product against the transposed copy
@@ -435,18 +427,8 @@ int softdot_bwd_i(const sf_softdot_w* w, const sf_softdot_g* g, int B, int L, in
 // ---- a4 EltwiseProdScoring --------------------------------------------------------------------------
 int scoring_fwd_i(const sf_scoring_w* w, const CandSrc& U, int B, int H, int D, const float* h,
                   float* logit, float* t_a, float* wt, float* r, Arena ar, hipStream_t st,
-                  const sf_follower_glue* glue = nullptr, const sf_decoder_fold* fold = nullptr,
-                  bool t_a_done = false) {     // t_a / wt already formed by the caller (paired launch)
+                  const sf_follower_glue* glue = nullptr, bool t_a_done = false) {     // t_a / wt already formed by the caller (paired launch)
     const int F = U.IMG + U.LOC;
-    if (fold) {      // inference: [r | c] = M_a h~ + c_a in one product ([B, F+4] scratch)
-        float* rext = ar.take((size_t)B * (F + 4));
-        NEED(rext);
-        TRY(linear_plain(h, H, fold->m_a, H, fold->c_a, B, F + 4, H, EPI_NONE, rext, F + 4, ar, st));
-        if (glue)
-            return score_glue_fwd(U, B, D, rext, nullptr, nullptr, nullptr,
-                                  make_glue(U, B, logit, glue), st, F + 4, rext + F);
-        return score_fwd(U, B, D, rext, nullptr, nullptr, nullptr, logit, st, F + 4, rext + F);
-    }
     Seg sg{h, H, w->w_h, H, H};
     LinearOut o{};
     o.y = wt; o.ldy = D; o.bias = w->b_h; o.mul = w->w_out; o.y_pre = t_a; o.ldy_pre = D;
@@ -688,7 +670,6 @@ int sf_gate_product_bf16_supported(int M, int K1, int K2, int N) {
     const int K[2] = {K1, K2};
     return sf::bf16w_supported(M, N, K, K2 ? 2 : 1) ? 1 : 0;
 }
-void sf_debug_fold_chain3(int on) { g_fold_chain3 = on; }
 void sf_debug_precise_attention(int on) { sf::g_precise_attention = on; }
 void sf_debug_tn_split_min_rows(int rows) { sf::g_tn_split_min_rows = rows < 0 ? 4096 : rows; }
 size_t sf_workspace_fault_offset(size_t ws_bytes) {
@@ -796,7 +777,7 @@ int sf_visual_attention_fwd_f64(const sf_visual_w* w, const sf_pano* X, int B, i
         ar.rest_n() < (size_t)B * (D + F) * 2 + visual_attn_split_floats(B, F) + 256)
         return SF_ERR_UNSUPPORTED;
     return visual_fwd_i(w, src, B, H, D, h, out, ldo, alpha, t_v, q, make_dropout(drop, drop_stream), drop_col0, ar,
-                        S(stream), nullptr, true);
+                        S(stream), true);
 }
 
 int sf_linear_f64(const float* x, int ldx, const float* w, int ldw, const float* b, int M, int N, int K, double* y64,
@@ -884,7 +865,7 @@ static int decoder_head_a(const sf_decoder_w* w, const sf_pano* X, int B, int H,
     const PanoSrc xs = pano(X);
     const int F = xs.IMG + xs.LOC;
     return visual_fwd_i(&w->visual, xs, B, H, D, h0, tp->xin + F, 2 * F, tp->alpha_v, tp->t_v, tp->q,
-                        make_dropout(drop, 2 * step_id, 2), F, ar, S(stream), w->fold);
+                        make_dropout(drop, 2 * step_id, 2), F, ar, S(stream));
 }
 
 int sf_attn_decoder_head_fwd(const sf_decoder_w* w, const sf_pano* X, int B, int H, int D,
@@ -906,7 +887,6 @@ static int plan_linear(const float* x, int ldx, const float* wgt, int ldw, const
 struct TextFold {
     const float* ctx_q;
     const float* ctx_o;
-    const sf_decoder_fold* mats;      // optional (sf_follower_episode.chain_fold): the THREE-launch chain
 };
 
 // ---- tail(t): what every launch chain of the step reads (decoder_tail_i builds it behind the cell, tail_dispatch picks
@@ -950,46 +930,45 @@ static int vis_next_alone(const TailStep& s, float* part, const Arena& ar) {
                        part ? ar.tickets() : nullptr);
 }
 
-static int score_tail(const TailStep& s, const Arena& ar, const sf_decoder_fold* fold, bool t_a_done = false) {
+static int score_tail(const TailStep& s, const Arena& ar, bool t_a_done = false) {
     const sf_decoder_tape* tp = s.tp;
     return scoring_fwd_i(&s.w->action, s.us, s.B, s.H, s.D, tp->h_tilde, tp->logit, tp->t_a, tp->wt, tp->r, ar, s.st, s.glue,
-                         fold, t_a_done);
+                         t_a_done);
 }
 
 // scratch of the two folded chains
 struct FoldScratch {
-    float *tpart, *ybuf, *zbuf, *rext, *part;
+    float *tpart, *ybuf, *zbuf, *part;
     unsigned* tcount;
     int ldp;
     bool ok;         // everything was there, and B within the split attention's limit
 };
 // `af` is the chain's own COPY of the step's arena: a chain that declines hands the whole workspace to the next one
-// (B = 300 fits only because of this).  rext_n: the [r | c] rows of the three-launch chain (0: none).
-static FoldScratch fold_scratch(const TailStep& s, Arena& af, size_t rext_n) {
+// (B = 300 fits only because of this).
+static FoldScratch fold_scratch(const TailStep& s, Arena& af) {
     FoldScratch f{};
     f.tpart = af.take(text_fold_part_floats(s.B, s.H));
     // (leading dimension H + 16: rows of a power-of-two stride share a few cache sets, CHANGELOG round 5 "2c")
     f.ldp = s.H + 16;
     f.ybuf = af.take((size_t)s.B * f.ldp);
     f.zbuf = af.take((size_t)s.B * f.ldp);
-    f.rext = rext_n ? af.take(rext_n) : nullptr;
     f.tcount = af.tickets() ? af.tickets() + TEXT_TICKET : nullptr;
     f.part = (s.paired && s.B <= 1024) ? af.take(visual_attn_split_floats(s.B, s.F)) : nullptr;
-    f.ok = f.tpart && f.ybuf && f.zbuf && (f.rext || !rext_n) && (f.part || !s.paired) && f.tcount && s.B <= VIS_SPLIT_MAX_B;
+    f.ok = f.tpart && f.ybuf && f.zbuf && (f.part || !s.paired) && f.tcount && s.B <= VIS_SPLIT_MAX_B;
     return f;
 }
 
-// the last launch of a folded chain: logit = u . r (+ the folded constant, or the biases through wt) -- with the glue and
-// the merge of the next step's attention partials `merge_part` in the same launch, with the glue alone, or bare
-static int fold_score(const TailStep& s, float* merge_part, const float* r, int ldr, const float* cst, const float* wt) {
+// the last launch of the four-launch folded chain: logit = u . r + the biases through wt -- with the glue and the merge of
+// the next step's attention partials `merge_part` in the same launch, with the glue alone, or bare
+static int fold_score(const TailStep& s, float* merge_part) {
     const sf_scoring_w& a = s.w->action;
-    const float *b_a = wt ? a.b_a : nullptr, *b_out = wt ? a.b_out : nullptr;
+    const sf_decoder_tape* tp = s.tp;
     if (merge_part)
-        return pair_score_merge(s.us, s.B, s.D, r, wt, b_a, b_out, make_glue(s.us, s.B, s.tp->logit, s.glue), s.xn,
-                                s.tn->alpha_v, s.tn->xin + s.F, 2 * s.F, s.dn_in, s.F, merge_part, s.st, ldr, cst);
+        return pair_score_merge(s.us, s.B, s.D, tp->r, tp->wt, a.b_a, a.b_out, make_glue(s.us, s.B, tp->logit, s.glue), s.xn,
+                                s.tn->alpha_v, s.tn->xin + s.F, 2 * s.F, s.dn_in, s.F, merge_part, s.st);
     if (s.glue)
-        return score_glue_fwd(s.us, s.B, s.D, r, wt, b_a, b_out, make_glue(s.us, s.B, s.tp->logit, s.glue), s.st, ldr, cst);
-    return score_fwd(s.us, s.B, s.D, r, wt, b_a, b_out, s.tp->logit, s.st, ldr, cst);
+        return score_glue_fwd(s.us, s.B, s.D, tp->r, tp->wt, a.b_a, a.b_out, make_glue(s.us, s.B, tp->logit, s.glue), s.st);
+    return score_fwd(s.us, s.B, s.D, tp->r, tp->wt, a.b_a, a.b_out, tp->logit, s.st);
 }
 
 // Projected chain (inference; tables of sf_projected_build registered for the step's feature table and decoder): TWO
@@ -1026,7 +1005,7 @@ static int tail_proj(const TailStep& s, const TextFold& tf) {
         !projected_for(s.w, s.us, s.paired ? &s.xn : nullptr, B, H, s.L, &pt))
         return SF_ERR_UNSUPPORTED;
     Arena af = s.ar;
-    const FoldScratch f = fold_scratch(s, af, 0);
+    const FoldScratch f = fold_scratch(s, af);
     SmallPlan py;
     const bool ok = f.ok &&
         plan_linear(tp->cat2 + H, 2 * H, s.w->text.w_out + H, 2 * H, nullptr, B, H, H, EPI_NONE, f.ybuf, f.ldp, &py) == SF_OK &&
@@ -1040,43 +1019,6 @@ static int tail_proj(const TailStep& s, const TextFold& tf) {
     return issued(pair_proj_score(s.us, B, H, s.L, pt, f.zbuf, f.ldp, f.ybuf, f.ldp, make_glue(s.us, B, tp->logit, s.glue),
                                   s.paired ? &s.xn : nullptr, late ? 0 : 2, tp->h1, H, s.paired ? tn->alpha_v : nullptr,
                                   s.paired ? tn->xin + F : nullptr, 2 * F, s.dn_in, F, f.part, af.tickets(), s.st));
-}
-
-// Folded text stage + folded query / scoring products (sf_decoder_fold through sf_follower_episode.chain_fold):
-// THREE dependent launches behind the cell --
-//   (1) folded text attention  ||  y = W_out[:, H:] h1  ||  q' = M_v h1 + c_v      (t_v' is never formed)
-//   (2) [r | c] = M_a tanh(z + y) + c_a (A-prologue)   ||  visual-attention partials of step t+1
-//   (3) scoring + glue (logit = u . r + c)             ||  merge of the partials
-// (a device-resident environment: (2) is the product alone, the attention follows the environment step)
-static int tail_fold3(const TailStep& s, const TextFold& tf) {
-    const sf_decoder_fold* fm = tf.mats;
-    const sf_decoder_tape *tp = s.tp, *tn = s.tn;
-    const int B = s.B, H = s.H, F = s.F;
-    // ---- plan
-    Arena af = s.ar;
-    const FoldScratch f = fold_scratch(s, af, (size_t)B * (F + 4));
-    SmallPlan py, pq, pm;
-    bool ok = f.ok && fm->m_v && fm->c_v && fm->m_a && fm->c_a &&
-              plan_linear(tp->cat2 + H, 2 * H, s.w->text.w_out + H, 2 * H, nullptr, B, H, H, EPI_NONE, f.ybuf, f.ldp, &py) == SF_OK;
-    if (ok && !s.last_step) ok = plan_linear(tp->h1, H, fm->m_v, H, fm->c_v, B, F, H, EPI_NONE, tn->q, F, &pq) == SF_OK;
-    else if (ok) pq = empty_plan(py);
-    if (ok) {
-        Seg sg{f.ybuf, f.ldp, fm->m_a, H, H};
-        LinearOut o{};
-        o.y = f.rext; o.ldy = F + 4; o.bias = fm->c_a; o.epi = EPI_NONE;
-        ok = linear_small_plan(&sg, 1, B, F + 4, o, &pm) && pair_vis_apro_accepts(pm.inst()) &&
-             pair_textfold_small_small_accepts(py.inst(), pq.inst());
-        pm.args.apro_part = f.zbuf;
-        pm.args.apro_stride = f.ldp;
-    }
-    if (!ok) return SF_ERR_UNSUPPORTED;          // (shapes outside the instantiations: the four-launch chain)
-    // ---- issue (the first launch checks its shapes before it launches: it may still decline)
-    TRY(pair_textfold_small_small(tf.ctx_q, tf.ctx_o, s.ctx_mask, B, s.L, H, tp->cat2 + H, 2 * H, f.tpart, f.tcount, f.zbuf,
-                                  f.ldp, tp->alpha, py, pq, s.st));
-    TRY(issued(pair_vis_apro(s.paired ? &s.xn : nullptr, B, s.paired ? tn->q : nullptr, F, f.part, pm, s.st)));
-    if (s.paired && !s.glue)                     // (no glue: the module-API step; merge by its own launch)
-        TRY(issued(vis_next_beside(s, f.part, nullptr, empty_plan(py), 2)));
-    return issued(fold_score(s, s.paired && s.glue ? f.part : nullptr, f.rext, F + 4, f.rext + F, nullptr));
 }
 
 // Folded text stage (inference; sf_attention.hip: text_fold_body): FOUR dependent launches behind the cell
@@ -1094,7 +1036,7 @@ static int tail_fold4(const TailStep& s, const TextFold& tf) {
     const int B = s.B, H = s.H, D = s.D, F = s.F;
     // ---- plan
     Arena af = s.ar;
-    const FoldScratch f = fold_scratch(s, af, 0);
+    const FoldScratch f = fold_scratch(s, af);
     SmallPlan py, pv, pta, pq, pr;
     bool ok = f.ok &&
         plan_linear(tp->cat2 + H, 2 * H, s.w->text.w_out + H, 2 * H, nullptr, B, H, H, EPI_NONE, f.ybuf, f.ldp, &py) == SF_OK &&
@@ -1129,51 +1071,7 @@ static int tail_fold4(const TailStep& s, const TextFold& tf) {
     if (merge_late) TRY(issued(vis_next_beside(s, f.part, nullptr, pr, 1)));
     else if (s.paired) TRY(issued(vis_next_beside(s, f.part, af.tickets(), pr, 0)));
     else TRY(issued(launch_small_plan(pr, s.st)));
-    return issued(fold_score(s, merge_late ? f.part : nullptr, tp->r, 0, nullptr, tp->wt));
-}
-
-// Folded inference step (sf_decoder_fold): two dependent stages fewer, and the attention
-// partials of step t+1 ride beside the text attention (the longest small stage) instead of
-// stretching the h~ product:
-//   (1) t_text = W_in h1                  ||  q' = M_v h1 + c_v
-//   (2) text attention                    ||  visual-attention partials of step t+1
-//   (3) h~ = tanh(W_out [wc ; h1])        ||  merge of the partials
-//   (4) [r | c] = M_a h~ + c_a            (5) scoring + glue
-// (never declines: a stage whose paired launch has no instantiation is issued as its plain launches)
-static int tail_decoder_fold(const TailStep& s) {
-    const sf_softdot_w* tw = &s.w->text;
-    const sf_decoder_fold* fm = s.w->fold;
-    const sf_decoder_tape *tp = s.tp, *tn = s.tn;
-    const int B = s.B, H = s.H, L = s.L, F = s.F;
-    // ---- plan (stage (1) keeps the whole arena, the later ones what the partials leave)
-    Arena ar = s.ar;
-    SmallPlan pa, pb, ph;
-    const bool ok1 =
-        plan_linear(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, &pa) == SF_OK &&
-        plan_linear(tp->h1, H, fm->m_v, H, fm->c_v, B, F, H, EPI_NONE, tn->q, F, &pb) == SF_OK;
-    float* part = B <= 1024 ? ar.take(visual_attn_split_floats(B, F)) : nullptr;
-    const bool ok3 = part && plan_linear(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H, EPI_TANH,
-                                         tp->h_tilde, H, &ph) == SF_OK;
-    // ---- issue
-    if (!ok1 || pair_small_small(pa, pb, s.st) != SF_OK) {
-        TRY(linear_plain(tp->cat2 + H, 2 * H, tw->w_in, H, nullptr, B, H, H, EPI_NONE, tp->t_text, H, s.ar, s.st));
-        TRY(linear_plain(tp->h1, H, fm->m_v, H, fm->c_v, B, F, H, EPI_NONE, tn->q, F, s.ar, s.st));
-    }
-    bool split = false;
-    if (ok3) {
-        const int rc = pair_vis_text(s.xn, B, tn->q, F, tn->alpha_v, tn->xin + F, 2 * F, s.dn_in, F, part, s.ctx,
-                                     s.ctx_mask, L, H, tp->t_text, H, tp->alpha, tp->cat2, 2 * H, s.ctx_row, s.st);
-        if (rc == SF_OK) split = true;
-        else if (rc != SF_ERR_UNSUPPORTED) return rc;
-    }
-    if (split && vis_next_beside(s, part, nullptr, ph, 2) != SF_OK)
-        return SF_ERR_LAUNCH;            // the partials exist: the merge must not be skipped
-    if (!split) {
-        TRY(text_attn_fwd(s.ctx, s.ctx_mask, B, L, H, tp->t_text, H, tp->alpha, tp->cat2, 2 * H, s.st, s.ctx_row));
-        TRY(linear_plain(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H, EPI_TANH, tp->h_tilde, H, ar, s.st));
-        TRY(vis_next_alone(s, part, ar));
-    }
-    return score_tail(s, ar, fm);
+    return issued(fold_score(s, merge_late ? f.part : nullptr));
 }
 
 // Stages (1) and (2) of the unfolded chains, each as one paired launch or -- where that has no instantiation -- as its
@@ -1231,13 +1129,13 @@ static int tail_paired(const TailStep& s) {
     TRY(text_and_query(s));
     if (ok4 && vis_next_beside(s, part, nullptr, ph, 1) == SF_OK) {
         TRY(vis_next_beside(s, part, nullptr, pc, 2));
-        return score_tail(s, ar, nullptr, true);
+        return score_tail(s, ar, true);
     }
     if (!ok3 || vis_next_beside(s, part, ar.tickets(), ph) != SF_OK) {
         TRY(linear_plain(tp->cat2, 2 * H, tw->w_out, 2 * H, nullptr, B, H, 2 * H, EPI_TANH, tp->h_tilde, H, ar, s.st));
         TRY(vis_next_alone(s, part, ar));
     }
-    return score_tail(s, ar, nullptr);
+    return score_tail(s, ar);
 }
 
 // tape_next WITHOUT X_next: the next panorama is not known yet (it depends on this step's action: a
@@ -1249,7 +1147,7 @@ static int tail_query_only(const TailStep& s) {
     TRY(text_and_query(s));
     TRY(linear_plain(tp->cat2, 2 * s.H, s.w->text.w_out, 2 * s.H, nullptr, s.B, s.H, 2 * s.H, EPI_TANH, tp->h_tilde, s.H,
                      s.ar, s.st));
-    return score_tail(s, s.ar, nullptr);
+    return score_tail(s, s.ar);
 }
 
 // The plain step: text attention and scoring, and -- with a next panorama but no transposed W_v to pair its query
@@ -1260,21 +1158,18 @@ static int tail_plain(const TailStep& s) {
                       tp->t_text, s.ar, s.st, s.ctx_row));
     if (s.has_xn)
         TRY(visual_fwd_i(&s.w->visual, s.xn, s.B, s.H, s.D, tp->h1, tn->xin + s.F, 2 * s.F, tn->alpha_v, tn->t_v, tn->q,
-                         s.dn_in, s.F, s.ar, s.st, s.w->fold));
-    return score_tail(s, s.ar, s.w->fold);
+                         s.dn_in, s.F, s.ar, s.st));
+    return score_tail(s, s.ar);
 }
 
 // The order of preference.  The folded chains (inference: no dropout of h1, no row indirection of the context, the
 // episode's TextFold) may decline -- before their first launch, see TailStep -- and hand the step to the next one.
 static int tail_dispatch(const TailStep& s, const TextFold* tf) {
-    const bool foldable = (s.paired || s.query_only || s.last_step) && tf && !s.w->fold && !s.ctx_row && !s.d_h.on() &&
-                          s.w->text.w_out;
+    const bool foldable = (s.paired || s.query_only || s.last_step) && tf && !s.ctx_row && !s.d_h.on() && s.w->text.w_out;
     int rc = SF_ERR_UNSUPPORTED;
     if (foldable) rc = tail_proj(s, *tf);
-    if (rc == SF_ERR_UNSUPPORTED && foldable && tf->mats && g_fold_chain3) rc = tail_fold3(s, *tf);
     if (rc == SF_ERR_UNSUPPORTED && foldable && s.w->action.w_a_t) rc = tail_fold4(s, *tf);
     if (rc != SF_ERR_UNSUPPORTED) return rc;
-    if (s.paired && s.w->fold) return tail_decoder_fold(s);
     if (s.paired) return tail_paired(s);
     if (s.query_only) return tail_query_only(s);
     return tail_plain(s);
@@ -1298,8 +1193,8 @@ static int decoder_tail_i(const sf_decoder_w* w, const sf_cands* U, int B, int H
     s.dn_in = make_dropout(drop, 2 * (step_id + 1), 2);
     s.has_xn = X_next != nullptr;
     if (X_next) s.xn = pano(X_next);
-    s.paired = X_next && w->visual.w_v_t;      // (a scoring fold, if any, is applied by scoring_fwd_i)
-    s.query_only = !X_next && tn && w->visual.w_v_t && !w->fold;      // (tail_query_only)
+    s.paired = X_next && w->visual.w_v_t;
+    s.query_only = !X_next && tn && w->visual.w_v_t;      // (tail_query_only)
     s.last_step = !X_next && !tn;              // (nothing of a next step to prepare: the text chain alone)
     const Dropout d_in = make_dropout(drop, 2 * step_id, 2);
     if (u_prev) TRY(dropout_copy(u_prev, s.F, B, s.F, tp->xin, 2 * s.F, d_in, 0, s.st));
@@ -1326,8 +1221,7 @@ static int decoder_tail_split_i(const sf_decoder_w* w, const sf_cands* U, int B,
     if (flag_h1) TRY(flag_set(flag_h1, flag_value, st));
     TRY(softdot_fwd_i(&w->text, B, L, H, nullptr, 0, ctx, ctx_mask, tp->h_tilde, tp->alpha, tp->cat2, tp->t_text,
                       ar, st, nullptr));
-    return scoring_fwd_i(&w->action, us, B, H, D, tp->h_tilde, tp->logit, tp->t_a, tp->wt, tp->r, ar, st, glue,
-                         nullptr);
+    return scoring_fwd_i(&w->action, us, B, H, D, tp->h_tilde, tp->logit, tp->t_a, tp->wt, tp->r, ar, st, glue);
 }
 
 int sf_attn_decoder_attend_fwd(const sf_pano* X, int B, const sf_decoder_tape* tp, const sf_dropout* drop,
@@ -1636,9 +1530,9 @@ int sf_follower_episode_fwd(const sf_decoder_w* w, const sf_follower_episode* e,
     const sf_dropout* drop = e->drop.p > 0.f ? &e->drop : nullptr;
     StepView cur = step_view(e, 0);
     // the folded text attention (ABI 9): ctx_q = ctx W_in, ctx_o = ctx W_out[:, :H]^T, once per episode
-    TextFold tfold{e->ctx_q, e->ctx_o, e->chain_fold};
+    TextFold tfold{e->ctx_q, e->ctx_o};
     const TextFold* tf = nullptr;
-    if (e->ctx_q && e->ctx_o && !drop && !w->fold && e->S > 1 && w->text.w_in_t && w->text.w_out && w->action.w_a_t) {
+    if (e->ctx_q && e->ctx_o && !drop && e->S > 1 && w->text.w_in_t && w->text.w_out && w->action.w_a_t) {
         const int M = e->B * e->L, H = e->H;
         const Arena ar = arena(ws, ws_bytes);
         TRY(linear_plain(e->ctx, H, w->text.w_in_t, H, nullptr, M, H, H, EPI_NONE, e->ctx_q, H, ar, S(stream)));
@@ -1671,8 +1565,8 @@ int sf_follower_episode_fwd(const sf_decoder_w* w, const sf_follower_episode* e,
     // (tape_next without X_next), and the attention follows as its own launch -- the schedule the host loop of
     // FollowerEngine.rollout issues call by call, here without host work between the launches.
     const sf_nav_io* nav0 = e->glue.nav;
-    if (nav0) SF_CHECK_ARG(!w->fold && w->visual.w_v_t);
-    if (!nav0 && e->side_stream && e->side_stream != stream && !w->fold && e->S > 1 && !tf) {
+    if (nav0) SF_CHECK_ARG(w->visual.w_v_t);
+    if (!nav0 && e->side_stream && e->side_stream != stream && e->S > 1 && !tf) {
         // Two chains, ONE fork and ONE join per episode, ordered per step by device flags
         // (flag_wait / flag_set kernels) instead of events:
         //   main:  [wait feat(t)] gate product, cell, [set h1(t)], t_text, text attention, h~, scoring + glue
@@ -1729,30 +1623,16 @@ int sf_follower_episode_bwd(const sf_decoder_w* w, const sf_follower_episode* e,
                             const sf_decoder_gtape* gtape, const float* gscale, float* dlogit,
                             float* dh_a, float* dc_a, float* dh_b, float* dc_b, float* dctx,
                             int* result_in_b, void* ws, size_t ws_bytes, sf_stream stream) {
-    return sf_follower_episode_bwd_range(w, e, gtape, gscale, dlogit, dh_a, dc_a, dh_b, dc_b, dctx, result_in_b,
-                                         0, e ? e->S : 0, nullptr, nullptr, ws, ws_bytes, stream);
-}
-
-int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episode* e,
-                                  const sf_decoder_gtape* gtape, const float* gscale, float* dlogit,
-                                  float* dh_a, float* dc_a, float* dh_b, float* dc_b, float* dctx,
-                                  int* result_in_b, int t_lo, int t_hi, const float* dh_in, const float* dc_in,
-                                  void* ws, size_t ws_bytes, sf_stream stream) {
     SF_ENTER();
     SF_CHECK_ARG(w && e && gtape && gscale && dlogit && dh_a && dc_a && dh_b && dc_b && result_in_b &&
-                 e->S > 0 && e->B > 0 && 0 <= t_lo && t_lo < t_hi && t_hi <= e->S &&
-                 (t_hi == e->S || (dh_in && dc_in)) && (!dh_in) == (!dc_in));
+                 e->S > 0 && e->B > 0);
     const sf_dropout* drop = e->drop.p > 0.f ? &e->drop : nullptr;
     sf_decoder_gtape gt_all = *gtape;          // the deferred context gradient only where it is covered
     if (!(gt_all.dcat2 && gt_all.ds && dctx && ctx_grad_supported(e->S, e->L, e->H)))
         gt_all.dcat2 = gt_all.ds = nullptr;
     gtape = &gt_all;
-    const float *dh1 = dh_in, *dc1 = dc_in;           // gradient arriving from step t_hi (null: the last step)
+    const float *dh1 = nullptr, *dc1 = nullptr;       // gradient arriving from the step behind (null: the last step)
     float *dho = dh_a, *dco = dc_a, *dhn = dh_b, *dcn = dc_b;
-    if (dh_in == dh_a) {                              // a chained call: the first output must not be its own input
-        std::swap(dho, dhn);
-        std::swap(dco, dcn);
-    }
     // Software-pipelined over two streams when the caller gives a side stream and per-step dh1d
     // storage: the heads (scoring / text-attention backward, ~45 us of small dependent launches per
     // step) run ahead on the side stream, the tails (LSTM / visual backward, ~65 us) follow on the main
@@ -1774,16 +1654,15 @@ int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episo
         // two disjoint regions of the one workspace; both keep the real ticket region
         Arena tail_ar{(float*)ws, usable - head_n, 0, whole.tk};
         Arena head_ar{(float*)ws + (usable - head_n), head_n, 0, whole.tk};
-        // (only the first chunk orders the side stream behind the caller's stream -- the forward pass; the heads
-        // of a later chunk need nothing from the tails of the chunk before it and keep running ahead)
-        if (t_hi == e->S) TRY(order_behind(side_st, main_st, ev[e->S]));
+        // (the side stream behind the caller's stream: the forward pass)
+        TRY(order_behind(side_st, main_st, ev[e->S]));
         // ALL heads are issued first (they depend on nothing the tails produce), each followed by
         // its event; then the tails, each behind the event of its head.  (Measured on MI355X: work of
         // two queues overlaps only where a kernel leaves CUs unoccupied -- tools/overlap_probe.py: an
         // 0.73 ms chain of recurrent steps beside 0.87 ms of gate products takes 1.35 ms, beside
         // chip-filling library GEMMs the plain sum, stream priority changes nothing -- so the gain of
         // the second stream is the small kernels of the heads filling the gaps of the tails.)
-        for (int t = t_hi - 1; t >= t_lo; --t) {
+        for (int t = e->S - 1; t >= 0; --t) {
             StepView v = step_view(e, t);
             const sf_decoder_gtape g = gtape_view(gtape, e, t);
             const CeSrc ce{v.tp.logit, v.glue.target_used, gscale + t, -1, (int)e->A};
@@ -1795,7 +1674,7 @@ int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episo
         // experiments"): heads alone 0.93 ms, tails alone 1.14 ms, both chains in one graph 1.46 ms, as two graphs on two
         // streams 1.43 ms -- they overlap either way.
         // (rocprofv3 --kernel-trace serialises the queues: its timelines show every head before the first tail.)
-        for (int t = t_hi - 1; t >= t_lo; --t) {
+        for (int t = e->S - 1; t >= 0; --t) {
             StepView v = step_view(e, t);
             const sf_decoder_gtape g = gtape_view(gtape, e, t);
             const StepState in = state_in(e, t);
@@ -1808,7 +1687,7 @@ int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episo
             std::swap(dco, dcn);
         }
     } else {
-        for (int t = t_hi - 1; t >= t_lo; --t) {
+        for (int t = e->S - 1; t >= 0; --t) {
             StepView v = step_view(e, t);
             const sf_decoder_gtape g = gtape_view(gtape, e, t);
             const StepState in = state_in(e, t);
@@ -1825,7 +1704,7 @@ int sf_follower_episode_bwd_range(const sf_decoder_w* w, const sf_follower_episo
         }
     }
     *result_in_b = (dh1 == dh_b) ? 1 : 0;
-    if (gtape->dcat2 && gtape->ds && dctx && t_lo == 0)     // the deferred context gradient, once for the episode
+    if (gtape->dcat2 && gtape->ds && dctx)     // the deferred context gradient, once for the episode
         TRY(ctx_grad_accum(e->tape.alpha, gtape->ds, gtape->dcat2, 2 * e->H, e->tape.t_text, e->S, e->B,
                            e->L, e->H, dctx, S(stream)));
     return SF_OK;
@@ -2470,7 +2349,7 @@ static int speaker_encoder_fwd_i(const sf_visual_fold64* fold64, const sf_visual
         // (float64 query and scores: see visual_fwd_i / csrc/sf_precise.hip; sf_debug_precise_attention(0) = fp32)
         TRY(visual_fwd_i(vw, pano(&X), B, H, D, hs + t * BH, x_t + F, 2 * F, alpha + (size_t)t * B * V,
                          t_v + (size_t)t * B * D, q + (size_t)t * B * F, make_dropout(drop, 2 * (step0 + t), 2), F,
-                         arena(ws, ws_bytes), S(stream), nullptr, g_precise_attention != 0, fold64));
+                         arena(ws, ws_bytes), S(stream), g_precise_attention != 0, fold64));
         if (act_emb)
             TRY(dropout_copy(act_emb + (size_t)t * B * F, F, B, F, x_t, 2 * F, make_dropout(drop, 2 * (step0 + t), 2), 0,
                              S(stream)));

@@ -998,21 +998,8 @@ __global__ __launch_bounds__(TXT_NW * 64) void pair_small_text_kernel(SmallArgs 
     }
 }
 
-// Folded inference step (sf_decoder_fold): the attention partials of step t+1 ride beside the TEXT
-// attention of step t.  512-thread blocks: the attention body needs its 163 registers per lane, so the
-// text body runs with 8 waves x RPW context rows (L <= 8 RPW) instead of 16 x RPW/2.
-template <int RPW, bool H16 = false>
-__global__ __launch_bounds__(SMALL_WAVES * 64) void pair_vis_text_kernel(VisArgs v, VisSplit sp, int nv,
-                                                                        TxtArgs t) {
-    const int bid = blockIdx.x;
-    if (bid < nv) {
-        if (threadIdx.x >= VSP_NW * 64) return;
-        visual_split_body<1, false, H16>(v, sp, bid % VSP_G, bid / VSP_G);
-    } else {
-        text_attn_body<RPW, 0, SMALL_WAVES>(t, bid - nv);
-    }
-}
-
+// (APRO is false in every instantiation since the three-launch folded chain went; the parameter stays because it is part
+//  of the surviving kernels' symbol names -- DESIGN.md, "Retired experiments", follow-up)
 template <int MT, int CPW, int PHASE, bool APRO = false, bool H16 = false>
 __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_vis_small_kernel(VisArgs v, VisSplit sp,
                                                                          int nv, SmallArgs b,
@@ -1352,19 +1339,6 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_textfold_small_small_ke
         small_gemm_body<1, 4>(b, (bid - nt - na) % gxb, (bid - nt - na) / gxb);
 }
 
-// ... the same with the next step's visual query as ONE folded product q' = M_v h1 + c_v (sf_decoder_fold) for third body
-template <int RPW, int MTB>
-__global__ __launch_bounds__(SMALL_WAVES * 64) void pair_textfold_small_wide_kernel(TxtFoldArgs t, int nt, SmallArgs a,
-                                                                                   int gxa, int na, SmallArgs b, int gxb) {
-    const int bid = blockIdx.x;
-    if (bid < nt)
-        text_fold_body<RPW, TXF_G>(t, bid % TXF_G, bid / TXF_G);
-    else if (bid < nt + na)
-        small_gemm_body<1, 4>(a, (bid - nt) % gxa, (bid - nt) / gxa);
-    else
-        small_gemm_body<MTB, 4>(b, (bid - nt - na) % gxb, (bid - nt - na) / gxb);
-}
-
 // launch (1) of the projected chain: [projected attention partials of step t + 1 | text_fold groups | y = W_out[:, H:] h1]
 // (the partials blocks pull the most bytes: first in the grid; proj_partials_body keeps the kernel within 128 registers,
 // two workgroups per CU).  VIS false: the instantiation without the partials body (nv == 0: an episode's last step, or
@@ -1543,22 +1517,19 @@ int ctx_grad_accum(const float* alpha, const float* ds, const float* dcat2, int 
 }
 
 int score_fwd(const CandSrc& src, int B, int D, const float* r, const float* wt, const float* b_a,
-              const float* b_out, float* logit, hipStream_t st, int ldr, const float* cst) {
-    if (ldr <= 0) ldr = src.IMG + src.LOC;
+              const float* b_out, float* logit, hipStream_t st) {
     if (!cand_rows_fit(shape(src))) return SF_ERR_UNSUPPORTED;
     if (half_misuse(src)) return SF_ERR_ARG;
-    ScoreArgs a{src, ldr, cst, r, wt, b_a, b_out, D, logit, nullptr, nullptr, CeSrc{}};
+    ScoreArgs a{src, src.IMG + src.LOC, nullptr, r, wt, b_a, b_out, D, logit, nullptr, nullptr, CeSrc{}};
     SF_LAUNCH_H16_AS(src.half, "score_fwd_kernel", score_fwd_kernel, dim3(B), dim3(SC_NW * 64), 0, st, a);
     return launch_status();
 }
 
 int score_glue_fwd(const CandSrc& src, int B, int D, const float* r, const float* wt,
-                   const float* b_a, const float* b_out, const FGlue& g, hipStream_t st, int ldr,
-                   const float* cst) {
-    if (ldr <= 0) ldr = src.IMG + src.LOC;
+                   const float* b_a, const float* b_out, const FGlue& g, hipStream_t st) {
     if (!cand_rows_fit(shape(src))) return SF_ERR_UNSUPPORTED;
     if (half_misuse(src)) return SF_ERR_ARG;
-    ScoreArgs a{src, ldr, cst, r, wt, b_a, b_out, D, g.logit, nullptr, nullptr, CeSrc{}};
+    ScoreArgs a{src, src.IMG + src.LOC, nullptr, r, wt, b_a, b_out, D, g.logit, nullptr, nullptr, CeSrc{}};
     SF_LAUNCH_H16_AS(src.half, "score_glue_kernel", score_glue_kernel, dim3(B), dim3(SC_NW * 64), 0, st, a, g);
     return launch_status();
 }
@@ -1566,12 +1537,11 @@ int score_glue_fwd(const CandSrc& src, int B, int D, const float* r, const float
 // score_glue_fwd beside the phase-2 merge of visual-attention partials written by an earlier phase-1 launch
 int pair_score_merge(const CandSrc& src, int B, int D, const float* r, const float* wt, const float* b_a,
                      const float* b_out, const FGlue& g, const PanoSrc& psrc, float* alpha, float* out, int ldo,
-                     const Dropout& drop, int drop_col0, float* split_part, hipStream_t st, int ldr, const float* cst) {
-    if (ldr <= 0) ldr = src.IMG + src.LOC;
+                     const Dropout& drop, int drop_col0, float* split_part, hipStream_t st) {
     if (!cand_rows_fit(shape(src))) return SF_ERR_UNSUPPORTED;
     if (!split_part || !in_split_range(psrc.V, B) || !aligned4(ldo)) return SF_ERR_UNSUPPORTED;
     if (half_misuse(src) || half_misuse(psrc)) return SF_ERR_ARG;
-    ScoreArgs a{src, ldr, cst, r, wt, b_a, b_out, D, g.logit, nullptr, nullptr, CeSrc{}};
+    ScoreArgs a{src, src.IMG + src.LOC, nullptr, r, wt, b_a, b_out, D, g.logit, nullptr, nullptr, CeSrc{}};
     VisArgs va{psrc, nullptr, 0, alpha, out, ldo, drop, drop_col0};
     const VisSplit sp{split_part, nullptr, g_trace};
     SF_LAUNCH_H16_AS(src.half, "pair_score_merge_kernel", pair_score_merge_kernel, dim3(2 * B), dim3(SC_NW * 64), 0, st, a,
@@ -1613,13 +1583,7 @@ int pair_textfold_small_small(const float* ctx_q, const float* ctx_o, const uint
     const dim3 grid(nt + na + nb), block(SMALL_WAVES * 64);
     return launched(with_index(fold_rpw(L, TXF_G), [&](auto r) {
         constexpr int R = decltype(r)::value;
-        if (b.mt == 1)
-            SF_LAUNCH_INST(pair_textfold_small_small_kernel, (R), grid, block, 0, st, ta, nt, a.args, a.gx, na, b.args, b.gx);
-        else                                          // (the folded visual query: N = F columns)
-            with_index(b.mt, [&](auto m) {
-                SF_LAUNCH_INST(pair_textfold_small_wide_kernel, (R, decltype(m)::value), grid, block, 0, st, ta, nt, a.args, a.gx,
-                               na, b.args, b.gx);
-            }, ints<2, 4>{});
+        SF_LAUNCH_INST(pair_textfold_small_small_kernel, (R), grid, block, 0, st, ta, nt, a.args, a.gx, na, b.args, b.gx);
     }, ints<1, 2, 3, 5>{}));
 }
 
@@ -1632,24 +1596,6 @@ int pair_apro_small(const SmallPlan& a, const SmallPlan& b, hipStream_t st) {
     return launched(with_index(b.mt, [&](auto m) {
         SF_LAUNCH_INST(pair_apro_small_kernel, (decltype(m)::value), grid, block, 0, st, a.args, a.gx, na, b.args, b.gx);
     }, ints<1, 2, 4>{}));
-}
-
-// visual-attention partials (phase 1 of the split attention) beside the text attention
-int pair_vis_text(const PanoSrc& src, int B, const float* vec, int ldvec, float* alpha, float* out, int ldo,
-                  const Dropout& drop, int drop_col0, float* split_part, const float* ctx, const uint8_t* mask,
-                  int L, int H, const float* t, int ldt, float* talpha, float* wc, int ldwc,
-                  const int32_t* ctx_row, hipStream_t st) {
-    if (!split_part || !split_rows_fit(shape(src), B) || !aligned4(ldvec, ldo)) return SF_ERR_UNSUPPORTED;
-    if (!text_rows_fit(L, PVT_MAX_L, H, ldt | ldwc)) return SF_ERR_UNSUPPORTED;
-    if (half_misuse(src)) return SF_ERR_ARG;
-    VisArgs va{src, vec, ldvec, alpha, out, ldo, drop, drop_col0};
-    const VisSplit sp{split_part, nullptr, g_trace};
-    TxtArgs ta{ctx, mask, L, H, t, ldt, nullptr, 0, talpha, wc, ldwc, nullptr, ctx_row, nullptr};
-    const int nv = VSP_G * B;
-    const dim3 grid(nv + B), block(SMALL_WAVES * 64);
-    return launched(with_index(vis_text_rpw(L), [&](auto r) {
-        SF_LAUNCH_INST_H16(src.half, pair_vis_text_kernel, (decltype(r)::value), grid, block, 0, st, va, sp, nv, ta);
-    }, ints<2, 5, 10>{}));
 }
 
 int pair_small_text(const SmallPlan& a, const float* ctx, const uint8_t* mask, int B, int L, int H,
@@ -1677,28 +1623,6 @@ int pair_visbwd_small(const PanoSrc& src, int B, const float* vec, int ldvec, fl
     const int nb = b.gx * b.gy;
     SF_LAUNCH_INST_H16(src.half, pair_visbwd_small_kernel, (1, 16), dim3(B + nb), dim3(VIS_NW * 64), 0, st, va, B, b.args, b.gx);
     return launch_status();
-}
-
-// the folded scoring product [r | c] = M_a tanh(z + y) + c_a (A-prologue; b.args.apro_part set) beside the phase-1
-// partials of the visual attention -- or alone (`src` null: a device-resident environment, an episode's last step)
-int pair_vis_apro(const PanoSrc* src, int B, const float* vec, int ldvec, float* split_part, const SmallPlan& b,
-                  hipStream_t st) {
-    if (!pair_vis_apro_accepts(b.inst()) || !b.args.apro_part || b.args.sg.total != b.args.sg.n0) return SF_ERR_UNSUPPORTED;
-    int nv = 0;
-    VisArgs va{};
-    if (src) {
-        if (!split_part || !split_rows_fit(shape(*src), B) || !aligned4(ldvec)) return SF_ERR_UNSUPPORTED;
-        if (half_misuse(*src)) return SF_ERR_ARG;
-        va = VisArgs{*src, vec, ldvec, nullptr, nullptr, 0, Dropout{}, 0};
-        nv = VSP_G * B;
-    }
-    const VisSplit sp{split_part, nullptr, g_trace};
-    const int nb = b.gx * b.gy;
-    const dim3 grid(nv + nb), block(SMALL_WAVES * 64);
-    const int h16 = src ? src->half : 0;
-    return launched(with_index(b.mt, [&](auto m) {
-        SF_LAUNCH_INST_H16(h16, pair_vis_small_kernel, (decltype(m)::value, 4, 1, true), grid, block, 0, st, va, sp, nv, b.args, b.gx);
-    }, ints<1, 2, 4>{}));
 }
 
 // ---- the projected decode chain (sf_api.hip: tail_proj).  proj_chain_supported is the PLAN: both launchers below check

@@ -20,7 +20,7 @@ constexpr int VSP_G = SF_VIS_GROUPS;                   // split visual attention
 constexpr int VSP_NW = VIS_NW / VSP_G, VSP_RPG = VSP_NW * VIS_RPW, VSP_SLOTS = VSP_NW < 3 ? VSP_NW : 3;
 static_assert(VSP_G == 2 || VSP_G == 4, "ticket arithmetic assumes a power of two");
 // Largest batch of the split visual attention (per-sample ticket counters) and of the schedules built around it: the
-// paired / folded decode steps and the two-stream backward through time (sf_follower_episode_bwd_range).  Above it the
+// paired / folded decode steps and the two-stream backward through time (sf_follower_episode_bwd).  Above it the
 // un-split kernels run and those schedules fall back to one launch at a time on one stream.
 constexpr int VIS_SPLIT_MAX_B = 256;
 constexpr int PRJ_CPL = 2;                             // float4 per lane of a projected row: H <= 512
@@ -32,7 +32,6 @@ constexpr int SC_CPL = 9, SC_NW = 16, SC_SLOTS = 4;    // scoring
 constexpr int TXF_G = 4;          // folded text: workgroups per sample; tickets a LAUNCH adds per sample (they count in fours)
 constexpr int TXF_MAX_L = TXF_G * SMALL_WAVES * 5, TXF_MAX_B = 512;
 constexpr int TXF_G2_MAX_L = 2 * SMALL_WAVES * 5;      // ... in two groups (proj_text_groups_plan)
-constexpr int PVT_MAX_L = SMALL_WAVES * 10;            // text attention beside the visual partials (pair_vis_text)
 constexpr int CG_ROWS = 10;                            // ctx_grad_kernel: rows per thread, L <= 8 * CG_ROWS
 static_assert(SC_NW == 2 * SMALL_WAVES, "the projected scoring (two rows per wave of a small block) takes the candidate rule");
 
@@ -87,7 +86,6 @@ inline size_t text_fold_part_floats(int B, int H) { return (size_t)B * TXF_G * (
 
 // ---- ladders: the template value of a length (0: none) ------------------------------------------------------------------
 inline int text_rpw(int L) { return L <= TXT_NW ? 1 : L <= TXT_NW * 5 ? 5 : L <= TXT_MAX_L ? 8 : 0; }             // text_attn_kernel
-inline int vis_text_rpw(int L) { return L <= SMALL_WAVES * 2 ? 2 : L <= SMALL_WAVES * 5 ? 5 : L <= PVT_MAX_L ? 10 : 0; }   // pair_vis_text_kernel
 // the folded text stage in G groups of SMALL_WAVES waves: rung 0 .. 3 = 1, 2, 3, 5 positions per wave
 inline int text_rung(int L, int G) {
     const int rpw = (L + G * SMALL_WAVES - 1) / (G * SMALL_WAVES);
@@ -116,12 +114,12 @@ inline int proj_text_groups_plan(int B, int L, bool with_partials, int na, int s
 // ---- what a paired launch accepts of its small products' (mt, cpw): the instantiations of its kernel ------------------
 inline bool mt_124(int mt) { return mt == 1 || mt == 2 || mt == 4; }
 inline bool pair_small_small_accepts(SmallInst a, SmallInst b) { return a.mt == 1 && a.cpw == 4 && b.cpw == 4 && mt_124(b.mt); }
-inline bool pair_textfold_small_small_accepts(SmallInst a, SmallInst b) { return pair_small_small_accepts(a, b); }
+// (y and t_v' of the four-launch folded chain: t_v' has the shape of t_a, which pair_apro_small takes as (1, 4) only)
+inline bool pair_textfold_small_small_accepts(SmallInst a, SmallInst b) { return a.mt == 1 && a.cpw == 4 && b.mt == 1 && b.cpw == 4; }
 inline bool pair_proj_textfold_accepts(SmallInst y) { return y.mt == 1 && y.cpw == 4; }
 inline bool pair_apro_small_accepts(SmallInst a, SmallInst b) { return a.mt == 1 && a.cpw == 4 && b.cpw == 2 && mt_124(b.mt); }
 inline bool pair_small_text_accepts(SmallInst a) { return a.mt == 4 && a.cpw == 2; }
 inline bool pair_visbwd_small_accepts(SmallInst b) { return b.mt == 1 && b.cpw == 16; }     // the K = 4H recurrent data gradient
-inline bool pair_vis_apro_accepts(SmallInst b) { return b.cpw == 4 && mt_124(b.mt); }
 // pair_vis_small_kernel<MT, CPW, PHASE>: beside the partials (phases 0, 1) the r = W_a^T wt product of the folded text
 // chain (K = D = 256: two chunks per wave) or a one-tile-row product of eight; beside the merge (phase 2) one of eight or four
 struct VisSmallInst { int mt, cpw, phase; };

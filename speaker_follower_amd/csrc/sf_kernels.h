@@ -36,7 +36,7 @@ int text_attn_bwd(const float* ctx, int B, int L, int H, const float* dwc, int l
 int ctx_grad_accum(const float* alpha, const float* ds, const float* dcat2, int lddc, const float* tt,
                    int S, int B, int L, int H, float* dctx, hipStream_t st);
 int score_fwd(const CandSrc& src, int B, int D, const float* r, const float* wt, const float* b_a,
-              const float* b_out, float* logit, hipStream_t st, int ldr = 0, const float* cst = nullptr);
+              const float* b_out, float* logit, hipStream_t st);
 // ce (optional): d(logit) = gscale (softmax(ce.logit) - onehot(ce.target)) is formed inside the
 // kernel (and written to dlogit) instead of being read from dlogit
 int score_bwd(const CandSrc& src, int B, const float* dlogit, float* dr, float* dc, hipStream_t st,
@@ -215,11 +215,6 @@ int pair_vis_small(const PanoSrc& src, int B, const float* vec, int ldvec, float
                    unsigned* split_counter, const SmallPlan& b, hipStream_t st, int phase = 0);
 // phase 0: the whole split attention (ticket inside the launch); 1: per-group partials only;
 // 2: merge of the partials written by a phase-1 launch (alpha, out)
-// phase-1 partials beside the text attention (folded inference step)
-int pair_vis_text(const PanoSrc& src, int B, const float* vec, int ldvec, float* alpha, float* out, int ldo,
-                  const Dropout& drop, int drop_col0, float* split_part, const float* ctx, const uint8_t* mask,
-                  int L, int H, const float* t, int ldt, float* talpha, float* wc, int ldwc,
-                  const int32_t* ctx_row, hipStream_t st);
 
 // the folded text stage of an inference decode step (sf_attention.hip: text_fold_body) and its consumer
 int pair_textfold_small_small(const float* ctx_q, const float* ctx_o, const uint8_t* mask, int B, int L, int H,
@@ -229,10 +224,7 @@ int pair_apro_small(const SmallPlan& a, const SmallPlan& b, hipStream_t st);
 struct FGlue;
 int pair_score_merge(const CandSrc& src, int B, int D, const float* r, const float* wt, const float* b_a,
                      const float* b_out, const FGlue& g, const PanoSrc& psrc, float* alpha, float* out, int ldo,
-                     const Dropout& drop, int drop_col0, float* split_part, hipStream_t st, int ldr = 0,
-                     const float* cst = nullptr);
-int pair_vis_apro(const PanoSrc* src, int B, const float* vec, int ldvec, float* split_part, const SmallPlan& b,
-                  hipStream_t st);
+                     const Dropout& drop, int drop_col0, float* split_part, hipStream_t st);
 
 // the projected decode chain (sf_attention.hip): the tables of sf_projected_build as the kernels take them
 struct ProjTables {
@@ -260,8 +252,7 @@ struct FGlue;
 int follower_glue_fwd(const FGlue& g, hipStream_t st);
 // scoring + glue in one launch (sf_attention.hip); g.logit receives the masked logits
 int score_glue_fwd(const CandSrc& src, int B, int D, const float* r, const float* wt,
-                   const float* b_a, const float* b_out, const FGlue& g, hipStream_t st, int ldr = 0,
-                   const float* cst = nullptr);
+                   const float* b_a, const float* b_out, const FGlue& g, hipStream_t st);
 // rps > 0: S stacked steps of rps rows each -- row m takes gscale[m / rps]
 int softmax_ce_bwd(int B, int N, int ld, const float* logit, const int64_t* target, int ignore,
                    const float* gscale, float* dlogit, hipStream_t st, int rps = 0);

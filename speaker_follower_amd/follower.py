@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from ._lib import call
 from .features import cand_sincos
-from .model import (decoder_params, decoder_w_struct, decoder_fold, _encoder_structs, _TAPE_KEYS,
+from .model import (decoder_params, decoder_w_struct, _encoder_structs, _TAPE_KEYS,
                     grad_ptr, trainable_embedding, bi_encoder_tapes, bi_encoder_fwd, bi_encoder_bwd)
 from .runtime import ptr, stream, ws_args, wgrad_ws_args, ensure_workspace, dropout_arg, fill_regions, fault_bits, reissue_per_step, concurrent_stream, graph_capture, WeightsMoved, transposed, check_gate_weights, gate_weights_pass, register_bf16_weights
 from .dp import collectives_on
@@ -256,25 +256,9 @@ class FollowerEngine:
         self.dropout_seed = None
         self.two_stream_backward = True  # heads of the backward on a side stream (see sf_follower_episode_bwd)
         self._side_stream = None
-        # BPTT in this many chunks with the weight-gradient products of finished chunks on a third stream.
-        # Correct (tests/test_gpu_follower.py) and SLOWER on MI355X: 5.25 ms per iteration with one product
-        # over all S*B rows at the end, 5.49 with 2 or 4 chunks, 5.7 with 10 (tools/train_time.py) -- a
-        # chip-filling product does not hide beside the dependent chain, it delays it.  Off (1).
-        self.wgrad_chunks = 1
         self.grad_sync = None            # dp.BucketedGrads(dp.follower_buckets(enc, dec)): all-reduce launched from the backward
         self._open_forks = []            # side streams forked from the current one and not joined yet (_backward)
-        # ... with q' = M_v h1 + c_v and [r | c] = M_a h~ + c_a as single products (ABI 9 chain_fold): three launches behind
-        # the cell instead of four -- BUILT, CORRECT, SLOWER (round 6: 2.03 ms per rollout against 1.77: the [100 x 512] x
-        # [2176 x 512]^T products re-read their A operand per 16-column block, 18.5 + 27.9 us for the two stages that replace
-        # 10.7 + 7.5 + 14.4): off
-        self.fold_chain = False
         self.fold_text = True            # inference rollouts: text attention over ctx W_in / ctx W_out[:, :H]^T (ABI 9)
-        self._wgrad_stream = None
-        # model.decoder_fold for no-grad eval rollouts (folded Linears + the folded paired schedule of
-        # sf_attn_decoder_tail_fwd).  Correct (tests/test_gpu_follower.py) but SLOWER on MI355X: the two
-        # folded [2176 x 512] products read 4.4 MB of weights each and take 11.6 us, the four unfolded
-        # ones 5-6 us each in paired stages: 2.20 vs 2.09 ms per rollout.  Off.
-        self.fold_inference = False
         self.pipelined = True           # head(t+1) next to tail(t) in paired launches (sf_hip.h)
         self.two_stream_forward = False  # experiment: visual half of step t+1 on a side stream, ordered by device flags
         self.episode_call = True        # the whole decode loop (and its backward) as ONE C call
@@ -447,10 +431,7 @@ class FollowerEngine:
         params = decoder_params(dec)
         all_params = list(params) + [p for p in enc.parameters()]
         st.differentiable = torch.is_grad_enabled() and any(p.requires_grad for p in all_params)
-        # inference: consecutive Linears folded (two dependent stages fewer per step); the backward
-        # needs the unfolded intermediates, so a differentiable rollout keeps them
-        fold = None if (st.differentiable or training or not self.fold_inference) else decoder_fold(dec)
-        dw = decoder_w_struct(params, fold=fold)
+        dw = decoder_w_struct(params)
         ws = ws_args(dev)
         d_dec = _lib.Dropout(float(st.drop_dec[0]), int(st.drop_dec[1]) & 0xFFFFFFFF, int(st.drop_dec[2]), st.site_dev, 1)
         d_ptr = C.pointer(d_dec) if st.drop_dec[0] else None
@@ -467,7 +448,7 @@ class FollowerEngine:
         # the same one-call episode for a device-resident environment (the env step inside every scoring + glue launch,
         # the attention of step t + 1 behind it): no host work between the launches of a TRAINING rollout either, and
         # the backward takes the two-stream episode path
-        nav_episode = (on_device_env and self.pipelined and self.episode_call and self.fused_env_step and fold is None
+        nav_episode = (on_device_env and self.pipelined and self.episode_call and self.fused_env_step
                        and bool(dw.visual.w_v_t))
         if (pipelined or nav_episode) and self.episode_call:
             # every per-step tensor is a stacked [S][...] array: hand step 0 to the library once
@@ -489,7 +470,7 @@ class FollowerEngine:
             if nav_episode:
                 st.navio0 = batch.fused_step(0)               # (sf_nav_io of step 0; the library strides it per step)
                 ep.glue.nav = C.cast(C.pointer(st.navio0), C.c_void_p)
-            if self.two_stream_forward and fold is None and not nav_episode:
+            if self.two_stream_forward and not nav_episode:
                 if self._side_stream is None:
                     self._side_stream = concurrent_stream(dev)
                 ep.side_stream = self._side_stream.cuda_stream
@@ -497,16 +478,11 @@ class FollowerEngine:
             # text_fold_body) -- the context is constant over the episode, so W_in and W_out[:, :H] are applied to it ONCE
             # and two dependent launches leave every decode step.  Nothing is taped for a backward, hence never for a
             # differentiable or train-mode rollout; one stream only.
-            st.text_folded = (self.fold_text and not st.differentiable and not training and fold is None
+            st.text_folded = (self.fold_text and not st.differentiable and not training
                               and ep.side_stream is None and S > 1 and T <= 80)
             if st.text_folded:
                 st.ctx_fold = new(2, B, T, H)
                 ep.ctx_q, ep.ctx_o = st.ctx_fold[0].data_ptr(), st.ctx_fold[1].data_ptr()
-                if self.fold_chain:
-                    # ... and the folded query / scoring matrices (model.decoder_fold: rebuilt in place per weight
-                    # version): three dependent launches behind the cell instead of four
-                    st.chain_fold = decoder_fold(dec)
-                    ep.chain_fold = C.pointer(st.chain_fold)
             # ... on the projected tables of (store, decoder) where the policy has them (`project` above): the library
             # takes the two-launch chain for every step it applies to and says how many it issued
             st.projected_tables = self._projected_tables(B, T=T, A=A) if (st.text_folded and not nav_episode) else None
@@ -521,7 +497,7 @@ class FollowerEngine:
         if pipelined and not st.episode:
             call('sf_attn_decoder_head_fwd', byref(dw), byref(panos[0]), B, H, D, ptr(st.h_init),
                  byref(tapes[0]), d_ptr, st.site_rel, *ws)
-        deferred = on_device_env and self.pipelined and fold is None and dw.visual.w_v_t and not st.episode
+        deferred = on_device_env and self.pipelined and dw.visual.w_v_t and not st.episode
         if deferred:
             call('sf_attn_decoder_head_fwd', byref(dw), byref(panos[0]), B, H, D, ptr(st.h_init),
                  byref(tapes[0]), d_ptr, st.site_rel, *ws)
@@ -641,7 +617,6 @@ class FollowerEngine:
         else:
             ew = bytes(_encoder_structs(enc))
         dw = decoder_w_struct(decoder_params(self.decoder))
-        fold = bytes(decoder_fold(self.decoder)) if (self.fold_inference or (self.fold_text and self.fold_chain)) else b''
         packed = b''
         if gate_weights == 'bf16':
             lstm = self.decoder.lstm
@@ -651,7 +626,7 @@ class FollowerEngine:
             # (refreshed in place here when a weight they depend on changed; re-allocated or gone: the bytes differ)
             hit = self.store.projected(self.decoder, build=False)
             tables = b'projected' + (bytes(hit['struct']) if hit is not None else b'')
-        return ew + bytes(dw) + fold + packed + tables
+        return ew + bytes(dw) + packed + tables
 
     @contextlib.contextmanager
     def _capture_policy(self):
@@ -866,34 +841,10 @@ class FollowerEngine:
                 ep.side_stream = self._side_stream.cuda_stream
             else:
                 ep.side_stream = None
-            # Backpropagation through time in chunks of steps: the weight-gradient products of a finished
-            # chunk (matrix-core work over its stacked rows, accumulated in place) run on a third stream
-            # while the earlier steps are still being walked (dependent, latency-bound launches that leave
-            # most of the chip idle); only the last chunk's products are left for the end, beside the
-            # encoder's backward.  `wgrad_chunks = 1` is the round-2 schedule (one product over all S*B rows).
-            overlap_w = (self.wgrad_chunks > 1 and ep.side_stream is not None and S >= 2 * self.wgrad_chunks)
-            n_chunks = self.wgrad_chunks if overlap_w else 1
-            bounds = [(S * k) // n_chunks for k in range(n_chunks + 1)]
             which = C.c_int(0)
-            tp_at = lambda t: _lib.DecoderTape(*(st.tape[k][t:].data_ptr() for k in _TAPE_KEYS))          # noqa: E731
-            gt_at = lambda t: _lib.DecoderGTape(*(gt[k][t:].data_ptr() for k in gkeys), None, None, None)  # noqa: E731
-            if overlap_w and self._wgrad_stream is None:
-                self._wgrad_stream = concurrent_stream(dev, exclude=[x for x in (self._side_stream,) if x is not None])
-            st.wgrad_done_from = S                   # steps >= this have their weight gradients issued
-            for k in range(n_chunks - 1, -1, -1):
-                lo, hi = bounds[k], bounds[k + 1]
-                call('sf_follower_episode_bwd_range', byref(dw), byref(ep), byref(gt0e), ptr(gscale), ptr(dlogit),
-                     ptr(dh_a), ptr(dc_a), ptr(dh_b), ptr(dc_b), ptr(dctx), byref(which), lo, hi,
-                     ptr(dh1), ptr(dc1), *ws)
-                dh1, dc1 = (dh_b, dc_b) if which.value else (dh_a, dc_a)
-                if overlap_w and k > 0:
-                    wst = self._wgrad_stream
-                    wst.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(wst):
-                        tpk, gtk = tp_at(lo), gt_at(lo)
-                        call('sf_attn_decoder_wgrad', byref(dw), byref(dg), (hi - lo) * B, H, D, F, ptr(st.hs[lo:]),
-                             byref(tpk), byref(gtk), *ws_args(dev))
-                    st.wgrad_done_from = lo
+            call('sf_follower_episode_bwd', byref(dw), byref(ep), byref(gt0e), ptr(gscale), ptr(dlogit),
+                 ptr(dh_a), ptr(dc_a), ptr(dh_b), ptr(dc_b), ptr(dctx), byref(which), *ws)
+            dh1, dc1 = (dh_b, dc_b) if which.value else (dh_a, dc_a)
         for t in range(S - 1 if st.episode is None else -1, -1, -1):
             pano = store.pano(batch.vp[t], batch.view[t])
             cnd = store.cands(batch.vp[t], batch.cand_view[t], batch.sincos[t], batch.a_num[t], A)
@@ -909,8 +860,6 @@ class FollowerEngine:
         # data parallelism: dp.BucketedGrads laid out as dp.follower_buckets -- each bucket's all-reduce is
         # launched from here, behind the launches that complete it
         sync = self.grad_sync
-        # rows whose weight gradients are still to be formed: all of them, or the first chunk's
-        Sw = getattr(st, 'wgrad_done_from', S) if st.episode is not None else S
         tp0 = _lib.DecoderTape(*(st.tape[k].data_ptr() for k in _TAPE_KEYS))
         gt0 = _lib.DecoderGTape(*(gt[k].data_ptr() for k in gkeys), None, None, None)
         # the decoder's weight gradients (a few large products over the stacked rows: matrix-core
@@ -918,21 +867,21 @@ class FollowerEngine:
         # independent: issued on two streams they overlap
         overlap = self.two_stream_backward and (self._side_stream is not None or not torch.cuda.is_current_stream_capturing())
         if overlap:
-            side = self._wgrad_stream if (st.episode is not None and Sw < S) else self._side_stream
+            side = self._side_stream
             if side is None:
                 side = self._side_stream = concurrent_stream(dev)
             side.wait_stream(torch.cuda.current_stream())
             self._open_forks = [side]                    # (a segmented capture joins / re-opens these at its cuts)
         # (Measured in round 5 by wall clock: the encoder first, the two latency-bound pieces side by side, a third stream
-        # and chunked weight gradients are all equal or slower than this order; what shortened the tail was fewer launches,
+        # and chunked weight gradients ("Retired experiments") are all equal or slower than this order; what shortened the tail was fewer launches,
         # gemm_tn_group.  The many-row weight-gradient tiles -- 512 threads x 188 VGPRs, 96 KB LDS -- cannot sit beside the
         # persistent encoder backward's 256-VGPR workgroup on a CU.  NOTE: rocprofv3 --kernel-trace serialises the queues;
         # its timelines show no overlap at all and must not be read for concurrency; DESIGN.md, "Retired experiments".)
         try:
             if overlap:
-                self._issue_wgrad(side, dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, dev, sync)
+                self._issue_wgrad(side, dw, dg, params, S * B, H, D, F, st, tp0, gt0, dev, sync)
             else:
-                self._decoder_wgrad(dw, dg, params, Sw * B, H, D, F, st, tp0, gt0, wgrad_ws_args(dev), sync)
+                self._decoder_wgrad(dw, dg, params, S * B, H, D, F, st, tp0, gt0, wgrad_ws_args(dev), sync)
             if enc.num_directions == 2:
                 bi_encoder_bwd(enc, batch.seq, batch.lengths_dev, T, dropout_arg(*st.drop_enc_bi), st.site_rel,
                                st.enc_table, st.enc_tape, st.h_init, dctx, dh1, dc1)

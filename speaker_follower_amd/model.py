@@ -598,7 +598,7 @@ def decoder_params(mod):
 
 
 def decoder_fold(mod):
-    """sf_decoder_fold for inference (see include/sf_hip.h), rebuilt only when one of the nine
+    """sf_decoder_fold (see include/sf_hip.h: what the projected tables are built from), rebuilt only when one of the nine
     tensors it is made of changed.  Kept on the module so that the pointers stay alive."""
     params = decoder_params(mod)
     src = [params[i] for i in (4, 5, 6, 10, 11, 12, 13, 14, 15)]
@@ -619,7 +619,7 @@ def decoder_fold(mod):
     return fold
 
 
-def decoder_w_struct(params, grad=False, fold=None):
+def decoder_w_struct(params, grad=False):
     if grad:
         vals = _grads(params)
         return _lib.DecoderW(_lib.LstmW(*vals[0:4]), _lib.VisualW(*vals[4:8]),
@@ -629,8 +629,7 @@ def decoder_w_struct(params, grad=False, fold=None):
     return _lib.DecoderW(_lib.LstmW(*vals[0:4], t(0), t(1)),
                          _lib.VisualW(*vals[4:8], t(6), t(4)),
                          _lib.SoftdotW(*vals[8:10], t(8), t(9)),
-                         _lib.ScoringW(*vals[10:16], t(12), t(10)),
-                         C.pointer(fold) if fold is not None else None)
+                         _lib.ScoringW(*vals[10:16], t(12), t(10)))
 
 
 class _DecoderStepFn(torch.autograd.Function):

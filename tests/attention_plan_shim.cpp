@@ -12,7 +12,7 @@ extern "C" {
 // out: the constants tests/attention_cases.py mirrors, then the other tile constants a rule reads; returns the count
 int shim_tables(int* out) {
     const int v[] = {VIS_CPL, VIS_RPW, VIS_NW, VSP_G, VSP_RPG, VIS_SPLIT_MAX_B, TXT_CPL, TXT_NW, SC_CPL, SC_NW, CG_ROWS,
-                     TXT_MAX_L, PVT_MAX_L, TXF_G, TXF_MAX_L, TXF_MAX_B, TXF_G2_MAX_L, PRJ_CPL, PPB_G, SPLIT_MAX_G, SMALL_WAVES};
+                     TXT_MAX_L, TXF_G, TXF_MAX_L, TXF_MAX_B, TXF_G2_MAX_L, PRJ_CPL, PPB_G, SPLIT_MAX_G, SMALL_WAVES};
     const int n = (int)(sizeof v / sizeof v[0]);
     for (int i = 0; i < n; ++i) out[i] = v[i];
     return n;
@@ -37,7 +37,6 @@ long long shim_visual_attn_split_floats(int B, int F) { return (long long)visual
 long long shim_text_fold_part_floats(int B, int H) { return (long long)text_fold_part_floats(B, H); }
 
 int shim_text_rpw(int L) { return text_rpw(L); }
-int shim_vis_text_rpw(int L) { return vis_text_rpw(L); }
 int shim_text_rung(int L, int G) { return text_rung(L, G); }
 int shim_fold_rpw(int L, int G) { return fold_rpw(L, G); }
 int shim_proj_text_groups_plan(int B, int L, int with_partials, int na, int slots, int force, int* grid) {
@@ -45,7 +44,7 @@ int shim_proj_text_groups_plan(int B, int L, int with_partials, int na, int slot
 }
 
 // which: 0 pair_small_small, 1 pair_textfold_small_small, 2 pair_apro_small (products a and b); 3 pair_small_text,
-// 4 pair_visbwd_small, 5 pair_vis_apro, 6 pair_proj_textfold (product a); 7 pair_vis_small (product a, phase)
+// 4 pair_visbwd_small, 5 pair_proj_textfold (product a); 6 pair_vis_small (product a, phase)
 int shim_accepts(int which, int amt, int acpw, int bmt, int bcpw, int phase) {
     const SmallInst a{amt, acpw}, b{bmt, bcpw};
     switch (which) {
@@ -54,9 +53,8 @@ int shim_accepts(int which, int amt, int acpw, int bmt, int bcpw, int phase) {
         case 2: return pair_apro_small_accepts(a, b);
         case 3: return pair_small_text_accepts(a);
         case 4: return pair_visbwd_small_accepts(a);
-        case 5: return pair_vis_apro_accepts(a);
-        case 6: return pair_proj_textfold_accepts(a);
-        case 7: return pair_vis_small_accepts(a, phase);
+        case 5: return pair_proj_textfold_accepts(a);
+        case 6: return pair_vis_small_accepts(a, phase);
     }
     return -1;
 }

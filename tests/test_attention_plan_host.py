@@ -17,7 +17,7 @@ from tests import attention_cases as A
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, UNSUPPORTED = 0, 2
 MTS, CPWS = range(1, 9), (1, 2, 4, 8, 16)
-SMALL_SMALL, TEXTFOLD, APRO_SMALL, SMALL_TEXT, VISBWD_SMALL, VIS_APRO, PROJ_TEXTFOLD, VIS_SMALL = range(8)
+SMALL_SMALL, TEXTFOLD, APRO_SMALL, SMALL_TEXT, VISBWD_SMALL, PROJ_TEXTFOLD, VIS_SMALL = range(7)
 PANORAMA = dict(IMG=2048, LOC=128)                    # the follower's rows: F = 2176
 
 
@@ -41,7 +41,7 @@ class Shim:
         lib.shim_visual_attn_split_floats.restype = lib.shim_text_fold_part_floats.restype = C.c_longlong
         t = (C.c_int * 64)()
         n = lib.shim_tables(t)
-        names = ('VIS_CPL VIS_RPW VIS_NW VSP_G VSP_RPG VIS_SPLIT_MAX_B TXT_CPL TXT_NW SC_CPL SC_NW CG_ROWS TXT_MAX_L PVT_MAX_L '
+        names = ('VIS_CPL VIS_RPW VIS_NW VSP_G VSP_RPG VIS_SPLIT_MAX_B TXT_CPL TXT_NW SC_CPL SC_NW CG_ROWS TXT_MAX_L '
                  'TXF_G TXF_MAX_L TXF_MAX_B TXF_G2_MAX_L PRJ_CPL PPB_G SPLIT_MAX_G SMALL_WAVES').split()
         assert n == len(names)
         self.const = dict(zip(names, t[:n]))
@@ -68,7 +68,7 @@ def test_constants_are_the_ones_the_cases_mirror(shim):
     assert (c['VSP_G'], c['VSP_RPG'], c['VIS_SPLIT_MAX_B']) == (A.VSP_G, A.VSP_RPG, A.VIS_SPLIT_MAX_B)
     assert (c['TXT_CPL'], c['TXT_NW'], c['TXT_MAX_L']) == (A.TXT_CPL, A.TXT_NW, A.L_MAX)
     assert (c['SC_CPL'], c['SC_NW'], c['CG_ROWS']) == (A.SC_CPL, A.SC_NW, A.CG_ROWS)
-    assert (c['PVT_MAX_L'], c['TXF_MAX_L'], c['TXF_MAX_B'], c['TXF_G2_MAX_L']) == (80, 160, 512, 80)
+    assert (c['TXF_MAX_L'], c['TXF_MAX_B'], c['TXF_G2_MAX_L']) == (160, 512, 80)
     assert (c['TXF_G'], c['PRJ_CPL'], c['PPB_G'], c['SPLIT_MAX_G'], c['SMALL_WAVES']) == (4, 2, 3, 3, 8)
 
 
@@ -149,7 +149,7 @@ def test_row_width_thresholds(shim):
 def test_text_thresholds(shim):
     text = lambda L, Lmax, H=512, lds=0: shim.text_rows_fit(L, Lmax, H, lds)
     assert text(1, 128) == 1 and text(0, 128) == 0
-    assert text(128, 128) == 1 and text(129, 128) == 0 and text(80, 80) == 1 and text(81, 80) == 0
+    assert text(128, 128) == 1 and text(129, 128) == 0
     assert text(160, 160) == 1 and text(161, 160) == 0
     assert text(40, 128, H=512) == 1 and text(40, 128, H=516) == 0 and text(40, 128, H=510) == 0          # H
     assert text(40, 128, lds=1024 | 512) == 1 and text(40, 128, lds=1024 | 514) == 0
@@ -164,12 +164,10 @@ def test_ladders(shim):
     ladder = lambda f, *a: [f(L, *a) for L in range(1, 170)]
     want = lambda steps: [next((v for top, v in steps if L <= top), 0) for L in range(1, 170)]
     assert ladder(shim.text_rpw) == want(((16, 1), (80, 5), (128, 8)))               # L, text: 16/17, 80/81, 128/129
-    assert ladder(shim.vis_text_rpw) == want(((16, 2), (40, 5), (80, 10)))           # L, pair_vis_text: 16/17, 40/41, 80/81
     assert ladder(shim.fold_rpw, 4) == want(((32, 1), (64, 2), (96, 3), (10 ** 6, 5)))   # L, fold: 32/33, 64/65, 96/97 (160: the gate)
     assert ladder(shim.fold_rpw, 2) == want(((16, 1), (32, 2), (48, 3), (10 ** 6, 5)))   # two text groups: 80 = 2 x 8 x 5 is the gate
     assert [shim.text_rung(L, 4) for L in (32, 33, 64, 65, 96, 97, 160)] == [0, 1, 1, 2, 2, 3, 3]
-    for f, top in ((shim.text_rpw, 128), (shim.vis_text_rpw, 80)):                   # a ladder ends where its gate does
-        assert f(top) and not f(top + 1)
+    assert shim.text_rpw(128) and not shim.text_rpw(129)                             # a ladder ends where its gate does
     assert shim.const['TXF_MAX_L'] == 4 * 8 * 5 and shim.const['TXF_G2_MAX_L'] == 2 * 8 * 5
 
 
@@ -204,15 +202,17 @@ ONE_TWO_FOUR = (1, 2, 4)
 
 
 def test_accepted_small_products(shim):
-    for which in (SMALL_SMALL, TEXTFOLD):
-        assert shim.accepted(which, a=(1, 4)) == {(m, 4) for m in ONE_TWO_FOUR}
+    assert shim.accepted(SMALL_SMALL, a=(1, 4)) == {(m, 4) for m in ONE_TWO_FOUR}
+    # the folded text stage: t_v' beside y is (1, 4) and nothing else -- (2, 4) and (4, 4), which only the retired
+    # three-launch chain planned (its q' product over F columns), are refused
+    assert shim.accepted(TEXTFOLD, a=(1, 4)) == {(1, 4)}
+    assert not shim.lib.shim_accepts(TEXTFOLD, 1, 4, 2, 4, 0) and not shim.lib.shim_accepts(TEXTFOLD, 1, 4, 4, 4, 0)
     assert shim.accepted(APRO_SMALL, a=(1, 4)) == {(m, 2) for m in ONE_TWO_FOUR}
     for which in (SMALL_SMALL, TEXTFOLD, APRO_SMALL):                                 # a = (1, 4) and nothing else
         for a in ((m, c) for m in MTS for c in CPWS if (m, c) != (1, 4)):
             assert shim.accepted(which, a=a) == set(), (which, a)
     assert shim.accepted(SMALL_TEXT) == {(4, 2)}
     assert shim.accepted(VISBWD_SMALL) == {(1, 16)}
-    assert shim.accepted(VIS_APRO) == {(m, 4) for m in ONE_TWO_FOUR}
     assert shim.accepted(PROJ_TEXTFOLD) == {(1, 4)}
     for phase in (0, 1):
         assert shim.accepted(VIS_SMALL, phase) == {(m, 2) for m in ONE_TWO_FOUR} | {(1, 8)}

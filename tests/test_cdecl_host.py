@@ -115,10 +115,10 @@ def test_the_package_header_is_read_whole():
     h = _cdecl.parse(text)
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)                   # the count of a plain search: nothing dropped
     assert [s for s, _ in h.structs] == re.findall(r'typedef struct (\w+) \{', text) and len(h.structs) >= 39
-    assert sorted(h.functions) == sorted(set(re.findall(r'\b(sf_[a-z0-9_]+)\s*\(', text))) and len(h.functions) >= 125
+    assert sorted(h.functions) == sorted(set(re.findall(r'\b(sf_[a-z0-9_]+)\s*\(', text))) and len(h.functions) >= 123   # (125 less the two retired entries)
     assert sorted(n for n in h.constants if n not in ('SF_OK',) and not n.startswith(('SF_ERR_', 'SF_SEARCH_OVF_'))) == \
         sorted(re.findall(r'#define (SF_\w+) \d+', text))
     assert h.typedefs == {'sf_stream': ('void', 1)}
-    assert h.constants['SF_ABI_VERSION'] == 9 and h.constants['SF_SEARCH_OVF_KEY'] == 16
+    assert h.constants['SF_ABI_VERSION'] == 10 and h.constants['SF_SEARCH_OVF_KEY'] == 16
     assert 'SF_HIP_H_' not in h.constants
     assert ('nav', 'sf_nav_io', 1) in dict(h.structs)['sf_follower_glue']          # the one forward reference

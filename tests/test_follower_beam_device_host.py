@@ -358,7 +358,7 @@ def test_follower_beam_select_entry_is_exported_and_bound():
     assert hasattr(raw, 'sf_follower_beam_select')
     assert 'sf_follower_beam_select' in _lib.EXPORTS
     assert _lib.lib.sf_follower_beam_select.argtypes is not None
-    assert _lib.ABI_VERSION == 9 and _lib.lib.sf_abi_version() == 9
+    assert _lib.ABI_VERSION == 10 and _lib.lib.sf_abi_version() == 10
 
 
 def test_follower_beam_select_rejects_bad_arguments_without_gpu():

@@ -21,8 +21,8 @@ def test_symbols_are_declared_exported_and_bound_under_abi_9():
         assert re.search(r'\b%s\s*\(' % s, text), '%s is not declared in sf_hip.h' % s
         assert hasattr(raw, s), 'libsf_hip.so does not export %s' % s
         assert s in _lib.EXPORTS
-    assert re.search(r'#define\s+SF_ABI_VERSION\s+9\b', text)
-    assert _lib.lib.sf_abi_version() == _lib.ABI_VERSION == 9
+    assert re.search(r'#define\s+SF_ABI_VERSION\s+10\b', text)
+    assert _lib.lib.sf_abi_version() == _lib.ABI_VERSION == 10
     assert C.sizeof(_lib.LstmW) == 6 * C.sizeof(C.c_void_p)               # sf_lstm_w did not grow a member
 
 

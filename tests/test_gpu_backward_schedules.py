@@ -1,7 +1,6 @@
-"""GPU: WHICH kernels one training iteration of the follower launches (csrc/sf_api.hip: sf_follower_episode_bwd_range
+"""GPU: WHICH kernels one training iteration of the follower launches (csrc/sf_api.hip: sf_follower_episode_bwd
 walks the steps on one stream or on two -- heads on a side stream, tails behind their events -- and declines the second
-stream above VIS_SPLIT_MAX_B; follower.FollowerEngine._backward calls it once, or once per chunk of steps with the
-weight gradients of finished chunks on a third stream).  The backward counterpart of tests/test_gpu_decode_schedules.py.
+stream above VIS_SPLIT_MAX_B; follower.FollowerEngine._backward calls it once).  The backward counterpart of tests/test_gpu_decode_schedules.py.
 
 The numeric tests cannot see a wrong choice: a backward that silently takes another path still gives the reference's
 gradients.  Here one eager training iteration per case -- rollout(..., 'teacher', train=True) with a fixed dropout seed,
@@ -44,7 +43,6 @@ CASES = {
     'two-stream': dict(),
     'above-split': dict(B=257, S=2),                                       # (above VIS_SPLIT_MAX_B: one stream)
     'one-stream257': dict(B=257, S=2, engine=dict(two_stream_backward=False)),
-    'chunked': dict(S=4, engine=dict(wgrad_chunks=2)),                     # (two chained ranges of two steps)
 }
 
 

@@ -1,6 +1,6 @@
 """GPU: WHICH kernels each schedule of the follower's decode step launches (csrc/sf_api.hip: decoder_tail_i picks one of
-six launch chains per step -- the three- and four-launch folded chains, the sf_decoder_fold schedule, the paired unfolded
-one, its query-only variant for a device-resident environment, the plain step).
+five launch chains per step -- the projected chain, the four-launch folded chain, the paired unfolded one, its query-only
+variant for a device-resident environment, the plain step).
 
 The numeric tests cannot see a wrong choice: a folded rollout that silently falls back to another chain still passes
 tests/test_gpu_text_fold.py.  Here one eager rollout per case runs under the library's own launch profile
@@ -38,9 +38,7 @@ TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'decode_schedul
 # 2..12, no_grad, 'argmax', train=False).  'paired257' is not a schedule of its own: it is what 'fallback' must equal.
 CASES = {
     'folded4': dict(),
-    'folded3': dict(engine=dict(fold_chain=True)),
     'paired': dict(engine=dict(fold_text=False)),
-    'decoder-fold': dict(engine=dict(fold_inference=True)),
     'train': dict(feedback='teacher', train=True, grad=True),             # (dropout on; forward only)
     'per-call': dict(engine=dict(fold_text=False, episode_call=False)),
     'plain': dict(engine=dict(pipelined=False)),
@@ -121,13 +119,12 @@ def test_schedule_launches_the_recorded_kernels(name, seen, recorded):
     assert got == recorded[name]
 
 
-def test_the_three_chains_are_three_different_schedules(seen):
-    f4, f3, pd = seen('folded4'), seen('folded3'), seen('paired')
-    assert f4 != f3 and f4 != pd and f3 != pd
+def test_the_two_chains_are_two_different_schedules(seen):
+    assert seen('folded4') != seen('paired')
 
 
 def test_above_the_split_limit_the_step_is_the_paired_one(seen):
-    """B = 257 is above VIS_SPLIT_MAX_B: both folded chains decline before their first launch and every step is the
+    """B = 257 is above VIS_SPLIT_MAX_B: the folded chains decline before their first launch and every step is the
     paired unfolded one -- launch for launch the rollout with fold_text off at that shape, none of the folded kernels.
     The only launches on top are the two many-row products that build ctx_q / ctx_o: the episode issues them once, in
     front of step 0, before any step can decline."""

@@ -206,7 +206,7 @@ def _follower(peaky_seed=77, train=False):
     return (enc.train(), dec.train(), enc_w, dec_w) if train else (enc.eval(), dec.eval(), enc_w, dec_w)
 
 
-CHAINS = [(False, False), (True, False), (True, True)]            # unfolded, folded four-launch, fold_chain
+CHAINS = [False, True]            # unfolded, folded four-launch (the three-launch chain, the third, is retired)
 
 
 @pytest.mark.parametrize('feedback', ['argmax', 'teacher'])
@@ -225,17 +225,17 @@ def test_rollouts_on_host_batches_in_all_three_chains(B, feedback):
     ref = np_model.follower_rollout(enc_w, dec_w, seq, lens, mask, S, lambda t: np_env.dense_follower_step(rt, loc, fb, t),
                                     fb.target, feedback, 2176, early_exit=False)
     n = len(ref['logits'])
-    for fold, chain in CHAINS:
+    for fold in CHAINS:
         res = []
         for s in (s16, s32):
             eng = follower.FollowerEngine(enc, dec, s)
-            eng.fold_text, eng.fold_chain = fold, chain
+            eng.fold_text = fold
             with torch.no_grad():
                 st = eng.rollout(batch, S, feedback, train=False)
             torch.cuda.synchronize()
             res.append((st.logits.clone(), st.actions.clone(), st.loss_buf.clone()))
         for a, b in zip(*res):
-            assert torch.equal(a, b), (fold, chain)
+            assert torch.equal(a, b), fold
         lg, ac = res[0][0].cpu().numpy(), res[0][1].cpu().numpy()
         assert np.array_equal(ac[:n], ref['actions'])                # the oracle on the ROUNDED table: actions identical,
         for t in range(n):                                           # logits within the existing parity bound
@@ -255,19 +255,19 @@ def test_rollouts_on_a_device_environment_in_all_three_chains(B, feedback):
     env.reset_epoch()
     env._next_minibatch(True)
     items = list(env.batch)
-    for fold, chain in CHAINS:
+    for fold in CHAINS:
         res = []
         for s in (s16, s32):
             nt = nav.NavTable(env, s)
             eng = follower.FollowerEngine(enc, dec, s)
-            eng.fold_text, eng.fold_chain = fold, chain
+            eng.fold_text = fold
             navb = nav.DeviceNavBatch(nt, items, 6)
             with torch.no_grad():
                 st = eng.rollout(navb, 6, feedback, train=False)
             torch.cuda.synchronize()
             res.append((st.logits.clone(), st.actions.clone(), navb.row.clone(), navb.view.clone()))
         for a, b in zip(*res):
-            assert torch.equal(a, b), (fold, chain)
+            assert torch.equal(a, b), fold
 
 
 # ------------------------------------------------------------------------------------------------------------ 5. training

@@ -177,36 +177,6 @@ def test_engine_teacher_gradients_golden(follower_modules, batch8, golden, case,
         m.zero_grad(set_to_none=True)
 
 
-@pytest.mark.parametrize('chunks', [2, 4])
-def test_chunked_backward_through_time_matches_the_reference_gradients(follower_modules, golden, chunks):
-    """sf_follower_episode_bwd_range: BPTT in chunks of steps with the weight gradients of finished chunks
-    accumulated from a third stream (FollowerEngine.wgrad_chunks) gives the reference's gradients (G4, B=100,
-    20 steps) and, to summation order, those of the one-product schedule."""
-    enc, dec, _, _ = follower_modules
-    fb = synth.follower_batch(seed=0, batch=100, steps=20, n_viewpoints=256)
-    table = synth.feature_table(0, 256)
-    g = golden('g4_rollout_b100_teacher')
-    engine, follower = _engine(follower_modules, table)
-    batch = follower.DeviceFollowerBatch.from_synth(fb)
-    grads = {}
-    for n_chunks in (1, chunks):
-        engine.wgrad_chunks = n_chunks
-        for m in (enc, dec):
-            m.zero_grad(set_to_none=True)
-        st = engine.rollout(batch, int(g['n_steps']), 'teacher', train=False)
-        st.loss.backward()
-        torch.cuda.synchronize()
-        grads[n_chunks] = {k: p.grad.clone() for m, pre in ((enc, 'enc/'), (dec, 'dec/'))
-                           for k, p in ((pre + k, p) for k, p in m.named_parameters()) if p.grad is not None}
-    _check_grads({k[4:]: v for k, v in grads[chunks].items() if k.startswith('enc/')}, g, 'enc/')
-    _check_grads({k[4:]: v for k, v in grads[chunks].items() if k.startswith('dec/')}, g, 'dec/')
-    for k, a in grads[1].items():
-        scale = float(a.abs().max())
-        assert float((a - grads[chunks][k]).abs().max()) <= 2e-5 * max(scale, 1e-6), k
-    for m in (enc, dec):
-        m.zero_grad(set_to_none=True)
-
-
 def test_grouped_weight_gradients_match_the_reference_and_the_single_products(follower_modules, golden):
     """gemm_tn_group: the decoder's seven small weight gradients in three launches (all transposes, all many-row
     products, all slab sums) give the reference's gradients (G4, B=100, 20 steps) and, to summation order, those of
@@ -477,37 +447,6 @@ def test_engine_edge_cases_against_oracle(case):
     else:
         fb = synth.follower_batch(seed=4, batch=260, steps=2, n_viewpoints=nvp, min_len=2, max_len=12, a_max=6)
         _rollout_vs_oracle(fb, table, enc, dec, enc_w, dec_w, 2)
-
-
-def test_folded_inference_schedule_matches_unfolded():
-    """sf_decoder_fold + the folded paired schedule (q' = M_v h + c_v beside t_text, attention partials
-    beside the text attention, [r | c] = M_a h~ + c_a): same actions, logits within 1e-4 of their scale.
-    (Kept off by default: slower on MI355X, see FollowerEngine.fold_inference.)"""
-    from speaker_follower_amd import model, features, follower
-    d = synth.FULL
-    enc_w, dec_w = synth.follower_weights_peaky(303)
-    enc = model.EncoderLSTM(d.vocab, d.word, d.hidden, 0, 0.5, glove=enc_w['embedding.weight'])
-    dec = model.AttnDecoderLSTM(d.feat, d.hidden, 0.5, feature_size=d.feat)
-    enc.load_state_dict({k: torch.tensor(v) for k, v in enc_w.items()})
-    dec.load_state_dict({k: torch.tensor(v) for k, v in dec_w.items()})
-    enc.cuda().eval()
-    dec.cuda().eval()
-    fb = synth.follower_batch(seed=47, batch=100, steps=12, n_viewpoints=256)
-    store = features.FeatureStore(synth.feature_table(8, 256))
-    batch = follower.DeviceFollowerBatch.from_synth(fb)
-    out = []
-    for fold in (False, True):
-        eng = follower.FollowerEngine(enc, dec, store)
-        eng.fold_inference = fold
-        with torch.no_grad():
-            out.append(eng.rollout(batch, 12, 'argmax', train=False))
-    a, b = out
-    assert torch.equal(a.actions, b.actions)
-    la, lb = a.logits.cpu().numpy(), b.logits.cpu().numpy()
-    fin = np.isfinite(la)
-    assert np.array_equal(fin, np.isfinite(lb))
-    assert float(np.abs(la[fin] - lb[fin]).max()) <= 1e-4 * float(np.abs(la[fin]).max())
-    np.testing.assert_allclose(float(b.loss), float(a.loss), rtol=1e-5)
 
 
 def test_two_stream_forward_equals_paired_schedule():

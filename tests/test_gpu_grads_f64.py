@@ -118,7 +118,7 @@ def _oracle_grads(state):
 
 # --------------------------------------------------------------------------------------------------------- follower
 
-def _follower(B, S, *, train, seed=11, weights='plain', glove=True, bidir=False, two_stream=True, chunks=1,
+def _follower(B, S, *, train, seed=11, weights='plain', glove=True, bidir=False, two_stream=True,
               persistent=True, min_len=10, max_len=79, a_max=14, stop_prob=1.0 / 6.0, mutate=None, max_length=80):
     from speaker_follower_amd import model, features, follower as fol
     if bidir:
@@ -151,7 +151,6 @@ def _follower(B, S, *, train, seed=11, weights='plain', glove=True, bidir=False,
         eng = fol.FollowerEngine(enc, dec, store)
         eng.dropout_seed = SEED
         eng.two_stream_backward = two_stream
-        eng.wgrad_chunks = chunks
         st_ = eng.rollout(batch, S, 'teacher', train=train)
         st_.loss.backward()
         torch.cuda.synchronize()
@@ -217,19 +216,12 @@ def test_f1_headline_training_shape(two_stream):
     assert not torch.equal(st_ps.ctx, c['st'].ctx)
 
 
-def test_f2_chunked_backward_through_time():
-    """F1 with wgrad_chunks = 4: sf_follower_episode_bwd_range, the weight gradients of finished chunks on a third stream."""
-    c = _follower(100, 20, train=True, chunks=4)
-    assert c['st'].wgrad_done_from == 5                          # chunks [15,20) [10,15) [5,10) issued early, [0,5) last
-    _check_case('F2 wgrad_chunks=4', c)
-
-
 @pytest.mark.parametrize('B,S', [(256, 20), (300, 14)])
 def test_f3_split_weight_gradient_and_unpaired_batches(B, S):
     """5120 / 4200 stacked rows: gemm_tn_split for the decoder weight gradients (pinned: the same pass with the split
     product switched off gives different bits); B > 128: the per-step encoder (pinned: forcing SF_ENC_PER_STEP changes
     no bit); B > 256: the un-paired launches.  B = 300 with the default two-stream backward failed with "workspace too
-    small" in sf_follower_episode_bwd_range; above VIS_SPLIT_MAX_B (256) rows the entry now walks the steps on one stream (the
+    small" in sf_follower_episode_bwd; above VIS_SPLIT_MAX_B (256) rows the entry now walks the steps on one stream (the
     two schedules give the same bits, so which one ran is not observable from the outputs)."""
     c = _follower(B, S, train=True, seed=31, min_len=5, max_len=40)
     assert B * c['n'] >= 4096

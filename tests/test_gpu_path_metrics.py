@@ -259,7 +259,7 @@ def test_refusals_of_the_entry(world):
     assert lib.sf_eval_score_routes(C.byref(_lib.EvalRoutes(**ok)), None, st) == _lib.SF_ERR_ARG
     torch.cuda.synchronize()
     assert (one == 0).all()
-    assert lib.sf_abi_version() == 9
+    assert lib.sf_abi_version() == 10
 
 
 # ------------------------------------------------------------------------------------------ Evaluation on the device

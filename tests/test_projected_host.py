@@ -24,7 +24,7 @@ def test_new_symbols_are_exported_and_bound():
         assert hasattr(raw, name), name
         assert name in L.EXPORTS
         assert getattr(L.lib, name).argtypes is not None
-    assert L.lib.sf_abi_version() == 9                              # additive: no struct of ABI 9 changed
+    assert L.lib.sf_abi_version() == 10                             # (additive; 10 is the removal of the retired schedules' fields)
 
 
 def test_row_stride_is_h_plus_one_padded_to_16_bytes():

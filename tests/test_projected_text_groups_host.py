@@ -86,5 +86,5 @@ def test_abi_version_and_new_symbols():
         assert name in L.EXPORTS
         assert getattr(L.lib, name).argtypes is not None
         assert name + '(' in header
-    assert L.lib.sf_abi_version() == 9 and L.ABI_VERSION == 9       # additive: no struct of ABI 9 changed
-    assert '#define SF_ABI_VERSION 9' in header
+    assert L.lib.sf_abi_version() == 10 and L.ABI_VERSION == 10     # (additive; 10 is the removal of the retired schedules' fields)
+    assert '#define SF_ABI_VERSION 10' in header

@@ -376,7 +376,7 @@ def test_beam_select_entry_is_exported_and_bound():
     assert hasattr(raw, 'sf_speaker_beam_select')
     assert 'sf_speaker_beam_select' in _lib.EXPORTS
     assert _lib.lib.sf_speaker_beam_select.argtypes is not None
-    assert _lib.ABI_VERSION == 9 and _lib.lib.sf_abi_version() == 9
+    assert _lib.ABI_VERSION == 10 and _lib.lib.sf_abi_version() == 10
 
 
 def test_beam_select_rejects_bad_arguments_without_gpu():

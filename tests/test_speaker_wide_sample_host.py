@@ -10,7 +10,7 @@ def test_sample_max_vocab_symbol_and_abi_version():
     assert hasattr(raw, 'sf_speaker_sample_max_vocab')
     assert 'sf_speaker_sample_max_vocab' in _lib.EXPORTS
     assert _lib.lib.sf_speaker_sample_max_vocab() == 4096
-    assert _lib.ABI_VERSION == 9 and _lib.lib.sf_abi_version() == 9      # additive: the version stays
+    assert _lib.ABI_VERSION == 10 and _lib.lib.sf_abi_version() == 10     # (additive; 10 is the removal of the retired schedules' fields)
 
 
 def test_check_sample_vocab():

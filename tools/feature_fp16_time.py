@@ -26,7 +26,7 @@ sys.argv = _argv
 from speaker_follower_amd import synth, features, follower             # noqa: E402
 from speaker_follower_amd._lib import kernel_profile                    # noqa: E402
 
-TABLE_KERNELS = ('pair_vis_small_kernel', 'pair_vis_text', 'visual_attn', 'score', 'follower_glue')
+TABLE_KERNELS = ('pair_vis_small_kernel', 'visual_attn', 'score', 'follower_glue')
 
 
 def spread(xs):

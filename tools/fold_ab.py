@@ -1,6 +1,6 @@
 """A/B of the inference decode chain on the headline batch (100 x 20 steps, hipGraph replay, ms per rollout):
-unfolded (round 5's six launches behind the cell), folded text attention with four launches (partials beside r, merge
-beside scoring + glue), and the three-launch chain over the M_v / M_a products."""
+unfolded (round 5's six launches behind the cell) and folded text attention with four launches (partials beside r, merge
+beside scoring + glue)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -27,11 +27,10 @@ def timed(replay, n=40):
 
 
 ref = None
-for name, fold, chain in (('unfolded (six launches behind the cell)', False, False),
-                          ('folded, partials beside r, merge beside the glue', True, False),
-                          ('folded, three launches (M_v / M_a products)', True, True)):
+for name, fold in (('unfolded (six launches behind the cell)', False),
+                   ('folded, partials beside r, merge beside the glue', True)):
     eng = follower.FollowerEngine(enc, dec, store)
-    eng.fold_text, eng.fold_chain = fold, chain
+    eng.fold_text = fold
     replay, st = eng.capture(batch, 20, 'argmax')
     ms = [timed(replay) for _ in range(3)]
     acts = st.actions.clone()

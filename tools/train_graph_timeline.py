@@ -22,7 +22,7 @@ if 'SF_SLAB_CONSUMERS' in os.environ:
     _lib.lib.sf_debug_slab_consumers(int(os.environ['SF_SLAB_CONSUMERS']))
 if 'SF_GROUPED' in os.environ:
     _lib.lib.sf_debug_grouped_weight_gradients(int(os.environ['SF_GROUPED']))
-for k, v in os.environ.items():                       # e.g. SF_ENGINE_wgrad_chunks=2
+for k, v in os.environ.items():                       # e.g. SF_ENGINE_two_stream_backward=0
     if k.startswith('SF_ENGINE_'):
         setattr(eng, k[len('SF_ENGINE_'):], int(v))
 for _ in range(3):
