@@ -1073,6 +1073,52 @@ int sf_projected_supported(int B, int H, int L, int A, int V, int IMG, int LOC);
 /* Test switch: table rows per product of sf_projected_build (default 16 384; rows <= 0 restores it), so that a build of
  * several chunks -- the 64-bit row offsets between them -- can be checked on a small table. */
 void sf_debug_projected_chunk_rows(int rows);
+/* GATE-SPACE ROWS for the action half of the decoder LSTM's input (opt-in, additive to ABI 10; rides on the projected chain).
+ *
+ * A decode step multiplies [u_prev | f | h0] by [W_ih | W_hh]^T.  In the projected inference chain u_prev is the all-zero
+ * stop embedding or the candidate row launch (2) of the previous step chose: row (vp, cand_view) of the feature table
+ * followed by four sin/cos values, each repeated LOC/4 times (contiguous blocks, the layout `la` above groups by).  The
+ * weights are constant during inference, so that half of the product is turned round once per (table, W_ih):
+ *     gu [n_rows, 4H]   row n = x_n W_ih[:, 0:IMG]^T                                   (n_rows = n_viewpoints * V)
+ *     gl [4, 4H]        row k = sum over block k of the columns W_ih[:, IMG + k LOC/4 .. IMG + (k + 1) LOC/4)
+ *     u_prev W_ih[:, 0:F]^T = gu[vp V + cand_view] + sum_k sincos_k gl[k]               (zeros for a zero row)
+ * Launch (2) of the projected chain then also writes that [B, 4H] row for the step behind it, whose gate product runs over
+ * K = F + H instead of 2 F + H and whose cell kernel adds the row in.  Step 0 keeps the full product, and the raw u_next
+ * row is still written (the tape's xin is what it was).
+ *
+ * MEMORY AND COST: gu takes n_rows * 4H * 4 bytes -- 3.1 GB for the 10 567 viewpoints of the full R2R table at H = 512 --
+ * and the build is n_rows * IMG * 4H * 2 flop = 3.2 Tflop of fp32-class products.
+ *
+ *   sf_gate_rows_build(w_ih, table, n_rows, IMG, LOC, H, gu, gl, ws, ws_bytes, stream)
+ *                                 fills both tables from W_ih [4H, 2 (IMG + LOC)] and the fp32 table (SF_ERR_UNSUPPORTED
+ *                                 for a table registered as binary16), 16 384 table rows per product (the switch
+ *                                 sf_debug_projected_chunk_rows applies), 64-bit row offsets.  IMG % 4 == 0, LOC % 16 == 0,
+ *                                 H % 4 == 0.  Never call it inside a stream capture.
+ *   sf_gate_rows_register(table, g)
+ *                                 the tables of `table` (g == NULL forgets the address): by the feature table's ADDRESS,
+ *                                 one entry per address, 16 addresses, like sf_projected_register; key_w names the
+ *                                 decoder (sf_lstm_w.w_ih).  Same lifetime rule: alive and current while registered and
+ *                                 while a captured hipGraph that ran with them may replay.
+ *   sf_gate_rows_registered(table, out)   1 and *out (optional) when the address is registered, else 0.
+ *   sf_gate_rows_use(on) / _is_used()     process-wide switch (default on).
+ *   sf_gate_rows_steps()                  decode steps whose gate product ran on a gate-space row since the library was loaded.
+ * Taken by sf_follower_episode_fwd only, and only TOGETHER with the projected chain: every condition of that chain, the
+ * entry's key_w / V / IMG / LOC / H match the step, no dropout, 2 (IMG + LOC) + H > 1024, the bf16 weight storage of the
+ * gate product (sf_gate_product_bf16_weights) does not apply to the pair -- its packed images cover the whole W_ih -- and
+ * the workspace holds two [B, 4H] rows beside what the steps take.  Otherwise every step launches what it launched
+ * without these tables. */
+typedef struct sf_gate_rows {
+    const float *gu, *gl;
+    const float* key_w;          /* sf_lstm_w.w_ih of the decoder the tables belong to */
+    int32_t H, V, IMG, LOC;
+} sf_gate_rows;
+int sf_gate_rows_build(const float* w_ih, const float* table, long long n_rows, int IMG, int LOC, int H, float* gu, float* gl,
+                       void* ws, size_t ws_bytes, sf_stream stream);
+int sf_gate_rows_register(const void* table, const sf_gate_rows* g);
+int sf_gate_rows_registered(const void* table, sf_gate_rows* out);
+void sf_gate_rows_use(int on);
+int sf_gate_rows_is_used(void);
+long long sf_gate_rows_steps(void);
 /* A/B switch of the projected chain: 0 (the default: measured faster, 1.429 against 1.474 ms per headline rollout)
  * puts the attention partials of step t + 1 into launch (1), beside the text stage, and leaves launch (2) their merge;
  * on != 0 puts them into launch (2) (partials, ticket and merge beside the scoring; launch (1) is the text stage and y

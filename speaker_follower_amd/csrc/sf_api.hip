@@ -122,6 +122,26 @@ bool projected_lookup(const void* table, sf_projected* out) {
 }
 inline int projected_ld(int H) { return (H + 1 + 3) & ~3; }
 
+// ---- gate-space rows (include/sf_hip.h: sf_gate_rows_register) --------------------------------------------------------------
+// The same registration by the feature table's ADDRESS; an entry names the decoder by its W_ih.
+constexpr int GATE_TABLES = 16;
+struct GateEntry { const void* table; sf_gate_rows g; };
+GateEntry g_gate[GATE_TABLES];
+int g_gate_n = 0;
+std::mutex g_gate_mutex;
+std::atomic<int> g_gate_use{1};             // sf_gate_rows_use
+std::atomic<long long> g_gate_steps{0};     // sf_gate_rows_steps: decode steps whose gate product ran on a gate-space row
+bool gate_rows_lookup(const void* table, sf_gate_rows* out) {
+    if (!table || !g_gate_use.load(std::memory_order_relaxed)) return false;
+    std::lock_guard<std::mutex> lock(g_gate_mutex);
+    for (int i = 0; i < g_gate_n; ++i)
+        if (g_gate[i].table == table) {
+            *out = g_gate[i].g;
+            return true;
+        }
+    return false;
+}
+
 // the ONLY places that turn the C structs into the kernels' sources: a dense source is never half
 inline PanoSrc pano(const sf_pano* p) {
     return PanoSrc{p->dense, p->table, p->loc_table, p->vp, p->view, p->V, p->IMG, p->LOC,
@@ -221,24 +241,26 @@ bool bf16_packed(const float* w_ih, const float* w_hh, const void* (&packed)[2])
 // ---- a2 LSTMCell --------------------------------------------------------------------------------
 int lstm_fwd_i(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx, const float* h0,
                const float* c0, float* h1, float* c1, float* gates, float* h1_drop, int ld_h1_drop,
-               const Dropout& drop, Arena ar, hipStream_t st) {
-    LstmPwFwd p{};
-    p.xg = nullptr; p.b_ih = w->b_ih; p.b_hh = w->b_hh;
+               const Dropout& drop, Arena ar, hipStream_t st,
+               const float* xg = nullptr, int x_col0 = 0) {     // xg [B, 4H]: x[:, :x_col0] W_ih[:, :x_col0]^T, formed elsewhere
+    LstmPwFwd p{};                                              // (the product then starts at column x_col0 of x and W_ih)
+    p.xg = xg; p.b_ih = w->b_ih; p.b_hh = w->b_hh;
     p.c0 = c0; p.h0 = h0; p.B = B; p.H = H; p.gates = gates; p.h1 = h1; p.c1 = c1;
     p.h1_drop = h1_drop; p.ld_h1_drop = ld_h1_drop; p.drop = drop; p.lengths = nullptr;
-    if (I + H <= 1024 && H % 16 == 0) {
+    if (!xg && I + H <= 1024 && H % 16 == 0) {
         // short reduction (speaker decoder LSTMCell(300 -> 512)): one fused launch
         LstmStepArgs f{};
         f.h0 = h0; f.w_hh = w->w_hh; f.x = x; f.ldx = ldx; f.w_ih = w->w_ih; f.I = I; f.xg = nullptr;
         f.b_ih = w->b_ih; f.b_hh = w->b_hh; f.B = B; f.H = H; f.pw = p;
         return lstm_step_fused(f, st);
     }
-    Seg segs[2] = {{x, ldx, w->w_ih, I, I}, {h0, H, w->w_hh, H, H}};
+    if (!xg) x_col0 = 0;
+    Seg segs[2] = {{x + x_col0, ldx, w->w_ih + x_col0, I, I - x_col0}, {h0, H, w->w_hh, H, H}};
     LinearOut o{};
     float* slabs = nullptr;
     int ks = 1;
     const void* packed[2];
-    const bool bf16w = bf16_packed(w->w_ih, w->w_hh, packed);
+    const bool bf16w = !xg && bf16_packed(w->w_ih, w->w_hh, packed);     // (the packed images cover the whole W_ih)
     TRY(linear_nt(segs, 2, B, 4 * H, o, ar.rest(), ar.rest_n(), st, &slabs, &ks, bf16w ? packed : nullptr));
     p.slabs = slabs; p.ks = ks;
     return lstm_pointwise_fwd(p, st);
@@ -663,6 +685,57 @@ int sf_projected_build(const sf_decoder_fold* fold, const float* table, long lon
     TRY(linear_plain(loc_table, LOC, wt_v + IMG, F, nullptr, V * V, ld, LOC, EPI_NONE, lv, ld, ar, st));
     return linear_plain(sel, Ks, wt_a + IMG, Fa, nullptr, 5, ld, Ks, EPI_NONE, la, ld, ar, st);
 }
+int sf_gate_rows_build(const float* w_ih, const float* table, long long n_rows, int IMG, int LOC, int H, float* gu, float* gl,
+                       void* ws, size_t ws_bytes, sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(w_ih && table && gu && gl && n_rows > 0 && IMG > 0 && IMG % 4 == 0 && LOC > 0 && LOC % 16 == 0 && H > 0 &&
+                 H % 4 == 0);
+    if (table_is_f16(table)) return SF_ERR_UNSUPPORTED;
+    const int F = IMG + LOC, G = 4 * H, g = LOC / 4;
+    Arena ar = arena(ws, ws_bytes);
+    hipStream_t st = S(stream);
+    float* sel = ar.take((size_t)4 * LOC);      // row k: ones over block k of the location part
+    NEED(sel);
+    TRY(fill(sel, (size_t)4 * LOC, 0.f, st));
+    for (int q = 0; q < 4; ++q) TRY(fill(sel + (size_t)q * LOC + (size_t)q * g, (size_t)g, 1.f, st));
+    // gu, PROJ_CHUNK_ROWS rows of the feature table per product against the leading IMG columns of W_ih [4H, 2F] (64-bit
+    // row offsets; the products write straight into the table)
+    for (long long r0 = 0; r0 < n_rows; r0 += g_proj_chunk_rows) {
+        const int m = (int)std::min<long long>(g_proj_chunk_rows, n_rows - r0);
+        TRY(linear_plain(table + (size_t)r0 * IMG, IMG, w_ih, 2 * F, nullptr, m, G, IMG, EPI_NONE, gu + (size_t)r0 * G, G, ar, st));
+    }
+    return linear_plain(sel, LOC, w_ih + IMG, 2 * F, nullptr, 4, G, LOC, EPI_NONE, gl, G, ar, st);
+}
+int sf_gate_rows_register(const void* table, const sf_gate_rows* g) {
+    SF_CHECK_ARG(table);
+    if (g) SF_CHECK_ARG(g->gu && g->gl && g->key_w && g->H > 0 && g->H % 4 == 0 && g->V > 0 && g->IMG > 0 && g->LOC > 0);
+    std::lock_guard<std::mutex> lock(g_gate_mutex);
+    int at = -1;
+    for (int i = 0; i < g_gate_n; ++i)
+        if (g_gate[i].table == table) at = i;
+    if (!g) {                                                   // forget the address (unknown: nothing to do)
+        if (at >= 0) g_gate[at] = g_gate[--g_gate_n];
+        return SF_OK;
+    }
+    if (at < 0) {
+        if (g_gate_n == GATE_TABLES) return SF_ERR_UNSUPPORTED;
+        at = g_gate_n++;
+    }
+    g_gate[at] = GateEntry{table, *g};
+    return SF_OK;
+}
+int sf_gate_rows_registered(const void* table, sf_gate_rows* out) {
+    std::lock_guard<std::mutex> lock(g_gate_mutex);
+    for (int i = 0; i < g_gate_n; ++i)
+        if (table && g_gate[i].table == table) {
+            if (out) *out = g_gate[i].g;
+            return 1;
+        }
+    return 0;
+}
+void sf_gate_rows_use(int on) { g_gate_use.store(on ? 1 : 0, std::memory_order_relaxed); }
+int sf_gate_rows_is_used(void) { return g_gate_use.load(std::memory_order_relaxed); }
+long long sf_gate_rows_steps(void) { return g_gate_steps.load(std::memory_order_relaxed); }
 void sf_gate_product_bf16_weights(int on) { g_bf16w_on.store(on ? 1 : 0, std::memory_order_relaxed); }
 int sf_gate_product_bf16_weights_is_on(void) { return g_bf16w_on.load(std::memory_order_relaxed); }
 int sf_gate_product_bf16_supported(int M, int K1, int K2, int N) {
@@ -908,6 +981,16 @@ struct TailStep {
     const int32_t* ctx_row;
     Arena ar;
     hipStream_t st;
+    struct GateStep* gate;              // gate-space rows of the episode (null: none), see GateStep
+};
+
+// Gate-space rows through one step (sf_follower_episode_fwd): `xg_in` is the row the step before left for this step's cell
+// (null: the full gate product), `rows.xg_next` where launch (2) of the projected chain leaves the next one; `wrote` says
+// whether it did -- any other chain writes the raw u_next alone, and the next step runs the full product.
+struct GateStep {
+    const float* xg_in;
+    GateRows rows;
+    bool wrote;
 };
 
 // a launch BEHIND a chain's first one: the step is half issued, "unsupported" can no longer mean "try the next chain"
@@ -1016,9 +1099,13 @@ static int tail_proj(const TailStep& s, const TextFold& tf) {
     TRY(pair_proj_textfold(tf.ctx_q, tf.ctx_o, s.ctx_mask, B, s.L, H, tp->cat2 + H, 2 * H, f.tpart, f.tcount, f.zbuf, f.ldp,
                            tp->alpha, py, s.us, s.paired && !late ? &s.xn : nullptr, pt, tp->h1, H, f.part, s.st));
     g_proj_steps.fetch_add(1, std::memory_order_relaxed);
-    return issued(pair_proj_score(s.us, B, H, s.L, pt, f.zbuf, f.ldp, f.ybuf, f.ldp, make_glue(s.us, B, tp->logit, s.glue),
-                                  s.paired ? &s.xn : nullptr, late ? 0 : 2, tp->h1, H, s.paired ? tn->alpha_v : nullptr,
-                                  s.paired ? tn->xin + F : nullptr, 2 * F, s.dn_in, F, f.part, af.tickets(), s.st));
+    const bool gate = s.gate && s.gate->rows.xg_next && s.paired;       // (a next step exists and reads the row)
+    TRY(issued(pair_proj_score(s.us, B, H, s.L, pt, f.zbuf, f.ldp, f.ybuf, f.ldp, make_glue(s.us, B, tp->logit, s.glue),
+                               s.paired ? &s.xn : nullptr, late ? 0 : 2, tp->h1, H, s.paired ? tn->alpha_v : nullptr,
+                               s.paired ? tn->xin + F : nullptr, 2 * F, s.dn_in, F, f.part, af.tickets(), s.st,
+                               gate ? &s.gate->rows : nullptr)));
+    if (gate) s.gate->wrote = true;
+    return SF_OK;
 }
 
 // Folded text stage (inference; sf_attention.hip: text_fold_body): FOUR dependent launches behind the cell
@@ -1180,10 +1267,11 @@ static int decoder_tail_i(const sf_decoder_w* w, const sf_cands* U, int B, int H
                           const uint8_t* ctx_mask, const int32_t* ctx_row, const sf_decoder_tape* tp,
                           const sf_follower_glue* glue, const sf_dropout* drop, uint32_t step_id,
                           const sf_pano* X_next, const sf_decoder_tape* tn, void* ws, size_t ws_bytes,
-                          sf_stream stream, const TextFold* tf = nullptr) {
+                          sf_stream stream, const TextFold* tf = nullptr, GateStep* gate = nullptr) {
     SF_CHECK_ARG(w && U && h0 && c0 && ctx && tp && B > 0 && L > 0 && (!glue || glue_ok(U, glue)) &&
                  (!X_next || tn));
     TailStep s{};
+    s.gate = gate;
     s.w = w; s.us = cands(U); s.B = B; s.H = H; s.D = D; s.L = L; s.F = s.us.IMG + s.us.LOC;
     s.tp = tp; s.tn = tn; s.glue = glue;
     s.ctx = ctx; s.ctx_mask = ctx_mask; s.ctx_row = ctx_row;
@@ -1198,8 +1286,11 @@ static int decoder_tail_i(const sf_decoder_w* w, const sf_cands* U, int B, int H
     s.last_step = !X_next && !tn;              // (nothing of a next step to prepare: the text chain alone)
     const Dropout d_in = make_dropout(drop, 2 * step_id, 2);
     if (u_prev) TRY(dropout_copy(u_prev, s.F, B, s.F, tp->xin, 2 * s.F, d_in, 0, s.st));
+    // (with a gate-space row of the action half: the product over [f | h0] alone, K = F + H, the row added by the cell)
+    const float* xg = gate && !u_prev ? gate->xg_in : nullptr;
     TRY(lstm_fwd_i(&w->lstm, B, 2 * s.F, H, tp->xin, 2 * s.F, h0, c0, tp->h1, tp->c1, tp->gates,
-                   tp->cat2 + H, 2 * H, s.d_h, s.ar, s.st));
+                   tp->cat2 + H, 2 * H, s.d_h, s.ar, s.st, xg, s.F));
+    if (xg) g_gate_steps.fetch_add(1, std::memory_order_relaxed);
     return tail_dispatch(s, tf);
 }
 
@@ -1603,15 +1694,44 @@ int sf_follower_episode_fwd(const sf_decoder_w* w, const sf_follower_episode* e,
         }
         return fk.join();
     }
+    // Gate-space rows (include/sf_hip.h: sf_gate_rows_build), together with the projected chain only: launch (2) of step t
+    // leaves the chosen action's row in gate space in one of two [B, 4H] buffers carved off the FRONT of the workspace (the
+    // ticket region at its end keeps its address), step t + 1 runs its gate product over [f | h0] and its cell adds the row.
+    // Decided once, here, before the first launch; a step whose chain declines leaves `wrote` false and the step behind
+    // it runs the full product on the raw row, which every chain still writes.
+    float* xg_buf[2] = {nullptr, nullptr};
+    sf_gate_rows gr{};
+    {
+        const CandSrc us0 = cands(&cur.U);
+        const PanoSrc x0 = pano(&cur.X);
+        const int F = us0.IMG + us0.LOC;
+        const size_t row = ((size_t)e->B * 4 * e->H + 63) & ~(size_t)63;
+        const Arena whole = arena(ws, ws_bytes);
+        ProjTables pt;
+        const void* packed[2];
+        if (tf && !nav0 && !drop && e->S > 1 && e->B <= VIS_SPLIT_MAX_B && !us0.dense && !us0.half &&
+            gate_rows_lookup(us0.table, &gr) && gr.key_w == w->lstm.w_ih && gr.H == e->H && gr.V == us0.V &&
+            gr.IMG == us0.IMG && gr.LOC == us0.LOC && e->H % 4 == 0 && F % 4 == 0 && 2 * F + e->H > 1024 &&
+            projected_for(w, us0, &x0, e->B, e->H, e->L, &pt) && !bf16_packed(w->lstm.w_ih, w->lstm.w_hh, packed) &&
+            whole.tk && 2 * row <= whole.cap / 8) {
+            xg_buf[0] = (float*)ws;
+            xg_buf[1] = xg_buf[0] + row;
+            ws = xg_buf[1] + row;
+            ws_bytes -= 2 * row * sizeof(float);
+        }
+    }
+    const float* xg_in = nullptr;
     for (int t = 0; t < e->S; ++t) {
         const bool more = t + 1 < e->S;
         StepView nxt = more ? step_view(e, t + 1) : cur;
         const sf_nav_io nv = nav0 ? nav_view(nav0, e, t) : sf_nav_io{};
         if (nav0) cur.glue.nav = &nv;
         const StepState in = state_in(e, t);
+        GateStep gs{xg_in, GateRows{gr.gu, gr.gl, more ? xg_buf[t & 1] : nullptr}, false};
         TRY(decoder_tail_i(w, &cur.U, e->B, e->H, e->D, e->L, nullptr, in.h, in.c, e->ctx, e->ctx_mask,
                            nullptr, &cur.tp, &cur.glue, drop, e->step0 + t, more && !nav0 ? &nxt.X : nullptr,
-                           more ? &nxt.tp : nullptr, ws, ws_bytes, stream, tf));
+                           more ? &nxt.tp : nullptr, ws, ws_bytes, stream, tf, xg_buf[0] ? &gs : nullptr));
+        xg_in = gs.wrote ? gs.rows.xg_next : nullptr;
         if (nav0 && more)
             TRY(sf_attn_decoder_attend_fwd(&nxt.X, e->B, &nxt.tp, drop, e->step0 + t + 1, ws, ws_bytes, stream));
         cur = nxt;

@@ -1050,6 +1050,9 @@ struct ProjScoreArgs {
     const float* z;        // [B, ldz] merged text-attention sum (text_fold_body)
     const float* y;        // [B, ldy] W_out[:, H:] h1
     int ldz, ldy;
+    const float* gu;       // [n_vp * V, 4H] gate-space image rows (sf_gate_rows_build) or null
+    const float* gl;       // [4, 4H]: the four sin/cos groups of the location part in gate space
+    float* xg_next;        // [B, 4H]: the chosen action's row in gate space, for the next step's cell (null: not formed)
 };
 
 __device__ __forceinline__ void proj_score_glue_body(const ProjScoreArgs& a, const FGlue& g, int b) {
@@ -1112,25 +1115,45 @@ __device__ __forceinline__ void proj_score_glue_body(const ProjScoreArgs& a, con
         if (lane == 0 && ac < A) s_logit[ac] = d + cst;
     }
     __syncthreads();
+    // The chosen row once more in GATE space (a.xg_next; sf_gate_rows_build): u W_ih[:, :F]^T = GU[vp V + view] +
+    // sum_k sincos_k GL[k], zeros for a zero row.  One float4 per thread (H <= PRJ_CPL * 256, the block's threads:
+    // proj_tables_fit).  The four GL chunks do not depend on the choice: asked for here, while wave 0 makes it.  Without a
+    // target the same loads read the first chunk of LA: pointers and indices are selected, no load sits behind a branch.
+    const bool gate = a.xg_next != nullptr;
+    const int gc = gate ? min(tid, H - 1) : 0, gs = gate ? H : 0;
+    const float4* glp = reinterpret_cast<const float4*>(gate ? a.gl : a.la);
+    const float4 gl0 = glp[gc], gl1 = glp[gs + gc], gl2 = glp[2 * gs + gc], gl3 = glp[3 * gs + gc];
     if (wave == 0) {
         const int at = follower_glue_row(g, b, lane < A ? s_logit[lane] : 0.f, gin);
         if (lane == 0) s_at = at;
         if (g.nav.on && lane < A) nav_advance_slot(g.nav, b, lane, at, gin.was_ended || at == 0);
     }
     __syncthreads();
+    const int at = min(max(s_at, 0), A - 1);
+    const bool zero = at == 0 || at >= an || vp < 0;
+    const int view = __shfl(cvl, at, WAVE);
+    const float c0 = __shfl(scl.x, at, WAVE), c1 = __shfl(scl.y, at, WAVE), c2 = __shfl(scl.z, at, WAVE),
+                c3 = __shfl(scl.w, at, WAVE);
+    const size_t trow = (size_t)max(vp, 0) * V + min(max(view, 0), V - 1);
+    // (the GU chunk ahead of the raw row's stores: both gathers are one round trip)
+    float4 gw = (gate ? reinterpret_cast<const float4*>(a.gu) + trow * H : glp)[gc];
     if (g.u_next) {                                              // block-uniform
-        const int at = min(max(s_at, 0), A - 1);
         const int n4 = (a.src.IMG + a.src.LOC) >> 2;
         CandRow row;
-        row.zero = at == 0 || at >= an || vp < 0;
+        row.zero = zero;
         row.I4 = a.src.IMG >> 2;
         row.g4 = max(a.src.LOC >> 4, 1);
-        const int view = __shfl(cvl, at, WAVE);
-        row.img = reinterpret_cast<const float4*>(a.src.table) + ((size_t)max(vp, 0) * V + min(max(view, 0), V - 1)) * row.I4;
+        row.img = reinterpret_cast<const float4*>(a.src.table) + trow * row.I4;
         row.img16 = nullptr;
-        row.s0 = __shfl(scl.x, at, WAVE); row.s1 = __shfl(scl.y, at, WAVE);
-        row.s2 = __shfl(scl.z, at, WAVE); row.s3 = __shfl(scl.w, at, WAVE);
+        row.s0 = c0; row.s1 = c1; row.s2 = c2; row.s3 = c3;
         for (int c = tid; c < n4; c += NW * 64) store_u_next(g, b, c, cand_load<false>(row, c, !row.zero, n4));
+    }
+    if (gate && tid < H) {
+        f4fma(gw, c0, gl0);
+        f4fma(gw, c1, gl1);
+        f4fma(gw, c2, gl2);
+        f4fma(gw, c3, gl3);
+        reinterpret_cast<float4*>(a.xg_next)[(size_t)b * H + tid] = zero ? f4zero() : gw;
     }
 }
 
@@ -1713,10 +1736,13 @@ int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* ma
 // projected attention of step t + 1 (needs `counter`); `xn` null: the scoring alone
 int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt, const float* z, int ldz, const float* y, int ldy,
                     const FGlue& g, const PanoSrc* xn, int vphase, const float* h1, int ldh1, float* alpha, float* out, int ldo,
-                    const Dropout& drop, int drop_col0, float* split_part, unsigned* counter, hipStream_t st) {
+                    const Dropout& drop, int drop_col0, float* split_part, unsigned* counter, hipStream_t st,
+                    const GateRows* gate) {
     if (!proj_chain_supported(us, xn, B, H, L, pt) || !aligned4(ldz, ldy, ldh1)) return SF_ERR_UNSUPPORTED;
     if (xn && (!split_part || !aligned4(ldo) || (vphase != 0 && vphase != 2) || (vphase == 0 && !counter))) return SF_ERR_UNSUPPORTED;
-    const ProjScoreArgs a{us, pt.pa, pt.la, pt.ld, H, z, y, ldz, ldy};
+    if (gate && (!gate->gu || !gate->gl || !gate->xg_next)) return SF_ERR_UNSUPPORTED;
+    ProjScoreArgs a{us, pt.pa, pt.la, pt.ld, H, z, y, ldz, ldy};
+    if (gate) { a.gu = gate->gu; a.gl = gate->gl; a.xg_next = gate->xg_next; }
     const VisArgs va = xn ? proj_vis_args(*xn, pt, h1, ldh1, alpha, out, ldo, drop, drop_col0) : VisArgs{};
     const VisSplit sp{split_part, counter, g_trace};
     const dim3 block(SMALL_WAVES * 64);

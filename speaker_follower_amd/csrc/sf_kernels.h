@@ -231,6 +231,11 @@ struct ProjTables {
     const float *pv, *pa, *lv, *la;
     int ld, H;
 };
+// the gate-space rows of sf_gate_rows_build and where launch (2) leaves the chosen action's one for the next step's cell
+struct GateRows {
+    const float *gu, *gl;    // [n_vp * V, 4H], [4, 4H]
+    float* xg_next;          // [B, 4H]
+};
 bool proj_chain_supported(const CandSrc& us, const PanoSrc* xn, int B, int H, int L, const ProjTables& pt);
 int proj_attention_alone(const PanoSrc& x, int B, const ProjTables& pt, const float* h1, int ldh1, float* alpha, float* out,
                          int ldo, int late, float* split_part, unsigned* counter, hipStream_t st);
@@ -246,7 +251,8 @@ int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* ma
                        hipStream_t st);
 int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt, const float* z, int ldz, const float* y, int ldy,
                     const FGlue& g, const PanoSrc* xn, int vphase, const float* h1, int ldh1, float* alpha, float* out, int ldo,
-                    const Dropout& drop, int drop_col0, float* split_part, unsigned* counter, hipStream_t st);
+                    const Dropout& drop, int drop_col0, float* split_part, unsigned* counter, hipStream_t st,
+                    const GateRows* gate = nullptr);
 
 struct FGlue;
 int follower_glue_fwd(const FGlue& g, hipStream_t st);

@@ -53,6 +53,15 @@ def cand_sincos(rel_heading, rel_elevation):
     return np.stack((np.sin(h), np.cos(h), np.sin(e), np.cos(e)), axis=-1).astype(np.float32)
 
 
+def gate_loc_groups(w_loc):
+    """[4, N] float64 from the location columns w_loc [N, loc] of a weight applied to candidate rows: row k is the sum of
+    block k (loc/4 contiguous columns) -- the k-th of `cand_sincos`'s four values fills exactly that block of a candidate
+    row, so the location part contributes sum_k sincos_k * row k.  What the library's `gl` table holds (sf_gate_rows_build)."""
+    w = np.asarray(w_loc, np.float64)
+    g = w.shape[1] // 4
+    return np.stack([w[:, k * g:(k + 1) * g].sum(axis=1) for k in range(4)])
+
+
 DTYPES = {'fp32': torch.float32, 'fp16': torch.float16}
 FILE_DTYPES = {'fp32': 'float32', 'fp16': 'float16'}     # the "dtype" key of '<bin>.json' (absent: float32)
 CHECK_ROWS = 256        # viewpoint rows rounded / checked at a time (never a second copy of the whole table)
@@ -114,6 +123,15 @@ def _forget_projected(addr, pv):
     _lib.lib.sf_projected_register(C.c_void_p(addr), None)
 
 
+def _forget_gate_rows(addr, gu):
+    """The same for the gate-space rows of the table at `addr` (`gu`: only if its gu table still lives there)."""
+    if gu is not None:
+        cur = _lib.GateRows()
+        if not _lib.lib.sf_gate_rows_registered(C.c_void_p(addr), C.byref(cur)) or cur.gu != gu:
+            return
+    _lib.lib.sf_gate_rows_register(C.c_void_p(addr), None)
+
+
 class FeatureStore:
     """The feature table in HBM + viewpoint-id index.
 
@@ -156,7 +174,9 @@ class FeatureStore:
                 weakref.finalize(self, _lib.lib.sf_feature_table_f16, C.c_void_p(addr), 0)
             # ... and a projected-table entry of a collected store that lived at this address (`projected` below)
             call('sf_projected_register', C.c_void_p(addr), None)
+            call('sf_gate_rows_register', C.c_void_p(addr), None)
         self._projected = weakref.WeakKeyDictionary()       # decoder module -> its projected tables (see `projected`)
+        self._gate_rows = weakref.WeakKeyDictionary()       # decoder module -> its gate-space rows (see `gate_rows`)
         self.LOC = loc
         self.F = self.IMG + loc
         self.device = self.table.device
@@ -254,6 +274,44 @@ class FeatureStore:
                 weakref.finalize(decoder, _forget_projected, addr, bufs[0].data_ptr())
                 weakref.finalize(self, _forget_projected, addr, None)
         call('sf_projected_register', C.c_void_p(self.table.data_ptr()), C.byref(hit['struct']))
+        return hit
+
+    # ---- gate-space rows (include/sf_hip.h: sf_gate_rows_build) ----------------------------------
+    def gate_rows(self, decoder, build=True):
+        """The gate-space rows of (this store, `decoder`): every table row carried through the action half of the decoder
+        LSTM's input weights ONCE (gu [n * V, 4H], gl [4, 4H]), so that a step of the projected chain takes its gate product
+        over K = F + H instead of 2 F + H (include/sf_hip.h).  Kept beside the projected tables with the same policy:
+        cached per decoder, rebuilt IN PLACE when `weight_ih`'s version counter or the table changes, dropped with the
+        store or the decoder, `build=False` returns them only if they exist (refreshed), else None; None for an fp16
+        store.  Costs n * V * 4H * 4 bytes (3.1 GB for the full R2R table at H = 512).  The callers ask for them only
+        where the projected tables are in use (FollowerEngine)."""
+        from .model import decoder_params                        # (model imports this module)
+        from .runtime import weight_key, ws_args
+        if self.dtype != 'fp32' or not self.table.numel() or self.IMG % 4 or self.LOC % 16:
+            return None
+        hit = self._gate_rows.get(decoder)
+        if hit is None and not build:
+            return None
+        w_ih = decoder_params(decoder)[0]
+        key = weight_key(w_ih) + (self.table.data_ptr(), self.table._version)
+        if hit is None or hit['key'] != key:
+            H = decoder.hidden_size
+            if H % 4 or decoder.feature_size != self.F or tuple(w_ih.shape) != (4 * H, 2 * self.F):
+                return None
+            rows = self.n * self.V
+            new = lambda r: torch.empty(r, 4 * H, device=self.device, dtype=torch.float32)  # noqa: E731
+            bufs = hit['bufs'] if hit is not None and hit['bufs'][0].shape == (rows, 4 * H) else (new(rows), new(4))
+            call('sf_gate_rows_build', ptr(w_ih), ptr(self.table), rows, self.IMG, self.LOC, H, ptr(bufs[0]), ptr(bufs[1]),
+                 *ws_args(self.device))
+            struct = _lib.GateRows(bufs[0].data_ptr(), bufs[1].data_ptr(), w_ih.data_ptr(), H, self.V, self.IMG, self.LOC)
+            first = hit is None
+            hit = dict(key=key, bufs=bufs, struct=struct, builds=(0 if first else hit['builds']) + 1)
+            self._gate_rows[decoder] = hit
+            if first:
+                addr = self.table.data_ptr()
+                weakref.finalize(decoder, _forget_gate_rows, addr, bufs[0].data_ptr())
+                weakref.finalize(self, _forget_gate_rows, addr, None)
+        call('sf_gate_rows_register', C.c_void_p(self.table.data_ptr()), C.byref(hit['struct']))
         return hit
 
     def note_unprojected(self, decoder):

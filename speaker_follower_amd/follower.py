@@ -244,6 +244,25 @@ class projected_pass:
         return False
 
 
+class gate_rows_pass:
+    """`with gate_rows_pass(on):` -- whether the projected decode steps issued inside look the gate-space rows up
+    (sf_gate_rows_use; process-wide like projected_pass).  Restores the switch on exit."""
+
+    def __init__(self, on):
+        self.on = int(bool(on))
+
+    def __enter__(self):
+        self.prev = int(_lib.lib.sf_gate_rows_is_used())
+        if self.prev != self.on:
+            _lib.lib.sf_gate_rows_use(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        if self.prev != self.on:
+            _lib.lib.sf_gate_rows_use(self.prev)
+        return False
+
+
 class FollowerEngine:
     def __init__(self, encoder, decoder, store, group=None):
         self.encoder, self.decoder, self.store = encoder, decoder, store
@@ -266,6 +285,7 @@ class FollowerEngine:
         self.fallbacks = 0              # rollouts re-issued on the per-step kernels after a persistent-launch fault (run)
         self._gate_weights = 'fp32'
         self._project = 'auto'
+        self.gate_rows = True           # projected rollouts: the action half of the LSTM input as a gate-space row (below)
         self._capturing = False         # inside capture() / capture_sharded(): 'auto' builds the projected tables
 
     # Whether inference rollouts score and attend on the PROJECTED feature tables of (store, decoder) -- two dependent
@@ -310,6 +330,16 @@ class FollowerEngine:
         if hit is None and self._project == 'auto' and not self._capturing:
             self.store.note_unprojected(self.decoder)
         return hit
+
+    def _gate_rows_tables(self, projected, train):
+        """The gate-space rows (include/sf_hip.h: sf_gate_rows_build; FeatureStore.gate_rows) a rollout that runs on the
+        projected tables `projected` may use now, or None.  They ride on the projected chain and follow its policy: built
+        where that policy builds (`project = True`, or 'auto' inside capture()), otherwise used only if they exist.  Never
+        with `gate_weights = 'bf16'` (the packed images cover the whole W_ih) and never with `gate_rows = False`: such
+        rollouts launch the gate product over the whole input, bit for bit what they did without the tables."""
+        if projected is None or not self.gate_rows or self.pass_gate_weights(train) != 'fp32':
+            return None
+        return self.store.gate_rows(self.decoder, build=self._project is True or self._capturing)
 
     # How the decoder LSTM's weights are stored for the gate product of INFERENCE passes: 'fp32' (default) or 'bf16'
     # (include/sf_hip.h: sf_gate_product_bf16_weights -- the product of the unrounded activations with the weights rounded
@@ -445,6 +475,7 @@ class FollowerEngine:
         pipelined = self.pipelined and not on_device_env
         st.episode = None
         st.projected, st.projected_tables = False, None
+        st.gate_rows, st.gate_rows_tables = False, None
         # the same one-call episode for a device-resident environment (the env step inside every scoring + glue launch,
         # the attention of step t + 1 behind it): no host work between the launches of a TRAINING rollout either, and
         # the backward takes the two-stream episode path
@@ -486,10 +517,12 @@ class FollowerEngine:
             # ... on the projected tables of (store, decoder) where the policy has them (`project` above): the library
             # takes the two-launch chain for every step it applies to and says how many it issued
             st.projected_tables = self._projected_tables(B, T=T, A=A) if (st.text_folded and not nav_episode) else None
-            with projected_pass(st.projected_tables is not None):
-                before = _lib.lib.sf_projected_steps()
+            st.gate_rows_tables = self._gate_rows_tables(st.projected_tables, training)
+            with projected_pass(st.projected_tables is not None), gate_rows_pass(st.gate_rows_tables is not None):
+                before, gate_before = _lib.lib.sf_projected_steps(), _lib.lib.sf_gate_rows_steps()
                 call('sf_follower_episode_fwd', byref(dw), byref(ep), *ws)
                 st.projected = _lib.lib.sf_projected_steps() > before
+                st.gate_rows = _lib.lib.sf_gate_rows_steps() > gate_before
             st.episode = (ep, dw)
         tapes = [] if st.episode else [_lib.DecoderTape(*(st.tape[k][t].data_ptr() for k in _TAPE_KEYS))
                                        for t in range(S)]
@@ -604,7 +637,7 @@ class FollowerEngine:
             st.loss = st.loss_buf.reshape(())
         return st
 
-    def _baked_pointers(self, gate_weights='fp32', projected=False):
+    def _baked_pointers(self, gate_weights='fp32', projected=False, gate_rows=False):
         """Every weight-side device pointer a captured rollout bakes into its hipGraph: the parameters
         and their derived copies (transposed layouts, the encoder's [vocab,4H] table, with
         gate_weights = 'bf16' the packed images of the decoder LSTM's weights).  Building the
@@ -626,6 +659,9 @@ class FollowerEngine:
             # (refreshed in place here when a weight they depend on changed; re-allocated or gone: the bytes differ)
             hit = self.store.projected(self.decoder, build=False)
             tables = b'projected' + (bytes(hit['struct']) if hit is not None else b'')
+        if gate_rows:
+            hit = self.store.gate_rows(self.decoder, build=False)
+            tables += b'gate_rows' + (bytes(hit['struct']) if hit is not None else b'')
         return ew + bytes(dw) + packed + tables
 
     @contextlib.contextmanager
@@ -637,15 +673,15 @@ class FollowerEngine:
         finally:
             self._capturing = prev
 
-    def _guarded(self, graph_replay, projected=False):
+    def _guarded(self, graph_replay, projected=False, gate_rows=False):
         mode = self._gate_weights          # (the captured rollouts ran train=False under no_grad: this mode, for good)
-        baked = self._baked_pointers(mode, projected)
+        baked = self._baked_pointers(mode, projected, gate_rows)
 
         def replay():
             # weights updated since capture (optimizer.step, load_state_dict)?  Their derived copies are
             # rebuilt in place here, ahead of the replay on the same stream, so the graph reads current
             # data everywhere.  A MOVED tensor cannot be patched into the graph: refuse.
-            if self._baked_pointers(mode, projected) != baked:
+            if self._baked_pointers(mode, projected, gate_rows) != baked:
                 raise WeightsMoved('a weight (or one of its cached layouts) moved since this rollout was '
                                    'captured; capture() again')
             graph_replay()
@@ -696,7 +732,7 @@ class FollowerEngine:
                 self.site_next += st.site_stride
                 self.iteration += 1
             graph.replay()
-        return self._guarded(graph_replay, st.projected), st
+        return self._guarded(graph_replay, st.projected, st.gate_rows), st
 
     def capture_training(self, batch, steps, feedback='sample', optimizers=(), zero=None):
         """hipGraph of ONE WHOLE TRAINING ITERATION (follower.py:1001-1020 + train.py:263-268): zero the gradients,
@@ -799,7 +835,7 @@ class FollowerEngine:
                 call('sf_add_f32', ptr(total), ptr(st.sum_cnt), total.numel(), stream())
             call('sf_loss_finalize', ptr(total), steps, ptr(loss_buf), ptr(gscale), stream())
 
-        return self._guarded(replay_all, any(st.projected for st in states)), states, loss_buf
+        return self._guarded(replay_all, any(st.projected for st in states), any(st.gate_rows for st in states)), states, loss_buf
 
     # ------------------------------------------------------------------------------ backward
     def _backward(self, st, dloss):
