@@ -1502,6 +1502,52 @@ int sf_bleu_max_refs(void);
 void sf_debug_bleu_limits(int max_dict, int max_hyp, int max_ref, int max_refs);
 int sf_bleu_counts(const sf_bleu_batch* b, int32_t* err, sf_stream stream);
 
+/* Caption metrics next to BLEU (no reference counterpart: ROUGE-L and CIDEr-D as DESIGN.md section 2 defines them over
+ * the BLEU words; speaker_follower_amd/speaker_evaluation.py), additive to ABI 10.
+ *
+ * sf_caption_scores: per hypothesis the PARTS the two metrics are functions of, in ONE launch.  The inputs up to
+ * `slot` are those of sf_bleu_batch, member for member: the same dictionary ids, both forms of hypotheses, the same
+ * slot, err and refusal conventions and the same limits (the sf_bleu_max getters; sf_debug_bleu_limits lowers them
+ * for this entry too).  On top of them one table of unique n-gram keys per order n = 1..4, each sorted ascending, laid
+ * one behind the other in `keys` (n_keys1 keys of order 1, then n_keys2 of order 2, ...; an order may hold none) with
+ * the float64 idf of every key in `idf` at the same index.  A key is the packing of the n-gram's ids, first word in
+ * the lowest 16 bits, the words above the order zero -- which is why the orders have tables of their own: the 2-gram
+ * (x, 0) and the 4-gram (x, 0, 0, 0) pack alike.  An n-gram that its table does not hold has idf `idf_miss` (log N
+ * of the corpus).  Written per slot s = slot[b], with R = n_refs:
+ *   hyp_len[s]        int32    the number of words of the hypothesis
+ *   lcs[s * R + j]    int32    the length of the longest common subsequence of the hypothesis and reference j: the
+ *                              full dynamic program, a row of it per hypothesis word as a prefix maximum over the wave
+ *   hnorm2[s * 4 + n-1]        float64  the sum over the DISTINCT n-grams g of the hypothesis of (tf_h(g) idf(g))^2
+ *   dot[(s * R + j) * 4 + n-1] float64  the sum over the same g of min(tf_h(g) idf(g), tf_j(g) idf(g)) * (tf_j(g) idf(g)),
+ *                              tf_j the count of g in reference j
+ * Sums of non-negative float64 products in an order the kernel is free to choose; the device calls neither log, exp
+ * nor sqrt, uses plain stores and no atomics.  The references' norms and lengths and everything else ROUGE-L and
+ * CIDEr-D need stay on the host (speaker_evaluation.caption_scores_of).  slot[b] == -1 writes nothing; anything
+ * inconsistent writes nothing and raises err[0], as in sf_bleu_counts.
+ *   SF_ERR_ARG on NULL pointers, a negative table size and whatever sf_bleu_counts answers it for;
+ *   SF_ERR_UNSUPPORTED, with nothing launched, above the limits of sf_bleu_counts. */
+typedef struct sf_caption_batch {
+    int32_t n_hyps, n_slots, n_refs, n_dict;
+    int32_t max_hyp, max_ref;          /* host copies of the longest hypothesis (packed form) / reference */
+    int32_t S, word_bytes, eos, n_vocab; /* matrix form */
+    const int32_t* hyp_ids;            /* packed form: [hyp_off[n_hyps]] dictionary ids */
+    const int32_t* hyp_off;            /* packed form: [n_hyps + 1] */
+    const void* words;                 /* matrix form: [S, n_hyps] vocabulary ids */
+    const int32_t* remap;              /* matrix form: [n_vocab, 2] vocabulary id -> its dictionary ids, -1: none */
+    const int32_t* ref_ids;            /* [ref_off[n_slots * n_refs]] dictionary ids */
+    const int32_t* ref_off;            /* [n_slots * n_refs + 1] */
+    const int32_t* slot;               /* [n_hyps] */
+    int32_t n_keys1, n_keys2, n_keys3, n_keys4;   /* the sizes of the four tables */
+    const uint64_t* keys;              /* [n_keys1 + .. + n_keys4] (at least one element: never NULL) */
+    const double* idf;                 /* the idf of every key */
+    double idf_miss;                   /* the idf of an n-gram outside its table: log N */
+    int32_t* hyp_len;                  /* [n_slots] */
+    int32_t* lcs;                      /* [n_slots, n_refs] */
+    double* dot;                       /* [n_slots, n_refs, 4] */
+    double* hnorm2;                    /* [n_slots, 4] */
+} sf_caption_batch;
+int sf_caption_scores(const sf_caption_batch* b, int32_t* err, sf_stream stream);
+
 /* In-process kernel timing (no reference counterpart; what bench.py's `roofline.kernels` table is
  * measured with).  Between sf_profile_begin() and sf_profile_end() every kernel ANY host thread of the
  * process launches through this library (torch runs backward() on its own thread) carries a start and a stop event on its own dispatch, so a

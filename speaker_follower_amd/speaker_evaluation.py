@@ -16,6 +16,11 @@ n-gram totals for n = 1..4, the hypothesis length, the closest reference length 
   * `SpeakerEvaluation`              eval_speaker.py's class: `score_results`, `score_file` with the reference's contract,
                                      and `score_speaker`: agent.test() + score_results as one device sweep with one host
                                      sync, the words counted where the decode left them.
+  * `caption_parts_rows`             (no reference counterpart) the parts of ROUGE-L and CIDEr-D per path in plain Python:
+                                     the SPECIFICATION of sf_caption_scores (csrc/sf_caption.hip); `caption_corpus` and
+                                     `caption_static_rows` are what they need of the references alone
+  * `caption_scores_of`              the one place the two scores are formed, for host and device counting alike;
+                                     `SpeakerEvaluation(..., caption_metrics=True)` is the switch
 
 Nothing here imports torch before a device is asked for, and nothing imports the reference.
 """
@@ -124,6 +129,120 @@ def single_bleu(references, hypotheses):
     return multi_bleu([[ref] for ref in references], hypotheses)
 
 
+# --------------------------------------------------------------------------------- caption metrics: ROUGE-L and CIDEr-D
+CAPTION_BETA = 1.2                                                       # ROUGE-L's weight of recall
+CAPTION_SIGMA = 6.0                                                      # CIDEr-D's length penalty
+PARTS = ('hyp_len', 'lcs', 'dot', 'hnorm2')
+
+
+def _ngram_counts(sentence, n):
+    """n-gram -> its count, in the order of first occurrence."""
+    return Counter(tuple(sentence[s:s + n]) for s in range(len(sentence) - n + 1))
+
+
+def _lcs(a, b):
+    """The length of the longest common subsequence: the full dynamic program, row by row."""
+    prev = [0] * (len(b) + 1)
+    for x in a:
+        cur = [0]
+        for j, y in enumerate(b):
+            cur.append(max(cur[j], prev[j] + 1 if x == y else prev[j + 1]))
+        prev = cur
+    return prev[-1]
+
+
+def caption_corpus(refs):
+    """refs[i]: the reference sentences of scored path i -- the corpus CIDEr-D's document frequencies are counted over.
+    Returns n_paths (N), log_n and idf: per order n = 1..4 a dictionary n-gram -> log N - log max(1, df), df the number
+    of paths that hold the n-gram in at least one reference.  An n-gram outside the dictionary has df 0: idf log_n."""
+    N = len(refs)
+    log_n = math.log(N) if N else 0.0
+    idf = []
+    for n in range(1, 5):
+        df = Counter()
+        for sentences in refs:
+            df.update({gram for ref in sentences for gram in _ngram_counts(ref, n)})
+        idf.append({gram: log_n - math.log(max(1, k)) for gram, k in df.items()})
+    return dict(n_paths=N, log_n=log_n, idf=idf)
+
+
+def caption_static_rows(refs, corpus):
+    """What the two metrics need of the references alone, per path: ref_len [R] and ref_norm [R][4], the norm of every
+    reference's tf-idf vector per order.  Static per evaluator; never on the device."""
+    rows = []
+    for sentences in refs:
+        norms = []
+        for ref in sentences:
+            norms.append([])
+            for n in range(1, 5):
+                idf, acc = corpus['idf'][n - 1], 0.0
+                for gram, k in _ngram_counts(ref, n).items():
+                    v = k * idf.get(gram, corpus['log_n'])
+                    acc += v * v
+                norms[-1].append(math.sqrt(acc))
+        rows.append(dict(ref_len=[len(ref) for ref in sentences], ref_norm=norms))
+    return rows
+
+
+def caption_parts_rows(refs, hyps, corpus=None):
+    """refs[i]: the reference sentences of path i, hyps[i]: its hypothesis (lists of BLEU words: any hashable); corpus:
+    `caption_corpus` of the evaluator's scored paths (None: of `refs` themselves).  Returns per path the PARTS the two
+    metrics are functions of -- the SPECIFICATION of sf_caption_scores (csrc/sf_caption.hip):
+      hyp_len        the number of words of the hypothesis
+      lcs [R]        the LCS length of the hypothesis and reference j
+      hnorm2 [4]     per order the sum over the hypothesis' distinct n-grams g of (tf_h(g) idf(g))^2
+      dot [R][4]     per reference and order the sum over the same g of min(tf_h idf, tf_j idf) * (tf_j idf)
+    The sums run over the n-grams in the order of their first occurrence in the hypothesis; every term is >= 0."""
+    corpus = caption_corpus(refs) if corpus is None else corpus
+    rows = []
+    for sentences, hyp in zip(refs, hyps):
+        hnorm2, dot = [0.0] * 4, [[0.0] * 4 for _ in sentences]
+        for n in range(1, 5):
+            idf = corpus['idf'][n - 1]
+            tf_refs = [_ngram_counts(ref, n) for ref in sentences]
+            for gram, k in _ngram_counts(hyp, n).items():
+                w = idf.get(gram, corpus['log_n'])
+                vh = k * w
+                hnorm2[n - 1] += vh * vh
+                for j, tf in enumerate(tf_refs):
+                    vr = tf.get(gram, 0) * w
+                    dot[j][n - 1] += min(vh, vr) * vr
+        rows.append(dict(hyp_len=len(hyp), lcs=[_lcs(hyp, ref) for ref in sentences], dot=dot, hnorm2=hnorm2))
+    return rows
+
+
+def caption_scores_of(parts, static):
+    """THE place where the two scores of a path are formed: parts (a row of caption_parts_rows, or what
+    sf_caption_scores wrote for the path) and static (the path's row of caption_static_rows) -> (rouge_l, cider_d).
+    Host and device counting both end here, so ROUGE-L -- a function of integers -- agrees bit for bit, and CIDEr-D
+    to the rounding of the sums in `dot` and `hnorm2`."""
+    H, lcs, ref_len = int(parts['hyp_len']), [int(x) for x in parts['lcs']], static['ref_len']
+    rouge_l = 0.0
+    if H > 0 and lcs:
+        p = max(lcs) / H
+        r = max(k / L if L else 0.0 for k, L in zip(lcs, ref_len))
+        if p > 0 and r > 0:
+            rouge_l = ((1 + CAPTION_BETA ** 2) * p * r) / (r + CAPTION_BETA ** 2 * p)
+    total = 0.0
+    for n in range(4):
+        hnorm = math.sqrt(float(parts['hnorm2'][n]))
+        over_refs = 0.0
+        for j, L in enumerate(ref_len):
+            val = float(parts['dot'][j][n])
+            rnorm = static['ref_norm'][j][n]
+            if hnorm != 0 and rnorm != 0:
+                val /= hnorm * rnorm
+            over_refs += val * math.exp(-((H - L) ** 2) / (2 * CAPTION_SIGMA ** 2))
+        total += over_refs / len(ref_len) if ref_len else 0.0
+    return rouge_l, 10 * (total / 4)
+
+
+def caption_mean(values):
+    """The corpus value: the plain mean over the scored paths (the exactly rounded sum over their number)."""
+    values = list(values)
+    return math.fsum(values) / len(values) if values else 0.0
+
+
 # ----------------------------------------------------------------------------------------------- counting on the device
 def _cuda_device(device):
     """The torch device to count on, or None: `device` as given, else the current GPU when there is one."""
@@ -149,17 +268,11 @@ def _packed(sentences):
     return (ids if len(ids) else np.zeros(1, np.int32)), off
 
 
-def count_rows(refs, hyps, device=None):
-    """`bleu_count_rows(refs, hyps)` with the paths inside sf_bleu_counts' limits counted on `device` (None: the
-    current GPU when there is one, else everything on the host) and the others on the host and merged.  Returns
-    (rows int32 [N, 10], indices of the paths counted on the host)."""
-    N = len(hyps)
-    dev = _cuda_device(device) if N else None
-    if dev is None:
-        return bleu_count_rows(refs, hyps), list(range(N))
+def _fitting(refs, hyps, ids):
+    """The paths inside the kernels' limits (`fit`) and the others (`rest`), with the references and hypotheses of the
+    former as ids: `ids` (word -> id) is extended by every new word, in path order."""
     max_dict, max_hyp, max_ref, max_refs = bleu_limits()
     R = len(refs[0])
-    ids = {}
     fit, rest, ref_ids, hyp_ids = [], [], [], []
     for i, (sentences, hyp) in enumerate(zip(refs, hyps)):
         ok = (len(sentences) == R and 1 <= R <= max_refs and len(hyp) <= max_hyp
@@ -177,6 +290,18 @@ def count_rows(refs, hyps, device=None):
             hyp_ids.append(mine[-1])
         else:
             rest.append(i)
+    return fit, rest, ref_ids, hyp_ids, R, ids
+
+
+def count_rows(refs, hyps, device=None):
+    """`bleu_count_rows(refs, hyps)` with the paths inside sf_bleu_counts' limits counted on `device` (None: the
+    current GPU when there is one, else everything on the host) and the others on the host and merged.  Returns
+    (rows int32 [N, 10], indices of the paths counted on the host)."""
+    N = len(hyps)
+    dev = _cuda_device(device) if N else None
+    if dev is None:
+        return bleu_count_rows(refs, hyps), list(range(N))
+    fit, rest, ref_ids, hyp_ids, R, ids = _fitting(refs, hyps, {})
     rows = np.zeros((N, 10), np.int32)
     if fit:
         got = _device_rows(ref_ids, hyp_ids, R, len(ids), dev)
@@ -219,6 +344,62 @@ def _device_rows(ref_ids, hyp_ids, R, n_dict, dev):
     return got
 
 
+def caption_key_tables(corpus, ids):
+    """The idf dictionaries of a corpus as sf_caption_scores takes them: per order the unique keys (the packing of the
+    n-gram's ids, first word lowest), sorted, the four tables one behind the other, and the idf of every key."""
+    keys, idf, n_keys = [], [], []
+    for n in range(4):
+        table = sorted((sum(ids[w] << (16 * k) for k, w in enumerate(gram)), v) for gram, v in corpus['idf'][n].items())
+        keys += [k for k, _ in table]
+        idf += [v for _, v in table]
+        n_keys.append(len(table))
+    return dict(keys=np.array(keys or [0], np.uint64), idf=np.array(idf or [0.0], np.float64), n_keys=n_keys,
+                log_n=corpus['log_n'], on_device={})
+
+
+def _device_parts(ref_ids, hyp_ids, R, n_dict, tables, dev):
+    """One sf_caption_scores over packed hypotheses (path i in slot i): the rows of caption_parts_rows; None where the
+    library refuses the shapes.  The key tables go to a device once."""
+    import torch
+    from . import _lib
+    from .runtime import stream
+    N = len(hyp_ids)
+    r_ids, r_off = _packed(ref_ids)
+    h_ids, h_off = _packed(hyp_ids)
+    with torch.cuda.device(dev):
+        if str(dev) not in tables['on_device']:
+            tables['on_device'][str(dev)] = (torch.from_numpy(tables['keys'].view(np.int64)).to(dev),
+                                             torch.from_numpy(tables['idf']).to(dev))
+        keys, idf = tables['on_device'][str(dev)]
+        up = [torch.from_numpy(a).to(dev) for a in (h_ids, h_off, r_ids, r_off, np.arange(N, dtype=np.int32))]
+        ints = torch.zeros(N * (1 + R) + 1, dtype=torch.int32, device=dev)          # hyp_len, lcs, err
+        reals = torch.zeros(N * (R * 4 + 4), dtype=torch.float64, device=dev)       # dot, hnorm2
+        k = tables['n_keys']
+        b = _lib.CaptionBatch(n_hyps=N, n_slots=N, n_refs=R, n_dict=max(1, n_dict),
+                              max_hyp=int(np.diff(h_off).max()), max_ref=int(np.diff(r_off).max()),
+                              hyp_ids=up[0].data_ptr(), hyp_off=up[1].data_ptr(), ref_ids=up[2].data_ptr(),
+                              ref_off=up[3].data_ptr(), slot=up[4].data_ptr(), n_keys1=k[0], n_keys2=k[1], n_keys3=k[2],
+                              n_keys4=k[3], keys=keys.data_ptr(), idf=idf.data_ptr(), idf_miss=tables['log_n'],
+                              hyp_len=ints.data_ptr(), lcs=ints[N:].data_ptr(), dot=reals.data_ptr(),
+                              hnorm2=reals[N * R * 4:].data_ptr())
+        rc = _lib.lib.sf_caption_scores(C.byref(b), C.c_void_p(ints[N * (1 + R):].data_ptr()), stream())
+        if rc == _lib.SF_ERR_UNSUPPORTED:
+            return None
+        _lib.check(rc, 'sf_caption_scores')
+        out = torch.cat((ints.to(torch.float64), reals)).cpu().numpy()              # (the one sync; int32 is exact)
+    ints, reals = out[:len(ints)].astype(np.int64), out[len(ints):]
+    if ints[-1]:
+        raise RuntimeError('sf_caption_scores: an id outside its dictionary, or a length above the limits')
+    return _parts_of(ints[:N], ints[N:N * (1 + R)].reshape(N, R), reals[:N * R * 4].reshape(N, R, 4),
+                     reals[N * R * 4:].reshape(N, 4))
+
+
+def _parts_of(hyp_len, lcs, dot, hnorm2):
+    """The kernel's four output arrays as the rows caption_parts_rows returns."""
+    return [dict(hyp_len=int(hyp_len[i]), lcs=[int(x) for x in lcs[i]], dot=[[float(x) for x in d] for d in dot[i]],
+                 hnorm2=[float(x) for x in hnorm2[i]]) for i in range(len(hyp_len))]
+
+
 # ----------------------------------------------------------------------------------------------- eval_speaker.py:11-122
 def _paths_of(items):
     """The first item of each path_id, in order.  An env holds one item per instruction, with the instruction's text
@@ -249,9 +430,12 @@ class SpeakerEvaluation(object):
     SpeakerEvaluation(env=env)                              the items of an env (one per instruction: the first item of
                                                             each path_id is kept, the path's instructions regrouped)
     SpeakerEvaluation(items=...)                            items with 'path_id', 'scan', 'instructions'
-    device: where score_results counts (None: the current GPU when there is one, else the host; 'cpu': the host)."""
+    device: where score_results counts (None: the current GPU when there is one, else the host; 'cpu': the host).
+    caption_metrics: also score ROUGE-L and CIDEr-D over the scored paths: the summary gains
+    'rouge_l' and 'cider_d', `captions` holds the per-path parts and scores.  Off, nothing is computed or launched."""
 
-    def __init__(self, splits=None, instructions_per_path=None, env=None, items=None, device=None):
+    def __init__(self, splits=None, instructions_per_path=None, env=None, items=None, device=None,
+                 caption_metrics=False):
         if env is not None:
             items = _paths_of(env.data) if items is None else items
             splits = list(getattr(env, 'splits', [])) if splits is None else splits
@@ -283,6 +467,9 @@ class SpeakerEvaluation(object):
         self.fallbacks = 0
         self.host_syncs = self.last_host_syncs = self.sweeps = 0
         self._sweep_tables = {}
+        self.caption_metrics = bool(caption_metrics)
+        self.captions = None
+        self._caption = None                                 # what the caption metrics need of the references alone
 
     def _references(self, base_id):
         refs = self._refs.get(base_id)
@@ -356,11 +543,72 @@ class SpeakerEvaluation(object):
         model_score = np.mean(model_scores)
         self.skipped = sorted(skipped_refs)
         rows, on_host = count_rows(all_refs, all_hyps, self._device)
+        if self.caption_metrics:
+            self._set_captions(scored, *self._caption_parts(scored, all_refs, all_hyps))
         return self._summary(model_score, self._set_counts(scored, rows, on_host)), instruction_replaced_gt
 
     def _summary(self, model_score, sums):
         bleu, unpenalized_bleu, self.bleu_record = bleu_from_counts(sums)
-        return {'model_score': model_score, 'bleu': bleu, 'unpenalized_bleu': unpenalized_bleu}
+        summary = {'model_score': model_score, 'bleu': bleu, 'unpenalized_bleu': unpenalized_bleu}
+        if self.caption_metrics:
+            summary['rouge_l'] = caption_mean(self.captions['rouge_l'].values())
+            summary['cider_d'] = caption_mean(self.captions['cider_d'].values())
+        return summary
+
+    # ---- ROUGE-L and CIDEr-D (caption_metrics=True)
+    def _caption_static(self):
+        """Built once per evaluator: the scored paths (exactly instructions_per_path references; sorted), the corpus
+        their references make (document frequencies -> idf), every path's static row, and the dictionary of the
+        reference words in the order _sweep_table numbers them -- the ids the key tables are packed from."""
+        if self._caption is None:
+            scored = [pid for pid in sorted(self.gt) if len(self.gt[pid]['instructions']) == self.instructions_per_path]
+            refs = [self._references(pid) for pid in scored]
+            corpus = caption_corpus(refs)
+            ids = {}
+            for sentences in refs:
+                for ref in sentences:
+                    for w in ref:
+                        ids.setdefault(w, len(ids))
+            self._caption = dict(scored=scored, corpus=corpus, ids=ids, tables=None,
+                                 static=dict(zip(scored, caption_static_rows(refs, corpus))))
+        return self._caption
+
+    def _caption_tables(self):
+        """The key tables of the corpus, or None where they do not fit: a reference dictionary above the kernel's."""
+        st = self._caption_static()
+        if len(st['ids']) > bleu_limits()[0]:
+            return None
+        if st['tables'] is None:
+            st['tables'] = caption_key_tables(st['corpus'], st['ids'])
+        return st['tables']
+
+    def _caption_parts(self, scored, refs, hyps):
+        """`caption_parts_rows` over the evaluator's corpus, with the paths inside the kernel's limits on the device
+        and the others on the host and merged, as count_rows does for BLEU.  Returns (parts, indices on the host)."""
+        st = self._caption_static()
+        N = len(hyps)
+        dev = _cuda_device(self._device) if N else None
+        tables = self._caption_tables() if dev is not None else None
+        if tables is None:
+            return caption_parts_rows(refs, hyps, st['corpus']), list(range(N))
+        fit, rest, ref_ids, hyp_ids, R, ids = _fitting(refs, hyps, dict(st['ids']))
+        parts = [None] * N
+        if fit:
+            got = _device_parts(ref_ids, hyp_ids, R, len(ids), tables, dev)
+            if got is None:                                  # (SF_ERR_UNSUPPORTED after all: the limits moved)
+                fit, rest = [], list(range(N))
+            for i, row in zip(fit, got or []):
+                parts[i] = row
+        for i, row in zip(rest, caption_parts_rows([refs[i] for i in rest], [hyps[i] for i in rest], st['corpus'])):
+            parts[i] = row
+        return parts, rest
+
+    def _set_captions(self, path_ids, parts, on_host):
+        static = self._caption_static()['static']
+        scores = [caption_scores_of(row, static[pid]) for pid, row in zip(path_ids, parts)]
+        self.captions = dict(parts=dict(zip(path_ids, parts)), rouge_l={pid: s[0] for pid, s in zip(path_ids, scores)},
+                             cider_d={pid: s[1] for pid, s in zip(path_ids, scores)},
+                             on_host=[path_ids[i] for i in on_host])
 
     def score_file(self, output_file, verbose=False):
         with open(output_file) as f:
@@ -398,6 +646,10 @@ class SpeakerEvaluation(object):
         R = self.instructions_per_path
         scored = [pid for pid in sorted(self.gt) if len(self.gt[pid]['instructions']) == R]
         ids, ok = {}, 1 <= R <= max_refs and len(scored) > 0
+        tables = None
+        if self.caption_metrics:                             # the key tables are packed from these ids: start from them
+            tables = self._caption_tables()
+            ids, ok = dict(self._caption_static()['ids']), ok and tables is not None
         refs = []
         for pid in scored if ok else []:
             for ref in self._references(pid):
@@ -426,6 +678,15 @@ class SpeakerEvaluation(object):
                      out=torch.zeros(12, dtype=torch.int64, device=dev),             # sums [10], err, (unused)
                      rows_h=torch.zeros(len(scored), 10, dtype=torch.int32).pin_memory(),
                      out_h=torch.zeros(12, dtype=torch.int64).pin_memory())
+            if tables is not None:                           # hyp_len, lcs | dot, hnorm2 of every slot
+                if str(dev) not in tables['on_device']:
+                    tables['on_device'][str(dev)] = (torch.from_numpy(tables['keys'].view(np.int64)).to(dev),
+                                                     torch.from_numpy(tables['idf']).to(dev))
+                n = len(scored)
+                t.update(tables=tables, cap_i=torch.zeros(n * (1 + R), dtype=torch.int32, device=dev),
+                         cap_f=torch.zeros(n * (R * 4 + 4), dtype=torch.float64, device=dev),
+                         cap_i_h=torch.zeros(n * (1 + R), dtype=torch.int32).pin_memory(),
+                         cap_f_h=torch.zeros(n * (R * 4 + 4), dtype=torch.float64).pin_memory())
         self._sweep_tables = {key: t}
         return t
 
@@ -514,6 +775,9 @@ class SpeakerEvaluation(object):
             slots_d = torch.from_numpy(slots).pin_memory().to(dev, non_blocking=True)
             table['rows'].zero_()
             table['out'].zero_()
+            if self.caption_metrics:
+                table['cap_i'].zero_()
+                table['cap_f'].zero_()
             for w in fault_views(dev):                       # (whatever an earlier pass left behind is not ours)
                 w.zero_()
             ptr_of = lambda x: x.data_ptr()                  # noqa: E731
@@ -528,6 +792,18 @@ class SpeakerEvaluation(object):
                                    ref_off=ptr_of(table['ref_off']), slot=ptr_of(slots_d[k]), rows=ptr_of(table['rows']),
                                    sums=ptr_of(table['out']))
                 _lib.call('sf_bleu_counts', C.byref(b), C.c_void_p(ptr_of(table['out'][10:11])), stream())
+                if self.caption_metrics:                     # next to it: the same words, slots and fault word
+                    n, R, nk = table['n_slots'], self.instructions_per_path, table['tables']['n_keys']
+                    keys, idf = table['tables']['on_device'][str(dev)]
+                    c = _lib.CaptionBatch(n_hyps=B, n_slots=n, n_refs=R, n_dict=table['n_dict'],
+                                          max_hyp=table['max_hyp'], max_ref=table['max_ref'], S=S, word_bytes=8, eos=EOS,
+                                          n_vocab=table['n_vocab'], words=b.words, remap=b.remap, ref_ids=b.ref_ids,
+                                          ref_off=b.ref_off, slot=b.slot, n_keys1=nk[0], n_keys2=nk[1], n_keys3=nk[2],
+                                          n_keys4=nk[3], keys=ptr_of(keys), idf=ptr_of(idf),
+                                          idf_miss=table['tables']['log_n'], hyp_len=ptr_of(table['cap_i']),
+                                          lcs=ptr_of(table['cap_i'][n:]), dot=ptr_of(table['cap_f']),
+                                          hnorm2=ptr_of(table['cap_f'][n * R * 4:]))
+                    _lib.call('sf_caption_scores', C.byref(c), C.c_void_p(ptr_of(table['out'][10:11])), stream())
             handle = sweep.issue([agent._routes_of(items, store)[0] for items in drawn], after=count,
                                  clear_faults=False)
             tail = sweep.streams[(K - 1) % len(sweep.streams)]
@@ -536,6 +812,9 @@ class SpeakerEvaluation(object):
             with torch.cuda.stream(tail):
                 table['rows_h'].copy_(table['rows'], non_blocking=True)
                 table['out_h'].copy_(table['out'], non_blocking=True)
+                if self.caption_metrics:
+                    table['cap_i_h'].copy_(table['cap_i'], non_blocking=True)
+                    table['cap_f_h'].copy_(table['cap_f'], non_blocking=True)
                 faults = fault_views(dev)
                 fpin = torch.empty(len(faults), dtype=torch.int32).pin_memory()
                 fpin.copy_(torch.cat(faults) if len(faults) > 1 else faults[0], non_blocking=True)
@@ -568,6 +847,12 @@ class SpeakerEvaluation(object):
         sums = self._set_counts(scored, rows, [])
         if (sums != out[:10]).any():
             raise RuntimeError('sf_bleu_counts: the sums are not the sums of the rows')
+        if self.caption_metrics:
+            n, R = table['n_slots'], self.instructions_per_path
+            ints, reals = table['cap_i_h'].numpy(), table['cap_f_h'].numpy()
+            parts = _parts_of(ints[:n], ints[n:].reshape(n, R), reals[:n * R * 4].reshape(n, R, 4),
+                              reals[n * R * 4:].reshape(n, 4))
+            self._set_captions(scored, [parts[table['slot_of'][pid]] for pid in scored], [])
         self.skipped = sorted(pid for pid in first_of if pid not in table['slot_of'])
         if self.skipped:
             print("skipped {} instructions without {} refs: {}".format(
