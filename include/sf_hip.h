@@ -449,10 +449,8 @@ typedef struct sf_follower_episode {
     /* optional: a second stream.  BACKWARD: with it (and gtape.dcat2 / ds / dh1d) the scoring and
      * text-attention backward of step t-1 run on it while the LSTM / visual backward of step t runs on
      * `stream` (they only meet at the LSTM pointwise backward); the two are ordered with events and the
-     * call leaves `stream` behind all of the side stream's work.  FORWARD: it means exactly one thing, the two-chain
-     * schedule -- the visual half of step t + 1 on it beside the rest of step t on `stream`, ordered per step by device
-     * flags, one fork and one join per episode -- taken for pre-drawn observations, S > 1 and no
-     * ctx_q / ctx_o; every other forward pass ignores it. */
+     * call leaves `stream` behind all of the side stream's work.  FORWARD: ignored -- every forward pass runs on
+     * `stream` alone. */
     sf_stream side_stream;
     /* ABI 9, optional, INFERENCE ONLY (drop.p == 0, no backward through this pass: t_text / cat2[:H] / h_tilde of the
      * tape are NOT written; alpha is): two [B,L,H] scratch tensors.  With them sf_follower_episode_fwd forms
@@ -460,8 +458,7 @@ typedef struct sf_follower_episode {
      * attention of every step but the last in folded form -- scores ctx_q[l] . h1, h~ = tanh(sum alpha_l ctx_o[l] +
      * W_out[:, H:] h1): the same function (fp32 re-association, like q = W_v^T t_v), two dependent launches fewer per
      * decode step.  Needs w->text.w_in_t and w->action.w_a_t; pre-drawn observations or a device-resident environment
-     * (glue.nav).  The two fold products run on `stream` in front of step 0's attention; with ctx_q / ctx_o the
-     * two-chain forward schedule of `side_stream` is not taken. */
+     * (glue.nav).  The two fold products run on `stream` in front of step 0's attention. */
     float *ctx_q, *ctx_o;
 } sf_follower_episode;
 int sf_follower_episode_fwd(const sf_decoder_w* w, const sf_follower_episode* e, void* ws,

@@ -198,7 +198,7 @@ __device__ __forceinline__ void vis_stamp(const VisSplit& sp, int block, int slo
 //          accumulated in float64; a group's record holds its scores RELATIVE to its own maximum (small numbers:
 //          exact in fp32 to 1e-7 of the softmax weight, where a raw score of +-80 would carry 4e-6) and that maximum as a
 //          float64 in two dwords.
-// PROJ (the projected decode chain, sf_api.hip: tail_proj): x_v . q with q = M_v h1 + c_v is re-associated to
+// PROJ (the projected decode chain, sf_api_follower.hip: tail_proj): x_v . q with q = M_v h1 + c_v is re-associated to
 //          (x_v^T M_v) . h1 + x_v . c_v, and the bracket is a row of a table built once per (feature table, weights):
 //          score_v = (PV[row_v][:H] + LV[view * V + v][:H]) . h1 + PV[row_v][H] + LV[..][H].  The query q is never
 //          formed; the rows themselves are still loaded (the weighted sum needs them) and the record is unchanged.
@@ -1033,7 +1033,7 @@ __global__ __launch_bounds__(SC_NW * 64) void pair_score_merge_kernel(ScoreArgs 
 
 
 // =================================================================================================
-// Scoring on PROJECTED candidate rows (the projected decode chain, sf_api.hip: tail_proj).
+// Scoring on PROJECTED candidate rows (the projected decode chain, sf_api_follower.hip: tail_proj).
 // logit[b,a] = u_a . r + c with [r | c] = M_a h~ + c_a (sf_decoder_fold) re-associated to (u_a^T M_a) . h~ + u_a . c_a + c:
 // the image part of the bracket is row (vp, cand_view) of PA -- candidate rows are rows of the same panoramas -- and the
 // location part, four values each repeated LOC/4 times (cand_load), is sum_g sc_g LA[g].  LA[4] = [m | c0] is the
@@ -1584,7 +1584,7 @@ int score_bwd(const CandSrc& src, int B, const float* dlogit, float* dr, float* 
 
 // ---- paired launches (host side).  SF_ERR_UNSUPPORTED = "not pairable": the caller launches the
 // two kernels one after the other instead.  What each accepts of a small product: pair_*_accepts, which the chains of
-// sf_api.hip ask as well.
+// sf_api_follower.hip ask as well.
 int pair_small_small(const SmallPlan& a, const SmallPlan& b, hipStream_t st) {
     if (!pair_small_small_accepts(a.inst(), b.inst())) return SF_ERR_UNSUPPORTED;
     const int na = a.gx * a.gy, nb = b.gx * b.gy;
@@ -1648,7 +1648,7 @@ int pair_visbwd_small(const PanoSrc& src, int B, const float* vec, int ldvec, fl
     return launch_status();
 }
 
-// ---- the projected decode chain (sf_api.hip: tail_proj).  proj_chain_supported is the PLAN: both launchers below check
+// ---- the projected decode chain (sf_api_follower.hip: tail_proj).  proj_chain_supported is the PLAN: both launchers below check
 // it again and return SF_ERR_UNSUPPORTED before launching, but tail_proj asks first so that it declines as a whole.
 // Here: what the rule of sf_attention_plan.h cannot see -- the tables are there, candidates and panorama share one.
 bool proj_chain_supported(const CandSrc& us, const PanoSrc* xn, int B, int H, int L, const ProjTables& pt) {

@@ -1,7 +1,7 @@
 // The attention dispatch as pure host code: the shape rules of the row-set kernels (visual attention, text attention,
 // scoring), what each paired launch accepts of the small products that ride in it, and the ladders that turn a length
 // into a template value.  Each rule stands here ONCE: the launchers of sf_attention.hip gate on these predicates and the
-// launch chains of sf_api.hip ask the same ones before their first launch.  Nothing here launches or follows a pointer
+// launch chains of sf_api_follower.hip ask the same ones before their first launch.  Nothing here launches or follows a pointer
 // and no HIP header is included (tests/test_attention_plan_host.py compiles it with g++).  DESIGN.md: "Attention
 // dispatch: rules and ladders".
 #pragma once

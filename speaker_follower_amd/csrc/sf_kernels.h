@@ -139,9 +139,6 @@ int dot_rows_accum(const float* s, const float* x, int ldx, int M, int N, float*
 int sum_accum(const float* s, int M, float* out, hipStream_t st);   // out[0] += sum_m s[m]
 int fill(float* p, size_t n, float v, hipStream_t st);
 int cotenant(int blocks, int threads, int lds_bytes, long long ticks, float* sink, hipStream_t st);   // sf_debug_cotenant
-// device-flag ordering between two streams (sf_pointwise.hip)
-int flag_wait(const unsigned* flag, unsigned target, hipStream_t st);
-int flag_set(unsigned* flag, unsigned value, hipStream_t st);
 int adam_step(float* p, const float* g, float* m, float* v, size_t n, double lr, double beta1,
               double beta2, double eps, double wd, int step, hipStream_t st);
 // the same with the 1-based step counter ON THE DEVICE (incremented by the call; coef: 2 floats of scratch)

@@ -279,7 +279,6 @@ class FollowerEngine:
         self._open_forks = []            # side streams forked from the current one and not joined yet (_backward)
         self.fold_text = True            # inference rollouts: text attention over ctx W_in / ctx W_out[:, :H]^T (ABI 9)
         self.pipelined = True           # head(t+1) next to tail(t) in paired launches (sf_hip.h)
-        self.two_stream_forward = False  # experiment: visual half of step t+1 on a side stream, ordered by device flags
         self.episode_call = True        # the whole decode loop (and its backward) as ONE C call
         self.fused_env_step = True      # nav.DeviceNavBatch: the env step inside the scoring + glue launch
         self.fallbacks = 0              # rollouts re-issued on the per-step kernels after a persistent-launch fault (run)
@@ -287,6 +286,17 @@ class FollowerEngine:
         self._project = 'auto'
         self.gate_rows = True           # projected rollouts: the action half of the LSTM input as a gate-space row (below)
         self._capturing = False         # inside capture() / capture_sharded(): 'auto' builds the projected tables
+
+    # The two-chain forward schedule (the visual half of step t + 1 on a side stream) is retired: DESIGN.md section 9.
+    # The name stays because callers still assign it; asking for the schedule fails instead of measuring the default.
+    @property
+    def two_stream_forward(self):
+        return False
+
+    @two_stream_forward.setter
+    def two_stream_forward(self, on):
+        if on:
+            raise ValueError('two_stream_forward is retired (DESIGN.md section 9): the forward runs on one stream')
 
     # Whether inference rollouts score and attend on the PROJECTED feature tables of (store, decoder) -- two dependent
     # launches per decode step behind the cell instead of four (include/sf_hip.h: sf_projected_build;
@@ -501,16 +511,12 @@ class FollowerEngine:
             if nav_episode:
                 st.navio0 = batch.fused_step(0)               # (sf_nav_io of step 0; the library strides it per step)
                 ep.glue.nav = C.cast(C.pointer(st.navio0), C.c_void_p)
-            if self.two_stream_forward and not nav_episode:
-                if self._side_stream is None:
-                    self._side_stream = concurrent_stream(dev)
-                ep.side_stream = self._side_stream.cuda_stream
             # INFERENCE: the text attention in folded form (include/sf_hip.h, ABI 9: ctx_q / ctx_o; csrc/sf_attention.hip:
             # text_fold_body) -- the context is constant over the episode, so W_in and W_out[:, :H] are applied to it ONCE
             # and two dependent launches leave every decode step.  Nothing is taped for a backward, hence never for a
-            # differentiable or train-mode rollout; one stream only.
+            # differentiable or train-mode rollout.
             st.text_folded = (self.fold_text and not st.differentiable and not training
-                              and ep.side_stream is None and S > 1 and T <= 80)
+                              and S > 1 and T <= 80)
             if st.text_folded:
                 st.ctx_fold = new(2, B, T, H)
                 ep.ctx_q, ep.ctx_o = st.ctx_fold[0].data_ptr(), st.ctx_fold[1].data_ptr()

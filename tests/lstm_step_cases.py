@@ -32,8 +32,8 @@ LSTM_KS = 4                                   # :983   K-slices of the 16-row ke
 LSTMW_WAVES = 16                              # :1058  K-slices of the 32-row kernel
 BWS_WAVES = 8                                 # :1187  K-slices of the fused backward step
 FUSED_ROWS, WIDE_ROWS = 16, 32                # :990, :1064
-CELL_FUSED_MAX = 1024                         # sf_api.hip:228  I + H <= 1024 takes the fused step
-BWD_FUSED_MAX_H = 512                         # sf_api.hip:2010
+CELL_FUSED_MAX = 1024                         # sf_api.hip: lstm_fwd_i  I + H <= 1024 takes the fused step
+BWD_FUSED_MAX_H = 512                         # sf_api_encoder.hip: sf_encoder_lstm_bwd
 
 STEP_FUSED, STEP_WIDE = 'lstm_step_fused_kernel<%d>', 'lstm_step_wide_kernel<%d>'
 BWD_FUSED, PW_BWD, PW_FWD = 'lstm_bwd_step_fused_kernel<%d>', 'lstm_pw_bwd_kernel', 'lstm_pw_fwd_kernel<%d>'
@@ -66,7 +66,7 @@ def step_kernel(B, H, I=None, ldx=None):
 
 
 def bwd_step_kernel(H, w_hh_t=True):
-    """sf_encoder_lstm_bwd per step (sf_api.hip:2010) over lstm_bwd_step_fused (sf_gemm.hip:2152-2163)."""
+    """sf_encoder_lstm_bwd per step (sf_api_encoder.hip) over lstm_bwd_step_fused (sf_gemm.hip:2152-2163)."""
     if not w_hh_t or H % 16 or H > BWD_FUSED_MAX_H:
         return PW_BWD
     c = ceil_div((4 * H) >> 4, BWS_WAVES)
@@ -74,7 +74,7 @@ def bwd_step_kernel(H, w_hh_t=True):
 
 
 def cell_kernel(B, I, H, ldx=None):
-    """lstm_fwd_i (sf_api.hip:221-244): the fused step, or the gate product and `lstm_pw_fwd_kernel<KS>` for some KS."""
+    """lstm_fwd_i (sf_api.hip): the fused step, or the gate product and `lstm_pw_fwd_kernel<KS>` for some KS."""
     if I + H <= CELL_FUSED_MAX and H % 16 == 0:
         return step_kernel(B, H, I, ldx)
     return PW_FWD_PREFIX

@@ -45,7 +45,7 @@ ENC_BWD_KERNEL, ENC_BWD_BI_KERNEL = 'enc_bwd_persist_kernel', 'enc_bwd_persist_k
 
 
 def ldv(vocab):
-    """Row stride of the logits tape (sf_api.hip: sf_speaker_decode, `ldv = (vocab + 3) & ~3`)."""
+    """Row stride of the logits tape (sf_api_speaker.hip: spk_ldv)."""
     return (vocab + 3) & ~3
 
 

@@ -1,6 +1,6 @@
 """The attention dispatch asked on the host: csrc/sf_attention_plan.h holds the shape rules of the row-set kernels, what each
 paired launch accepts of its small products and the ladders that pick a template value -- pure C++ that includes no HIP
-header -- and the launchers of csrc/sf_attention.hip and the chains of csrc/sf_api.hip only ask it.
+header -- and the launchers of csrc/sf_attention.hip and the chains of csrc/sf_api_follower.hip only ask it.
 tests/attention_plan_shim.cpp wraps it; it is compiled here with g++ and loaded with ctypes.  No GPU, no HIP, nothing of the
 library itself is loaded.
 

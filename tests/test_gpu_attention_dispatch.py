@@ -30,7 +30,7 @@ The float64-score forward (visual_attn_split_f64_kernel) is held to the bound of
 3.6e-06 at max |out| 20.7).  Every exact-family case passed bit for bit on every kernel: no kernel had to leave it.
 
 Not reachable as planned, assertion kept under the planned name:
-  * "fp16 flag with a dense source -> SF_ERR_ARG": the ABI never tags a dense source as half (sf_api.hip: pano(), cands():
+  * "fp16 flag with a dense source -> SF_ERR_ARG": the ABI never tags a dense source as half (sf_api_util.h: pano(), cands():
     `dense ? 0 : table_is_f16(table)`), so a sf_pano / sf_cands that names a registered binary16 table BESIDE a dense
     tensor runs the fp32 dense kernel on the dense rows; the test asserts that (same kernel name, same bits as without
     the table pointer) -- the table is never read as fp32.

@@ -1,4 +1,4 @@
-"""GPU: WHICH kernels one training iteration of the follower launches (csrc/sf_api.hip: sf_follower_episode_bwd
+"""GPU: WHICH kernels one training iteration of the follower launches (csrc/sf_api_follower.hip: sf_follower_episode_bwd
 walks the steps on one stream or on two -- heads on a side stream, tails behind their events -- and declines the second
 stream above VIS_SPLIT_MAX_B; follower.FollowerEngine._backward calls it once).  The backward counterpart of tests/test_gpu_decode_schedules.py.
 
@@ -15,7 +15,6 @@ The table is a recording of the schedules as they were BEFORE the experiment swi
 run at that commit with this module copied into it -- never a recording of the code under test.  Re-record only with a
 change that is meant to alter a schedule, and say so.
 
-two_stream_forward is left out on purpose, as it is there: its two streams order each other by spinning flag kernels.
 The two streams of the backward order each other by events only, so the profile is safe on both."""
 import json
 import os

@@ -1,4 +1,4 @@
-"""GPU: WHICH kernels each schedule of the follower's decode step launches (csrc/sf_api.hip: decoder_tail_i picks one of
+"""GPU: WHICH kernels each schedule of the follower's decode step launches (csrc/sf_api_follower.hip: decoder_tail_i picks one of
 five launch chains per step -- the projected chain, the four-launch folded chain, the paired unfolded one, its query-only
 variant for a device-resident environment, the plain step).
 
@@ -11,10 +11,7 @@ The table is a recording of the schedules as they were BEFORE the decode step wa
     python tests/test_gpu_decode_schedules.py --record tests/decode_schedules.json
 
 run at that commit with this module copied into it -- never a recording of the code under test.  Re-record only with a
-change that is meant to alter a schedule, and say so.
-
-two_stream_forward is left out on purpose: its two streams order each other by spinning flag kernels, and timing events
-on both are not worth the risk; test_gpu_follower.py::test_two_stream_forward_equals_paired_schedule covers it."""
+change that is meant to alter a schedule, and say so."""
 import json
 import os
 import sys

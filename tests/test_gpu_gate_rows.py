@@ -1,4 +1,4 @@
-"""GPU: GATE-SPACE ROWS for the action half of the decoder LSTM's input (include/sf_hip.h: sf_gate_rows_build; csrc/sf_api.hip:
+"""GPU: GATE-SPACE ROWS for the action half of the decoder LSTM's input (include/sf_hip.h: sf_gate_rows_build; csrc/sf_api_follower.hip:
 sf_follower_episode_fwd) -- launch (2) of the projected chain leaves the chosen action's row as GU[vp V + view] +
 sum_k sincos_k GL[k], and the next step's gate product runs over K = F + H instead of 2 F + H.
 

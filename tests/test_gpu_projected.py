@@ -1,4 +1,4 @@
-"""GPU: the PROJECTED decode chain (include/sf_hip.h: sf_projected_build; csrc/sf_api.hip: tail_proj) -- scores of the
+"""GPU: the PROJECTED decode chain (include/sf_hip.h: sf_projected_build; csrc/sf_api_follower.hip: tail_proj) -- scores of the
 panorama and of the candidates taken from feature-table rows carried through the folded query / scoring matrices once per
 (table, weights), two dependent launches per decode step behind the cell instead of four.
 

@@ -33,7 +33,7 @@ from speaker_follower_amd import synth                                # noqa: E4
 from oracle import np_env, np_model                                   # noqa: E402
 from tests.follower_models import full_size_models                    # noqa: E402
 
-DEFAULT_LATE = 0            # the library's default placement (csrc/sf_api.hip: g_proj_partials_late)
+DEFAULT_LATE = 0            # the library's default placement (csrc/sf_api.hip: sf_debug_projected_partials_late)
 NVP = 6
 _cache = {}
 

@@ -12,7 +12,7 @@ sys.argv = ['bench.py']
 import bench
 from speaker_follower_amd import synth, features, follower, _lib
 ROUNDS = int(os.environ.get('SF_AB_ROUNDS', '7'))
-DEFAULT_LATE = 0         # csrc/sf_api.hip: g_proj_partials_late
+DEFAULT_LATE = 0         # csrc/sf_api.hip: sf_debug_projected_partials_late
 dev = torch.device('cuda', 0)
 enc, dec, _, _ = bench.build_models(101, dev)
 enc.eval(); dec.eval()
