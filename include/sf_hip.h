@@ -304,7 +304,12 @@ int sf_eltwise_prod_scoring_bwd(const sf_scoring_w* w, const sf_scoring_g* g, co
  * writes this step's score[b] = log p(a_t) (the caller sums steps: follower.py:504-505), writes
  * u_next[b,:] = U[b, a_t, :] (optionally through the NEXT step's input dropout, so that it can land
  * directly in that step's LSTM input buffer), updates ended[b] |= (a_t == 0).  ce_term[b] / live[b]
- * receive the row's CE term and 0/1 liveness; target_used the effective targets for the backward. */
+ * receive the row's CE term and 0/1 liveness; target_used the effective targets for the backward.
+ * The sample (feedback 2): one uniform u per row, the top 24 bits of the hash of (sample_seed, sample_stream +
+ * *sample_site_dev, row0 + b), column 0 (oracle/rng.py: sample_uniforms, follower_sample).  With e = expf(l - max) over the
+ * valid candidates, the action is the first candidate with e > 0 whose inclusive float32 prefix sum exceeds u * sum e;
+ * if there is none (u * sum within an ulp of the total) it is the highest candidate with e > 0.  A candidate whose float32
+ * weight underflowed to 0 is never drawn, at u = 1 - 2^-24 either. */
 typedef struct sf_follower_glue {
     const float* is_valid;    /* [B,A] or NULL */
     const int64_t* target;    /* [B] */

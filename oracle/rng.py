@@ -46,6 +46,27 @@ def sample_uniforms(seed, stream, rows):
            (bits[:, 1] >> np.uint32(8)).astype(np.float64) / 16777216.0
 
 
+def follower_sample(masked_row, valid_row, u):
+    """float64 mirror of the follower's one-level inverse-CDF draw (speaker_follower_amd/csrc/sf_glue.h, feedback 2; the
+    reference's Categorical sample at follower.py:491-497 draws from torch's stateful generator).  masked_row [A] logits
+    (whatever stands on an invalid candidate is ignored), valid_row [A] bool with at least one finite valid logit, u the
+    row's uniform: sample_uniforms(seed, sample_stream + site word, [row0 + b])[0].  e = exp(l - max) over the valid
+    candidates and 0 elsewhere, cdf its inclusive sum in candidate order: the first valid candidate with cdf > u * sum,
+    the highest valid candidate if there is none.  Returns (action, margin): margin = the smallest |cdf_i - u * sum| / sum
+    over the valid candidates -- the device forms the same sums in fp32 (64 lanes, a 6-level shuffle scan), so a draw
+    whose margin is ~1e-6 can fall on either side there."""
+    l = np.asarray(masked_row, np.float64)
+    valid = np.asarray(valid_row, bool)
+    assert valid.any()
+    e = np.zeros(len(l))
+    e[valid] = np.exp(l[valid] - l[valid].max())
+    cdf = np.cumsum(e)
+    thr = u * cdf[-1]
+    hit = np.flatnonzero(valid & (cdf > thr))
+    a = int(hit[0]) if len(hit) else int(np.flatnonzero(valid)[-1])
+    return a, float(np.min(np.abs(cdf[valid] - thr)) / cdf[-1])
+
+
 def speaker_sample(logit_row, u1, u2, slot=32):
     """float64 mirror of the device's two-level inverse-CDF draw (speaker_follower_amd/csrc/sf_sampling.h; the
     reference's D.Categorical(probs).sample() at speaker.py:170-174 draws from torch's stateful generator, which cannot be

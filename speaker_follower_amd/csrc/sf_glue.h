@@ -133,9 +133,15 @@ __device__ __forceinline__ int follower_glue_row(const FGlue& g, int b, float ra
             const float v = __shfl_up(cdf, off, WAVE);
             if (lane >= off) cdf += v;
         }
-        const unsigned long long hit = __ballot(lane < A && valid && cdf > u);
-        const unsigned long long any = __ballot(lane < A && valid);
-        at = hit ? (int)__ffsll((long long)hit) - 1 : (63 - __clzll((long long)any));
+        // Only a lane that carries weight can be drawn (e is 0 on invalid lanes and where expf underflowed).  Every
+        // lane's prefix sum is rounded in an order of its own, so over a run of zero weights the sums are level only
+        // up to an ulp: with u * se within an ulp of the total, `cdf > u` alone could first hold in such a lane, or
+        // in none.  No lane: the highest lane that carries weight (the lane of the maximum has e == 1; a row whose
+        // valid logits are all -inf or NaN has none and keeps the highest valid lane, a row without candidates 0).
+        const unsigned long long hit = __ballot(e > 0.f && cdf > u);
+        const unsigned long long any = __ballot(e > 0.f);
+        const unsigned long long last = any ? any : __ballot(lane < A && valid);
+        at = hit ? (int)__ffsll((long long)hit) - 1 : (last ? 63 - __clzll((long long)last) : 0);
     }
     const float la = __shfl(l, at, WAVE);
     if (lane == 0) {

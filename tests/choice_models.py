@@ -9,6 +9,10 @@ themselves -- the lowest index among the maxima -- so they do not depend on `dty
     softmax_ce_bwd                   gscale * (softmax - onehot), zero rows for ignored targets
     reduce_terms / loss_finalize     per-step (sum, count), the sum of per-step means, 1 / count
     logprob_topk                     masked log-softmax and the stable descending order of the masked row
+    follower_glue(feedback=2, u=)    the sampled action: oracle.rng.follower_sample at the row's uniform, always in float64
+    follower_sample_case, sample_expectation, check_draws, check_sample_scores, chi2_softmax
+                                     the launches of test_gpu_choice_kernels.py section 6, the mirror's side of each, the
+                                     draw-by-draw rule and the chi-square test (also used by test_gpu_follower_sample.py)
 """
 import numpy as np
 
@@ -48,9 +52,18 @@ def speaker_glue(logit, target, feedback, pad, eos, ended, dtype):
     return dict(w=w, ended=out_ended, score=score, nll=nll, live=lv.astype(F32))
 
 
-def follower_glue(logit, valid, target, feedback, ended, dtype):
-    """logit float32 [B, A]; valid bool [B, A]; target int64 [B] (-1 = ignore); ended uint8 [B] before the step."""
-    assert logit.dtype == F32 and feedback in (0, 1)
+def follower_draws(masked, valid, u, eps=0.0):
+    """oracle.rng.follower_sample per row at the uniforms u * (1 + eps) -> (action int64 [B], margin float64 [B])."""
+    from oracle.rng import follower_sample
+    out = [follower_sample(masked[i], valid[i], float(u[i]) * (1.0 + eps)) for i in range(len(masked))]
+    return np.array([a for a, _ in out], np.int64), np.array([m for _, m in out], np.float64)
+
+
+def follower_glue(logit, valid, target, feedback, ended, dtype, u=None):
+    """logit float32 [B, A]; valid bool [B, A]; target int64 [B] (-1 = ignore); ended uint8 [B] before the step;
+    feedback 0 teacher / 1 argmax / 2 sample with the uniforms u float64 [B] (oracle.rng.follower_sample: the draw is
+    made in float64 whatever `dtype` is, and a row that had ended draws like any other)."""
+    assert logit.dtype == F32 and feedback in (0, 1, 2) and (feedback == 2) == (u is not None)
     B = len(logit)
     rows = np.arange(B)
     masked = np.where(valid, logit, F32(-np.inf)).astype(F32)                # follower.py:477
@@ -59,7 +72,10 @@ def follower_glue(logit, valid, target, feedback, ended, dtype):
     tgt = np.where(ended != 0, -1, target).astype(np.int64)                  # follower.py:322-328
     live = tgt >= 0
     ce = np.where(live, z - x[rows, np.maximum(tgt, 0)], 0).astype(dtype)    # CrossEntropyLoss(ignore_index=-1)
-    a = np.maximum(tgt, 0) if feedback == 0 else first_max(masked)           # follower.py:486 / 488
+    if feedback == 2:
+        a = follower_draws(masked, valid, u)[0]                              # follower.py:491-497
+    else:
+        a = np.maximum(tgt, 0) if feedback == 0 else first_max(masked)       # follower.py:486 / 488
     score = (x[rows, a] - z).astype(dtype)                                   # follower.py:504
     out_ended = ((ended != 0) | (a == 0)).astype(np.uint8)                   # follower.py:527-530
     return dict(masked=masked, a=a, target_used=tgt, ended=out_ended, score=score, ce=ce, live=live.astype(F32))
@@ -233,3 +249,223 @@ def follower_glue_case(A, via_a_num, seed=0):
             target[i] = int(rng.integers(0, n))
     return dict(logit=x, shift=sh, a_num=a_num.astype(np.int32), valid=valid, target=target, ended=ended, kind=kind,
                 tkind=tkind)
+
+
+# ----------------------------------------------------------------------------------- the follower's sampled action
+SAMPLE_SEED = 0xC0FFEE
+CLEAR = 1e-5                     # a draw whose margin (oracle.rng.follower_sample) exceeds this is out of float32's reach
+U_ONE = 1.0 - 2.0 ** -24         # the largest uniform the device forms: (2^24 - 1) / 2^24
+# global rows whose uniform at (SAMPLE_SEED, stream 1) is exactly 0 / exactly U_ONE (found by a scan of oracle.rng's
+# sample_uniforms over row ids; tests/test_choice_models_host.py re-verifies both)
+U_ZERO_AT = dict(seed=SAMPLE_SEED, stream=1, row=7078075)
+U_ONE_AT = dict(seed=SAMPLE_SEED, stream=1, row=25335644)
+U_HALF_AT = dict(seed=SAMPLE_SEED, stream=1, row=7127063)      # ... and exactly 0.5
+UNDERFLOW = 104.0                # expf(-x) is 0 in float32 for x > 103.98 (flushed) .. 104 (rounded)
+
+
+def follower_uniforms(seed, stream, row0, B):
+    """The uniforms of rows row0 .. row0 + B - 1 at (seed, stream): sf_glue.h keys the draw of row b on
+    dropout_row_key(seed + G * site, stream, row0 + b) = the key of stream + site, and takes the top 24 bits of the
+    hash of column 0 -- sample_uniforms(...)[0]."""
+    from oracle.rng import sample_uniforms
+    return sample_uniforms(seed, stream, np.arange(B, dtype=np.int64) + row0)[0]
+
+
+def softmax64(row, valid=None):
+    x = np.asarray(row, np.float64)
+    e = np.exp(x - x[valid if valid is not None else slice(None)].max())
+    if valid is not None:
+        e = np.where(valid, e, 0.0)
+    return e / e.sum()
+
+
+def chi2_softmax(counts, p, n):
+    """The chi-square test of tests/test_gpu_robustness._chi2: cells with p * n < 5 are pooled into one (and that one
+    into its neighbour while it is still below 5) -> (chi2, p-value); callers assert p-value > 1e-4."""
+    from scipy import stats
+    keep = p * n >= 5
+    obs = np.append(counts[keep], counts[~keep].sum())
+    exp = np.append(p[keep] * n, p[~keep].sum() * n)
+    if exp[-1] < 5:
+        obs[-2] += obs[-1]
+        exp[-2] += exp[-1]
+        obs, exp = obs[:-1], exp[:-1]
+    chi2 = float(((obs - exp) ** 2 / exp).sum())
+    return chi2, float(stats.chi2.sf(chi2, len(obs) - 1))
+
+
+def f32_lane_sums(e):
+    """What the glue's two float32 sums over 64 lanes make of the weights e [<= 64]: (the inclusive shuffle-up scan's
+    value in every lane, the butterfly sum).  Every lane's additions come in an order of their own, so over a run of zero
+    weights the scan need not stay level, and its last value can stand below the butterfly's sum.  Used to BUILD rows
+    on which that matters (numpy's
+    float32 exp may differ from the device's by an ulp, so this predicts the device, it does not define it)."""
+    c = np.zeros(64, F32)
+    c[:len(e)] = np.asarray(e, F32)
+    v = c.copy()
+    off = 1
+    while off < 64:
+        prev = c.copy()
+        c[off:] = prev[off:] + prev[:-off]
+        off *= 2
+    lanes = np.arange(64)
+    off = 32
+    while off:
+        v = (v + v[lanes ^ off]).astype(F32)
+        off //= 2
+    return c, v[0]
+
+
+def follower_sample_case(A, via_a_num, special=None, seed=0):
+    """Inputs of one sf_follower_glue_fwd launch with feedback 2: logits, validity, targets, flags as in
+    follower_glue_case, and the launch's (sample seed, stream, row0).  Row kinds, by position:
+      every a_num of 1 .. A; through is_valid also masks with holes: an invalid candidate between valid ones, candidate 0
+      invalid, only the last candidate valid; rows moved by SHIFTS; rows whose valid candidates span more than UNDERFLOW
+      (the head within a few units of the maximum, the tail below expf's float32 range); rows with one valid candidate.
+    special 'zero' / 'one': row `at` of the launch is the global row whose uniform is exactly 0 / U_ONE (row0 is chosen
+    for it; stream 1).  The 'zero' row has candidate 0 invalid (through is_valid) and a first valid candidate of solid
+    weight; the 'one' row has every candidate valid, a head of ordinary weights and a tail that underflows in float32,
+    drawn until f32_lane_sums predicts that a draw which looks at cdf > u * sum alone lands on the tail (case['zero_pick']):
+    either no lane exceeds u * sum and the highest valid lane is taken, or a tail lane's sum, rounded in another order
+    than the last head lane's, is the first to exceed it.  special 'half': the row's uniform is exactly 0.5 and its
+    weights are 1 in candidates (A - 1) // 2 and A - 1 and 0 in float32 elsewhere, so that u * sum is a prefix sum and
+    every float32 operation is exact: `cdf > u * sum` takes the second of the two, `>=` would take the first."""
+    rng = np.random.default_rng([3000, A, seed, int(via_a_num), {None: 0, 'zero': 1, 'one': 2, 'half': 3}[special]])
+    B = 4 * max(A, 32)                                          # (one row unclear by design still leaves 0.99 clear)
+    x, sh = shifted_rows(rng, B, A)
+    a_num = (1 + rng.permutation(B) % A).astype(np.int32)
+    at = B // 2 + 1
+    if special:
+        a_num[at] = A
+    valid = np.arange(A)[None, :] < a_num[:, None]
+    hole = np.zeros(B, np.int64)                                # 0 prefix, 1 a hole inside, 2 candidate 0 invalid, 3 last only
+    wide = np.zeros(B, bool)
+    for i in range(B):
+        n = int(a_num[i])
+        x[i, n:] = x[i, :n].max() + F32(1 + 7 * rng.random())   # masked candidates score ABOVE every valid one
+        if not via_a_num and i != at:
+            k = (i // 2) % 4
+            if k == 1 and n >= 3:
+                hole[i] = 1
+                valid[i, int(rng.integers(1, n - 1))] = False
+            elif k == 2 and n >= 2:
+                hole[i] = 2
+                valid[i, 0] = False
+            elif k == 3 and A >= 2:
+                hole[i] = 3
+                valid[i] = False
+                valid[i, A - 1] = True
+                x[i, A - 1] = x[i, 0]
+        v = np.flatnonzero(valid[i])
+        if i % 7 == 5 and len(v) >= 2 and i != at:              # a tail below float32's exp
+            wide[i] = True
+            tail = v[(len(v) + 1) // 2:] if i % 14 == 5 else v[:len(v) // 2]
+            x[i, tail] = (x[i, np.setdiff1d(v, tail)].max() - (UNDERFLOW + 2 + 30 * rng.random(len(tail)))).astype(F32)
+    stream, row0, zero_pick = seed, 1000, False
+    if special:
+        where = dict(zero=U_ZERO_AT, one=U_ONE_AT, half=U_HALF_AT)[special]
+        stream, row0 = where['stream'], where['row'] - at
+        sh[at] = 0.0
+        x[at] = (rng.standard_normal(A) * 1.5).astype(F32)
+        if special == 'zero' and not via_a_num and A >= 2:
+            valid[at, 0] = False
+        if special == 'half':                                   # two equal maxima, nothing else within float32's exp
+            x[at] -= F32(2 * UNDERFLOW)
+            x[at, [(A - 1) // 2, A - 1]] = F32(1.25)
+            wide[at] = A > 2
+        if special == 'one' and A >= 2:
+            head = (A + 1) // 2
+            for _ in range(400):
+                x[at] = (rng.standard_normal(A) * 1.5).astype(F32)
+                x[at, head:] = (x[at, :head].max() - (UNDERFLOW + 2 + 30 * rng.random(A - head))).astype(F32)
+                e = np.exp((x[at] - x[at].max()).astype(F32)).astype(F32)
+                cdf, se = f32_lane_sums(e)
+                hit = np.flatnonzero(cdf[:A] > F32(F32(U_ONE) * se))
+                zero_pick = e[hit[0] if len(hit) else A - 1] == 0
+                if zero_pick:
+                    break
+            wide[at] = True
+    target = np.zeros(B, np.int64)
+    for i in range(B):
+        v, nv = np.flatnonzero(valid[i]), np.flatnonzero(~valid[i])
+        tk = int(rng.integers(0, 4))
+        target[i] = int(rng.choice(nv)) if tk == 1 and len(nv) else (-1 if tk == 2 else int(rng.choice(v)))
+    ended = (rng.random(B) < 0.25).astype(np.uint8)
+    return dict(logit=x, shift=sh, a_num=a_num, valid=valid, target=target, ended=ended, hole=hole, wide=wide,
+                seed=SAMPLE_SEED, stream=stream, row0=row0, at=at if special else None, zero_pick=bool(zero_pick))
+
+
+# the launches of tests/test_gpu_choice_kernels.py, section 6: (A, via_a_num, special).  Every one keeps a clear share of
+# at least 0.99 (tests/test_choice_models_host.py asserts it on the mirror alone).
+SAMPLE_CASES = [(A, v, None) for A in (1, 2, 9, 16, 63, 64) for v in (False, True)] + \
+               [(A, v, s) for A in (2, 9, 16, 64) for v in (False, True) for s in ('zero', 'one')] + \
+               [(A, v, 'half') for A in (2, 16, 64) for v in (False, True)]
+
+
+def sample_expectation(case):
+    """The mirror's side of one case: dict(u, a, margin, lo, hi, clear) -- lo / hi the mirror's actions at u * (1 -+ CLEAR),
+    the two an unclear row may take."""
+    masked = np.where(case['valid'], case['logit'], F32(-np.inf)).astype(F32)
+    B = len(masked)
+    u = follower_uniforms(case['seed'], case['stream'], case['row0'], B)
+    return draw_expectation(masked, case['valid'], u)
+
+
+def draw_expectation(masked, valid, u):
+    a, margin = follower_draws(masked, valid, u)
+    lo = follower_draws(masked, valid, u, -CLEAR)[0]
+    hi = follower_draws(masked, valid, u, +CLEAR)[0]
+    return dict(u=u, a=a, margin=margin, lo=lo, hi=hi, clear=margin > CLEAR)
+
+
+def check_draws(what, a, masked, valid, ex):
+    """The draw-by-draw rule: a clear row takes the mirror's action, an unclear one the mirror's action at
+    u * (1 - CLEAR) or u * (1 + CLEAR); every action is a valid candidate whose logit is finite and whose float32 weight
+    exp(l - max) is not 0.  Returns the clear share."""
+    rows = np.arange(len(a))
+    assert ((a >= 0) & (a < masked.shape[1])).all(), what
+    clear = ex['clear']
+    l = masked[rows, a]
+    assert valid[rows, a].all() and np.isfinite(l).all(), what
+    top = np.where(valid, masked, F32(-np.inf)).max(1)
+    bad = np.flatnonzero(top - l > UNDERFLOW)
+    assert len(bad) == 0, '%s: row %d took candidate %d, %.1f below the maximum: its float32 probability is exactly 0' % (
+        what, bad[0], a[bad[0]], (top - l)[bad[0]])
+    bad = np.flatnonzero(clear & (a != ex['a']))
+    assert len(bad) == 0, '%s: %d clear rows differ from the mirror, first %d: got %d, mirror %d (u %.9g, margin %.3g)' % (
+        what, len(bad), bad[0], a[bad[0]], ex['a'][bad[0]], ex['u'][bad[0]], ex['margin'][bad[0]])
+    bad = np.flatnonzero(~clear & (a != ex['lo']) & (a != ex['hi']))
+    assert len(bad) == 0, '%s: unclear row %d took %d, the mirror allows %d or %d' % (
+        what, bad[0] if len(bad) else -1, a[bad[0]] if len(bad) else -1, ex['lo'][bad[0]] if len(bad) else -1,
+        ex['hi'][bad[0]] if len(bad) else -1)
+    return float(clear.mean())
+
+
+def check_sample_scores(what, got_score, masked, a, shift):
+    """score = log p(action taken) by check_values, the rows of every shift on their own -> [(shift, e, e32)]."""
+    rows = np.arange(len(a))
+    r = masked.astype(np.float64)[rows, a] - lse(masked, np.float64)
+    f = masked[rows, a] - lse(masked, F32)
+    out = []
+    for sh in sorted(set(shift.tolist())):
+        sel = shift == sh
+        out.append((sh,) + check_values('%s shift %g score' % (what, sh), got_score[sel], r[sel], f[sel]))
+    return out
+
+
+def chi2_rows():
+    """The fixed logit rows of the chi-square tests: (name, row float32 [A], valid bool [A])."""
+    out = []
+    for A in (9, 64):
+        for temp in (0.5, 2.5):
+            row = (np.random.default_rng([5, A]).standard_normal(A) * temp).astype(F32)
+            out.append(('A %d temp %g' % (A, temp), row, np.ones(A, bool)))
+    row = (np.random.default_rng([5, 9, 1]).standard_normal(9) * 1.5).astype(F32)
+    valid = np.ones(9, bool)
+    valid[[0, 2, 3, 6, 8]] = False                                 # 5 of 9 masked, candidate 0 and the last among them
+    row[~valid] += F32(6)                                          # (and they hold the largest numbers)
+    out.append(('A 9, 5 masked', row, valid))
+    return out
+
+
+CHI2_N, CHI2_STREAM, CHI2_ROW0 = 40000, 3, 99

@@ -12,6 +12,23 @@ the beam, rows with one valid candidate, ragged widths, logits far from zero.
                                    against float64 sums with a priori bounds (choice_models.reduce_bound /
                                    finalize_bound), steps without a live row, the entries behind T untouched
     (5, sf_logprob_topk at its edges, stands beside the older tests of that entry in tests/test_gpu_search.py)
+    6  sf_follower_glue_fwd, feedback 2 (the sampled action), and u_next at every feedback
+                                   draw by draw against the float64 mirror oracle.rng.follower_sample at the row's own
+                                   uniform; chi-square against softmax; addressing by global row, stream and site
+                                   word; u_next = the chosen row times the next step's dropout mask, bit for bit
+
+The draw-by-draw rule of section 6 (choice_models.check_draws): a row whose margin -- the smallest distance of u to a
+boundary of the float64 cdf -- exceeds 1e-5 is CLEAR and must take the mirror's action; an unclear row must take one of
+the mirror's actions at u * (1 - 1e-5) and u * (1 + 1e-5); no row is skipped; every action is a valid candidate with a
+finite logit and a float32 weight above 0.  The cases keep a clear share of at least 0.99 (asserted on the mirror alone
+in tests/test_choice_models_host.py).
+
+A bug this section found, fixed with it (csrc/sf_glue.h, follower_glue_row): the draw took the first valid lane whose
+float32 prefix sum exceeded u * sum, or the highest valid lane when none did.  Every lane's prefix sum is rounded in an
+order of its own, so behind the last candidate that carries weight the sums of an underflowed tail (expf gives 0 below
+-104) are level only up to an ulp: at u = 1 - 2^-24 the device drew a tail candidate -- probability exactly 0 in float32,
+below 1e-45 in float64 -- in 3 of the 6 rows built for it (A 9: candidate 7 of a tail 5..8; A 16: 15; A 64: 32, the first
+behind the head), through the hit as well as through the fallback.  Now only a lane with e > 0 can be drawn.
 
 Float outputs that are differences of logits and a log-sum-exp follow the rule of tests/grad_compare.py: with r the
 float64 model and f the same formula in numpy float32, e = max|got - r| <= max(K * max|f - r|, 1e-5), K = 4.  Every
@@ -28,12 +45,21 @@ Measured on an MI355X (e / e32, the worst case of each group; nothing came near 
                                         7.79e-07 / 4.81e-04   n 991, k 991, +1e4: the kernel subtracts the row maximum
                                                               before the log-sum, the float32 model adds it back first
     loss                                4.92e-05 at T 130, B 1000 (a priori bound 2.5e-03); counts, gscale zeros exact
+    sampled score, rows not shifted     6.29e-07 / 5.05e-07   A 64, a_num, the u = 0 launch                (bound 1.0e-05)
+    sampled score, rows shifted +-80    4.00e-06 / 3.87e-06   A 64, is_valid, +80                         (bound 1.5e-05)
+    sampled score, rows shifted +1e4    4.88e-04 / 4.88e-04   A 64, is_valid, the u = 0.5 launch          (bound 2.0e-03)
+    clear share of the draws            1.0000 in the 12 ordinary launches and the 8 with the u = 0 row (3 320 rows: no
+                                        unclear row came up); 127 / 128 and 255 / 256 where the u = 1 - 2^-24 or the
+                                        u = 0.5 row is unclear by construction; 0.9986 .. 0.9999 over the 40 000 rows
+                                        of a chi-square case (p-values 0.039 .. 0.54).  Every clear row took the
+                                        mirror's action.
 
 The shifted rows cost what float32 costs there -- one step of a logit near 1e4 is 9.8e-04 -- and the kernels stay within
-the float32 model's own error.  The whole module (131 tests) takes 4 to 5 s of wall time, 0.5 s of it in its slowest test
-(the beam selection at B = 64, beam 64).
+the float32 model's own error.  The whole module (216 tests) takes about 6 s of wall time, 0.7 s of it in its slowest
+test (the first chi-square case: 40 000 rows and scipy's import).
 """
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -385,3 +411,215 @@ def test_logprob_topk_of_equal_columns_is_in_column_order(n):
     assert np.array_equal(down(d_idx), order)
     assert np.array_equal(order[0], np.arange(k))
     CM.check_values('logprob_topk equal columns n %d' % n, down(d_lp), r, f)
+
+
+# ----------------------------------------------------------------- 6. the follower's sampled action (feedback 2) and u_next
+def launch_follower_glue(logit, valid, a_num, target, ended, feedback, via_a_num, seed=0, stream_id=0, row0=0, site=None):
+    """One sf_follower_glue_fwd launch without u_next on host arrays -> dict of everything it writes."""
+    from speaker_follower_amd import _lib
+    from speaker_follower_amd._lib import call
+    from speaker_follower_amd.runtime import ptr, stream
+    B, A = logit.shape
+    d_lg, d_t, d_e = (up(np.array(x)) for x in (logit, target, ended))    # (copies: the shared cases are read-only)
+    d_valid, d_anum = up(valid.astype(F32)), up(np.array(a_num))
+    d_a, d_tu = up(np.full(B, -7, np.int64)), up(np.full(B, -7, np.int64))
+    d_s, d_ce, d_l = up(poison_f32(B)), up(poison_f32(B)), up(poison_f32(B))
+    d_u = torch.zeros(B, A, 4, device='cuda')                         # (never read: u_next is NULL)
+    d_site = None if site is None else up(np.array([site, 0x7FFFFFFF], np.int32))
+    cands = _lib.Cands(d_u.data_ptr(), None, None, None, None, d_anum.data_ptr() if via_a_num else None, A, 1, 4, 0)
+    glue = _lib.FollowerGlue(None if via_a_num else d_valid.data_ptr(), d_t.data_ptr(), feedback, d_e.data_ptr(),
+                             d_a.data_ptr(), d_tu.data_ptr(), d_s.data_ptr(), None, 0, None, 0, d_ce.data_ptr(),
+                             d_l.data_ptr(), seed, stream_id, row0, None if site is None else d_site.data_ptr())
+    call('sf_follower_glue_fwd', C.byref(cands), B, ptr(d_lg), C.byref(glue), stream())
+    return dict(masked=down(d_lg), a=down(d_a), target_used=down(d_tu), ended=down(d_e), score=down(d_s),
+                ce=down(d_ce), live=down(d_l))
+
+
+def launch_sample_case(case, via_a_num, feedback=2, rows=slice(None), stream_id=None, site=None):
+    n0 = rows.start or 0
+    return launch_follower_glue(case['logit'][rows], case['valid'][rows], case['a_num'][rows], case['target'][rows],
+                                case['ended'][rows], feedback, via_a_num, case['seed'],
+                                case['stream'] if stream_id is None else stream_id, case['row0'] + n0, site)
+
+
+@functools.lru_cache(maxsize=None)
+def sample_reference(A, via_a_num, special):
+    case = CM.follower_sample_case(A, via_a_num, special)
+    ex = CM.sample_expectation(case)
+    for v in list(case.values()) + list(ex.values()):
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return case, ex
+
+
+@pytest.mark.parametrize('A,via_a_num,special', CM.SAMPLE_CASES)
+def test_follower_glue_sample_draw_by_draw(A, via_a_num, special):
+    """feedback 2 through the stand-alone kernel, every row against oracle.rng.follower_sample at the row's own uniform
+    (seed, stream, row0 + b): masks with holes, every a_num, shifted rows, tails below float32's exp, rows of one
+    candidate, and by row0 the global rows whose uniform is exactly 0, exactly 1 - 2^-24 and exactly 0.5 (on a row whose
+    prefix sum meets u * sum exactly: `>` it is, not `>=`).  Everything else the launch
+    writes is the feedback 0 launch's, bit for bit; `ended` and the score follow the action taken."""
+    case, ex = sample_reference(A, via_a_num, special)
+    what = 'follower glue sample A %d %s%s' % (A, 'a_num' if via_a_num else 'is_valid', ' u=' + special if special else '')
+    got = launch_sample_case(case, via_a_num)
+    ref = launch_sample_case(case, via_a_num, feedback=0)
+    masked = np.where(case['valid'], case['logit'], F32(-np.inf)).astype(F32)
+    assert np.array_equal(bits(got['masked']), bits(masked))
+    share = CM.check_draws(what, got['a'], masked, case['valid'], ex)
+    print('[choice] %-58s clear share %.4f, %d of %d rows' % (what, share, int(ex['clear'].sum()), len(masked)))
+    assert share >= 0.99
+    if special:
+        at = case['at']
+        assert ex['u'][at] == dict(zero=0.0, one=CM.U_ONE, half=0.5)[special]
+        print('[choice] %-58s u = %.9g: action %d (mirror %d, at u (1 + 1e-5) %d)' % (what, ex['u'][at], got['a'][at],
+                                                                                  ex['a'][at], ex['hi'][at]))
+        # 'one': the other allowed action has float32 weight 0; 'half': every float32 operation of the row is exact
+        assert got['a'][at] == ex['a'][at]
+    for key in ('masked', 'target_used', 'live', 'ce'):               # the loss does not depend on the feedback
+        assert np.array_equal(bits(got[key]), bits(ref[key])), key
+    assert np.array_equal(got['ended'], ((case['ended'] != 0) | (got['a'] == 0)).astype(np.uint8))
+    had = case['ended'] != 0
+    assert A == 1 or (got['a'][had] != 0).any()                       # a row that had ended still draws
+    CM.check_sample_scores(what, got['score'], masked, got['a'], case['shift'])
+
+
+@pytest.mark.parametrize('name,row,valid', CM.chi2_rows(), ids=[c[0] for c in CM.chi2_rows()])
+def test_follower_glue_sample_follows_softmax(name, row, valid):
+    """40 000 copies of one logit row, each with its own global row id: the counts pass the chi-square test of
+    test_gpu_robustness.py against float64 softmax, masked candidates are drawn exactly zero times, and every clear row
+    equals the mirror (here as one searchsorted over the float64 cdf)."""
+    N, A = CM.CHI2_N, len(row)
+    vm = np.tile(valid, (N, 1))
+    got = launch_follower_glue(np.tile(row, (N, 1)), vm, np.full(N, A, np.int32), np.zeros(N, np.int64),
+                               np.zeros(N, np.uint8), 2, False, CM.SAMPLE_SEED, CM.CHI2_STREAM, CM.CHI2_ROW0)
+    a = got['a']
+    assert ((a >= 0) & (a < A)).all()
+    counts = np.bincount(a, minlength=A).astype(np.float64)
+    assert not counts[~valid].any()
+    p = CM.softmax64(row, valid)
+    chi2, pval = CM.chi2_softmax(counts, p, N)
+    u = CM.follower_uniforms(CM.SAMPLE_SEED, CM.CHI2_STREAM, CM.CHI2_ROW0, N)
+    cdf = np.cumsum(p)
+    mirror = np.searchsorted(cdf / cdf[-1], u, side='right')
+    clear = np.abs(cdf[valid][None, :] / cdf[-1] - u[:, None]).min(1) > CM.CLEAR
+    print('[choice] follower sample chi-square %-16s chi2 = %.2f  p = %.4f  clear share %.4f' % (name, chi2, pval, clear.mean()))
+    assert pval > 1e-4, (chi2, pval)
+    assert clear.mean() >= 0.99 and np.array_equal(a[clear], mirror[clear])
+
+
+def test_follower_glue_sample_addressing():
+    """The draw is keyed on the GLOBAL row and on stream + site word: the rows [half, B) launched alone with row0 + half
+    draw what they draw in the full launch; (stream s, site word k) draws what (s + k, no word) draws; two streams differ
+    in at least a tenth of the rows."""
+    case, ex = sample_reference(16, False, None)
+    B = len(case['logit'])
+    half = B // 2 + 3
+    full = launch_sample_case(case, False)
+    assert np.array_equal(full['a'][ex['clear']], ex['a'][ex['clear']])
+    part = launch_sample_case(case, False, rows=slice(half, B))
+    for key in ('a', 'ended', 'score', 'ce', 'masked'):
+        assert np.array_equal(bits(part[key]), bits(full[key][half:])), key
+    assert not np.array_equal(launch_follower_glue(case['logit'][half:], case['valid'][half:], case['a_num'][half:],
+                                                   case['target'][half:], case['ended'][half:], 2, False, case['seed'],
+                                                   case['stream'], case['row0'])['a'], full['a'][half:])
+    s, k = 5, 9
+    moved = launch_sample_case(case, False, stream_id=s + k)
+    worded = launch_sample_case(case, False, stream_id=s, site=k)
+    plain = launch_sample_case(case, False, stream_id=s)
+    assert np.array_equal(worded['a'], moved['a']) and np.array_equal(bits(worded['score']), bits(moved['score']))
+    assert (plain['a'] != moved['a']).mean() >= 0.1 and (plain['a'] != full['a']).mean() >= 0.1
+    zero_word = launch_sample_case(case, False, stream_id=s, site=0)
+    assert np.array_equal(zero_word['a'], plain['a'])
+
+
+U_NEXT_B, U_NEXT_A, U_NEXT_V = 8, 5, 3
+U_NEXT_SEED, U_NEXT_STREAM = 0xD1CE, 6
+
+
+@pytest.mark.parametrize('feedback', [0, 1, 2])
+@pytest.mark.parametrize('F4', [4, 64, 65, 544, 580])
+@pytest.mark.parametrize('form', ['dense', 'fp32', 'fp16'])
+def test_follower_glue_u_next_bit_for_bit(form, F4, feedback):
+    """u_next[b, :F] = U[b, a_t, :F] times the mask of the NEXT step's input dropout -- site u_drop_stream + 2 * the
+    u_drop site word (make_glue hands the word the multiplier 2 of the decoder's 2 * step + k numbering), global row
+    u_drop.row0 + b, columns 0 .. F - 1 -- bit for bit, for dense candidates and for index-form ones on an fp32 and a
+    binary16 table (zero rows for a_t = 0, a_t >= a_num and vp < 0), with u_drop absent, p = 0.5 at a non-zero row0,
+    and p = 0.5 with a site word; ld_u_next = F and F + 8 with the poison behind column F untouched.  F / 4 = 580 >
+    64 * 9 takes the copy loop's second pass."""
+    from speaker_follower_amd import _lib
+    from speaker_follower_amd._lib import call
+    from speaker_follower_amd.runtime import ptr, stream
+    from oracle.rng import dropout_mask
+    from tests import mover_cases as MC
+    B, A, V = U_NEXT_B, U_NEXT_A, U_NEXT_V
+    F = 4 * F4
+    LOC = 0 if form == 'dense' or F4 == 4 else 16
+    IMG = F - LOC
+    rng = np.random.default_rng([F4, feedback, ('dense', 'fp32', 'fp16').index(form)])
+    vp = np.array([0, 1, 2, -1, 0, 1, 2, 0], np.int32)
+    a_num = np.array([5, 3, 1, 5, 2, 5, 4, 5], np.int32)
+    target = np.array([0, 4, 0, 2, 1, 4, 3, 2], np.int64)              # teacher: stop, behind a_num, stop, vp < 0, ...
+    logit = (rng.standard_normal((B, A)) * 2).astype(F32)
+    logit[0, 0] = logit[0].max() + F32(40)                             # argmax and (all but surely) the sample stop in row 0
+    valid = np.arange(A)[None, :] < a_num[:, None]
+    cand_view = rng.integers(-1, V + 1, (B, A)).astype(np.int32)       # (clamped into the table)
+    sincos = MC.sincos_constants(B * A).reshape(B, A, 4)
+    if form == 'dense':
+        U = (rng.standard_normal((B, A, F)) + 3).astype(F32)
+        d_U, table16 = up(U), None
+    else:
+        table16 = MC.feature_table16(V, IMG)
+        U = MC.model_candidates(table16.astype(F32), vp, cand_view, sincos, a_num, LOC)[0]
+    d_vp, d_cv, d_sc, d_an = up(vp), up(cand_view), up(sincos), up(a_num)
+    d_table = None if form == 'dense' else up(table16 if form == 'fp16' else table16.astype(F32))
+    if d_table is not None:
+        call('sf_feature_table_f16', C.c_void_p(d_table.data_ptr()), 1 if form == 'fp16' else 0)
+    try:
+        if form == 'dense':
+            cands = _lib.Cands(d_U.data_ptr(), None, None, None, None, d_an.data_ptr(), A, 1, IMG, LOC)
+        else:
+            cands = _lib.Cands(None, d_table.data_ptr(), d_vp.data_ptr(), d_cv.data_ptr(), d_sc.data_ptr(), d_an.data_ptr(),
+                               A, V, IMG, LOC)
+        seen = set()
+        for p, row0, word, ld in ((0.0, 0, None, F + 8), (0.5, 77, None, F), (0.5, 5, 3, F + 8)):
+            d_lg, d_t, d_e = up(logit), up(target), up(np.zeros(B, np.uint8))
+            d_a, d_tu = up(np.full(B, -7, np.int64)), up(np.full(B, -7, np.int64))
+            d_s, d_ce, d_l = up(poison_f32(B)), up(poison_f32(B)), up(poison_f32(B))
+            host = poison_f32(B + 1, ld)
+            d_un = up(host)
+            d_word = None if word is None else up(np.array([word, 0x7FFFFFFF], np.int32))
+            drop = _lib.Dropout(p, U_NEXT_SEED, row0, None if word is None else d_word.data_ptr(), 0) if p else None
+            glue = _lib.FollowerGlue(None, d_t.data_ptr(), feedback, d_e.data_ptr(), d_a.data_ptr(), d_tu.data_ptr(),
+                                     d_s.data_ptr(), d_un.data_ptr(), ld, C.pointer(drop) if drop else None, U_NEXT_STREAM,
+                                     d_ce.data_ptr(), d_l.data_ptr(), CM.SAMPLE_SEED, 2, 300, None)
+            call('sf_follower_glue_fwd', C.byref(cands), B, ptr(d_lg), C.byref(glue), stream())
+            a = down(d_a)
+            masked = np.where(valid, logit, F32(-np.inf)).astype(F32)
+            if feedback == 0:
+                assert np.array_equal(a, np.maximum(target, 0))
+            elif feedback == 1:
+                assert np.array_equal(a, CM.first_max(masked))
+            else:
+                u = CM.follower_uniforms(CM.SAMPLE_SEED, 2, 300, B)
+                am, margin = CM.follower_draws(masked, valid, u)
+                assert (margin > CM.CLEAR).all() and np.array_equal(a, am)
+            rows = U[np.arange(B), a]
+            if form != 'dense':
+                zero = (a == 0) | (a >= a_num) | (vp < 0)
+                assert not rows[zero].any() and rows[~zero].all()
+                seen |= {'stop'} if (a == 0).any() else set()
+                seen |= {'behind'} if (a >= a_num).any() else set()
+                seen |= {'padded'} if ((vp < 0) & (a > 0) & (a < a_num)).any() else set()
+                seen |= {'row'} if (~zero).any() else set()
+            mask = dropout_mask(U_NEXT_SEED, U_NEXT_STREAM + 2 * (word or 0), row0 + np.arange(B), F, p)
+            want = host.copy()
+            want[:B, :F] = np.where(mask != 0, rows * mask, F32(0))
+            assert p == 0 or ((mask == 0).any() and (mask == 2).any())
+            MC.same_bits(down(d_un), want, 'u_next %s F/4 %d feedback %d p %g row0 %d word %s ld %d' % (
+                form, F4, feedback, p, row0, word, ld))
+        if form != 'dense':
+            assert 'row' in seen and 'stop' in seen and (feedback != 0 or seen == {'row', 'stop', 'behind', 'padded'})
+    finally:
+        if d_table is not None:
+            torch.cuda.synchronize()
+            call('sf_feature_table_f16', C.c_void_p(d_table.data_ptr()), 0)
