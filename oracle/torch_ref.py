@@ -9,8 +9,73 @@ function computes in the dtype of the weights it is given: fp32 by default
 anchor the training-gradient tests measure both the HIP path and the fp32 reference
 against.  Inputs (features, masks) are cast to that dtype where they enter.
 """
+import contextlib
+
 import torch
 import torch.nn.functional as F
+
+# ---- rounded evaluation ---------------------------------------------------------------------------------------------
+# Off by default.  Inside `rounded(...)` the result of every operator the oracle composes (linear, bmm, softmax, tanh,
+# sigmoid, and the two sums of `lstm_cell`: the gate pre-activations and c_1) is rounded once to fp32 precision -- a model
+# of a perfect implementation that stores every operator's result in fp32.  Run on float64 weights, the distance of such
+# a run to the plain float64 one measures how far fp32 storage alone can move an output: the conditioning of the case.
+_ROUND = None          # None | ('nearest', None) | ('random', torch.Generator)
+
+
+@contextlib.contextmanager
+def rounded(mode, generator=None):
+    """mode 'nearest': x.float().double(); 'random': x * (1 + d), d uniform in +-2^-24 drawn from `generator`."""
+    global _ROUND
+    if mode not in ('nearest', 'random'):
+        raise ValueError(mode)
+    if mode == 'random' and generator is None:
+        raise ValueError('random rounding needs a torch.Generator')
+    prev, _ROUND = _ROUND, (mode, generator)
+    try:
+        yield
+    finally:
+        _ROUND = prev
+
+
+def _r(x):
+    if _ROUND is None:
+        return x
+    mode, gen = _ROUND
+    if mode == 'nearest':
+        return x.float().to(x.dtype)
+    d = (torch.rand(x.shape, generator=gen, dtype=torch.float64) * 2.0 - 1.0) * 2.0 ** -24
+    return x * (1.0 + d).to(x.dtype)
+
+
+def _linear(x, w, b=None):
+    return _r(F.linear(x, w, b))
+
+
+def _bmm(a, b):
+    return _r(torch.bmm(a, b))
+
+
+def _softmax(x, dim):
+    return _r(torch.softmax(x, dim=dim))
+
+
+def _tanh(x):
+    return _r(torch.tanh(x))
+
+
+def _sigmoid(x):
+    return _r(torch.sigmoid(x))
+
+
+def _rec(tape, name, value, per_step=True):
+    """Record a named intermediate: appended to the list tape[name] (one entry per step), or stored as tape[name]."""
+    if tape is None:
+        return
+    v = value.detach()
+    if per_step:
+        tape.setdefault(name, []).append(v)
+    else:
+        tape[name] = v
 
 
 def to_torch(state, requires_grad=False, frozen=(), dtype=torch.float32):
@@ -23,42 +88,50 @@ def to_torch(state, requires_grad=False, frozen=(), dtype=torch.float32):
     return out
 
 
-def lstm_cell(x, h, c, w_ih, w_hh, b_ih, b_hh):
-    """nn.LSTMCell (gate order i,f,g,o) as used at model.py:393, 434, 515."""
-    gates = F.linear(x, w_ih, b_ih) + F.linear(h, w_hh, b_hh)
+def lstm_cell(x, h, c, w_ih, w_hh, b_ih, b_hh, tape=None):
+    """nn.LSTMCell (gate order i,f,g,o) as used at model.py:393, 434, 515.  tape: records 'gates' (pre-activations) and
+    'gates_act' (sigmoid / tanh applied: what the HIP cell keeps for its backward)."""
+    gates = _r(_linear(x, w_ih, b_ih) + _linear(h, w_hh, b_hh))
+    _rec(tape, 'gates', gates)
     i, f, g, o = gates.chunk(4, dim=1)
-    c1 = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
-    h1 = torch.sigmoid(o) * torch.tanh(c1)
+    sf = _sigmoid(f)
+    si = _sigmoid(i)
+    tg = _tanh(g)
+    c1 = _r(sf * c + si * tg)
+    so = _sigmoid(o)
+    h1 = so * _tanh(c1)
+    if tape is not None:
+        _rec(tape, 'gates_act', torch.cat((si, sf, tg, so), 1))
     return h1, c1
 
 
 def soft_dot_attention(h, context, mask, w_in, w_out):
     """model.py:122-143.  mask True = masked; filled on .data in the reference
     (:135), i.e. outside autograd -- masked_fill gives the same gradients."""
-    target = F.linear(h, w_in)
-    attn = torch.bmm(context, target.unsqueeze(2)).squeeze(2)
+    target = _linear(h, w_in)
+    attn = _bmm(context, target.unsqueeze(2)).squeeze(2)
     if mask is not None:
         attn = attn.masked_fill(mask, float('-inf'))
-    attn = torch.softmax(attn, dim=1)
-    weighted = torch.bmm(attn.unsqueeze(1), context).squeeze(1)
-    h_tilde = torch.tanh(F.linear(torch.cat((weighted, h), 1), w_out))
+    attn = _softmax(attn, 1)
+    weighted = _bmm(attn.unsqueeze(1), context).squeeze(1)
+    h_tilde = _tanh(_linear(torch.cat((weighted, h), 1), w_out))
     return h_tilde, attn
 
 
 def visual_soft_dot_attention(h, visual_context, w_h, b_h, w_v, b_v):
     """model.py:310-326."""
-    target = F.linear(h, w_h, b_h)
-    context = F.linear(visual_context, w_v, b_v)
-    attn = torch.softmax(torch.bmm(context, target.unsqueeze(2)).squeeze(2), dim=1)
-    weighted = torch.bmm(attn.unsqueeze(1), visual_context).squeeze(1)
+    target = _linear(h, w_h, b_h)
+    context = _linear(visual_context, w_v, b_v)
+    attn = _softmax(_bmm(context, target.unsqueeze(2)).squeeze(2), 1)
+    weighted = _bmm(attn.unsqueeze(1), visual_context).squeeze(1)
     return weighted, attn
 
 
 def eltwise_prod_scoring(h, all_u, w_h, b_h, w_a, b_a, w_out, b_out):
     """model.py:342-352."""
-    target = F.linear(h, w_h, b_h).unsqueeze(1)
-    context = F.linear(all_u, w_a, b_a)
-    return F.linear(target * context, w_out, b_out).squeeze(2)
+    target = _linear(h, w_h, b_h).unsqueeze(1)
+    context = _linear(all_u, w_a, b_a)
+    return _linear(target * context, w_out, b_out).squeeze(2)
 
 
 def _lstm_over(enc, emb, lens, sfx, reverse=False):
@@ -97,8 +170,7 @@ def encoder_lstm(enc, seq, lengths, drop_ctx=None, drop_emb=None):
     embedded tokens (:86-87, trainable embedding only; GloVe: no input dropout)."""
     emb = _embed(enc, seq, drop_emb)
     ctx, h, c = _lstm_over(enc, emb, torch.as_tensor(lengths), '')
-    decoder_init = torch.tanh(F.linear(h, enc['encoder2decoder.weight'],
-                                       enc['encoder2decoder.bias']))
+    decoder_init = _tanh(_linear(h, enc['encoder2decoder.weight'], enc['encoder2decoder.bias']))
     if drop_ctx is not None:
         ctx = ctx * drop_ctx.to(ctx.dtype)
     return ctx, decoder_init, c
@@ -118,8 +190,7 @@ def encoder_bilstm(enc, seq, lengths, drop_ctx=None, drop_emb=None):
     ctx = torch.cat((ctx_f, ctx_r), 2)
     h_t = torch.cat((h_r, h_f), 1)
     c_t = torch.cat((c_r, c_f), 1)
-    decoder_init = torch.tanh(F.linear(h_t, enc['encoder2decoder.weight'],
-                                       enc['encoder2decoder.bias']))
+    decoder_init = _tanh(_linear(h_t, enc['encoder2decoder.weight'], enc['encoder2decoder.bias']))
     if drop_ctx is not None:
         ctx = ctx * drop_ctx.to(ctx.dtype)
     return ctx, decoder_init, c_t
@@ -192,9 +263,11 @@ def follower_rollout(enc, dec, seq, lengths, ctx_mask, steps, step_inputs, targe
                 scores=seq_scores, h=h, c=c, ctx=ctx)
 
 
-def speaker_encoder(enc, action_embs, world_feats, drop_masks=None):
+def speaker_encoder(enc, action_embs, world_feats, drop_masks=None, tape=None):
     """model.py:437-457.  drop_masks(t) -> mask for the concat input (:433);
-    drop_masks('ctx') -> mask for :456."""
+    drop_masks('ctx') -> mask for :456.  tape (a dict): per path step the lists 'alpha' (attention weights), 'feature'
+    (attended feature), 'concat' (the masked LSTM input), 'gates', 'gates_act', 'h', 'c'; once 'decoder_init',
+    'ctx_raw' and 'ctx' (the context before and after its mask)."""
     dt = enc['lstm.weight_hh'].dtype
     B = world_feats[0].shape[0]
     H = enc['lstm.weight_hh'].shape[1]
@@ -204,20 +277,27 @@ def speaker_encoder(enc, action_embs, world_feats, drop_masks=None):
     p = 'visual_attention_layer.'
     for t, (a_emb, X) in enumerate(zip(action_embs, world_feats)):
         a_emb, X = torch.as_tensor(a_emb).to(dt), torch.as_tensor(X).to(dt)
-        feature, _ = visual_soft_dot_attention(
+        feature, alpha_v = visual_soft_dot_attention(
             h, X, enc[p + 'linear_in_h.weight'], enc[p + 'linear_in_h.bias'],
             enc[p + 'linear_in_v.weight'], enc[p + 'linear_in_v.bias'])
         concat = torch.cat((a_emb, feature), 1)
         if drop_masks:
             concat = concat * drop_masks(t).to(dt)
+        _rec(tape, 'alpha', alpha_v)
+        _rec(tape, 'feature', feature)
+        _rec(tape, 'concat', concat)
         h, c = lstm_cell(concat, h, c, enc['lstm.weight_ih'], enc['lstm.weight_hh'],
-                         enc['lstm.bias_ih'], enc['lstm.bias_hh'])
+                         enc['lstm.bias_ih'], enc['lstm.bias_hh'], tape)
+        _rec(tape, 'h', h)
+        _rec(tape, 'c', c)
         hs.append(h)
-    decoder_init = torch.tanh(F.linear(h, enc['encoder2decoder.weight'],
-                                       enc['encoder2decoder.bias']))
+    decoder_init = _tanh(_linear(h, enc['encoder2decoder.weight'], enc['encoder2decoder.bias']))
     ctx = torch.stack(hs, dim=1)
+    _rec(tape, 'decoder_init', decoder_init, False)
+    _rec(tape, 'ctx_raw', ctx, False)
     if drop_masks:
         ctx = ctx * drop_masks('ctx').to(dt)
+    _rec(tape, 'ctx', ctx, False)
     return ctx, decoder_init, c
 
 
@@ -233,46 +313,63 @@ def speaker_decoder_step(dec, prev_word, h0, c0, ctx, ctx_mask, drop_h=None, dro
     h_tilde, alpha = soft_dot_attention(
         h1_drop, ctx, ctx_mask, dec['attention_layer.linear_in.weight'],
         dec['attention_layer.linear_out.weight'])
-    logit = F.linear(h_tilde, dec['decoder2action.weight'], dec['decoder2action.bias'])
+    logit = _linear(h_tilde, dec['decoder2action.weight'], dec['decoder2action.bias'])
     return h1, c1, alpha, logit
 
 
-def context_only_soft_dot_attention(h, context, mask, w_in):
-    """ContextOnlySoftDotAttention.forward, model.py:161-177."""
-    target = F.linear(h, w_in)
-    attn = torch.bmm(context, target.unsqueeze(2)).squeeze(2)
+def context_only_soft_dot_attention(h, context, mask, w_in, tape=None):
+    """ContextOnlySoftDotAttention.forward, model.py:161-177.  tape: records 'target' (the linear_in output)."""
+    target = _linear(h, w_in)
+    _rec(tape, 'target', target)
+    attn = _bmm(context, target.unsqueeze(2)).squeeze(2)
     if mask is not None:
         attn = attn.masked_fill(mask, float('-inf'))
-    attn = torch.softmax(attn, dim=1)
-    weighted = torch.bmm(attn.unsqueeze(1), context).squeeze(1)
+    attn = _softmax(attn, 1)
+    weighted = _bmm(attn.unsqueeze(1), context).squeeze(1)
     return weighted, attn
 
 
-def speaker_decoder_step_att_feed(dec, prev_word, h0, c0, ctx, ctx_mask, drops=None):
+def speaker_decoder_step_att_feed(dec, prev_word, h0, c0, ctx, ctx_mask, drops=None, tape=None):
     """SpeakerDecoderLSTM.forward, the use_input_att_feed branch, model.py:497-513.
     drops: None (eval mode) or the four masks (embedded word [B,E] or None for GloVe,
-    h_0 [B,H], h_tilde [B,H], cat(h_1, h_tilde) [B,2H]) of :500, :503, :504, :507."""
+    h_0 [B,H], h_tilde [B,H], cat(h_1, h_tilde) [B,2H]) of :500, :503, :504, :507.
+    tape (a dict): appends this step's 'emb' (embedded word), 'h0_drop' (masked h_0), 'target' (linear_in output),
+    'alpha' (attention weights), 'weighted' (weighted context), 'concat' (the masked LSTM input), 'gates', 'gates_act',
+    'h1', 'c1', 'x_in' (the masked cat(h_1, h_tilde)), 'x' (the output_l1 tanh output) and 'logit' to the lists of those
+    names."""
     d_emb, d_h0, d_ht, d_x = drops if drops is not None else (None, None, None, None)
     mul = lambda x, m: x if m is None else x * m.to(x.dtype)                # noqa: E731
     emb = mul(dec['embedding.weight'][prev_word], d_emb)                    # :497-500
-    h_tilde, alpha = context_only_soft_dot_attention(mul(h0, d_h0), ctx, ctx_mask,
-                                                     dec['attention_layer.linear_in.weight'])  # :502-503
+    h0_drop = mul(h0, d_h0)
+    _rec(tape, 'emb', emb)
+    _rec(tape, 'h0_drop', h0_drop)
+    h_tilde, alpha = context_only_soft_dot_attention(h0_drop, ctx, ctx_mask,
+                                                     dec['attention_layer.linear_in.weight'], tape)  # :502-503
     concat = torch.cat((emb, mul(h_tilde, d_ht)), 1)                        # :504
+    _rec(tape, 'alpha', alpha)
+    _rec(tape, 'weighted', h_tilde)
+    _rec(tape, 'concat', concat)
     h1, c1 = lstm_cell(concat, h0, c0, dec['lstm.weight_ih'], dec['lstm.weight_hh'],
-                       dec['lstm.bias_ih'], dec['lstm.bias_hh'])            # :505
-    x = mul(torch.cat((h1, h_tilde), 1), d_x)                               # :506-507
-    x = torch.tanh(F.linear(x, dec['output_l1.weight'], dec['output_l1.bias']))   # :508-509
-    logit = F.linear(x, dec['decoder2action.weight'], dec['decoder2action.bias'])  # :510
+                       dec['lstm.bias_ih'], dec['lstm.bias_hh'], tape)      # :505
+    x_in = mul(torch.cat((h1, h_tilde), 1), d_x)                            # :506-507
+    x = _tanh(_linear(x_in, dec['output_l1.weight'], dec['output_l1.bias']))   # :508-509
+    logit = _linear(x, dec['decoder2action.weight'], dec['decoder2action.bias'])  # :510
+    for name, v in (('h1', h1), ('c1', c1), ('x_in', x_in), ('x', x), ('logit', logit)):
+        _rec(tape, name, v)
     return h1, c1, alpha, logit
 
 
 def speaker_score(enc, dec, action_embs, world_feats, path_mask, instr_seq, steps,
-                  feedback, pad_idx=0, bos_idx=3, eos_idx=2, enc_drop=None, dec_drop=None):
+                  feedback, pad_idx=0, bos_idx=3, eos_idx=2, enc_drop=None, dec_drop=None, tape=None):
     """speaker.py:135-197.  Train mode: enc_drop as `speaker_encoder`'s drop_masks;
     dec_drop(t) -> the masks of word step t: (drop_emb or None, drop_h) for the plain
     decoder, the four of `speaker_decoder_step_att_feed` for an att-feed decoder (its
-    state holds `output_l1.weight`, model.py:475-481)."""
-    ctx, h, c = speaker_encoder(enc, action_embs, world_feats, enc_drop)
+    state holds `output_l1.weight`, model.py:475-481).  tape (a dict): filled with tape['enc'] (`speaker_encoder`'s
+    tape) and, for an att-feed decoder, tape['dec'] (`speaker_decoder_step_att_feed`'s, one list entry per word step)."""
+    enc_tape = dec_tape = None
+    if tape is not None:
+        enc_tape, dec_tape = tape.setdefault('enc', {}), tape.setdefault('dec', {})
+    ctx, h, c = speaker_encoder(enc, action_embs, world_feats, enc_drop, enc_tape)
     dt = ctx.dtype
     att_feed = 'output_l1.weight' in dec
     B = ctx.shape[0]
@@ -284,7 +381,7 @@ def speaker_score(enc, dec, action_embs, world_feats, path_mask, instr_seq, step
     for t in range(steps):
         if att_feed:
             h, c, alpha, logit = speaker_decoder_step_att_feed(
-                dec, w_t, h, c, ctx, path_mask, dec_drop(t) if dec_drop else None)
+                dec, w_t, h, c, ctx, path_mask, dec_drop(t) if dec_drop else None, dec_tape)
         else:
             d_emb, d_h = dec_drop(t) if dec_drop else (None, None)
             h, c, alpha, logit = speaker_decoder_step(dec, w_t, h, c, ctx, path_mask, d_h, d_emb)

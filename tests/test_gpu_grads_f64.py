@@ -6,7 +6,9 @@ SpeakerEngine.score, teacher forcing), feeds the identical inputs and the same c
 
   * the loss: relative 1e-5 to float64;
   * the logits of every step: 1e-4 absolute to float64 (finite entries; the -inf pattern identical); F6 alone (peaky
-    weights, where the reference's own fp32 logits are 3.4e-4 from float64) is held to 4x that distance;
+    weights, where the reference's own fp32 logits are 3.4e-4 from float64) is held to 4x that distance; S4 in train
+    mode (the att-feed decoder, one ill-conditioned row) per (step, row) to max(1e-4, K x its conditioning envelope),
+    tests/conditioning.py;
   * EVERY element of EVERY parameter's gradient with tests/grad_compare.py: e = max|g - r| / max|r| against
     e32 = max|f - r| / max|r| (the reference's own fp32 arithmetic), e <= max(4 e32, 2e-6) and e <= 1e-4, per tensor and
     per block (LSTM gates x input segments, the halves of the text attention's linear_out, every embedding row; rows
@@ -22,9 +24,16 @@ S4 in train mode e <= 1.4e-5 (e32 9.2e-6); the trainable embedding (E1, peaky we
 peaky weights (F6) e <= 4.2e-4 with e32 4.5e-4 -- there the reference's own fp32 drift exceeds the 1e-4 ceiling, so F6
 is held to 4 e32 alone.  Exact-zero biases: max|g| <= 3.0e-8, within 4x the fp32 reference's own roundoff of the zero.
 Logits: <= 5.7e-6 from float64 everywhere except F6 (1.29e-4, the fp32 reference 3.36e-4) and the att-feed decoder in
-train mode (2.75e-4, the fp32 reference 6.2e-5: an open finding, recorded as a strict xfail below).
+train mode: 2.75e-4 at (step 8, row 0), 5.3e-5 at most in rows 1-11 (row 1: 4.6e-5).  That was this module's open
+finding (a strict xfail: "2.75e-4 where the fp32 reference stays within 6.2e-5; rows 0-1") and is closed as CONDITIONING
+OF ROW 0: rounding every operator's result once to fp32 in an otherwise float64 evaluation moves that entry by 3.8e-4
+(the envelope), every stage of the HIP trace stays inside K x the envelope of the same stage, every operator alone is
+within its fp32-class bound (tests/test_gpu_module_ladder.py), and the fp32 reference's 6.2e-5 was one lucky sample: the
+same computation is 2.29e-4 away with 8 threads (tests/test_conditioning_host.py).  Row 1 is well-conditioned (envelope
+2.3e-5), keeps the 1e-4 bound and is within it.  Numbers: profiles/att_feed_drift.txt.
 """
 import dataclasses
+import functools
 
 import numpy as np
 import pytest
@@ -34,6 +43,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import np_env, rng as orng, torch_ref                    # noqa: E402
 from speaker_follower_amd import synth                                # noqa: E402
+from tests import conditioning as cn                                  # noqa: E402
 from tests import grad_compare as gc                                  # noqa: E402
 
 D = synth.FULL
@@ -387,7 +397,9 @@ def test_s3_trainable_speaker_embedding():
     _check_case('S3 speaker trainable embedding', c)
 
 
+@functools.lru_cache(maxsize=None)
 def _s4(train):
+    """The case and its references, computed once and shared by the two tests below (neither changes them)."""
     c = _speaker(12, 10, train=train, seed=31, att_feed=True, min_len=4, max_len=9, nvp=48)
     assert not c['st'].teacher_path and not c['st'].persistent
     if train:
@@ -402,17 +414,51 @@ def test_s4_input_att_feed_decoder(train):
     Train mode with the modules' counter-based masks (encoder: sites 2t / 2Tp + 1, decoder: 4t + k for the dropped h_0,
     h_tilde and cat(h_1, h_tilde)); the embedding is GloVe (a trainable one is refused on this path).  Loss and every
     gradient element in both modes; the logits in eval mode here (measured 5.6e-6 from float64, the fp32 reference
-    9.6e-6), in train mode in the test below."""
+    9.6e-6), in train mode in the test below, per entry against the conditioning envelope."""
     c = _s4(train)
     _check_case('S4 att-feed %s' % ('train' if train else 'eval'), c, logits=not train)
 
 
-@pytest.mark.xfail(strict=True, reason='open finding: att-feed decoder, train mode -- logits up to 2.75e-4 from float64 '
-                   '(|logit| <= 20; rows 0-1; steps 1-8) where the fp32 reference stays within 6.2e-5, while loss and every '
-                   'gradient element are within bound (test above); cause not yet isolated, the 1e-4 bound is kept')
-def test_s4_att_feed_train_logits_within_1e4_of_float64():
+def test_s4_att_feed_train_logits_within_envelope_of_float64():
+    """Every (step, row) of the train-mode logits within max(1e-4, K x env) of float64, env the conditioning envelope of
+    that entry (tests/conditioning.py: the float64 oracle with every operator's result rounded once to fp32, 1 nearest + 32
+    seeded random roundings; computed once per process).  The earlier yardstick, one fp32 evaluation of the reference,
+    is printed beside it: it is a single sample whose value depends on the host's thread count
+    (tests/test_conditioning_host.py).  No entry is skipped; the -inf pattern must be identical."""
     c = _s4(True)
-    _check_logits('S4 att-feed train', c['logits'], c['r64']['logits'], c['r32']['logits'], c['n'])
+    case = cn.s4(True)
+    env, _ = cn.s4_envelope(True)
+    bound = cn.entry_bounds(env)
+    ref = case.run()
+    n = c['n']
+    assert n == len(ref) == env.shape[0] == 10 and env.shape[1] == 12
+    for t in range(n):                          # the envelope's float64 run IS this module's float64 reference
+        assert torch.equal(ref[t], c['r64']['logits'][t].detach())
+    got = [c['logits'][t][:, :ref[t].shape[1]] for t in range(n)]
+    for t in range(n):
+        assert got[t].shape == tuple(ref[t].shape)
+        assert np.array_equal(np.isfinite(got[t]), np.isfinite(ref[t].numpy())), 'step %d: -inf pattern differs' % t
+    d = cn.logit_distance(got, ref)
+    d32 = cn.logit_distance(c['r32']['logits'], ref)
+    assert d.shape == bound.shape
+    ratio = d / bound
+    t_, r_ = np.unravel_index(np.argmax(ratio), ratio.shape)
+    plain = bound == cn.ABS_BOUND
+    dp = np.where(plain, d, -1.0)
+    tp, rp = np.unravel_index(np.argmax(dp), dp.shape)
+    ta, ra = np.unravel_index(np.argmax(d), d.shape)
+    print('[parity] S4 att-feed train: worst entry by ratio (step %d, row %d): |dlogit| %.3e, env %.3e, bound %.3e, '
+          'ratio %.2f' % (t_, r_, d[t_, r_], env[t_, r_], bound[t_, r_], ratio[t_, r_]))
+    print('[parity] S4 att-feed train: largest |dlogit| %.3e at (step %d, row %d), env there %.3e' % (d[ta, ra], ta, ra,
+                                                                                                      env[ta, ra]))
+    print('[parity] S4 att-feed train: worst entry among the %d of %d pairs whose bound is 1e-4 (step %d, row %d): '
+          '|dlogit| %.3e, env %.3e' % (plain.sum(), plain.size, tp, rp, d[tp, rp], env[tp, rp]))
+    print('[parity] S4 att-feed train: per-row max |dlogit| %s' % ['%.2e' % v for v in d.max(0)])
+    print('[parity] S4 att-feed train: the fp32 reference on this host (%d threads): %.3e from float64 at (step %d, row '
+          '%d)' % ((torch.get_num_threads(), d32.max()) + np.unravel_index(np.argmax(d32), d32.shape)))
+    bad = ['(step %d, row %d): %.3e > %.3e (env %.3e)' % (t, r, d[t, r], bound[t, r], env[t, r])
+           for t, r in zip(*np.nonzero(d > bound))]
+    assert not bad, 'S4 att-feed train logits outside max(1e-4, K env): ' + '; '.join(bad)
 
 
 def test_s5_vocabulary_above_1024():
