@@ -67,32 +67,56 @@ def follower_sample(masked_row, valid_row, u):
     return a, float(np.min(np.abs(cdf[valid] - thr)) / cdf[-1])
 
 
-def speaker_sample(logit_row, u1, u2, slot=32):
+def speaker_sample(logit_row, u1, u2, slot=32, underflow=None, detail=False):
     """float64 mirror of the device's two-level inverse-CDF draw (speaker_follower_amd/csrc/sf_sampling.h; the
     reference's D.Categorical(probs).sample() at speaker.py:170-174 draws from torch's stateful generator, which cannot be
     reproduced).  Returns (word, margin): margin = the smallest relative distance of either threshold to a CDF boundary
-    -- fp32 roundoff on the device can flip a draw whose margin is ~1e-6, so callers skip those."""
+    of an item that carries weight -- fp32 roundoff on the device can flip a draw whose margin is ~1e-6.  (The margin
+    differs from what it was before only where zero-weight items LEAD a prefix: their boundary at 0 no longer makes a draw at
+    u ~ 0 look unclear; behind an item that carries weight a zero-weight item repeats that item's boundary.)
+
+    The contract's edges, as sf_sampling.h states them: a slot with no finite column has weight 0 and is never chosen
+    (its columns weigh 0 too, nothing here is NaN); a row with no finite column at all stays outside the contract
+    (AssertionError); level 1 falls back to the slot of the arg max, level 2 to the LAST column of the slot WHOSE WEIGHT
+    IS POSITIVE.  `underflow` (tests pass 104.0, where float32's expf reaches 0): a column more than that below its
+    slot's maximum, and a slot whose maximum lies more than that below the row's, weigh exactly 0 as they do on the
+    device, so "positive weight" means the same on both sides; None keeps every float64 weight.  detail=True returns
+    (word, margin, info) with info = dict(slot, col, fallback1, fallback2, margin1, margin2, p = the slot weights, e =
+    the column weights of the chosen slot)."""
     l = np.asarray(logit_row, np.float64)
     V = len(l)
     ns = (V + slot - 1) // slot
-    m_s = np.full(ns, -np.inf)
-    z_s = np.zeros(ns)
-    for s in range(ns):
-        seg = l[slot * s:slot * (s + 1)]
-        m_s[s] = seg.max()
-        z_s[s] = np.exp(seg - m_s[s]).sum()
+    seg = np.full(ns * slot, -np.inf)
+    seg[:V] = l
+    seg = seg.reshape(ns, slot)
+    m_s = seg.max(1)
+    live = m_s > -np.inf
+    assert live.any(), 'a row without a finite column is outside the contract of the draw'
+    d = seg - np.where(live, m_s, 0.0)[:, None]                        # (an empty slot: -inf throughout, weight 0)
+    e_all = np.exp(d)
     M = m_s.max()
-    p = z_s * np.exp(m_s - M)
+    ds = np.where(live, m_s - M, -np.inf)
+    w = np.exp(ds)
+    if underflow is not None:
+        e_all[d < -underflow] = 0.0
+        w[ds < -underflow] = 0.0
+    z_s = e_all.sum(1)
+    p = z_s * w
     cdf = np.cumsum(p)
     thr = u1 * cdf[-1]
-    hit = np.flatnonzero((cdf > thr) & (p > 0))
+    pos = p > 0
+    hit = np.flatnonzero((cdf > thr) & pos)
     s = int(hit[0]) if len(hit) else int(np.argmax(l)) // slot
-    margin = np.min(np.abs(cdf - thr)) / cdf[-1]
-    seg = l[slot * s:slot * (s + 1)]
-    e = np.exp(seg - m_s[s])
+    margin1 = float(np.min(np.abs(cdf[pos] - thr)) / cdf[-1])
+    e = e_all[s]
     c2 = np.cumsum(e)
     thr2 = u2 * z_s[s]
-    hit2 = np.flatnonzero((c2 > thr2) & (e > 0))
-    c = int(hit2[0]) if len(hit2) else len(seg) - 1
-    margin = min(margin, np.min(np.abs(c2 - thr2)) / z_s[s])
-    return slot * s + c, float(margin)
+    pos2 = e > 0
+    hit2 = np.flatnonzero((c2 > thr2) & pos2)
+    c = int(hit2[0]) if len(hit2) else int(np.flatnonzero(pos2)[-1])
+    margin2 = float(np.min(np.abs(c2[pos2] - thr2)) / z_s[s])
+    word, margin = slot * s + c, min(margin1, margin2)
+    if not detail:
+        return word, margin
+    return word, margin, dict(slot=s, col=c, fallback1=len(hit) == 0, fallback2=len(hit2) == 0, margin1=margin1,
+                              margin2=margin2, p=p, e=e)

@@ -703,6 +703,11 @@ __device__ __forceinline__ int row16_min(int v) {
     for (int off = 8; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 16));
     return v;
 }
+__device__ __forceinline__ int row16_max(int v) {
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 16));
+    return v;
+}
 // Inverse-CDF pick over 32 weights held two per lane by the 16 lanes of a row (lane eu: items eu and eu + 16, in
 // item order): the first item whose inclusive prefix sum exceeds `thr` and whose weight is positive, INT_MAX if none
 // (thr rounded up to the total).  This is sf_sampling.h's two-level draw with the slots spread over workgroups.
@@ -1007,7 +1012,8 @@ __global__ __launch_bounds__(256, 1) void spk_persist_kernel(SpkPersistArgs p) {
                 const int oa = __shfl_xor(am, off, 16);
                 if (om > m || (om == m && oa < am)) { m = om; am = oa; }
             }
-            const float e0 = col0 < vocab ? expf(l0 - m) : 0.f, e1 = col1 < vocab ? expf(l1 - m) : 0.f;
+            // (wexp: a slot whose columns are all -inf publishes z = 0, not NaN -- the same bits wherever m is finite)
+            const float e0 = col0 < vocab ? wexp(l0, m) : 0.f, e1 = col1 < vocab ? wexp(l1, m) : 0.f;
             const float se = row16_sum(e0 + e1);
             const float tl = row16_sum((col0 == tgt ? l0 : 0.f) + (col1 == tgt ? l1 : 0.f));
             if (eu == 0)
@@ -1020,7 +1026,9 @@ __global__ __launch_bounds__(256, 1) void spk_persist_kernel(SpkPersistArgs p) {
                 float u1, u2;
                 sample_uniforms(p.sample_seed + 0x9E3779B9u * site_value(p.sample_site), p.sample_stream + (uint32_t)t, (uint32_t)(p.sample_row0 + eb), &u1, &u2);
                 const int it = row16_pick32(e0, e1, u2 * se, eu);
-                const int sc_ = it != 0x7FFFFFFF ? 32 * slot + it : min(32 * slot + 31, vocab - 1);
+                // u2 se rounded up to the total: the slot's last column that carries weight (none: an empty slot, never chosen)
+                const int lt = row16_max(e1 > 0.f ? eu + 16 : (e0 > 0.f ? eu : -1));
+                const int sc_ = it != 0x7FFFFFFF ? 32 * slot + it : (lt >= 0 ? 32 * slot + lt : min(32 * slot + 31, vocab - 1));
                 const float sl_ = row16_sum((sc_ == col0 ? l0 : 0.f) + (sc_ == col1 ? l1 : 0.f));
                 if (eu == 0) {
                     xstore32(local, (unsigned)sc_, rs, (bo + SPX_SS + (unsigned)((slot * EP_ROWS + er) * 2)) * 4u);

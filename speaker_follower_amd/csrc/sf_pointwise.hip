@@ -536,7 +536,7 @@ __device__ __forceinline__ int speaker_sample_row(const SGlue& g, const float* r
     float sl = 0.f;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-        e[j] = 16 * lane + j < g.vocab ? expf(x[j] - ms) : 0.f;
+        e[j] = 16 * lane + j < g.vocab ? wexp(x[j], ms) : 0.f;    // (a slot of all -inf: every weight 0, not NaN)
         sl += e[j];
     }
     const float so = __shfl_xor(sl, 1, WAVE);
@@ -546,14 +546,16 @@ __device__ __forceinline__ int speaker_sample_row(const SGlue& g, const float* r
     // level 2: this slot's column
     const float thr2 = u2 * zs;
     float cum = (lane & 1) ? so : 0.f;
-    int pick = 0x7FFFFFFF;
+    int pick = 0x7FFFFFFF, last = -1;                            // last: the slot's last column that carries weight
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         cum += e[j];
         if (pick == 0x7FFFFFFF && cum > thr2 && e[j] > 0.f) pick = 16 * lane + j;
+        if (e[j] > 0.f) last = 16 * lane + j;
     }
     pick = min(pick, __shfl_xor(pick, 1, WAVE));
-    if (pick == 0x7FFFFFFF) pick = min(32 * (lane >> 1) + 31, g.vocab - 1);
+    last = max(last, __shfl_xor(last, 1, WAVE));
+    if (pick == 0x7FFFFFFF) pick = last >= 0 ? last : min(32 * (lane >> 1) + 31, g.vocab - 1);   // (last < 0: an empty slot, never chosen)
     // level 1: the slot
     const float ps = (lane & 1) ? 0.f : zs * wexp(ms, m);
     float cdf = ps;
@@ -701,14 +703,16 @@ __global__ __launch_bounds__(TPB) void speaker_glue_wide_sample_kernel(SGlue g) 
             // level 2: this slot's column
             const float thr2 = u2 * zs;
             float cum = (lane & 1) ? so : 0.f;
-            int pk = 0x7FFFFFFF;
+            int pk = 0x7FFFFFFF, last = -1;                      // last: the slot's last column that carries weight
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 cum += e[j];
                 if (pk == 0x7FFFFFFF && cum > thr2 && e[j] > 0.f) pk = c0 + j;
+                if (e[j] > 0.f) last = c0 + j;
             }
             pk = min(pk, __shfl_xor(pk, 1, WAVE));
-            if (pk == 0x7FFFFFFF) pk = min(32 * (32 * p + (lane >> 1)) + 31, g.vocab - 1);
+            last = max(last, __shfl_xor(last, 1, WAVE));
+            if (pk == 0x7FFFFFFF) pk = last >= 0 ? last : min(32 * (32 * p + (lane >> 1)) + 31, g.vocab - 1);   // (an empty slot)
             pick[p] = pk;
             // level 1: this panel's slots behind the prefix of the panels before it
             const float w = (lane & 1) ? 0.f : zs * wexp(ms, m);

@@ -9,9 +9,15 @@
 //                         of those weights exceeds  u1 * Z  (Z = their sum over all ns slots)
 //   level 2 (uniform u2): inside that slot, the first column with positive weight whose inclusive prefix of
 //                         exp(l - m_s) exceeds  u2 * z_s
-// P(column c of slot s) = P(s) P(c | s) = softmax(l)_c.  Fallbacks when a threshold rounds up to the total: the slot
-// of the arg max; the last valid column of the slot, min(32 s + 31, V - 1).  A slot whose columns are all -inf has
-// weight 0 (wexp) and is never chosen.  oracle/rng.py mirrors the draw in float64, for any V.
+// P(column c of slot s) = P(s) P(c | s) = softmax(l)_c.  "Positive weight" is meant in float32: a column more than
+// ~104 below its slot's maximum, or -inf, has weight expf(.) = 0 and is never drawn, whatever the prefix sums say.
+// The edges of the contract, the same in all three kernels and in the float64 mirror (oracle/rng.py::speaker_sample):
+//   - a slot with no finite column has weight 0 (wexp: its m_s = -inf must not turn l - m_s into NaN, neither in
+//     z_s nor in the slot's weight) and is never chosen; the prefix of level 1 walks over it;
+//   - a row with no finite column at all stays outside the contract: nothing is promised about its word;
+//   - fallbacks when a threshold rounds up to the total (each lane's float32 prefix is rounded in an order of its
+//     own, so at u = 1 - 2^-24 no item may pass): level 1 takes the slot of the arg max; level 2 takes the LAST COLUMN
+//     OF THE SLOT WHOSE WEIGHT IS POSITIVE -- not min(32 s + 31, V - 1), which may be a banned or underflowed word.
 // V <= 1024 (ns <= 32): one wave holds every slot at once, lanes 2 s and 2 s + 1 slot s (speaker_sample_row), and the
 // persistent loop one slot per workgroup.  1024 < V <= 4096: the per-step glue alone (speaker_glue_wide_sample_kernel),
 // in PANELS of 1024 columns = 32 slots: panel p holds slots 32 p .. 32 p + 31 in the same lane order, the panels are
