@@ -1440,6 +1440,22 @@ typedef struct sf_eval_routes {
     int32_t *steps, *success, *oracle_success;                   /* [n_slots] */
 } sf_eval_routes;
 int sf_eval_score_routes(const sf_eval_routes* e, int32_t* err, sf_stream stream);
+/* sf_eval_score_routes_coverage (csrc/sf_eval_routes.hip; no reference counterpart), additive to ABI 10: everything
+ * sf_eval_score_routes does -- the same launch shape, both layouts, the same eight outputs to the last bit, the same
+ * refusals -- plus, in the SAME launch, the one route-dependent part of CLS (coverage weighted by length score;
+ * DESIGN.md section 2): per gold node the least distance from any visited pose,
+ *   near[slot[b] * near_ld + k] = min over a = 0 .. n of D[p_a][r_k]      for k < g
+ * FROM the pose TO the gold node, the direction of dtw's cost.  These are the table elements the warping recurrence
+ * loads anyway: lane k folds the cost of each of its cells into a minimum (every (pose, gold node) pair passes there
+ * exactly once) and stores its own value.  A minimum is exact, so the bits do not depend on the order.  coverage,
+ * length_score and cls are formed on the host from it (evaluation.coverage_metrics_of).  `near` is [n_slots, near_ld];
+ * elements k >= g of a row, and the rows of slots no route writes, are not written.
+ *   SF_ERR_ARG as sf_eval_score_routes, and for near == NULL or near_ld < max_gold; SF_ERR_UNSUPPORTED likewise.
+ *   Every per-route refusal of sf_eval_score_routes, and slot[b] == -1, write nothing to `near` either.  max_gold is a
+ *   HOST copy, so the kernel checks the row itself: a route whose gold path has more than near_ld nodes writes nothing
+ *   and sets err[0] = 1. */
+int sf_eval_score_routes_coverage(const sf_eval_routes* e, double* near, int32_t near_ld, int32_t* err,
+                                  sf_stream stream);
 
 /* Scoring of speaker results (tasks/R2R/eval_speaker.py:11-122, tasks/R2R/bleu.py:15-72 and the multi-bleu script it
  * runs; speaker_follower_amd/speaker_evaluation.py), additive to ABI 9.

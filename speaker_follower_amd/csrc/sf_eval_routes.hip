@@ -5,6 +5,9 @@
 // with the cost in the direction D[pred][gold], dtw = C[n+1][g].  Every cell is ONE rounded float64 add of one table
 // element to an exact three-way minimum, so every evaluation order gives the same bits: the host runs the rows, this
 // kernel the anti-diagonals.  Hence no contraction and no fast-math in this file, as in sf_eval.hip.
+// With COVER (sf_eval_score_routes_coverage) the same launch also leaves near[b] = min over a of D[p_a][r_b] per gold
+// node, the one route-dependent part of CLS: a minimum over the table elements the recurrence loads anyway, exact in
+// any order.  The exponentials and the length score are formed on the host (evaluation.coverage_metrics_of).
 #include "sf_common.h"
 
 #pragma clang fp contract(off)
@@ -17,7 +20,10 @@ constexpr int AHEAD = 8;               // anti-diagonals whose table elements ar
 
 // Lane l owns gold position l.  At anti-diagonal t it forms cell (a, l) with a = t - l the pose index: the left and the
 // diagonal predecessor are lane l - 1's values of steps t - 1 and t - 2, the upper one is its own value of step t - 1.
-__global__ __launch_bounds__(ROUTES_PER_BLOCK* WAVE) void eval_routes_kernel(sf_eval_routes p, int32_t* __restrict__ err) {
+// COVER: lane l < g also folds the costs of its cells into a minimum and stores it at near_out[slot * near_ld + l].
+template <bool COVER>
+__global__ __launch_bounds__(ROUTES_PER_BLOCK* WAVE) void eval_routes_kernel(sf_eval_routes p, int32_t* __restrict__ err,
+                                                                            double* __restrict__ near_out, int32_t near_ld) {
     const int lane = threadIdx.x & (WAVE - 1);
     const int b = blockIdx.x * ROUTES_PER_BLOCK + (threadIdx.x >> 6);
     if (b >= p.B) return;                                    // (wave-uniform: no barrier in this kernel)
@@ -33,6 +39,7 @@ __global__ __launch_bounds__(ROUTES_PER_BLOCK* WAVE) void eval_routes_kernel(sf_
         g0 = p.gold_off[gid];
         g = p.gold_off[gid + 1] - g0;
         bad = g0 < 0 || g < 1 || g > SF_EVAL_MAX_GOLD || g0 > p.n_gold_nodes - g;
+        if (COVER) bad = bad || g > near_ld;                 // (max_gold is a host copy: the row is checked here)
     }
     // the step count: given, or the first stop of actions [S, B] plus one, else S (sf_eval_score's rule)
     int n = 0;
@@ -120,6 +127,7 @@ __global__ __launch_bounds__(ROUTES_PER_BLOCK* WAVE) void eval_routes_kernel(sf_
     };
     double cur = inf;                // C[a][l + 1] of the pose before: the upper predecessor; C[0][l + 1] = inf
     double diag = inf;               // lane l - 1's value of two steps ago
+    double nearest = inf;            // COVER: the least cost of this lane's cells so far
     double cost[AHEAD], next[AHEAD];
 #pragma unroll
     for (int i = 0; i < AHEAD; ++i) cost[i] = cost_of(i);
@@ -139,6 +147,7 @@ __global__ __launch_bounds__(ROUTES_PER_BLOCK* WAVE) void eval_routes_kernel(sf_
                 double best = cur < left ? cur : left;
                 best = diag < best ? diag : best;
                 cur = cost[i] + best;
+                if (COVER) nearest = cost[i] < nearest ? cost[i] : nearest;
             }
             diag = left;
         }
@@ -156,20 +165,39 @@ __global__ __launch_bounds__(ROUTES_PER_BLOCK* WAVE) void eval_routes_kernel(sf_
         p.success[slot] = nav < p.margin;
         p.oracle_success[slot] = oracle < p.margin;
     }
+    if (COVER && lane < g) near_out[(int64_t)slot * near_ld + lane] = nearest;
 }
 
 }  // namespace
 }  // namespace sf
 
-extern "C" int sf_eval_score_routes(const sf_eval_routes* e, int32_t* err, sf_stream stream) {
-    SF_ENTER();
+static int score_routes(const sf_eval_routes* e, int32_t* err, double* near, int32_t near_ld, bool cover,
+                        sf_stream stream) {
     SF_CHECK_ARG(e && err && e->B >= 1 && e->n_slots >= 1 && e->row_stride >= 1 && e->n_gold >= 1 && e->max_gold >= 1 &&
                  e->n_gold_nodes >= 1 && e->n_rows >= 1 && e->row && e->row_first && e->gold_off && e->gold_node &&
                  e->gold_id && e->scan_base && e->m && e->dist_off && e->slot && e->table && e->nav_error &&
                  e->oracle_error && e->length && e->shortest && e->dtw && e->steps && e->success && e->oracle_success);
     SF_CHECK_ARG(e->n_steps || (e->actions && e->S >= 1));
+    SF_CHECK_ARG(!cover || (near && near_ld >= e->max_gold));
     if (e->max_gold > SF_EVAL_MAX_GOLD) return SF_ERR_UNSUPPORTED;
-    SF_LAUNCH(sf::eval_routes_kernel, dim3(sf::ceil_div(e->B, sf::ROUTES_PER_BLOCK)), dim3(sf::ROUTES_PER_BLOCK * sf::WAVE),
-              0, (hipStream_t)stream, *e, err);
+    const dim3 grid(sf::ceil_div(e->B, sf::ROUTES_PER_BLOCK)), block(sf::ROUTES_PER_BLOCK * sf::WAVE);
+    if (cover) {
+        SF_LAUNCH_AS("sf::eval_routes_kernel<cover>", sf::eval_routes_kernel<true>, grid, block, 0, (hipStream_t)stream, *e,
+                     err, near, near_ld);
+    } else {
+        SF_LAUNCH_AS("sf::eval_routes_kernel", sf::eval_routes_kernel<false>, grid, block, 0, (hipStream_t)stream, *e, err,
+                     (double*)nullptr, 0);
+    }
     return sf::launch_status();
+}
+
+extern "C" int sf_eval_score_routes(const sf_eval_routes* e, int32_t* err, sf_stream stream) {
+    SF_ENTER();
+    return score_routes(e, err, nullptr, 0, false, stream);
+}
+
+extern "C" int sf_eval_score_routes_coverage(const sf_eval_routes* e, double* near, int32_t near_ld, int32_t* err,
+                                             sf_stream stream) {
+    SF_ENTER();
+    return score_routes(e, err, near, near_ld, true, stream);
 }

@@ -12,6 +12,8 @@ summary averages over the instructions '<path_id>_0' .. '_2' of the split.
                       `path_metrics=True` adds SPL, nDTW and SDTW (no reference counterpart: their published
                       definitions, DESIGN.md section 2) through sf_eval_score_routes (csrc/sf_eval_routes.hip);
                       `score_routes` scores a batch of routes in one launch.
+                      `coverage_metrics=True` adds CLS (coverage weighted by length score) on top of those: the
+                      per-gold-node minimum distance comes out of the same launch (sf_eval_score_routes_coverage).
 
 The reference takes its table from networkx (all_pairs_dijkstra_path_length); nothing here imports it.
 """
@@ -29,11 +31,15 @@ EvalResult = namedtuple('EvalResult', 'nav_error, oracle_error, trajectory_steps
 
 PathEvalResult = namedtuple('PathEvalResult', EvalResult._fields + ('shortest_length', 'dtw', 'spl', 'ndtw', 'sdtw'))
 
+CoverageEvalResult = namedtuple('CoverageEvalResult', PathEvalResult._fields + ('gold_length', 'coverage', 'length_score',
+                                                                               'cls'))
+
 DATA_JSON = 'tasks/R2R/data/R2R_%s.json'                                 # utils.py:54-59
 CONNECTIVITY = 'connectivity'
 
 _LISTS = ('nav_errors', 'oracle_errors', 'trajectory_steps', 'trajectory_lengths', 'success', 'oracle_success')
 _PATH_LISTS = ('shortest_lengths', 'dtw', 'spl', 'ndtw', 'sdtw')
+_COVERAGE_LISTS = ('gold_lengths', 'coverage', 'length_score', 'cls')
 
 
 def path_metrics_of(r, shortest, dtw, gold_nodes, margin):
@@ -47,6 +53,25 @@ def path_metrics_of(r, shortest, dtw, gold_nodes, margin):
         spl = 1.0 if longest == 0 else shortest / longest
     ndtw = math.exp(-dtw / (gold_nodes * margin))
     return PathEvalResult(*r, shortest_length=shortest, dtw=dtw, spl=spl, ndtw=ndtw, sdtw=ndtw if r.success else 0.0)
+
+
+def coverage_metrics_of(r, near, gold_length, margin):
+    """PathEvalResult `r` + near[b] = min over the poses of D[pose][gold node b] + the gold path's length ->
+    CoverageEvalResult.  THE place where coverage, length_score and cls are formed, for the host
+    and the device path alike: the sum runs left to right in gold order with math.exp on Python floats.  A gold node no
+    pose reaches (near = inf) contributes 0.0; a gold path nobody can walk scores 0.0: no inf / inf is formed."""
+    total = 0.0
+    for d in near:
+        total = total + (0.0 if d == math.inf else math.exp(-d / margin))
+    coverage = total / len(near)
+    expected = coverage * gold_length
+    if gold_length == math.inf:
+        length_score = 0.0
+    else:
+        spread = expected + abs(expected - r.trajectory_length)
+        length_score = 1.0 if spread == 0 else expected / spread
+    return CoverageEvalResult(*r, gold_length=gold_length, coverage=coverage, length_score=length_score,
+                              cls=coverage * length_score)
 
 
 def dtw_rows(cost):
@@ -165,13 +190,19 @@ class Evaluation(object):
     `score_routes` return PathEvalResult (EvalResult's fields, then shortest_length, dtw, spl, ndtw, sdtw), `scores`
     gains the lists 'shortest_lengths', 'dtw', 'spl', 'ndtw', 'sdtw' and the summary 'spl', 'ndtw', 'sdtw'.  With the
     distance table on the device every batch of results is ONE sf_eval_score_routes launch (csrc/sf_eval_routes.hip)
-    and one host sync, else the host loop: the same values to the last bit."""
+    and one host sync, else the host loop: the same values to the last bit.
+
+    coverage_metrics=True turns path_metrics on and adds CLS (Jain et al. 2019): the results are
+    CoverageEvalResult (PathEvalResult's fields, then gold_length, coverage, length_score, cls), `scores` gains the
+    lists 'gold_lengths', 'coverage', 'length_score', 'cls' and the summary 'cls'.  The launch is then
+    sf_eval_score_routes_coverage: the same one, which also leaves the least distance to every gold node."""
 
     def __init__(self, splits=None, env=None, items=None, graphs=None, nav_graph_path=CONNECTIVITY, device=None,
-                 path_metrics=False):
+                 path_metrics=False, coverage_metrics=False):
         self.error_margin = 3.0
-        self.path_metrics = bool(path_metrics)
-        self._gold = None
+        self.coverage_metrics = bool(coverage_metrics)
+        self.path_metrics = bool(path_metrics) or self.coverage_metrics
+        self._gold = self._gold_len = None
         if env is not None:
             items = list(env.data) if items is None else items
             graphs = env.graphs if graphs is None else graphs
@@ -218,14 +249,19 @@ class Evaluation(object):
         return float(t.block(scan)[t.index[scan][a], t.index[scan][b]])
 
     # ---- eval.py:46-84
-    def _score_rows(self, scan, rows, goal, gold=None):
-        """One path as LOCAL node indices of its scan (`gold`: the gold path likewise, with path_metrics)."""
+    def _score_rows(self, scan, rows, goal, gold=None, gold_length=None):
+        """One path as LOCAL node indices of its scan (`gold`: the gold path likewise, with path_metrics; `gold_length`:
+        its length, with coverage_metrics)."""
         r = self._score_six(scan, rows, goal)
         if not self.path_metrics:
             return r
         D = self.table.block(scan)
-        return path_metrics_of(r, float(D[rows[0], goal]), dtw_rows(D[np.ix_(rows, gold)].tolist()), len(gold),
-                               self.error_margin)
+        if not self.coverage_metrics:
+            return path_metrics_of(r, float(D[rows[0], goal]), dtw_rows(D[np.ix_(rows, gold)].tolist()), len(gold),
+                                   self.error_margin)
+        cost = D[np.ix_(rows, gold)].tolist()
+        r = path_metrics_of(r, float(D[rows[0], goal]), dtw_rows(cost), len(gold), self.error_margin)
+        return coverage_metrics_of(r, [min(col) for col in zip(*cost)], gold_length, self.error_margin)
 
     def _score_six(self, scan, rows, goal):
         D = self.table.block(scan)
@@ -246,7 +282,8 @@ class Evaluation(object):
         assert gt['path'][0] == path[0][0], 'Result trajectories should include the start position'
         ix = self.table.index[gt['scan']]
         return self._score_rows(gt['scan'], np.fromiter((ix[p[0]] for p in path), np.int64, len(path)),
-                                ix[gt['path'][-1]], [ix[v] for v in gt['path']] if self.path_metrics else None)
+                                ix[gt['path'][-1]], [ix[v] for v in gt['path']] if self.path_metrics else None,
+                                self._gold_lengths()[gt['path_id']] if self.coverage_metrics else None)
 
     def _local_rows(self, nav, scan):
         """First nav row of `scan` in `nav`, after checking ONCE that the table's rows of that scan are this table's
@@ -310,6 +347,21 @@ class Evaluation(object):
             self._gold = gold
         return self._gold
 
+    def _gold_lengths(self):
+        """path_id -> the length of its gold path: the edges D[r_k][r_k+1] of the HOST table added left to right in path
+        order (0.0 for a path of one node).  Static per gold path: formed once per Evaluation."""
+        if self._gold_len is None:
+            t, out = self.table, {}
+            for pid, gt in self.gt.items():
+                D, ix = t.block(gt['scan']), t.index[gt['scan']]
+                nodes = [ix[v] for v in gt['path']]
+                length = 0.0
+                for d in D[nodes[:-1], nodes[1:]].tolist():
+                    length = length + d
+                out[pid] = length
+            self._gold_len = out
+        return self._gold_len
+
     def _route_of(self, instr_id, result):
         """(ground truth, the poses as LOCAL node indices) of a trajectory [(viewpoint, heading, elevation), ...] or of
         a result of a device rollout, with the reference's assertion on the start."""
@@ -336,7 +388,8 @@ class Evaluation(object):
             for gt, rows in routes:
                 ix = t.index[gt['scan']]
                 out.append(self._score_rows(gt['scan'], rows, ix[gt['path'][-1]],
-                                            [ix[v] for v in gt['path']] if self.path_metrics else None))
+                                            [ix[v] for v in gt['path']] if self.path_metrics else None,
+                                            self._gold_lengths()[gt['path_id']] if self.coverage_metrics else None))
         return out
 
     def _score_routes_on_device(self, routes):
@@ -366,33 +419,48 @@ class Evaluation(object):
                                 ptr_of(gold['dev'][1]), ptr_of(d32[1]), ptr_of(d32[4]), ptr_of(d32[2]), ptr_of(d64[1]),
                                 ptr_of(d32[3]), ptr_of(t.dev), self.error_margin, *[ptr_of(o64[k]) for k in range(5)],
                                 *[ptr_of(o32[k * N:]) for k in range(3)])
-            status = _lib.lib.sf_eval_score_routes(C.byref(e), C.c_void_p(ptr_of(o32[3 * N:])), stream())
+            if self.coverage_metrics:                         # the same launch, + near [N, longest]
+                entry, ld = 'sf_eval_score_routes_coverage', gold['longest']
+                near = torch.empty(N, ld, dtype=torch.float64, device=dev)
+                status = _lib.lib.sf_eval_score_routes_coverage(C.byref(e), C.c_void_p(ptr_of(near)), ld,
+                                                                C.c_void_p(ptr_of(o32[3 * N:])), stream())
+            else:
+                entry = 'sf_eval_score_routes'
+                status = _lib.lib.sf_eval_score_routes(C.byref(e), C.c_void_p(ptr_of(o32[3 * N:])), stream())
             if status == _lib.SF_ERR_UNSUPPORTED:             # a gold path above the kernel's 64 nodes
                 self.fallbacks += 1
                 return None
-            _lib.check(status, 'sf_eval_score_routes')
+            _lib.check(status, entry)
             h64 = torch.empty(5, N, dtype=torch.float64).pin_memory()
             h32 = torch.empty(3 * N + 1, dtype=torch.int32).pin_memory()
             h64.copy_(o64, non_blocking=True)
             h32.copy_(o32, non_blocking=True)
+            if self.coverage_metrics:
+                hnear = torch.empty(N, ld, dtype=torch.float64).pin_memory()
+                hnear.copy_(near, non_blocking=True)
             torch.cuda.current_stream().synchronize()         # the one host sync of the batch
         self.last_host_syncs = 1
         self.host_syncs += 1
         if int(h32[3 * N]):
-            raise RuntimeError('sf_eval_score_routes: a route left its scan or does not start where its gold path does')
+            raise RuntimeError('%s: a route left its scan or does not start where its gold path does' % entry)
         f, k = h64.numpy(), h32.numpy()[:3 * N].reshape(3, N)
         margin = self.error_margin
         six = [EvalResult(a, b, c, d, bool(s), bool(o)) for a, b, c, d, s, o in
                zip(f[0].tolist(), f[1].tolist(), k[0].tolist(), f[2].tolist(), k[1].tolist(), k[2].tolist())]
         if not self.path_metrics:
             return six
-        return [path_metrics_of(r, sh, dtw, len(gt['path']), margin)
+        full = [path_metrics_of(r, sh, dtw, len(gt['path']), margin)
                 for r, sh, dtw, (gt, _) in zip(six, f[3].tolist(), f[4].tolist(), routes)]
+        if not self.coverage_metrics:
+            return full
+        lengths = self._gold_lengths()
+        return [coverage_metrics_of(r, row[:len(gt['path'])], lengths[gt['path_id']], margin)
+                for r, row, (gt, _) in zip(full, hnear.numpy().tolist(), routes)]
 
     def score_routes(self, instr_ids, trajectories):
         """What `_score_item(instr_id, trajectory)` returns for every pair, as one batch: EvalResult -- PathEvalResult
-        with path_metrics -- per route (a trajectory: [(viewpoint, heading, elevation), ...] or a result of a device
-        rollout)."""
+        with path_metrics, CoverageEvalResult with coverage_metrics -- per route (a trajectory: [(viewpoint, heading,
+        elevation), ...] or a result of a device rollout)."""
         return self._score_routes([self._route_of(i, p) for i, p in zip(instr_ids, trajectories)])
 
     # ---- eval.py:86-145
@@ -425,7 +493,10 @@ class Evaluation(object):
                                         r.success, r.oracle_success)):
                 self.scores[name].append(v)
             if self.path_metrics:
-                for name, v in zip(_PATH_LISTS, r[6:]):
+                for name, v in zip(_PATH_LISTS, r[6:11]):
+                    self.scores[name].append(v)
+            if self.coverage_metrics:
+                for name, v in zip(_COVERAGE_LISTS, r[11:]):
                     self.scores[name].append(v)
         return self._summary(instr_ids, len(taken), model_scores), self.scores
 
@@ -448,6 +519,8 @@ class Evaluation(object):
         if self.path_metrics:
             for name in ('spl', 'ndtw', 'sdtw'):
                 summary[name] = np.average(sc[name])
+        if self.coverage_metrics:
+            summary['cls'] = np.average(sc['cls'])
         return summary
 
     def score_file(self, output_file):
@@ -493,6 +566,9 @@ class Evaluation(object):
                        err=d(1, dt=i32), err_h=p(1, dt=i32))
             if self.path_metrics:
                 buf['first'] = torch.arange(B, dtype=i64, device=dev)                     # sweep layout: row_first[b] = b
+            if self.coverage_metrics:                                                     # near [slot, gold position]
+                ld = self._gold_table()['longest']
+                buf.update(near=d(n, ld, dt=f64), near_h=p(n, ld, dt=f64))
             self._sweep_buffers = {key: buf}
         if keep and 'rows_h' not in buf:
             import torch
@@ -513,7 +589,9 @@ class Evaluation(object):
         take, means agent.test() + score_results instead (`fallbacks`): a faulting sweep is never scored, and the
         environment's item order and `random` are put back first, so that test() walks what the sweep walked.
         With path_metrics the launch behind every rollout is sf_eval_score_routes in its sweep layout (the same arrays,
-        plus the episode's gold path index): still one host sync."""
+        plus the episode's gold path index): still one host sync.  With coverage_metrics it is
+        sf_eval_score_routes_coverage, which also fills `near` [instruction, gold position]: one more download behind the
+        same sync."""
         nav = self._sweepable(agent, use_dropout, feedback)
         if nav is None:
             return self._by_test(agent, use_dropout, feedback)
@@ -597,7 +675,11 @@ class Evaluation(object):
                                          ptr_of(d32[4]), ptr_of(d32[1]), ptr_of(d32[2]), ptr_of(buf['per64'][k]),
                                          ptr_of(d32[3]), ptr_of(t.dev), self.error_margin,
                                          *[ptr_of(o64[i]) for i in (0, 1, 2, 3, 4)], *[ptr_of(o32[i]) for i in (0, 1, 2)])
-                    _lib.call('sf_eval_score_routes', C.byref(ep), C.c_void_p(buf['err'].data_ptr()), stream())
+                    if self.coverage_metrics:
+                        _lib.call('sf_eval_score_routes_coverage', C.byref(ep), C.c_void_p(ptr_of(buf['near'])),
+                                  gold['longest'], C.c_void_p(buf['err'].data_ptr()), stream())
+                    else:
+                        _lib.call('sf_eval_score_routes', C.byref(ep), C.c_void_p(buf['err'].data_ptr()), stream())
                 else:
                     ep = _lib.EvalEpisodes(S, B, len(self.instr_ids), 0, ptr_of(batch.row), ptr_of(st.actions),
                                            ptr_of(d32[0]), ptr_of(d32[1]), ptr_of(d32[2]), ptr_of(buf['per64'][k]),
@@ -612,7 +694,7 @@ class Evaluation(object):
                     buf['acts_h'][k].copy_(st.actions[:S], non_blocking=True)
                 issued.append(items)
             n_mb = len(issued)
-            for name in ('out64', 'out32', 'loss', 'sc', 'err'):
+            for name in ('out64', 'out32', 'loss', 'sc', 'err') + (('near',) if self.coverage_metrics else ()):
                 buf[name + '_h'].copy_(buf[name], non_blocking=True)
             faults = fault_views(dev)
             fpin = torch.empty(len(faults), dtype=torch.int32).pin_memory()
@@ -631,7 +713,8 @@ class Evaluation(object):
         self.host_syncs += syncs
         if int(buf['err_h'][0]):
             raise RuntimeError('%s: a rollout left its scan, or a slot its array'
-                               % ('sf_eval_score_routes' if self.path_metrics else 'sf_eval_score'))
+                               % ('sf_eval_score_routes_coverage' if self.coverage_metrics else
+                                  'sf_eval_score_routes' if self.path_metrics else 'sf_eval_score'))
         M = len(order)
         o64, o32 = buf['out64_h'].numpy(), buf['out32_h'].numpy()
         self.scores = defaultdict(list)
@@ -648,6 +731,12 @@ class Evaluation(object):
                     for six, sh, dtw, g in zip(zip(*lists), o64[3, :M].tolist(), o64[4, :M].tolist(), goldn)]
             for i, name in enumerate(_PATH_LISTS):
                 self.scores[name] = [r[6 + i] for r in full]
+            if self.coverage_metrics:                         # cls per item by the one function of the host path
+                lengths = self._gold_lengths()
+                full = [coverage_metrics_of(r, row[:g], lengths[int(iid.split('_')[0])], self.error_margin)
+                        for r, row, g, iid in zip(full, buf['near_h'].numpy()[:M].tolist(), goldn, order)]
+                for i, name in enumerate(_COVERAGE_LISTS):
+                    self.scores[name] = [r[11 + i] for r in full]
         # 'score' of a result: the sequential float32 sum of its step scores up to the stop (nav.trajectories_from)
         sc = buf['sc_h'].numpy()[:n_mb]
         totals = np.cumsum(sc, axis=1, dtype=np.float32)

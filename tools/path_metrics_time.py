@@ -6,7 +6,13 @@ scans: the world of tests/test_gpu_evaluation.py), in one process, after a warm-
 * 16 x 156 recorded routes scored candidate by candidate with _score_item (what run_rational_follower(compute_oracle=True)
   did per minibatch) and as one batch with score_routes (one ragged launch), for both result types: median of 5.
 
-    python tools/path_metrics_time.py [--out profiles/path_metrics_sweep.txt]"""
+    python tools/path_metrics_time.py [--out profiles/path_metrics_sweep.txt]
+
+--coverage takes a third turn in both parts with coverage_metrics on (CLS: sf_eval_score_routes_coverage, the same launch
+plus `near`, and one more download behind the same sync) under the name `cls`, and ends with the device time of the
+kernel's two instantiations (sf_profile_begin / sf_profile_end) over the recorded routes and over the sweep:
+
+    python tools/path_metrics_time.py --coverage [--out profiles/coverage_metrics_sweep.txt]"""
 import os
 import random
 import statistics
@@ -22,6 +28,7 @@ from speaker_follower_amd import agents, evaluation, features, model, nav, synth
 
 REPS, ROUTE_REPS, COPIES = 12, 5, 16
 out_path = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else None
+coverage = '--coverage' in sys.argv
 lines = []
 
 
@@ -45,6 +52,8 @@ agent = agents.Seq2SeqAgent(env, '/tmp/sf_path_metrics_time.json', enc, dec, epi
 agent.store = features.FeatureStore(table)
 agent.use_device_env(nav.NavTable(env, agent.store))
 evs = {'off': evaluation.Evaluation(env=env), 'on': evaluation.Evaluation(env=env, path_metrics=True)}
+if coverage:
+    evs['cls'] = evaluation.Evaluation(env=env, coverage_metrics=True)
 data0, state0 = list(env.data), random.getstate()
 
 
@@ -53,10 +62,10 @@ def rewind():
     random.setstate(state0)
 
 
-times = {'off': [], 'on': []}
+times = {name: [] for name in evs}
 summaries = {}
 for rep in range(REPS + 2):                                                  # (the first two of each: warm-up, captures)
-    for name in ('off', 'on'):
+    for name in evs:
         rewind()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -65,7 +74,7 @@ for rep in range(REPS + 2):                                                  # (
         if rep >= 2:
             times[name].append(dt * 1e3)
 rewind()
-for name in ('off', 'on'):
+for name in evs:
     assert evs[name].fallbacks == 0 and evs[name].last_host_syncs == 1
     ms = times[name]
     say('Evaluation.score_agent, path_metrics %-3s  median %.2f ms  min %.2f  max %.2f  (%d runs, %d instructions, %d '
@@ -73,13 +82,17 @@ for name in ('off', 'on'):
                                 cfg['batch']))
 for k in summaries['off']:
     assert summaries['on'][k] == summaries['off'][k], k
+if coverage:
+    for k in summaries['on']:
+        assert summaries['cls'][k] == summaries['on'][k], k
+    say('cls %.4f' % summaries['cls']['cls'])
 say('spl %.4f  ndtw %.4f  sdtw %.4f  at success_rate %.4f' % tuple(summaries['on'][k] for k in
                                                                    ('spl', 'ndtw', 'sdtw', 'success_rate')))
 
 results = {k: [(v, h, 0.0) for v, h in zip(w['viewpoints'], w['headings'])] for k, w in gold['items'].items()}
 ids = [k for k in results if k in evs['on'].instr_ids] * COPIES
 paths = [results[k] for k in ids]
-for name in ('off', 'on'):
+for name in evs:
     ev = evs[name]
     ev.score_routes(ids, paths)
     loop, batch = [], []
@@ -94,6 +107,25 @@ for name in ('off', 'on'):
         assert [tuple(x) for x in one_by_one] == [tuple(x) for x in at_once]
     say('%d routes, path_metrics %-3s  _score_item per route: median %.1f ms   score_routes (one launch): median %.1f ms'
         '  (%d runs)' % (len(ids), name, statistics.median(loop), statistics.median(batch), ROUTE_REPS))
+if coverage:                                                                 # the two instantiations of the one kernel
+    from speaker_follower_amd import _lib
+    with _lib.kernel_profile() as prof:
+        for rep in range(ROUTE_REPS):
+            for name in ('on', 'cls'):
+                evs[name].score_routes(ids, paths)
+    for kernel, row in sorted(prof.rows.items()):
+        say('%d routes, kernel %-30s  avg %.1f us  min %.1f  max %.1f  (%d launches, taking turns)'
+            % (len(ids), kernel, row['avg_us'], row['min_us'], row['max_us'], row['calls']))
+    with _lib.kernel_profile() as prof:
+        for rep in range(ROUTE_REPS):
+            for name in ('on', 'cls'):
+                rewind()
+                evs[name].score_agent(agent)
+    rewind()
+    for kernel, row in sorted(prof.rows.items()):
+        if 'eval_routes_kernel' in kernel:
+            say('sweep of %d routes per launch, kernel %-30s  avg %.1f us  min %.1f  max %.1f  (%d launches)'
+                % (cfg['batch'], kernel, row['avg_us'], row['min_us'], row['max_us'], row['calls']))
 if out_path:
     with open(out_path, 'w') as f:
         f.write('\n'.join(lines) + '\n')
