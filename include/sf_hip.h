@@ -1217,6 +1217,36 @@ int sf_nav_step(const sf_nav_table* nav, int B, const int32_t* row, const int32_
                 const int32_t* hop_base, int32_t* row_next, int32_t* vp_next, int32_t* view_next,
                 int32_t* a_num_next, int32_t* cand_view_next, float* sincos_next,
                 int64_t* target_next, sf_stream stream);
+/* sf_nav_walk (csrc/sf_nav.hip; follower.py:197-259, env.py:742-761, 823-848), additive to ABI 10: B whole episodes of
+ * a policy that is a table look-up, at most S actions each, in ONE launch.  It leaves a rollout's own arrays -- row /
+ * view [S+1,B] (slot 0 = the start state row0 / view0, action t takes slot t to slot t + 1), actions [S,B] -- so that
+ * sf_eval_score_routes and DeviceNavBatch.trajectories_from read them as they are, and n_steps [B]: the poses of the
+ * RESULT minus one.  The state transition is sf_nav_step's to the letter: s = row * V + view; an action >= a_num[s]
+ * counts as 0; action 0, and a candidate whose next_row is the current row, leave the state; otherwise row =
+ * next_row[s][a], view = cand_view[s][a].
+ *   SF_WALK_STOP      action 0 at t = 0; n_steps = 0.
+ *   SF_WALK_SHORTEST  sf_nav_step's teacher: with hop = goal_hop[b][row - hop_base[b]] the action is 0 if hop == row,
+ *                     else the first candidate c in [1, a_num) with next_row[s][c] == hop, 0 if there is none.  With k
+ *                     the index of the first action 0 (S if there is none) n_steps = min(k, S - 1): the reference
+ *                     drops the last observation as the duplicated end state, also when max_steps cut the walk off.
+ *   SF_WALK_RANDOM    needs S >= SF_WALK_RANDOM_MOVES + 1.  Action 0 is first_action[b], which must lie in [1, a_num);
+ *                     actions 1 .. 4 are 1 and their states must have a_num > 1; action 5 is 0; n_steps = 5.  A row
+ *                     that breaks either condition raises err[0], gets n_steps = -1, actions 0 throughout and the
+ *                     start state in every slot.
+ * After a row's stop its later actions are 0 and its later slots repeat the last state: every element of the four
+ * outputs is written by every launch.  first_action is read for SF_WALK_RANDOM only, goal_hop / ld_hop / hop_base for
+ * SF_WALK_SHORTEST only (NULL / 0 otherwise).  One wavefront per episode, lane c owns candidate slot c.
+ *   SF_ERR_ARG on NULL pointers (of the table: a_num, next_row, cand_view), arrays the policy needs and did not get,
+ *   B < 1, S < 1, an unknown policy, SF_WALK_RANDOM with S < 6; SF_ERR_UNSUPPORTED for nav->A > 64; nothing is launched
+ *   or written then.  Start rows are the caller's, as for sf_nav_step; a view0 outside [0, V) raises err[0] (only ever
+ *   raised) and the row is left as a failed SF_WALK_RANDOM row is, without a look at the table. */
+#define SF_WALK_STOP 0
+#define SF_WALK_SHORTEST 1
+#define SF_WALK_RANDOM 2
+#define SF_WALK_RANDOM_MOVES 5
+int sf_nav_walk(const sf_nav_table* nav, int policy, int B, int S, const int32_t* row0, const int32_t* view0,
+                const int32_t* first_action, const int32_t* goal_hop, int ld_hop, const int32_t* hop_base,
+                int32_t* row, int32_t* view, int64_t* actions, int32_t* n_steps, int32_t* err, sf_stream stream);
 
 /* The follower's beam selection for one decode step (follower.py:606-690), all instances at once, no host round trip:
  * what search.DeviceFollowerBeam issues after sf_attn_decoder_fwd + sf_logprob_topk (n_valid = a_num) in its device

@@ -8,6 +8,9 @@ book-keeping and the simulator calls stay in Python exactly where the reference 
 When observations are available in index form, `FollowerEngine` / `SpeakerEngine` are the fast
 path; this module is the drop-in path.  Beam search, state-factored search and the speaker's beam search
 (follower.py:541-980, speaker.py:211-318) live in search.py and run on index-form observations.
+
+The baseline agents (StopAgent, ShortestAgent, RandomAgent; follower.py:197-259) have no network: a host path over the
+environment's own calls, and a device path that is one sf_nav_walk launch per rollout.
 """
 import ctypes as C
 import json
@@ -83,6 +86,10 @@ class BaseAgent(object):
     def rollout(self):
         raise NotImplementedError
 
+    @staticmethod
+    def get_agent(name):
+        return globals()[name + 'Agent']                               # follower.py:131-133
+
     def test(self):
         self.env.reset_epoch()
         self.losses = []
@@ -97,6 +104,121 @@ class BaseAgent(object):
             if looped:
                 break
         return self.results
+
+
+class _TableAgent(BaseAgent):
+    """What the three baseline agents (follower.py:197-259) share: a policy that is a table look-up, walked either on
+    the host over env.reset / observe / step, or -- when the environment yields a navigation table on the device, the
+    way Seq2SeqAgent._device_table finds one -- as ONE sf_nav_walk launch (nav.NavTable.walk) with one download and one
+    host sync per rollout().  Both paths give == results."""
+    walk_policy = None           # _lib.SF_WALK_*
+    walk_steps = 1               # S of the launch: the most actions an episode takes
+    nav_table = None
+    store = None
+    auto_device_env = True
+
+    def use_device_env(self, nav_table):
+        self.nav_table = nav_table
+
+    def _device_table(self):
+        """The navigation table to walk on, or None for the host path: the one given to use_device_env, else (auto) the
+        current env's own when it carries a feature store and no host table -- and only a table that is on a GPU."""
+        nav = self.nav_table
+        if nav is None:
+            if not self.auto_device_env or getattr(self.env, 'host_table', 1) is not None or not hasattr(self.env, 'graphs'):
+                return None
+            feats = getattr(self.env, 'image_features_list', None) or [None]
+            store = self.store if self.store is not None else getattr(feats[0], 'store', None)
+            if store is None:
+                return None
+            from .nav import table_for
+            nav = table_for(self.env, store)
+        return nav if nav.device.type == 'cuda' else None
+
+    def _first_actions(self, nav, rows, views):
+        return None
+
+    def walk_inputs(self, nav, items):
+        """Host side of a device walk of `items`: start states, and what the policy reads (RandomAgent draws here)."""
+        rows, views = nav.start_states(items)
+        hop, base = nav.hop_rows(items) if self.walk_policy == _lib.SF_WALK_SHORTEST else (None, None)
+        return dict(rows=rows, views=views, first_action=self._first_actions(nav, rows, views), hop=hop, base=base)
+
+    def walk_error(self):
+        """The host path's exception for a row sf_nav_walk refused."""
+        return RuntimeError('sf_nav_walk: a start view outside the table')
+
+    def _rollout_on_device(self, nav):
+        self.env.reset()
+        items = list(self.env.batch)
+        out = nav.walk(self.walk_policy, self.walk_steps, **self.walk_inputs(nav, items))
+        S, B = self.walk_steps, len(items)
+        host = torch.empty(2 * (S + 1) * B + B + 1, dtype=torch.int32).pin_memory()
+        host.copy_(torch.cat([out['row'].reshape(-1), out['view'].reshape(-1), out['n_steps'], out['err']]),
+                   non_blocking=True)
+        torch.cuda.current_stream().synchronize()                      # the one host sync of the rollout
+        h = host.numpy()
+        if h[-1]:
+            raise self.walk_error()
+        n = (S + 1) * B
+        return nav.walk_results(items, h[:n].reshape(S + 1, B), h[n:2 * n].reshape(S + 1, B), h[2 * n:2 * n + B])
+
+    def rollout(self):
+        nav = self._device_table()
+        return self._rollout_on_device(nav) if nav is not None else self._rollout_on_host()
+
+
+class StopAgent(_TableAgent):
+    """follower.py:197-207: an agent that does not move."""
+    walk_policy, walk_steps = _lib.SF_WALK_STOP, 1
+
+    def _rollout_on_host(self):
+        obs = self.env.observe(self.env.reset())
+        return [{'instr_id': ob['instr_id'], 'trajectory': [path_element_from_observation(ob)]} for ob in obs]
+
+
+class RandomAgent(_TableAgent):
+    """follower.py:210-243: a random first direction, then candidate 1 ("straight on") for four more viewpoint steps,
+    then stop.  The first action comes from numpy's GLOBAL stream, `np.random.randint(len(adj) - 1) + 1`, one draw per
+    observation in observation order, on both paths."""
+    walk_policy, walk_steps = _lib.SF_WALK_RANDOM, _lib.SF_WALK_RANDOM_MOVES + 1
+
+    def _rollout_on_host(self):
+        env = self.env
+        ws = env.reset()
+        obs = env.observe(ws)
+        traj = [{'instr_id': ob['instr_id'], 'trajectory': [path_element_from_observation(ob)]} for ob in obs]
+        for t in range(_lib.SF_WALK_RANDOM_MOVES):                     # (the stop behind them is a no-op: not walked)
+            if t == 0:
+                actions = [np.random.randint(len(ob['adj_loc_list']) - 1) + 1 for ob in obs]
+            else:
+                for ob in obs:
+                    assert len(ob['adj_loc_list']) > 1
+                actions = [1] * len(obs)
+            ws = env.step(ws, actions, obs)
+            obs = env.observe(ws)
+            for tr, ob in zip(traj, obs):
+                tr['trajectory'].append(path_element_from_observation(ob))
+        return traj
+
+    def _first_actions(self, nav, rows, views):
+        from .nav import V
+        a_num = nav.host['a_num'][rows.astype(np.int64) * V + views].tolist()
+        return np.array([np.random.randint(n - 1) + 1 for n in a_num], np.int32)
+
+    def walk_error(self):
+        return AssertionError('RandomAgent: a dead end on the way')
+
+
+class ShortestAgent(_TableAgent):
+    """follower.py:245-259: the teacher's route to the goal, at most 20 actions; the last observation is dropped (the
+    stop is a no-op, so the end state would appear twice)."""
+    walk_policy, walk_steps = _lib.SF_WALK_SHORTEST, 20
+
+    def _rollout_on_host(self):
+        all_obs, _ = self.env.shortest_paths_to_goals(self.env.reset(), self.walk_steps)
+        return [{'instr_id': obs[0]['instr_id'], 'trajectory': [path_element_from_observation(ob) for ob in obs[:-1]]}
+                for obs in all_obs]
 
 
 class Seq2SeqAgent(BaseAgent):

@@ -314,7 +314,9 @@ class R2RIndexEnv:
         ob = dict(instr_id=item['instr_id'], scan=ws.scanId, viewpoint=ws.viewpointId,
                   viewIndex=view, heading=(view % 12) * ANGLE_INC, elevation=(view // 12 - 1) * ANGLE_INC,
                   adj_loc_list=adj, vp_row=self.row_of[ws.scanId + '_' + ws.viewpointId],
-                  instr_encoding=item['instr_encoding'], instructions=item.get('instructions', ''))
+                  instructions=item.get('instructions', ''))
+        if 'instr_encoding' in item:                          # (env.py:791-792: an env built without a tokenizer has none)
+            ob['instr_encoding'] = item['instr_encoding']
         if include_teacher:
             ob['teacher'] = self._teacher(ws, adj, item['path'][-1])
         if dense:

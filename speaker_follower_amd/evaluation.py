@@ -14,6 +14,9 @@ summary averages over the instructions '<path_id>_0' .. '_2' of the split.
                       `score_routes` scores a batch of routes in one launch.
                       `coverage_metrics=True` adds CLS (coverage weighted by length score) on top of those: the
                       per-gold-node minimum distance comes out of the same launch (sf_eval_score_routes_coverage).
+                      For a baseline agent (agents.StopAgent / ShortestAgent / RandomAgent) `score_agent` is one
+                      sf_nav_walk launch over the split and one route-scoring launch behind it.
+  * `evaluate_simple_agents`, `eval_simple_agents`   eval.py:148-163, the Stop / Shortest / Random table.
 
 The reference takes its table from networkx (all_pairs_dijkstra_path_length); nothing here imports it.
 """
@@ -592,6 +595,8 @@ class Evaluation(object):
         plus the episode's gold path index): still one host sync.  With coverage_metrics it is
         sf_eval_score_routes_coverage, which also fills `near` [instruction, gold position]: one more download behind the
         same sync."""
+        if hasattr(agent, 'walk_policy'):                     # a baseline agent: its own sweep, or its own test()
+            return self._score_table_agent(agent, keep_results)
         nav = self._sweepable(agent, use_dropout, feedback)
         if nav is None:
             return self._by_test(agent, use_dropout, feedback)
@@ -717,6 +722,27 @@ class Evaluation(object):
                                   'sf_eval_score_routes' if self.path_metrics else 'sf_eval_score'))
         M = len(order)
         o64, o32 = buf['out64_h'].numpy(), buf['out32_h'].numpy()
+        self._scores_of_sweep(order, o64, o32, buf['near_h'].numpy() if self.coverage_metrics else None)
+        # 'score' of a result: the sequential float32 sum of its step scores up to the stop (nav.trajectories_from)
+        sc = buf['sc_h'].numpy()[:n_mb]
+        totals = np.cumsum(sc, axis=1, dtype=np.float32)
+        kb = np.asarray(where, np.int64).reshape(M, 2)
+        model_scores = totals[kb[:, 0], o32[0, :M] - 1, kb[:, 1]].tolist()
+        agent.losses = buf['loss_h'][:n_mb].tolist()
+        agent.loss = torch.tensor(agent.losses[-1])
+        if keep_results:
+            for k, items in enumerate(issued):
+                rows, views, acts = (buf[x][k].numpy().copy() for x in ('rows_h', 'views_h', 'acts_h'))
+                for tr, it in zip(cached[2].trajectories_from(items, S, rows, views, acts, sc[k].copy()), items):
+                    tr['instr_encoding'] = it['instr_encoding']
+                    agent.results.setdefault(tr['instr_id'], tr)
+        return self._summary(self.instr_ids - set(order), M, model_scores), self.scores
+
+    def _scores_of_sweep(self, order, o64, o32, near):
+        """`self.scores` from a sweep's downloaded outputs: o64 [3 or 5, n_slots] (nav_error, oracle_error, length,
+        + shortest, dtw), o32 [3, n_slots] (steps, success, oracle_success), near [n_slots, longest] with
+        coverage_metrics; slot i belongs to instruction order[i]."""
+        M = len(order)
         self.scores = defaultdict(list)
         self.scores['nav_errors'] = o64[0, :M].tolist()
         self.scores['oracle_errors'] = o64[1, :M].tolist()
@@ -734,20 +760,135 @@ class Evaluation(object):
             if self.coverage_metrics:                         # cls per item by the one function of the host path
                 lengths = self._gold_lengths()
                 full = [coverage_metrics_of(r, row[:g], lengths[int(iid.split('_')[0])], self.error_margin)
-                        for r, row, g, iid in zip(full, buf['near_h'].numpy()[:M].tolist(), goldn, order)]
+                        for r, row, g, iid in zip(full, near[:M].tolist(), goldn, order)]
                 for i, name in enumerate(_COVERAGE_LISTS):
                     self.scores[name] = [r[11 + i] for r in full]
-        # 'score' of a result: the sequential float32 sum of its step scores up to the stop (nav.trajectories_from)
-        sc = buf['sc_h'].numpy()[:n_mb]
-        totals = np.cumsum(sc, axis=1, dtype=np.float32)
-        kb = np.asarray(where, np.int64).reshape(M, 2)
-        model_scores = totals[kb[:, 0], o32[0, :M] - 1, kb[:, 1]].tolist()
-        agent.losses = buf['loss_h'][:n_mb].tolist()
-        agent.loss = torch.tensor(agent.losses[-1])
+
+    # ---- a baseline agent's test() + score_results: one walk launch, one scoring launch
+    def _score_table_agent(self, agent, keep_results=False):
+        """score_agent for agents.StopAgent / ShortestAgent / RandomAgent.  The environment is walked as BaseAgent.test
+        walks it (reset_epoch, reset() until an id repeats; `env.ix`, `random` and `np.random` end where test() leaves
+        them: RandomAgent draws for every row of every minibatch, repeated ids included), but nothing is launched per
+        minibatch: the first occurrences of the whole split are ONE sf_nav_walk launch, and behind it ONE
+        sf_eval_score_routes launch over the walk's own arrays (row_stride = B, row_first[b] = b, the walk's n_steps;
+        sf_eval_score_routes_coverage with coverage_metrics), then one host sync.  The classic six come from that
+        launch whatever the metric switches say.  An agent without a table on the device, distances that are not
+        there, or gold paths the kernel refuses: agent.test() + score_results (`fallbacks`)."""
+        from . import _lib                                   # (loaded: the agent's class reads its policy from it)
+        nav = agent._device_table()
+        gold = self._gold_table() if nav is not None and self.table.dev is not None else None
+        if gold is None or gold['dev'] is None or not 1 <= gold['longest'] <= _lib.SF_EVAL_MAX_GOLD:
+            self.fallbacks += 1
+            agent.test()
+            return self.score_results(agent.results)
+        import torch
+        from .runtime import stream
+        env, t = agent.env, self.table
+        dev = t.dev.device
+        env.reset_epoch()
+        agent.losses, agent.results = [], {}
+        walked, seen, looped = [], set(), False               # walked: (item, row, view, first action) per first occurrence
+        while not looped:
+            env.reset()
+            items = list(env.batch)
+            rows, views = nav.start_states(items)
+            first = agent._first_actions(nav, rows, views)
+            for b, it in enumerate(items):
+                if it['instr_id'] in seen:
+                    looped = True
+                else:
+                    seen.add(it['instr_id'])
+                    walked.append((it, rows[b], views[b], 0 if first is None else first[b]))
+        S, B, n = agent.walk_steps, len(walked), len(self.instr_ids)
+        order = []
+        i32 = np.zeros((4, B), np.int32)                      # gold_id, scan_base, m, slot
+        i64 = np.zeros((2, B), np.int64)                      # row_first, dist_off
+        i64[0] = np.arange(B)
+        for b, (it, _, _, _) in enumerate(walked):
+            scan, slot = it['scan'], -1
+            if it['instr_id'] in self.instr_ids:
+                slot = len(order)
+                order.append(it['instr_id'])
+            i32[:, b] = gold['ids'].get(it.get('path_id'), 0), self._local_rows(nav, scan), t.m[scan], slot
+            i64[1, b] = t.off[scan]
+        items = [w[0] for w in walked]
+        hop, base = nav.hop_rows(items) if agent.walk_policy == _lib.SF_WALK_SHORTEST else (None, None)
+        ptr_of = lambda x: x.data_ptr()                       # noqa: E731
+        with torch.cuda.device(dev):
+            out = nav.walk(agent.walk_policy, S, np.array([w[1] for w in walked], np.int32),
+                           np.array([w[2] for w in walked], np.int32),
+                           None if first is None else np.array([w[3] for w in walked], np.int32), hop, base)
+            d32, d64 = torch.from_numpy(i32).to(dev), torch.from_numpy(i64).to(dev)
+            o64 = torch.empty(5, n, dtype=torch.float64, device=dev)
+            o32 = torch.zeros(3 * n + 1, dtype=torch.int32, device=dev)                   # (the last word: err)
+            e = _lib.EvalRoutes(S, B, n, B, len(gold['ids']), len(gold['node']), gold['longest'], 0, (S + 1) * B,
+                                ptr_of(out['row']), ptr_of(d64[0]), ptr_of(out['n_steps']), ptr_of(out['actions']),
+                                ptr_of(gold['dev'][0]), ptr_of(gold['dev'][1]), ptr_of(d32[0]), ptr_of(d32[1]),
+                                ptr_of(d32[2]), ptr_of(d64[1]), ptr_of(d32[3]), ptr_of(t.dev), self.error_margin,
+                                *[ptr_of(o64[k]) for k in range(5)], *[ptr_of(o32[k * n:]) for k in range(3)])
+            near = None
+            if self.coverage_metrics:
+                entry, ld = 'sf_eval_score_routes_coverage', gold['longest']
+                near = torch.empty(n, ld, dtype=torch.float64, device=dev)
+                _lib.call(entry, C.byref(e), C.c_void_p(ptr_of(near)), ld, C.c_void_p(ptr_of(o32[3 * n:])), stream())
+            else:
+                entry = 'sf_eval_score_routes'
+                _lib.call(entry, C.byref(e), C.c_void_p(ptr_of(o32[3 * n:])), stream())
+            down = [o64, o32, out['err']] + ([near] if near is not None else [])
+            if keep_results:
+                down += [out['row'], out['view'], out['n_steps']]
+            got = [torch.empty(x.shape, dtype=x.dtype).pin_memory() for x in down]
+            for h, x in zip(got, down):
+                h.copy_(x, non_blocking=True)
+            torch.cuda.current_stream().synchronize()         # the one host sync of the sweep
+        self.sweeps += 1
+        self.last_host_syncs = 1
+        self.host_syncs += 1
+        if int(got[2][0]):
+            raise agent.walk_error()
+        if int(got[1][3 * n]):
+            raise RuntimeError('%s: a walk left its scan, or a slot its array' % entry)
+        self._scores_of_sweep(order, got[0].numpy(), got[1].numpy()[:3 * n].reshape(3, n),
+                              got[3].numpy() if near is not None else None)
         if keep_results:
-            for k, items in enumerate(issued):
-                rows, views, acts = (buf[x][k].numpy().copy() for x in ('rows_h', 'views_h', 'acts_h'))
-                for tr, it in zip(cached[2].trajectories_from(items, S, rows, views, acts, sc[k].copy()), items):
-                    tr['instr_encoding'] = it['instr_encoding']
-                    agent.results.setdefault(tr['instr_id'], tr)
-        return self._summary(self.instr_ids - set(order), M, model_scores), self.scores
+            rows, views, steps = (x.numpy() for x in got[-3:])
+            for r in nav.walk_results(items, rows, views, steps):
+                agent.results[r['instr_id']] = r
+        return self._summary(self.instr_ids - set(order), len(order), []), self.scores
+
+
+def evaluate_simple_agents(env, ev, result_dir, agent_types=('Stop', 'Shortest', 'Random')):
+    """eval.py:155-163 for one environment and its evaluator: every baseline agent is tested, its results written to
+    `<result_dir><split>_<type in lower case>_agent.json` and that file scored; the name and the summary are printed.
+    Returns {type: summary}."""
+    import pprint
+    from .agents import BaseAgent
+    split = ','.join(getattr(env, 'splits', None) or ev.splits)
+    summaries = {}
+    for agent_type in agent_types:
+        outfile = '%s%s_%s_agent.json' % (result_dir, split, agent_type.lower())
+        agent = BaseAgent.get_agent(agent_type)(env, outfile)
+        agent.test()
+        agent.write_results()
+        summaries[agent_type], _ = ev.score_file(outfile)
+        print('\n%s' % agent_type)
+        pprint.PrettyPrinter(indent=4).pprint(summaries[agent_type])
+    return summaries
+
+
+def eval_simple_agents(args):
+    """eval.py:148-163: the Stop / Shortest / Random table of every split, over compat.env's construction surface.  The
+    result directory is train.RESULT_DIR when `train` imports (the reference's script beside the caller), else
+    tasks/R2R/results/."""
+    from .compat.env import ImageFeatures, R2RBatch
+    try:
+        import train
+        result_dir = train.RESULT_DIR
+    except ImportError:
+        result_dir = 'tasks/R2R/results/'
+    img_features = ImageFeatures.from_args(args)
+    out = {}
+    for split in ['train', 'val_seen', 'val_unseen', 'test']:
+        env = R2RBatch(img_features, batch_size=1, splits=[split])
+        out[split] = evaluate_simple_agents(env, Evaluation([split]), result_dir)
+    return out

@@ -12,7 +12,10 @@ function of the state (scan, viewpoint, view index):
   * `DeviceNavBatch`  -- one R2R minibatch: instructions, start states, and per sample the next hop of
                          the shortest path to ITS goal from every viewpoint of its scan (the teacher);
   * `sf_nav_step`     -- the per-step kernel (csrc/sf_nav.hip): state + a_t -> next state, written as
-                         the next decode step's index-form observation.
+                         the next decode step's index-form observation;
+  * `sf_nav_walk`     -- whole episodes of a policy that is a table look-up (stop, the shortest-path
+                         teacher, the random baseline: follower.py:197-259) as ONE launch, through
+                         `NavTable.walk`; it leaves a rollout's row / view / action arrays.
 
 `FollowerEngine.rollout(DeviceNavBatch, ...)` then runs encoder + S decode steps with ONE host sync at
 the end; `trajectories()` turns the recorded states into the reference's result format.
@@ -167,6 +170,46 @@ class NavTable:
         for t, (idx, part) in enumerate(recs):
             rows[first[idx] + t] = part                      # (a route's steps are consecutive from step 0)
         return n, rows
+
+    def start_states(self, items):
+        """(nav rows, view indices) [B] int32 of the items' start poses: newEpisode snaps an item's heading to the
+        discrete view (env.py:814-819)."""
+        env = self.env
+        rows = np.array([self.row_of[(it['scan'], it['path'][0])] for it in items], np.int32)
+        views = np.array([env.start_view(WorldState(it['scan'], it['path'][0], it['heading'], 0)) for it in items], np.int32)
+        return rows, views
+
+    def hop_rows(self, items):
+        """(hop [B, ld] int32, base [B] int32): per item the next nav row towards ITS goal from every row of its scan,
+        and the scan's first nav row -- the teacher's table as sf_nav_step / sf_nav_walk read it."""
+        hop_of = [self.hops(it['scan'], it['path'][-1]) for it in items]
+        hop = np.zeros((len(items), max(len(x) for x in hop_of)), np.int32)
+        for b, x in enumerate(hop_of):
+            hop[b, :len(x)] = x
+        return hop, np.array([self.base[it['scan']] for it in items], np.int32)
+
+    def walk(self, policy, S, rows, views, first_action=None, hop=None, base=None):
+        """ONE sf_nav_walk launch (csrc/sf_nav.hip) on the current stream: B episodes of a table-driven policy
+        (_lib.SF_WALK_STOP / SHORTEST / RANDOM) from the start states `rows`, `views` (host arrays, [B] int32), at most S
+        actions each.  Returns the device tensors it leaves -- row, view [S+1,B] int32, actions [S,B] int64, n_steps [B]
+        int32 (poses of the result minus one), err [1] int32 -- without waiting for them."""
+        dev = self.device
+        B = len(rows)
+        up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)   # noqa: E731
+        ins = [up(a) for a in (rows, views, first_action, hop, base)]
+        z = lambda *s, dt=torch.int32: torch.empty(*s, dtype=dt, device=dev)              # noqa: E731
+        out = dict(row=z(S + 1, B), view=z(S + 1, B), actions=z(S, B, dt=torch.int64), n_steps=z(B),
+                   err=torch.zeros(1, dtype=torch.int32, device=dev))
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())                     # noqa: E731
+        call('sf_nav_walk', C.byref(self.struct()), int(policy), B, int(S), p(ins[0]), p(ins[1]), p(ins[2]), p(ins[3]),
+             hop.shape[1] if hop is not None else 0, p(ins[4]), p(out['row']), p(out['view']), p(out['actions']),
+             p(out['n_steps']), p(out['err']), stream())
+        out['inputs'] = ins                                  # (kept alive until the caller has synchronised)
+        return out
+
+    def walk_results(self, items, rows, views, n_steps):
+        """The result dictionaries of a walk from host copies of its arrays (rows / views [S+1,B], n_steps [B])."""
+        return [_WalkResult(self, it['instr_id'], int(n_steps[b]), rows[:, b], views[:, b]) for b, it in enumerate(items)]
 
     def hops(self, scan, goal):
         """[rows of `scan`] int32: next nav row on the shortest path to `goal` (itself at the goal, and
@@ -381,6 +424,19 @@ class _Trajectory(LazyDict):
             v = int(self._views[t])
             out.append((vp_of[self._rows[t]][1], (v % 12) * ANGLE_INC, (v // 12 - 1) * ANGLE_INC))
         return out
+
+
+class _WalkResult(LazyDict):
+    """One result of a baseline agent's device walk (NavTable.walk): 'instr_id' is there, 'trajectory' -- n + 1 poses
+    with snapped headings -- is made on demand, as _Trajectory's is."""
+    __slots__ = ('_nav', '_n', '_rows', '_views')
+
+    def __init__(self, nav, instr_id, n, rows, views):
+        LazyDict.__init__(self, {'instr_id': instr_id}, ('trajectory',))
+        self._nav, self._n, self._rows, self._views = nav, n, rows, views
+
+    nav_rows = _Trajectory.nav_rows
+    _make = _Trajectory._make
 
 
 def table_for(env, store):
