@@ -1247,6 +1247,68 @@ int sf_nav_step(const sf_nav_table* nav, int B, const int32_t* row, const int32_
 int sf_nav_walk(const sf_nav_table* nav, int policy, int B, int S, const int32_t* row0, const int32_t* view0,
                 const int32_t* first_action, const int32_t* goal_hop, int ld_hop, const int32_t* hop_base,
                 int32_t* row, int32_t* view, int64_t* actions, int32_t* n_steps, int32_t* err, sf_stream stream);
+/* sf_nav_routes (csrc/sf_nav.hip; env.py:742-761, 823-848; speaker.py:68-121), additive to ABI 10: the shortest-path
+ * routes of a whole split in ONE launch, either as their lengths or as the speaker's packed index minibatches.  Slot j
+ * (0 <= j < n_slots) walks route r = route[j] (route == NULL: r = j) from (row0[r], view0[r]) with SF_WALK_SHORTEST's
+ * teacher and sf_nav_step's transition, at most S actions, the stop counted.  The hop comes from ONE table shared by
+ * all routes, hop = hop_all[hop_off[r] + (row - hop_base[r])]: hop_all holds, scan after scan, for every goal g of a
+ * scan of m rows the m next nav rows towards g (the row itself at the goal and where no path exists), hop_off[r] is
+ * the first element of the row of r's goal, hop_base[r] the scan's first nav row and hop_rows[r] its m.  A route stops
+ * where hop == row, or where no candidate in [1, a_num) leads to the hop; a candidate that is the current row leaves
+ * the state alone.  n = the actions of the walk (1 <= n <= S).
+ *   n_actions [n_slots]   n;   reached [n_slots]   1 when the last action is a stop at goal[r], else 0;
+ *   rows [S+1, n_slots]   the nav row before action t in slot t (slot 0 = row0[r]), the last row from slot n on.
+ * Lengths mode (out == NULL): the three arrays are required.  Pack mode (out != NULL): they are optional (all or none)
+ * and hold the same values; slot j is column j % B of minibatch i = j / B (n_slots = M * B), whose block starts at byte
+ * mb_off[i] of `out` and has the sections of speaker.packed_layout with (B, Tp = mb_Tp[i], Lmax), each 8-byte aligned,
+ * in this order (the gaps between them are not written):
+ *   instr_seq  int64 [B, Lmax]  the route's tokens instr_tokens[instr_off[r] .. instr_off[r + 1]) (no tokens given: none)
+ *                               cut to Lmax - 1, then `eos` if all of them fit, `pad` behind; where len + 1 > Lmax the
+ *                               last column holds token Lmax - 1 instead of eos
+ *   vp         int32 [Tp, B]    feat_row of the row before action t;  -1 for t >= n
+ *   view       int32 [Tp, B]    the view before action t;              0 for t >= n
+ *   act        int32 [Tp, B]    1 for a move, 0 for the stop and for t >= n
+ *   act_view   int32 [Tp, B]    cand_view of the chosen slot for a move, else 0
+ *   act_sincos float [Tp, B, 4] cand_sincos of the chosen slot for a move, bit for bit; else (0, 1, 0, 1)
+ *   path_mask  uint8 [B, Tp]    0 for t < n, 1 behind
+ * Every element of every array and section is written by every launch.  mb_Tp / mb_off are HOST arrays: the entry
+ * checks them; mb_Tp_dev / mb_off_dev are the same values on the device, which the kernel reads (and checks again: a
+ * minibatch whose device values break the rules below raises err[0] and none of its slots is written).
+ *   Per slot, each of these raises err[0] (only ever raised) and the slot is written as ONE stop at its start state
+ *   (n_actions 1, reached 0, rows = row0[r] throughout): a route index outside [0, N); view0[r] outside [0, V); a row of
+ *   the walk, the start row first, whose local index row - hop_base[r] lies outside [0, hop_rows[r]).  Its vp is then
+ *   feat_row[row0[r]], or -1 where the route index or the start row itself is at fault (row 0, view 0 for the former).
+ *   In pack mode a route with n > mb_Tp[i] raises err[0] too and its column holds one stop at its start; n_actions,
+ *   reached and rows still report the walk.
+ *   SF_ERR_ARG, with nothing launched or written: NULL nav / io / err, table arrays (a_num, next_row, cand_view; in
+ *   pack mode cand_sincos and feat_row too), row0, view0, goal, hop_all, hop_off, hop_base, hop_rows; N < 1, S < 1,
+ *   n_slots < 1; lengths mode without its three arrays; pack mode with B < 1, Lmax < 1, M < 1, n_slots != M * B,
+ *   out_bytes < 1, a missing mb_* array, only some of n_actions / reached / rows, only one of instr_tokens /
+ *   instr_off, mb_Tp[i] outside [1, S], mb_off[i] negative or not a multiple of 8, or a block that would end beyond
+ *   out_bytes.  SF_ERR_UNSUPPORTED for nav->A > 64.  One wavefront per slot, lane c owns candidate slot c; no LDS, no
+ *   barrier, no atomics. */
+typedef struct sf_nav_routes_io {
+    int32_t N, S, n_slots;         /* routes of the split; most actions of a route; slots of this launch */
+    int32_t B, Lmax, M;            /* pack mode: columns of a minibatch, instruction columns, minibatches */
+    int32_t pad, eos;              /* pack mode: the two token ids instr_seq is completed with */
+    const int32_t *row0, *view0;   /* [N] start states */
+    const int32_t* goal;           /* [N] goal nav rows */
+    const int32_t* hop_all;        /* the shared next-hop table */
+    const int64_t* hop_off;        /* [N] */
+    const int32_t *hop_base, *hop_rows; /* [N] */
+    const int32_t* route;          /* [n_slots] or NULL */
+    int32_t *n_actions, *reached;  /* [n_slots] */
+    int32_t* rows;                 /* [S+1, n_slots] */
+    const int32_t* mb_Tp;          /* HOST [M] */
+    const int64_t* mb_off;         /* HOST [M] */
+    const int32_t* mb_Tp_dev;      /* [M] */
+    const int64_t* mb_off_dev;     /* [M] */
+    const int64_t* instr_tokens;   /* flat, or NULL */
+    const int64_t* instr_off;      /* [N+1], or NULL */
+    uint8_t* out;                  /* NULL: lengths mode */
+    int64_t out_bytes;
+} sf_nav_routes_io;
+int sf_nav_routes(const sf_nav_table* nav, const sf_nav_routes_io* io, int32_t* err, sf_stream stream);
 
 /* The follower's beam selection for one decode step (follower.py:606-690), all instances at once, no host round trip:
  * what search.DeviceFollowerBeam issues after sf_attn_decoder_fwd + sf_logprob_topk (n_valid = a_num) in its device

@@ -1523,7 +1523,6 @@ class Seq2SeqSpeaker(object):
                 and self.feedback == 'argmax' and getattr(self.env, 'host_table', 1) is None
                 and hasattr(self.env, 'graphs') and hasattr(self.env, 'data') and store.device.type == 'cuda'):
             return False
-        from . import speaker as spk
         B = self.env.batch_size
         n_batches = -(-len(self.env.data) // B)
         seen = self.__dict__.get('_test_minibatches', 0)
@@ -1539,24 +1538,63 @@ class Seq2SeqSpeaker(object):
                 if it['instr_id'] in ids:
                     looped = True
                 ids.add(it['instr_id'])
+        sweep = self._sweep_for(store, B)
+        if self.device_routes:
+            from .nav import table_for
+            from .routes import RouteSet
+            routes = RouteSet.from_items(table_for(self.env, store), [it for items in drawn for it in items])
+            batches = routes.pack(B, self.instruction_len, chunk=self.device_routes_chunk, S=self.max_episode_len)
+        else:
+            batches = [self._routes_of(items, store)[0] for items in drawn]
+        self._collect_sweep(sweep.run(batches), [[it['instr_id'] for it in items] for items in drawn], store)
+        return True
+
+    def _sweep_for(self, store, B):
+        """The agent's speaker.SpeakerSweep for minibatches of B routes over `store`, kept between calls."""
+        from . import speaker as spk
         key = (id(store), B, self.instruction_len, self.wide_sample)
         cached = self.__dict__.get('_test_sweep')
         if cached is None or cached[0] != key:
             cached = self._test_sweep = (key, spk.SpeakerSweep(self.encoder, self.decoder, store, B, self.instruction_len,
                                                                feedback='argmax', Lmax=self.instruction_len,
                                                                with_scores=True, wide_sample=self.wide_sample), store)
-        sweep = cached[1]
-        words, scores, cnt = sweep.run([self._routes_of(items, store)[0] for items in drawn])
+        return cached[1]
+
+    def _collect_sweep(self, swept, ids_of, store):
+        """The result dictionaries and losses of a finished sweep: minibatch k holds the instructions ids_of[k]."""
+        words, scores, cnt = swept
         S = self.instruction_len
-        for k, items in enumerate(drawn):
+        for k, ids in enumerate(ids_of):
             both = np.concatenate((words[k].astype(np.float32), scores[k]), axis=0)
-            outputs, loss = self._score_outputs([it['instr_id'] for it in items], both, S, None, cnt[k], store.device)
+            outputs, loss = self._score_outputs(ids, both, S, None, cnt[k], store.device)
             self.loss = loss
             self.losses.append(float(loss))
             for result in outputs:
                 if result['instr_id'] not in self.results:
                     self.results[result['instr_id']] = result
-        return True
+
+    # test()'s sweep over blocks packed ON THE DEVICE (routes.RouteSet.from_items(...).pack: two sf_nav_routes launches and
+    # one host sync for the whole split, one D2D copy per minibatch) instead of gold_routes + pack_speaker_batch + one
+    # H2D copy per minibatch.  Same staging bytes, same words.  Off by default.
+    device_routes = False
+    device_routes_chunk = None       # minibatches per device buffer (routes.PACK_CHUNK)
+
+    def augment(self, routes, batch_size=100):
+        """data_augmentation_from_speaker.py:35-82 without an environment: greedy instructions for every route of a
+        routes.RouteSet (minibatches of `batch_size` in the set's order, a short last one filled from the front), decoded
+        as ONE sweep over blocks packed on the device.  Returns what test() returns, keyed by instr_id;
+        `routes.replaced_items(results)` is the split with the generated instructions."""
+        store = self._env_store()
+        if store is None or store.device.type != 'cuda':
+            raise RuntimeError('Seq2SeqSpeaker.augment needs a feature store on the GPU (agent.store)')
+        self.feedback, self.beam_size = 'argmax', 1
+        for m in (self.encoder, self.decoder):
+            m.eval()
+        self.losses, self.results = [], {}
+        packed = routes.pack(batch_size, self.instruction_len, chunk=self.device_routes_chunk, S=self.max_episode_len)
+        ids = np.asarray(routes.instr_ids, object)[packed.route].reshape(len(packed), batch_size)
+        self._collect_sweep(self._sweep_for(store, batch_size).run(packed), [row.tolist() for row in ids], store)
+        return self.results
 
     def test(self, use_dropout=False, feedback='argmax', allow_cheat=False, beam_size=1):
         if not allow_cheat:

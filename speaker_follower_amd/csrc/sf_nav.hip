@@ -119,7 +119,194 @@ __global__ __launch_bounds__(WALKS_PER_BLOCK* WAVE) void nav_walk_kernel(
     if (lane == 0) n_steps[b] = n_out;
 }
 
+// ---- sf_nav_routes: the shortest-path routes of a split, as lengths or as the speaker's packed minibatches ----------
+
+__host__ __device__ inline int64_t align8(int64_t x) { return (x + 7) & ~(int64_t)7; }
+
+// speaker.packed_layout(B, Tp, Lmax): the byte offset of every section of a block, and the block's size
+struct RouteLayout {
+    int64_t vp, view, act, act_view, sincos, mask, bytes;    // (instr_seq stands at 0)
+};
+__host__ __device__ inline RouteLayout route_layout(int B, int Tp, int Lmax) {
+    RouteLayout l;
+    const int64_t grid = (int64_t)Tp * B * 4;
+    l.vp = align8((int64_t)B * Lmax * 8);
+    l.view = align8(l.vp + grid);
+    l.act = align8(l.view + grid);
+    l.act_view = align8(l.act + grid);
+    l.sincos = align8(l.act_view + grid);
+    l.mask = align8(l.sincos + grid * 4);
+    l.bytes = align8(l.mask + (int64_t)B * Tp);
+    return l;
+}
+
+// column `col` of a block's sections (pack mode), or all NULL
+struct RouteCols {
+    int64_t* seq;
+    int32_t *vp, *view, *act, *act_view;
+    uint32_t* sincos;                                        // (bit patterns: the table's floats are copied, not computed)
+    uint8_t* mask;
+    int B, Tp, col;
+};
+
+// lanes 0 .. 3: step t of the column; `from` = the table's four values of a move, NULL for a stop or a dead step
+__device__ __forceinline__ void route_store_step(const RouteCols& c, int lane, int t, int vp, int view, int act_view,
+                                                 const uint32_t* from) {
+    const int64_t at = (int64_t)t * c.B + c.col;
+    if (lane == 0) {
+        c.vp[at] = vp;
+        c.view[at] = view;
+        c.act[at] = from != nullptr;
+        c.act_view[at] = act_view;
+    }
+    if (lane < 4) c.sincos[at * 4 + lane] = from ? from[lane] : ((lane & 1) ? 0x3f800000u : 0u);   // (0, 1, 0, 1)
+}
+
+// One walk of route r's teacher from (row, view).  WRITE = false: nothing is stored, the walk is only measured (k
+// actions, `stopped` by an action 0, `bad` on a row outside the route's hop block).  WRITE = true (a walk already
+// measured: not bad, and in pack mode k <= Tp): rows and the column's live steps are stored as it goes.
+template <bool WRITE>
+__device__ __forceinline__ void route_walk(const sf_nav_table& nav, const sf_nav_routes_io& p, const RouteCols& c, int slot,
+                                           int lane, int base, int m, const int32_t* __restrict__ hop_row, int& row,
+                                           int& view, int& k, bool& stopped, bool& bad) {
+    const int A = nav.A, V = nav.V;
+    k = 0;
+    stopped = false;
+    while (!stopped && k < p.S) {
+        const unsigned local = (unsigned)(row - base);
+        if (local >= (unsigned)m) {
+            bad = true;
+            return;
+        }
+        const size_t s = (size_t)row * V + view;
+        int n = nav.a_num[s];
+        n = n > A ? A : n;
+        int nr = -1, cv = 0;
+        if (lane < A) {
+            nr = nav.next_row[s * A + lane];
+            cv = nav.cand_view[s * A + lane];
+        }
+        const int hop = hop_row[local];
+        int act = 0;
+        if (hop != row) {                                    // the first candidate that leads to the hop, else stop
+            const unsigned long long leads = __ballot(lane >= 1 && lane < n && nr == hop);
+            act = leads ? __ffsll(leads) - 1 : 0;
+        }
+        const int to = __shfl(nr, act, WAVE), to_view = __shfl(cv, act, WAVE);
+        if (WRITE && c.vp)
+            route_store_step(c, lane, k, nav.feat_row[row], view, act ? to_view : 0,
+                             act ? (const uint32_t*)nav.cand_sincos + (s * A + act) * 4 : nullptr);
+        if (act != 0 && to != row) {                         // (a candidate that is the current viewpoint stays)
+            view = to_view;
+            row = to;
+        }
+        ++k;
+        if (WRITE && p.rows && lane == 0) p.rows[(int64_t)k * p.n_slots + slot] = row;
+        stopped = act == 0;
+    }
+}
+
+__global__ __launch_bounds__(WALKS_PER_BLOCK* WAVE) void nav_routes_kernel(sf_nav_table nav, sf_nav_routes_io p,
+                                                                           int32_t* __restrict__ err) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int slot = blockIdx.x * WALKS_PER_BLOCK + (threadIdx.x >> 6);
+    if (slot >= p.n_slots) return;                           // (wave-uniform: no barrier in this kernel)
+    const int S = p.S;
+    RouteCols c = {};
+    if (p.out) {
+        const int i = slot / p.B;
+        c.B = p.B;
+        c.col = slot - i * p.B;
+        c.Tp = p.mb_Tp_dev[i];
+        const int64_t off = p.mb_off_dev[i];
+        if (c.Tp < 1 || c.Tp > S || off < 0 || (off & 7) || off > p.out_bytes ||
+            route_layout(p.B, c.Tp, p.Lmax).bytes > p.out_bytes - off) {
+            if (lane == 0) *err = 1;                         // not what the entry checked: the minibatch is left alone
+            return;
+        }
+        const RouteLayout l = route_layout(p.B, c.Tp, p.Lmax);
+        uint8_t* blk = p.out + off;
+        c.seq = (int64_t*)blk + (int64_t)c.col * p.Lmax;
+        c.vp = (int32_t*)(blk + l.vp);
+        c.view = (int32_t*)(blk + l.view);
+        c.act = (int32_t*)(blk + l.act);
+        c.act_view = (int32_t*)(blk + l.act_view);
+        c.sincos = (uint32_t*)(blk + l.sincos);
+        c.mask = blk + l.mask + (int64_t)c.col * c.Tp;
+    }
+    const int r = p.route ? p.route[slot] : slot;
+    const bool known = (unsigned)r < (unsigned)p.N;
+    int start_row = 0, start_view = 0, base = 0, m = 0, goal = -1;
+    const int32_t* hop_row = p.hop_all;
+    if (known) {
+        start_row = p.row0[r];
+        start_view = p.view0[r];
+        base = p.hop_base[r];
+        m = p.hop_rows[r];
+        goal = p.goal[r];
+        hop_row += p.hop_off[r];
+    }
+    const bool row_ok = known && (unsigned)(start_row - base) < (unsigned)m;
+    bool bad = !row_ok || (unsigned)start_view >= (unsigned)nav.V, stopped = false;
+    int row = start_row, view = start_view, k = 0;
+    if (!bad) route_walk<false>(nav, p, c, slot, lane, base, m, hop_row, row, view, k, stopped, bad);
+    const int n_out = bad ? 1 : k;
+    const int did_reach = !bad && stopped && row == goal;
+    const bool refused = bad || (c.vp && k > c.Tp);          // the column (and, if bad, the rows) hold one stop at the start
+    if (refused && lane == 0) *err = 1;
+    if (lane == 0 && p.rows) p.rows[slot] = start_row;
+    int n_live = 1;                                          // live steps of the column
+    if (!refused || !bad) {                                  // the walk again, this time stored
+        RouteCols cw = c;
+        if (refused) cw.vp = nullptr;                        // (too long for its block: its rows only)
+        row = start_row;
+        view = start_view;
+        route_walk<true>(nav, p, cw, slot, lane, base, m, hop_row, row, view, k, stopped, bad);
+        if (!refused) n_live = k;
+    } else {
+        row = start_row;
+        k = 0;
+    }
+    if (p.rows)
+        for (int t = k + 1 + lane; t <= S; t += WAVE) p.rows[(int64_t)t * p.n_slots + slot] = row;
+    if (lane == 0 && p.n_actions) {
+        p.n_actions[slot] = n_out;
+        p.reached[slot] = did_reach;
+    }
+    if (!c.vp) return;
+    if (refused) route_store_step(c, lane, 0, row_ok ? nav.feat_row[start_row] : -1, start_view, 0, nullptr);
+    for (int t = n_live + lane; t < c.Tp; t += WAVE) {       // dead steps: a lane per step
+        const int64_t at = (int64_t)t * c.B + c.col;
+        c.vp[at] = -1;
+        c.view[at] = 0;
+        c.act[at] = 0;
+        c.act_view[at] = 0;
+        for (int q = 0; q < 4; ++q) c.sincos[at * 4 + q] = (q & 1) ? 0x3f800000u : 0u;
+    }
+    for (int t = lane; t < c.Tp; t += WAVE) c.mask[t] = t >= n_live;
+    int64_t first = 0, len = 0;
+    if (p.instr_tokens && known) {
+        first = p.instr_off[r];
+        len = p.instr_off[r + 1] - first;
+        len = len < 0 ? 0 : len;
+    }
+    const int L = p.Lmax;
+    const int64_t kept = len < L - 1 ? len : L - 1;          // follower.py:75-105, reverse = False
+    for (int j = lane; j < L; j += WAVE) {
+        int64_t w = p.pad;
+        if (j < kept) w = p.instr_tokens[first + j];
+        else if (len + 1 <= L ? j == kept : j == L - 1) w = len + 1 <= L ? (int64_t)p.eos : p.instr_tokens[first + L - 1];
+        c.seq[j] = w;
+    }
+}
+
 }  // namespace
+
+int nav_routes(const sf_nav_table* nav, const sf_nav_routes_io* io, int32_t* err, hipStream_t st) {
+    SF_LAUNCH(nav_routes_kernel, dim3(ceil_div(io->n_slots, WALKS_PER_BLOCK)), dim3(WALKS_PER_BLOCK * WAVE), 0, st, *nav, *io,
+              err);
+    return launch_status();
+}
 
 int nav_step(const sf_nav_table* nav, int B, const int32_t* row, const int32_t* view, const int64_t* a_t,
              const uint8_t* ended, const int32_t* goal_hop, int ld_hop, const int32_t* hop_base,
@@ -154,6 +341,30 @@ extern "C" int sf_nav_walk(const sf_nav_table* nav, int policy, int B, int S, co
     if (nav->A > 64) return SF_ERR_UNSUPPORTED;              // one lane per candidate slot
     return sf::nav_walk(nav, policy, B, S, row0, view0, first_action, goal_hop, ld_hop, hop_base, row, view, actions,
                         n_steps, err, (hipStream_t)stream);
+}
+
+extern "C" int sf_nav_routes(const sf_nav_table* nav, const sf_nav_routes_io* io, int32_t* err, sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(nav && io && err && nav->a_num && nav->next_row && nav->cand_view && nav->A > 0 && nav->V > 0);
+    SF_CHECK_ARG(io->N >= 1 && io->S >= 1 && io->n_slots >= 1 && io->row0 && io->view0 && io->goal && io->hop_all &&
+                 io->hop_off && io->hop_base && io->hop_rows);
+    if (!io->out) {
+        SF_CHECK_ARG(io->n_actions && io->reached && io->rows);
+    } else {
+        SF_CHECK_ARG(nav->cand_sincos && nav->feat_row && io->B >= 1 && io->Lmax >= 1 && io->M >= 1 &&
+                     (int64_t)io->M * io->B == io->n_slots && io->out_bytes >= 1 && io->mb_Tp && io->mb_off &&
+                     io->mb_Tp_dev && io->mb_off_dev);
+        SF_CHECK_ARG(!io->n_actions == !io->reached && !io->n_actions == !io->rows);
+        SF_CHECK_ARG(!io->instr_tokens == !io->instr_off);
+        for (int i = 0; i < io->M; ++i) {
+            const int Tp = io->mb_Tp[i];
+            const int64_t off = io->mb_off[i];
+            SF_CHECK_ARG(Tp >= 1 && Tp <= io->S && off >= 0 && !(off & 7) && off <= io->out_bytes &&
+                         sf::route_layout(io->B, Tp, io->Lmax).bytes <= io->out_bytes - off);
+        }
+    }
+    if (nav->A > 64) return SF_ERR_UNSUPPORTED;              // one lane per candidate slot
+    return sf::nav_routes(nav, io, err, (hipStream_t)stream);
 }
 
 extern "C" int sf_nav_step(const sf_nav_table* nav, int B, const int32_t* row, const int32_t* view,

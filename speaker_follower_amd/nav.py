@@ -15,7 +15,9 @@ function of the state (scan, viewpoint, view index):
                          the next decode step's index-form observation;
   * `sf_nav_walk`     -- whole episodes of a policy that is a table look-up (stop, the shortest-path
                          teacher, the random baseline: follower.py:197-259) as ONE launch, through
-                         `NavTable.walk`; it leaves a rollout's row / view / action arrays.
+                         `NavTable.walk`; it leaves a rollout's row / view / action arrays;
+  * `sf_nav_routes`   -- the teacher's routes of a whole split over ONE shared next-hop table
+                         (`NavTable.all_hops`), as lengths or as the speaker's packed minibatches (routes.py).
 
 `FollowerEngine.rollout(DeviceNavBatch, ...)` then runs encoder + S decode steps with ONE host sync at
 the end; `trajectories()` turns the recorded states into the reference's result format.
@@ -226,6 +228,31 @@ class NavTable:
                     out[i] = self.row_of[(scan, hop)]
             self._hops[key] = out
         return self._hops[key]
+
+    def all_hops(self):
+        """The next-hop table of EVERY goal as one flat int32 array, block by block in `self.scans` order (what
+        sf_nav_routes reads as hop_all): with m the rows of scan s and off = self.hop_off[s], element off + g * m + r is
+        the nav row of the next hop from local row r towards local goal g -- row g of the block is `hops(s, goal g)`,
+        which builds it, so the teacher's tie rule stays the environment's (NOT derived from a distance table: a table
+        that accumulates outward from the source need not satisfy w(u, x) + D[x][t] == D[u][t] to the last bit).  As many
+        elements as evaluation.DistanceTable's table.  Built once; `all_hops_device()` is its device copy."""
+        if getattr(self, '_all_hops', None) is None:
+            self.hop_off, total = {}, 0
+            for s in self.scans:
+                self.hop_off[s] = total
+                total += self.scan_rows[s] ** 2
+            out = np.empty(total, np.int32)
+            for s in self.scans:
+                b, m, o = self.base[s], self.scan_rows[s], self.hop_off[s]
+                for g in range(m):
+                    out[o + g * m:o + (g + 1) * m] = self.hops(s, self.vp_of[b + g][1])
+            self._all_hops = out
+        return self._all_hops
+
+    def all_hops_device(self):
+        if getattr(self, '_all_hops_dev', None) is None:
+            self._all_hops_dev = torch.from_numpy(self.all_hops()).to(self.device)
+        return self._all_hops_dev
 
 
 class DeviceNavBatch:

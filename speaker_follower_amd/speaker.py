@@ -589,6 +589,25 @@ def batch_from_packed(buf, B, Tp, Lmax=80, row0=0):
                               act_sincos=view('act_sincos', torch.float32, (Tp, B, 4)), row0=row0)
 
 
+class PackedBlocks:
+    """Minibatches that are already packed ON THE DEVICE (routes.RouteSet.pack: sf_nav_routes wrote them): `blocks` =
+    per minibatch (uint8 device buffer, byte offset of its block, Tp), each block in packed_layout(B, Tp, Lmax) order.
+    SpeakerSweep.issue takes one in place of host batches; `err` is the pack launches' error word, `keep` whatever must
+    outlive the launches that read it."""
+
+    def __init__(self, blocks, B, Lmax, err=None, keep=None, n_actions=None, route=None):
+        self.blocks, self.B, self.Lmax, self.err, self.keep = blocks, B, Lmax, err, keep
+        self.n_actions, self.route = n_actions, route        # host: actions per route, route index of every column
+
+    def __len__(self):
+        return len(self.blocks)
+
+    def block(self, i):
+        """Minibatch i as a uint8 device tensor (a view)."""
+        buf, off, Tp = self.blocks[i]
+        return buf[off:off + packed_layout(self.B, Tp, self.Lmax)['bytes']]
+
+
 class SpeakerSweep:
     """Greedy (or sampled) decoding of MANY path minibatches at full device rate.
 
@@ -651,7 +670,9 @@ class SpeakerSweep:
         return self.graphs[key]
 
     def run(self, batches, _persistent=True):
-        """`batches`: sequence of synth.SpeakerBatch-like index batches of `batch_size` paths.  Returns an int16 array
+        """`batches`: sequence of synth.SpeakerBatch-like index batches of `batch_size` paths -- or a PackedBlocks: the
+        minibatches already packed on the device, which cost one D2D copy each instead of the host pack, the pinned
+        slot and the H2D copy (they stay alive in the handle until `finish` returns).  Returns an int16 array
         [n, S, B] of generated word ids (pinned host memory); with_scores: (words, scores [n,S,B] f32, sum_cnt [n,S,2])."""
         return self.finish(self.issue(batches, _persistent))
 
@@ -684,10 +705,25 @@ class SpeakerSweep:
             s_.wait_stream(torch.cuda.current_stream(dev))
         # a path-step count met for the first time is captured for EVERY stream at once (a capture is tens of
         # milliseconds: better in front of the sweep than in the middle of it)
-        for Tp in sorted({int(sb.path_len.max()) for sb in batches}):
+        def decode(i, replay, st, words16):
+            """Minibatch i behind its staging copy, on the current (sweep) stream."""
+            replay()
+            if after is not None:
+                after(i, st)
+            words16.copy_(st.words[1:])                          # int64 -> int16 on the device (ids < 2^15)
+            out[i].copy_(words16, non_blocking=True)
+            if self.with_scores:
+                sc[i].copy_(st.step_scores, non_blocking=True)
+                cnt[i].copy_(st.sum_cnt, non_blocking=True)
+
+        packed = isinstance(batches, PackedBlocks)
+        if packed and (batches.B, batches.Lmax) != (self.B, self.Lmax):
+            raise ValueError('SpeakerSweep was built for minibatches of %d paths and %d words, got blocks of %d and %d'
+                             % (self.B, self.Lmax, batches.B, batches.Lmax))
+        for Tp in sorted({b[2] for b in batches.blocks} if packed else {int(sb.path_len.max()) for sb in batches}):
             for si in range(len(self.streams)):
                 self._graph(si, Tp, _persistent)
-        for i, sb in enumerate(batches):
+        for i, sb in enumerate(() if packed else batches):
             si, slot = i % len(self.streams), (i // len(self.streams)) % self.slots
             pin = self.pinned[si][slot]
             if self.free_ev[si][slot] is not None:
@@ -706,14 +742,13 @@ class SpeakerSweep:
                 ev = torch.cuda.Event()
                 ev.record()
                 self.free_ev[si][slot] = ev
-                replay()
-                if after is not None:
-                    after(i, st)
-                words16.copy_(st.words[1:])                      # int64 -> int16 on the device (ids < 2^15)
-                out[i].copy_(words16, non_blocking=True)
-                if self.with_scores:
-                    sc[i].copy_(st.step_scores, non_blocking=True)
-                    cnt[i].copy_(st.sum_cnt, non_blocking=True)
+                decode(i, replay, st, words16)
+        for i in range(n if packed else 0):                      # blocks packed on the device: ONE D2D copy, the same replay
+            si = i % len(self.streams)
+            replay, st, buf, words16 = self._graph(si, batches.blocks[i][2], _persistent)
+            with torch.cuda.stream(self.streams[si]):
+                buf.copy_(batches.block(i), non_blocking=True)
+                decode(i, replay, st, words16)
         return dict(batches=batches, out=out, scores=sc, cnt=cnt, persistent=_persistent)
 
     def finish(self, handle, check_faults=True):
@@ -722,6 +757,9 @@ class SpeakerSweep:
         dev = self.store.device
         for s in self.streams:
             s.synchronize()
+        src = handle['batches']
+        if isinstance(src, PackedBlocks) and src.err is not None and int(src.err.item()):
+            raise RuntimeError('sf_nav_routes refused a route while packing: the blocks are not the split')
         bits = take_fault(dev) if check_faults else 0
         if bits:
             if not handle['persistent']:
