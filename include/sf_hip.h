@@ -1121,6 +1121,58 @@ int sf_gate_rows_registered(const void* table, sf_gate_rows* out);
 void sf_gate_rows_use(int on);
 int sf_gate_rows_is_used(void);
 long long sf_gate_rows_steps(void);
+/* GATE-SPACE ROWS for the ATTENDED half of the LSTM input (additive to ABI 10; rides on the rows above and follows their
+ * build, use and refresh rules).
+ *
+ * The other half of the input is the attended feature f = sum_v alpha_v [table[vp, v] | loc[view, v]].  In the projected
+ * chain f feeds nothing but the gate product, and the product is linear in f, so its image part is turned round too:
+ *     gf [n_rows, 4H]   row n = x_n W_ih[:, F:F+IMG]^T                                  (F = IMG + LOC)
+ *     f_img W_ih[:, F:F+IMG]^T = sum_v alpha_v gf[vp V + v]
+ * Launch (1)'s attention partials then load gate-space rows where they loaded image rows (4H floats per view: the bytes
+ * of an image row at 4H = IMG), their record is (sum of 4H | sum of LOC | scores | m, l), and launch (2)'s merge leaves
+ * the normalised 4H part as a [B, 4H] row beside the action half's and the LOC part where it always went
+ * (xin[:, F+IMG:2F]).  The location columns W_ih[:, F+IMG:2F] are NOT tabulated: the step behind runs its product over
+ * [f_loc | h0], K = LOC + H, and its cell adds both rows.  The image columns xin[:, F:F+IMG] of such a step are not
+ * written (nothing reads them: the chain is inference only).  Step 0 keeps the full product.
+ *
+ * MEMORY AND COST: gf is ANOTHER n_rows * 4H * 4 bytes -- 3.1 GB for the full R2R table at H = 512, beside gu's 3.1 GB --
+ * and about 22 ms of build on an MI355X (n_rows * IMG * 4H * 2 flop = 3.2 Tflop).
+ *
+ *   sf_gate_rows_attended_build(w_ih, table, n_rows, IMG, LOC, H, gf, ws, ws_bytes, stream)
+ *                                 fills gf as sf_gate_rows_build fills gu: 16 384 table rows per product
+ *                                 (sf_debug_projected_chunk_rows applies), 64-bit row offsets, SF_ERR_UNSUPPORTED for a
+ *                                 binary16 table.  Never call it inside a stream capture.
+ *   sf_gate_rows_attended_register(table, g) / _registered(table, out)
+ *                                 by the feature table's address, like sf_gate_rows_register (g == NULL forgets).
+ *   sf_gate_rows_attended_use(on) / _is_used()   process-wide switch (default on).
+ *   sf_gate_rows_attended_steps()         decode steps whose cell added an attended row since the library was loaded
+ *                                 (each of them also counts in sf_gate_rows_steps, which keeps its meaning).
+ *   sf_gate_rows_attended_supported(H, LOC)  1 when launch (1)'s partials take rows of 4H + LOC floats.
+ * Taken only where the rows above are taken, and further only with the partials in launch (1)
+ * (sf_debug_projected_partials_late off), a row of 4H + LOC floats that their body takes (H <= 512 at LOC = 128), an
+ * entry whose key_w / V / IMG / LOC / H match, LOC + H <= 1024, and a workspace that holds two more [B, 4H] rows.
+ * Otherwise every step launches what it launched without this table.
+ *
+ * sf_lstm_cell_rows_fwd is the cell of such a step alone, on caller buffers (tests, tools/gate_rows_attended_ab.py): the product
+ * runs over x[:, x_col0:I] and h0, xg (required) and xg2 (optional) are added ahead of the cell.  path 0: what a step
+ * takes; 1: the K-split product and the cell kernel (one addend: SF_ERR_UNSUPPORTED with xg2); 2: the fused step kernel
+ * (its 32-row x 8-unit form at every B: the 16 x 16 form needs more registers than there are at K = LOC + H = 640). */
+typedef struct sf_gate_rows_attended {
+    const float* gf;
+    const float* key_w;          /* sf_lstm_w.w_ih of the decoder the table belongs to */
+    int32_t H, V, IMG, LOC;
+} sf_gate_rows_attended;
+int sf_gate_rows_attended_build(const float* w_ih, const float* table, long long n_rows, int IMG, int LOC, int H, float* gf,
+                                void* ws, size_t ws_bytes, sf_stream stream);
+int sf_gate_rows_attended_register(const void* table, const sf_gate_rows_attended* g);
+int sf_gate_rows_attended_registered(const void* table, sf_gate_rows_attended* out);
+void sf_gate_rows_attended_use(int on);
+int sf_gate_rows_attended_is_used(void);
+long long sf_gate_rows_attended_steps(void);
+int sf_gate_rows_attended_supported(int H, int LOC);
+int sf_lstm_cell_rows_fwd(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx, int x_col0, const float* xg,
+                          const float* xg2, const float* h0, const float* c0, float* h1, float* c1, float* gates, int path,
+                          void* ws, size_t ws_bytes, sf_stream stream);
 /* A/B switch of the projected chain: 0 (the default: measured faster, 1.429 against 1.474 ms per headline rollout)
  * puts the attention partials of step t + 1 into launch (1), beside the text stage, and leaves launch (2) their merge;
  * on != 0 puts them into launch (2) (partials, ticket and merge beside the scoring; launch (1) is the text stage and y

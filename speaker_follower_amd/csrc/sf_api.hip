@@ -58,8 +58,9 @@ int g_slab_consumers = 1;     // sf_debug_slab_consumers: consumers add up K-spl
 // ---- a2 LSTMCell --------------------------------------------------------------------------------
 int lstm_fwd_i(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx, const float* h0,
                const float* c0, float* h1, float* c1, float* gates, float* h1_drop, int ld_h1_drop,
-               const Dropout& drop, Arena ar, hipStream_t st, const float* xg, int x_col0) {
+               const Dropout& drop, Arena ar, hipStream_t st, const float* xg, int x_col0, const float* xg2, int path) {
     LstmPwFwd p{};
+    if (!xg) xg2 = nullptr;
     p.xg = xg; p.b_ih = w->b_ih; p.b_hh = w->b_hh;
     p.c0 = c0; p.h0 = h0; p.B = B; p.H = H; p.gates = gates; p.h1 = h1; p.c1 = c1;
     p.h1_drop = h1_drop; p.ld_h1_drop = ld_h1_drop; p.drop = drop; p.lengths = nullptr;
@@ -71,6 +72,15 @@ int lstm_fwd_i(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx,
         return lstm_step_fused(f, st);
     }
     if (!xg) x_col0 = 0;
+    // both halves of the input as gate-space rows: what is left, [x[:, x_col0:] | h0], is a short reduction again
+    if (xg && (path == 2 || (path == 0 && xg2 && short_gate_fused(I - x_col0, H)))) {
+        LstmStepArgs f{};
+        f.h0 = h0; f.w_hh = w->w_hh; f.x = x + x_col0; f.ldx = ldx; f.w_ih = w->w_ih + x_col0; f.ld_w_ih = I;
+        f.I = I - x_col0; f.xg = xg; f.xg2 = xg2; f.wide = true;
+        f.b_ih = w->b_ih; f.b_hh = w->b_hh; f.B = B; f.H = H; f.pw = p;
+        return lstm_step_fused(f, st);
+    }
+    if (xg2) return SF_ERR_UNSUPPORTED;      // (the cell kernel behind the product has one addend; nothing was launched)
     Seg segs[2] = {{x + x_col0, ldx, w->w_ih + x_col0, I, I - x_col0}, {h0, H, w->w_hh, H, H}};
     LinearOut o{};
     float* slabs = nullptr;
@@ -435,6 +445,16 @@ int sf_lstm_cell_fwd(const sf_lstm_w* w, int B, int I, int H, const float* x, in
     SF_CHECK_ARG(w && x && h0 && c0 && h1 && c1 && B > 0 && I > 0 && H > 0 && H % 4 == 0);
     return lstm_fwd_i(w, B, I, H, x, ldx, h0, c0, h1, c1, gates, h1_drop, ld_h1_drop,
                       make_dropout(drop, drop_stream), arena(ws, ws_bytes), S(stream));
+}
+
+int sf_lstm_cell_rows_fwd(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx, int x_col0, const float* xg,
+                          const float* xg2, const float* h0, const float* c0, float* h1, float* c1, float* gates, int path,
+                          void* ws, size_t ws_bytes, sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(w && x && xg && h0 && c0 && h1 && c1 && B > 0 && H > 0 && H % 4 == 0 && x_col0 > 0 && x_col0 < I &&
+                 x_col0 % 4 == 0 && I % 4 == 0 && ldx % 4 == 0 && path >= 0 && path <= 2);
+    return lstm_fwd_i(w, B, I, H, x, ldx, h0, c0, h1, c1, gates, nullptr, 0, Dropout{}, arena(ws, ws_bytes), S(stream), xg,
+                      x_col0, xg2, path);
 }
 
 int sf_lstm_cell_bwd(const sf_lstm_w* w, const sf_lstm_g* g, int B, int I, int H, const float* x,

@@ -42,10 +42,15 @@ struct TextFold {
 // Gate-space rows through one step (sf_follower_episode_fwd): `xg_in` is the row the step before left for this step's cell
 // (null: the full gate product), `rows.xg_next` where launch (2) of the projected chain leaves the next one; `wrote` says
 // whether it did -- any other chain writes the raw u_next alone, and the next step runs the full product.
+// The attended half (sf_gate_rows_attended_build) rides on that: `xg_f_in` is the [B, 4H] row launch (2) of the step before
+// merged from gate-space partials (null: the raw attended feature is in xin, as without the table; never set without
+// `xg_in`), `rows.gf` / `rows.xg_f` the table and where this step's launch (2) leaves the next one, `wrote_f` whether it did.
 struct GateStep {
     const float* xg_in;
     GateRows rows;
     bool wrote;
+    const float* xg_f_in = nullptr;
+    bool wrote_f = false;
 };
 
 // ---- tail(t): what every launch chain of the step reads (decoder_tail_i builds it behind the cell, tail_dispatch picks
@@ -113,7 +118,9 @@ FoldScratch fold_scratch(const TailStep& s, Arena& af) {
     f.ybuf = af.take((size_t)s.B * f.ldp);
     f.zbuf = af.take((size_t)s.B * f.ldp);
     f.tcount = af.tickets() ? af.tickets() + TEXT_TICKET : nullptr;
-    f.part = (s.paired && s.B <= 1024) ? af.take(visual_attn_split_floats(s.B, s.F)) : nullptr;
+    // (with gate-space rows for the attended half a record holds 4H + LOC floats: sized for the larger of the two widths)
+    const int width = s.gate && s.gate->rows.gf && s.paired ? std::max(s.F, 4 * s.H + s.xn.LOC) : s.F;
+    f.part = (s.paired && s.B <= 1024) ? af.take(visual_attn_split_floats(s.B, width)) : nullptr;
     f.ok = f.tpart && f.ybuf && f.zbuf && (f.part || !s.paired) && f.tcount && s.B <= VIS_SPLIT_MAX_B;
     return f;
 }
@@ -173,15 +180,22 @@ int tail_proj(const TailStep& s, const TextFold& tf) {
     if (!ok) return SF_ERR_UNSUPPORTED;
     // ---- issue (the first launch checks its shapes before it launches: it may still decline)
     const bool late = s.paired && (g_proj_partials_late || !proj_partials_supported(s.xn.IMG, s.xn.LOC));
-    TRY(pair_proj_textfold(tf.ctx_q, tf.ctx_o, s.ctx_mask, B, s.L, H, tp->cat2 + H, 2 * H, f.tpart, f.tcount, f.zbuf, f.ldp,
-                           tp->alpha, py, s.us, s.paired && !late ? &s.xn : nullptr, pt, tp->h1, H, f.part, s.st));
-    g_proj_steps.fetch_add(1, std::memory_order_relaxed);
     const bool gate = s.gate && s.gate->rows.xg_next && s.paired;       // (a next step exists and reads the row)
+    // the attended half in gate space: only beside the action half's row, with the partials in launch (1), and where their
+    // body takes rows of 4H + LOC floats (episode_gate_rows has checked the table and the shape of what is left)
+    const bool att = gate && !late && s.gate->rows.gf && s.gate->rows.xg_f && !s.dn_in.on() &&
+                     proj_partials_supported(4 * H, s.xn.LOC);
+    GateRows rows = gate ? s.gate->rows : GateRows{};
+    if (!att) rows.gf = nullptr, rows.xg_f = nullptr;
+    TRY(pair_proj_textfold(tf.ctx_q, tf.ctx_o, s.ctx_mask, B, s.L, H, tp->cat2 + H, 2 * H, f.tpart, f.tcount, f.zbuf, f.ldp,
+                           tp->alpha, py, s.us, s.paired && !late ? &s.xn : nullptr, pt, tp->h1, H, f.part, s.st, rows.gf));
+    g_proj_steps.fetch_add(1, std::memory_order_relaxed);
     TRY(issued(pair_proj_score(s.us, B, H, s.L, pt, f.zbuf, f.ldp, f.ybuf, f.ldp, make_glue(s.us, B, tp->logit, s.glue),
                                s.paired ? &s.xn : nullptr, late ? 0 : 2, tp->h1, H, s.paired ? tn->alpha_v : nullptr,
                                s.paired ? tn->xin + F : nullptr, 2 * F, s.dn_in, F, f.part, af.tickets(), s.st,
-                               gate ? &s.gate->rows : nullptr)));
+                               gate ? &rows : nullptr)));
     if (gate) s.gate->wrote = true;
+    if (att) s.gate->wrote_f = true;
     return SF_OK;
 }
 
@@ -365,9 +379,12 @@ int decoder_tail_i(const sf_decoder_w* w, const sf_cands* U, int B, int H, int D
     if (u_prev) TRY(dropout_copy(u_prev, s.F, B, s.F, tp->xin, 2 * s.F, d_in, 0, s.st));
     // (with a gate-space row of the action half: the product over [f | h0] alone, K = F + H, the row added by the cell)
     const float* xg = gate && !u_prev ? gate->xg_in : nullptr;
+    // (with a row of the attended half's image part too: the product over [f_loc | h0], K = LOC + H, both rows added)
+    const float* xg_f = xg ? gate->xg_f_in : nullptr;
     TRY(lstm_fwd_i(&w->lstm, B, 2 * s.F, H, tp->xin, 2 * s.F, h0, c0, tp->h1, tp->c1, tp->gates,
-                   tp->cat2 + H, 2 * H, s.d_h, s.ar, s.st, xg, s.F));
+                   tp->cat2 + H, 2 * H, s.d_h, s.ar, s.st, xg, xg_f ? s.F + s.us.IMG : s.F, xg_f));
     if (xg) g_gate_steps.fetch_add(1, std::memory_order_relaxed);
+    if (xg_f) g_gate_att_steps.fetch_add(1, std::memory_order_relaxed);
     return tail_dispatch(s, tf);
 }
 
@@ -632,9 +649,13 @@ int episode_head(const EpisodeFwd& ep, Arena ha) {
 // ticket region at its end keeps its address), step t + 1 runs its gate product over [f | h0] and its cell adds the row.
 // Decided once, here, before the first launch; a step whose chain declines leaves `wrote` false and the step behind
 // it runs the full product on the raw row, which every chain still writes.
+// The attended half's table (sf_gate_rows_attended_build) adds two more rows `xg_f` beside them, under the same capacity
+// rule, where the partials sit in launch (1) and take rows of 4H + LOC floats.
 struct GateCarve {
     float* xg_buf[2] = {nullptr, nullptr};      // null: the full gate product in every step
     sf_gate_rows gr{};
+    float* xgf_buf[2] = {nullptr, nullptr};     // null: the attended feature stays a raw row
+    const float* gf = nullptr;
 };
 GateCarve episode_gate_rows(const EpisodeFwd& ep, Arena& ar) {
     const sf_follower_episode* e = ep.e;
@@ -660,6 +681,17 @@ GateCarve episode_gate_rows(const EpisodeFwd& ep, Arena& ar) {
         c.xg_buf[1] = c.xg_buf[0] + row;
         ar.base = c.xg_buf[1] + row;
         ar.cap -= 2 * row;
+        sf_gate_rows_attended ga{};
+        if (gate_rows_attended_lookup(us0.table, &ga) && ga.key_w == gr.key_w && ga.H == gr.H && ga.V == gr.V &&
+            ga.IMG == gr.IMG && ga.LOC == gr.LOC && !g_proj_partials_late && x0.IMG == us0.IMG && x0.LOC == us0.LOC &&
+            proj_partials_supported(x0.IMG, x0.LOC) && proj_partials_supported(4 * e->H, x0.LOC) &&
+            short_gate_fused(x0.LOC, e->H) && 4 * row <= whole.cap / 8) {
+            c.gf = ga.gf;
+            c.xgf_buf[0] = ar.base;
+            c.xgf_buf[1] = c.xgf_buf[0] + row;
+            ar.base = c.xgf_buf[1] + row;
+            ar.cap -= 2 * row;
+        }
     }
     return c;
 }
@@ -679,18 +711,20 @@ int episode_steps(const EpisodeFwd& ep, const GateCarve& c, Arena ar) {
     float* const* xg_buf = c.xg_buf;
     const hipStream_t st = S(ep.stream);
     StepView cur = ep.cur;
-    const float* xg_in = nullptr;
+    const float *xg_in = nullptr, *xg_f_in = nullptr;
     for (int t = 0; t < e->S; ++t) {
         const bool more = t + 1 < e->S;
         StepView nxt = more ? step_view(e, t + 1) : cur;
         const sf_nav_io nv = nav0 ? nav_view(nav0, e, t) : sf_nav_io{};
         if (nav0) cur.glue.nav = &nv;
         const StepState in = state_in(e, t);
-        GateStep gs{xg_in, GateRows{gr.gu, gr.gl, more ? xg_buf[t & 1] : nullptr}, false};
+        GateStep gs{xg_in, GateRows{gr.gu, gr.gl, more ? xg_buf[t & 1] : nullptr, c.gf, more ? c.xgf_buf[t & 1] : nullptr},
+                    false, xg_f_in};
         TRY(decoder_tail_i(w, &cur.U, e->B, e->H, e->D, e->L, nullptr, in.h, in.c, e->ctx, e->ctx_mask,
                            nullptr, &cur.tp, &cur.glue, drop, e->step0 + t, more && !nav0 ? &nxt.X : nullptr,
                            more ? &nxt.tp : nullptr, ar, st, tf, xg_buf[0] ? &gs : nullptr));
         xg_in = gs.wrote ? gs.rows.xg_next : nullptr;
+        xg_f_in = gs.wrote && gs.wrote_f ? gs.rows.xg_f : nullptr;
         if (nav0 && more) TRY(attend_i(&nxt.X, e->B, &nxt.tp, drop, e->step0 + t + 1, ar, st));
         cur = nxt;
     }

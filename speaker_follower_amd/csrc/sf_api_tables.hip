@@ -7,6 +7,7 @@ namespace sf {
 
 std::atomic<long long> g_proj_steps{0};
 std::atomic<long long> g_gate_steps{0};
+std::atomic<long long> g_gate_att_steps{0};
 
 namespace {
 
@@ -27,6 +28,8 @@ std::atomic<int> g_proj_use{1};             // sf_projected_use
 // ---- gate-space rows (include/sf_hip.h: sf_gate_rows_register); an entry names the decoder by its W_ih ---------------------
 Registry<const void*, sf_gate_rows> g_gate;
 std::atomic<int> g_gate_use{1};             // sf_gate_rows_use
+Registry<const void*, sf_gate_rows_attended> g_gate_att;    // sf_gate_rows_attended_register
+std::atomic<int> g_gate_att_use{1};         // sf_gate_rows_attended_use
 // ---- bf16 weight storage of the gate product (include/sf_hip.h: sf_gate_product_bf16_weights) ---------------------------
 Registry<WeightPair, PackedPair> g_bf16_pairs;
 std::atomic<int> g_bf16w_on{0};
@@ -43,6 +46,9 @@ bool projected_lookup(const void* table, sf_projected* out) {
 }
 bool gate_rows_lookup(const void* table, sf_gate_rows* out) {
     return table && g_gate_use.load(std::memory_order_relaxed) && g_gate.find(table, out);
+}
+bool gate_rows_attended_lookup(const void* table, sf_gate_rows_attended* out) {
+    return table && g_gate_att_use.load(std::memory_order_relaxed) && g_gate_att.find(table, out);
 }
 bool bf16_packed(const float* w_ih, const float* w_hh, const void* (&packed)[2]) {
     if (!g_bf16w_on.load(std::memory_order_relaxed) || sf::g_nt_force_f32) return false;
@@ -183,5 +189,39 @@ int sf_gate_rows_registered(const void* table, sf_gate_rows* out) { return table
 void sf_gate_rows_use(int on) { g_gate_use.store(on ? 1 : 0, std::memory_order_relaxed); }
 int sf_gate_rows_is_used(void) { return g_gate_use.load(std::memory_order_relaxed); }
 long long sf_gate_rows_steps(void) { return g_gate_steps.load(std::memory_order_relaxed); }
+
+int sf_gate_rows_attended_build(const float* w_ih, const float* table, long long n_rows, int IMG, int LOC, int H, float* gf,
+                                void* ws, size_t ws_bytes, sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(w_ih && table && gf && n_rows > 0 && IMG > 0 && IMG % 4 == 0 && LOC > 0 && LOC % 16 == 0 && H > 0 &&
+                 H % 4 == 0);
+    if (table_is_f16(table)) return SF_ERR_UNSUPPORTED;
+    const int F = IMG + LOC, G = 4 * H;
+    Arena ar = arena(ws, ws_bytes);
+    hipStream_t st = S(stream);
+    // as gu, against the image columns of the ATTENDED half, W_ih[:, F:F+IMG]
+    for (long long r0 = 0; r0 < n_rows; r0 += g_proj_chunk_rows) {
+        const int m = (int)std::min<long long>(g_proj_chunk_rows, n_rows - r0);
+        TRY(linear_plain(table + (size_t)r0 * IMG, IMG, w_ih + F, 2 * F, nullptr, m, G, IMG, EPI_NONE, gf + (size_t)r0 * G, G, ar,
+                         st));
+    }
+    return SF_OK;
+}
+int sf_gate_rows_attended_register(const void* table, const sf_gate_rows_attended* g) {
+    SF_CHECK_ARG(table);
+    if (!g) return g_gate_att.forget(table);
+    SF_CHECK_ARG(g->gf && g->key_w && g->H > 0 && g->H % 4 == 0 && g->V > 0 && g->IMG > 0 && g->LOC > 0);
+    return g_gate_att.put(table, *g);
+}
+int sf_gate_rows_attended_registered(const void* table, sf_gate_rows_attended* out) {
+    return table && g_gate_att.find(table, out) ? 1 : 0;
+}
+void sf_gate_rows_attended_use(int on) { g_gate_att_use.store(on ? 1 : 0, std::memory_order_relaxed); }
+int sf_gate_rows_attended_is_used(void) { return g_gate_att_use.load(std::memory_order_relaxed); }
+long long sf_gate_rows_attended_steps(void) { return g_gate_att_steps.load(std::memory_order_relaxed); }
+int sf_gate_rows_attended_supported(int H, int LOC) {
+    return H > 0 && LOC > 0 && H % 4 == 0 && LOC % 4 == 0 && proj_partials_supported(4 * H, LOC) &&
+           short_gate_fused(LOC, H) ? 1 : 0;
+}
 
 }  // extern "C"

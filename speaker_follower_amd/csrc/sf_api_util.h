@@ -99,11 +99,13 @@ public:
 int table_is_f16(const void* table);                               // sf_feature_table_f16
 bool projected_lookup(const void* table, sf_projected* out);       // sf_projected_register, where sf_projected_use is on
 bool gate_rows_lookup(const void* table, sf_gate_rows* out);       // sf_gate_rows_register, where sf_gate_rows_use is on
+bool gate_rows_attended_lookup(const void* table, sf_gate_rows_attended* out);   // ... _attended_register / _attended_use
 // the packed images of (w_ih, w_hh) when the switch is on and the pair is registered; false: today's kernels
 bool bf16_packed(const float* w_ih, const float* w_hh, const void* (&packed)[2]);
 inline int projected_ld(int H) { return (H + 1 + 3) & ~3; }
 extern std::atomic<long long> g_proj_steps;     // sf_projected_steps: decode steps issued on the projected chain
 extern std::atomic<long long> g_gate_steps;     // sf_gate_rows_steps: decode steps whose gate product ran on a gate-space row
+extern std::atomic<long long> g_gate_att_steps; // sf_gate_rows_attended_steps: ... whose cell added an attended row too
 extern int g_proj_partials_late;                // sf_debug_projected_partials_late (sf_api.hip)
 
 // the ONLY places that turn the C structs into the kernels' sources: a dense source is never half
@@ -185,8 +187,15 @@ inline int context_fold(const float* ctx, const float* w_in_t, const float* w_ou
 int lstm_fwd_i(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx, const float* h0,
                const float* c0, float* h1, float* c1, float* gates, float* h1_drop, int ld_h1_drop,
                const Dropout& drop, Arena ar, hipStream_t st,
-               const float* xg = nullptr, int x_col0 = 0);     // xg [B, 4H]: x[:, :x_col0] W_ih[:, :x_col0]^T, formed elsewhere
+               const float* xg = nullptr, int x_col0 = 0,      // xg [B, 4H]: x[:, :x_col0] W_ih[:, :x_col0]^T, formed elsewhere
                                                                // (the product then starts at column x_col0 of x and W_ih)
+               const float* xg2 = nullptr,     // with xg: a second [B, 4H] row formed elsewhere, of further columns below x_col0
+                                               // (the fused step only: SF_ERR_UNSUPPORTED where the product + cell kernel run)
+               int path = 0);                  // with xg: 0 short_gate_fused decides; 1 the product + cell kernel; 2 the fused step
+// Whether a step with a gate-space row runs what is left of its product, K = I - x_col0 + H, inside the fused step kernel
+// (lstm_step_fused: one launch, the rows added ahead of the cell) instead of as a K-split product plus the cell kernel.
+// A pure function of the shape; the rule of the step WITHOUT a row (lstm_fwd_i: I + H <= 1024) applied to what remains.
+inline bool short_gate_fused(int K_x, int H) { return K_x > 0 && K_x + H <= 1024 && H % 16 == 0 && K_x % 4 == 0; }
 int lstm_bwd_i(const sf_lstm_w* w, const sf_lstm_g* g, int B, int I, int H, const float* x, int ldx,
                const float* h0, const float* c0, const float* c1, const float* gates,
                const float* dh1, const float* dh1_b, const float* dc1, float* dx, int lddx,

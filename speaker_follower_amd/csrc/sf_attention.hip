@@ -34,6 +34,10 @@ struct VisArgs {
     const float* pv;       // [n_vp * V, ldp]: row n = [x_n^T M_v[:IMG, :] | x_n . c_v[:IMG]]
     const float* lv;       // [V * V, ldp]: the same of the location-embedding table's rows
     int ldp, pH;           // row stride of both (floats, a multiple of 4); H (the constant sits at column H)
+    // proj_merge_body only: the first src.IMG floats of the merged sum go to out_img [B, ld_img] and `out` takes the
+    // location part alone, from its column 0 (null: the whole sum to `out`)
+    float* out_img;
+    int ld_img;
 };
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
@@ -641,7 +645,13 @@ __device__ __forceinline__ void proj_merge_body(const VisArgs& a, const VisSplit
             t.z = dropout_keep(rkey, col + 2, dr.thresh) ? t.z * dr.scale : 0.f;
             t.w = dropout_keep(rkey, col + 3, dr.thresh) ? t.w * dr.scale : 0.f;
         }
-        reinterpret_cast<float4*>(orow)[c] = t;
+        // (gate-space rows, block-uniform: the 4H part is the next cell's addend, the location part stays an input)
+        float4* dst = reinterpret_cast<float4*>(orow) + c;
+        if (a.out_img) {
+            const int i4 = a.src.IMG >> 2;
+            dst = c < i4 ? reinterpret_cast<float4*>(a.out_img + (size_t)b * a.ld_img) + c : reinterpret_cast<float4*>(orow) + (c - i4);
+        }
+        *dst = t;
     }
 }
 
@@ -1709,12 +1719,17 @@ void proj_text_slots_warm() { (void)proj_text_slots(0); }
 int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* mask, int B, int L, int H, const float* vec,
                        int ldvec, float* part, unsigned* counter, float* z, int ldz, float* alpha, const SmallPlan& y,
                        const CandSrc& us, const PanoSrc* xn, const ProjTables& pt, const float* h1, int ldh1, float* split_part,
-                       hipStream_t st) {
+                       hipStream_t st, const float* gf) {
     if (!pair_proj_textfold_accepts(y.inst()) || !proj_chain_supported(us, xn, B, H, L, pt)) return SF_ERR_UNSUPPORTED;
     if (!aligned4(ldvec, ldh1, ldz) || !counter || !z || ldz < H || (xn && !split_part)) return SF_ERR_UNSUPPORTED;
     if (xn && !proj_partials_supported(xn->IMG, xn->LOC)) return SF_ERR_UNSUPPORTED;
+    if (gf && (!xn || !proj_partials_supported(4 * H, xn->LOC))) return SF_ERR_UNSUPPORTED;
     const TxtFoldArgs ta{ctx_q, ctx_o, mask, L, H, vec, ldvec, part, counter, z, ldz, alpha};
-    const VisArgs va = xn ? proj_vis_args(*xn, pt, h1, ldh1, nullptr, nullptr, 0, Dropout{}, 0) : VisArgs{};
+    VisArgs va = xn ? proj_vis_args(*xn, pt, h1, ldh1, nullptr, nullptr, 0, Dropout{}, 0) : VisArgs{};
+    if (gf) {             // the row source in gate space: row (vp, v) of gf, 4H floats, in the slots of the image row
+        va.src.table = gf;
+        va.src.IMG = 4 * H;
+    }
     const VisSplit sp{split_part, nullptr, g_trace};
     const int nv = xn ? PPB_G * B : 0, na = y.gx * y.gy;
     const int force = g_proj_text_groups;
@@ -1743,7 +1758,17 @@ int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt
     if (gate && (!gate->gu || !gate->gl || !gate->xg_next)) return SF_ERR_UNSUPPORTED;
     ProjScoreArgs a{us, pt.pa, pt.la, pt.ld, H, z, y, ldz, ldy};
     if (gate) { a.gu = gate->gu; a.gl = gate->gl; a.xg_next = gate->xg_next; }
-    const VisArgs va = xn ? proj_vis_args(*xn, pt, h1, ldh1, alpha, out, ldo, drop, drop_col0) : VisArgs{};
+    VisArgs va = xn ? proj_vis_args(*xn, pt, h1, ldh1, alpha, out, ldo, drop, drop_col0) : VisArgs{};
+    if (gate && gate->xg_f) {
+        // launch (1) summed gate-space rows: records of 4H + LOC floats; the 4H part to xg_f, the LOC part to its columns
+        // of `out`
+        if (!xn || vphase != 2 || drop.on() || !gate->gf || !proj_partials_supported(4 * H, xn->LOC)) return SF_ERR_UNSUPPORTED;
+        va.out = out + xn->IMG;
+        va.src.table = gate->gf;
+        va.src.IMG = 4 * H;
+        va.out_img = gate->xg_f;
+        va.ld_img = 4 * H;
+    }
     const VisSplit sp{split_part, counter, g_trace};
     const dim3 block(SMALL_WAVES * 64);
     if (xn && vphase == 0)

@@ -1017,12 +1017,16 @@ __global__ __launch_bounds__(4 * LSTM_KS * 64) void lstm_step_fused_kernel(LstmS
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) pre[g] = bi[g] + bh[g] + xv[g];
+        if (p.xg2) {                                             // block-uniform
+#pragma unroll
+            for (int g = 0; g < 4; ++g) pre[g] += p.xg2[(size_t)qb * 4 * H + g * H + pj];
+        }
     }
 
     Seg2 sg;
     sg.s0 = Seg{p.h0, H, p.w_hh, H, H};
     sg.n0 = (H + 15) >> 4;
-    sg.s1 = p.x ? Seg{p.x, p.ldx, p.w_ih, p.I, p.I} : sg.s0;
+    sg.s1 = p.x ? Seg{p.x, p.ldx, p.w_ih, p.ld_w_ih ? p.ld_w_ih : p.I, p.I} : sg.s0;
     sg.total = sg.n0 + (p.x ? ((p.I + 15) >> 4) : 0);
     const int n = gate * H + slice * 16 + li;
     int mrow[1] = {min(m0 + li, p.B - 1)};
@@ -1086,6 +1090,7 @@ __global__ __launch_bounds__(LSTMW_WAVES * 64) void lstm_step_wide_kernel(LstmSt
             xv = p.xg[xr * 4 * H + pg * H + pj];
         }
         pre_g = bi + bh + xv;
+        if (p.xg2) pre_g += p.xg2[(size_t)qb * 4 * H + pg * H + pj];      // block-uniform
     }
 
     // this wave's K-slice of all four tiles: every fragment is loaded before the first MFMA
@@ -1103,7 +1108,7 @@ __global__ __launch_bounds__(LSTMW_WAVES * 64) void lstm_step_wide_kernel(LstmSt
         const int lc = second ? c - n0c : c;
         const float* W = second ? p.w_ih : p.w_hh;
         const float* A = second ? p.x : p.h0;
-        const int ldw = second ? p.I : H;
+        const int ldw = second ? (p.ld_w_ih ? p.ld_w_ih : p.I) : H;
         const int lda = second ? p.ldx : H;
         const int K = second ? p.I : H;
         const int k = lc * 16 + 4 * kk;
@@ -1913,9 +1918,11 @@ int linear_nt(const Seg* segs, int nseg, int M, int N, const LinearOut& out, flo
 }
 
 int lstm_step_fused(const LstmStepArgs& p, hipStream_t st) {
-    if (p.H % 16 || (p.x && (p.I % 4 || p.ldx % 4))) return SF_ERR_UNSUPPORTED;
+    if (p.H % 16 || (p.x && (p.I % 4 || p.ldx % 4 || p.ld_w_ih % 4))) return SF_ERR_UNSUPPORTED;
     const int total = ceil_div(p.H, 16) + (p.x ? ceil_div(p.I, 16) : 0);
-    if (p.B > 16 && p.H % 8 == 0) {          // 32 x 8 patches: fewer bytes per block (see the kernel)
+    // (p.wide: the decoder's step on gate-space rows takes them at every B -- its K = 640 needs lstm_step_fused_kernel<16>,
+    //  which spills, 19.4 us at B = 16 -- profiles/gate_rows_attended_ab.txt)
+    if ((p.B > 16 || p.wide) && p.H % 8 == 0) {          // 32 x 8 patches: fewer bytes per block (see the kernel)
         const int cw = ceil_div(total, LSTMW_WAVES);
         dim3 wgrid(p.H / 8, ceil_div(p.B, 32)), wblock(LSTMW_WAVES * 64);
         if (cw <= 2) {

@@ -232,6 +232,9 @@ struct ProjTables {
 struct GateRows {
     const float *gu, *gl;    // [n_vp * V, 4H], [4, 4H]
     float* xg_next;          // [B, 4H]
+    // the ATTENDED half (sf_gate_rows_attended_build; both null: the raw attended feature, as without this table):
+    const float* gf;         // [n_vp * V, 4H]: launch (1)'s partials load these rows where they loaded image rows
+    float* xg_f;             // [B, 4H]: where launch (2)'s merge leaves the normalised 4H part for the next step's cell
 };
 bool proj_chain_supported(const CandSrc& us, const PanoSrc* xn, int B, int H, int L, const ProjTables& pt);
 int proj_attention_alone(const PanoSrc& x, int B, const ProjTables& pt, const float* h1, int ldh1, float* alpha, float* out,
@@ -245,7 +248,7 @@ void proj_text_slots_warm();          // asks the device for `slots` once (ahead
 int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* mask, int B, int L, int H, const float* vec,
                        int ldvec, float* part, unsigned* counter, float* z, int ldz, float* alpha, const SmallPlan& y,
                        const CandSrc& us, const PanoSrc* xn, const ProjTables& pt, const float* h1, int ldh1, float* split_part,
-                       hipStream_t st);
+                       hipStream_t st, const float* gf = nullptr);      // gf: the partials sum gate-space rows of 4H floats
 int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt, const float* z, int ldz, const float* y, int ldy,
                     const FGlue& g, const PanoSrc* xn, int vphase, const float* h1, int ldh1, float* alpha, float* out, int ldo,
                     const Dropout& drop, int drop_col0, float* split_part, unsigned* counter, hipStream_t st,

@@ -29,6 +29,9 @@ struct LstmStepArgs {            // fused recurrent step (sf_gemm.hip: lstm_step
     const float* b_ih; const float* b_hh;
     int B, H;
     LstmPwFwd pw;                                   // outputs / state (slabs, xg, biases unused)
+    int ld_w_ih;                                    // row stride of w_ih (0: I) -- a column range of a wider matrix
+    const float* xg2;                               // [B,4H] a second addend (the attended half in gate space), row b, or null
+    bool wide;                                      // the 32 x 8 patches at B <= 16 too (lstm_step_fused: measured for this caller)
 };
 
 // Encoder-only operands of the cell update (row liveness at step t, previous h), fetched by the

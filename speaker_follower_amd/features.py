@@ -130,6 +130,7 @@ def _forget_gate_rows(addr, gu):
         if not _lib.lib.sf_gate_rows_registered(C.c_void_p(addr), C.byref(cur)) or cur.gu != gu:
             return
     _lib.lib.sf_gate_rows_register(C.c_void_p(addr), None)
+    _lib.lib.sf_gate_rows_attended_register(C.c_void_p(addr), None)      # (the attended half lives and dies with them)
 
 
 class FeatureStore:
@@ -175,6 +176,7 @@ class FeatureStore:
             # ... and a projected-table entry of a collected store that lived at this address (`projected` below)
             call('sf_projected_register', C.c_void_p(addr), None)
             call('sf_gate_rows_register', C.c_void_p(addr), None)
+            call('sf_gate_rows_attended_register', C.c_void_p(addr), None)
         self._projected = weakref.WeakKeyDictionary()       # decoder module -> its projected tables (see `projected`)
         self._gate_rows = weakref.WeakKeyDictionary()       # decoder module -> its gate-space rows (see `gate_rows`)
         self.LOC = loc
@@ -277,14 +279,22 @@ class FeatureStore:
         return hit
 
     # ---- gate-space rows (include/sf_hip.h: sf_gate_rows_build) ----------------------------------
-    def gate_rows(self, decoder, build=True):
+    def gate_rows(self, decoder, build=True, attended=True):
         """The gate-space rows of (this store, `decoder`): every table row carried through the action half of the decoder
         LSTM's input weights ONCE (gu [n * V, 4H], gl [4, 4H]), so that a step of the projected chain takes its gate product
         over K = F + H instead of 2 F + H (include/sf_hip.h).  Kept beside the projected tables with the same policy:
         cached per decoder, rebuilt IN PLACE when `weight_ih`'s version counter or the table changes, dropped with the
         store or the decoder, `build=False` returns them only if they exist (refreshed), else None; None for an fp16
         store.  Costs n * V * 4H * 4 bytes (3.1 GB for the full R2R table at H = 512).  The callers ask for them only
-        where the projected tables are in use (FollowerEngine)."""
+        where the projected tables are in use (FollowerEngine).
+
+        `attended` (default on) keeps, in the SAME entry and under the same rules, the table of the other half of the
+        input: gf [n * V, 4H], every row through the image columns of the attended feature (sf_gate_rows_attended_build),
+        which leaves the product K = LOC + H.  Another n * V * 4H * 4 bytes.  hit['attended'] is dict(buf, struct), or
+        None where it was not asked for or launch (1)'s partials do not take rows of 4H + LOC floats; one `builds` count
+        covers both tables.  The table is ADDED only where `build` is true (the first build, or a caller that builds and
+        asks for it behind an entry made without it); a refresh keeps what the entry holds -- both tables or the action
+        half's alone -- so a rollout captured with `attended=False` never grows the entry by replaying."""
         from .model import decoder_params                        # (model imports this module)
         from .runtime import weight_key, ws_args
         if self.dtype != 'fp32' or not self.table.numel() or self.IMG % 4 or self.LOC % 16:
@@ -294,24 +304,37 @@ class FeatureStore:
             return None
         w_ih = decoder_params(decoder)[0]
         key = weight_key(w_ih) + (self.table.data_ptr(), self.table._version)
-        if hit is None or hit['key'] != key:
-            H = decoder.hidden_size
+        H = decoder.hidden_size
+        attended = bool(attended) and H % 4 == 0 and bool(_lib.lib.sf_gate_rows_attended_supported(H, self.LOC))
+        late = hit is not None and attended and hit['attended'] is None       # (asked for behind a build without it)
+        if hit is None or hit['key'] != key or (late and build):
             if H % 4 or decoder.feature_size != self.F or tuple(w_ih.shape) != (4 * H, 2 * self.F):
                 return None
             rows = self.n * self.V
             new = lambda r: torch.empty(r, 4 * H, device=self.device, dtype=torch.float32)  # noqa: E731
-            bufs = hit['bufs'] if hit is not None and hit['bufs'][0].shape == (rows, 4 * H) else (new(rows), new(4))
+            same = hit is not None and hit['bufs'][0].shape == (rows, 4 * H)
+            bufs = hit['bufs'] if same else (new(rows), new(4))
             call('sf_gate_rows_build', ptr(w_ih), ptr(self.table), rows, self.IMG, self.LOC, H, ptr(bufs[0]), ptr(bufs[1]),
                  *ws_args(self.device))
             struct = _lib.GateRows(bufs[0].data_ptr(), bufs[1].data_ptr(), w_ih.data_ptr(), H, self.V, self.IMG, self.LOC)
+            att = hit['attended'] if same else None
+            had = hit is not None and hit['attended'] is not None       # (a re-shaped table re-allocates what there was)
+            if had or (attended and build):
+                gf = att['buf'] if att is not None else new(rows)
+                call('sf_gate_rows_attended_build', ptr(w_ih), ptr(self.table), rows, self.IMG, self.LOC, H, ptr(gf),
+                     *ws_args(self.device))
+                att = dict(buf=gf, struct=_lib.GateRowsAttended(gf.data_ptr(), w_ih.data_ptr(), H, self.V, self.IMG,
+                                                                self.LOC))
             first = hit is None
-            hit = dict(key=key, bufs=bufs, struct=struct, builds=(0 if first else hit['builds']) + 1)
+            hit = dict(key=key, bufs=bufs, struct=struct, attended=att, builds=(0 if first else hit['builds']) + 1)
             self._gate_rows[decoder] = hit
             if first:
                 addr = self.table.data_ptr()
                 weakref.finalize(decoder, _forget_gate_rows, addr, bufs[0].data_ptr())
                 weakref.finalize(self, _forget_gate_rows, addr, None)
         call('sf_gate_rows_register', C.c_void_p(self.table.data_ptr()), C.byref(hit['struct']))
+        call('sf_gate_rows_attended_register', C.c_void_p(self.table.data_ptr()),
+             C.byref(hit['attended']['struct']) if hit['attended'] is not None else None)
         return hit
 
     def note_unprojected(self, decoder):

@@ -263,6 +263,25 @@ class gate_rows_pass:
         return False
 
 
+class gate_rows_attended_pass:
+    """`with gate_rows_attended_pass(on):` -- whether the steps that run on gate-space rows also look the attended half's
+    table up (sf_gate_rows_attended_use; process-wide like gate_rows_pass).  Restores the switch on exit."""
+
+    def __init__(self, on):
+        self.on = int(bool(on))
+
+    def __enter__(self):
+        self.prev = int(_lib.lib.sf_gate_rows_attended_is_used())
+        if self.prev != self.on:
+            _lib.lib.sf_gate_rows_attended_use(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        if self.prev != self.on:
+            _lib.lib.sf_gate_rows_attended_use(self.prev)
+        return False
+
+
 class FollowerEngine:
     def __init__(self, encoder, decoder, store, group=None):
         self.encoder, self.decoder, self.store = encoder, decoder, store
@@ -285,6 +304,9 @@ class FollowerEngine:
         self._gate_weights = 'fp32'
         self._project = 'auto'
         self.gate_rows = True           # projected rollouts: the action half of the LSTM input as a gate-space row (below)
+        # ... and the image part of the attended half too (sf_gate_rows_attended_build): the product shrinks to K = LOC + H.
+        # Means something only while `gate_rows` is on; built, used and refreshed with those rows
+        self.gate_rows_attended = True
         self._capturing = False         # inside capture() / capture_sharded(): 'auto' builds the projected tables
 
     # The two-chain forward schedule (the visual half of step t + 1 on a side stream) is retired: DESIGN.md section 9.
@@ -349,7 +371,9 @@ class FollowerEngine:
         rollouts launch the gate product over the whole input, bit for bit what they did without the tables."""
         if projected is None or not self.gate_rows or self.pass_gate_weights(train) != 'fp32':
             return None
-        return self.store.gate_rows(self.decoder, build=self._project is True or self._capturing)
+        # (the store's default keeps the attended half's table beside them; only `gate_rows_attended = False` says otherwise)
+        opt = {} if self.gate_rows_attended else {'attended': False}
+        return self.store.gate_rows(self.decoder, build=self._project is True or self._capturing, **opt)
 
     # How the decoder LSTM's weights are stored for the gate product of INFERENCE passes: 'fp32' (default) or 'bf16'
     # (include/sf_hip.h: sf_gate_product_bf16_weights -- the product of the unrounded activations with the weights rounded
@@ -485,7 +509,7 @@ class FollowerEngine:
         pipelined = self.pipelined and not on_device_env
         st.episode = None
         st.projected, st.projected_tables = False, None
-        st.gate_rows, st.gate_rows_tables = False, None
+        st.gate_rows, st.gate_rows_tables, st.gate_rows_attended = False, None, False
         # the same one-call episode for a device-resident environment (the env step inside every scoring + glue launch,
         # the attention of step t + 1 behind it): no host work between the launches of a TRAINING rollout either, and
         # the backward takes the two-stream episode path
@@ -524,11 +548,16 @@ class FollowerEngine:
             # takes the two-launch chain for every step it applies to and says how many it issued
             st.projected_tables = self._projected_tables(B, T=T, A=A) if (st.text_folded and not nav_episode) else None
             st.gate_rows_tables = self._gate_rows_tables(st.projected_tables, training)
-            with projected_pass(st.projected_tables is not None), gate_rows_pass(st.gate_rows_tables is not None):
+            attended = (st.gate_rows_tables is not None and self.gate_rows_attended
+                        and st.gate_rows_tables['attended'] is not None)
+            with projected_pass(st.projected_tables is not None), gate_rows_pass(st.gate_rows_tables is not None), \
+                    gate_rows_attended_pass(attended):
                 before, gate_before = _lib.lib.sf_projected_steps(), _lib.lib.sf_gate_rows_steps()
+                att_before = _lib.lib.sf_gate_rows_attended_steps()
                 call('sf_follower_episode_fwd', byref(dw), byref(ep), *ws)
                 st.projected = _lib.lib.sf_projected_steps() > before
                 st.gate_rows = _lib.lib.sf_gate_rows_steps() > gate_before
+                st.gate_rows_attended = _lib.lib.sf_gate_rows_attended_steps() > att_before
             st.episode = (ep, dw)
         tapes = [] if st.episode else [_lib.DecoderTape(*(st.tape[k][t].data_ptr() for k in _TAPE_KEYS))
                                        for t in range(S)]
@@ -643,7 +672,7 @@ class FollowerEngine:
             st.loss = st.loss_buf.reshape(())
         return st
 
-    def _baked_pointers(self, gate_weights='fp32', projected=False, gate_rows=False):
+    def _baked_pointers(self, gate_weights='fp32', projected=False, gate_rows=False, attended=False):
         """Every weight-side device pointer a captured rollout bakes into its hipGraph: the parameters
         and their derived copies (transposed layouts, the encoder's [vocab,4H] table, with
         gate_weights = 'bf16' the packed images of the decoder LSTM's weights).  Building the
@@ -666,8 +695,14 @@ class FollowerEngine:
             hit = self.store.projected(self.decoder, build=False)
             tables = b'projected' + (bytes(hit['struct']) if hit is not None else b'')
         if gate_rows:
-            hit = self.store.gate_rows(self.decoder, build=False)
+            # (`attended`: whether the CAPTURED rollout ran on the attended half's table.  Only then is that table part of
+            # what the graph reads: a table another engine added to the entry since is none of this graph's business, and
+            # a refresh here never adds one -- FeatureStore.gate_rows grows the entry only where `build` is true)
+            hit = self.store.gate_rows(self.decoder, build=False, **({} if attended else {'attended': False}))
             tables += b'gate_rows' + (bytes(hit['struct']) if hit is not None else b'')
+            if attended:
+                att = hit['attended'] if hit is not None else None
+                tables += b'attended' + (bytes(att['struct']) if att is not None else b'')
         return ew + bytes(dw) + packed + tables
 
     @contextlib.contextmanager
@@ -679,15 +714,15 @@ class FollowerEngine:
         finally:
             self._capturing = prev
 
-    def _guarded(self, graph_replay, projected=False, gate_rows=False):
+    def _guarded(self, graph_replay, projected=False, gate_rows=False, attended=False):
         mode = self._gate_weights          # (the captured rollouts ran train=False under no_grad: this mode, for good)
-        baked = self._baked_pointers(mode, projected, gate_rows)
+        baked = self._baked_pointers(mode, projected, gate_rows, attended)
 
         def replay():
             # weights updated since capture (optimizer.step, load_state_dict)?  Their derived copies are
             # rebuilt in place here, ahead of the replay on the same stream, so the graph reads current
             # data everywhere.  A MOVED tensor cannot be patched into the graph: refuse.
-            if self._baked_pointers(mode, projected, gate_rows) != baked:
+            if self._baked_pointers(mode, projected, gate_rows, attended) != baked:
                 raise WeightsMoved('a weight (or one of its cached layouts) moved since this rollout was '
                                    'captured; capture() again')
             graph_replay()
@@ -738,7 +773,7 @@ class FollowerEngine:
                 self.site_next += st.site_stride
                 self.iteration += 1
             graph.replay()
-        return self._guarded(graph_replay, st.projected, st.gate_rows), st
+        return self._guarded(graph_replay, st.projected, st.gate_rows, st.gate_rows_attended), st
 
     def capture_training(self, batch, steps, feedback='sample', optimizers=(), zero=None):
         """hipGraph of ONE WHOLE TRAINING ITERATION (follower.py:1001-1020 + train.py:263-268): zero the gradients,
@@ -841,7 +876,8 @@ class FollowerEngine:
                 call('sf_add_f32', ptr(total), ptr(st.sum_cnt), total.numel(), stream())
             call('sf_loss_finalize', ptr(total), steps, ptr(loss_buf), ptr(gscale), stream())
 
-        return self._guarded(replay_all, any(st.projected for st in states), any(st.gate_rows for st in states)), states, loss_buf
+        return self._guarded(replay_all, any(st.projected for st in states), any(st.gate_rows for st in states),
+                             any(st.gate_rows_attended for st in states)), states, loss_buf
 
     # ------------------------------------------------------------------------------ backward
     def _backward(self, st, dloss):

@@ -83,7 +83,7 @@ def timed(replay, n=40):
 for label in ('first build (allocates %.2f GB)', 'rebuild in place'):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    hit = store.gate_rows(dec)
+    hit = store.gate_rows(dec, attended=False)
     torch.cuda.synchronize()
     gb = hit['bufs'][0].numel() * 4 / 1e9
     print('gate-space rows, %-32s %.2f ms' % ((label % gb) if '%' in label else label, 1e3 * (time.perf_counter() - t0)), flush=True)
@@ -94,6 +94,7 @@ runs = {}
 for name, rows in LEGS:
     eng = follower.FollowerEngine(enc, dec, store)
     eng.gate_rows = rows
+    eng.gate_rows_attended = False          # (the action half alone: the other half is tools/gate_rows_attended_ab.py's)
     replay, st = eng.capture(batch, 20, 'argmax')
     assert st.projected and bool(st.gate_rows) == rows
     replay()
@@ -116,6 +117,7 @@ for name, _ in LEGS:
 for name, rows in LEGS:                      # per-kernel times of one eager rollout per leg
     eng = follower.FollowerEngine(enc, dec, store)
     eng.gate_rows = rows
+    eng.gate_rows_attended = False          # (the action half alone: the other half is tools/gate_rows_attended_ab.py's)
     with torch.no_grad():
         eng.rollout(batch, 20, 'argmax', train=False)
         torch.cuda.synchronize()
