@@ -26,6 +26,7 @@ from .lazydict import LazyDict
 from .follower import batch_instructions_from_encoded, FEEDBACK, PAD, EOS, BOS
 from .runtime import (ptr, stream, require_gpu, cands_dense, gc_paused, WeightsMoved, take_fault, fault_views, fault_bits,
                       per_step_kernels, reissue_per_step)
+from .sweeps import epoch_minibatches
 
 byref = C.byref
 
@@ -1529,15 +1530,7 @@ class Seq2SeqSpeaker(object):
         self._test_minibatches = seen + n_batches
         if seen + n_batches < self.sweep_test_after:
             return False
-        drawn, ids, looped = [], set(), False
-        while not looped:                                      # (the loop of speaker.py:404-413 over the items themselves)
-            self.env.reset()
-            items = list(self.env.batch)
-            drawn.append(items)
-            for it in items:
-                if it['instr_id'] in ids:
-                    looped = True
-                ids.add(it['instr_id'])
+        drawn = [items for _, items, _ in epoch_minibatches(self.env)]   # (speaker.py:404-413 over the items themselves)
         sweep = self._sweep_for(store, B)
         if self.device_routes:
             from .nav import table_for

@@ -24,7 +24,6 @@ import ctypes as C
 import json
 import math
 import os
-import random
 from collections import defaultdict, namedtuple
 
 import numpy as np
@@ -181,6 +180,43 @@ def _load_graphs(scans, nav_graph_path=CONNECTIVITY):
     return {s: NavGraph(os.path.join(nav_graph_path, s + '_connectivity.json')) for s in sorted(scans)}
 
 
+def _err_text(entry, noun, ragged=False):
+    """The sentence for a raised err word of a scoring launch over `noun`s (include/sf_hip.h: the refusals per route)."""
+    return '%s: a %s left its scan%s' % (entry, noun, ' or does not start where its gold path does' if ragged
+                                         else ', or a slot its array')
+
+
+class _Outputs:
+    """The output block of a scoring launch over n slots, with a pinned mirror (`*_h`) of every array:
+      o64 [5, n]   nav_error, oracle_error, length, shortest, dtw ([3, n] with wide=False: sf_eval_score's)
+      o32 [3, n]   steps, success, oracle_success
+      err [1]      only ever raised by the kernels: zeroed here, and by an owner that keeps the block, before it launches
+      near [n, near_ld]   with near_ld > 0: the coverage launch's least distance to every gold node
+    `download()` issues the copies to the mirrors on the current stream; behind the caller's sync, `check(text)` raises
+    a set err word in the words the launch gave and `host()` is (o64, o32, near or None) as numpy arrays."""
+
+    def __init__(self, dev, n, wide=True, near_ld=0):
+        import torch
+        pair = lambda shape, dt: (torch.empty(shape, dtype=dt, device=dev),           # noqa: E731
+                                  torch.empty(shape, dtype=dt).pin_memory())
+        self.o64, self.o64_h = pair((5 if wide else 3, n), torch.float64)
+        self.o32, self.o32_h = pair((3, n), torch.int32)
+        self.err, self.err_h = pair((1,), torch.int32)
+        self.near, self.near_h = pair((n, near_ld), torch.float64) if near_ld else (None, None)
+        self.err.zero_()
+
+    def download(self):
+        for name in ('o64', 'o32', 'err') + (('near',) if self.near is not None else ()):
+            getattr(self, name + '_h').copy_(getattr(self, name), non_blocking=True)
+
+    def check(self, text):
+        if int(self.err_h[0]):
+            raise RuntimeError(text)
+
+    def host(self):
+        return self.o64_h.numpy(), self.o32_h.numpy(), None if self.near is None else self.near_h.numpy()
+
+
 class Evaluation(object):
     """eval.py:23-139.  Results: {instr_id: {'instr_id', 'trajectory': [(viewpoint_id, heading, elevation), ...]}}.
 
@@ -259,11 +295,10 @@ class Evaluation(object):
         if not self.path_metrics:
             return r
         D = self.table.block(scan)
-        if not self.coverage_metrics:
-            return path_metrics_of(r, float(D[rows[0], goal]), dtw_rows(D[np.ix_(rows, gold)].tolist()), len(gold),
-                                   self.error_margin)
         cost = D[np.ix_(rows, gold)].tolist()
         r = path_metrics_of(r, float(D[rows[0], goal]), dtw_rows(cost), len(gold), self.error_margin)
+        if not self.coverage_metrics:
+            return r
         return coverage_metrics_of(r, [min(col) for col in zip(*cost)], gold_length, self.error_margin)
 
     def _score_six(self, scan, rows, goal):
@@ -395,70 +430,110 @@ class Evaluation(object):
                                             self._gold_lengths()[gt['path_id']] if self.coverage_metrics else None))
         return out
 
+    def _episode_words(self, nav, items, slots):
+        """int64 [5, B]: gold_id, scan_base, m, dist_off, slot -- the per-episode words of a scoring launch, for items
+        of the environment whose poses are rows of `nav`, or (nav = None) ground truths whose poses are local already.
+        gold_id is 0 where the gold table has not been built (path_metrics off) or does not hold the item's path: the
+        kernels read it only where slot >= 0."""
+        t, ids = self.table, {} if self._gold is None else self._gold['ids']
+        return np.array([(ids.get(it.get('path_id'), 0), 0 if nav is None else self._local_rows(nav, it['scan']),
+                          t.m[it['scan']], t.off[it['scan']], slot)
+                         for it, slot in zip(items, slots)], np.int64).reshape(len(items), 5).T
+
+    def _launch_route_scoring(self, out, noun, *, S, B, n_slots, row_stride, n_rows, row, row_first, gold_id,
+                              scan_base, m, dist_off, slot, n_steps=None, actions=None, refusable=False):
+        """THE route-scoring launch (include/sf_hip.h: sf_eval_routes), issued on the current stream for B routes
+        (device tensors, by name) into the output block `out`: sf_eval_score_routes_coverage with coverage_metrics
+        -- it also fills out.near -- else sf_eval_score_routes.  The gold paths, the distances and the margin are the
+        evaluator's.  The layouts:
+          ragged   routes back to back in `row`: row_stride = 1, row_first = their offsets, n_steps given (S = 0)
+          sweep    row [S+1, B] as a rollout or a walk leaves it: row_stride = B, row_first[b] = b, and either `actions`
+                   [S, B] (the step count is derived from them) or the walk's own n_steps
+        Returns (status, text): `text` is the sentence for a raised err word in the caller's terms (`noun`: 'route',
+        'rollout', 'walk'), for `out.check(text)` after the caller's sync.  A failing status raises here; only a
+        `refusable` caller gets SF_ERR_UNSUPPORTED back (a gold path above SF_EVAL_MAX_GOLD nodes, nothing launched)."""
+        from . import _lib
+        from .runtime import stream
+        gold = self._gold_table()
+        at = lambda x: None if x is None else x.data_ptr()    # noqa: E731
+        e = _lib.EvalRoutes(S=S, B=B, n_slots=n_slots, row_stride=row_stride, n_gold=len(gold['ids']),
+                            n_gold_nodes=len(gold['node']), max_gold=gold['longest'], n_rows=n_rows, row=at(row),
+                            row_first=at(row_first), n_steps=at(n_steps), actions=at(actions),
+                            gold_off=at(gold['dev'][0]), gold_node=at(gold['dev'][1]), gold_id=at(gold_id),
+                            scan_base=at(scan_base), m=at(m), dist_off=at(dist_off), slot=at(slot),
+                            table=at(self.table.dev), margin=self.error_margin,
+                            nav_error=at(out.o64[0]), oracle_error=at(out.o64[1]), length=at(out.o64[2]),
+                            shortest=at(out.o64[3]), dtw=at(out.o64[4]),
+                            steps=at(out.o32[0]), success=at(out.o32[1]), oracle_success=at(out.o32[2]))
+        if self.coverage_metrics:
+            entry, near = 'sf_eval_score_routes_coverage', (C.c_void_p(at(out.near)), out.near.shape[1])
+        else:
+            entry, near = 'sf_eval_score_routes', ()
+        status = getattr(_lib.lib, entry)(C.byref(e), *near, C.c_void_p(at(out.err)), stream())
+        if not (refusable and status == _lib.SF_ERR_UNSUPPORTED):
+            _lib.check(status, entry)
+        return status, _err_text(entry, noun, ragged=row_stride == 1)
+
+    def _assemble(self, gts, o64, o32, near=None, lists=False):
+        """A scoring launch's downloaded outputs (_Outputs.host()) -> the per-item results of this evaluator's type, or
+        with `lists` -> `self.scores`, one list per field.  Slot i belongs to ground truth gts[i]; slots behind the last
+        one, and the elements of a `near` row behind its gold path, hold nothing.  The classic six come by columns (and
+        stay columns where nothing else is asked for); spl / ndtw / sdtw and coverage / length_score / cls are formed
+        per item by the one function each that the host path uses."""
+        M = len(gts)
+        cols = (o64[0, :M].tolist(), o64[1, :M].tolist(), o32[0, :M].tolist(), o64[2, :M].tolist(),
+                (o32[1, :M] != 0).tolist(), (o32[2, :M] != 0).tolist())
+        if self.path_metrics or not lists:
+            out = [EvalResult(*r) for r in zip(*cols)]
+            margin = self.error_margin
+            if self.path_metrics:
+                out = [path_metrics_of(r, sh, dtw, len(gt['path']), margin)
+                       for r, sh, dtw, gt in zip(out, o64[3, :M].tolist(), o64[4, :M].tolist(), gts)]
+            if self.coverage_metrics:
+                lengths = self._gold_lengths()
+                out = [coverage_metrics_of(r, row[:len(gt['path'])], lengths[gt['path_id']], margin)
+                       for r, row, gt in zip(out, near[:M].tolist(), gts)]
+            if not lists:
+                return out
+            cols = zip(*out)
+        return self._scores_of(cols)
+
+    def _scores_of(self, cols):
+        """`self.scores` from the columns of the results: one list per field of this evaluator's result type."""
+        names = _LISTS + (_PATH_LISTS if self.path_metrics else ()) + (_COVERAGE_LISTS if self.coverage_metrics else ())
+        self.scores = defaultdict(list, zip(names, map(list, cols)))
+        return self.scores
+
     def _score_routes_on_device(self, routes):
         import torch
         from . import _lib
-        from .runtime import stream
         t, gold = self.table, self._gold_table()
         if gold['dev'] is None:
             return None
         dev = t.dev.device
         N = len(routes)
         n = np.array([len(rows) - 1 for _, rows in routes], np.int64)
-        i32 = np.zeros((5, N), np.int32)                     # n_steps, gold_id, m, slot, scan_base (0: poses are local)
-        i64 = np.zeros((2, N), np.int64)                     # row_first, dist_off
-        i32[0], i32[3] = n, np.arange(N)
-        i64[0, 1:] = np.cumsum(n[:-1] + 1)
-        for i, (gt, _) in enumerate(routes):
-            i32[1, i], i32[2, i], i64[1, i] = gold['ids'][gt['path_id']], t.m[gt['scan']], t.off[gt['scan']]
+        first = np.concatenate(([0], np.cumsum(n[:-1] + 1)))
+        w = self._episode_words(None, [gt for gt, _ in routes], range(N))
+        i32 = np.concatenate((w[[0, 1, 2, 4]], n[None])).astype(np.int32)      # gold_id, scan_base, m, slot, n_steps
+        i64 = np.stack((first, w[3]))                                          # row_first, dist_off
         poses = np.concatenate([rows for _, rows in routes]).astype(np.int32)
-        ptr_of = lambda x: x.data_ptr()                       # noqa: E731
         with torch.cuda.device(dev):
             d32, d64, rows_d = (torch.from_numpy(a).to(dev) for a in (i32, i64, poses))
-            o64 = torch.empty(5, N, dtype=torch.float64, device=dev)
-            o32 = torch.zeros(3 * N + 1, dtype=torch.int32, device=dev)                   # (the last word: err)
-            e = _lib.EvalRoutes(0, N, N, 1, len(gold['ids']), len(gold['node']), gold['longest'], 0, len(poses),
-                                ptr_of(rows_d), ptr_of(d64[0]), ptr_of(d32[0]), None, ptr_of(gold['dev'][0]),
-                                ptr_of(gold['dev'][1]), ptr_of(d32[1]), ptr_of(d32[4]), ptr_of(d32[2]), ptr_of(d64[1]),
-                                ptr_of(d32[3]), ptr_of(t.dev), self.error_margin, *[ptr_of(o64[k]) for k in range(5)],
-                                *[ptr_of(o32[k * N:]) for k in range(3)])
-            if self.coverage_metrics:                         # the same launch, + near [N, longest]
-                entry, ld = 'sf_eval_score_routes_coverage', gold['longest']
-                near = torch.empty(N, ld, dtype=torch.float64, device=dev)
-                status = _lib.lib.sf_eval_score_routes_coverage(C.byref(e), C.c_void_p(ptr_of(near)), ld,
-                                                                C.c_void_p(ptr_of(o32[3 * N:])), stream())
-            else:
-                entry = 'sf_eval_score_routes'
-                status = _lib.lib.sf_eval_score_routes(C.byref(e), C.c_void_p(ptr_of(o32[3 * N:])), stream())
+            out = _Outputs(dev, N, near_ld=gold['longest'] if self.coverage_metrics else 0)
+            status, text = self._launch_route_scoring(out, 'route', S=0, B=N, n_slots=N, row_stride=1,
+                                                      n_rows=len(poses), row=rows_d, row_first=d64[0], n_steps=d32[4],
+                                                      gold_id=d32[0], scan_base=d32[1], m=d32[2], dist_off=d64[1],
+                                                      slot=d32[3], refusable=True)
             if status == _lib.SF_ERR_UNSUPPORTED:             # a gold path above the kernel's 64 nodes
                 self.fallbacks += 1
                 return None
-            _lib.check(status, entry)
-            h64 = torch.empty(5, N, dtype=torch.float64).pin_memory()
-            h32 = torch.empty(3 * N + 1, dtype=torch.int32).pin_memory()
-            h64.copy_(o64, non_blocking=True)
-            h32.copy_(o32, non_blocking=True)
-            if self.coverage_metrics:
-                hnear = torch.empty(N, ld, dtype=torch.float64).pin_memory()
-                hnear.copy_(near, non_blocking=True)
+            out.download()
             torch.cuda.current_stream().synchronize()         # the one host sync of the batch
         self.last_host_syncs = 1
         self.host_syncs += 1
-        if int(h32[3 * N]):
-            raise RuntimeError('%s: a route left its scan or does not start where its gold path does' % entry)
-        f, k = h64.numpy(), h32.numpy()[:3 * N].reshape(3, N)
-        margin = self.error_margin
-        six = [EvalResult(a, b, c, d, bool(s), bool(o)) for a, b, c, d, s, o in
-               zip(f[0].tolist(), f[1].tolist(), k[0].tolist(), f[2].tolist(), k[1].tolist(), k[2].tolist())]
-        if not self.path_metrics:
-            return six
-        full = [path_metrics_of(r, sh, dtw, len(gt['path']), margin)
-                for r, sh, dtw, (gt, _) in zip(six, f[3].tolist(), f[4].tolist(), routes)]
-        if not self.coverage_metrics:
-            return full
-        lengths = self._gold_lengths()
-        return [coverage_metrics_of(r, row[:len(gt['path'])], lengths[gt['path_id']], margin)
-                for r, row, (gt, _) in zip(full, hnear.numpy().tolist(), routes)]
+        out.check(text)
+        return self._assemble([gt for gt, _ in routes], *out.host())
 
     def score_routes(self, instr_ids, trajectories):
         """What `_score_item(instr_id, trajectory)` returns for every pair, as one batch: EvalResult -- PathEvalResult
@@ -470,7 +545,6 @@ class Evaluation(object):
     def score_results(self, results):
         """results: instr_id -> dictionary with (at least) 'trajectory' -- or a result of a device rollout
         (nav._Trajectory), which is scored from its nav rows."""
-        self.scores = defaultdict(list)
         model_scores = []
         instr_ids = set(self.instr_ids)
         taken, on_device = [], []
@@ -491,16 +565,7 @@ class Evaluation(object):
         if on_device:
             scored = iter(self._score_device_results(on_device))
             taken = [next(scored) if r is None else r for r in taken]
-        for r in taken:
-            for name, v in zip(_LISTS, (r.nav_error, r.oracle_error, r.trajectory_steps, r.trajectory_length,
-                                        r.success, r.oracle_success)):
-                self.scores[name].append(v)
-            if self.path_metrics:
-                for name, v in zip(_PATH_LISTS, r[6:11]):
-                    self.scores[name].append(v)
-            if self.coverage_metrics:
-                for name, v in zip(_COVERAGE_LISTS, r[11:]):
-                    self.scores[name].append(v)
+        self._scores_of(zip(*taken))
         return self._summary(instr_ids, len(taken), model_scores), self.scores
 
     def _summary(self, missing, instr_count, model_scores):
@@ -556,45 +621,36 @@ class Evaluation(object):
         import torch
         key = (str(dev), K, S, B, len(self.instr_ids))
         buf = self._sweep_buffers.get(key)
+        p = lambda *s, dt: torch.empty(*s, dtype=dt).pin_memory()                         # noqa: E731
         if buf is None:
-            n = len(self.instr_ids)
             d = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)                      # noqa: E731
-            p = lambda *s, dt: torch.empty(*s, dtype=dt).pin_memory()                     # noqa: E731
-            i32, i64, f32, f64 = torch.int32, torch.int64, torch.float32, torch.float64
-            w32, w64 = (5, 5) if self.path_metrics else (4, 3)                            # (+ gold_id; + shortest, dtw)
+            i32, i64, f32 = torch.int32, torch.int64, torch.float32
+            w32 = 5 if self.path_metrics else 4                                           # (+ gold_id)
             buf = dict(per32=d(K, w32, B, dt=i32), per64=d(K, B, dt=i64), per32_h=p(K, w32, B, dt=i32),
                        per64_h=p(K, B, dt=i64),
-                       out64=d(w64, n, dt=f64), out32=d(3, n, dt=i32), out64_h=p(w64, n, dt=f64), out32_h=p(3, n, dt=i32),
-                       loss=d(K, dt=f32), loss_h=p(K, dt=f32), sc=d(K, S, B, dt=f32), sc_h=p(K, S, B, dt=f32),
-                       err=d(1, dt=i32), err_h=p(1, dt=i32))
+                       out=_Outputs(dev, len(self.instr_ids), wide=self.path_metrics,      # near [slot, gold position]
+                                    near_ld=self._gold_table()['longest'] if self.coverage_metrics else 0),
+                       loss=d(K, dt=f32), loss_h=p(K, dt=f32), sc=d(K, S, B, dt=f32), sc_h=p(K, S, B, dt=f32))
             if self.path_metrics:
                 buf['first'] = torch.arange(B, dtype=i64, device=dev)                     # sweep layout: row_first[b] = b
-            if self.coverage_metrics:                                                     # near [slot, gold position]
-                ld = self._gold_table()['longest']
-                buf.update(near=d(n, ld, dt=f64), near_h=p(n, ld, dt=f64))
             self._sweep_buffers = {key: buf}
         if keep and 'rows_h' not in buf:
-            import torch
-            p = lambda *s, dt: torch.empty(*s, dtype=dt).pin_memory()                     # noqa: E731
             buf.update(rows_h=p(K, S + 1, B, dt=torch.int32), views_h=p(K, S + 1, B, dt=torch.int32),
                        acts_h=p(K, S, B, dt=torch.int64))
         return buf
 
     def score_agent(self, agent, use_dropout=False, feedback='argmax', keep_results=False):
         """What `agent.test(use_dropout, feedback)` followed by `score_results(agent.results)` returns, as ONE sweep on
-        the device: the environment is walked exactly as BaseAgent.test walks it (reset_epoch, reset(sort=True) until an
-        id repeats, the first occurrence of an id wins -- `env.ix` and `random` end where test() leaves them), every
-        minibatch's captured rollout is replayed back to back with sf_eval_score behind it on the same stream (ids
-        already issued, and ids outside `instr_ids`, write nothing), and the host waits ONCE, after the last minibatch
-        (`last_host_syncs`; the capture of a rollout nobody has captured yet synchronises on its own).  `agent.losses`
-        is set as test() sets it; `agent.results` stays empty unless keep_results (the row / view / action downloads per
-        minibatch, still without a wait in between).  A raised fault word, or an agent `_rollout_on_graph` does not
-        take, means agent.test() + score_results instead (`fallbacks`): a faulting sweep is never scored, and the
-        environment's item order and `random` are put back first, so that test() walks what the sweep walked.
-        With path_metrics the launch behind every rollout is sf_eval_score_routes in its sweep layout (the same arrays,
-        plus the episode's gold path index): still one host sync.  With coverage_metrics it is
-        sf_eval_score_routes_coverage, which also fills `near` [instruction, gold position]: one more download behind the
-        same sync."""
+        the device.  The environment is walked exactly as BaseAgent.test walks it (sweeps.epoch_minibatches with
+        reset(sort=True): `env.ix` and `random` end where test() leaves them), every minibatch's captured rollout is
+        replayed back to back with the scoring launch behind it on the same stream -- sf_eval_score, or with
+        path_metrics `_launch_route_scoring` in its sweep layout over the same arrays; ids already issued, and ids
+        outside `instr_ids`, write nothing -- and the host waits ONCE, after the last minibatch (`last_host_syncs`; the
+        capture of a rollout nobody has captured yet synchronises on its own).  `agent.losses` is set as test() sets it;
+        `agent.results` stays empty unless keep_results (the row / view / action downloads per minibatch, still without
+        a wait in between).  A raised fault word, or an agent `_rollout_on_graph` does not take, means agent.test() +
+        score_results instead (`fallbacks`): a faulting sweep is never scored, and the environment's item order and
+        `random` are put back first, so that test() walks what the sweep walked."""
         if hasattr(agent, 'walk_policy'):                     # a baseline agent: its own sweep, or its own test()
             return self._score_table_agent(agent, keep_results)
         nav = self._sweepable(agent, use_dropout, feedback)
@@ -602,9 +658,9 @@ class Evaluation(object):
             return self._by_test(agent, use_dropout, feedback)
         import torch
         from . import _lib
-        from .nav import DeviceNavBatch
-        from .runtime import stream, fault_views, take_fault, WeightsMoved
-        env, eng, t = agent.env, agent._engine, self.table
+        from .runtime import stream, clear_faults, download_faults, take_fault
+        from .sweeps import epoch_minibatches, snapshot, restore
+        env, t = agent.env, self.table
         dev = agent._device()
         agent.feedback = feedback
         for mod in (agent.encoder, agent.decoder):
@@ -614,83 +670,52 @@ class Evaluation(object):
         S, B = agent.episode_len, min(env.batch_size, max(1, len(env.data)))
         K = -(-len(env.data) // B) + 1                        # an id repeats in minibatch ceil(N / B) + 1 at the latest
         buf = self._buffers(dev, K, S, B, keep_results)
-        gold = self._gold_table() if self.path_metrics else None
+        out = buf['out']
+        if self.path_metrics:
+            self._gold_table()                                # (the episodes' gold ids are read from it)
         per32, per64 = buf['per32_h'].numpy(), buf['per64_h'].numpy()
-        walk0 = (list(env.data), random.getstate())          # (a faulting sweep is undone: test() then walks from here)
+        walk0 = snapshot(env)                                 # (a faulting sweep is undone: test() then walks from here)
         env.reset_epoch()
         agent.losses, agent.results = [], {}
-        syncs = 0
-        for w in fault_views(dev):                            # (whatever an earlier pass left behind is not ours)
-            w.zero_()
-        buf['err'].zero_()
-        order, where, seen, issued, looped = [], [], set(), [], False
+        clear_faults(dev)                                     # (whatever an earlier pass left behind is not ours)
+        out.err.zero_()
+        order, where, issued = [], [], []
         ptr_of = lambda x: x.data_ptr()                       # noqa: E731
         with torch.no_grad():
-            while not looped:
-                env.reset(sort=True)
-                items = list(env.batch)
-                k = len(issued)
+            for k, items, fresh in epoch_minibatches(env, sort=True):
                 if len(items) != B or k >= K:
                     raise RuntimeError('score_agent: minibatch %d holds %d items (batches of %d, at most %d)'
                                        % (k, len(items), B, K))
+                slots = [-1] * B
                 for b, it in enumerate(items):
-                    iid, scan = it['instr_id'], it['scan']
-                    slot = -1
-                    if iid in seen:
-                        looped = True
-                    else:
-                        seen.add(iid)
-                        if iid in self.instr_ids:
-                            slot = len(order)
-                            order.append(iid)
-                            where.append((k, b))
-                    goal = self.gt.get(it.get('path_id'), it)['path'][-1]
-                    per32[k, 0, b], per32[k, 1, b] = nav.row_of[(scan, goal)], self._local_rows(nav, scan)
-                    per32[k, 2, b], per32[k, 3, b] = t.m[scan], slot
-                    per64[k, b] = t.off[scan]
-                    if gold is not None:
-                        per32[k, 4, b] = gold['ids'].get(it.get('path_id'), 0)            # (read only where slot >= 0)
-                host = DeviceNavBatch.host_arrays_for(nav, items, agent.max_instruction_length,
-                                                      agent.reverse_instruction, True)
-                key = agent._test_graph_key(nav, eng, B)
-                for attempt in (0, 1):
-                    cached = agent.__dict__.setdefault('_test_graphs', {}).get(key)
-                    if cached is None:
-                        cached = agent._capture_test_rollout(nav, items, key, host)
-                    else:
-                        mirrors = cached[2].__dict__.setdefault('_sweep_mirrors', [])
-                        while len(mirrors) <= k:
-                            mirrors.append(cached[2].new_mirror())
-                        cached[2].load(items, host, mirror=mirrors[k])
-                    try:
-                        cached[0]()
-                        break
-                    except WeightsMoved:                      # (a weight moved since the capture: capture again)
-                        if attempt:
-                            raise
-                        agent._test_graphs.pop(key, None)
-                st, batch = cached[1], cached[2]
+                    if fresh[b] and it['instr_id'] in self.instr_ids:
+                        slots[b] = len(order)
+                        order.append(it['instr_id'])
+                        where.append((k, b))
+                w = self._episode_words(nav, items, slots)
+                per32[k, 0] = [nav.row_of[(it['scan'], self.gt.get(it.get('path_id'), it)['path'][-1])] for it in items]
+                per32[k, 1:4], per64[k] = w[[1, 2, 4]], w[3]      # goal_row, scan_base, m, slot (+ gold_id); dist_off
+                if self.path_metrics:
+                    per32[k, 4] = w[0]
+                st, batch = self._replay_rollout(agent, nav, items, k, B)
                 buf['per32'][k].copy_(buf['per32_h'][k], non_blocking=True)
                 buf['per64'][k].copy_(buf['per64_h'][k], non_blocking=True)
-                d32, o64, o32 = buf['per32'][k], buf['out64'], buf['out32']
-                if gold is not None:                          # the sweep layout of sf_eval_score_routes: + shortest, dtw
-                    ep = _lib.EvalRoutes(S, B, len(self.instr_ids), B, len(gold['ids']), len(gold['node']),
-                                         gold['longest'], 0, (S + 1) * B, ptr_of(batch.row), ptr_of(buf['first']), None,
-                                         ptr_of(st.actions), ptr_of(gold['dev'][0]), ptr_of(gold['dev'][1]),
-                                         ptr_of(d32[4]), ptr_of(d32[1]), ptr_of(d32[2]), ptr_of(buf['per64'][k]),
-                                         ptr_of(d32[3]), ptr_of(t.dev), self.error_margin,
-                                         *[ptr_of(o64[i]) for i in (0, 1, 2, 3, 4)], *[ptr_of(o32[i]) for i in (0, 1, 2)])
-                    if self.coverage_metrics:
-                        _lib.call('sf_eval_score_routes_coverage', C.byref(ep), C.c_void_p(ptr_of(buf['near'])),
-                                  gold['longest'], C.c_void_p(buf['err'].data_ptr()), stream())
-                    else:
-                        _lib.call('sf_eval_score_routes', C.byref(ep), C.c_void_p(buf['err'].data_ptr()), stream())
+                d32 = buf['per32'][k]
+                if self.path_metrics:
+                    _, text = self._launch_route_scoring(out, 'rollout', S=S, B=B, n_slots=len(self.instr_ids),
+                                                         row_stride=B, n_rows=(S + 1) * B, row=batch.row,
+                                                         row_first=buf['first'], actions=st.actions, gold_id=d32[4],
+                                                         scan_base=d32[1], m=d32[2], dist_off=buf['per64'][k], slot=d32[3])
                 else:
-                    ep = _lib.EvalEpisodes(S, B, len(self.instr_ids), 0, ptr_of(batch.row), ptr_of(st.actions),
-                                           ptr_of(d32[0]), ptr_of(d32[1]), ptr_of(d32[2]), ptr_of(buf['per64'][k]),
-                                           ptr_of(d32[3]), ptr_of(t.dev), self.error_margin, ptr_of(o64[0]),
-                                           ptr_of(o64[1]), ptr_of(o64[2]), ptr_of(o32[0]), ptr_of(o32[1]), ptr_of(o32[2]))
-                    _lib.call('sf_eval_score', C.byref(ep), C.c_void_p(buf['err'].data_ptr()), stream())
+                    text = _err_text('sf_eval_score', 'rollout')
+                    ep = _lib.EvalEpisodes(S=S, B=B, n_slots=len(self.instr_ids), row=ptr_of(batch.row),
+                                           actions=ptr_of(st.actions), goal_row=ptr_of(d32[0]), scan_base=ptr_of(d32[1]),
+                                           m=ptr_of(d32[2]), dist_off=ptr_of(buf['per64'][k]), slot=ptr_of(d32[3]),
+                                           table=ptr_of(t.dev), margin=self.error_margin,
+                                           nav_error=ptr_of(out.o64[0]), oracle_error=ptr_of(out.o64[1]),
+                                           length=ptr_of(out.o64[2]), steps=ptr_of(out.o32[0]),
+                                           success=ptr_of(out.o32[1]), oracle_success=ptr_of(out.o32[2]))
+                    _lib.call('sf_eval_score', C.byref(ep), C.c_void_p(ptr_of(out.err)), stream())
                 buf['loss'][k:k + 1].copy_(st.loss_buf.reshape(1))
                 buf['sc'][k].copy_(st.step_scores[:S])
                 if keep_results:
@@ -699,30 +724,24 @@ class Evaluation(object):
                     buf['acts_h'][k].copy_(st.actions[:S], non_blocking=True)
                 issued.append(items)
             n_mb = len(issued)
-            for name in ('out64', 'out32', 'loss', 'sc', 'err') + (('near',) if self.coverage_metrics else ()):
+            out.download()
+            for name in ('loss', 'sc'):
                 buf[name + '_h'].copy_(buf[name], non_blocking=True)
-            faults = fault_views(dev)
-            fpin = torch.empty(len(faults), dtype=torch.int32).pin_memory()
-            fpin.copy_(torch.cat(faults) if len(faults) > 1 else faults[0], non_blocking=True)
+            fpin = download_faults(dev)
             torch.cuda.current_stream().synchronize()         # the one host sync of the sweep
-            syncs += 1
         self.sweeps += 1
         if any(fpin.tolist()):
             take_fault(dev)                                   # (read and cleared: test() starts clean)
-            self.last_host_syncs = syncs + 1
-            self.host_syncs += syncs + 1
-            env.data[:] = walk0[0]
-            random.setstate(walk0[1])
+            self.last_host_syncs = 2
+            self.host_syncs += 2
+            restore(env, walk0)
             return self._by_test(agent, use_dropout, feedback)
-        self.last_host_syncs = syncs
-        self.host_syncs += syncs
-        if int(buf['err_h'][0]):
-            raise RuntimeError('%s: a rollout left its scan, or a slot its array'
-                               % ('sf_eval_score_routes_coverage' if self.coverage_metrics else
-                                  'sf_eval_score_routes' if self.path_metrics else 'sf_eval_score'))
+        self.last_host_syncs = 1
+        self.host_syncs += 1
+        out.check(text)
         M = len(order)
-        o64, o32 = buf['out64_h'].numpy(), buf['out32_h'].numpy()
-        self._scores_of_sweep(order, o64, o32, buf['near_h'].numpy() if self.coverage_metrics else None)
+        o64, o32, near = out.host()
+        self._assemble([self.gt[int(iid.split('_')[0])] for iid in order], o64, o32, near, lists=True)
         # 'score' of a result: the sequential float32 sum of its step scores up to the stop (nav.trajectories_from)
         sc = buf['sc_h'].numpy()[:n_mb]
         totals = np.cumsum(sc, axis=1, dtype=np.float32)
@@ -733,47 +752,47 @@ class Evaluation(object):
         if keep_results:
             for k, items in enumerate(issued):
                 rows, views, acts = (buf[x][k].numpy().copy() for x in ('rows_h', 'views_h', 'acts_h'))
-                for tr, it in zip(cached[2].trajectories_from(items, S, rows, views, acts, sc[k].copy()), items):
+                for tr, it in zip(batch.trajectories_from(items, S, rows, views, acts, sc[k].copy()), items):
                     tr['instr_encoding'] = it['instr_encoding']
                     agent.results.setdefault(tr['instr_id'], tr)
         return self._summary(self.instr_ids - set(order), M, model_scores), self.scores
 
-    def _scores_of_sweep(self, order, o64, o32, near):
-        """`self.scores` from a sweep's downloaded outputs: o64 [3 or 5, n_slots] (nav_error, oracle_error, length,
-        + shortest, dtw), o32 [3, n_slots] (steps, success, oracle_success), near [n_slots, longest] with
-        coverage_metrics; slot i belongs to instruction order[i]."""
-        M = len(order)
-        self.scores = defaultdict(list)
-        self.scores['nav_errors'] = o64[0, :M].tolist()
-        self.scores['oracle_errors'] = o64[1, :M].tolist()
-        self.scores['trajectory_steps'] = o32[0, :M].tolist()
-        self.scores['trajectory_lengths'] = o64[2, :M].tolist()
-        self.scores['success'] = (o32[1, :M] != 0).tolist()
-        self.scores['oracle_success'] = (o32[2, :M] != 0).tolist()
-        if self.path_metrics:                                 # spl, ndtw, sdtw per item by the one function of the host path
-            lists = [self.scores[name] for name in _LISTS]
-            goldn = [len(self.gt[int(iid.split('_')[0])]['path']) for iid in order]
-            full = [path_metrics_of(EvalResult(*six), sh, dtw, g, self.error_margin)
-                    for six, sh, dtw, g in zip(zip(*lists), o64[3, :M].tolist(), o64[4, :M].tolist(), goldn)]
-            for i, name in enumerate(_PATH_LISTS):
-                self.scores[name] = [r[6 + i] for r in full]
-            if self.coverage_metrics:                         # cls per item by the one function of the host path
-                lengths = self._gold_lengths()
-                full = [coverage_metrics_of(r, row[:g], lengths[int(iid.split('_')[0])], self.error_margin)
-                        for r, row, g, iid in zip(full, near[:M].tolist(), goldn, order)]
-                for i, name in enumerate(_COVERAGE_LISTS):
-                    self.scores[name] = [r[11 + i] for r in full]
+    @staticmethod
+    def _replay_rollout(agent, nav, items, k, B):
+        """Minibatch k of a sweep through the agent's captured test rollout: loaded through the k-th of the capture's
+        staging mirrors (no wait for one in the middle of a sweep) and replayed -- or captured, where nobody has yet, or
+        a weight moved since.  Returns (the rollout's state, its device batch)."""
+        from .nav import DeviceNavBatch
+        from .runtime import WeightsMoved
+        host = DeviceNavBatch.host_arrays_for(nav, items, agent.max_instruction_length, agent.reverse_instruction, True)
+        key = agent._test_graph_key(nav, agent._engine, B)
+        for attempt in (0, 1):
+            cached = agent.__dict__.setdefault('_test_graphs', {}).get(key)
+            if cached is None:
+                cached = agent._capture_test_rollout(nav, items, key, host)
+            else:
+                mirrors = cached[2].__dict__.setdefault('_sweep_mirrors', [])
+                while len(mirrors) <= k:
+                    mirrors.append(cached[2].new_mirror())
+                cached[2].load(items, host, mirror=mirrors[k])
+            try:
+                cached[0]()
+                break
+            except WeightsMoved:                              # (a weight moved since the capture: capture again)
+                if attempt:
+                    raise
+                agent._test_graphs.pop(key, None)
+        return cached[1], cached[2]
 
     # ---- a baseline agent's test() + score_results: one walk launch, one scoring launch
     def _score_table_agent(self, agent, keep_results=False):
-        """score_agent for agents.StopAgent / ShortestAgent / RandomAgent.  The environment is walked as BaseAgent.test
-        walks it (reset_epoch, reset() until an id repeats; `env.ix`, `random` and `np.random` end where test() leaves
-        them: RandomAgent draws for every row of every minibatch, repeated ids included), but nothing is launched per
-        minibatch: the first occurrences of the whole split are ONE sf_nav_walk launch, and behind it ONE
-        sf_eval_score_routes launch over the walk's own arrays (row_stride = B, row_first[b] = b, the walk's n_steps;
-        sf_eval_score_routes_coverage with coverage_metrics), then one host sync.  The classic six come from that
-        launch whatever the metric switches say.  An agent without a table on the device, distances that are not
-        there, or gold paths the kernel refuses: agent.test() + score_results (`fallbacks`)."""
+        """score_agent for agents.StopAgent / ShortestAgent / RandomAgent.  The epoch is walked on the host with
+        reset() (`np.random` too ends where test() leaves it: RandomAgent draws for every row of every minibatch,
+        repeated ids included), but nothing is launched per minibatch: the first occurrences of the whole split are ONE
+        sf_nav_walk launch, and behind it ONE `_launch_route_scoring` over the walk's own arrays and n_steps, then one
+        host sync.  The classic six come from that launch whatever the metric switches say.  An agent without a table
+        on the device, distances that are not there, or gold paths the kernel refuses: agent.test() + score_results
+        (`fallbacks`)."""
         from . import _lib                                   # (loaded: the agent's class reads its policy from it)
         nav = agent._device_table()
         gold = self._gold_table() if nav is not None and self.table.dev is not None else None
@@ -782,61 +801,38 @@ class Evaluation(object):
             agent.test()
             return self.score_results(agent.results)
         import torch
-        from .runtime import stream
-        env, t = agent.env, self.table
-        dev = t.dev.device
+        from .sweeps import epoch_minibatches
+        env, dev = agent.env, self.table.dev.device
         env.reset_epoch()
         agent.losses, agent.results = [], {}
-        walked, seen, looped = [], set(), False               # walked: (item, row, view, first action) per first occurrence
-        while not looped:
-            env.reset()
-            items = list(env.batch)
+        walked = []                                           # (item, row, view, first action) per first occurrence
+        for _, items, fresh in epoch_minibatches(env):
             rows, views = nav.start_states(items)
             first = agent._first_actions(nav, rows, views)
-            for b, it in enumerate(items):
-                if it['instr_id'] in seen:
-                    looped = True
-                else:
-                    seen.add(it['instr_id'])
-                    walked.append((it, rows[b], views[b], 0 if first is None else first[b]))
+            walked += [(it, rows[b], views[b], 0 if first is None else first[b])
+                       for b, it in enumerate(items) if fresh[b]]
         S, B, n = agent.walk_steps, len(walked), len(self.instr_ids)
-        order = []
-        i32 = np.zeros((4, B), np.int32)                      # gold_id, scan_base, m, slot
-        i64 = np.zeros((2, B), np.int64)                      # row_first, dist_off
-        i64[0] = np.arange(B)
-        for b, (it, _, _, _) in enumerate(walked):
-            scan, slot = it['scan'], -1
-            if it['instr_id'] in self.instr_ids:
-                slot = len(order)
+        items, order, slots = [x[0] for x in walked], [], []
+        for it in items:
+            slots.append(len(order) if it['instr_id'] in self.instr_ids else -1)
+            if slots[-1] >= 0:
                 order.append(it['instr_id'])
-            i32[:, b] = gold['ids'].get(it.get('path_id'), 0), self._local_rows(nav, scan), t.m[scan], slot
-            i64[1, b] = t.off[scan]
-        items = [w[0] for w in walked]
+        w = self._episode_words(nav, items, slots)
+        i32 = w[[0, 1, 2, 4]].astype(np.int32)                # gold_id, scan_base, m, slot
+        i64 = np.stack((np.arange(B), w[3]))                  # row_first, dist_off
         hop, base = nav.hop_rows(items) if agent.walk_policy == _lib.SF_WALK_SHORTEST else (None, None)
-        ptr_of = lambda x: x.data_ptr()                       # noqa: E731
         with torch.cuda.device(dev):
-            out = nav.walk(agent.walk_policy, S, np.array([w[1] for w in walked], np.int32),
-                           np.array([w[2] for w in walked], np.int32),
-                           None if first is None else np.array([w[3] for w in walked], np.int32), hop, base)
+            walk = nav.walk(agent.walk_policy, S, np.array([x[1] for x in walked], np.int32),
+                            np.array([x[2] for x in walked], np.int32),
+                            None if first is None else np.array([x[3] for x in walked], np.int32), hop, base)
             d32, d64 = torch.from_numpy(i32).to(dev), torch.from_numpy(i64).to(dev)
-            o64 = torch.empty(5, n, dtype=torch.float64, device=dev)
-            o32 = torch.zeros(3 * n + 1, dtype=torch.int32, device=dev)                   # (the last word: err)
-            e = _lib.EvalRoutes(S, B, n, B, len(gold['ids']), len(gold['node']), gold['longest'], 0, (S + 1) * B,
-                                ptr_of(out['row']), ptr_of(d64[0]), ptr_of(out['n_steps']), ptr_of(out['actions']),
-                                ptr_of(gold['dev'][0]), ptr_of(gold['dev'][1]), ptr_of(d32[0]), ptr_of(d32[1]),
-                                ptr_of(d32[2]), ptr_of(d64[1]), ptr_of(d32[3]), ptr_of(t.dev), self.error_margin,
-                                *[ptr_of(o64[k]) for k in range(5)], *[ptr_of(o32[k * n:]) for k in range(3)])
-            near = None
-            if self.coverage_metrics:
-                entry, ld = 'sf_eval_score_routes_coverage', gold['longest']
-                near = torch.empty(n, ld, dtype=torch.float64, device=dev)
-                _lib.call(entry, C.byref(e), C.c_void_p(ptr_of(near)), ld, C.c_void_p(ptr_of(o32[3 * n:])), stream())
-            else:
-                entry = 'sf_eval_score_routes'
-                _lib.call(entry, C.byref(e), C.c_void_p(ptr_of(o32[3 * n:])), stream())
-            down = [o64, o32, out['err']] + ([near] if near is not None else [])
-            if keep_results:
-                down += [out['row'], out['view'], out['n_steps']]
+            out = _Outputs(dev, n, near_ld=gold['longest'] if self.coverage_metrics else 0)
+            _, text = self._launch_route_scoring(out, 'walk', S=S, B=B, n_slots=n, row_stride=B, n_rows=(S + 1) * B,
+                                                 row=walk['row'], row_first=d64[0], n_steps=walk['n_steps'],
+                                                 actions=walk['actions'], gold_id=d32[0], scan_base=d32[1], m=d32[2],
+                                                 dist_off=d64[1], slot=d32[3])
+            out.download()
+            down = [walk['err']] + ([walk['row'], walk['view'], walk['n_steps']] if keep_results else [])
             got = [torch.empty(x.shape, dtype=x.dtype).pin_memory() for x in down]
             for h, x in zip(got, down):
                 h.copy_(x, non_blocking=True)
@@ -844,14 +840,12 @@ class Evaluation(object):
         self.sweeps += 1
         self.last_host_syncs = 1
         self.host_syncs += 1
-        if int(got[2][0]):
+        if int(got[0][0]):
             raise agent.walk_error()
-        if int(got[1][3 * n]):
-            raise RuntimeError('%s: a walk left its scan, or a slot its array' % entry)
-        self._scores_of_sweep(order, got[0].numpy(), got[1].numpy()[:3 * n].reshape(3, n),
-                              got[3].numpy() if near is not None else None)
+        out.check(text)
+        self._assemble([self.gt[int(iid.split('_')[0])] for iid in order], *out.host(), lists=True)
         if keep_results:
-            rows, views, steps = (x.numpy() for x in got[-3:])
+            rows, views, steps = (x.numpy() for x in got[1:])
             for r in nav.walk_results(items, rows, views, steps):
                 agent.results[r['instr_id']] = r
         return self._summary(self.instr_ids - set(order), len(order), []), self.scores

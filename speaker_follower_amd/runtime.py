@@ -344,6 +344,23 @@ def fault_views(device):
     return [_fault_view(ws) for (d, _), ws in _workspaces.items() if d == idx]
 
 
+def clear_faults(device):
+    """Zero the fault words of every workspace of `device`, in stream order: what a sweep issues before its first
+    launch (whatever an earlier pass left behind is not its own)."""
+    for w in fault_views(device):
+        w.zero_()
+
+
+def download_faults(device):
+    """Issue the asynchronous copy of `device`'s fault words on the current stream, behind what was launched there,
+    and return the pinned int32 tensor it fills: read it after the caller's own sync (`any(pinned.tolist())`), and
+    `take_fault` where a word is raised."""
+    views = fault_views(device)
+    pinned = torch.empty(len(views), dtype=torch.int32).pin_memory()
+    pinned.copy_(torch.cat(views) if len(views) > 1 else views[0], non_blocking=True)
+    return pinned
+
+
 def take_fault(device):
     """Reads AND clears the fault words of EVERY workspace of `device` (one per stream that ever ran library
     calls: the backward's side streams and captured rollouts have their own).  A host sync: callers put it where

@@ -27,7 +27,6 @@ Nothing here imports torch before a device is asked for, and nothing imports the
 import ctypes as C
 import json
 import math
-import random
 import re
 import string
 from collections import Counter
@@ -708,8 +707,8 @@ class SpeakerEvaluation(object):
 
     def score_speaker(self, agent, use_dropout=False, feedback='argmax', keep_results=False):
         """What `agent.test(use_dropout, feedback)` followed by `score_results(agent.results)` returns, as ONE sweep on
-        the device: the environment is drawn exactly as Seq2SeqSpeaker._test_as_a_sweep draws it (reset_epoch, reset()
-        until an id repeats -- `env.ix` and `random` end where test() leaves them), every minibatch is decoded through
+        the device: the environment is drawn exactly as Seq2SeqSpeaker._test_as_a_sweep draws it (reset_epoch, then
+        sweeps.epoch_minibatches -- `env.ix` and `random` end where test() leaves them), every minibatch is decoded through
         speaker.SpeakerSweep whatever `sweep_test_after` says, sf_bleu_counts is issued behind each minibatch's replay
         on the same stream and reads the words where the decode left them (a path's slot goes to the FIRST of its
         instruction ids the walk meets; ids already issued, ids outside `instr_ids` and skipped paths write nothing),
@@ -732,31 +731,26 @@ class SpeakerEvaluation(object):
         import torch
         from . import _lib, speaker as spk
         from .follower import EOS
-        from .runtime import stream, fault_views, take_fault
+        from .runtime import stream, clear_faults, download_faults, take_fault
+        from .sweeps import epoch_minibatches, snapshot, restore
         env, dev = agent.env, store.device
         agent.feedback = feedback
         for m in (agent.encoder, agent.decoder):
             m.eval()
         agent.beam_size = 1
-        walk0 = (list(env.data), random.getstate())          # (a faulting sweep is undone: test() then walks from here)
+        walk0 = snapshot(env)                                # (a faulting sweep is undone: test() then walks from here)
         env.reset_epoch()
         agent.losses, agent.results = [], {}
         B, S = env.batch_size, agent.instruction_len
-        drawn, ids, looped = [], set(), False
+        drawn = []
         first_of = {}                                        # path_id -> (minibatch, column) of its first result
-        while not looped:                                    # (speaker.py:404-413 over the items themselves)
-            env.reset()
-            items = list(env.batch)
+        for k, items, fresh in epoch_minibatches(env):       # (speaker.py:404-413 over the items themselves)
             for b, it in enumerate(items):
-                iid = it['instr_id']
-                if iid in ids:
-                    looped = True
-                elif iid in self.instr_ids:
-                    first_of.setdefault(int(iid.split('_')[0]), (len(drawn), b))
-                ids.add(iid)
+                if fresh[b] and it['instr_id'] in self.instr_ids:
+                    first_of.setdefault(int(it['instr_id'].split('_')[0]), (k, b))
             drawn.append(items)
         agent._test_minibatches = agent.__dict__.get('_test_minibatches', 0) + len(drawn)
-        missing = self.instr_ids - ids
+        missing = self.instr_ids - {it['instr_id'] for items in drawn for it in items}
         assert len(missing) == 0, 'Missing %d of %d instruction ids from %s' % (
             len(missing), len(self.instr_ids), ",".join(self.splits))
         K = len(drawn)
@@ -778,8 +772,7 @@ class SpeakerEvaluation(object):
             if self.caption_metrics:
                 table['cap_i'].zero_()
                 table['cap_f'].zero_()
-            for w in fault_views(dev):                       # (whatever an earlier pass left behind is not ours)
-                w.zero_()
+            clear_faults(dev)
             ptr_of = lambda x: x.data_ptr()                  # noqa: E731
 
             def count(k, st):
@@ -815,9 +808,7 @@ class SpeakerEvaluation(object):
                 if self.caption_metrics:
                     table['cap_i_h'].copy_(table['cap_i'], non_blocking=True)
                     table['cap_f_h'].copy_(table['cap_f'], non_blocking=True)
-                faults = fault_views(dev)
-                fpin = torch.empty(len(faults), dtype=torch.int32).pin_memory()
-                fpin.copy_(torch.cat(faults) if len(faults) > 1 else faults[0], non_blocking=True)
+                fpin = download_faults(dev)
             tail.synchronize()                               # the one host sync of the sweep
         self.sweeps += 1
         out = table['out_h'].numpy()
@@ -825,8 +816,7 @@ class SpeakerEvaluation(object):
             take_fault(dev)                                  # (read and cleared: test() starts clean)
             self.last_host_syncs = 2
             self.host_syncs += 2
-            env.data[:] = walk0[0]
-            random.setstate(walk0[1])
+            restore(env, walk0)
             return self._by_test(agent, use_dropout, feedback)
         self.last_host_syncs = 1
         self.host_syncs += 1
