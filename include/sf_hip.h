@@ -1361,6 +1361,58 @@ typedef struct sf_nav_routes_io {
     int64_t out_bytes;
 } sf_nav_routes_io;
 int sf_nav_routes(const sf_nav_table* nav, const sf_nav_routes_io* io, int32_t* err, sf_stream stream);
+/* sf_nav_follower_batches (csrc/sf_nav.hip; env.py:601-626, follower.py:75-105), additive to ABI 10: M FOLLOWER
+ * minibatches of B routes each, written in ONE launch in the layout a captured training iteration reads
+ * (nav.DeviceNavBatch.pack_layout) -- per minibatch what env._next_minibatch(sort=True) followed by
+ * DeviceNavBatch.host_arrays_for(..., fixed=True) forms on the host.  The routes are sf_nav_routes' (row0, view0,
+ * hop_all, hop_off, hop_base, hop_rows over N routes; instr_tokens / instr_off, both NULL: every instruction is empty).
+ * Slot j (0 <= j < M * B) holds route r = order[j]; minibatch i draws slots i*B .. i*B + B - 1 and its block starts at
+ * byte mb_off[i] of `out`.
+ *   Sort.  raw[j] = instr_off[r + 1] - instr_off[r], the route's token count (NOT cut to Lmax).  Slot j goes to column
+ *   #{j' : raw[j'] > raw[j]} + #{j' < j : raw[j'] == raw[j]} of its minibatch: descending, equal lengths in draw order
+ *   (Python's stable sorted(..., reverse=True)).
+ *   The block has seven sections, each starting on a 64-byte boundary, in this order (the gaps are not written); column
+ *   c holds route r:
+ *     seq      int64 [B, Lmax]  the tokens (last first when `reverse`), then `eos`, cut to Lmax, `pad` behind
+ *     mask     uint8 [B, Lmax]  1 where the stored id equals `pad`, over the full width
+ *     lengths  int32 [B]        min(raw + 1, Lmax)
+ *     rows     int32 [B]        row0[r]
+ *     views    int32 [B]        view0[r]
+ *     hop      int32 [B, ld]    hop_all[hop_off[r] + k] for k < min(hop_rows[r], ld), 0 behind
+ *     base     int32 [B]        hop_base[r]
+ *   col_route / col_len (int32 [M, B], both or neither): the route index in column c of minibatch i, and `lengths`.
+ *   Every element of every section and of col_route / col_len is written by every launch.
+ *   Per slot, each of these raises err[0] (only ever raised) and the column holds an empty instruction (seq = eos then
+ *   pad, length 1; the slot sorts with raw = 0): a route index outside [0, N) -- rows, views, base and hop are then 0 and
+ *   col_route holds the index as given; view0[r] outside [0, V); hop_rows[r] > ld; a last token equal to `eos` (the
+ *   host path asserts on it).
+ *   mb_off is a HOST array, which the entry checks; mb_off_dev holds the same values on the device, which the kernel
+ *   reads (and checks again: a minibatch whose device value breaks the rules raises err[0] and is not written).
+ *   SF_ERR_ARG, with nothing launched or written: NULL io / err, row0, view0, hop_all, hop_off, hop_base, hop_rows,
+ *   order, mb_off, mb_off_dev, out; N < 1, V < 1, B < 1, Lmax < 1, ld < 1, M < 1; only one of instr_tokens / instr_off,
+ *   only one of col_route / col_len; `out` not 8-byte aligned (seq is stored as int64 words); an mb_off[i] that is
+ *   negative or not a multiple of 64, or a block that would end beyond out_bytes.  SF_ERR_UNSUPPORTED for B > sf_nav_follower_batches_max_b() (1 024).
+ *   One workgroup per minibatch: raw lengths in LDS, a barrier, the slot of every column in LDS, a barrier, then one
+ *   wavefront per column with its lanes along Lmax and along ld.  No atomics. */
+typedef struct sf_nav_follower_io {
+    int32_t N, V;                  /* routes of the set; views of a row (view0 must lie in [0, V)) */
+    int32_t B, Lmax, ld, M;        /* columns of a minibatch, instruction columns, hop columns, minibatches */
+    int32_t pad, eos, reverse;     /* the two token ids seq is completed with; != 0: last token first */
+    const int32_t *row0, *view0;   /* [N] start states */
+    const int32_t* hop_all;        /* the shared next-hop table */
+    const int64_t* hop_off;        /* [N] */
+    const int32_t *hop_base, *hop_rows; /* [N] */
+    const int64_t* instr_tokens;   /* flat, or NULL */
+    const int64_t* instr_off;      /* [N+1], or NULL */
+    const int32_t* order;          /* [M * B] route index of every slot */
+    const int64_t* mb_off;         /* HOST [M] */
+    const int64_t* mb_off_dev;     /* [M] */
+    uint8_t* out;
+    int64_t out_bytes;
+    int32_t *col_route, *col_len;  /* [M, B] or NULL */
+} sf_nav_follower_io;
+int sf_nav_follower_batches(const sf_nav_follower_io* io, int32_t* err, sf_stream stream);
+int sf_nav_follower_batches_max_b(void);
 
 /* The follower's beam selection for one decode step (follower.py:606-690), all instances at once, no host round trip:
  * what search.DeviceFollowerBeam issues after sf_attn_decoder_fwd + sf_logprob_topk (n_valid = a_num) in its device

@@ -45,6 +45,7 @@ _SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'uint32_t': C.c_uint32, 'int64
             'float': C.c_float, 'double': C.c_double}
 # the Python class of struct sf_some_name is SomeName, except for
 _NAMES = {'sf_nav_table': 'NavTableS', 'sf_nav_io': 'NavIO', 'sf_nav_routes_io': 'NavRoutesIO',
+          'sf_nav_follower_io': 'NavFollowerIO',
           'sf_decoder_gtape': 'DecoderGTape', 'sf_spk_decoder_gtape': 'SpkDecoderGTape'}
 # "Gradient structs mirror the weight structs member for member": callers hand a gradient parameter or member the weight
 # class filled with gradient pointers.  Held to the header below: same size, and field by field the same offset and size.

@@ -773,22 +773,34 @@ class Seq2SeqAgent(BaseAgent):
     def _graph_trainable(self, encoder_optimizer, decoder_optimizer):
         """Whole iterations can be replayed when the environment is walked on the device, both optimizers keep their
         state in flat buffers with device-side step counters (optim.FusedAdam) and nothing leaves the process."""
+        return self._why_not_graph_trainable(encoder_optimizer, decoder_optimizer) is None
+
+    def _why_not_graph_trainable(self, encoder_optimizer, decoder_optimizer):
+        """None where `_graph_trainable` holds, else the first condition that fails, in words."""
         from .optim import FusedAdam
-        if not self.train_graph or '+' in self.feedback or self.beam_size != 1:
-            return False
+        if not self.train_graph:
+            return 'train_graph is off'
+        if '+' in self.feedback:
+            return "'+' feedback"
+        if self.beam_size != 1:
+            return 'a beam'
         for o in (encoder_optimizer, decoder_optimizer):
             if not (isinstance(o, FusedAdam) or (self.adopt_torch_adam and FusedAdam.adoptable(o))):
-                return False
+                return 'an optimizer that is neither an optim.FusedAdam nor a torch Adam it can adopt'
         if self._device_table() is None or self._engine is None:
-            return False
+            return 'no navigation table on the device'
         eng = self._engine
+        alone = eng.group is None and eng.grad_sync is None
         # (a process group: iterations replay as SEGMENTS cut at the collective points, FollowerEngine._capture_training_dp;
         # that needs the gradient buckets the all-reduces work on)
-        dp_ok = (eng.group is None and eng.grad_sync is None) or (eng.group is not None and eng.grad_sync is not None)
+        if not (alone or (eng.group is not None and eng.grad_sync is not None)):
+            return 'a process group without its gradient buckets'
         # (a bidirectional encoder: single process only -- its data-parallel iteration keeps the eager loop)
-        one_dir = getattr(self.encoder, 'num_directions', 1) == 1
-        return (dp_ok and (one_dir or (eng.group is None and eng.grad_sync is None))
-                and getattr(self.encoder, 'persistent', True))
+        if getattr(self.encoder, 'num_directions', 1) != 1 and not alone:
+            return 'a bidirectional encoder under a process group'
+        if not getattr(self.encoder, 'persistent', True):
+            return 'an encoder without its persistent launch'
+        return None
 
     def _train_on_graph(self, encoder_optimizer, decoder_optimizer, n_iters):
         """follower.py:1001-1020 with every iteration after the first ONE graph replay: the next minibatch is written
@@ -828,13 +840,143 @@ class Seq2SeqAgent(BaseAgent):
         hit[1].load_torch_state(opt)
         return hit[1]
 
+    def _train_graph_key(self, opts, table):
+        """What tells the captured training iterations apart (a captured iteration holds the optimizers'
+        hyper-parameters as kernel arguments: a changed learning rate is a new graph)."""
+        hyper = tuple((g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']) for o in opts for g in o.param_groups)
+        return (id(opts[0]), id(opts[1]), self.feedback, id(table), self.episode_len, hyper)
+
+    def _train_pins_for(self, n_words):
+        """Two pinned (loss, fault words) pairs for the pipelined replays (one fault word per workspace; a workspace
+        created later -- a side stream of the per-step fallback -- makes the list longer: the pairs are re-made to match)."""
+        pins = self.__dict__.get('_train_pins')
+        if pins is None or pins[0][1].numel() != n_words:
+            pins = self._train_pins = [(torch.empty(1, dtype=torch.float32).pin_memory(),
+                                        torch.empty(n_words, dtype=torch.int32).pin_memory()) for _ in range(2)]
+        return pins
+
+    def train_on_routes(self, routes, encoder_optimizer, decoder_optimizer, n_iters, feedback='teacher', batch_size=100,
+                        order=None, seed=0):
+        """`train` over a routes.RouteSet instead of the environment (train.py --use_pretraining on an augmentation
+        split, with no file and no environment object in between): the same replayed iterations, their minibatches
+        drawn from `routes.pack_follower(batch_size, ...)` -- packed on the device by sf_nav_follower_batches, ONE
+        device-to-device copy per iteration (nav.DeviceNavBatch.load_packed).  order: the route index of every slot,
+        n_iters * batch_size of them (default `routes.epoch_order(batch_size, n_iters, seed)`); a minibatch is sorted by
+        instruction length as env.reset(sort=True) sorts it.  The captured graph is `train`'s own where optimizers,
+        feedback, table and batch size match.  The minibatches are packed `route_window` (default routes.PACK_CHUNK = 256)
+        at a time, one launch and one host sync per window, at most two windows alive: 2 x 256 x 213 KB at B = 100, 80
+        words, however long the call.  Only what can be replayed in ONE process is supported: NotImplementedError names
+        what stands in the way (a process group among them: data-parallel training on routes is not built)."""
+        assert all(f in self.feedback_options for f in feedback.split('+'))
+        self.feedback = feedback
+        self.encoder.train()
+        self.decoder.train()
+        self.losses = []
+        # (data-parallel training on routes is not built: the pipelined loop below decides about a fault from this
+        # process's own words, and every rank would draw the same order -- refused whatever else holds)
+        why = self._why_not_graph_trainable(encoder_optimizer, decoder_optimizer)
+        eng = self._engine
+        if eng is not None and (eng.group is not None or eng.grad_sync is not None):
+            why = 'a process group'
+        if why is not None:
+            raise NotImplementedError('train_on_routes replays captured iterations in one process only: ' + why)
+        table, eng, dev = self._device_table(), self._engine, self._device()
+        if routes.nav is not table:
+            raise ValueError("train_on_routes: the routes' navigation table is not the agent's device table")
+        B = int(batch_size)
+        if order is None:
+            order = routes.epoch_order(B, n_iters, seed)
+        order = np.ascontiguousarray(order, np.int32).reshape(-1)
+        if len(order) != n_iters * B:
+            raise ValueError('train_on_routes: an order of %d slots for %d iterations of %d' % (len(order), n_iters, B))
+        if n_iters < 1:
+            return
+        # (packed a window of minibatches at a time: the blocks of a whole call would be n_iters x 213 KB at B = 100)
+        blocks = routes.follower_windows(B, self.max_instruction_length, order, reverse=self.reverse_instruction,
+                                         window=self.route_window)
+        given = (encoder_optimizer, decoder_optimizer)
+        opts = tuple(self._fused_for(o) for o in given)
+        try:
+            return self._replay_route_blocks(opts, n_iters, routes, order, blocks, table, eng, dev)
+        finally:
+            for o, f in zip(given, opts):             # the reference's own optimizer objects get their state back
+                if f is not o:
+                    f.store_torch_state(o)
+
+    route_window = None          # train_on_routes: minibatches packed per pack_follower call (None: routes.PACK_CHUNK)
+
+    def _replay_route_blocks(self, opts, n_iters, routes, order, blocks, table, eng, dev):
+        """`_replay_iterations` / `_replay_pipelined` over routes.FollowerWindows: iteration i is load_packed(*blocks.at(i))
+        and a replay, replay i + 1 queued before the loss of replay i is read.  Where no graph exists yet, iteration 0
+        captures it over a batch built from the host form of the same minibatch (RouteSet.follower_minibatch_host)."""
+        from .nav import DeviceNavBatch
+        key = self._train_graph_key(opts, table)
+        cached = self.__dict__.get('_train_graph_state')
+        take_fault(dev)                                       # (whatever an earlier pass left behind is not ours)
+        if cached is not None and (cached[0] != key or cached[2].batch_size != blocks.B):
+            cached = None
+        issued = 0
+        if cached is None:
+            before = [o.host_steps() for o in opts]
+            where = (eng.site_next, eng.iteration)
+            host = routes.follower_minibatch_host(order[:blocks.B], blocks.Lmax, reverse=self.reverse_instruction)
+            batch = DeviceNavBatch(table, host['route'].tolist(), self.episode_len, max_length=self.max_instruction_length,
+                                   reverse=self.reverse_instruction, fixed_shapes=True, host=host)
+            for o in opts:
+                o.guard_faults = True
+            tg = eng.capture_training(batch, self.episode_len, self.feedback, optimizers=opts, zero=eng.grad_sync)
+            cached = self._train_graph_state = (key, tg, batch)
+            st = tg.first                                     # (the capture ran this iteration eagerly)
+            loss = float(st.loss_buf)
+            bits = fault_bits(dev, eng.group)
+            if bits:
+                batch.load_packed(*blocks.at(0))
+                st = self._reissue_training_iteration(opts, eng, dev, batch, before, where, bits)
+                loss = float(st.loss_buf)
+            self.loss = st.loss_buf.reshape(())
+            self.losses.append(loss)
+            issued = 1
+            if n_iters == 1:
+                return
+        _, tg, batch = cached
+        flight = None                  # the iteration whose loss has not been read: (slot, event, state before it, block, pins)
+        while issued < n_iters or flight is not None:
+            cur = None
+            if issued < n_iters:
+                before = ([o.host_steps() for o in opts], eng.site_next, eng.iteration)
+                batch.load_packed(*blocks.at(issued))
+                st = tg.replay()
+                slot = issued & 1
+                views = fault_views(dev)
+                if flight is not None and flight[4][0][1].numel() != len(views):
+                    flight[1].synchronize()                   # (the pair in flight is read before it is replaced)
+                pins = self._train_pins_for(len(views))
+                pins[slot][0].copy_(st.loss_buf.reshape(1), non_blocking=True)
+                pins[slot][1].copy_(torch.cat(views) if len(views) > 1 else views[0], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                cur = (slot, ev, before, issued, pins)
+                issued += 1
+            if flight is not None:
+                slot, ev, before_f, block_f, pins = flight
+                ev.synchronize()
+                if any(pins[slot][1].tolist()):
+                    torch.cuda.synchronize(dev)               # (the replay queued behind it did nothing either)
+                    bits = take_fault(dev)
+                    batch.load_packed(*blocks.at(block_f))
+                    st2 = self._reissue_training_iteration(opts, eng, dev, batch, before_f[0], before_f[1:], bits)
+                    self.losses.append(float(st2.loss_buf))
+                    if cur is not None:                       # the one queued behind it is issued again
+                        issued -= 1
+                        cur = None
+                else:
+                    self.losses.append(float(pins[slot][0]))
+            flight = cur
+        self.loss = tg.state.loss_buf.reshape(())
+
     def _replay_iterations(self, opts, n_iters, table, eng, dev):
         from .nav import DeviceNavBatch
-        encoder_optimizer, decoder_optimizer = opts
-        # (a captured iteration holds the optimizers' hyper-parameters as kernel arguments: a changed learning rate is a
-        # new graph)
-        hyper = tuple((g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']) for o in opts for g in o.param_groups)
-        key = (id(encoder_optimizer), id(decoder_optimizer), self.feedback, id(table), self.episode_len, hyper)
+        key = self._train_graph_key(opts, table)
         cached = self.__dict__.get('_train_graph_state')
         take_fault(dev)                                       # (whatever an earlier pass left behind is not ours)
         ahead = None            # the NEXT minibatch and its host arrays, formed while the device ran this iteration
@@ -916,14 +1058,7 @@ class Seq2SeqAgent(BaseAgent):
         same sites, same steps: losses and weights of the serial loop (tests/test_gpu_nav.py)."""
         import collections
         _, tg, batch = cached
-        def pins_for(n_words):
-            # (one fault word per workspace; a workspace created later -- a side stream of the per-step fallback --
-            # makes the list longer: the pinned pair is re-made to match)
-            pins = self.__dict__.get('_train_pins')
-            if pins is None or pins[0][1].numel() != n_words:
-                pins = self._train_pins = [(torch.empty(1, dtype=torch.float32).pin_memory(),
-                                            torch.empty(n_words, dtype=torch.int32).pin_memory()) for _ in range(2)]
-            return pins
+        pins_for = self._train_pins_for
         todo = collections.deque()     # minibatches drawn and not issued yet: (items, host arrays or None)
         drawn = issued = 0
         if first is not None:          # (what the serial loop had already drawn for its next iteration)

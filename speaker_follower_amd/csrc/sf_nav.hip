@@ -300,7 +300,129 @@ __global__ __launch_bounds__(WALKS_PER_BLOCK* WAVE) void nav_routes_kernel(sf_na
     }
 }
 
+// ---- sf_nav_follower_batches: the follower's minibatches of a route set, sorted and padded as the host path does -----
+
+constexpr int FOLLOWER_MAX_B = 1024;   // raw lengths and column slots in LDS: 2 x 4 KB
+constexpr int FOLLOWER_THREADS = 256;
+
+__host__ __device__ inline int64_t align64(int64_t x) { return (x + 63) & ~(int64_t)63; }
+
+// nav.DeviceNavBatch.pack_layout(B, Lmax, ld): the byte offset of every section of a block, and the block's size
+struct FollowerLayout {
+    int64_t mask, lengths, rows, views, hop, base, bytes;    // (seq stands at 0)
+};
+__host__ __device__ inline FollowerLayout follower_layout(int B, int Lmax, int ld) {
+    FollowerLayout l;
+    l.mask = align64((int64_t)B * Lmax * 8);
+    l.lengths = align64(l.mask + (int64_t)B * Lmax);
+    l.rows = align64(l.lengths + (int64_t)B * 4);
+    l.views = align64(l.rows + (int64_t)B * 4);
+    l.hop = align64(l.views + (int64_t)B * 4);
+    l.base = align64(l.hop + (int64_t)B * ld * 4);
+    l.bytes = align64(l.base + (int64_t)B * 4);
+    return l;
+}
+
+// what slot j of the launch holds: its route, whether the index is one, its token count and whether the column is
+// written as an empty instruction
+struct FollowerSlot {
+    int r, raw;
+    int64_t first;
+    bool known, bad;
+};
+__device__ __forceinline__ FollowerSlot follower_slot(const sf_nav_follower_io& p, int64_t j) {
+    FollowerSlot s;
+    s.r = p.order[j];
+    s.known = (unsigned)s.r < (unsigned)p.N;
+    s.raw = 0;
+    s.first = 0;
+    s.bad = !s.known;
+    if (s.known) {
+        s.bad = (unsigned)p.view0[s.r] >= (unsigned)p.V || p.hop_rows[s.r] > p.ld;
+        if (p.instr_tokens) {
+            s.first = p.instr_off[s.r];
+            int64_t len = p.instr_off[s.r + 1] - s.first;
+            len = len < 0 ? 0 : (len > 0x7ffffffe ? 0x7ffffffe : len);
+            s.raw = (int)len;
+            if (len > 0 && p.instr_tokens[s.first + len - 1] == (int64_t)p.eos) s.bad = true;
+        }
+    }
+    if (s.bad) s.raw = 0;
+    return s;
+}
+
+__global__ __launch_bounds__(FOLLOWER_THREADS) void nav_follower_batches_kernel(sf_nav_follower_io p,
+                                                                                int32_t* __restrict__ err) {
+    __shared__ int raw[FOLLOWER_MAX_B];
+    __shared__ int slot_of[FOLLOWER_MAX_B];                  // column -> slot of the minibatch
+    const int i = blockIdx.x, B = p.B, L = p.Lmax, ld = p.ld;
+    const int64_t off = p.mb_off_dev[i];
+    const FollowerLayout l = follower_layout(B, L, ld);
+    if (off < 0 || (off & 63) || off > p.out_bytes || l.bytes > p.out_bytes - off) {   // (block-uniform)
+        if (threadIdx.x == 0) *err = 1;                      // not what the entry checked: the minibatch is left alone
+        return;
+    }
+    const int64_t slot0 = (int64_t)i * B;
+    for (int j = threadIdx.x; j < B; j += FOLLOWER_THREADS) {
+        const FollowerSlot s = follower_slot(p, slot0 + j);
+        if (s.bad) *err = 1;
+        raw[j] = s.raw;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < B; j += FOLLOWER_THREADS) {
+        const int mine = raw[j];
+        int col = 0;
+        for (int q = 0; q < B; ++q) col += raw[q] > mine || (raw[q] == mine && q < j);
+        slot_of[col] = j;                                    // (the columns are a permutation of the slots)
+    }
+    __syncthreads();
+    uint8_t* blk = p.out + off;
+    int64_t* seq = (int64_t*)blk;
+    uint8_t* mask = blk + l.mask;
+    int32_t* lengths = (int32_t*)(blk + l.lengths);
+    int32_t* rows = (int32_t*)(blk + l.rows);
+    int32_t* views = (int32_t*)(blk + l.views);
+    int32_t* hop = (int32_t*)(blk + l.hop);
+    int32_t* base = (int32_t*)(blk + l.base);
+    const int lane = threadIdx.x & (WAVE - 1);
+    for (int c = threadIdx.x >> 6; c < B; c += FOLLOWER_THREADS / WAVE) {   // a wavefront per column
+        const FollowerSlot s = follower_slot(p, slot0 + slot_of[c]);
+        const int len = s.raw;
+        const int kept = len + 1 < L ? len + 1 : L;
+        for (int k = lane; k < L; k += WAVE) {
+            int64_t w = p.pad;
+            if (k < len) w = p.instr_tokens[s.first + (p.reverse ? len - 1 - k : k)];
+            else if (k == len) w = p.eos;
+            seq[(int64_t)c * L + k] = w;
+            mask[(int64_t)c * L + k] = w == (int64_t)p.pad;
+        }
+        int m = 0;
+        const int32_t* from = p.hop_all;
+        if (s.known) {
+            m = p.hop_rows[s.r];
+            m = m > ld ? ld : m;
+            from += p.hop_off[s.r];
+        }
+        for (int k = lane; k < ld; k += WAVE) hop[(int64_t)c * ld + k] = k < m ? from[k] : 0;
+        if (lane == 0) {
+            lengths[c] = kept;
+            rows[c] = s.known ? p.row0[s.r] : 0;
+            views[c] = s.known ? p.view0[s.r] : 0;
+            base[c] = s.known ? p.hop_base[s.r] : 0;
+            if (p.col_route) {
+                p.col_route[slot0 + c] = s.r;
+                p.col_len[slot0 + c] = kept;
+            }
+        }
+    }
+}
+
 }  // namespace
+
+int nav_follower_batches(const sf_nav_follower_io* io, int32_t* err, hipStream_t st) {
+    SF_LAUNCH(nav_follower_batches_kernel, dim3(io->M), dim3(FOLLOWER_THREADS), 0, st, *io, err);
+    return launch_status();
+}
 
 int nav_routes(const sf_nav_table* nav, const sf_nav_routes_io* io, int32_t* err, hipStream_t st) {
     SF_LAUNCH(nav_routes_kernel, dim3(ceil_div(io->n_slots, WALKS_PER_BLOCK)), dim3(WALKS_PER_BLOCK * WAVE), 0, st, *nav, *io,
@@ -365,6 +487,24 @@ extern "C" int sf_nav_routes(const sf_nav_table* nav, const sf_nav_routes_io* io
     }
     if (nav->A > 64) return SF_ERR_UNSUPPORTED;              // one lane per candidate slot
     return sf::nav_routes(nav, io, err, (hipStream_t)stream);
+}
+
+extern "C" int sf_nav_follower_batches_max_b(void) { return sf::FOLLOWER_MAX_B; }
+
+extern "C" int sf_nav_follower_batches(const sf_nav_follower_io* io, int32_t* err, sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(io && err && io->row0 && io->view0 && io->hop_all && io->hop_off && io->hop_base && io->hop_rows &&
+                 io->order && io->mb_off && io->mb_off_dev && io->out);
+    SF_CHECK_ARG(io->N >= 1 && io->V >= 1 && io->B >= 1 && io->Lmax >= 1 && io->ld >= 1 && io->M >= 1);
+    SF_CHECK_ARG(!io->instr_tokens == !io->instr_off && !io->col_route == !io->col_len);
+    SF_CHECK_ARG(((uintptr_t)io->out & 7) == 0);                  // (seq is stored as int64 words)
+    const int64_t bytes = sf::follower_layout(io->B, io->Lmax, io->ld).bytes;
+    for (int i = 0; i < io->M; ++i) {
+        const int64_t off = io->mb_off[i];
+        SF_CHECK_ARG(off >= 0 && !(off & 63) && off <= io->out_bytes && bytes <= io->out_bytes - off);
+    }
+    if (io->B > sf::FOLLOWER_MAX_B) return SF_ERR_UNSUPPORTED;    // raw lengths and column slots live in LDS
+    return sf::nav_follower_batches(io, err, (hipStream_t)stream);
 }
 
 extern "C" int sf_nav_step(const sf_nav_table* nav, int B, const int32_t* row, const int32_t* view,

@@ -17,7 +17,9 @@ function of the state (scan, viewpoint, view index):
                          teacher, the random baseline: follower.py:197-259) as ONE launch, through
                          `NavTable.walk`; it leaves a rollout's row / view / action arrays;
   * `sf_nav_routes`   -- the teacher's routes of a whole split over ONE shared next-hop table
-                         (`NavTable.all_hops`), as lengths or as the speaker's packed minibatches (routes.py).
+                         (`NavTable.all_hops`), as lengths or as the speaker's packed minibatches (routes.py);
+  * `sf_nav_follower_batches` -- the FOLLOWER's minibatches of such a split, sorted and padded in the layout a captured
+                         training iteration reads (`DeviceNavBatch.pack_layout`, `load_packed`, `FollowerBlocks`).
 
 `FollowerEngine.rollout(DeviceNavBatch, ...)` then runs encoder + S decode steps with ONE host sync at
 the end; `trajectories()` turns the recorded states into the reference's result format.
@@ -289,14 +291,27 @@ class DeviceNavBatch:
     _LOADED = (('seq', 'seq'), ('mask', 'mask'), ('lengths_dev', 'lengths'), ('row0_state', 'rows'), ('view0_state', 'views'),
                ('goal_hop', 'hop'), ('hop_base', 'base'))
 
+    @staticmethod
+    def pack_layout(B, Lmax, ld):
+        """The packed minibatch of a fixed-shape batch: section name -> (byte offset, bytes), and 'bytes' -- seq int64
+        [B, Lmax], mask uint8 [B, Lmax], lengths, rows, views int32 [B], hop int32 [B, ld], base int32 [B], in `_LOADED`
+        order, each on a 64-byte boundary.  What `_pack_for_load` lays out and sf_nav_follower_batches writes."""
+        lay, total = {}, 0
+        for key, n in (('seq', B * Lmax * 8), ('mask', B * Lmax), ('lengths', B * 4), ('rows', B * 4), ('views', B * 4),
+                       ('hop', B * ld * 4), ('base', B * 4)):
+            lay[key] = (total, n)
+            total += (n + 63) & ~63
+        lay['bytes'] = total
+        return lay
+
     def _pack_for_load(self):
         """The seven tensors `load` rewrites become views of ONE device buffer with a pinned host mirror: a minibatch is
         one asynchronous H2D copy instead of seven pageable ones (0.2 ms of the training loop's host time)."""
-        offs, total = {}, 0
-        for attr, _ in self._LOADED:
+        lay = self.pack_layout(self.seq.shape[0], self.seq.shape[1], self.ld_hop)
+        offs, total = {attr: lay[key][0] for attr, key in self._LOADED}, lay['bytes']
+        for attr, key in self._LOADED:
             t = getattr(self, attr)
-            offs[attr] = total
-            total += (t.numel() * t.element_size() + 63) & ~63
+            assert t.numel() * t.element_size() == lay[key][1], key
         dev_buf = torch.empty(total, dtype=torch.uint8, device=self.seq.device)
         self._pack_host = torch.empty(total, dtype=torch.uint8).pin_memory()
         self._pack_np = {}
@@ -381,6 +396,19 @@ class DeviceNavBatch:
         for attr, key in self._LOADED:
             getattr(self, attr).copy_(torch.from_numpy(h[key]))
 
+    def load_packed(self, blocks, i):
+        """Minibatch i of `blocks` (FollowerBlocks: routes.RouteSet.pack_follower wrote it on the device) INTO the same
+        device tensors (fixed_shapes only): ONE device-to-device copy on the current stream -- no host arrays, no pinned
+        mirror, nothing waited for.  `lengths` are the block's col_len, `items` the route indices of its columns."""
+        if not self.fixed or getattr(self, '_pack_dev', None) is None:
+            raise ValueError('DeviceNavBatch.load_packed needs fixed_shapes=True on a GPU')
+        have = (self.batch_size, self.seq.shape[1], self.ld_hop)
+        if (blocks.B, blocks.Lmax, blocks.ld) != have:
+            raise ValueError('DeviceNavBatch.load_packed: blocks of (B, Lmax, ld) = %r for a batch of %r'
+                             % ((blocks.B, blocks.Lmax, blocks.ld), have))
+        self._pack_dev.copy_(blocks.block(i), non_blocking=True)
+        self.items, self.lengths = blocks.col_route[i].tolist(), blocks.col_len[i].tolist()
+
     @property
     def batch_size(self):
         return self.seq.shape[0]
@@ -464,6 +492,26 @@ class _WalkResult(LazyDict):
 
     nav_rows = _Trajectory.nav_rows
     _make = _Trajectory._make
+
+
+class FollowerBlocks:
+    """Follower minibatches that are already packed ON THE DEVICE (routes.RouteSet.pack_follower: sf_nav_follower_batches
+    wrote them): `blocks` = per minibatch (uint8 device buffer, byte offset of its block), each block in
+    DeviceNavBatch.pack_layout(B, Lmax, ld) order.  `col_route` / `col_len` (host, int32 [M, B]): the route index and
+    the instruction length of every column; `keep` whatever must outlive the launches that read it."""
+
+    def __init__(self, blocks, B, Lmax, ld, col_route, col_len, keep=None):
+        self.blocks, self.B, self.Lmax, self.ld = blocks, B, Lmax, ld
+        self.col_route, self.col_len, self.keep = col_route, col_len, keep
+        self.bytes = DeviceNavBatch.pack_layout(B, Lmax, ld)['bytes']
+
+    def __len__(self):
+        return len(self.blocks)
+
+    def block(self, i):
+        """Minibatch i as a uint8 device tensor (a view)."""
+        buf, off = self.blocks[i]
+        return buf[off:off + self.bytes]
 
 
 def table_for(env, store):

@@ -17,7 +17,14 @@ N of them as arrays -- start row and view, goal row, and where the goal's row of
 on the device: one sf_nav_routes launch for the lengths, one host sync, one launch per chunk of minibatches for the
 blocks (csrc/sf_nav.hip; the layout is speaker.packed_layout's).  `speaker.SpeakerSweep.issue` takes the result in
 place of host batches; `Seq2SeqSpeaker.augment(routes)` decodes it and `.replaced_items(results)` is the file
-data_augmentation_from_speaker.py writes."""
+data_augmentation_from_speaker.py writes.
+
+The follower's side (train.py --use_pretraining on the generated split): `.with_generated(results)` is the set with the
+speaker's words as its instructions, `.pack_follower(B, Lmax, order)` its follower minibatches -- sorted by instruction
+length, padded and laid out as nav.DeviceNavBatch.pack_layout -- written on the device by sf_nav_follower_batches, and
+`Seq2SeqAgent.train_on_routes(routes, ...)` replays its training iterations over them with one device copy each.
+`.follower_minibatch_host` is the same minibatch formed on the host, `.epoch_order` the default order of the draws."""
+import copy
 import ctypes as C
 import json
 
@@ -53,7 +60,10 @@ class RouteSet:
         ix = self.scan_ix
         self.hop_base, self.hop_rows = base[ix].astype(np.int32), m[ix].astype(np.int32)
         self.hop_off = off[ix] + (self.goal - base[ix]) * m[ix]
-        self._dev = None
+        self._dev = None                                 # the device arrays, tokens among them (_device_arrays)
+        self._tok = None                                 # the flat host token table (_host_tokens)
+        self._route_dev = None                           # with_instructions: the route arrays of the set it copied
+        # (`enc` is read once into `_tok` / `_dev`: another set of instructions is another set, `with_instructions`)
 
     def __len__(self):
         return len(self.row0)
@@ -200,16 +210,27 @@ class RouteSet:
         return out
 
     # ---- on the device
+    def _host_tokens(self):
+        """(flat int64 token ids of every route end to end, one spare element behind; instr_off [N+1] int64)."""
+        if self._tok is None:
+            enc = self.enc if self.enc is not None else [()] * len(self)
+            off = np.concatenate(([0], np.cumsum([len(e) for e in enc]))).astype(np.int64)
+            flat = np.concatenate([np.asarray(e, np.int64).reshape(-1) for e in enc] + [np.zeros(1, np.int64)])
+            self._tok = (flat, off)
+        return self._tok
+
     def _device_arrays(self):
         if self._dev is None:
             dev = self.nav.device
             up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)             # noqa: E731
-            d = dict(row0=up(self.row0, np.int32), view0=up(self.view0, np.int32), goal=up(self.goal, np.int32),
-                     hop_off=up(self.hop_off, np.int64), hop_base=up(self.hop_base, np.int32),
-                     hop_rows=up(self.hop_rows, np.int32), hop_all=self.nav.all_hops_device(), tokens=None, instr_off=None)
+            shared = self._route_dev
+            d = dict(shared) if shared is not None else dict(
+                row0=up(self.row0, np.int32), view0=up(self.view0, np.int32), goal=up(self.goal, np.int32),
+                hop_off=up(self.hop_off, np.int64), hop_base=up(self.hop_base, np.int32),
+                hop_rows=up(self.hop_rows, np.int32), hop_all=self.nav.all_hops_device())
+            d['tokens'] = d['instr_off'] = None
             if self.enc is not None:
-                off = np.concatenate(([0], np.cumsum([len(e) for e in self.enc]))).astype(np.int64)
-                flat = np.concatenate([np.asarray(e, np.int64) for e in self.enc] + [np.zeros(1, np.int64)])
+                flat, off = self._host_tokens()
                 d['tokens'], d['instr_off'] = up(flat, np.int64), up(off, np.int64)
             self._dev = d
         return self._dev
@@ -270,3 +291,152 @@ class RouteSet:
             blocks += [(buf, int(off[i]), int(Tp[lo + i])) for i in range(hi - lo)]
             keep.append(off_dev)
         return PackedBlocks(blocks, B, Lmax, err=err, keep=keep, n_actions=n, route=route)
+
+    # ---- the follower's side: pre-training on the set (train.py --use_pretraining), minibatches packed on the device
+    def with_instructions(self, enc):
+        """A copy of the set whose instructions are `enc`: per route its token ids.  The routes, and their device
+        arrays where they exist, are shared; the device token arrays are rebuilt when next needed."""
+        enc = [np.asarray(e, np.int64).reshape(-1) for e in enc]
+        if len(enc) != len(self):
+            raise ValueError('%d instructions for %d routes' % (len(enc), len(self)))
+        out = copy.copy(self)
+        out.enc, out._tok, out._dev = enc, None, None
+        if self._dev is not None or self._route_dev is not None:
+            src = self._dev if self._dev is not None else self._route_dev
+            out._route_dev = {k: v for k, v in src.items() if k not in ('tokens', 'instr_off')}
+        return out
+
+    def with_generated(self, results, tokenizer=None):
+        """`with_instructions` of what `Seq2SeqSpeaker.augment(self)` returned: per route (by `instr_ids`) the result's
+        'word_indices' up to, not including, the first EOS -- the cut of decode_sentence(break_on_eos=True).  The
+        vocabulary ids are used as they are.  The reference writes the words joined into a string and re-tokenises
+        that string when the split is loaded; the two differ only for an id whose text does not encode back to the id
+        itself (<UNK>, <BOS>, <PAD>).  With a `tokenizer` (decode_sentence / encode_sentence) returns (set, number of
+        routes holding such an id), else the set."""
+        enc = []
+        for key in self.instr_ids:
+            w = np.asarray(results[key]['word_indices'], np.int64).reshape(-1)
+            stop = np.flatnonzero(w == EOS)
+            enc.append(w[:stop[0]] if len(stop) else w)
+        out = self.with_instructions(enc)
+        if tokenizer is None:
+            return out
+        ids = np.unique(np.concatenate(enc)) if enc else np.zeros(0, np.int64)
+        back = lambda v: [int(x) for x in tokenizer.encode_sentence(                             # noqa: E731
+            tokenizer.decode_sentence([int(v)], break_on_eos=True, join=True))[0]]
+        odd = np.array([v for v in ids if back(v) != [int(v)]], np.int64)
+        return out, sum(1 for e in enc if np.isin(e, odd).any())
+
+    def follower_minibatch_host(self, idx, Lmax, reverse=True):
+        """The follower minibatch that draws the routes `idx` (in that order), formed on the host from the set's arrays
+        and NavTable.all_hops: what env._next_minibatch(sort=True) + DeviceNavBatch.host_arrays_for(..., fixed=True)
+        form from item dictionaries -- columns by token count descending, equal counts in draw order; seq [B, Lmax]
+        int64 (tokens, last first when `reverse`, then EOS, cut to Lmax, PAD behind), mask uint8 (seq == PAD), lengths,
+        rows, views, hop [B, largest scan] (zeros behind a smaller scan's rows), base -- plus 'route': idx as sorted.
+        The contract sf_nav_follower_batches is held to, and the minibatch a capturing iteration is built from."""
+        idx = np.asarray(idx, np.int64).reshape(-1)
+        flat, off = self._host_tokens()
+        raw = off[idx + 1] - off[idx]
+        route = idx[np.argsort(-raw, kind='stable')]
+        first, n = off[route], off[route + 1] - off[route]
+        assert not ((n > 0) & (flat[first + n - 1] == EOS)).any(), 'an instruction that ends in EOS'
+        k = np.arange(Lmax, dtype=np.int64)[None, :]
+        src = first[:, None] + np.where(k < n[:, None], (n[:, None] - 1 - k) if reverse else k, 0)
+        seq = np.where(k < n[:, None], flat[np.minimum(src, len(flat) - 1)], np.where(k == n[:, None], EOS, PAD)).astype(np.int64)
+        hop_all, ld = self.nav.all_hops(), max(self.nav.scan_rows.values())
+        m = self.hop_rows[route].astype(np.int64)
+        c = np.arange(ld, dtype=np.int64)[None, :]
+        live = c < m[:, None]
+        hop = np.where(live, hop_all[self.hop_off[route][:, None] + np.where(live, c, 0)], 0).astype(np.int32)
+        return dict(seq=np.ascontiguousarray(seq), mask=np.ascontiguousarray((seq == PAD).astype(np.uint8)),
+                    lengths=np.minimum(n + 1, Lmax).astype(np.int32), rows=self.row0[route].copy(),
+                    views=self.view0[route].copy(), hop=np.ascontiguousarray(hop), base=self.hop_base[route].copy(),
+                    route=route)
+
+    def epoch_order(self, B, n_minibatches, seed=0):
+        """int32 [n_minibatches * B]: epoch e is default_rng([seed, e]).permutation(N); the epochs laid end to end and
+        cut to length (a minibatch may straddle two epochs, as the environment's does)."""
+        N, total = len(self), int(n_minibatches) * int(B)
+        if N < 1:
+            raise ValueError('no routes to order')
+        epochs = [np.random.default_rng([seed, e]).permutation(N) for e in range(-(-total // N))]
+        return np.concatenate(epochs + [np.zeros(0, np.int64)])[:total].astype(np.int32)
+
+    def pack_follower(self, B, Lmax, order=None, reverse=True, chunk=None):
+        """The set as follower minibatches of B routes on the device (nav.FollowerBlocks; the layout is
+        DeviceNavBatch.pack_layout(B, Lmax, ld) with ld the largest scan of `nav`): one sf_nav_follower_batches launch per
+        `chunk` minibatches, each into its own uint8 buffer, then ONE host sync that brings down err, col_route and
+        col_len.  order: the route index of every slot, minibatch i draws slots i*B .. i*B + B - 1 (None: arange(M * B)
+        % N, a short tail filled from the front as `pack` fills it)."""
+        from .nav import DeviceNavBatch, FollowerBlocks
+        N, dev = len(self), self.nav.device
+        if N < 1:
+            raise ValueError('no routes to pack')
+        if order is None:
+            order = np.arange(-(-N // B) * B) % N
+        order = np.ascontiguousarray(order, np.int32).reshape(-1)
+        if len(order) < B or len(order) % B:
+            raise ValueError('an order of %d slots is not a whole number of minibatches of %d' % (len(order), B))
+        M, ld = len(order) // B, max(self.nav.scan_rows.values())
+        nbytes = DeviceNavBatch.pack_layout(B, Lmax, ld)['bytes']
+        chunk = int(chunk or PACK_CHUNK)
+        d = self._device_arrays()
+        p = lambda t: None if t is None else t.data_ptr()                                        # noqa: E731
+        order_dev = torch.from_numpy(order).to(dev)
+        down = torch.zeros(1 + 2 * M * B, dtype=torch.int32, device=dev)     # err, col_route [M, B], col_len [M, B]
+        blocks, keep = [], [d, order_dev]
+        for lo in range(0, M, chunk):
+            hi = min(M, lo + chunk)
+            off = np.arange(hi - lo, dtype=np.int64) * nbytes
+            buf = torch.empty((hi - lo) * nbytes, dtype=torch.uint8, device=dev)
+            off_dev = torch.from_numpy(off).to(dev)
+            io = _lib.NavFollowerIO(N=N, V=V, B=B, Lmax=Lmax, ld=ld, M=hi - lo, pad=PAD, eos=EOS, reverse=int(bool(reverse)),
+                                    row0=p(d['row0']), view0=p(d['view0']), hop_all=p(d['hop_all']), hop_off=p(d['hop_off']),
+                                    hop_base=p(d['hop_base']), hop_rows=p(d['hop_rows']), instr_tokens=p(d['tokens']),
+                                    instr_off=p(d['instr_off']), order=p(order_dev[lo * B:]), mb_off=off.ctypes.data,
+                                    mb_off_dev=p(off_dev), out=p(buf), out_bytes=buf.numel(),
+                                    col_route=p(down[1 + lo * B:]), col_len=p(down[1 + (M + lo) * B:]))
+            _lib.call('sf_nav_follower_batches', C.byref(io), C.c_void_p(down.data_ptr()), stream())
+            blocks += [(buf, int(o)) for o in off]
+            keep.append(off_dev)
+        host = down.cpu().numpy()                                            # the one host sync
+        if int(host[0]):
+            raise RuntimeError('sf_nav_follower_batches refused a slot: a route index, a start view, a scan wider than '
+                               'the hop columns, or an instruction that ends in EOS')
+        return FollowerBlocks(blocks, B, Lmax, ld, col_route=host[1:1 + M * B].reshape(M, B),
+                              col_len=host[1 + M * B:].reshape(M, B), keep=keep)
+
+    def follower_windows(self, B, Lmax, order, reverse=True, window=None):
+        """`pack_follower` of a long `order` a window at a time (FollowerWindows): what a training loop of many
+        iterations draws its minibatches from without holding all of them on the device."""
+        return FollowerWindows(self, B, Lmax, order, reverse, int(window or PACK_CHUNK))
+
+
+class FollowerWindows:
+    """The minibatches of `order` (route index of every slot, a whole number of minibatches of B), packed `window` of
+    them per `RouteSet.pack_follower` call when the first of a window is asked for -- one launch and one host sync per
+    window.  `at(i)` -> (nav.FollowerBlocks, index in it) for `DeviceNavBatch.load_packed`.  The window before the
+    current one is kept (a training loop reloads the iteration still in flight when it faulted), older ones are dropped:
+    at most 2 * window blocks are alive."""
+
+    def __init__(self, routes, B, Lmax, order, reverse=True, window=PACK_CHUNK):
+        order = np.ascontiguousarray(order, np.int32).reshape(-1)
+        if len(order) < B or len(order) % B:
+            raise ValueError('an order of %d slots is not a whole number of minibatches of %d' % (len(order), B))
+        self.routes, self.B, self.Lmax, self.order, self.reverse, self.window = routes, B, Lmax, order, reverse, window
+        self.packed = 0                                      # pack_follower calls so far
+        self._alive = {}
+
+    def __len__(self):
+        return len(self.order) // self.B
+
+    def at(self, i):
+        w, B = i // self.window, self.B
+        if w not in self._alive:
+            for old in [k for k in self._alive if k != w - 1]:
+                del self._alive[old]
+            lo = w * self.window * B
+            self._alive[w] = self.routes.pack_follower(B, self.Lmax, order=self.order[lo:lo + self.window * B],
+                                                       reverse=self.reverse)
+            self.packed += 1
+        return self._alive[w], i - w * self.window
