@@ -1173,6 +1173,38 @@ int sf_gate_rows_attended_supported(int H, int LOC);
 int sf_lstm_cell_rows_fwd(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx, int x_col0, const float* xg,
                           const float* xg2, const float* h0, const float* c0, float* h1, float* c1, float* gates, int path,
                           void* ws, size_t ws_bytes, sf_stream stream);
+/* The RECURRENT half of the gates as a row (additive to ABI 10; rides on both tables above).
+ *
+ * h0 of step t + 1 is h1 of step t, final when step t's cell ends -- two launches before step t + 1's cell starts -- and
+ * h0 W_hh^T is 512 of the 640 K columns that cell streams.  So launch (2) of step t also carries the product blocks of
+ *     xg_h [B, 4H] = h1 W_hh^T + b_ih + b_hh                     (the small product's body, behind the scoring blocks)
+ * and the cell of step t + 1 is a product over f_loc alone (K = LOC) that adds three rows: xg_h, the action half's row and
+ * the attended half's.  Step 0 keeps its full product; the last step's launch (2) carries no product blocks.
+ *
+ *   sf_gate_rows_recurrent_use(on) / _is_used()   process-wide switch (default on); means something only where the
+ *                                 attended half's rows are taken.
+ *   sf_gate_rows_recurrent_steps()        decode steps whose cell added the recurrent row since the library was loaded
+ *                                 (each of them also counts in sf_gate_rows_attended_steps).
+ *   sf_gate_rows_recurrent_supported(B, H, LOC)   1 when the attended rows are supported, the cell's rule holds (LOC <= 256,
+ *                                 LOC % 4 == 0, H % 8 == 0) and launch (2) takes the plan of [B, H] x [4H, H]^T.
+ * Taken only where the attended half's rows are taken and the workspace holds two more [B, 4H] rows: the six rows (each
+ * rounded up to 64 floats) must fit an eighth of what the workspace has LEFT once the first four are carved, i.e. 52 rows
+ * within the capacity the episode starts with -- B <= 157 or so at H = 512 with a 64 MB workspace; a step
+ * whose predecessor did not leave the row takes the K = LOC + H step.  Off, or declined, every step launches what it
+ * launched without it: the same kernels and the same bits.
+ *
+ * sf_lstm_cell_rows3_fwd is that cell alone on caller buffers (tests, tools/recurrent_row_ab.py): xg, xg2 and xg_h are
+ * required and 16-byte aligned, xg_h holds the recurrent product AND both biases (w's are not added), the product runs over
+ * x[:, x_col0:I]; SF_ERR_UNSUPPORTED where I - x_col0 > 256 or H % 8 != 0.  sf_debug_recurrent_row forms xg_h from h1 on the
+ * kernel launch (2) forms it in, with no scoring or merge blocks beside it. */
+void sf_gate_rows_recurrent_use(int on);
+int sf_gate_rows_recurrent_is_used(void);
+long long sf_gate_rows_recurrent_steps(void);
+int sf_gate_rows_recurrent_supported(int B, int H, int LOC);
+int sf_lstm_cell_rows3_fwd(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx, int x_col0, const float* xg,
+                           const float* xg2, const float* xg_h, const float* h0, const float* c0, float* h1, float* c1,
+                           float* gates, void* ws, size_t ws_bytes, sf_stream stream);
+int sf_debug_recurrent_row(const sf_lstm_w* w, int B, int H, const float* h1, int ldh1, float* xg_h, sf_stream stream);
 /* A/B switch of the projected chain: 0 (the default: measured faster, 1.429 against 1.474 ms per headline rollout)
  * puts the attention partials of step t + 1 into launch (1), beside the text stage, and leaves launch (2) their merge;
  * on != 0 puts them into launch (2) (partials, ticket and merge beside the scoring; launch (1) is the text stage and y
@@ -1181,10 +1213,11 @@ void sf_debug_projected_partials_late(int on);
 /* Text groups per sample of launch (1) when it carries the attention partials.  The rule (a pure function of B, L and the
  * device): TWO groups of 8 * RPW positions iff the partials ride in the launch, L <= 80 and the four-group grid
  * 3 B + 4 B + product_blocks exceeds `slots`, the workgroups of that launch the device holds at once (CUs x the runtime's
- * occupancy of the four-group kernel: 512 on an MI355X, so B >= 69 at H = 512); four groups otherwise.  Every launch adds
+ * occupancy of the four-group kernel: 512 on an MI355X, so B >= 55 at H = 512, where y takes 32 blocks per 16 rows of
+ * the batch -- not B >= 69, which counted 32 blocks in all); four groups otherwise.  Every launch adds
  * 4 tickets per sample whatever its count, so launches of both kinds share a workspace.
  * sf_projected_text_groups_plan is the rule alone, no device needed: returns the count (0: bad arguments) and, with
- * `grid`, the launch's block count; product_blocks = blocks of y = W_out[:, H:] h1 (32 at H = 512); slots 0 = unknown,
+ * `grid`, the launch's block count; product_blocks = blocks of y = W_out[:, H:] h1 (32 x ceil(B / 16) at H = 512: 224 at B = 100); slots 0 = unknown,
  * four groups.  sf_debug_projected_text_groups: 0 the rule (default), 2 or 4 that count wherever it is legal (2: with
  * partials and L <= 80 only) -- for A/B timing and the tests. */
 int sf_projected_text_groups_plan(int B, int L, int with_partials, int slots, int product_blocks, int* grid);

@@ -58,9 +58,11 @@ int g_slab_consumers = 1;     // sf_debug_slab_consumers: consumers add up K-spl
 // ---- a2 LSTMCell --------------------------------------------------------------------------------
 int lstm_fwd_i(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx, const float* h0,
                const float* c0, float* h1, float* c1, float* gates, float* h1_drop, int ld_h1_drop,
-               const Dropout& drop, Arena ar, hipStream_t st, const float* xg, int x_col0, const float* xg2, int path) {
+               const Dropout& drop, Arena ar, hipStream_t st, const float* xg, int x_col0, const float* xg2, int path,
+               const float* xg_h) {
     LstmPwFwd p{};
     if (!xg) xg2 = nullptr;
+    if (xg_h && !(xg && xg2 && path == 0)) return SF_ERR_UNSUPPORTED;     // (all three rows or none of the third)
     p.xg = xg; p.b_ih = w->b_ih; p.b_hh = w->b_hh;
     p.c0 = c0; p.h0 = h0; p.B = B; p.H = H; p.gates = gates; p.h1 = h1; p.c1 = c1;
     p.h1_drop = h1_drop; p.ld_h1_drop = ld_h1_drop; p.drop = drop; p.lengths = nullptr;
@@ -72,6 +74,13 @@ int lstm_fwd_i(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx,
         return lstm_step_fused(f, st);
     }
     if (!xg) x_col0 = 0;
+    // all three rows: the recurrent half and the biases are in xg_h, what is left is x[:, x_col0:] alone
+    if (xg_h) {
+        LstmRowsArgs r{};
+        r.x = x + x_col0; r.ldx = ldx; r.w = w->w_ih + x_col0; r.ldw = I; r.K = I - x_col0;
+        r.xg_h = xg_h; r.xg = xg; r.xg2 = xg2; r.B = B; r.H = H; r.pw = p;
+        return lstm_step_rows(r, st);
+    }
     // both halves of the input as gate-space rows: what is left, [x[:, x_col0:] | h0], is a short reduction again
     if (xg && (path == 2 || (path == 0 && xg2 && short_gate_fused(I - x_col0, H)))) {
         LstmStepArgs f{};
@@ -455,6 +464,27 @@ int sf_lstm_cell_rows_fwd(const sf_lstm_w* w, int B, int I, int H, const float* 
                  x_col0 % 4 == 0 && I % 4 == 0 && ldx % 4 == 0 && path >= 0 && path <= 2);
     return lstm_fwd_i(w, B, I, H, x, ldx, h0, c0, h1, c1, gates, nullptr, 0, Dropout{}, arena(ws, ws_bytes), S(stream), xg,
                       x_col0, xg2, path);
+}
+
+int sf_lstm_cell_rows3_fwd(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx, int x_col0, const float* xg,
+                           const float* xg2, const float* xg_h, const float* h0, const float* c0, float* h1, float* c1,
+                           float* gates, void* ws, size_t ws_bytes, sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(w && x && xg && xg2 && xg_h && h0 && c0 && h1 && c1 && B > 0 && H > 0 && H % 4 == 0 && x_col0 > 0 &&
+                 x_col0 < I && x_col0 % 4 == 0 && I % 4 == 0 && ldx % 4 == 0);
+    return lstm_fwd_i(w, B, I, H, x, ldx, h0, c0, h1, c1, gates, nullptr, 0, Dropout{}, arena(ws, ws_bytes), S(stream), xg,
+                      x_col0, xg2, 0, xg_h);
+}
+
+int sf_debug_recurrent_row(const sf_lstm_w* w, int B, int H, const float* h1, int ldh1, float* xg_h, sf_stream stream) {
+    SF_ENTER();
+    SF_CHECK_ARG(w && w->w_hh && w->b_ih && w->b_hh && h1 && xg_h && B > 0 && H > 0 && H % 4 == 0 && ldh1 % 4 == 0 && ldh1 >= H);
+    Seg sg{h1, ldh1, w->w_hh, H, H};
+    LinearOut o{};
+    o.y = xg_h; o.ldy = 4 * H; o.bias = w->b_ih; o.bias2 = w->b_hh; o.epi = EPI_NONE;
+    SmallPlan p;
+    if (!linear_small_plan(&sg, 1, B, 4 * H, o, &p)) return SF_ERR_UNSUPPORTED;
+    return proj_score_hh_alone(p, S(stream));
 }
 
 int sf_lstm_cell_bwd(const sf_lstm_w* w, const sf_lstm_g* g, int B, int I, int H, const float* x,

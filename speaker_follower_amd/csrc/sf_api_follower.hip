@@ -45,12 +45,17 @@ struct TextFold {
 // The attended half (sf_gate_rows_attended_build) rides on that: `xg_f_in` is the [B, 4H] row launch (2) of the step before
 // merged from gate-space partials (null: the raw attended feature is in xin, as without the table; never set without
 // `xg_in`), `rows.gf` / `rows.xg_f` the table and where this step's launch (2) leaves the next one, `wrote_f` whether it did.
+// The recurrent half (sf_gate_rows_recurrent_use) rides on both: `xg_h_in` is the [B, 4H] row h0 W_hh^T + b_ih + b_hh the
+// product blocks of launch (2) of the step before formed (null: the cell forms it; never set without `xg_f_in`),
+// `rows.xg_h` where this step's launch (2) leaves the next one, `wrote_h` whether it did.
 struct GateStep {
     const float* xg_in;
     GateRows rows;
     bool wrote;
     const float* xg_f_in = nullptr;
     bool wrote_f = false;
+    const float* xg_h_in = nullptr;
+    bool wrote_h = false;
 };
 
 // ---- tail(t): what every launch chain of the step reads (decoder_tail_i builds it behind the cell, tail_dispatch picks
@@ -186,16 +191,28 @@ int tail_proj(const TailStep& s, const TextFold& tf) {
     const bool att = gate && !late && s.gate->rows.gf && s.gate->rows.xg_f && !s.dn_in.on() &&
                      proj_partials_supported(4 * H, s.xn.LOC);
     GateRows rows = gate ? s.gate->rows : GateRows{};
-    if (!att) rows.gf = nullptr, rows.xg_f = nullptr;
+    if (!att) rows.gf = nullptr, rows.xg_f = nullptr, rows.xg_h = nullptr;
+    // the recurrent half of the next step's gates as product blocks of launch (2): only beside both rows, where
+    // episode_gate_rows carved the row (switch, shape of the cell behind, capacity) and the plan is one launch (2) takes --
+    // planned HERE, ahead of launch (1): without a plan the step runs without the row, it is never left half issued
+    SmallPlan phh;
+    if (rows.xg_h) {
+        Seg sg{tp->h1, H, s.w->lstm.w_hh, H, H};
+        LinearOut o{};
+        o.y = rows.xg_h; o.ldy = 4 * H; o.bias = s.w->lstm.b_ih; o.bias2 = s.w->lstm.b_hh; o.epi = EPI_NONE;
+        if (!linear_small_plan(&sg, 1, B, 4 * H, o, &phh) || !pair_proj_score_hh_accepts(phh.inst())) rows.xg_h = nullptr;
+    }
+    const bool rec = rows.xg_h != nullptr;
     TRY(pair_proj_textfold(tf.ctx_q, tf.ctx_o, s.ctx_mask, B, s.L, H, tp->cat2 + H, 2 * H, f.tpart, f.tcount, f.zbuf, f.ldp,
                            tp->alpha, py, s.us, s.paired && !late ? &s.xn : nullptr, pt, tp->h1, H, f.part, s.st, rows.gf));
     g_proj_steps.fetch_add(1, std::memory_order_relaxed);
     TRY(issued(pair_proj_score(s.us, B, H, s.L, pt, f.zbuf, f.ldp, f.ybuf, f.ldp, make_glue(s.us, B, tp->logit, s.glue),
                                s.paired ? &s.xn : nullptr, late ? 0 : 2, tp->h1, H, s.paired ? tn->alpha_v : nullptr,
                                s.paired ? tn->xin + F : nullptr, 2 * F, s.dn_in, F, f.part, af.tickets(), s.st,
-                               gate ? &rows : nullptr)));
+                               gate ? &rows : nullptr, rec ? &phh : nullptr)));
     if (gate) s.gate->wrote = true;
     if (att) s.gate->wrote_f = true;
+    if (rec) s.gate->wrote_h = true;
     return SF_OK;
 }
 
@@ -381,10 +398,13 @@ int decoder_tail_i(const sf_decoder_w* w, const sf_cands* U, int B, int H, int D
     const float* xg = gate && !u_prev ? gate->xg_in : nullptr;
     // (with a row of the attended half's image part too: the product over [f_loc | h0], K = LOC + H, both rows added)
     const float* xg_f = xg ? gate->xg_f_in : nullptr;
+    // (with the recurrent half and the biases as a third row: the product over f_loc alone, K = LOC, three rows added)
+    const float* xg_h = xg_f ? gate->xg_h_in : nullptr;
     TRY(lstm_fwd_i(&w->lstm, B, 2 * s.F, H, tp->xin, 2 * s.F, h0, c0, tp->h1, tp->c1, tp->gates,
-                   tp->cat2 + H, 2 * H, s.d_h, s.ar, s.st, xg, xg_f ? s.F + s.us.IMG : s.F, xg_f));
+                   tp->cat2 + H, 2 * H, s.d_h, s.ar, s.st, xg, xg_f ? s.F + s.us.IMG : s.F, xg_f, 0, xg_h));
     if (xg) g_gate_steps.fetch_add(1, std::memory_order_relaxed);
     if (xg_f) g_gate_att_steps.fetch_add(1, std::memory_order_relaxed);
+    if (xg_h) g_gate_rec_steps.fetch_add(1, std::memory_order_relaxed);
     return tail_dispatch(s, tf);
 }
 
@@ -656,6 +676,7 @@ struct GateCarve {
     sf_gate_rows gr{};
     float* xgf_buf[2] = {nullptr, nullptr};     // null: the attended feature stays a raw row
     const float* gf = nullptr;
+    float* xgh_buf[2] = {nullptr, nullptr};     // null: every cell forms h0 W_hh^T itself
 };
 GateCarve episode_gate_rows(const EpisodeFwd& ep, Arena& ar) {
     const sf_follower_episode* e = ep.e;
@@ -691,6 +712,17 @@ GateCarve episode_gate_rows(const EpisodeFwd& ep, Arena& ar) {
             c.xgf_buf[1] = c.xgf_buf[0] + row;
             ar.base = c.xgf_buf[1] + row;
             ar.cap -= 2 * row;
+            // the recurrent half's rows (sf_gate_rows_recurrent_use) behind them, under the rule as the checks above apply
+            // it: `whole` IS `ar`, so the six rows must fit an eighth of what is LEFT once the four rows above are carved
+            // (52 rows <= the capacity this function was handed; the four-row check is 34 rows, the two-row check 16).  A
+            // workspace too small for six keeps the four, and the episode runs what it ran without this row: with the
+            // default 64 MB workspace at H = 512 that is B > 157 or a little below (tests/test_gpu_recurrent_row.py: B = 160)
+            if (gate_rows_recurrent_on() && recurrent_row_cell(x0.LOC, e->H) && 6 * row <= whole.cap / 8) {
+                c.xgh_buf[0] = ar.base;
+                c.xgh_buf[1] = c.xgh_buf[0] + row;
+                ar.base = c.xgh_buf[1] + row;
+                ar.cap -= 2 * row;
+            }
         }
     }
     return c;
@@ -711,20 +743,22 @@ int episode_steps(const EpisodeFwd& ep, const GateCarve& c, Arena ar) {
     float* const* xg_buf = c.xg_buf;
     const hipStream_t st = S(ep.stream);
     StepView cur = ep.cur;
-    const float *xg_in = nullptr, *xg_f_in = nullptr;
+    const float *xg_in = nullptr, *xg_f_in = nullptr, *xg_h_in = nullptr;
     for (int t = 0; t < e->S; ++t) {
         const bool more = t + 1 < e->S;
         StepView nxt = more ? step_view(e, t + 1) : cur;
         const sf_nav_io nv = nav0 ? nav_view(nav0, e, t) : sf_nav_io{};
         if (nav0) cur.glue.nav = &nv;
         const StepState in = state_in(e, t);
-        GateStep gs{xg_in, GateRows{gr.gu, gr.gl, more ? xg_buf[t & 1] : nullptr, c.gf, more ? c.xgf_buf[t & 1] : nullptr},
-                    false, xg_f_in};
+        GateStep gs{xg_in, GateRows{gr.gu, gr.gl, more ? xg_buf[t & 1] : nullptr, c.gf, more ? c.xgf_buf[t & 1] : nullptr,
+                                    more ? c.xgh_buf[t & 1] : nullptr},
+                    false, xg_f_in, false, xg_h_in};
         TRY(decoder_tail_i(w, &cur.U, e->B, e->H, e->D, e->L, nullptr, in.h, in.c, e->ctx, e->ctx_mask,
                            nullptr, &cur.tp, &cur.glue, drop, e->step0 + t, more && !nav0 ? &nxt.X : nullptr,
                            more ? &nxt.tp : nullptr, ar, st, tf, xg_buf[0] ? &gs : nullptr));
         xg_in = gs.wrote ? gs.rows.xg_next : nullptr;
         xg_f_in = gs.wrote && gs.wrote_f ? gs.rows.xg_f : nullptr;
+        xg_h_in = xg_f_in && gs.wrote_h ? gs.rows.xg_h : nullptr;
         if (nav0 && more) TRY(attend_i(&nxt.X, e->B, &nxt.tp, drop, e->step0 + t + 1, ar, st));
         cur = nxt;
     }

@@ -8,6 +8,7 @@ namespace sf {
 std::atomic<long long> g_proj_steps{0};
 std::atomic<long long> g_gate_steps{0};
 std::atomic<long long> g_gate_att_steps{0};
+std::atomic<long long> g_gate_rec_steps{0};
 
 namespace {
 
@@ -30,6 +31,7 @@ Registry<const void*, sf_gate_rows> g_gate;
 std::atomic<int> g_gate_use{1};             // sf_gate_rows_use
 Registry<const void*, sf_gate_rows_attended> g_gate_att;    // sf_gate_rows_attended_register
 std::atomic<int> g_gate_att_use{1};         // sf_gate_rows_attended_use
+std::atomic<int> g_gate_rec_use{1};         // sf_gate_rows_recurrent_use
 // ---- bf16 weight storage of the gate product (include/sf_hip.h: sf_gate_product_bf16_weights) ---------------------------
 Registry<WeightPair, PackedPair> g_bf16_pairs;
 std::atomic<int> g_bf16w_on{0};
@@ -50,6 +52,7 @@ bool gate_rows_lookup(const void* table, sf_gate_rows* out) {
 bool gate_rows_attended_lookup(const void* table, sf_gate_rows_attended* out) {
     return table && g_gate_att_use.load(std::memory_order_relaxed) && g_gate_att.find(table, out);
 }
+bool gate_rows_recurrent_on() { return g_gate_rec_use.load(std::memory_order_relaxed) != 0; }
 bool bf16_packed(const float* w_ih, const float* w_hh, const void* (&packed)[2]) {
     if (!g_bf16w_on.load(std::memory_order_relaxed) || sf::g_nt_force_f32) return false;
     PackedPair p;
@@ -222,6 +225,14 @@ long long sf_gate_rows_attended_steps(void) { return g_gate_att_steps.load(std::
 int sf_gate_rows_attended_supported(int H, int LOC) {
     return H > 0 && LOC > 0 && H % 4 == 0 && LOC % 4 == 0 && proj_partials_supported(4 * H, LOC) &&
            short_gate_fused(LOC, H) ? 1 : 0;
+}
+void sf_gate_rows_recurrent_use(int on) { g_gate_rec_use.store(on ? 1 : 0, std::memory_order_relaxed); }
+int sf_gate_rows_recurrent_is_used(void) { return g_gate_rec_use.load(std::memory_order_relaxed); }
+long long sf_gate_rows_recurrent_steps(void) { return g_gate_rec_steps.load(std::memory_order_relaxed); }
+int sf_gate_rows_recurrent_supported(int B, int H, int LOC) {
+    int mt = 0, cpw = 0;
+    return B > 0 && sf_gate_rows_attended_supported(H, LOC) && recurrent_row_cell(LOC, H) &&
+           plan_detail::small_shape(B, 4 * H, (H + 15) / 16, &mt, &cpw) && pair_proj_score_hh_accepts(SmallInst{mt, cpw}) ? 1 : 0;
 }
 
 }  // extern "C"

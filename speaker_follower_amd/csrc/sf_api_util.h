@@ -106,6 +106,8 @@ inline int projected_ld(int H) { return (H + 1 + 3) & ~3; }
 extern std::atomic<long long> g_proj_steps;     // sf_projected_steps: decode steps issued on the projected chain
 extern std::atomic<long long> g_gate_steps;     // sf_gate_rows_steps: decode steps whose gate product ran on a gate-space row
 extern std::atomic<long long> g_gate_att_steps; // sf_gate_rows_attended_steps: ... whose cell added an attended row too
+extern std::atomic<long long> g_gate_rec_steps; // sf_gate_rows_recurrent_steps: ... whose cell added the recurrent row too
+bool gate_rows_recurrent_on();                  // sf_gate_rows_recurrent_use (sf_api_tables.hip)
 extern int g_proj_partials_late;                // sf_debug_projected_partials_late (sf_api.hip)
 
 // the ONLY places that turn the C structs into the kernels' sources: a dense source is never half
@@ -191,11 +193,16 @@ int lstm_fwd_i(const sf_lstm_w* w, int B, int I, int H, const float* x, int ldx,
                                                                // (the product then starts at column x_col0 of x and W_ih)
                const float* xg2 = nullptr,     // with xg: a second [B, 4H] row formed elsewhere, of further columns below x_col0
                                                // (the fused step only: SF_ERR_UNSUPPORTED where the product + cell kernel run)
-               int path = 0);                  // with xg: 0 short_gate_fused decides; 1 the product + cell kernel; 2 the fused step
+               int path = 0,                   // with xg: 0 short_gate_fused decides; 1 the product + cell kernel; 2 the fused step
+               const float* xg_h = nullptr);   // with xg and xg2 (path 0): h0 W_hh^T + b_ih + b_hh formed elsewhere -- the step is
+                                               // lstm_step_rows over x[:, x_col0:] alone (recurrent_row_cell, sf_gemm_plan.h);
+                                               // SF_ERR_UNSUPPORTED, nothing launched, where that rule or a row is missing
 // Whether a step with a gate-space row runs what is left of its product, K = I - x_col0 + H, inside the fused step kernel
 // (lstm_step_fused: one launch, the rows added ahead of the cell) instead of as a K-split product plus the cell kernel.
 // A pure function of the shape; the rule of the step WITHOUT a row (lstm_fwd_i: I + H <= 1024) applied to what remains.
 inline bool short_gate_fused(int K_x, int H) { return K_x > 0 && K_x + H <= 1024 && H % 16 == 0 && K_x % 4 == 0; }
+// (the step with the recurrent half as a third row, K = I - x_col0 alone: recurrent_row_cell, sf_gemm_plan.h -- a header
+//  the host tests compile)
 int lstm_bwd_i(const sf_lstm_w* w, const sf_lstm_g* g, int B, int I, int H, const float* x, int ldx,
                const float* h0, const float* c0, const float* c1, const float* gates,
                const float* dh1, const float* dh1_b, const float* dc1, float* dx, int lddx,

@@ -1184,6 +1184,22 @@ __global__ __launch_bounds__(SMALL_WAVES * 64) void pair_proj_score_kernel(ProjS
     }
 }
 
+// Launch (2) with the NEXT step's recurrent gate product beside it: blocks [0, nh) run the small product
+// xg_h = h1 W_hh^T + b_ih + b_hh (small_gemm_body<MT, 4> over the plan of [B, H] x [4H, H]^T: nothing in this launch reads
+// it, and it reads nothing launches (1) or (2) write) behind the scoring + glue blocks [0, nb) and the merge blocks
+// [nb, nb + nm).  The product blocks come LAST: measured at B = 100, 11.4 us per launch and 1.155 ms per rollout against
+// 12.8 us and 1.180 ms with them first (profiles/recurrent_row_ab.txt) -- the scoring blocks' dependent load chain starts at
+// once and the products fill in behind.  A kernel of its own: pair_proj_score_kernel<2> stays what it was for every step
+// without the row.
+template <int MT>
+__global__ __launch_bounds__(SMALL_WAVES * 64) void pair_proj_score_hh_kernel(ProjScoreArgs a, FGlue g, int nb, VisArgs v, VisSplit sp,
+                                                                            int nm, SmallArgs hh, int gxh) {
+    const int bid = blockIdx.x;
+    if (bid < nb) return proj_score_glue_body(a, g, bid);
+    if (bid < nb + nm) return proj_merge_body<PPB_G, PPB_RPG>(v, sp, bid - nb);
+    small_gemm_body<MT, 4>(hh, (bid - nb - nm) % gxh, (bid - nb - nm) / gxh);
+}
+
 // =================================================================================================
 // The text attention in FOLDED form (inference only: nothing here is taped for a backward).
 // model.py:129-141 per decode step: t = W_in h1, s_l = ctx_l . t, alpha = softmax(s), wc = sum alpha_l ctx_l,
@@ -1752,8 +1768,11 @@ int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* ma
 int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt, const float* z, int ldz, const float* y, int ldy,
                     const FGlue& g, const PanoSrc* xn, int vphase, const float* h1, int ldh1, float* alpha, float* out, int ldo,
                     const Dropout& drop, int drop_col0, float* split_part, unsigned* counter, hipStream_t st,
-                    const GateRows* gate) {
+                    const GateRows* gate, const SmallPlan* hh) {
     if (!proj_chain_supported(us, xn, B, H, L, pt) || !aligned4(ldz, ldy, ldh1)) return SF_ERR_UNSUPPORTED;
+    if (hh && (!xn || vphase != 2 || !gate || !gate->xg_f || !gate->xg_h || hh->args.y != gate->xg_h ||
+               !pair_proj_score_hh_accepts(hh->inst())))
+        return SF_ERR_UNSUPPORTED;
     if (xn && (!split_part || !aligned4(ldo) || (vphase != 0 && vphase != 2) || (vphase == 0 && !counter))) return SF_ERR_UNSUPPORTED;
     if (gate && (!gate->gu || !gate->gl || !gate->xg_next)) return SF_ERR_UNSUPPORTED;
     ProjScoreArgs a{us, pt.pa, pt.la, pt.ld, H, z, y, ldz, ldy};
@@ -1771,11 +1790,28 @@ int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt
     }
     const VisSplit sp{split_part, counter, g_trace};
     const dim3 block(SMALL_WAVES * 64);
+    if (hh) {
+        const int nh = hh->gx * hh->gy;
+        return launched(with_index(hh->mt, [&](auto m) {
+            constexpr int MT = decltype(m)::value;
+            SF_LAUNCH_INST(pair_proj_score_hh_kernel, (MT), dim3(2 * B + nh), block, 0, st, a, g, B, va, sp, B, hh->args, hh->gx);
+        }, ints<1, 2, 4>{}));
+    }
     if (xn && vphase == 0)
         SF_LAUNCH((pair_proj_score_kernel<0>), dim3(VSP_G * B + B), block, 0, st, a, g, B, va, sp, VSP_G * B);
     else
         SF_LAUNCH((pair_proj_score_kernel<2>), dim3(xn ? 2 * B : B), block, 0, st, a, g, B, va, sp, 0);
     return launch_status();
+}
+
+int proj_score_hh_alone(const SmallPlan& hh, hipStream_t st) {
+    if (!pair_proj_score_hh_accepts(hh.inst())) return SF_ERR_UNSUPPORTED;
+    const int nh = hh.gx * hh.gy;
+    return launched(with_index(hh.mt, [&](auto m) {
+        constexpr int MT = decltype(m)::value;
+        SF_LAUNCH_INST(pair_proj_score_hh_kernel, (MT), dim3(nh), dim3(SMALL_WAVES * 64), 0, st, ProjScoreArgs{}, FGlue{}, 0,
+                       VisArgs{}, VisSplit{}, 0, hh.args, hh.gx);
+    }, ints<1, 2, 4>{}));
 }
 
 // The attention of launches (1) and (2) ALONE, on caller buffers (sf_debug_projected_attention: tests at panorama shapes

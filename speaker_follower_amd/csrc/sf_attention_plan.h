@@ -95,10 +95,11 @@ constexpr int FOLD_RPW[4] = {1, 2, 3, 5};
 inline int fold_rpw(int L, int G) { return FOLD_RPW[text_rung(L, G)]; }
 
 // ---- text groups per sample of launch (1) of the projected chain.  With the partials the kernel holds proj_partials_body's
-// ~125 registers, two workgroups per CU: at batch 100 the four-group grid (300 + 400 + 32 blocks) is 732 blocks on 512
-// resident slots, and the text groups of the second round pay their load -> reduce -> ticket -> merge latency behind a
-// first-round block, on the chain cell -> text -> score -> next gate product.  TWO groups of 8 * RPW positions (RPW <= 5:
-// L <= 80) make it 532.  The rule is a pure function of (B, L, device) -- a captured replay and an eager rollout of one
+// ~125 registers, two workgroups per CU: at batch 100 the four-group grid (300 + 400 + 224 blocks: the y product plans
+// (mt 1, cpw 4), a 32 x 7 grid, not the 32 blocks earlier notes counted) is 924 blocks on 512 resident slots, and the
+// text groups of the second round pay their load -> reduce -> ticket -> merge latency behind a first-round block, on the
+// chain cell -> text -> score -> next gate product.  TWO groups of 8 * RPW positions (RPW <= 5: L <= 80) make it 724: every
+// text group starts in the first round, 212 of the y blocks in a second.  The rule is a pure function of (B, L, device) -- a captured replay and an eager rollout of one
 // shape choose alike: two groups iff the partials ride in this launch, L <= 80, and the four-group grid exceeds the
 // resident slots.  force (sf_debug_projected_text_groups): 0 the rule, 2 / 4 that count where it is legal.  na: blocks of
 // the y product, slots: resident workgroups of the four-group launch (0: unknown).
@@ -117,6 +118,8 @@ inline bool pair_small_small_accepts(SmallInst a, SmallInst b) { return a.mt == 
 // (y and t_v' of the four-launch folded chain: t_v' has the shape of t_a, which pair_apro_small takes as (1, 4) only)
 inline bool pair_textfold_small_small_accepts(SmallInst a, SmallInst b) { return a.mt == 1 && a.cpw == 4 && b.mt == 1 && b.cpw == 4; }
 inline bool pair_proj_textfold_accepts(SmallInst y) { return y.mt == 1 && y.cpw == 4; }
+// launch (2)'s product blocks (the next step's h1 W_hh^T + biases, K = H <= 512: four chunks per wave)
+inline bool pair_proj_score_hh_accepts(SmallInst hh) { return hh.cpw == 4 && mt_124(hh.mt); }
 inline bool pair_apro_small_accepts(SmallInst a, SmallInst b) { return a.mt == 1 && a.cpw == 4 && b.cpw == 2 && mt_124(b.mt); }
 inline bool pair_small_text_accepts(SmallInst a) { return a.mt == 4 && a.cpw == 2; }
 inline bool pair_visbwd_small_accepts(SmallInst b) { return b.mt == 1 && b.cpw == 16; }     // the K = 4H recurrent data gradient

@@ -1186,6 +1186,108 @@ __global__ __launch_bounds__(LSTMW_WAVES * 64) void lstm_step_wide_kernel(LstmSt
     lstm_cell_update(p.pw, pb, pj, g4, c0v, lv);
 }
 
+// The decoder's step with its recurrent half as a row (LstmRowsArgs): what is left of the product is K <= 256 columns
+// of x (the attended feature's location part, K = 128), so the same 32-row x 8-unit patch takes 8 waves = 8 K-slices of
+// <= CPW chunks, and the block's bytes are the three [32 rows, 4 gates, 8 units] row patches: 32-byte runs along the gate
+// row, one float4 per thread of waves 4-7 per row, while waves 0-3 (the tail threads) fetch the state.
+// grid (H/8, ceil(B/32)).  Tile layout, partial-tile exchange and tail as in lstm_step_wide_kernel.
+constexpr int LSTMR_WAVES = 8;
+
+template <int CPW>
+__global__ __launch_bounds__(LSTMR_WAVES * 64) void lstm_step_rows_kernel(LstmRowsArgs p) {
+    __shared__ float s_red[LSTMR_WAVES][4][256];         // 32 KB: partial tiles (t, q) of the 8 waves
+    __shared__ float s_pre[4][256];                      // the three rows summed: [gate][row * 8 + unit]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int slice = blockIdx.x, m0 = blockIdx.y * 32;
+    const int li = lane & 15, kk = lane >> 4;
+    const int H = p.H;
+
+    // rows: thread 256 + e4 holds float4 e4 of the patch: row e4 / 8, gate (e4 / 2) % 4, units 4 (e4 % 2) .. + 3
+    const int e4 = threadIdx.x & 255;
+    const int r_row = e4 >> 3, r_gate = (e4 >> 1) & 3, r_half = e4 & 1;
+    float4 pre4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (threadIdx.x >= 256) {                                    // wave-uniform; rows outside the batch read a clamped address
+        const size_t off = (size_t)min(m0 + r_row, p.B - 1) * 4 * H + r_gate * H + slice * 8 + r_half * 4;
+        const float4 a = ld4(p.xg_h + off), b = ld4(p.xg + off), c = ld4(p.xg2 + off);
+        pre4 = make_float4((a.x + b.x) + c.x, (a.y + b.y) + c.y, (a.z + b.z) + c.z, (a.w + b.w) + c.w);
+    }
+
+    // this wave's K-slice of all four tiles: every fragment is loaded before the first MFMA
+    const int total = (p.K + 15) >> 4;
+    const int c_lo = (wave * total) / LSTMR_WAVES, c_hi = ((wave + 1) * total) / LSTMR_WAVES;
+    const int nrow[2] = {(li >> 3) * H + slice * 8 + (li & 7), (2 + (li >> 3)) * H + slice * 8 + (li & 7)};
+    const int mrow[2] = {min(m0 + li, p.B - 1), min(m0 + 16 + li, p.B - 1)};
+    float4 fa[CPW][2], fb[CPW][2];
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int i = 0; i < CPW; ++i) {
+        const int c = min(min(c_lo + i, max(c_hi - 1, c_lo)), total - 1);   // clamped: surplus slots re-load a valid chunk
+        const int k = c * 16 + 4 * kk;
+        const bool ok = k < p.K && c_lo + i < c_hi;              // partial last chunk / surplus slot / idle wave
+        const int kc = k < p.K ? k : 0;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const float4 bv = ld4(p.w + (size_t)nrow[q] * p.ldw + kc);
+            fb[i][q] = ok ? bv : z;
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const float4 av = ld4(p.x + (size_t)mrow[t] * p.ldx + kc);
+            fa[i][t] = ok ? av : z;
+        }
+    }
+    // state operands of the tail threads (waves 0-3)
+    const int prow = e4 >> 3, pcol = e4 & 7;
+    const int pb = m0 + prow, pj = slice * 8 + pcol;
+    const bool ptail = threadIdx.x < 256 && pb < p.B;
+    float c0v = 0.f;
+    LstmLive lv{true, 0.f};
+    if (threadIdx.x < 256) {                                     // wave-uniform
+        const int qb = min(pb, p.B - 1);
+        c0v = p.pw.c0[qb * H + pj];
+        lv = lstm_live_load(p.pw, qb, pj);
+    }
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < CPW; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int q = 0; q < 2; ++q)
+                    acc[t][q] = mfma16(comp(fa[i][t], c), comp(fb[i][q], c), acc[t][q]);
+
+    if (threadIdx.x >= 256) {
+        float* sp = &s_pre[r_gate][r_row * 8 + r_half * 4];
+        sp[0] = pre4.x; sp[1] = pre4.y; sp[2] = pre4.z; sp[3] = pre4.w;
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s_red[wave][t * 2 + q][(kk * 4 + r) * 16 + li] = acc[t][q][r];
+    __syncthreads();
+
+    if (!ptail) return;
+    float g4[4];
+    const int tt = prow >> 4, rr = prow & 15;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        float v = s_pre[g][e4];
+        const int e = rr * 16 + (g & 1) * 8 + pcol;
+#pragma unroll
+        for (int k = 0; k < LSTMR_WAVES; ++k) v += s_red[k][tt * 2 + (g >> 1)][e];
+        g4[g] = v;
+    }
+    lstm_cell_update(p.pw, pb, pj, g4, c0v, lv);
+}
+
 // Fused BACKWARD time step of the encoder LSTM: block = 16 rows x 16 hidden units, 8 waves = 8
 // K-slices of dh_{t+1}[tile] = dgates_{t+1}[16 rows, 4H] . W_hh^T[16 units, 4H] (all loads up front,
 // partial tiles meet in LDS), then the cell backward of step t for the tile's 256 elements in the
@@ -1942,6 +2044,18 @@ int lstm_step_fused(const LstmStepArgs& p, hipStream_t st) {
         SF_LAUNCH(lstm_step_fused_kernel<16>, grid, block, 0, st, p);
     else
         return SF_ERR_UNSUPPORTED;
+    return launch_status();
+}
+
+int lstm_step_rows(const LstmRowsArgs& p, hipStream_t st) {
+    if (!recurrent_row_cell(p.K, p.H) || p.ldx % 4 || p.ldw % 4 || p.B < 1 || !p.x || !p.w || !p.xg_h || !p.xg || !p.xg2 ||
+        (((uintptr_t)p.x | (uintptr_t)p.w | (uintptr_t)p.xg_h | (uintptr_t)p.xg | (uintptr_t)p.xg2) & 15))
+        return SF_ERR_UNSUPPORTED;
+    const dim3 grid(p.H / 8, ceil_div(p.B, 32)), block(LSTMR_WAVES * 64);
+    if (ceil_div(ceil_div(p.K, 16), LSTMR_WAVES) <= 1)
+        SF_LAUNCH(lstm_step_rows_kernel<1>, grid, block, 0, st, p);
+    else
+        SF_LAUNCH(lstm_step_rows_kernel<2>, grid, block, 0, st, p);
     return launch_status();
 }
 

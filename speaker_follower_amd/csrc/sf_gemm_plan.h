@@ -40,6 +40,11 @@ constexpr int nn_inst(int mt) {
     return i;
 }
 
+// The decoder's step with ALL THREE halves of its gates as rows (lstm_step_rows_kernel<1|2>: action half, attended image
+// half, recurrent half + biases): what is left of the product is K_x columns of x, 8 waves of <= 2 chunks of 16 over a
+// 32-row x 8-unit patch.  A pure function of the shape, like short_gate_fused (sf_api_util.h), whose step it replaces.
+inline bool recurrent_row_cell(int K_x, int H) { return K_x > 0 && K_x <= 256 && K_x % 4 == 0 && H > 0 && H % 8 == 0; }
+
 // Epilogue applied by the split-K reduce pass (or inline when there is a single split).
 enum Epi : int {
     EPI_NONE = 0,    // y = acc + bias

@@ -51,6 +51,7 @@ int gemm_nn_ws(const float* A, int lda, const float* W, int ldw, int M, int N, i
 // LSTM gates: reduce `ks` split-K slabs [ks][B][4H] + biases (+ hoisted xg), activate, update state.
 int lstm_pointwise_fwd(const LstmPwFwd& a, hipStream_t st);
 int lstm_step_fused(const LstmStepArgs& p, hipStream_t st);      // sf_gemm.hip
+int lstm_step_rows(const LstmRowsArgs& p, hipStream_t st);       // sf_gemm.hip: SF_ERR_UNSUPPORTED before any launch
 
 extern unsigned long long* g_trace;   // sf_debug_trace buffer (development aid), null = off
 extern int g_force_sc1;               // sf_debug_force_write_through
@@ -235,6 +236,8 @@ struct GateRows {
     // the ATTENDED half (sf_gate_rows_attended_build; both null: the raw attended feature, as without this table):
     const float* gf;         // [n_vp * V, 4H]: launch (1)'s partials load these rows where they loaded image rows
     float* xg_f;             // [B, 4H]: where launch (2)'s merge leaves the normalised 4H part for the next step's cell
+    // the RECURRENT half (null: the next step's cell forms h0 W_hh^T itself; never set without xg_f):
+    float* xg_h;             // [B, 4H]: where launch (2)'s product blocks leave h1 W_hh^T + b_ih + b_hh
 };
 bool proj_chain_supported(const CandSrc& us, const PanoSrc* xn, int B, int H, int L, const ProjTables& pt);
 int proj_attention_alone(const PanoSrc& x, int B, const ProjTables& pt, const float* h1, int ldh1, float* alpha, float* out,
@@ -252,8 +255,10 @@ int pair_proj_textfold(const float* ctx_q, const float* ctx_o, const uint8_t* ma
 int pair_proj_score(const CandSrc& us, int B, int H, int L, const ProjTables& pt, const float* z, int ldz, const float* y, int ldy,
                     const FGlue& g, const PanoSrc* xn, int vphase, const float* h1, int ldh1, float* alpha, float* out, int ldo,
                     const Dropout& drop, int drop_col0, float* split_part, unsigned* counter, hipStream_t st,
-                    const GateRows* gate = nullptr);
-
+                    const GateRows* gate = nullptr,
+                    const SmallPlan* hh = nullptr);     // product blocks beside the scoring (vphase 2; pair_proj_score_hh_accepts)
+// those product blocks alone, on the kernel launch (2) runs them in (sf_debug_recurrent_row)
+int proj_score_hh_alone(const SmallPlan& hh, hipStream_t st);
 struct FGlue;
 int follower_glue_fwd(const FGlue& g, hipStream_t st);
 // scoring + glue in one launch (sf_attention.hip); g.logit receives the masked logits

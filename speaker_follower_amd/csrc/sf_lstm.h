@@ -34,6 +34,17 @@ struct LstmStepArgs {            // fused recurrent step (sf_gemm.hip: lstm_step
     bool wide;                                      // the 32 x 8 patches at B <= 16 too (lstm_step_fused: measured for this caller)
 };
 
+// The decoder's step whose recurrent half arrives as a row too (sf_gemm.hip: lstm_step_rows_kernel):
+// gates = x W^T over K columns + xg_h + xg + xg2.  No recurrent segment and no bias operand: xg_h holds
+// h0 W_hh^T + b_ih + b_hh (launch (2) of the step before formed it, sf_attention.hip: pair_proj_score_hh_kernel).
+struct LstmRowsArgs {
+    const float* x; int ldx;                        // [B, >= K], row stride ldx
+    const float* w; int ldw; int K;                 // [4H, >= K]: the K columns of W_ih that are left, row stride ldw
+    const float* xg_h; const float* xg; const float* xg2;   // [B, 4H] each, 16-byte aligned, all required
+    int B, H;
+    LstmPwFwd pw;                                   // outputs / state (slabs, xg, biases unused; h0 for the live carry only)
+};
+
 // Encoder-only operands of the cell update (row liveness at step t, previous h), fetched by the
 // caller up front with its other tail operands so that no load sits behind the gate reduction.
 struct LstmLive {

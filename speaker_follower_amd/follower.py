@@ -282,6 +282,26 @@ class gate_rows_attended_pass:
         return False
 
 
+class gate_rows_recurrent_pass:
+    """`with gate_rows_recurrent_pass(on):` -- whether the steps that run on both gate-space rows also take the recurrent
+    half of their gates as a row launch (2) of the step before formed (sf_gate_rows_recurrent_use; process-wide like
+    gate_rows_attended_pass).  Restores the switch on exit."""
+
+    def __init__(self, on):
+        self.on = int(bool(on))
+
+    def __enter__(self):
+        self.prev = int(_lib.lib.sf_gate_rows_recurrent_is_used())
+        if self.prev != self.on:
+            _lib.lib.sf_gate_rows_recurrent_use(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        if self.prev != self.on:
+            _lib.lib.sf_gate_rows_recurrent_use(self.prev)
+        return False
+
+
 class FollowerEngine:
     def __init__(self, encoder, decoder, store, group=None):
         self.encoder, self.decoder, self.store = encoder, decoder, store
@@ -307,6 +327,10 @@ class FollowerEngine:
         # ... and the image part of the attended half too (sf_gate_rows_attended_build): the product shrinks to K = LOC + H.
         # Means something only while `gate_rows` is on; built, used and refreshed with those rows
         self.gate_rows_attended = True
+        # ... and the recurrent half of the next step's gates (h1 W_hh^T + biases) as product blocks of launch (2)
+        # (sf_gate_rows_recurrent_use): the cell behind is a product over K = LOC that adds three rows.  Means something only
+        # while `gate_rows_attended` is on; needs no table
+        self.gate_rows_recurrent = True
         self._capturing = False         # inside capture() / capture_sharded(): 'auto' builds the projected tables
 
     # The two-chain forward schedule (the visual half of step t + 1 on a side stream) is retired: DESIGN.md section 9.
@@ -510,6 +534,7 @@ class FollowerEngine:
         st.episode = None
         st.projected, st.projected_tables = False, None
         st.gate_rows, st.gate_rows_tables, st.gate_rows_attended = False, None, False
+        st.gate_rows_recurrent = False
         # the same one-call episode for a device-resident environment (the env step inside every scoring + glue launch,
         # the attention of step t + 1 behind it): no host work between the launches of a TRAINING rollout either, and
         # the backward takes the two-stream episode path
@@ -551,13 +576,14 @@ class FollowerEngine:
             attended = (st.gate_rows_tables is not None and self.gate_rows_attended
                         and st.gate_rows_tables['attended'] is not None)
             with projected_pass(st.projected_tables is not None), gate_rows_pass(st.gate_rows_tables is not None), \
-                    gate_rows_attended_pass(attended):
+                    gate_rows_attended_pass(attended), gate_rows_recurrent_pass(attended and self.gate_rows_recurrent):
                 before, gate_before = _lib.lib.sf_projected_steps(), _lib.lib.sf_gate_rows_steps()
-                att_before = _lib.lib.sf_gate_rows_attended_steps()
+                att_before, rec_before = _lib.lib.sf_gate_rows_attended_steps(), _lib.lib.sf_gate_rows_recurrent_steps()
                 call('sf_follower_episode_fwd', byref(dw), byref(ep), *ws)
                 st.projected = _lib.lib.sf_projected_steps() > before
                 st.gate_rows = _lib.lib.sf_gate_rows_steps() > gate_before
                 st.gate_rows_attended = _lib.lib.sf_gate_rows_attended_steps() > att_before
+                st.gate_rows_recurrent = _lib.lib.sf_gate_rows_recurrent_steps() > rec_before
             st.episode = (ep, dw)
         tapes = [] if st.episode else [_lib.DecoderTape(*(st.tape[k][t].data_ptr() for k in _TAPE_KEYS))
                                        for t in range(S)]
